@@ -21,7 +21,7 @@ CRISPR screen of configs[3] as the reference's example runs it besides the naive
 examples/GSE120861/code/cmd_highmoi.sh:19-22), coex_c2_f64 / coex_c5_f64 = configs[1] / the configs[4] per-rank slice on the fp64 matrix cores
 (NRM_GRAM=f64: the dtype the north star names literally), binnet_c5 = binnet on a 30 000 x 30 000 fp64 P-value matrix (the consumer of configs[4]'s output), normvar_c2 = norm.normvar on a
 configs[1]-sized matrix resident in HBM (the step in front of the hot path), chain_c2 = normvar -> coex -> binnet as one resident chain.
-`--workload X` makes X the headline instead; `--no-extras` skips them.
+`--workload X` makes X the headline instead; the extra workloads run only under `--full`, and `--no-extras` skips them there.
 
 Launch: `python bench.py --gpus N` starts its own N ranks (torch.distributed.run on 127.0.0.1) when it is
 not already running under one; under `python -m torch.distributed.run ... bench.py --gpus N` it uses the
@@ -31,6 +31,12 @@ reference's algorithm, test infrastructure) on a bounded sample on this box's ho
 workloads carry their own, extrapolated from sampled rows.  `kernels_roofline` prices the two kernels beside K2 against the rooflines that
 bound them (K1: HBM; K3: fp64 vector ALU).  `guard` is the verdict of the integer engine's accuracy
 guard over the timed steps (pairs it could not certify: must be 0 here).
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets the headline up, runs W untimed and K timed steps, and prints the contract
+line alone; its roofline and kernel split come from HIP events recorded inside the timed steps.  `--full` adds everything else: the CPU
+baseline, the numpy-in/numpy-out PCIe leg, the extra workloads, the N > 1 self-check and the extra steps that price the kernels one by one
+where the timed region carries no events, the cold calls, and the full record of every workload on the lines before the contract line.
+`--dump-outputs DIR` writes what the headline's last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -132,6 +138,42 @@ def side_rooflines(kernels_ms, rows, n, esz, ns, tests, out_esz):
 									frac=250 * tests / (k3 * 1e-3) / 1e12 / (F64_VALU_PEAK_TFLOPS / 2), algorithmic_bytes=b,
 									hbm_gbs=b / (k3 * 1e-3) / 1e9, kernel_ms=k3)
 	return out
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays, limit=DUMP_BYTES):
+	"""--dump-outputs: every output of a step (name -> torch tensor or numpy array; None = not computed) as <path>/<name>.npy, in float64
+	when the output is fp64 or a wide integer and in float32 otherwise (fp32, booleans, bytes).  An output larger than its share of `limit`
+	is sampled: rows along its first axis (elements of a 1-D output, or of an output whose single row is already too large) drawn with a
+	fixed seed, so the same rows on every run of the same shape, written in increasing order with their indices beside them as
+	<name>_rows.npy (float64).  A share is limit / (3 x the number of outputs): values and indices of every output fit in `limit`.
+	Returns {name: shape written}."""
+	import torch
+	os.makedirs(path, exist_ok=True)
+	arrays = {k: v for k, v in arrays.items() if v is not None}
+	share = limit // (3 * max(1, len(arrays)))
+	written = {}
+	for name, a in sorted(arrays.items()):
+		t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+		to = torch.float64 if t.dtype in (torch.float64, torch.int32, torch.int64) else torch.float32
+		esz = 8 if to == torch.float64 else 4
+		if t.dim() == 0:
+			t = t.reshape(1)
+		rows = None
+		if t.numel() * esz > share:
+			if t.dim() > 1 and (t.numel() // t.shape[0]) * esz > share:
+				t = t.reshape(-1)
+			k = max(1, share // ((t.numel() // t.shape[0]) * esz))
+			rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=k, replace=False))
+			t = t.index_select(0, torch.as_tensor(rows, device=t.device))
+		v = t.detach().to(to).cpu().numpy()
+		np.save(os.path.join(path, name + '.npy'), v)
+		if rows is not None:
+			np.save(os.path.join(path, name + '_rows.npy'), rows.astype(np.float64))
+		written[name] = list(v.shape)
+	return written
 
 
 C5_ROWS_PER_RANK = 3750  # configs[4]: 30 000 genes over 8 GPUs
@@ -466,8 +508,17 @@ def guard_verdict(flags, eng):
 				note='rigorous bound (csrc/nrm_fix.h); 0 uncertified pairs = every P-value of the timed steps came from the integer engine')
 
 
-def bench_coex(rk, nd, steps, warmup, rows_local, n, seed, dtype, label, loading=0.3):
-	"""Sharded coex: every rank owns `rows_local` gene rows (generated on its GPU), see normalisr_amd.distributed.CoexPlan."""
+def step_outputs(plan):
+	"""p and stat of every block pair of a CoexPlan step, named by the block pair when there are several (this rank's pairs at N > 1)."""
+	outs = plan.outputs
+	if len(outs) == 1:
+		return dict(p=outs[0]['p'], stat=outs[0]['stat'])
+	return {'{}_b{}_{}_r{}'.format(k, o['bi'], o['bj'], o['row_lo']): o[k] for o in outs for k in ('p', 'stat')}
+
+
+def bench_coex(rk, nd, steps, warmup, rows_local, n, seed, dtype, label, loading=0.3, full=True, grab=None):
+	"""Sharded coex: every rank owns `rows_local` gene rows (generated on its GPU), see normalisr_amd.distributed.CoexPlan.
+	full=False: the timed steps and what their own events give; grab(outputs) is called right after them."""
 	torch = rk.torch
 	world, rank = rk.world, rk.rank
 	ng = rows_local * world
@@ -479,7 +530,10 @@ def bench_coex(rk, nd, steps, warmup, rows_local, n, seed, dtype, label, loading
 	# them and the per-kernel breakdown comes from three extra steps after it (`kernels_ms_from`).
 	events_inside = world == 1 and not plan.multi
 	elapsed = timed_steps(rk, plan, steps, warmup, events_inside)
-	if not events_inside:
+	if grab is not None:
+		grab(step_outputs(plan))
+	priced = events_inside or full  # (without events in the timed region, the kernels are priced by extra steps: --full only)
+	if not events_inside and full:
 		for _ in range(3):
 			plan.step(timed=True)
 		rk.barrier()
@@ -495,16 +549,18 @@ def bench_coex(rk, nd, steps, warmup, rows_local, n, seed, dtype, label, loading
 							   'fixed-point digit planes in {} cell chunks, one all-gather each, block pairs accumulated as the chunks land'.format(plan.chunks)
 							   if plan.chunks else 'all-gather of residual blocks as fixed-point digit planes + exponents + sums of squares'),
 						   exchange_bytes_per_rank=None if world == 1 else int((world - 1) * rows_local * n * (esz if plan.exchange_raw else (SLICES(n) or 8)))),
-			   roofline=gram_roofline(n, flops, gram_ms, plan.rows_pad, plan.k_pad),
-			   kernels_ms=plan.kernel_breakdown(), kernels_ms_from='timed region' if events_inside else '3 extra steps after the timed region',
+			   roofline=gram_roofline(n, flops, gram_ms, plan.rows_pad, plan.k_pad) if priced else None,
+			   kernels_ms=plan.kernel_breakdown() if priced else None,
+			   kernels_ms_from=('timed region' if events_inside else '3 extra steps after the timed region') if priced else None,
 			   guard=guard_verdict(plan.flags, plan.be.eng))
-	out['kernels_roofline'] = side_rooflines(out['kernels_ms'], rows_local, n, esz, SLICES(n), plan.local_pair_count(), esz)
-	if world > 1:
+	if priced:
+		out['kernels_roofline'] = side_rooflines(out['kernels_ms'], rows_local, n, esz, SLICES(n), plan.local_pair_count(), esz)
+	if world > 1 and full:
 		out['self_check'] = self_check(rk, plan, dt_local, dc)
 	return out, plan
 
 
-def bench_de(rk, nd, steps, warmup, which, covariates=20):
+def bench_de(rk, nd, steps, warmup, which, covariates=20, full=True, grab=None):
 	"""de shapes of BASELINE configs[2] (1 x 20k x 100k, 20 covariates: HBM-bound streaming path) and configs[3]
 	(1k gRNAs x 15k genes x 50k cells: MFMA-bound general path); gene rows of Y sharded over the ranks, no collective."""
 	torch = rk.torch
@@ -525,6 +581,8 @@ def bench_de(rk, nd, steps, warmup, which, covariates=20):
 	dy[:16] += 0.2 * dx[0]
 	plan = nd.DePlan(dx, dy, dc, rank=rank, world=world)
 	elapsed = timed_steps(rk, plan, steps, warmup, True)
+	if grab is not None:
+		grab(dict(zip(('p', 'gamma', 'varx', 'vary'), plan.results())))
 	tests = nx * ny_local * world
 	ms = plan.step_ms()
 	# per-kernel split of the step: three more steps, eager (a captured graph cannot be bracketed kernel by kernel), with the engine's
@@ -555,29 +613,30 @@ def bench_de(rk, nd, steps, warmup, which, covariates=20):
 					dense_path_flop_equivalent_tflops=2.0 * n * nx * ny_local / (kms * 1e-3) / 1e12)
 		# A COLD call: a design tensor the engine has not seen (every step of the timed region reuses the lists the plan keeps for its
 		# design; a one-shot norm.de pays for them).  Fresh copies of the design are made outside the timed region; every timed call builds
-		# the lists (csrc/nrm_design_lists.hip), the design rows' statistics and everything else of a resident step, eagerly.
-		fresh = [dx.clone() for _ in range(max(2, min(steps, 5)) + 1)]
-		call = lambda d: eng.association_single0(d, dy, plan.dc64, plan.dci, plan.dcr, 0, return_dot=False, want_alpha=False, out_dtype=plan.out_dtype, cov=plan.cov, resident=True)
-		call(fresh.pop())
-		rk.barrier()
-		t0 = time.perf_counter()
-		for d in fresh:
-			call(d)
-		rk.barrier()
-		cold_ms = 1e3 * rk.max_over_ranks(time.perf_counter() - t0) / len(fresh)
-		eng.trace = []
-		call(dx.clone())
-		torch.cuda.synchronize()
-		cold_split = {}
-		for name, e0, e1 in eng.trace:
-			cold_split[name] = round(cold_split.get(name, 0.0) + e0.elapsed_time(e1), 4)
-		eng.trace = None
+		# the lists (csrc/nrm_design_lists.hip), the design rows' statistics and everything else of a resident step, eagerly.  (--full)
+		if full:
+			fresh = [dx.clone() for _ in range(max(2, min(steps, 5)) + 1)]
+			call = lambda d: eng.association_single0(d, dy, plan.dc64, plan.dci, plan.dcr, 0, return_dot=False, want_alpha=False, out_dtype=plan.out_dtype, cov=plan.cov, resident=True)
+			call(fresh.pop())
+			rk.barrier()
+			t0 = time.perf_counter()
+			for d in fresh:
+				call(d)
+			rk.barrier()
+			cold_ms = 1e3 * rk.max_over_ranks(time.perf_counter() - t0) / len(fresh)
+			eng.trace = []
+			call(dx.clone())
+			torch.cuda.synchronize()
+			cold_split = {}
+			for name, e0, e1 in eng.trace:
+				cold_split[name] = round(cold_split.get(name, 0.0) + e0.elapsed_time(e1), 4)
+			eng.trace = None
 	else:
 		roof = gram_roofline(n, 2.0 * n * nx * ny_local, split.get('gram', ms), 0, 0)  # K2 alone
 		roof['algorithmic_bytes'] = float(SLICES(n) or 8) * (nx + ny_local) * n
 		roof['step_ms'] = ms
 	extra = {}
-	if 'de_sparse' in split:
+	if 'de_sparse' in split and full:
 		extra = dict(cold_ms=cold_ms, cold_kernels_ms=cold_split, cold_note='a call on a design tensor the engine has not seen (lists built by csrc/nrm_design_lists.hip inside the call); '
 					 'ms_per_step is a resident DePlan step, which keeps the lists of its design', cold_tests_per_s=tests / (cold_ms * 1e-3))
 	return dict(extra, value=tests * steps / elapsed, unit='tests/s', steps=steps, warmup=warmup, ms_per_step=1e3 * elapsed / steps,
@@ -589,7 +648,7 @@ def bench_de(rk, nd, steps, warmup, which, covariates=20):
 					   if 'de_sparse' in split else guard_verdict(plan.result.get('flags'), eng)))
 
 
-def bench_de_method(rk, steps, warmup, single):
+def bench_de_method(rk, steps, warmup, single, full=True, grab=None):
 	"""BASELINE configs[3] as the reference's CRISPR example runs it besides the naive test (cmd_highmoi.sh:19-22): norm.de with
 	single=4 (`-m covariate`: every other gRNA a covariate, association.py:421-576,926-980) or single=1 (`-m single`: every gRNA on the
 	cells free of the others, :263-390,911-925).  1000 gRNAs x 15000 genes x 50000 cells, inputs resident in HBM, results left there;
@@ -639,6 +698,11 @@ def bench_de_method(rk, steps, warmup, single):
 		plan.step()
 	elapsed = timed_steps(rk, plan, steps, warmup, False)
 	plan.check()  # (the reference's assertions over the timed steps: device counters, looked at once)
+	if grab is not None:
+		res = plan.results(device_out=True) if hasattr(plan, 'results') else plan.out
+		if len(res) == 2 and isinstance(res[0], tuple):
+			res = res[0]
+		grab(dict(zip(('p', 'stat', 'alpha', 'varx', 'vary'), res)))
 	guard = dict(eng.last_guard)
 	eng.trace = []
 	for _ in range(2):
@@ -651,7 +715,7 @@ def bench_de_method(rk, steps, warmup, single):
 	tests = nx * ny_local * world
 	ms = 1e3 * elapsed / steps
 	cold = {}
-	if single == 1:
+	if single == 1 and full:
 		# a COLD call: the public entry on a design tensor the engine has not seen -- entry lists, a plan's buffers, one step, the counters read
 		fresh = [dx.clone() for _ in range(max(2, min(steps, 5)) + 1)]
 		fn(fresh.pop(), dy, dc_h, return_dot=False, device_out=True)
@@ -664,7 +728,7 @@ def bench_de_method(rk, steps, warmup, single):
 		cold_ms = 1e3 * rk.max_over_ranks(time.perf_counter() - t0) / len(fresh)
 		del out, fresh
 		cold = dict(cold_ms=cold_ms, cold_tests_per_s=tests / (cold_ms * 1e-3), cold_note='association_tests(single=1) on a design tensor the engine has not seen: entry lists, buffers, one step, the counters read back; ms_per_step is a resident Single1Plan step (one HIP graph)')
-	if single == 4:
+	if single == 4 and full:
 		# a COLD call: a design tensor the engine has not seen (the timed steps reuse the lists kept for their design tensor; single=1 lists
 		# its design anew in every call).  Fresh copies are made outside the timed region.
 		fresh = [dx.clone() for _ in range(max(2, min(steps, 5)) + 1)]
@@ -706,7 +770,7 @@ def bench_de_method(rk, steps, warmup, single):
 						   fp64_rerun=bool(guard.get('fallback', False))), metric='association tests/sec (de)')
 
 
-def bench_binnet(rk, steps, warmup):
+def bench_binnet(rk, steps, warmup, grab=None):
 	"""binnet (binnet.py:77-173) on a 30 000 x 30 000 fp64 P-value matrix resident in HBM -- the consumer of configs[4]'s output
 	(examples/GSE123139/code/cmd_coex.sh:40-42): per-row Benjamini-Hochberg threshold, one byte out per pair."""
 	torch = rk.torch
@@ -726,6 +790,8 @@ def bench_binnet(rk, steps, warmup):
 			self.out = nb.binnet(p, 0.05)
 	plan = Plan()
 	elapsed = timed_steps(rk, plan, steps, warmup, False)
+	if grab is not None:
+		grab(dict(net=plan.out))
 	ms = 1e3 * elapsed / steps
 	byts = float(ng) * ng * (8 + 1)
 	kept = int(plan.out.sum())
@@ -735,7 +801,7 @@ def bench_binnet(rk, steps, warmup):
 							  algorithmic_bytes=byts, traffic=None, kernel_ms=ms))
 
 
-def bench_normvar(rk, steps, warmup):
+def bench_normvar(rk, steps, warmup, full=True, grab=None):
 	"""norm.normvar (norm.py:166-289) on a configs[1]-sized matrix, the step in front of the hot path: 5000 genes x 10 000 cells fp32,
 	5 covariates, the matrix resident in HBM and the result left there (device_out=True: what coex / de take next) -- per-gene moments in one
 	pass, a thread per gene solves its small OLS, one pass writes the result (csrc/nrm_normvar.hip).  The numpy -> numpy call (0.2 GB up,
@@ -756,24 +822,27 @@ def bench_normvar(rk, steps, warmup):
 	plan.step()
 	elapsed = timed_steps(rk, plan, steps, warmup, False)
 	plan.check()
+	if grab is not None:
+		grab(dict(dtn=plan.out, dcn=plan.dcn))
 	ms = 1e3 * elapsed / steps
-	t0 = time.perf_counter()
-	for _ in range(5):
-		pub = norm.normvar(d_dt, dc, w, wt, device_out=True)
-	torch.cuda.synchronize()
-	public_ms = 1e3 * (time.perf_counter() - t0) / 5
-	assert torch.equal(pub[0], plan.out)  # (the same kernels on the same inputs)
-	del pub
-	eng.trace = []
-	norm.normvar(d_dt, dc, w, wt, device_out=True)
-	torch.cuda.synchronize()
-	split = {}
-	for name, e0, e1 in eng.trace:
-		split[name] = round(split.get(name, 0.0) + e0.elapsed_time(e1), 4)
-	eng.trace = None
-	t0 = time.perf_counter()
-	norm.normvar(dt, dc, w, wt)
-	host_ms = 1e3 * (time.perf_counter() - t0)
+	split, public_ms, host_ms = {}, None, None
+	if full:  # the public call beside the plan, its kernels one by one, and the numpy -> numpy call
+		t0 = time.perf_counter()
+		for _ in range(5):
+			pub = norm.normvar(d_dt, dc, w, wt, device_out=True)
+		torch.cuda.synchronize()
+		public_ms = 1e3 * (time.perf_counter() - t0) / 5
+		assert torch.equal(pub[0], plan.out)  # (the same kernels on the same inputs)
+		del pub
+		eng.trace = []
+		norm.normvar(d_dt, dc, w, wt, device_out=True)
+		torch.cuda.synchronize()
+		for name, e0, e1 in eng.trace:
+			split[name] = round(split.get(name, 0.0) + e0.elapsed_time(e1), 4)
+		eng.trace = None
+		t0 = time.perf_counter()
+		norm.normvar(dt, dc, w, wt)
+		host_ms = 1e3 * (time.perf_counter() - t0)
 	byts = float(ng) * n * (4 + 8)  # algorithmic: the fp32 matrix read once, the fp64 result written once
 	kms = sum(split.values()) or ms
 	return dict(metric='normvar values/sec (resident)', value=float(ng) * n * steps / elapsed, unit='values/s', steps=steps, warmup=warmup, ms_per_step=ms,
@@ -784,7 +853,7 @@ def bench_normvar(rk, steps, warmup):
 							  note='the matrix is read twice (moments, then the result); the result pass runs at the HBM rate, the moments pass re-reads the covariates per gene from L2 (DESIGN.md section 6); a step also uploads the covariates and weights (0.5 MB) and reads one word of flags back'))
 
 
-def bench_chain(rk, steps, warmup):
+def bench_chain(rk, steps, warmup, full=True, grab=None):
 	"""The reference's pipeline normvar -> coex -> binnet (examples/GSE123139/code/cmd_coex.sh:38-46; norm.py:166-289 feeds coex.py:46-48 feeds
 	binnet.py:134-173) at configs[1] size as ONE resident chain: the expression matrix, the normalised matrix, the P-values and the network stay in
 	HBM between the three steps (the reference passes them through files)."""
@@ -812,14 +881,17 @@ def bench_chain(rk, steps, warmup):
 	plan = Plan()
 	plan.step()
 	elapsed = timed_steps(rk, plan, steps, warmup, False)
+	if grab is not None:
+		grab(dict(net=plan.net))
 	ms = 1e3 * elapsed / steps
-	eng.trace = []
-	plan.step()
-	torch.cuda.synchronize()
 	split = {}
-	for name, e0, e1 in eng.trace:
-		split[name] = round(split.get(name, 0.0) + e0.elapsed_time(e1), 4)
-	eng.trace = None
+	if full:  # the kernels of one more step, one by one
+		eng.trace = []
+		plan.step()
+		torch.cuda.synchronize()
+		for name, e0, e1 in eng.trace:
+			split[name] = round(split.get(name, 0.0) + e0.elapsed_time(e1), 4)
+		eng.trace = None
 	tests = ng * (ng - 1) // 2
 	roof = gram_roofline(n, 2.0 * n * (tests + ng), split.get('gram', ms), 5120, n)
 	roof['step_ms'] = ms
@@ -828,7 +900,7 @@ def bench_chain(rk, steps, warmup):
 																 edges_kept=int(plan.net.sum())), kernels_ms=split, roofline=roof)
 
 
-def bench_c5_full(rk):
+def bench_c5_full(rk, grab=None):
 	"""BASELINE configs[4] WHOLE on one GPU: 30 000 genes x 500 000 cells fp64 (4.5e8 pairs).  The 120 GB matrix is generated and
 	dropped in blocks of 3840 gene rows; only its 90 GB of digit planes stay resident (engine.coex_blocks_resident).  value = pairs /
 	(K1 + K2 + K3 time, HIP events); generating the synthetic blocks between the K1 launches is not part of the hot path."""
@@ -853,6 +925,8 @@ def bench_c5_full(rk):
 		split[name] = split.get(name, 0.0) + e0.elapsed_time(e1)
 	eng.trace = None
 	guard = guard_verdict(res['flags'], eng)
+	if grab is not None:
+		grab({k: v for k, v in res.items() if k != 'flags' and (torch.is_tensor(v) or isinstance(v, np.ndarray))})
 	del res
 	torch.cuda.empty_cache()
 	tests = ng * (ng - 1) // 2
@@ -869,10 +943,10 @@ def bench_c5_full(rk):
 def short(v, n=160):
 	return v if not isinstance(v, str) or len(v) <= n else v[:n - 3] + '...'
 
-def contract_line(head, extras, world, e2e=None):
+def contract_line(head, extras, world, e2e=None, full=True):
 	"""The one line the driver reads: BASELINE's metric on its config, roofline, cpu_baseline, the scaling series, and one summary row
 	per extra workload -- kept under 4 KB (the full records are the lines before it)."""
-	roof = {k: short(v, 120) for k, v in head['roofline'].items() if k in ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'algorithmic_bytes', 'kernel_ms',
+	roof = None if head['roofline'] is None else {k: short(v, 120) for k, v in head['roofline'].items() if k in ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'algorithmic_bytes', 'kernel_ms',
 																		  'frac_of_fp32_mfma_peak', 'frac_of_fp64_mfma_peak', 'effective_clock_ghz_profiled', 'traffic_source')}
 	cb = head.get('cpu_baseline')
 	line = dict(metric=head['metric'], value=head['value'], unit=head['unit'], n_gpus=world, steps=head['steps'], warmup=head['warmup'], ms_per_step=head['ms_per_step'],
@@ -895,7 +969,8 @@ def contract_line(head, extras, world, e2e=None):
 			row['cold_ms'] = round(r['cold_ms'], 3)
 		rows[w] = row
 	line['extra_workloads'] = rows
-	line['detail'] = 'full records: the JSON lines before this one (one per workload; also gpurun_out/bench_detail_n{}.jsonl)'.format(world)
+	if full:
+		line['detail'] = 'full records: the JSON lines before this one, one per workload'
 	if '_abandoned' in extras:
 		line['extras_abandoned'] = extras['_abandoned']
 	return line
@@ -923,7 +998,13 @@ def main():
 	ap.add_argument('--covariates', type=int, default=20, help='covariates of the de_c3 workload (<= 15 selects the half-width streaming kernel)')
 	ap.add_argument('--seed', type=int, default=2)
 	ap.add_argument('--e2e', type=int, default=2, help='repetitions of the numpy-in/numpy-out end-to-end timing (0 = skip)')
+	ap.add_argument('--full', action='store_true', help='everything beside the headline: CPU baseline, PCIe leg, extra workloads, N > 1 self-check, '
+					'per-kernel passes and cold calls, the full record of every workload (--cpu-seconds, --e2e and the --extras options apply here)')
+	ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the headline\'s last timed step computed as DIR/<name>.npy '
+					'(float32 / float64, at most 64 MB in all: larger outputs as a fixed, seeded sample of their rows)')
 	args = ap.parse_args()
+	if args.steps < 1 or args.warmup < 0:
+		ap.error('--steps must be >= 1 and --warmup >= 0')
 	if args.cpu_worker:
 		w = args.cpu_worker
 		cpu_baseline_worker(int(w[0]), int(w[1]), int(w[2]), int(w[3]), float(w[4]), bool(int(w[5])))
@@ -937,7 +1018,7 @@ def main():
 	if args.workload is None:
 		args.workload = 'coex_c2' if world == 1 else 'coex_c5'
 	cpu = None
-	if world == 1 and args.cpu_seconds > 0 and args.workload == 'coex_c2':
+	if args.full and world == 1 and args.cpu_seconds > 0 and args.workload == 'coex_c2':
 		# CPU baseline first, in a child process, before this process touches the GPU
 		cpu = cpu_baseline(int(round(args.genes)), args.cells, 3, args.seed, args.cpu_seconds, extras=not args.no_extras)
 
@@ -948,7 +1029,7 @@ def main():
 	n = args.cells
 
 	e2e = None
-	if world == 1 and args.e2e > 0 and args.workload == 'coex_c2':
+	if args.full and world == 1 and args.e2e > 0 and args.workload == 'coex_c2':
 		# numpy in -> numpy out through the drop-in API (H2D + kernels + D2H over PCIe); reported beside `value`, never as it
 		import normalisr_amd.normalisr as norm
 		# (measured before any timing event exists in this process: after hipEvents with timing have been recorded,
@@ -967,43 +1048,46 @@ def main():
 				   note='norm.coex(numpy fp32) -> numpy, pageable host memory, PCIe inclusive')
 		res = h_dt = None
 
-	def run(which, steps, warmup):
+	def run(which, steps, warmup, grab=None):
+		"""One workload; grab(outputs) is handed what its last timed step computed (the headline's, for --dump-outputs)."""
 		if which == 'coex_c2':
 			# weak scaling: pairs per GPU fixed -> genes ~ sqrt(N); rounded so every rank owns the same number of rows
 			rows_local = int(round(args.genes * np.sqrt(world) / world))
 			out, plan = bench_coex(rk, nd, steps, warmup, rows_local, n, args.seed, torch.float32,
-								   'norm.coex gene x gene, {genes} genes x {cells} cells, fp32 input, 3 covariates (BASELINE configs[1]' + ('' if world == 1 else ', genes scaled by sqrt(N)') + ')')
+								   'norm.coex gene x gene, {genes} genes x {cells} cells, fp32 input, 3 covariates (BASELINE configs[1]' + ('' if world == 1 else ', genes scaled by sqrt(N)') + ')',
+								   full=args.full, grab=grab)
 			out['metric'] = 'association tests/sec (gene x gene coex)'
-			if world == 1 and rows_local == 5000 and n == 10000:
+			if world == 1 and rows_local == 5000 and n == 10000 and out['roofline'] is not None:
 				pmc_traffic('coex_c2', out['roofline'])
 			return out
 		if which == 'coex_c5':
 			preflight_c5(rk, args.c5_rows, args.c5_cells)
 			out, plan = bench_coex(rk, nd, steps, warmup, args.c5_rows, args.c5_cells, 5, torch.float64,
 								   'norm.coex gene x gene, {genes} genes x {cells} cells, fp64 input, 3 covariates (BASELINE configs[4] at %d gene rows per rank' % args.c5_rows +
-								   ('; N=8 is the full 30k x 30k problem)' if world != 8 or args.c5_rows != C5_ROWS_PER_RANK else ': the full problem)'), loading=0.05)
+								   ('; N=8 is the full 30k x 30k problem)' if world != 8 or args.c5_rows != C5_ROWS_PER_RANK else ': the full problem)'), loading=0.05,
+								   full=args.full, grab=grab)
 			out['metric'] = 'association tests/sec (gene x gene coex)'
 			out['scaling'] = 'weak'  # (the contract's word for a per-rank input that stays fixed as N grows; what grows with N is said beside it)
 			out['scaling_note'] = 'gene rows per rank fixed; the block pairs a rank computes grow as (N+1)/2, the problem as N^2'
-			if world == 1:
+			if world == 1 and out['roofline'] is not None:
 				pmc_traffic('coex_c5', out['roofline'])
 			return out
 		if which == 'coex_c5_full_1gpu':
-			return bench_c5_full(rk)
+			return bench_c5_full(rk, grab=grab)
 		if which in ('de_c4_single4', 'de_c4_single1'):
-			out = bench_de_method(rk, steps, warmup, 4 if which.endswith('4') else 1)
+			out = bench_de_method(rk, steps, warmup, 4 if which.endswith('4') else 1, full=args.full, grab=grab)
 			kern = out['roofline'].pop('pmc_kernels', None)
 			if world == 1:
 				pmc_traffic(which + ('_dense' if out['roofline']['kernel'].startswith('k_gram') else ''), out['roofline'], kernels=kern)
 			return out
 		if which == 'normvar_c2':
-			out = bench_normvar(rk, steps, warmup)
+			out = bench_normvar(rk, steps, warmup, full=args.full, grab=grab)
 			pmc_traffic(which, out['roofline'], kernels=out['roofline'].pop('pmc_kernels', None))
 			return out
 		if which == 'chain_c2':
-			return bench_chain(rk, steps, warmup)
+			return bench_chain(rk, steps, warmup, full=args.full, grab=grab)
 		if which == 'binnet_c5':
-			out = bench_binnet(rk, steps, warmup)
+			out = bench_binnet(rk, steps, warmup, grab=grab)
 			if out is not None:
 				pmc_traffic(which, out['roofline'], kernels=['k_binnet_rows'])
 			return out
@@ -1011,17 +1095,18 @@ def main():
 			prev = os.environ.get('NRM_GRAM')
 			os.environ['NRM_GRAM'] = 'f64'
 			try:
-				out = run(which[:-4], steps, warmup)
+				out = run(which[:-4], steps, warmup, grab)
 			finally:
 				if prev is None:
 					del os.environ['NRM_GRAM']
 				else:
 					os.environ['NRM_GRAM'] = prev
 			for k in ('traffic', 'traffic_source', 'traffic_unit', 'effective_clock_ghz_profiled'):  # (the counters on file are the integer engine's)
-				out['roofline'].pop(k, None)
-			out['roofline']['traffic'] = None
+				(out['roofline'] or {}).pop(k, None)
+			if out['roofline'] is not None:
+				out['roofline']['traffic'] = None
 			return out
-		out = bench_de(rk, nd, steps, warmup, which, args.covariates)
+		out = bench_de(rk, nd, steps, warmup, which, args.covariates, full=args.full, grab=grab)
 		out['metric'] = 'association tests/sec (de)'
 		if world == 1:
 			dense = out['roofline']['kernel'].startswith('k_gram_i8') or out['roofline']['kernel'].startswith('k_gram_f64')
@@ -1030,7 +1115,14 @@ def main():
 			out['roofline'].pop('pmc_kernels', None)
 		return out
 
-	head = run(args.workload, args.steps, args.warmup)
+	dumped = {}
+
+	def grab(outputs):
+		if rank == 0:
+			dumped.update(dump_outputs(args.dump_outputs, outputs))
+	head = run(args.workload, args.steps, args.warmup, grab if args.dump_outputs else None)
+	if args.dump_outputs and rank == 0 and not dumped:
+		raise SystemExit('bench.py --dump-outputs: the {} workload handed no outputs'.format(args.workload))
 	head = dict(dict(metric=head.pop('metric'), value=head.pop('value'), unit=head.pop('unit'), n_gpus=world, steps=head.pop('steps'),
 					 warmup=head.pop('warmup'), ms_per_step=head.pop('ms_per_step'), higher_is_better=True, scaling=head.pop('scaling'),
 					 vs_baseline=None, dtype=head.pop('dtype'), data='synthetic'), **head)
@@ -1041,7 +1133,7 @@ def main():
 	cpu_extras = cpu.pop('extras', {}) if cpu else {}
 	head['cpu_baseline'] = cpu
 	head['end_to_end_pcie'] = e2e
-	head['frac_of_fp32_mfma_peak'] = head['roofline'].get('frac_of_fp32_mfma_peak')  # the roofline BASELINE.json's north_star names
+	head['frac_of_fp32_mfma_peak'] = (head['roofline'] or {}).get('frac_of_fp32_mfma_peak')  # the roofline BASELINE.json's north_star names
 
 	# ONE workload is measured at every N: the per-rank slice of BASELINE configs[4] (3750 gene rows per rank x 500 000 cells fp64; N = 8 is
 	# the full 30 000-gene problem the 8-GPU target is quoted on).  It is the headline at N > 1 and an extra at N = 1, where the headline is
@@ -1049,7 +1141,7 @@ def main():
 	def series_of(r):
 		return dict(workload='coex_c5: BASELINE configs[4] per-rank slice, {} gene rows per rank x {} cells fp64'.format(args.c5_rows, args.c5_cells), value=r['value'], unit=r['unit'],
 					ms_per_step=r['ms_per_step'], ranks=world, tests_per_step=r['config']['tests_per_step'], value_per_rank=r['value'] / world,
-					roofline_frac=r['roofline']['frac'], exchange_ms_not_hidden=r.get('kernels_ms', {}).get('exchange'))
+					roofline_frac=(r['roofline'] or {}).get('frac'), exchange_ms_not_hidden=(r.get('kernels_ms') or {}).get('exchange'))
 	head['scaling_series'] = series_of(head) if args.workload == 'coex_c5' else None
 	head['config']['scaling_series'] = 'top-level `scaling_series` = BASELINE configs[4] per-rank slice, the same workload at every N (the headline itself at N > 1)'
 
@@ -1060,7 +1152,7 @@ def main():
 	def say(obj):
 		"""A JSON line that is NOT the contract line: the full record of an extra workload (or of the headline), printed as soon as it exists
 		and appended to gpurun_out/bench_detail_nN.jsonl; the contract line, last and short, carries their summary."""
-		if rank != 0:
+		if rank != 0 or not args.full:
 			return
 		line = json.dumps(obj)
 		print(line, flush=True)
@@ -1079,15 +1171,15 @@ def main():
 				ctypes.CDLL(None).fflush(None)
 			except Exception:  # noqa: BLE001
 				pass
-			print(json.dumps(contract_line(head, extras, world, e2e)), flush=True)
+			print(json.dumps(contract_line(head, extras, world, e2e, full=args.full)), flush=True)
 
-	if rank == 0:
+	if rank == 0 and args.full:
 		try:
 			os.remove(detail_path)
 		except OSError:
 			pass
 	say(dict(workload_detail=args.workload, **head))
-	if not args.no_extras:
+	if args.full and not args.no_extras:
 		# the other BASELINE configs, measured like the headline; a stuck collective must not lose the headline line
 		def give_up():
 			extras['_abandoned'] = 'extra workloads exceeded --extras-timeout {} s'.format(args.extras_timeout)

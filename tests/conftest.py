@@ -83,9 +83,9 @@ def run_bench(extra_args, env_extra, timeout=900):
 
 @pytest.fixture(scope='session')
 def bench_default():
-	"""One default N=1 run of bench.py (short: 3 steps, no CPU baseline, no PCIe leg), shared by the test of the line's CONTENT
-	(tests/test_gpu_round2.py) and the timing bounds (tests/test_zz_perf_gpu.py)."""
-	return run_bench(['--steps', '3', '--warmup', '1', '--cpu-seconds', '0', '--e2e', '0', '--extras-steps', '2'], {})
+	"""One --full N=1 run of bench.py (short: 3 steps, no CPU baseline, no PCIe leg, every extra workload), shared by the test of the line's
+	CONTENT (tests/test_gpu_round2.py) and the timing bounds (tests/test_zz_perf_gpu.py)."""
+	return run_bench(['--full', '--steps', '3', '--warmup', '1', '--cpu-seconds', '0', '--e2e', '0', '--extras-steps', '2'], {})
 
 
 def queue_get(q, procs, timeout=300):

@@ -51,3 +51,29 @@ def test_traffic_comes_from_the_kernels_that_ran(tmp_path, monkeypatch):
 	roof = dict(kernel='k_fused_new', traffic=1.0, traffic_source='stale')
 	bench.pmc_traffic('w', roof)  # no counters for this kernel on file: null, never another kernel's
 	assert roof['traffic'] is None and 'traffic_source' not in roof
+
+
+def test_dump_outputs_float_files_within_the_budget(tmp_path):
+	"""--dump-outputs: one float32 / float64 .npy per output, small ones whole, large ones as the same seeded sample of rows on every call
+	(indices beside them), everything within the byte limit."""
+	import numpy as np
+	rng = np.random.default_rng(5)
+	big = rng.random((3000, 700)).astype(np.float32)
+	arrays = dict(p=big, stat=rng.random((3000, 700)), var=rng.random(3000), net=big > 0.5, flags=np.arange(8, dtype=np.int32), none=None)
+	limit = 4 << 20
+	shapes = bench.dump_outputs(str(tmp_path / 'a'), arrays, limit=limit)
+	assert set(shapes) == {'p', 'stat', 'var', 'net', 'flags'}
+	files = {f.name: f for f in (tmp_path / 'a').iterdir()}
+	assert sum(f.stat().st_size for f in files.values()) <= limit
+	loaded = {f[:-4]: np.load(files[f]) for f in files}
+	assert loaded['p'].dtype == np.float32 and loaded['net'].dtype == np.float32 and loaded['stat'].dtype == np.float64 and loaded['flags'].dtype == np.float64
+	assert np.array_equal(loaded['var'], arrays['var']) and np.array_equal(loaded['flags'], np.arange(8))  # small enough: whole
+	rows = loaded['p_rows'].astype(np.int64)
+	assert loaded['p_rows'].dtype == np.float64 and 0 < len(rows) < 3000 and (np.diff(rows) > 0).all()
+	assert np.array_equal(loaded['p'], big[rows]) and np.array_equal(loaded['net'], (big > 0.5)[loaded['net_rows'].astype(np.int64)].astype(np.float32))
+	bench.dump_outputs(str(tmp_path / 'b'), arrays, limit=limit)  # the same rows again
+	assert all(np.array_equal(np.load(tmp_path / 'b' / f), loaded[f[:-4]]) for f in files)
+	# a single row above its share: elements of the flattened output are sampled instead
+	shapes = bench.dump_outputs(str(tmp_path / 'c'), dict(wide=rng.random((2, 1 << 20))), limit=limit)
+	w = np.load(tmp_path / 'c' / 'wide.npy')
+	assert w.ndim == 1 and sum(f.stat().st_size for f in (tmp_path / 'c').iterdir()) <= limit

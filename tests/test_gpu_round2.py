@@ -264,7 +264,7 @@ from conftest import run_bench as _run_bench  # noqa: E402
 def test_bench_self_launches_two_ranks_on_one_gpu():
 	"""`python bench.py --gpus 2` as a plain invocation starts its own ranks (here both on this GPU over gloo: functional
 	check of the launcher and the N>1 path; RCCL needs one GPU per rank); the contract line is the last line of stdout."""
-	out = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'coex_c2', '--genes', '1200', '--cells', '2000', '--no-extras'],
+	out = _run_bench(['--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'coex_c2', '--genes', '1200', '--cells', '2000', '--no-extras'],
 					 dict(NRM_DIST_BACKEND='gloo', NRM_SHARE_GPU='1'))
 	assert out['n_gpus'] == 2 and out['ranks_seen_by_collective'] == 2 and out['value'] > 0
 	assert out['roofline']['bound'] == 'mfma' and out['roofline']['kernel_ms'] > 0 and 'exchange' in out['kernels_ms']
@@ -272,17 +272,17 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
 	sc = out['self_check']
 	assert sc['ok'] and sc['ranks'] == 2 and sc['ranks_seen_by_collective'] == 2 and sc['gene_rows_checked'] >= 12 and sc['max_relative_p_difference'] <= 1e-6
 	assert out['config']['exchange'] == 'all-gather of raw fp32 blocks'  # below 2048 cells: fp64 engine, raw rows travel
-	out = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'coex_c2', '--genes', '1200', '--cells', '8192', '--no-extras'],
+	out = _run_bench(['--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'coex_c2', '--genes', '1200', '--cells', '8192', '--no-extras'],
 					 dict(NRM_DIST_BACKEND='gloo', NRM_SHARE_GPU='1'))
 	assert out['n_gpus'] == 2 and out['value'] > 0 and out['config']['exchange'] == 'all-gather of raw fp32 blocks'  # auto on 2 ranks
-	out = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'coex_c2', '--genes', '1200', '--cells', '8192', '--no-extras'],
+	out = _run_bench(['--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'coex_c2', '--genes', '1200', '--cells', '8192', '--no-extras'],
 					 dict(NRM_DIST_BACKEND='gloo', NRM_SHARE_GPU='1', NRM_EXCHANGE='chunks'))
 	assert out['n_gpus'] == 2 and out['value'] > 0 and 'in 2 cell chunks' in out['config']['exchange']
 	assert out['kernels_ms']['gram'] > 0 and out['kernels_ms']['exchange'] >= 0
 	# the N > 1 DEFAULT is the workload the 8-GPU target is quoted on: configs[4] (here at a reduced per-rank block so that two ranks
 	# share one GPU in seconds): fp64 rows, digit planes exchanged in cell chunks, exchange accounting in the line -- and the SAME key,
 	# `scaling_series`, that the N = 1 line carries for this workload
-	out = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--c5-rows', '384', '--c5-cells', '40000', '--no-extras'],
+	out = _run_bench(['--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--c5-rows', '384', '--c5-cells', '40000', '--no-extras'],
 					 dict(NRM_DIST_BACKEND='gloo', NRM_SHARE_GPU='1'))
 	assert out['n_gpus'] == 2 and out['ranks_seen_by_collective'] == 2 and 'BASELINE configs[4]' in out['config']['workload']
 	assert out['config']['genes'] == 768 and out['config']['cells'] == 40000 and out['dtype'].startswith('i8 digits')
@@ -291,12 +291,12 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
 	assert out['self_check']['ok'] and out['self_check']['gene_rows_checked'] >= 12 and out['self_check']['max_relative_p_difference'] <= 1e-6
 	# ... and fails, non-zero, when a rank's P-values are not what one rank computes (one value of the last rank moved by 1e-3)
 	import subprocess
-	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1', '--c5-rows', '384', '--c5-cells', '40000', '--no-extras'],
+	r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '1', '--warmup', '1', '--c5-rows', '384', '--c5-cells', '40000', '--no-extras'],
 					   env=dict(os.environ, NRM_DIST_BACKEND='gloo', NRM_SHARE_GPU='1', NRM_BENCH_FAULT='p'), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
 	assert r.returncode != 0 and 'failed its own check' in r.stderr, (r.returncode, r.stderr[-1500:])
 	ser = out['scaling_series']
 	assert ser['ranks'] == 2 and ser['value'] == out['value'] and ser['ms_per_step'] == out['ms_per_step'] and ser['workload'].startswith('coex_c5') and 'scaling_series' in out['config']
-	one = _run_bench(['--steps', '2', '--warmup', '1', '--c5-rows', '384', '--c5-cells', '40000', '--cpu-seconds', '0', '--e2e', '0', '--extras', 'coex_c5', '--extras-steps', '2'], {})
+	one = _run_bench(['--full', '--steps', '2', '--warmup', '1', '--c5-rows', '384', '--c5-cells', '40000', '--cpu-seconds', '0', '--e2e', '0', '--extras', 'coex_c5', '--extras-steps', '2'], {})
 	assert one['n_gpus'] == 1 and one['config']['genes'] == 5000 and one['scaling_series']['ranks'] == 1 and one['scaling_series']['workload'] == ser['workload']
 	assert one['scaling_series']['ms_per_step'] == one['_detail']['coex_c5']['ms_per_step'] and one['scaling_series']['tests_per_step'] == 384 * 383 // 2
 
