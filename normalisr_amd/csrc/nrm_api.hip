@@ -174,11 +174,57 @@ extern "C" int nrm_copy_rect_to_host(void* h_dst, int64_t dst_pitch, const void*
 	return NRM_OK;
 }
 
+// Fills and device-to-device row copies as kernels of the library rather than hipMemsetAsync / hipMemcpy2DAsync: these run inside the steps
+// a resident plan captures as a HIP graph (DePlan: the result counters, the padded rows, the Z buffer), and a memset or copy node of a
+// replayed graph was seen to leave the 16 bytes of a DePlan's counters holding two addresses once other launches and host copies had run
+// between replays -- the third replay after a rewrite, every time; as kernels, the same sequence gives the counters it should
+// (tests/test_gpu_plan_rewrites.py).
+namespace {
+constexpr int FILL_THREADS = 256;
+
+inline unsigned fill_blocks(uint64_t units) {
+	uint64_t b = (units + FILL_THREADS - 1) / FILL_THREADS;
+	return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));  // (grid-stride loops below)
+}
+
+__global__ void k_fill_zero16(uint4* __restrict__ d, uint64_t n16) {
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (uint64_t)gridDim.x * blockDim.x) d[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ void k_fill_bytes(unsigned char* __restrict__ d, uint64_t n, unsigned char v) {
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) d[i] = v;
+}
+
+__global__ void k_fill_i32(int32_t* __restrict__ d, uint64_t n, int32_t v) {
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) d[i] = v;
+}
+
+// rows x per_row units of type T; pitches in units of T
+template <typename T>
+__global__ void k_copy_rows(T* __restrict__ d, uint64_t dp, const T* __restrict__ s, uint64_t sp, uint64_t per_row, uint64_t rows) {
+	const uint64_t total = per_row * rows;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t r = i / per_row, c = i - r * per_row;
+		d[r * dp + c] = s[r * sp + c];
+	}
+}
+}  // namespace
+
 extern "C" int nrm_fill_zero(void* d_dst, int64_t bytes, void* stream) {
 	NRM_REQUIRE(bytes >= 0, "nrm_fill_zero: negative size");
 	if (bytes == 0) return NRM_OK;
 	NRM_REQUIRE(d_dst != nullptr, "nrm_fill_zero: null pointer");
-	NRM_HIP(hipMemsetAsync(d_dst, 0, (size_t)bytes, (hipStream_t)stream));
+	hipStream_t st = (hipStream_t)stream;
+	unsigned char* d = (unsigned char*)d_dst;
+	uint64_t n = (uint64_t)bytes, n16 = ((uintptr_t)d % 16 == 0) ? n / 16 : 0;
+	if (n16) {
+		hipLaunchKernelGGL(k_fill_zero16, dim3(fill_blocks(n16)), dim3(FILL_THREADS), 0, st, (uint4*)d, n16);
+		NRM_HIP(hipGetLastError());
+	}
+	if (n > n16 * 16) {
+		hipLaunchKernelGGL(k_fill_bytes, dim3(fill_blocks(n - n16 * 16)), dim3(FILL_THREADS), 0, st, d + n16 * 16, n - n16 * 16, (unsigned char)0);
+		NRM_HIP(hipGetLastError());
+	}
 	return NRM_OK;
 }
 
@@ -186,7 +232,8 @@ extern "C" int nrm_fill_i32(void* d_dst, int32_t value, int64_t count, void* str
 	NRM_REQUIRE(count >= 0, "nrm_fill_i32: negative size");
 	if (count == 0) return NRM_OK;
 	NRM_REQUIRE(d_dst != nullptr && (uintptr_t)d_dst % 4 == 0, "nrm_fill_i32: bad pointer");
-	NRM_HIP(hipMemsetD32Async((hipDeviceptr_t)d_dst, value, (size_t)count, (hipStream_t)stream));
+	hipLaunchKernelGGL(k_fill_i32, dim3(fill_blocks((uint64_t)count)), dim3(FILL_THREADS), 0, (hipStream_t)stream, (int32_t*)d_dst, (uint64_t)count, value);
+	NRM_HIP(hipGetLastError());
 	return NRM_OK;
 }
 
@@ -195,8 +242,22 @@ extern "C" int nrm_copy_rows(void* d_dst, int64_t dst_pitch, const void* d_src, 
 	NRM_REQUIRE(row_bytes >= 0 && rows >= 0 && dst_pitch >= row_bytes && src_pitch >= row_bytes, "nrm_copy_rows: pitches smaller than the row");
 	if (row_bytes == 0 || rows == 0) return NRM_OK;
 	NRM_REQUIRE(d_dst && d_src, "nrm_copy_rows: null pointer");
-	NRM_HIP(hipMemcpy2DAsync(d_dst, (size_t)dst_pitch, d_src, (size_t)src_pitch, (size_t)row_bytes, (size_t)rows, hipMemcpyDeviceToDevice,
-							 (hipStream_t)stream));
+	hipStream_t st = (hipStream_t)stream;
+	const uint64_t a = (uint64_t)(uintptr_t)d_dst | (uint64_t)(uintptr_t)d_src | (uint64_t)dst_pitch | (uint64_t)src_pitch | (uint64_t)row_bytes;
+	const uint64_t r = (uint64_t)rows;
+	if (a % 16 == 0) {
+		const uint64_t per = (uint64_t)row_bytes / 16;
+		hipLaunchKernelGGL(k_copy_rows<uint4>, dim3(fill_blocks(per * r)), dim3(FILL_THREADS), 0, st, (uint4*)d_dst, (uint64_t)dst_pitch / 16,
+						   (const uint4*)d_src, (uint64_t)src_pitch / 16, per, r);
+	} else if (a % 4 == 0) {
+		const uint64_t per = (uint64_t)row_bytes / 4;
+		hipLaunchKernelGGL(k_copy_rows<uint32_t>, dim3(fill_blocks(per * r)), dim3(FILL_THREADS), 0, st, (uint32_t*)d_dst, (uint64_t)dst_pitch / 4,
+						   (const uint32_t*)d_src, (uint64_t)src_pitch / 4, per, r);
+	} else {
+		hipLaunchKernelGGL(k_copy_rows<unsigned char>, dim3(fill_blocks((uint64_t)row_bytes * r)), dim3(FILL_THREADS), 0, st, (unsigned char*)d_dst,
+						   (uint64_t)dst_pitch, (const unsigned char*)d_src, (uint64_t)src_pitch, (uint64_t)row_bytes, r);
+	}
+	NRM_HIP(hipGetLastError());
 	return NRM_OK;
 }
 

@@ -789,7 +789,10 @@ class DePlan:
 	"""Sharded de (dy given): rank r owns a block of gene rows of Y; the design rows X and the covariates are
 	replicated and residualised redundantly, so there is NO collective on the data path (outputs are disjoint
 	column blocks of the (n_x, n_y) result).  step() runs one resident pass (outputs stay in HBM, self.result);
-	results() returns this rank's (p, gamma, varx, vary) as numpy arrays."""
+	results() returns this rank's (p, gamma, varx, vary) as numpy arrays.  dx / dy_local may be rewritten in place between steps: a graph
+	replays what it captured on the buffers as they are, which covers new values of dy, but the sparse-design path keeps entry lists built
+	from dx's values -- so a write to dx (torch counts it in ._version) drops the graph, those lists and a refusal of the sparse kernels, and
+	the next step decides again (eagerly) and the one after it captures again."""
 
 	def __init__(self, dx, dy_local, dc, rank=0, world=1, dimreduce=0, return_dot=False, device=None):
 		from .association import _prepare_covariates
@@ -812,6 +815,7 @@ class DePlan:
 		# buffers of the streaming path that a captured graph points into, and the row scales of the resident expression rows: owned by
 		# the plan (see association_de_streaming); keep=True: the plan is resident, its rows will be streamed again
 		self._state = {'keep': True}
+		self._dx_version = dx._version
 
 	def _run(self):
 		# resident step: p / gamma / sums of squares stay in HBM; results() brings them to the host and checks the flags
@@ -822,6 +826,11 @@ class DePlan:
 	@_on_engine
 	def step(self, timed=False):
 		torch = self.eng.torch
+		if self.dx._version != self._dx_version:  # the design written to in place since the last step (see the class docstring)
+			self._dx_version = self.dx._version
+			self._graph.graph, self._graph.result, self._graph.calls = None, None, 0
+			self._state.pop('sparse', None)
+			self._state.pop('sparse_refused', None)  # (a refusal was about the old values)
 		if timed:
 			e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 			e0.record()

@@ -344,7 +344,8 @@ class Single4Plan:
 	counted on the device instead and checked in results(): rows too close to the span of the covariates, a diagonal of N~ that is not positive, a
 	last Newton-Schulz residual above the eager criterion, non-finite results, R^2 out of range -- any of them and the step is redone by the public
 	call (which has the fallbacks).  Anything else (dense design, guard-carrying integer engine, rank-deficient design, per-gene dimreduce) keeps
-	calling the public function every step."""
+	calling the public function every step.  dx / dy may be rewritten in place between steps (torch counts that in ._version): the next step is the
+	public call on the new values, the one after it decides anew and the graph is captured again -- the old one is never replayed."""
 
 	def __init__(self, dx, dy, dc, dimreduce=0, lowmem=True, return_dot=True, eng=None):
 		eng = self.eng = eng or _engine.get_engine()
@@ -354,14 +355,22 @@ class Single4Plan:
 		self.out = None
 		self.lean = None  # decided by the first step
 		self.fallbacks = 0
+		self._forget()
+
+	def _forget(self):
+		"""A fresh graph and no residual of a lean step: whenever the plan decides anew (the first step, inputs written to in place since), what a graph
+		captured before points into -- flags, covariates, entry lists, the second stream -- is replaced by _first() and the Newton-Schulz start and step
+		count may change, so that graph must never be replayed again (its buffers are back in torch's allocator)."""
 		from .distributed import StepGraph
-		self._graph = StepGraph(eng.torch)
+		self._graph = StepGraph(self.eng.torch)
+		self.res = None
 
 	def _public(self):
 		return association_tests_single4(self.dx, self.dy, self.dc, lowmem=self.lowmem, return_dot=self.return_dot, dimreduce=self.dimreduce, device_out=True)
 
 	def _first(self):
 		eng = self.eng
+		self._forget()
 		eng._s4_inverse = eng._s4_path = None
 		out = self._public()
 		path, inv = getattr(eng, '_s4_path', None), getattr(eng, '_s4_inverse', None)
@@ -429,8 +438,9 @@ class Single4Plan:
 			if not self.lean or (self.dx._version, self.dy._version) != self.versions:
 				self.out = None
 				self.out = self._public()
-				if self.lean:  # (inputs written to since the first step: decided anew)
+				if self.lean:  # (inputs written to since the first step: decided anew by the next step, which captures a graph of its own)
 					self.lean = None
+					self._forget()
 				return
 			if eng.trace is not None:
 				p, stat, varx, vary, self.res = self._launch()
@@ -440,7 +450,8 @@ class Single4Plan:
 			eng.last_guard = dict(hits=0, worst=0.0, fallback=False)
 
 	def check(self):
-		"""True when the lean steps since the last look stand; otherwise the last step has been redone by the public call (self.out replaced)."""
+		"""True when the lean steps since the last look stand; otherwise the last step has been redone by the public call (self.out replaced -- by what
+		that call raised, if it raised: results() raises it) and False."""
 		if not self.lean:
 			return True
 		eng = self.eng
@@ -454,13 +465,18 @@ class Single4Plan:
 			self.fallbacks += 1
 			self.lean = False
 			self.out = None
-			self.out = self._public()
+			try:
+				self.out = self._public()
+			except (AssertionError, ValueError, RuntimeError, np.linalg.LinAlgError) as e:  # (what the public call raises on these inputs -- a result
+				self.out = e.with_traceback(None)  # that is not finite -- comes out of results(); no frame of the failed call is kept alive)
 			return False
 
 	def results(self, device_out=False):
-		"""(p, gamma|dot, alpha|None, varx (n_x,), vary (n_x, n_y)) of the last step."""
+		"""(p, gamma|dot, alpha|None, varx (n_x,), vary (n_x, n_y)) of the last step; raises what the public call raised when check() redid the step."""
 		self.check()
 		out = self.out
+		if isinstance(out, Exception):
+			raise out
 		if isinstance(out, tuple) and len(out) == 2 and isinstance(out[0], tuple):
 			out = out[0]
 		p, stat, alpha, varx, vary = out

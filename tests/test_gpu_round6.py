@@ -139,6 +139,7 @@ def test_single4_plan_replays_the_public_call(dtype, monkeypatch):
 	for a, b, c in zip(ref, first, lean):
 		assert (a is None and b is None and c is None) or (np.array_equal(a, b) and np.array_equal(a, c))
 	# the expression matrix written to in place: the next step is the public call again (and decides anew), results follow the new values
+	g0 = plan._graph.graph
 	d_y[7] += 2.0 * d_x[5]
 	plan.step()
 	changed = plan.results()
@@ -147,6 +148,15 @@ def test_single4_plan_replays_the_public_call(dtype, monkeypatch):
 	ok = want2[0] > (1e-30 if dtype == np.float32 else 1e-290)  # (fp32 outputs end at 1e-38: the pair just made significant lies far below)
 	assert not ok[5, 7] or want2[0][5, 7] < 1e-6
 	assert p_close(changed[0][ok], want2[0][ok], 1e-6) and changed[0][5, 7] < 1e-6
+	# the step after decides anew with a graph of its own (the old one points at buffers of the old decision), then eager, captured, replayed: the
+	# public call's bits every time
+	ref2 = association_tests_single4(d_x, d_y, dc, return_dot=False)
+	for k in range(4):
+		plan.step()
+		assert plan.lean is True and plan._graph.graph is not g0 and plan.check() and plan.fallbacks == 0
+		again = plan.results()
+		assert all((a is None and b is None) or np.array_equal(a, b) for a, b in zip(ref2, again))
+	assert plan._graph.graph is not None and plan._graph.graph is not g0 and p_close(again[0][ok], want2[0][ok], 1e-6)
 	# a dense design has no lean form: the plan keeps calling the public function
 	monkeypatch.setenv('NRM_DE_SPARSE', '0')
 	dense = Single4Plan(d_x, d_y, dc, return_dot=False)
