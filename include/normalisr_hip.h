@@ -454,7 +454,10 @@ int nrm_association_tests_host(const void* h_dx, int x_dtype, int64_t nx,
  *     at most 32 covariates (the gRNA incidence of a screen; the package's masked-Gram path takes the rest);
  *   nrm_association_tests_single4_host (`-m covariate`, association.py:421-576,926-980): the closed form for full-rank designs -- rank == nc
  *     (h_dci, rank from the host's inv_rank of C C^T) and A A^T certified full rank at `tol` (association.py:77) from norms at hand; a sparse design
- *     goes through the sparse-design kernels, any other through nrm_residualize + nrm_gram_f64.
+ *     goes through the sparse-design kernels, any other through nrm_residualize + nrm_gram_f64;
+ *   nrm_association_tests_single4_pinv_host: the same closed form for covariates of any rank 0 < rank <= nc (one-hot batches and an intercept:
+ *     rank < nc), the rows residualised with h_dci = inv_rank's pseudo-inverse of C C^T and dof = n - nx - rank - dimreduce, when every grouping's
+ *     matrix in the reference's loop certainly has the rank nx - 1 + rank at `tol` (single4.py: pinv_rank_certificate, from norms at hand).
  * nrm_binnet_host (binnet.py:134-173): h_p (ng, ng) -> h_net (ng, ng) bytes 0 / 1, *total = selected entries (0: the reference raises).
  */
 int nrm_association_tests_single1_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const void* h_dc, int c_dtype,
@@ -463,6 +466,9 @@ int nrm_association_tests_single1_host(const void* h_dx, int x_dtype, int64_t nx
 int nrm_association_tests_single4_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const void* h_dc, int c_dtype,
 									   int64_t nc, int64_t n_cells, const double* h_dci, int rank, int dimreduce, int return_dot, double tol, void* h_p,
 									   void* h_stat, void* h_alpha, void* h_varx, void* h_vary, int out_dtype);
+int nrm_association_tests_single4_pinv_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const void* h_dc, int c_dtype,
+											int64_t nc, int64_t n_cells, const double* h_dci, int rank, int dimreduce, int return_dot, double tol, void* h_p,
+											void* h_stat, void* h_alpha, void* h_varx, void* h_vary, int out_dtype);
 int nrm_binnet_host(const void* h_p, int p_dtype, int64_t ng, double qcut, unsigned char* h_net, int64_t* total);
 /* (Round 6) What the package needs to follow the reference's per-grouping algorithm of single=4 without torch where the closed form of
  * nrm_association_tests_single4_host does not apply (rank-deficient A A^T, mpc / method / qr, dy=None): the Gram matrices association.py:926-968 forms with

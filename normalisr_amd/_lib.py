@@ -108,6 +108,7 @@ _SIGNATURES = {
 	'nrm_alpha': ([_vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp], _i32),
 	'nrm_association_tests_single1_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32], _i32),
 	'nrm_association_tests_single4_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _i32], _i32),
+	'nrm_association_tests_single4_pinv_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _i32], _i32),
 	'nrm_binnet_host': ([_vp, _i32, _i64, _dbl, _vp, _vp], _i32),
 	'nrm_gram_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _vp], _i32),
 	'nrm_pvalues_host': ([_vp, _i64, _dbl, _vp], _i32),

@@ -282,7 +282,7 @@ def _use_host_entry():
 def _single14_host_entry(single, dx, dy, dc, lowmem, return_dot, ka):
 	"""single=1 / single=4 through nrm_association_tests_single1_host / _single4_host (include/normalisr_hip.h): host buffers in and out, no torch --
 	what `normalisr de -m single|covariate` needs in a process that has numpy and the library only.  NotImplementedError (NRM_E_UNSUPPORTED) for the
-	calls the entries do not cover (per-gene dimreduce, mpc / method / qr, rank-deficient designs, negative entries, dy=None): with torch present the
+	calls the entries do not cover (per-gene dimreduce, mpc / method / qr, designs without a rank certificate, negative entries, dy=None): with torch present the
 	caller then takes the package's device paths."""
 	import ctypes
 	ka = dict(ka)
@@ -322,8 +322,9 @@ def _single14_host_entry(single, dx, dy, dc, lowmem, return_dot, ka):
 		_lib.check(lib.nrm_association_tests_single1_host(vp(dx), code(dx), nx, vp(dy), code(dy), ny, vp(dc64), _lib.NRM_F64, nc, n, int(dimreduce), 1 if return_dot else 0,
 														  vp(p), vp(stat), vp(alpha), vp(varx), vp(vary), ocode))
 	else:
-		_lib.check(lib.nrm_association_tests_single4_host(vp(dx), code(dx), nx, vp(dy), code(dy), ny, vp(dc64), _lib.NRM_F64, nc, n, vp(dci), int(dcr), int(dimreduce),
-														  1 if return_dot else 0, float(tol), vp(p), vp(stat), vp(alpha), vp(varx), vp(vary), ocode))
+		# (covariates of any rank: one-hot batches with an intercept take the closed form too, nrm_association_tests_single4_pinv_host)
+		_lib.check(lib.nrm_association_tests_single4_pinv_host(vp(dx), code(dx), nx, vp(dy), code(dy), ny, vp(dc64), _lib.NRM_F64, nc, n, vp(dci), int(dcr),
+															   int(dimreduce), 1 if return_dot else 0, float(tol), vp(p), vp(stat), vp(alpha), vp(varx), vp(vary), ocode))
 	return (p, stat, alpha, varx, vary)
 
 

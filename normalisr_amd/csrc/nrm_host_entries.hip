@@ -3,6 +3,7 @@
 //   * the sparse-design form of single=0 de inside nrm_association_tests_host (association.py:224-235 for a design with few entries),
 //   * nrm_association_tests_single1_host   (`normalisr de -m single`:    association.py:263-390,911-925),
 //   * nrm_association_tests_single4_host   (`normalisr de -m covariate`: association.py:421-576,926-980, full-rank designs),
+//   * nrm_association_tests_single4_pinv_host (the same, covariates of any rank: one-hot batches and an intercept),
 //   * nrm_binnet_host                      (binnet.py:134-173)
 // -- the same kernels the Python host (normalisr_amd/de_sparse.py, single1.py, single4.py, binnet.py) drives through the device-pointer
 // entries, sequenced here in C++ with the library's own scratch pool.  Round 4 had only the dense path behind the C seam: configs[3] ran in
@@ -13,6 +14,7 @@
 #include <vector>
 #include "nrm_host_entry.h"
 #include "nrm_design.h"
+#include "nrm_jacobi.h"
 
 int NrmDesignLists::build(const void* d_x, int x_dtype, int64_t nx, int64_t n, bool want_ell, double max_density, hipStream_t st) {
 	nslots = nrm_round_up(nx, 64);
@@ -890,22 +892,69 @@ bool spd_inverse_host(std::vector<double>& m, int64_t n) {
 	return true;
 }
 
-}  // namespace
+// Does the closed form on rows residualised with the pseudo-inverse of C C^T (rank < nc) give the reference's per-grouping results?  Every T_i --
+// A A^T without row and column i, which association.py:521-530 pseudo-inverts -- must have the rank nx - 1 + rank at `tol` (association.py:77).
+// The certificate of single4.py (pinv_rank_certificate): with Mcc = V diag(w) V^T split into kept and dropped eigenvectors and eps0 the largest
+// dropped eigenvalue, eps0 <= tol w_max / 2, and lambda_min(R) - ||E|| - eps0 >= 2 tol (lambda_max(R) + ||E|| + eps0), R the Gram matrix of
+// [X; V_r^T C] bounded from ||M~||_1, ||N~||_1 and b V_r, ||E|| <= ||X||_F sqrt(eps0).  mcc is destroyed.
+bool pinv_rank_certified(std::vector<double>& mcc, int64_t nc, int rank, const std::vector<double>& bx, const std::vector<double>& ssx, int64_t nx,
+						 double norm_mt, double norm_ninv, double tol) {
+	std::vector<double> v((size_t)nc * nc), w((size_t)nc);
+	nrm_jacobi(mcc.data(), v.data(), w.data(), (int)nc);
+	double lam1 = 0.0;
+	for (int64_t k = 0; k < nc; k++) lam1 = w[(size_t)k] > lam1 ? w[(size_t)k] : lam1;
+	if (!(lam1 > 0) || !std::isfinite(lam1)) return false;
+	double eps0 = 0.0, wmin = INFINITY, wmax = 0.0;
+	int kept = 0;
+	for (int64_t k = 0; k < nc; k++) {
+		const double e = w[(size_t)k];
+		if (!std::isfinite(e)) return false;
+		if (e >= tol * lam1) {
+			kept++;
+			wmin = e < wmin ? e : wmin;
+			wmax = e > wmax ? e : wmax;
+		} else if (e > eps0)
+			eps0 = e;
+	}
+	if (kept != rank || !(eps0 <= 0.5 * tol * lam1)) return false;
+	double a2 = 0.0, b2 = 0.0, xf2 = 0.0;
+	for (int64_t i = 0; i < nx; i++) {
+		xf2 += ssx[(size_t)i];
+		for (int64_t k = 0; k < nc; k++) {
+			const double e = w[(size_t)k];
+			if (!(e >= tol * lam1)) continue;
+			double br = 0.0;  // (b V_r)_ik
+			for (int64_t d = 0; d < nc; d++) br += bx[(size_t)(i * nc + d)] * v[(size_t)(d * nc + k)];
+			a2 += br * br * e * e;
+			b2 += br * br;
+			xf2 += br * br * e;
+		}
+	}
+	const double lam_max = norm_mt + a2 / wmin + wmax;
+	const double inv_norm = norm_ninv * (1.0 + std::sqrt(b2)) * (1.0 + std::sqrt(b2)) + 1.0 / wmin;
+	const double e = std::sqrt((xf2 > 0 ? xf2 : 0.0) * eps0);
+	const double lo = 1.0 / inv_norm - e - eps0, hi = lam_max + e + eps0;
+	return std::isfinite(lo) && std::isfinite(hi) && norm_mt > 0 && norm_ninv > 0 && hi > 0 && lo >= 2.0 * tol * hi;
+}
 
-extern "C" int nrm_association_tests_single4_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const void* h_dc, int c_dtype,
-												   int64_t nc, int64_t n, const double* h_dci, int rank, int dimreduce, int return_dot, double tol, void* h_p,
-												   void* h_stat, void* h_alpha, void* h_varx, void* h_vary, int out_dtype) {
-	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+// single=4's closed form, both entries: rank == nc (full-rank covariates, A A^T certified full rank) or 0 < rank < nc (pinv_rank_certified)
+int single4_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const void* h_dc, int c_dtype, int64_t nc, int64_t n,
+				 const double* h_dci, int rank, int dimreduce, int return_dot, double tol, void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary,
+				 int out_dtype, bool full_rank_only) {
 	NRM_TRY(nrm_bind_device());
 	NRM_REQUIRE(h_dx && h_dy && nx > 0 && ny > 0 && n > 0 && nc >= 0 && (nc == 0 || (h_dc && h_dci)), "Unmatching dx/dy/dc dimensions.");
 	NRM_REQUIRE(h_p && h_stat && h_varx && h_vary, "nrm_association_tests_single4_host: null output");
 	NRM_REQUIRE((x_dtype == NRM_F32 || x_dtype == NRM_F64) && (y_dtype == NRM_F32 || y_dtype == NRM_F64) && (out_dtype == NRM_F32 || out_dtype == NRM_F64), "bad dtype");
-	const int64_t m = nx + nc;
-	if (rank != nc) {  // (a rank-deficient C C^T is a principal block of A A^T: no closed form)
+	if (full_rank_only && rank != nc) {  // (the closed form for rank-deficient covariates: nrm_association_tests_single4_pinv_host)
 		nrm_set_error("nrm_association_tests_single4_host covers full-rank designs (closed form); rank-deficient covariates follow the per-grouping algorithm of the package");
 		return NRM_E_UNSUPPORTED;
 	}
-	if (n <= m + dimreduce) {
+	NRM_REQUIRE(rank >= 0 && rank <= nc, "dcr higher than covariate dimension.");
+	if (rank < nc && rank == 0) {  // (all-zero covariates)
+		nrm_set_error("nrm_association_tests_single4_pinv_host: covariates of rank 0 follow the per-grouping algorithm of the package");
+		return NRM_E_UNSUPPORTED;
+	}
+	if (n <= nx + rank + dimreduce) {  // (rank nx - 1 + rank per grouping: dof = n - nx - rank - dimreduce, association.py:558)
 		nrm_set_error("Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.");
 		return NRM_E_DEVICE;
 	}
@@ -1058,7 +1107,7 @@ extern "C" int nrm_association_tests_single4_host(const void* h_dx, int x_dtype,
 		NRM_TRY(ostat.alloc(ob));
 		NRM_TRY(ovary.alloc(ob));
 		NRM_TRY(work.alloc((size_t)ny * 8));
-		NRM_TRY(nrm_single4_sweep(bt.as<double>(), g.as<double>(), nxp, ssy.as<double>(), ddxx.as<double>(), nx, ny, nx, n, (double)(n - m - dimreduce), return_dot, op.p, ostat.p,
+		NRM_TRY(nrm_single4_sweep(bt.as<double>(), g.as<double>(), nxp, ssy.as<double>(), ddxx.as<double>(), nx, ny, nx, n, (double)(n - nx - rank - dimreduce), return_dot, op.p, ostat.p,
 								  ovary.p, out_dtype, ny, work.as<double>(), flags.as<int32_t>(), st));
 		// (the reference's assertions on the closed form's results speak only if the closed form applies: a nearly rank-deficient design can fail them
 		//  where the per-grouping algorithm -- which the package then takes -- returns results; association.py:421-576.  Round-5 advisory.)
@@ -1068,7 +1117,21 @@ extern "C" int nrm_association_tests_single4_host(const void* h_dx, int x_dtype,
 		// norms at hand (single4.py: _surely_full_rank): lambda_max <= ||M~||_1 + ||a||_F^2 ||Mcc^-1|| + ||Mcc||, 1 / lambda_min <= ||N~||_1 (1 + ||b||_F)^2 + ||Mcc^-1||
 		double lam_max = norm_mt, inv_norm = norm_ninv;
 		std::vector<double> hbx;
-		if (nc) {
+		if (rank < nc) {  // rank-deficient covariates: every grouping's rank nx - 1 + rank (pinv_rank_certified)
+			std::vector<double> mcc((size_t)nc * nc, 0.0), hss;
+			for (int64_t c = 0; c < nc; c++)
+				for (int64_t d = c; d < nc; d++) {
+					double s = 0.0;
+					for (int64_t k = 0; k < n; k++) s += c64[(size_t)(c * n + k)] * c64[(size_t)(d * n + k)];
+					mcc[(size_t)(c * nc + d)] = mcc[(size_t)(d * nc + c)] = s;
+				}
+			NRM_TRY(download(hbx, bx.p, (size_t)nx * nc));
+			NRM_TRY(download(hss, ssx.p, (size_t)nx));
+			if (!pinv_rank_certified(mcc, nc, rank, hbx, hss, nx, norm_mt, norm_ninv, tol)) {
+				nrm_set_error("nrm_association_tests_single4_pinv_host: some grouping may not have the rank nx - 1 + %d at tol = %g (no certificate from the norms); the package takes the spectrum of A A^T and, if need be, the per-grouping algorithm", rank, tol);
+				return NRM_E_UNSUPPORTED;
+			}
+		} else if (nc) {
 			std::vector<double> mcc((size_t)nc * nc, 0.0), ev((size_t)nc);
 			for (int64_t c = 0; c < nc; c++)
 				for (int64_t d = c; d < nc; d++) {
@@ -1092,7 +1155,7 @@ extern "C" int nrm_association_tests_single4_host(const void* h_dx, int x_dtype,
 				inv_norm = norm_ninv * (1.0 + std::sqrt(b2)) * (1.0 + std::sqrt(b2)) + 1.0 / ev[0];
 			}
 		}
-		if (!(std::isfinite(lam_max) && std::isfinite(inv_norm) && lam_max > 0 && inv_norm > 0 && 1.0 / (inv_norm * lam_max) >= 2.0 * tol)) {
+		if (rank == nc && !(std::isfinite(lam_max) && std::isfinite(inv_norm) && lam_max > 0 && inv_norm > 0 && 1.0 / (inv_norm * lam_max) >= 2.0 * tol)) {
 			nrm_set_error("nrm_association_tests_single4_host: the design may be rank deficient at tol = %g (no certificate from the norms); the package takes the spectrum of A A^T and, if need be, the per-grouping algorithm", tol);
 			return NRM_E_UNSUPPORTED;
 		}
@@ -1133,4 +1196,22 @@ extern "C" int nrm_association_tests_single4_host(const void* h_dx, int x_dtype,
 	}
 	nrm_set_error("nrm_association_tests_single4_host: internal error (no pass completed)");
 	return NRM_E_DEVICE;
+}
+
+}  // namespace
+
+extern "C" int nrm_association_tests_single4_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const void* h_dc, int c_dtype,
+												   int64_t nc, int64_t n, const double* h_dci, int rank, int dimreduce, int return_dot, double tol, void* h_p,
+												   void* h_stat, void* h_alpha, void* h_varx, void* h_vary, int out_dtype) {
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	return single4_host(h_dx, x_dtype, nx, h_dy, y_dtype, ny, h_dc, c_dtype, nc, n, h_dci, rank, dimreduce, return_dot, tol, h_p, h_stat, h_alpha, h_varx, h_vary,
+						out_dtype, true);
+}
+
+extern "C" int nrm_association_tests_single4_pinv_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const void* h_dc,
+														int c_dtype, int64_t nc, int64_t n, const double* h_dci, int rank, int dimreduce, int return_dot, double tol,
+														void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary, int out_dtype) {
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	return single4_host(h_dx, x_dtype, nx, h_dy, y_dtype, ny, h_dc, c_dtype, nc, n, h_dci, rank, dimreduce, return_dot, tol, h_p, h_stat, h_alpha, h_varx, h_vary,
+						out_dtype, false);
 }

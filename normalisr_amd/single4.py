@@ -14,9 +14,11 @@ exactly the pieces of ONE multiple regression of each gene on all rows of A (SUR
     dof      = n - 1 - (nx + nc - 1) - dimreduce   (association.py:558, rank = nx+nc-1)
 
 so the device does three Gram contractions on the fp64 matrix cores (A A^T, Y A^T, (Y A^T) N) and one sweep.
-If A A^T is rank deficient with respect to the reference's threshold (singular values < tol * largest,
-association.py:77) the per-grouping ranks differ and the reference's own algorithm is followed on the host,
-using the device-computed Gram matrices (slow path, same results).
+Rank-deficient covariates (one-hot batches and an intercept: C C^T of rank rc < nc) keep that closed form on rows residualised with
+inv_rank's pseudo-inverse of C C^T, with rank nx - 1 + rc per grouping (dof = n - nx - rc - dimreduce), whenever every grouping's
+rank is certainly that (pinv_rank_certificate).  Otherwise -- A A^T rank deficient in any other way with respect to the reference's
+threshold (singular values < tol * largest, association.py:77) -- the per-grouping ranks differ and the reference's own algorithm is
+followed on the host, using the device-computed Gram matrices (slow path, same results).
 """
 import logging
 import os
@@ -148,7 +150,8 @@ def _single4_samexy(dx, dc, lowmem, return_dot, dimreduce, ka, eng, out_dtype):
 	covariates (association.py:489-498,506-510,1037-1068).  Full-rank A A^T (A = [dx; dc], N its inverse): the pair (i, j)
 	conditioned on the rest has covariance inv([[N_ii, N_ij], [N_ij, N_jj]]) / n, so
 	    gamma_ij = -N_ij / N_jj,   vary_ij = N_ii / (n det),   R^2_ij = N_ij^2 / (N_ii N_jj),   det = N_ii N_jj - N_ij^2,
-	rank = nx + nc - 2 for every pair.  The reference then forms dot = gamma * vary for i < j, mirrors p, dot and vary
+	rank = nx + nc - 2 for every pair (rank-deficient covariates: N the inverse of M~ = Mxx - Mxc Mcc^+ Mcx, rank nx - 2 + rc, under the
+	certificate of the module header).  The reference then forms dot = gamma * vary for i < j, mirrors p, dot and vary
 	(diagonal of vary = 1) and divides dot by vary again when return_dot is False."""
 	if not lowmem:
 		raise NotImplementedError('alpha for dy=None is not meaningful in the reference (symmetrised) and is not provided.')
@@ -172,17 +175,30 @@ def _single4_samexy(dx, dc, lowmem, return_dot, dimreduce, ka, eng, out_dtype):
 	tol, mpc = ka.get('tol', 1E-8), ka.get('mpc', 0)
 	with _engine.host_blas():
 		ev = np.linalg.eigvalsh(prod)
-		closed = mpc == 0 and ka.get('method', 'auto') in ('auto', 'scipy') and ev[-1] > 0 and ev[0] >= tol * ev[-1] * (1 + 1e-6)
+		may_close = mpc == 0 and ka.get('method', 'auto') in ('auto', 'scipy') and ev[-1] > 0
+		closed = may_close and ev[0] >= tol * ev[-1] * (1 + 1e-6)
+		nij, rank = None, m - 2
 		if closed:
-			ninv = _spd_inverse(prod)
-			d = np.diag(ninv)[:nx]
-			nij = ninv[:nx, :nx]
+			nij = _spd_inverse(prod)[:nx, :nx]
+		elif may_close and nc:
+			# rank-deficient covariates: the same closed form from the design block of the inverse of R (the Gram matrix of [X; a basis of C's
+			# row space]), N~ = M~^-1 with M~ = Mxx - Mxc Mcc^+ Mcx, when every pair's rank is nx - 2 + rc (pinv_rank_certificate)
+			from .association import inv_rank
+			mcc = prod[nx:, nx:]
+			dci, dcr = inv_rank(mcc, tol=tol) if (mcc != 0).any() else (None, 0)
+			if 0 < dcr < nc and _pinv_rank_spectrum(ev, mcc, tol):
+				mt = prod[:nx, :nx] - prod[:nx, nx:] @ dci @ prod[nx:, :nx]
+				nt = _spd_inverse(0.5 * (mt + mt.T))
+				if np.isfinite(nt).all() and (np.diag(nt) > 0).all():
+					nij, rank, closed = nt, nx - 2 + dcr, True
+		if closed:
+			d = np.diag(nij)
 			det = np.outer(d, d) - nij**2
 			with np.errstate(divide='ignore', invalid='ignore'):
 				gam = -nij / d[None, :]
 				vy = d[:, None] / (n * det)
 				r2 = nij**2 / np.outer(d, d)
-			ranks = np.full((nx, nx), m - 2)
+			ranks = np.full((nx, nx), rank)
 		else:
 			logging.info('single=4, dy=None: no closed form (rank-deficient A A^T or truncated inverse); following the per-pair algorithm on the host.')
 			gam, vy, r2, ranks = _pairwise_host(prod, nx, nc, n, dimreduce, eng, ka)
@@ -334,7 +350,7 @@ class Single4Plan:
 	The FIRST step is the public call, association_tests_single4(device_out=True): it decides everything that depends on the design and the
 	covariates alone -- whether the closed form applies (the reference's rank test on A A^T through the norm certificate, association.py:77), whether
 	the design is sparse enough for the entry lists, which start the Newton-Schulz inverse of M~ needs and how many steps.  When that call took the
-	sparse-design closed form with a scalar dimreduce and nothing was handed back (no row near the span of the covariates), every later step on the
+	sparse-design closed form (full-rank or certified rank-deficient covariates) with a scalar dimreduce and nothing was handed back (no row near the span of the covariates), every later step on the
 	same, unwritten tensors is that call's device work and nothing else --
 
 	    k_design_stats, k_de_sparse on the design rows (M~), nrm_spd_* + 2 K2' products per Newton-Schulz step (the count the first call needed),
@@ -399,7 +415,6 @@ class Single4Plan:
 		d_x, d_y, lists, d_c, d_dci, dcr = self.dx, self.dy, self.lists, self.d_c, self.d_dci, self.dcr
 		nx, n = d_x.shape
 		ny, nc = d_y.shape[0], self.dc.shape[0]
-		m = nx + nc
 		flags = self.flags  # [0] non-finite, [1] R^2 out of range (the sweep), [2] rows near the span of the covariates (k_design_stats, k_de_sparse), [5] diagonal of N~
 		rx = de_sparse.design_stats(eng, lists, d_c, d_dci, dcr, nx, nc, flags)
 		nxp = _engine._round_up(nx, _lib.ROW_TILE)
@@ -425,7 +440,7 @@ class Single4Plan:
 		work = torch.empty((ny, ), dtype=torch.float64, device=eng.device)
 		code = _lib.NRM_F64 if tdt == torch.float64 else _lib.NRM_F32
 		with _engine._Span(eng, 'sweep'):
-			_lib.check(eng.lib.nrm_single4_sweep(bt_d.data_ptr(), g_d.data_ptr(), bt_d.stride(0), ssy.data_ptr(), dxx.data_ptr(), nx, ny, nx, n, float(n - m - int(self.dimreduce)),
+			_lib.check(eng.lib.nrm_single4_sweep(bt_d.data_ptr(), g_d.data_ptr(), bt_d.stride(0), ssy.data_ptr(), dxx.data_ptr(), nx, ny, nx, n, float(n - nx - dcr - int(self.dimreduce)),
 												 1 if self.return_dot else 0, p.data_ptr(), stat.data_ptr(), vary.data_ptr(), code, ny, work.data_ptr(), flags.data_ptr(), eng._stream()))
 		return p, stat, varx, vary, res
 
@@ -592,10 +607,12 @@ def association_tests_single4(dx, dy, dc, lowmem=True, return_dot=True, return_s
 			dc64 = np.asarray(dc, dtype=np.float64)
 			mcc = dc64 @ dc64.T
 			dci, dcr = inv_rank(mcc, tol=tol) if nc and (dc64 != 0).any() else (np.zeros((nc, nc)), 0)
-			if dcr == nc:  # (a rank-deficient C C^T is a principal block of A A^T: no closed form then)
+			# Rank-deficient covariates (one-hot batches and an intercept): the closed form on rows residualised with inv_rank's pseudo-inverse is
+			# the reference's result when every grouping's rank is nx - 1 + dcr (pinv_rank_certificate); all-zero covariates keep the host loop
+			if dcr == nc or dcr > 0:
 				try:
 					res, cert = _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, out_dtype, device_out=device_out, mark=mark)
-					closed = _surely_full_rank(cert, mcc, dci, tol)
+					closed = _surely_full_rank(cert[:3], mcc, dci, tol) if dcr == nc else pinv_rank_certificate(*cert, mcc, tol)
 					mark('rank certificate')
 				except (AssertionError, RuntimeError, np.linalg.LinAlgError) as e:  # raised for good only if the closed form applies
 					err = e
@@ -611,10 +628,13 @@ def association_tests_single4(dx, dy, dc, lowmem=True, return_dot=True, return_s
 			prod = prod_d[:m, :m].cpu().numpy()
 			prod = np.triu(prod) + np.triu(prod, 1).T
 			mark('A A^T')
-			if may_close and dcr == nc and (res is not None or err is not None):  # (a rank-deficient C C^T is a principal block of A A^T)
+			if may_close and (res is not None or err is not None):
 				with _engine.host_blas():
 					ev = np.linalg.eigvalsh(prod)
-				closed = ev[-1] > 0 and ev[0] >= tol * ev[-1] * (1 + 1e-6)
+					if dcr == nc:
+						closed = ev[-1] > 0 and ev[0] >= tol * ev[-1] * (1 + 1e-6)
+					else:
+						closed = _pinv_rank_spectrum(ev, mcc, tol)
 		mark.report()
 		if closed:
 			if err is not None:
@@ -636,6 +656,59 @@ def association_tests_single4(dx, dy, dc, lowmem=True, return_dot=True, return_s
 		stat = (gam.T * vx).T if return_dot else gam
 		cast = lambda v: None if v is None else v.astype(out_dtype, copy=False)
 		return (cast(p), cast(stat), cast(alpha), cast(vx), cast(vy))
+
+
+def pinv_rank_certificate(norm_mt, norm_ninv, bx, ss_x, mcc, tol=1E-8):
+	"""True when every grouping's matrix in the reference's loop -- T_i, A A^T without row and column i (association.py:521-530) -- certainly
+	has the rank nx - 1 + rc under the reference's threshold (singular values >= tol x the largest, association.py:77), rc being the rank
+	inv_rank gives C C^T at the same tol.  Then the closed form on rows residualised with that pseudo-inverse (Frisch-Waugh holds for any basis
+	of C's row space) is the reference's result, with dof = n - nx - rc - dimreduce.  Pure numpy, from what the closed form has at hand:
+	    norm_mt = ||M~||_1, norm_ninv = ||N~||_1 (M~ = X~ X~^T, N~ = M~^-1), bx = (nx, nc) coefficients of the design rows on C
+	    (b = Mxc (C C^T)^+), ss_x = |x~_i|^2 (nx,), mcc = C C^T.
+	With Mcc = V diag(lambda) V^T split into kept (V_r, Lambda_r) and dropped (V_0) eigenvectors and eps0 the largest dropped eigenvalue, A A^T
+	in the basis [X; V_r^T C; V_0^T C] is [[R, E], [E^T, D0]]: R the Gram matrix of [X; V_r^T C] (its Schur complement is M~), E = X C^T V_0
+	(||E|| <= ||X||_F sqrt(eps0)), ||D0|| = eps0.
+	  - dropped directions: {(0, V_0 w)} has Rayleigh quotients <= eps0 in every T_i and sigma_max(T_i) >= lambda_max(Mcc): asks for
+	    eps0 <= tol lambda_max(Mcc) / 2;
+	  - kept directions: lambda_{nx-1+rc}(T_i) >= lambda_{nx+rc}(A A^T) >= lambda_min(R) - ||E|| - eps0 (interlacing, Weyl) and
+	    sigma_max(T_i) <= lambda_max(R) + ||E|| + eps0, with lambda_max(R) and 1 / lambda_min(R) bounded as in _surely_full_rank on the
+	    reduced basis (Lambda_r for Mcc, b V_r for b): asks for twice the margin.
+	False means "no certificate" (take the spectrum of A A^T: _pinv_rank_spectrum), never "rank deficient"."""
+	bx = np.asarray(bx, dtype=np.float64).reshape(len(ss_x), -1)
+	mcc = np.asarray(mcc, dtype=np.float64)
+	nc = mcc.shape[0]
+	if nc == 0:
+		return _surely_full_rank((norm_mt, norm_ninv, bx), mcc, None, tol)
+	w, v = np.linalg.eigh(mcc)
+	lam1 = float(w[-1])
+	if not (np.isfinite(w).all() and lam1 > 0):
+		return False
+	keep = w >= tol * lam1  # (inv_rank's rule)
+	wr, vr = w[keep], v[:, keep]
+	eps0 = max(float(w[~keep].max()), 0.0) if (~keep).any() else 0.0
+	if not eps0 <= 0.5 * tol * lam1:
+		return False
+	br = bx @ vr
+	ar = br * wr[None, :]
+	lam_max_r = norm_mt + float((ar * ar).sum()) / wr[0] + wr[-1]
+	inv_norm_r = norm_ninv * (1.0 + float(np.sqrt((br * br).sum())))**2 + 1.0 / wr[0]
+	xf2 = float(np.sum(ss_x)) + float((br * br * wr[None, :]).sum())  # ||X||_F^2 = sum |x~_i|^2 + |b_i C|^2
+	e = float(np.sqrt(max(xf2, 0.0) * eps0))
+	lo, hi = 1.0 / inv_norm_r - e - eps0, lam_max_r + e + eps0
+	return bool(np.isfinite(lo) and np.isfinite(hi) and norm_mt > 0 and norm_ninv > 0 and hi > 0 and lo >= 2.0 * tol * hi)
+
+
+def _pinv_rank_spectrum(ev, mcc, tol=1E-8):
+	"""pinv_rank_certificate from the spectrum of A A^T (ev ascending) instead of the norms: lambda_{nx+rc}(A A^T) >= 2 tol lambda_1(A A^T) and the
+	dropped directions of C C^T below half the threshold.  The same for dy=None's pairs (rank nx - 2 + rc): interlacing skips two rows there."""
+	w = np.linalg.eigvalsh(np.asarray(mcc, dtype=np.float64))
+	lam1 = float(w[-1])
+	if not (np.isfinite(w).all() and lam1 > 0 and ev[-1] > 0):
+		return False
+	keep = w >= tol * lam1
+	eps0 = max(float(w[~keep].max()), 0.0) if (~keep).any() else 0.0
+	nd = int((~keep).sum())
+	return bool(eps0 <= 0.5 * tol * lam1 and ev[nd] >= 2.0 * tol * ev[-1])
 
 
 def _surely_full_rank(cert, mcc, mcc_inv, tol):
@@ -671,8 +744,7 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 	torch = eng.torch
 	nx, n = d_x.shape
 	ny, nc = dy.shape[0], dc64.shape[0]
-	m = nx + nc
-	if n <= m + np.max(dimreduce):
+	if n <= nx + dcr + np.max(dimreduce):  # (rank nx - 1 + dcr per grouping: dof = n - nx - dcr - dimreduce, association.py:558)
 		raise RuntimeError('Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.')
 	ns = 0 if force_f64 else eng.gram_slices(n)
 	with torch.cuda.device(eng.device):
@@ -769,10 +841,10 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 			mark('kappa')
 		dr_groups = [int(dimreduce)] if np.ndim(dimreduce) == 0 else [int(v) for v in np.unique(dimreduce)]
 		p_host = None
-		# dof = n - 1 - (m - 1) - dimreduce (association.py:558): uniform, or one sweep per distinct per-gene dimreduce value
+		# dof = n - 1 - (nx - 1 + dcr) - dimreduce (association.py:558; dcr = nc for full-rank covariates): uniform, or one sweep per distinct per-gene dimreduce value
 		# (gamma and vary do not depend on it; the P-value columns of each group are kept)
 		for dr in dr_groups:
-			args = (bt_d.data_ptr(), g_d.data_ptr(), bt_d.stride(0), ry.ss.data_ptr(), d_dxx.data_ptr(), nx, ny, nx, n, float(n - m - dr),
+			args = (bt_d.data_ptr(), g_d.data_ptr(), bt_d.stride(0), ry.ss.data_ptr(), d_dxx.data_ptr(), nx, ny, nx, n, float(n - nx - dcr - dr),
 					1 if return_dot else 0, p.data_ptr(), stat.data_ptr(), vary.data_ptr(), code, ny, work.data_ptr(), flags.data_ptr())
 			with _engine._Span(eng, 'sweep'):
 				if guard and eng.guard_tol > 0:
@@ -808,7 +880,7 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 			work_s = torch.empty((k, ), dtype=torch.float64, device=eng.device)
 			flags_s = eng.zeros((2, ), torch.int32)
 			_lib.check(eng.lib.nrm_single4_sweep(bt_s.data_ptr(), g_s.data_ptr(), bt_s.stride(0), ry_s.ss.data_ptr(), d_dxx.data_ptr(), nx, k, nx, n,
-												 float(n - m - dr_groups[0]), 1 if return_dot else 0, p_s.data_ptr(), stat_s.data_ptr(), vary_s.data_ptr(), code, k,
+												 float(n - nx - dcr - dr_groups[0]), 1 if return_dot else 0, p_s.data_ptr(), stat_s.data_ptr(), vary_s.data_ptr(), code, k,
 												 work_s.data_ptr(), flags_s.data_ptr(), eng._stream()))
 			eng.check_flags(flags_s)
 			for whole, part in ((p, p_s), (stat, stat_s), (vary, vary_s)):
@@ -830,7 +902,7 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 		vx = dxx.copy()
 		vx[vx == 0] = 1
 		mark('flags')
-		cert = (norm_mt, norm_ninv, rx.coef[:nx].cpu().numpy() if nc else np.zeros((nx, 0)))
+		cert = (norm_mt, norm_ninv, rx.coef[:nx].cpu().numpy() if nc else np.zeros((nx, 0)), rx.ss[:nx].cpu().numpy() if dcr < nc else np.zeros(nx))
 		if device_out and p_host is None:
 			return (p, stat, alpha, vx.astype(out_dtype), vary), cert
 		out = (eng.download(p) if p_host is None else p_host, eng.download(stat), alpha, vx.astype(out_dtype), eng.download(vary))
