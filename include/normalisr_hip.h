@@ -618,6 +618,54 @@ int64_t nrm_tsv_width(int kind);
 int nrm_tsv_format(const void* data, int dtype, int64_t rows, int64_t cols, int64_t ld, int delim, int kind, char* out, int64_t part_cap,
 				   int64_t* lens, int parts);
 
+/*
+ * lcpm and scaling_factor (reference lcpm.py:21-283): Bayesian logCPM from a read-count matrix, the first stage of the pipeline.  With the reference's default
+ * arguments lcpm[g,k] = T[x_gk] - t1[k] with T[x] = psi(1 + x) - psi(sum(x) + 2) and t1[k] = ln sum_g exp(T[x_gk]) - ln 1e6 (lcpm.py:96-160): three streaming
+ * passes over d_x (rows, ld) of integer counts -- dtype NRM_I64, NRM_I32, NRM_I16 or NRM_U8 -- and two tables of (largest count + 1) doubles.
+ *   nrm_lcpm_count:   d_cell_total[k] += sum_g x_gk and d_cell_nnz[k] += #{g: x_gk != 0} (lcpm.py:194-200: the covariates), d_gene_zero[g] += #{k: x_gk == 0}
+ *       (lcpm.py:258: scaling_factor's default variable), d_info[0] = sum(x) (lcpm.py:94), d_info[1] = max(x) (lcpm.py:100), d_info[2] = 1
+ *       for a negative entry (lcpm.py:85-86 raises).  All int64; d_gene_zero zeroed by the caller (integer atomics, exact); the per-cell sums and d_info go
+ *       through d_partial -- one slab per row tile, one record per workgroup -- and are folded in a fixed order (counts below 2^53).
+ *   nrm_lcpm_digamma: HOST: h_psi[x] = psi(1 + x), x = 0 .. xmax, and *h_psi_t0 = psi(t0) (scipy.special.digamma in lcpm.py:96,101-107): -gamma + H_x by
+ *       recurrence below 12, the asymptotic series (after an upward shift) from there.  xmax < nrm_lcpm_table_cap(), NRM_E_ARG beyond.
+ *   nrm_lcpm_colsum:  d_t1[k] = ln sum_g d_exp_table[x_gk] - ln 1e6 (lcpm.py:158; d_exp_table = exp(T): exp once per table entry).  d_partial:
+ *       ceil(rows / nrm_lcpm_row_tile()) x n doubles of scratch: one partial sum per row tile, added in a fixed order (no floating-point atomics).
+ *   nrm_lcpm_write:   d_out[g,k] = d_table[x_gk] - d_t1[k] (lcpm.py:150,159; d_t1 == NULL: normalize=False), out_dtype NRM_F32 / NRM_F64: one rounding.
+ * A count outside [0, table_len) reads the nearest end of the table.
+ */
+#define NRM_I64 16
+#define NRM_I32 17
+#define NRM_U8 18
+#define NRM_I16 19
+int64_t nrm_lcpm_row_tile(void);
+int64_t nrm_lcpm_table_cap(void);
+int64_t nrm_lcpm_count_workspace(int64_t rows, int64_t n);
+int nrm_lcpm_count(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld, int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_gene_zero,
+				   int64_t* d_info /* int64[4] */, int64_t* d_partial /* nrm_lcpm_count_workspace(rows, n) words of scratch */, void* stream);
+int nrm_lcpm_digamma(int64_t xmax, double t0, double* h_psi, double* h_psi_t0);
+int nrm_lcpm_colsum(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld, const double* d_exp_table, int64_t table_len, double* d_partial,
+					double* d_t1, void* stream);
+int nrm_lcpm_write(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld, const double* d_table, int64_t table_len, const double* d_t1, void* d_out,
+				   int out_dtype, int64_t ldo, void* stream);
+
+/*
+ * compute_var (reference norm.py:56-128, `normalisr fitvar`): one iteration of the fit with cell weights u (n) -- all ones in the first, 1 / (fitted scale) of
+ * the previous one after it (norm.py:98-99).  The reference's two regressions are used for their fitted values only, so the first is b_g = M^+ a_g with
+ * M = sum_k u_k^2 C_k C_k^T (its pseudo-inverse d_mi (nc, nc) from the caller: inv_rank) and a_g = sum_k u_k^2 y_gk C_k.  1 <= nc <= 63.
+ *   nrm_fitvar_moments: d_a (rows, nc) = Y Cw^T with d_cw (nc, ldc) = u^2 C                                                       (norm.py:100)
+ *   nrm_fitvar_genes:   d_b (rows, nc) = a M^+;  r_gk = u_k (y_gk - sum_c b_gc C_ck);  d_mean[g] = mean_k r_gk,  d_sc[g] = sqrt(mean_k (r_gk - mean)^2)
+ *       (norm.py:101-107);  d_flags[0] += genes with d_sc == 0 or not finite (the reference divides by it, norm.py:108, and fails norm.py:125)
+ *   nrm_fitvar_cells:   d_v[k] = mean_g ((r_gk - mean_g) / sc_g)^2 (norm.py:108, before its sqrt and log).  d_partial: ceil(rows / nrm_fitvar_row_tile()) x n
+ *       doubles of scratch, one partial sum per row tile, added in a fixed order (no floating-point atomics).
+ * The residual is recomputed in every pass and never stored.
+ */
+int64_t nrm_fitvar_row_tile(void);
+int nrm_fitvar_moments(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_cw, int64_t nc, int64_t ldc, double* d_a, void* stream);
+int nrm_fitvar_genes(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_u, const double* d_c, int64_t nc, int64_t ldc,
+					 const double* d_a, const double* d_mi, double* d_b, double* d_mean, double* d_sc, int32_t* d_flags, void* stream);
+int nrm_fitvar_cells(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_u, const double* d_c, int64_t nc, int64_t ldc,
+					 const double* d_b, const double* d_mean, const double* d_sc, double* d_partial, double* d_v, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

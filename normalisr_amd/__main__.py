@@ -1,14 +1,14 @@
-"""`python -m normalisr_amd <cmd>` / `normalisr <cmd>`: command line of the association hot path.
-Same sub-commands, positionals and flags as the reference CLI for `de` (__main__.py:358-436) and
-`coex` (:442-492), `binnet` (:498-509) and `normvar` (:311-352), global -v (:14-17), help on stderr + exit 1 without arguments (:649-651)."""
+"""`python -m normalisr_amd <cmd>` / `normalisr <cmd>`: command line of the pipeline from read counts to the network.
+Same sub-commands, positionals and flags as the reference CLI for `lcpm` (__main__.py:164-216), `normcov` (:222-245), `fitvar` (:251-272), `normvar` (:311-352),
+`de` (:358-436), `coex` (:442-492) and `binnet` (:498-509), global -v (:14-17), help on stderr + exit 1 without arguments (:649-651)."""
 import argparse
 import logging
 import sys
 
 
 def build_parser():
-	p0 = argparse.ArgumentParser(prog='normalisr', description='Normalisr association testing (DE, co-expression) on AMD MI355X. '
-								 'Only the linear-association sub-commands de and coex are provided by this build.')
+	p0 = argparse.ArgumentParser(prog='normalisr', description='Normalisr on AMD MI355X: normalisation (lcpm, normcov, fitvar, normvar), association testing '
+								 '(de, coex) and network binarisation (binnet).  The quality-control and post-processing sub-commands are not provided by this build.')
 	p0.add_argument('-v', dest='verbose', action='store_true', help='Verbose mode.')
 	sub = p0.add_subparsers(help='sub-commands', dest='cmd')
 
@@ -40,6 +40,27 @@ def build_parser():
 	p.add_argument('--dot_out', dest='dot_out', action='store',
 				   help='Output covariance of gene pairs after covariate removal (inner product / cell count), TSV. Pearson R = dot/sqrt(var_i var_j).')
 	p.add_argument('--gpus', dest='gpus', action='store', type=int, default=1, help='GPUs of this node to shard the problem over (one process per GPU, RCCL); every rank reads only its gene rows of exp_in. Default: 1.')
+	p = sub.add_parser('lcpm', help='Compute Bayesian expectation of logCPM and cellular summary covariates from read counts.')
+	p.add_argument('reads_in', help='Input read-count matrix (genes x cells) without row or column names: TSV if dense (default), Matrix Market (.mtx, .mtx.gz) with -s.')
+	p.add_argument('lcpm_out', help='Output Bayesian logCPM matrix (genes x cells), always dense, TSV.')
+	p.add_argument('scale_out', help='Output vector of the variance-normalisation scaling factor of each gene, TSV.')
+	p.add_argument('cov_out', help='Output matrix of the 3 cellular summary covariates (after the rows of -c, if given), TSV.')
+	p.add_argument('-s', dest='sparse', action='store_true', help='Read reads_in as a sparse Matrix Market (COO) file; needs scipy.')
+	p.add_argument('-r', dest='rseed', action='store', type=int, help='Initial random seed (kept for compatibility; the posterior expectation draws nothing).')
+	p.add_argument('-n', dest='nth', action='store', type=int, default='0', help='Number of CPU cores (kept for compatibility; the GPU path ignores it).')
+	p.add_argument('-c', dest='cov_in', help='Input matrix of existing covariates (covariates x cells), TSV; the new covariates are appended after them in cov_out.')
+	p.add_argument('--var_out', help='Output matrix of the variance of the posterior distribution of logCPM (genes x cells), TSV.')
+
+	p = sub.add_parser('normcov', help='Normalize continuous covariates and include constant 1 covariate as intercept.')
+	p.add_argument('cov_in', help='Input covariate matrix (covariates x cells), TSV; can be cov_out of lcpm.')
+	p.add_argument('cov_out', help='Output matrix of normalized covariates, same format.')
+	p.add_argument('--no1', dest='no1', action='store_true', default=False, help='Do not add the constant 1 covariate (only if this is not the last normcov step).')
+
+	p = sub.add_parser('fitvar', help='Fit lognormal distribution of variance with covariates.')
+	p.add_argument('lcpm_in', help='Input Bayesian logCPM matrix (genes x cells), TSV.')
+	p.add_argument('cov_in', help='Input covariate matrix (covariates x cells), TSV.')
+	p.add_argument('weights_out', help='Output vector of the fitted weight (variance**-0.5) of each cell, TSV.')
+
 	p = sub.add_parser('normvar', help='Normalize variances of gene expressions and covariates.')
 	p.add_argument('lcpm_in', help='Input Bayesian logCPM matrix (genes x cells), TSV.')
 	p.add_argument('weights_in', help='Input vector of the fitted weight of each cell, TSV.')

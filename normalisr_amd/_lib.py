@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(HERE, 'libnormalisr_hip.so')
 
 NRM_F32, NRM_F64 = 0, 1
 NRM_TSV_I64, NRM_TSV_I32, NRM_TSV_U8 = 16, 17, 18  # integer dtypes of nrm_tsv_format
+NRM_I64, NRM_I32, NRM_U8, NRM_I16 = 16, 17, 18, 19  # count dtypes of nrm_lcpm_*
 NRM_S1_COMMON, NRM_S1_SKIP = -2, -1  # cell codes of nrm_single1_stream (include/normalisr_hip.h)
 DESIGN_NOTONE, DESIGN_NEG, DESIGN_GT1, DESIGN_HAS1, DESIGN_NAN = 1, 2, 4, 8, 16  # bits of nrm_design_count's d_info[2]
 NRM_E_ARG, NRM_E_DEVICE, NRM_E_NUMERIC, NRM_E_UNSUPPORTED = -1, -2, -3, -4
@@ -116,6 +117,17 @@ _SIGNATURES = {
 	'nrm_small_eigvals': ([_vp, _i64, _vp], _i32),
 	'nrm_association_tests_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32,
 									_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32], _i32),
+	'nrm_lcpm_row_tile': ([], _i64),
+	'nrm_lcpm_table_cap': ([], _i64),
+	'nrm_lcpm_count_workspace': ([_i64, _i64], _i64),
+	'nrm_lcpm_count': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_lcpm_digamma': ([_i64, _dbl, _vp, _vp], _i32),
+	'nrm_lcpm_colsum': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp], _i32),
+	'nrm_lcpm_write': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _vp], _i32),
+	'nrm_fitvar_row_tile': ([], _i64),
+	'nrm_fitvar_moments': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _i32),
+	'nrm_fitvar_genes': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_fitvar_cells': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 }
 
 _lib = None

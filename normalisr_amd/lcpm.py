@@ -1,0 +1,226 @@
+"""Bayesian logCPM and the variance-normalisation scaling factor (mirror of the reference's lcpm.lcpm / lcpm.scaling_factor, lcpm.py:21-283) on the device.
+
+With varscale == 0 the posterior expectation is a function of the count alone, so lcpm is a table lookup,
+    lcpm[g,k] = T[reads[g,k]] - t1[k],    T[x] = psi(1 + x) - psi(sum(reads) + 2),    t1[k] = ln sum_g exp(T[reads[g,k]]) - ln 1e6 ,
+and csrc/nrm_lcpm.hip streams the count matrix three times: integer totals (which are also the covariates and scaling_factor's zero counts),
+the per-cell sums of exp(T) from a second table, and the pass that writes the result.  The tables come from the library's own digamma
+(nrm_lcpm_digamma: no scipy on this path).  Counts up to nrm_lcpm_table_cap() - 1 (2**24 - 1); NotImplementedError beyond."""
+import ctypes
+import logging
+
+import numpy as np
+
+from . import _lib
+from . import engine as _engine
+
+_WARN_LCPM = "Modifying keyword arguments other than nth or seed is neither recommended nor supported for function 'lcpm'. Do so at your own risk."
+_WARN_SF = "Modifying keyword arguments is neither recommended nor supported for function 'scaling_factor'. Do so at your own risk."
+
+
+def _is_dev(a):
+	return hasattr(a, 'is_cuda') and a.is_cuda
+
+
+def _is_sparse(a):
+	try:
+		import scipy.sparse
+	except ImportError:
+		return False
+	return scipy.sparse.issparse(a)
+
+
+def digamma_table(xmax, t0):
+	"""(psi(1 + x) for x = 0 .. xmax, psi(t0)) from the library (host code: csrc/nrm_lcpm.hip)."""
+	xmax = int(xmax)
+	if xmax >= int(_lib.load().nrm_lcpm_table_cap()):
+		raise NotImplementedError('lcpm on the device tabulates psi(1 + count) for counts below {}; the largest count here is {}.'.format(
+			int(_lib.load().nrm_lcpm_table_cap()), xmax))
+	psi = np.empty(xmax + 1, dtype=np.float64)
+	psi_t0 = ctypes.c_double()
+	_lib.check(_lib.load().nrm_lcpm_digamma(xmax, float(t0), psi.ctypes.data, ctypes.addressof(psi_t0)))
+	return psi, psi_t0.value
+
+
+def _host_counts(d):
+	"""A host count matrix as a C-contiguous int32 / int64 array: (array, has a negative entry).  Floats hold integer values (lcpm.py:138-139 casts them)."""
+	d = np.asarray(d)
+	if d.dtype == np.bool_:
+		d = d.astype(np.int32)
+	if d.dtype.kind not in 'iuf':
+		raise TypeError('reads must be an integer (or integer-valued floating-point) matrix.')
+	neg = bool(d.size and d.dtype.kind != 'u' and d.min() < 0)
+	if d.dtype.kind == 'f' or d.dtype.itemsize > 4 or d.dtype == np.uint32:
+		big = bool(d.size) and d.max() > np.iinfo(np.int32).max
+		d = d.astype(np.int64 if big else np.int32)
+	elif d.dtype != np.int32:
+		d = d.astype(np.int32)
+	return np.ascontiguousarray(d), neg
+
+
+_CODES = {'torch.int64': _lib.NRM_I64, 'torch.int32': _lib.NRM_I32, 'torch.int16': _lib.NRM_I16, 'torch.uint8': _lib.NRM_U8}
+
+
+def _device_counts(eng, d):
+	"""The count matrix in HBM with unit column stride and a dtype the kernels read: (tensor, dtype code, has a negative entry on the host side)."""
+	torch = eng.torch
+	neg = False
+	if not _is_dev(d):
+		if _is_sparse(d):
+			neg = bool(d.data.size and d.data.min() < 0)
+			d = d.toarray()  # (densified on the host, as lcpm.py:134-137 does)
+		d, neg2 = _host_counts(d)
+		neg = neg or neg2
+		d = eng.upload(d)
+	else:
+		if d.dtype in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+			neg = bool((d < 0).any().item())
+			d = d.to(torch.int64)
+		elif str(d.dtype) not in _CODES:
+			d = d.to(torch.int32 if d.dtype in (torch.int8, torch.bool) else torch.int64)
+		if d.stride(1) != 1:
+			d = d.contiguous()
+	return d, _CODES[str(d.dtype)], neg
+
+
+class _Counts:
+	"""The integer pass over a count matrix (nrm_lcpm_count): per-cell totals and non-zero counts, per-gene zero counts, grand total, maximum, negative flag."""
+
+	def __init__(self, eng, d, code):
+		torch = eng.torch
+		nt, ns = d.shape
+		buf = eng.zeros((2 * ns + nt + 4, ), torch.int64)
+		self.cell_total, self.cell_nnz, self.gene_zero, self.info = buf[:ns], buf[ns:2 * ns], buf[2 * ns:2 * ns + nt], buf[2 * ns + nt:]
+		part = torch.empty((int(eng.lib.nrm_lcpm_count_workspace(nt, ns)), ), dtype=torch.int64, device=eng.device)
+		_lib.check(eng.lib.nrm_lcpm_count(d.data_ptr(), code, nt, ns, d.stride(0), self.cell_total.data_ptr(), self.cell_nnz.data_ptr(), self.gene_zero.data_ptr(),
+										  self.info.data_ptr(), part.data_ptr(), eng._stream()))
+		h = buf.cpu().numpy()  # (one small read-back: 2 n_cell + n_gene + 4 integers)
+		self.h_cell_total, self.h_cell_nnz, self.h_gene_zero = h[:ns], h[ns:2 * ns], h[2 * ns:2 * ns + nt]
+		self.total, self.max, self.negative = int(h[-4]), int(h[-3]), bool(h[-2])
+
+
+def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=True, nocov=False, device_out=False, out_dtype=None):
+	"""Bayesian logCPM from raw read counts, same contract as reference lcpm.py:21-208: returns (lcpm, mean, var, cov).
+	reads: (n_gene, n_cell) counts -- a numpy array of any integer dtype (or floats holding integers), a scipy.sparse matrix (densified on the host) or a torch
+	CUDA integer tensor already in HBM.  nth and seed are accepted for compatibility and ignored.  varscale != 0 resamples from numpy's global random stream in
+	the reference and is not provided: NotImplementedError.
+	out_dtype: None / numpy.float64 (the reference's) or numpy.float32 (the fp64 value rounded once, at the store).  device_out=True leaves lcpm (and mean, var)
+	in HBM as torch tensors -- what compute_var and normvar take next; cov is always a (3, n_cell) numpy array (None with nocov)."""
+	d = reads
+	if d.ndim != 2:
+		raise ValueError('reads must have 2 dimensions.')
+	if varscale < 0:
+		raise ValueError('varscale must be non-negative.')
+	otype = np.dtype(np.float64 if out_dtype is None else out_dtype)
+	if otype not in (np.dtype(np.float32), np.dtype(np.float64)):
+		raise ValueError('out_dtype must be numpy.float32 or numpy.float64.')
+	if not _is_dev(d) and not _is_sparse(d):
+		d, neg = _host_counts(d)
+		if neg:
+			raise ValueError('Negative value in d detected.')
+	elif _is_sparse(d) and d.data.size and d.data.min() < 0:
+		raise ValueError('Negative value in d detected.')
+	if not normalize or ntot is not None or varscale != 0:
+		logging.warning(_WARN_LCPM)
+	if varscale != 0:
+		raise NotImplementedError('lcpm with varscale != 0 draws its resampling noise from numpy\'s global random stream (lcpm.py:126-127); '
+								  'only the posterior expectation (varscale=0) is provided on the device.')
+	nt, ns = d.shape
+	if ntot is None:
+		assert nt * ns > 0  # t0 > 2 (lcpm.py:95): an empty matrix has no reads
+	else:
+		assert ntot + 2 > 2
+		if nt * ns == 0:
+			raise ValueError('reads must not be empty.')
+	eng = _engine.get_engine(d.device.index if _is_dev(d) else None)
+	with eng.lock:
+		torch = eng.torch
+		with torch.cuda.device(eng.device):
+			x, code, neg = _device_counts(eng, d)
+			if neg:
+				raise ValueError('Negative value in d detected.')
+			cnt = _Counts(eng, x, code)
+			if cnt.negative:
+				raise ValueError('Negative value in d detected.')
+			t0 = cnt.total + 2 if ntot is None else ntot + 2
+			assert t0 > 2
+			psi, psi_t0 = digamma_table(cnt.max, t0)
+			tab = psi - psi_t0  # T[x] (lcpm.py:107)
+			d_tab = eng.upload(tab)
+			d_t1 = None
+			if normalize:
+				d_exp = eng.upload(np.exp(tab))  # exp() once per table entry: the per-cell sums of lcpm.py:158 are sums of table entries
+				tiles = -(-nt // int(eng.lib.nrm_lcpm_row_tile()))
+				part = torch.empty((tiles, ns), dtype=torch.float64, device=eng.device)
+				d_t1 = torch.empty((ns, ), dtype=torch.float64, device=eng.device)
+				with _engine._Span(eng, 'lcpm_colsum'):
+					_lib.check(eng.lib.nrm_lcpm_colsum(x.data_ptr(), code, nt, ns, x.stride(0), d_exp.data_ptr(), tab.size, part.data_ptr(), d_t1.data_ptr(), eng._stream()))
+			out = torch.empty((nt, ns), dtype=torch.float64 if otype == np.float64 else torch.float32, device=eng.device)
+			with _engine._Span(eng, 'lcpm_write'):
+				_lib.check(eng.lib.nrm_lcpm_write(x.data_ptr(), code, nt, ns, x.stride(0), d_tab.data_ptr(), tab.size, 0 if d_t1 is None else d_t1.data_ptr(), out.data_ptr(),
+												  _lib.NRM_F64 if otype == np.float64 else _lib.NRM_F32, out.stride(0), eng._stream()))
+			if nocov:
+				dcov = None
+			else:
+				if (cnt.h_cell_total == 0).any():
+					raise ValueError('Found cell with no read at all. Please remove.')
+				t1 = np.log(cnt.h_cell_total)
+				dcov = np.array([t1, nt - cnt.h_cell_nnz, t1**2])
+				assert dcov.shape == (3, ns) and np.isfinite(dcov).all()
+			# every table entry is finite, so is every per-cell sum of positive entries: the reference's isfinite assertions (lcpm.py:203-206) hold by construction
+			assert np.isfinite(tab).all()
+			dtn = out if device_out else eng.download(out)
+			if lowmem:
+				dmean = dvar = None
+			elif device_out:
+				dmean, dvar = out.clone(), eng.zeros((nt, ns), out.dtype)  # (varscale == 0: the mean is the estimate, its variance scaled by 0: lcpm.py:176,184-186)
+			else:
+				dmean, dvar = dtn.copy(), np.zeros((nt, ns), dtype=otype)
+	return (dtn, dmean, dvar, dcov)
+
+
+def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
+	"""Scaling factor of variance normalisation for every gene, same contract as reference lcpm.py:211-283.
+	dt: the read-count matrix, a numpy array or a torch CUDA integer tensor.  The default variable (the share of zero entries per gene) is counted on the
+	device (nrm_lcpm_count); the other four are whole-matrix numpy expressions and run on the host."""
+	if dt.ndim != 2:
+		raise ValueError('dt must have 2 dimensions.')
+	if v0 != 0 or v1 != 'max' or varname != 'nt0mean':
+		logging.warning(_WARN_SF)
+	if varname not in ('logtpropmean', 'logtmeanprop', 'nt0mean', 'lognt0mean', 'log1-nt0mean'):
+		raise ValueError('Unknown varname: {}'.format(varname))
+	if varname == 'nt0mean':
+		eng = _engine.get_engine(dt.device.index if _is_dev(dt) else None)
+		with eng.lock, eng.torch.cuda.device(eng.device):
+			x, code, _ = _device_counts(eng, dt)
+			zeros = _Counts(eng, x, code).h_gene_zero
+		d = zeros / float(dt.shape[1])  # (dt == 0).mean(axis=1)
+	else:
+		h = dt.cpu().numpy() if _is_dev(dt) else (dt.toarray() if _is_sparse(dt) else np.asarray(dt))
+		with np.errstate(divide='ignore', invalid='ignore'):
+			if varname == 'logtpropmean':
+				d = h.mean(axis=1)
+				d = np.log(d / d.sum())
+			elif varname == 'logtmeanprop':
+				d = h / h.sum(axis=0)
+				d = np.log(d.mean(axis=1))
+			elif varname == 'lognt0mean':
+				d = np.log((h == 0).mean(axis=1))
+			else:
+				d = np.log(1 - (h == 0).mean(axis=1))
+	ans = []
+	for v in [v0, v1]:
+		if isinstance(v, str) and v == 'max':
+			ans.append(d.max())
+		elif isinstance(v, str) and v == 'min':
+			ans.append(d.min())
+		else:
+			ans.append(float(v))
+	v0, v1 = ans
+	assert v1 != v0
+	ans = (d - v0) / (v1 - v0)
+	assert ans.shape == (dt.shape[0], )
+	assert np.isfinite(ans).all()
+	return ans
+
+
+assert __name__ != "__main__"

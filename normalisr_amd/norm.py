@@ -6,7 +6,12 @@ Gram matrices and moment vectors are rows of two Gram contractions on the fp64 m
     M_g = sum_k e_gk^2 C_k C_k^T = (U P^T)_g        a_g = sum_k e_gk^2 y_gk C_k = (V C^T)_g ,
 with U = e^2, V = e^2 y, P = the pairwise products of covariate rows; the pseudo-inverses (integer ranks) are a
 batched SVD on the host, and two HBM-bound element-wise kernels (csrc/nrm_normvar.hip) do the rest.
-Only normvar / normvar1 are provided from the reference's norm module (normcov, compute_var are out of scope)."""
+
+normcov (norm.py:4-53) standardises the continuous covariate rows: a (covariates, cells) matrix, numpy on the host.
+compute_var (norm.py:56-128) fits the per-cell weights normvar takes: the reference's two regressions are used for their fitted values only, so
+each iteration is two orthogonal projections -- the gene rows onto the weighted covariates, in three streaming passes of csrc/nrm_fitvar.hip that
+never store the residual, and the per-cell log-RMS onto span(covariates, 1), O(cells x covariates) on the host."""
+import logging
 import os
 
 import numpy as np
@@ -275,6 +280,112 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 			assert _finite_within(dextran)
 			ans.append(dextran)
 		return ans
+
+
+def normcov(dc, c=True):
+	"""Standardise every continuous covariate to zero mean and unit variance and (c=True) append the constant-1 row, same contract as reference norm.py:4-53.
+	Rows holding only 0 and 1 (one-hot categories) are left as they are.  Host numpy: the matrix is (n_cov, n_cell)."""
+	import warnings
+	assert dc is not None
+	dc = dc.cpu().numpy() if _is_dev(dc) else np.asarray(dc)
+	if dc.ndim != 2:
+		raise ValueError('Covariates must have 2 dimensions.')
+	ns = dc.shape[1]
+	if dc.shape[0] == 0:
+		return np.ones((1, ns)) if c else dc
+	if ns == 0 or (dc == dc[:, :1]).all(axis=1).any():
+		raise ValueError('Detected constant covariate. Please only provide full-rank covariate without constant covariate.')
+	cont = ((dc != 0) & (dc != 1)).any(axis=1)
+	out = dc.copy()
+	if cont.any():
+		mean = dc[cont].mean(axis=1)
+		dev = dc[cont].T - mean
+		sd = np.sqrt((dev**2).mean(axis=0))
+		with np.errstate(divide='ignore', invalid='ignore'):
+			near = sd.min() < 1E-50 or np.abs(sd / mean).min() < 1E-6
+		if near:
+			warnings.warn('Detected near constant covariate. Results may be error-prone.', RuntimeWarning)
+		out[cont] = (dev / sd).T
+	if c:
+		out = np.concatenate([out, np.ones((1, ns))], axis=0)
+	return out
+
+
+def _projector(x):
+	"""x^T (x x^T)^+ x for x (rows, cells): the fitted values of a least-squares regression on the rows of x, whatever their rank."""
+	mi, r = inv_rank(np.matmul(x, x.T))
+	return lambda z: np.matmul(np.matmul(mi, np.matmul(x, z)), x)
+
+
+def compute_var(dt, dc, stepmax=1, eps=1E-6):
+	"""Variance-normalisation multiplier of every cell, same contract as reference norm.py:56-128 (`normalisr fitvar`): returns (n_cell,) weights >= 1.
+	dt: (n_gene, n_cell) logCPM, fp32 or fp64, a numpy array or a torch CUDA tensor already in HBM (lcpm(..., device_out=True)); dc (n_cov, n_cell), 1 to 63
+	rows, rank-deficient sets included (both projections take the pseudo-inverse of inv_rank).  AssertionError for a gene whose residual is constant (the
+	reference divides by its zero spread, norm.py:108, and fails norm.py:125)."""
+	if eps <= 0 or stepmax <= 0:
+		raise ValueError('eps and stepmax must be positive.')
+	if not _is_dev(dt):
+		dt = np.asarray(dt)
+	dc = dc.cpu().numpy() if _is_dev(dc) else np.asarray(dc)
+	if dt.ndim != 2 or dc.ndim != 2:
+		raise ValueError('dt and dc must both have 2 dimensions.')
+	if dt.shape[1] != dc.shape[1]:
+		raise ValueError('dt and dc must have the same cell count.')
+	nt, ns = dt.shape
+	nc = dc.shape[0]
+	if nc == 0 or nc > 63:
+		raise NotImplementedError('compute_var on the device takes 1 to 63 covariates.')
+	if nt == 0 or ns == 0:
+		raise ValueError('dt must not be empty.')
+	c64 = np.ascontiguousarray(dc, dtype=np.float64)
+	fit_log = _projector(np.concatenate([c64, np.ones((1, ns))], axis=0))  # the second regression has an intercept (norm.py:92,109-110)
+	eng = _engine.get_engine(dt.device.index if _is_dev(dt) else None)
+	with eng.lock:
+		torch = eng.torch
+		with torch.cuda.device(eng.device):
+			y = dt if _is_dev(dt) else eng.upload(_engine.as_input(dt))
+			if y.dtype not in (torch.float32, torch.float64):
+				y = y.to(torch.float64)
+			if y.stride(1) != 1:
+				y = y.contiguous()
+			ycode = _lib.NRM_F64 if y.dtype == torch.float64 else _lib.NRM_F32
+			d_c = eng.upload(c64)
+			f64 = dict(dtype=torch.float64, device=eng.device)
+			d_a, d_b = torch.empty((nt, nc), **f64), torch.empty((nt, nc), **f64)
+			d_mean, d_sc, d_v = torch.empty((nt, ), **f64), torch.empty((nt, ), **f64), torch.empty((ns, ), **f64)
+			part = torch.empty((-(-nt // int(eng.lib.nrm_fitvar_row_tile())), ns), **f64)
+			flags = eng.zeros((4, ), torch.int32)
+			scale = np.ones(ns)
+			best, bestv, n = None, 1E300, 0
+			while n < stepmax and bestv > eps:
+				u = 1 / scale
+				cu = c64 * u
+				mi, r = inv_rank(np.matmul(cu, cu.T))
+				d_u, d_cw, d_mi = eng.upload(u), eng.upload(cu * u), eng.upload(np.ascontiguousarray(mi, dtype=np.float64))
+				with _engine._Span(eng, 'fitvar'):
+					_lib.check(eng.lib.nrm_fitvar_moments(y.data_ptr(), ycode, nt, ns, y.stride(0), d_cw.data_ptr(), nc, d_cw.stride(0), d_a.data_ptr(), eng._stream()))
+					_lib.check(eng.lib.nrm_fitvar_genes(y.data_ptr(), ycode, nt, ns, y.stride(0), d_u.data_ptr(), d_c.data_ptr(), nc, d_c.stride(0), d_a.data_ptr(),
+														d_mi.data_ptr(), d_b.data_ptr(), d_mean.data_ptr(), d_sc.data_ptr(), flags.data_ptr(), eng._stream()))
+					_lib.check(eng.lib.nrm_fitvar_cells(y.data_ptr(), ycode, nt, ns, y.stride(0), d_u.data_ptr(), d_c.data_ptr(), nc, d_c.stride(0), d_b.data_ptr(),
+														d_mean.data_ptr(), d_sc.data_ptr(), part.data_ptr(), d_v.data_ptr(), eng._stream()))
+				v = d_v.cpu().numpy()
+				assert not flags.cpu().numpy()[0]  # a gene whose residual is constant: its spread divides (norm.py:108), the result is not finite (norm.py:125)
+				with np.errstate(divide='ignore', invalid='ignore'):
+					new = np.exp(fit_log(np.log(np.sqrt(v)))) * scale
+					new /= new.min()
+					t1 = np.abs((new - scale) / scale).max()
+				scale = new
+				n += 1
+				if t1 < bestv:
+					bestv, best = t1, scale
+				logging.debug('Step {}, maximum relative difference: {}'.format(n, t1))
+	assert best is not None
+	w = 1 / best.astype(float, copy=False)
+	w /= w.min()
+	assert w.shape == (ns, )
+	assert np.isfinite(w).all()
+	assert (w > 0).all()
+	return w
 
 
 

@@ -1,17 +1,18 @@
 """User API facade: `import normalisr_amd.normalisr as norm` (reference normalisr.py:3-9).
-Only the linear-association hot path (de, coex) its direct consumer binnet and its direct producer normvar are provided; the reference's pre/post-processing
-steps (qc_reads, lcpm, normcov, gotop, ...) are outside this build's scope."""
+The pipeline from read counts to the network is provided: lcpm (+ scaling_factor) -> normcov -> compute_var -> normvar -> de / coex -> binnet.  The reference's
+quality-control and post-processing steps (qc_reads, qc_outlier, gotop, pccovt) are outside this build's scope."""
 from .de import de
 from .coex import coex
 from .binnet import binnet
-from .norm import normvar
+from .norm import normvar, normcov, compute_var
+from .lcpm import lcpm, scaling_factor
 
-_OUT_OF_SCOPE = ('qc_reads', 'qc_outlier', 'lcpm', 'scaling_factor', 'normcov', 'compute_var', 'gotop', 'pccovt')
+_OUT_OF_SCOPE = ('qc_reads', 'qc_outlier', 'gotop', 'pccovt')
 
 
 def __getattr__(name):
 	if name in _OUT_OF_SCOPE:
-		raise NotImplementedError('normalisr_amd only provides the association hot path (de, coex); '
+		raise NotImplementedError('normalisr_amd provides the pipeline from lcpm to binnet; '
 								  '{} is not part of this build.'.format(name))
 	raise AttributeError(name)
 

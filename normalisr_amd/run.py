@@ -1,4 +1,4 @@
-"""Command runners and matrix IO behind `normalisr de | coex | binnet | normvar`.
+"""Command runners and matrix IO behind `normalisr lcpm | normcov | fitvar | normvar | de | coex | binnet`.
 
 Every sub-command is one row of COMMANDS: which files are read (and how they are shaped), which command-line
 options become which keyword arguments, which function runs, and which of its results go to which file.
@@ -153,6 +153,12 @@ def _flat_alpha(a):
 	return a.reshape(a.shape[0], -1)  # (predictor, gene * covariate), row-major
 
 
+def _nth(v):
+	if int(v) < 0:
+		raise ValueError('Parameter nth must be non-negative.')
+	return int(v)
+
+
 def _call_de(m, ka):
 	from .de import de
 	return de(m['design_in'], m['exp_in'], m['cov_in'], **ka)
@@ -166,6 +172,47 @@ def _call_coex(m, ka):
 def _call_normvar(m, ka):
 	from .norm import normvar
 	return normvar(m['lcpm_in'], m['cov_in'], m['weights_in'].ravel(), m['scale_in'].ravel(), **ka)
+
+
+def _call_normcov(m, ka):
+	from .norm import normcov
+	return (normcov(m['cov_in'], **ka), )
+
+
+def _call_fitvar(m, ka):
+	from .norm import compute_var
+	return (compute_var(m['lcpm_in'], m['cov_in']), )
+
+
+def file_read_coo(f):
+	"""Sparse count matrix from a Matrix Market file (.mtx, .mtx.gz), as the reference reads it for `lcpm -s` (run.py:37-43)."""
+	try:
+		from scipy.io import mmread
+	except ImportError:
+		raise RuntimeError('normalisr lcpm -s reads Matrix Market files through scipy.io.mmread, and scipy is not installed; convert the matrix to a dense TSV '
+						   '(or .npy) file, or install scipy.')
+	logging.debug('Start reading file ' + f)
+	ans = mmread(f)
+	logging.debug('Finish reading file ' + f)
+	return ans
+
+
+def _call_lcpm(m, ka):
+	"""lcpm and scaling_factor on one upload of the counts; the covariates of -c come first in cov_out (run.py:153-189)."""
+	from .lcpm import lcpm, scaling_factor
+	from . import engine as _engine
+	d = m['reads_in']
+	if hasattr(d, 'toarray'):
+		d = d.toarray()
+	d = np.asarray(d)
+	if d.dtype.kind == 'f':
+		d = d.astype(np.int64)  # the reference reads the file with dtype=int (run.py:157-159)
+	eng = _engine.get_engine()
+	x = eng.upload(d if d.dtype in (np.int32, np.int64) else d.astype(np.int64))
+	ans = lcpm(x, **ka)
+	sf = scaling_factor(x)
+	cov = ans[3] if m.get('cov_in') is None else np.concatenate([m['cov_in'], ans[3]], axis=0)
+	return (ans[0], sf, cov, ans[2])
 
 
 def _call_binnet(m, ka):
@@ -188,6 +235,11 @@ COMMANDS = {
 	'normvar': dict(inputs=('lcpm_in', 'cov_in', 'weights_in', 'scale_in'), options=dict(nth=('nth', int), bs=('bs', int)), call=_call_normvar,
 					outputs=dict(exp_out=(0, None, fmt_float), cov_out=(1, None, fmt_float))),
 	'binnet': dict(inputs=('pv_in', ), options=dict(qcut=('qcut', float)), call=_call_binnet, outputs=dict(net_out=(0, None, fmt_int))),
+	# the reference passes var=None to its writer when --var_out is given (lowmem stays True, run.py:175,188-189) and fails: asking for the file asks for lowmem=False
+	'lcpm': dict(inputs=('reads_in', 'cov_in'), options=dict(nth=('nth', _nth), rseed=('seed', int), var_out=('lowmem', lambda name: False)), call=_call_lcpm,
+				 outputs=dict(lcpm_out=(0, None, fmt_float), cov_out=(2, None, fmt_float), scale_out=(1, None, fmt_float), var_out=(3, None, fmt_float))),
+	'normcov': dict(inputs=('cov_in', ), options=dict(no1=('c', lambda no1: not no1)), call=_call_normcov, outputs=dict(cov_out=(0, None, fmt_float))),
+	'fitvar': dict(inputs=('lcpm_in', 'cov_in'), options={}, call=_call_fitvar, outputs=dict(weights_out=(0, None, fmt_float))),
 }
 
 
@@ -208,7 +260,14 @@ def run(cmd, args):
 
 
 def _run(cmd, spec, args):
-	mats = {k: file_read_tsv(args[k]) for k in spec['inputs']}
+	mats = {}
+	for k in spec['inputs']:
+		if args.get(k) is None:
+			mats[k] = None  # (an optional input: lcpm's -c)
+		elif cmd == 'lcpm' and k == 'reads_in' and args.get('sparse'):
+			mats[k] = file_read_coo(args[k])
+		else:
+			mats[k] = file_read_tsv(args[k])
 	ka = {}
 	for key, (kw, conv) in spec['options'].items():
 		if args.get(key) is not None:
@@ -229,6 +288,6 @@ def _runner(cmd):
 	return f
 
 
-de, coex, normvar, binnet = (_runner(c) for c in ('de', 'coex', 'normvar', 'binnet'))  # module-level entry points, as in the reference's run module
+de, coex, normvar, binnet, lcpm, normcov, fitvar = (_runner(c) for c in ('de', 'coex', 'normvar', 'binnet', 'lcpm', 'normcov', 'fitvar'))  # module-level entry points, as in the reference's run module
 
 assert __name__ != "__main__"
