@@ -649,6 +649,29 @@ int nrm_lcpm_write(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t 
 				   int out_dtype, int64_t ldo, void* stream);
 
 /*
+ * The same three passes over a SPARSE count matrix (the reference accepts scipy.sparse input, lcpm.py:118-137, and densifies it; these never form the dense
+ * counts): canonical CSR over genes -- d_indptr int64[rows + 1] from 0 to nnz, d_indices int32[nnz] (the cell; strictly increasing inside a row), d_data[nnz]
+ * of dtype NRM_I64 / NRM_I32 / NRM_I16 / NRM_U8; stored zeros are legal and count as zeros.  Outputs and layouts as the dense entries'.
+ *   nrm_lcpm_csr_count:  d_cell_total, d_cell_nnz, d_info[0..2] as nrm_lcpm_count (lcpm.py:94,100,85-86,194-200); d_gene_zero[g] = n - #{stored entries of g
+ *       that are not 0} (lcpm.py:258; written, not added to).  d_info[3] = 1 for a malformed matrix: a column outside [0, n), a row whose columns do not
+ *       strictly increase, d_indptr not 0 = p[0] <= ... <= p[rows] = nnz.  No entry reads or writes out of bounds for such a matrix (indptr is clamped, a
+ *       column outside its chunk is skipped); its results mean nothing.  d_partial: nrm_lcpm_csr_workspace(rows, n) int64 words of scratch.
+ *   nrm_lcpm_csr_colsum: d_t1[k] = ln(rows * E[0] + sum over the stored entries of cell k of (E[x] - E[0])) - ln 1e6 (lcpm.py:158), E = d_exp_table.  The
+ *       terms are added as 64-bit fixed-point integers (exact, in any order: the same bits every run; no floating-point atomics), scaled per cell by the
+ *       power of two that puts d_cell_total[k] * unit below 2^62; unit = max over x >= 1 of (E[x] - E[0]) / x.  d_cell_total from nrm_lcpm_csr_count;
+ *       d_partial as there.
+ *   nrm_lcpm_csr_write:  d_out[g,k] = d_table[x_gk] - d_t1[k] for every cell, d_table[0] - d_t1[k] where nothing is stored (lcpm.py:150,159); each element
+ *       stored once.  d_t1 == NULL: normalize=False.  out_dtype NRM_F32 / NRM_F64: one rounding.
+ */
+int64_t nrm_lcpm_csr_workspace(int64_t rows, int64_t n);
+int nrm_lcpm_csr_count(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
+					   int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_gene_zero, int64_t* d_info /* int64[4] */, int64_t* d_partial, void* stream);
+int nrm_lcpm_csr_colsum(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
+						const double* d_exp_table, int64_t table_len, double unit, const int64_t* d_cell_total, int64_t* d_partial, double* d_t1, void* stream);
+int nrm_lcpm_csr_write(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
+					   const double* d_table, int64_t table_len, const double* d_t1, void* d_out, int out_dtype, int64_t ldo, void* stream);
+
+/*
  * compute_var (reference norm.py:56-128, `normalisr fitvar`): one iteration of the fit with cell weights u (n) -- all ones in the first, 1 / (fitted scale) of
  * the previous one after it (norm.py:98-99).  The reference's two regressions are used for their fitted values only, so the first is b_g = M^+ a_g with
  * M = sum_k u_k^2 C_k C_k^T (its pseudo-inverse d_mi (nc, nc) from the caller: inv_rank) and a_g = sum_k u_k^2 y_gk C_k.  1 <= nc <= 63.

@@ -124,6 +124,10 @@ _SIGNATURES = {
 	'nrm_lcpm_digamma': ([_i64, _dbl, _vp, _vp], _i32),
 	'nrm_lcpm_colsum': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp], _i32),
 	'nrm_lcpm_write': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _vp], _i32),
+	'nrm_lcpm_csr_workspace': ([_i64, _i64], _i64),
+	'nrm_lcpm_csr_count': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_lcpm_csr_colsum': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _dbl, _vp, _vp, _vp, _vp], _i32),
+	'nrm_lcpm_csr_write': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _vp], _i32),
 	'nrm_fitvar_row_tile': ([], _i64),
 	'nrm_fitvar_moments': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _i32),
 	'nrm_fitvar_genes': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),

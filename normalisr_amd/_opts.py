@@ -28,6 +28,7 @@ DEBUG_KEYS = {
 	'small_svd': "lapack: numpy's stacked SVD instead of the library's threaded Jacobi iteration",
 	'upload': "torch: host -> device copies of half a GB and more through torch instead of the library's staged copy",
 	'upload_block_mb': "staging block size of that copy", 'upload_threads': "host threads filling a staging block",
+	'lcpm_sparse': "0: a scipy.sparse count matrix is densified on the host whatever its density; force: it takes the CSR kernels whatever its density",
 	'tsv': "numpy: the command line reads / writes text with numpy.loadtxt / savetxt",
 	'trace': "1: timeline of a pipelined coex call",
 	'host_mirror': "1: numpy-out coex ships half of the symmetric results and mirrors them on the host",

@@ -11,6 +11,7 @@ import logging
 import numpy as np
 
 from . import _lib
+from . import _opts
 from . import engine as _engine
 
 _WARN_LCPM = "Modifying keyword arguments other than nth or seed is neither recommended nor supported for function 'lcpm'. Do so at your own risk."
@@ -59,13 +60,128 @@ def _host_counts(d):
 
 _CODES = {'torch.int64': _lib.NRM_I64, 'torch.int32': _lib.NRM_I32, 'torch.int16': _lib.NRM_I16, 'torch.uint8': _lib.NRM_U8}
 
+# A scipy.sparse input takes the CSR kernels (csrc/nrm_lcpm_sparse.hip) up to this share of stored entries and today's dense route above it.
+# A PLACEHOLDER from byte counts, not a measured crossing: tools/time_front_sparse.py measures both routes per density and writes the crossing
+# (from_host_threshold) into profiles/front_half_sparse.json; no such record exists yet.  NRM_DEBUG lcpm_sparse=0 | force overrides
+# it; a DeviceCSR always takes the CSR kernels.
+SPARSE_MAX_DENSITY = 0.25
+
+
+def canonical_csr(m):
+	"""A scipy.sparse matrix of counts as canonical CSR over its rows, in O(stored entries): (indptr int64, indices int32, data), duplicates summed, columns
+	sorted, zeros dropped, data in the narrowest of uint8 / int16 / int32 / int64 that holds its maximum.  Floats hold integer values and are cast as
+	_host_counts casts them (lcpm.py:138-139); ValueError for a negative value."""
+	kind = m.dtype.kind
+	if kind not in 'iufb':
+		raise TypeError('reads must be an integer (or integer-valued floating-point) matrix.')
+	if m.shape[1] > np.iinfo(np.int32).max:
+		raise NotImplementedError('sparse reads with more than 2**31 - 1 cells.')
+	c = m.tocsr()
+	if c is m:
+		c = c.copy()
+	if c.data.size and kind not in 'ub' and c.data.min() < 0:
+		raise ValueError('Negative value in d detected.')
+	c.sum_duplicates()  # (sorts the columns of every row as well)
+	if kind in 'fb':
+		c.data = c.data.astype(np.int64)
+	if c.data.size and (c.data == 0).any():
+		c.eliminate_zeros()
+	top = int(c.data.max()) if c.data.size else 0
+	dtype = np.uint8 if top <= 255 else np.int16 if top <= 32767 else np.int32 if top <= np.iinfo(np.int32).max else np.int64
+	return c.indptr.astype(np.int64), c.indices.astype(np.int32), c.data.astype(dtype)
+
+
+class DeviceCSR:
+	"""A sparse count matrix in HBM, canonical CSR over genes: indptr (rows + 1), indices (the cell of every stored entry, strictly increasing inside a row),
+	data (the counts; stored zeros are legal), all 1-D torch CUDA tensors of integer dtype, shape = (n_gene, n_cell).  lcpm and scaling_factor take it as it
+	is -- nothing is sorted or merged: the count kernel checks the structure and a malformed matrix is a ValueError."""
+	is_cuda, ndim = True, 2
+
+	def __init__(self, indptr, indices, data, shape):
+		shape = tuple(int(v) for v in shape)
+		if len(shape) != 2 or min(shape) < 0:
+			raise ValueError('DeviceCSR: shape must be (n_gene, n_cell).')
+		for name, t in (('indptr', indptr), ('indices', indices), ('data', data)):
+			if not hasattr(t, 'data_ptr') or t.dim() != 1:
+				raise ValueError('DeviceCSR: {} must be a 1-D torch tensor.'.format(name))
+		for name, t in (('indptr', indptr), ('indices', indices)):
+			if t.dtype.is_floating_point or t.dtype.is_complex or str(t.dtype) == 'torch.bool':
+				raise ValueError('DeviceCSR: {} must have an integer dtype.'.format(name))
+		if data.dtype.is_complex:
+			raise ValueError('DeviceCSR: data must hold counts.')
+		if indptr.numel() != shape[0] + 1:
+			raise ValueError('DeviceCSR: indptr must have n_gene + 1 = {} entries, not {}.'.format(shape[0] + 1, indptr.numel()))
+		if indices.numel() != data.numel():
+			raise ValueError('DeviceCSR: indices and data must have the same length.')
+		if shape[1] > np.iinfo(np.int32).max:
+			raise NotImplementedError('DeviceCSR with more than 2**31 - 1 cells.')
+		if not (indptr.is_cuda and indices.is_cuda and data.is_cuda) or not (indptr.device == indices.device == data.device):
+			raise ValueError('DeviceCSR: indptr, indices and data must be CUDA tensors on one device.')
+		self.indptr, self.indices, self.data, self.shape = indptr, indices, data, shape
+
+	@property
+	def device(self):
+		return self.data.device
+
+	@classmethod
+	def from_scipy(cls, m, device=None):
+		"""Canonicalise a scipy.sparse matrix on the host (canonical_csr) and upload its three arrays."""
+		eng = _engine.get_engine(device)
+		return cls(*[eng.upload(a) for a in canonical_csr(m)], m.shape)
+
+
+class _Csr:
+	"""What the CSR kernels read: indptr int64, indices int32, data of a dtype in _CODES, all contiguous."""
+
+	def __init__(self, indptr, indices, data, shape):
+		self.indptr, self.indices, self.data, self.shape, self.code, self.nnz = indptr, indices, data, shape, _CODES[str(data.dtype)], int(data.numel())
+
+	def args(self):
+		return (self.indptr.data_ptr(), self.indices.data_ptr(), self.data.data_ptr(), self.code, self.shape[0], self.shape[1], self.nnz)
+
+
+def _as_device_csr(d):
+	"""The device forms of a sparse matrix -- a DeviceCSR, a torch tensor of layout torch.sparse_csr in HBM -- as a DeviceCSR; None for anything else."""
+	if isinstance(d, DeviceCSR):
+		return d
+	if _is_dev(d) and str(getattr(d, 'layout', '')) == 'torch.sparse_csr':
+		return DeviceCSR(d.crow_indices(), d.col_indices(), d.values(), d.shape)
+	return None
+
+
+def _takes_csr(d):
+	"""Whether a scipy.sparse matrix goes through the CSR kernels (True) or is densified as before (False)."""
+	mode = _opts.debug('lcpm_sparse', 'auto')
+	if mode in ('0', 'force'):
+		return mode == 'force'
+	return d.nnz <= SPARSE_MAX_DENSITY * d.shape[0] * d.shape[1]
+
+
+def _ready_csr(eng, c):
+	"""(_Csr, has a negative entry on this side) of a DeviceCSR: index tensors cast on the device to the widths the kernels read, the values to a count dtype."""
+	torch = eng.torch
+	neg, data = False, c.data
+	if data.dtype.is_floating_point:
+		neg = bool(data.numel() and (data < 0).any().item())
+		data = data.to(torch.int64)
+	elif str(data.dtype) not in _CODES:
+		data = data.to(torch.int32 if data.dtype in (torch.int8, torch.bool) else torch.int64)
+	return _Csr(c.indptr.to(torch.int64).contiguous(), c.indices.to(torch.int32).contiguous(), data.contiguous(), c.shape), neg
+
 
 def _device_counts(eng, d):
-	"""The count matrix in HBM with unit column stride and a dtype the kernels read: (tensor, dtype code, has a negative entry on the host side)."""
+	"""The count matrix in HBM as the kernels read it -- a dense tensor with unit column stride, or a _Csr for the CSR kernels: (matrix, dtype code, has a
+	negative entry on the host side)."""
 	torch = eng.torch
 	neg = False
+	if isinstance(d, DeviceCSR):
+		x, neg = _ready_csr(eng, d)
+		return x, x.code, neg
 	if not _is_dev(d):
 		if _is_sparse(d):
+			if _takes_csr(d):
+				x = _Csr(*[eng.upload(a) for a in canonical_csr(d)], d.shape)  # (three arrays of the stored entries: no dense matrix on either side)
+				return x, x.code, False
 			neg = bool(d.data.size and d.data.min() < 0)
 			d = d.toarray()  # (densified on the host, as lcpm.py:134-137 does)
 		d, neg2 = _host_counts(d)
@@ -83,19 +199,27 @@ def _device_counts(eng, d):
 
 
 class _Counts:
-	"""The integer pass over a count matrix (nrm_lcpm_count): per-cell totals and non-zero counts, per-gene zero counts, grand total, maximum, negative flag."""
+	"""The integer pass over a count matrix (nrm_lcpm_count, or nrm_lcpm_csr_count for a _Csr): per-cell totals and non-zero counts, per-gene zero counts, grand
+	total, maximum, negative flag; for a _Csr the structure check as well (ValueError for a malformed matrix)."""
 
 	def __init__(self, eng, d, code):
 		torch = eng.torch
 		nt, ns = d.shape
 		buf = eng.zeros((2 * ns + nt + 4, ), torch.int64)
 		self.cell_total, self.cell_nnz, self.gene_zero, self.info = buf[:ns], buf[ns:2 * ns], buf[2 * ns:2 * ns + nt], buf[2 * ns + nt:]
-		part = torch.empty((int(eng.lib.nrm_lcpm_count_workspace(nt, ns)), ), dtype=torch.int64, device=eng.device)
-		_lib.check(eng.lib.nrm_lcpm_count(d.data_ptr(), code, nt, ns, d.stride(0), self.cell_total.data_ptr(), self.cell_nnz.data_ptr(), self.gene_zero.data_ptr(),
-										  self.info.data_ptr(), part.data_ptr(), eng._stream()))
+		out = (self.cell_total.data_ptr(), self.cell_nnz.data_ptr(), self.gene_zero.data_ptr(), self.info.data_ptr())
+		if isinstance(d, _Csr):
+			part = torch.empty((int(eng.lib.nrm_lcpm_csr_workspace(nt, ns)), ), dtype=torch.int64, device=eng.device)
+			_lib.check(eng.lib.nrm_lcpm_csr_count(*d.args(), *out, part.data_ptr(), eng._stream()))
+		else:
+			part = torch.empty((int(eng.lib.nrm_lcpm_count_workspace(nt, ns)), ), dtype=torch.int64, device=eng.device)
+			_lib.check(eng.lib.nrm_lcpm_count(d.data_ptr(), code, nt, ns, d.stride(0), *out, part.data_ptr(), eng._stream()))
 		h = buf.cpu().numpy()  # (one small read-back: 2 n_cell + n_gene + 4 integers)
 		self.h_cell_total, self.h_cell_nnz, self.h_gene_zero = h[:ns], h[ns:2 * ns], h[2 * ns:2 * ns + nt]
 		self.total, self.max, self.negative = int(h[-4]), int(h[-3]), bool(h[-2])
+		if h[-1]:
+			raise ValueError('Malformed CSR matrix: indptr must rise from 0 to the number of stored entries, and the columns of every row must lie in '
+							 '[0, n_cell) and increase strictly (sum duplicates and sort the indices first).')
 
 
 def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=True, nocov=False, device_out=False, out_dtype=None):
@@ -105,7 +229,7 @@ def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=
 	the reference and is not provided: NotImplementedError.
 	out_dtype: None / numpy.float64 (the reference's) or numpy.float32 (the fp64 value rounded once, at the store).  device_out=True leaves lcpm (and mean, var)
 	in HBM as torch tensors -- what compute_var and normvar take next; cov is always a (3, n_cell) numpy array (None with nocov)."""
-	d = reads
+	d = _as_device_csr(reads) or reads
 	if d.ndim != 2:
 		raise ValueError('reads must have 2 dimensions.')
 	if varscale < 0:
@@ -136,6 +260,7 @@ def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=
 		torch = eng.torch
 		with torch.cuda.device(eng.device):
 			x, code, neg = _device_counts(eng, d)
+			csr = isinstance(x, _Csr)
 			if neg:
 				raise ValueError('Negative value in d detected.')
 			cnt = _Counts(eng, x, code)
@@ -148,16 +273,31 @@ def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=
 			d_tab = eng.upload(tab)
 			d_t1 = None
 			if normalize:
-				d_exp = eng.upload(np.exp(tab))  # exp() once per table entry: the per-cell sums of lcpm.py:158 are sums of table entries
-				tiles = -(-nt // int(eng.lib.nrm_lcpm_row_tile()))
-				part = torch.empty((tiles, ns), dtype=torch.float64, device=eng.device)
+				etab = np.exp(tab)  # exp() once per table entry: the per-cell sums of lcpm.py:158 are sums of table entries
+				d_exp = eng.upload(etab)
 				d_t1 = torch.empty((ns, ), dtype=torch.float64, device=eng.device)
-				with _engine._Span(eng, 'lcpm_colsum'):
-					_lib.check(eng.lib.nrm_lcpm_colsum(x.data_ptr(), code, nt, ns, x.stride(0), d_exp.data_ptr(), tab.size, part.data_ptr(), d_t1.data_ptr(), eng._stream()))
+				if csr:
+					# sum over the stored entries of E[x] - E[0] <= x * unit, in fixed point scaled by the cell's total (csrc/nrm_lcpm_sparse.hip)
+					unit = float(((etab[1:] - etab[0]) / np.arange(1, etab.size)).max()) if etab.size > 1 else 0.0
+					part = torch.empty((int(eng.lib.nrm_lcpm_csr_workspace(nt, ns)), ), dtype=torch.int64, device=eng.device)
+					with _engine._Span(eng, 'lcpm_csr_colsum'):
+						_lib.check(eng.lib.nrm_lcpm_csr_colsum(*x.args(), d_exp.data_ptr(), tab.size, unit, cnt.cell_total.data_ptr(), part.data_ptr(), d_t1.data_ptr(),
+															   eng._stream()))
+				else:
+					tiles = -(-nt // int(eng.lib.nrm_lcpm_row_tile()))
+					part = torch.empty((tiles, ns), dtype=torch.float64, device=eng.device)
+					with _engine._Span(eng, 'lcpm_colsum'):
+						_lib.check(eng.lib.nrm_lcpm_colsum(x.data_ptr(), code, nt, ns, x.stride(0), d_exp.data_ptr(), tab.size, part.data_ptr(), d_t1.data_ptr(), eng._stream()))
+				del part
 			out = torch.empty((nt, ns), dtype=torch.float64 if otype == np.float64 else torch.float32, device=eng.device)
-			with _engine._Span(eng, 'lcpm_write'):
-				_lib.check(eng.lib.nrm_lcpm_write(x.data_ptr(), code, nt, ns, x.stride(0), d_tab.data_ptr(), tab.size, 0 if d_t1 is None else d_t1.data_ptr(), out.data_ptr(),
-												  _lib.NRM_F64 if otype == np.float64 else _lib.NRM_F32, out.stride(0), eng._stream()))
+			tail = (d_tab.data_ptr(), tab.size, 0 if d_t1 is None else d_t1.data_ptr(), out.data_ptr(), _lib.NRM_F64 if otype == np.float64 else _lib.NRM_F32,
+					out.stride(0), eng._stream())
+			if csr:
+				with _engine._Span(eng, 'lcpm_csr_write'):
+					_lib.check(eng.lib.nrm_lcpm_csr_write(*x.args(), *tail))
+			else:
+				with _engine._Span(eng, 'lcpm_write'):
+					_lib.check(eng.lib.nrm_lcpm_write(x.data_ptr(), code, nt, ns, x.stride(0), *tail))
 			if nocov:
 				dcov = None
 			else:
@@ -182,6 +322,7 @@ def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
 	"""Scaling factor of variance normalisation for every gene, same contract as reference lcpm.py:211-283.
 	dt: the read-count matrix, a numpy array or a torch CUDA integer tensor.  The default variable (the share of zero entries per gene) is counted on the
 	device (nrm_lcpm_count); the other four are whole-matrix numpy expressions and run on the host."""
+	dt = _as_device_csr(dt) or dt
 	if dt.ndim != 2:
 		raise ValueError('dt must have 2 dimensions.')
 	if v0 != 0 or v1 != 'max' or varname != 'nt0mean':
@@ -195,6 +336,9 @@ def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
 			zeros = _Counts(eng, x, code).h_gene_zero
 		d = zeros / float(dt.shape[1])  # (dt == 0).mean(axis=1)
 	else:
+		if isinstance(dt, DeviceCSR):  # (these four are whole-matrix numpy expressions: dense on the host)
+			import scipy.sparse
+			dt = scipy.sparse.csr_matrix((dt.data.cpu().numpy(), dt.indices.cpu().numpy(), dt.indptr.cpu().numpy()), shape=dt.shape)
 		h = dt.cpu().numpy() if _is_dev(dt) else (dt.toarray() if _is_sparse(dt) else np.asarray(dt))
 		with np.errstate(divide='ignore', invalid='ignore'):
 			if varname == 'logtpropmean':

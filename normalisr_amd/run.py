@@ -199,16 +199,19 @@ def file_read_coo(f):
 
 def _call_lcpm(m, ka):
 	"""lcpm and scaling_factor on one upload of the counts; the covariates of -c come first in cov_out (run.py:153-189)."""
-	from .lcpm import lcpm, scaling_factor
+	from .lcpm import lcpm, scaling_factor, DeviceCSR, _takes_csr
 	from . import engine as _engine
 	d = m['reads_in']
-	if hasattr(d, 'toarray'):
-		d = d.toarray()
-	d = np.asarray(d)
-	if d.dtype.kind == 'f':
-		d = d.astype(np.int64)  # the reference reads the file with dtype=int (run.py:157-159)
-	eng = _engine.get_engine()
-	x = eng.upload(d if d.dtype in (np.int32, np.int64) else d.astype(np.int64))
+	if hasattr(d, 'toarray') and _takes_csr(d):
+		x = DeviceCSR.from_scipy(d)  # (`lcpm -s`: the stored entries only, uploaded once for both calls)
+	else:
+		if hasattr(d, 'toarray'):
+			d = d.toarray()
+		d = np.asarray(d)
+		if d.dtype.kind == 'f':
+			d = d.astype(np.int64)  # the reference reads the file with dtype=int (run.py:157-159)
+		eng = _engine.get_engine()
+		x = eng.upload(d if d.dtype in (np.int32, np.int64) else d.astype(np.int64))
 	ans = lcpm(x, **ka)
 	sf = scaling_factor(x)
 	cov = ans[3] if m.get('cov_in') is None else np.concatenate([m['cov_in'], ans[3]], axis=0)
