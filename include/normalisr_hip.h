@@ -689,6 +689,30 @@ int nrm_fitvar_genes(const void* d_y, int y_dtype, int64_t rows, int64_t n, int6
 int nrm_fitvar_cells(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_u, const double* d_c, int64_t nc, int64_t ldc,
 					 const double* d_b, const double* d_mean, const double* d_sc, double* d_partial, double* d_v, void* stream);
 
+/*
+ * compute_var with nothing on the host (norm.ComputeVarPlan; csrc/nrm_fitvar_plan.hip): what the reference does between the passes above, on device pointers only,
+ * so that all stepmax iterations are one enqueue.  A state record is four doubles {bestv, steps taken, the last t1, 0}; iteration i reads d_state and writes
+ * d_state_next.  Once `bestv > eps` (the loop test of norm.py:98) fails, the entries below leave the scale, best, u, cw and M^+ as they are and copy the record.
+ * d_ws: nrm_fitvar_plan_workspace doubles of scratch, the same block for every call of one plan.  Sums over cells are per-chunk partial sums added in a fixed order.
+ *   nrm_fitvar_plan_start: d_s = 1 (norm.py:93), d_best = NaN (`best is None`), the first record {1e300, 0, NaN, 0} (norm.py:94-96)
+ *   nrm_fitvar_design:     d_u = 1 / d_s, d_cw (nc, n) = C u^2, the chunks' upper triangles of sum_k (u_k C_k)(u_k C_k)^T                      (norm.py:99-100)
+ *   nrm_fitvar_pinv:       d_mi (nc, nc) = the pseudo-inverse of that sum by the rule of inv_rank (association.py:77-80), *d_rank its rank; one workgroup,
+ *       the cyclic Jacobi iteration of csrc/nrm_jacobi_lanes.h with both matrices in LDS                                                         (norm.py:100)
+ *   nrm_fitvar_update:     after nrm_fitvar_cells: l = log sqrt v, new = exp(fit of l on [C;1]) s with d_m2i ((nc + 1)^2) the pseudo-inverse of [C;1][C;1]^T
+ *       from the caller, new /= min(new), t1 = max |new - s| / s, s = new, best = new and bestv = t1 if t1 < bestv, steps + 1                  (norm.py:109-120)
+ *   nrm_fitvar_weights:    d_w = 1 / d_best, d_w /= min(d_w); d_flags[1] += weights that are not finite and positive                            (norm.py:123-127)
+ *   nrm_fitvar_pinv_host:  nrm_fitvar_pinv's routine on one host matrix m (n, n), n <= 64, one lane: the same sequence of rotations
+ */
+int64_t nrm_fitvar_plan_workspace(int64_t n, int64_t nc);
+int nrm_fitvar_plan_start(int64_t n, double* d_s, double* d_best, double* d_state, void* stream);
+int nrm_fitvar_design(const double* d_c, int64_t nc, int64_t ldc, int64_t n, const double* d_s, const double* d_state, double eps, double* d_u, double* d_cw, double* d_ws,
+					  void* stream);
+int nrm_fitvar_pinv(int64_t n, int64_t nc, double tol, const double* d_state, double eps, const double* d_ws, double* d_mi, int64_t* d_rank, void* stream);
+int nrm_fitvar_update(const double* d_v, const double* d_c, int64_t nc, int64_t ldc, int64_t n, const double* d_m2i, double* d_s, double* d_best, const double* d_state,
+					  double* d_state_next, double eps, double* d_ws, void* stream);
+int nrm_fitvar_weights(const double* d_best, int64_t n, double* d_ws, double* d_w, int32_t* d_flags, void* stream);
+int nrm_fitvar_pinv_host(const double* m, int64_t n, double tol, double* inv, int64_t* rank);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,13 @@ _SIGNATURES = {
 	'nrm_fitvar_moments': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _i32),
 	'nrm_fitvar_genes': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 	'nrm_fitvar_cells': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_fitvar_plan_workspace': ([_i64, _i64], _i64),
+	'nrm_fitvar_plan_start': ([_i64, _vp, _vp, _vp, _vp], _i32),
+	'nrm_fitvar_design': ([_vp, _i64, _i64, _i64, _vp, _vp, _dbl, _vp, _vp, _vp, _vp], _i32),
+	'nrm_fitvar_pinv': ([_i64, _i64, _dbl, _vp, _dbl, _vp, _vp, _vp, _vp], _i32),
+	'nrm_fitvar_update': ([_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp], _i32),
+	'nrm_fitvar_weights': ([_vp, _i64, _vp, _vp, _vp, _vp], _i32),
+	'nrm_fitvar_pinv_host': ([_vp, _i64, _dbl, _vp, _vp], _i32),
 }
 
 _lib = None

@@ -464,4 +464,104 @@ class NormvarPlan:
 		return [self.eng.download(self.out), self.dcn]
 
 
+class ComputeVarPlan:
+	"""compute_var on a logCPM matrix RESIDENT in HBM, step after step (the matrix rewritten in place between steps), with nothing on the host: what a call of
+	compute_var does in numpy between its three streaming passes -- the weighted covariates and the pseudo-inverse of their Gram matrix, the log, the fit on
+	span(dc, 1), exp, the minimum, the best-step rule of norm.py:116-120 and the loop test of norm.py:98 -- are the kernels of csrc/nrm_fitvar_plan.hip on a
+	small state record in HBM.  A step enqueues all stepmax iterations and the weights; no kernel waits for the host and the host decides nothing, so a step is ONE
+	HIP graph from the second on and that graph stays valid when dt is rewritten in place.  Iterations enqueued past the stop condition leave the state as it is.
+	The covariates' upload, the pseudo-inverse of [dc;1][dc;1]^T (host inv_rank: it does not depend on dt) and every buffer are made once, here.
+	check() reads the counters of the steps since the last check and raises what compute_var raises (norm.py:125-127); results() returns the weights as compute_var
+	does and sets steps_taken (iterations that ran) and best_change (the smallest maximum relative change of the scale, the reference's bestv)."""
+
+	def __init__(self, dt, dc, stepmax=1, eps=1E-6, eng=None):
+		from .distributed import StepGraph
+		if eps <= 0 or stepmax <= 0:
+			raise ValueError('eps and stepmax must be positive.')
+		dc = dc.cpu().numpy() if _is_dev(dc) else np.asarray(dc)
+		shape = tuple(dt.shape) if _is_dev(dt) else np.asarray(dt).shape
+		if len(shape) != 2 or dc.ndim != 2:
+			raise ValueError('dt and dc must both have 2 dimensions.')
+		if shape[1] != dc.shape[1]:
+			raise ValueError('dt and dc must have the same cell count.')
+		nt, ns = shape
+		nc = dc.shape[0]
+		if nc == 0 or nc > 63:
+			raise NotImplementedError('compute_var on the device takes 1 to 63 covariates.')
+		if nt == 0 or ns == 0:
+			raise ValueError('dt must not be empty.')
+		if not _is_dev(dt):
+			raise ValueError('ComputeVarPlan takes a logCPM matrix resident in HBM (a torch CUDA tensor); compute_var() is the call for host arrays.')
+		self.eng = eng = eng or _engine.get_engine(dt.device.index)
+		torch = eng.torch
+		if dt.dtype not in (torch.float32, torch.float64) or dt.stride(1) != 1:
+			raise ValueError('ComputeVarPlan takes an fp32 or fp64 matrix with unit column stride.')
+		self.dt, self.stepmax, self.eps = dt, int(stepmax), float(eps)
+		self.dc = c64 = np.array(dc, dtype=np.float64, order='C')
+		c1 = np.concatenate([c64, np.ones((1, ns))], axis=0)  # the second regression has an intercept (norm.py:92,109-110)
+		m2i = inv_rank(np.matmul(c1, c1.T))[0]
+		self.steps_taken = self.best_change = None
+		self._graph = StepGraph(torch)
+		with eng.lock, torch.cuda.device(eng.device):
+			f64 = dict(dtype=torch.float64, device=eng.device)
+			self._c, self._m2i = eng.upload(c64), eng.upload(np.ascontiguousarray(m2i, dtype=np.float64))
+			self._a, self._b = torch.empty((nt, nc), **f64), torch.empty((nt, nc), **f64)
+			self._mean, self._sc, self._v = torch.empty((nt, ), **f64), torch.empty((nt, ), **f64), torch.empty((ns, ), **f64)
+			self._part = torch.empty((-(-nt // int(eng.lib.nrm_fitvar_row_tile())), ns), **f64)
+			self._s, self._best, self._u = torch.empty((ns, ), **f64), torch.empty((ns, ), **f64), torch.empty((ns, ), **f64)
+			self._cw, self._mi = torch.empty((nc, ns), **f64), torch.empty((nc, nc), **f64)
+			self._rank = torch.empty((1, ), dtype=torch.int64, device=eng.device)
+			self._ws = torch.empty((int(eng.lib.nrm_fitvar_plan_workspace(ns, nc)), ), **f64)
+			# the state records (one per iteration and the first) and, right after the last, the weights: results() reads both in one copy
+			self._out = torch.empty((4 * (self.stepmax + 1) + ns, ), **f64)
+			self._state = self._out[:4 * (self.stepmax + 1)].view(self.stepmax + 1, 4)
+			self.w = self._out[4 * (self.stepmax + 1):]
+			self._flags = eng.zeros((4, ), torch.int32)
+
+	def _launch(self):
+		eng, y, lib = self.eng, self.dt, self.eng.lib
+		nt, ns = y.shape
+		nc = self.dc.shape[0]
+		ycode = _lib.NRM_F64 if y.dtype == eng.torch.float64 else _lib.NRM_F32
+		st, p = eng._stream(), lambda t: t.data_ptr()
+		_lib.check(lib.nrm_fitvar_plan_start(ns, p(self._s), p(self._best), p(self._state[0]), st))
+		for i in range(self.stepmax):
+			now, nxt = p(self._state[i]), p(self._state[i + 1])
+			_lib.check(lib.nrm_fitvar_design(p(self._c), nc, self._c.stride(0), ns, p(self._s), now, self.eps, p(self._u), p(self._cw), p(self._ws), st))
+			_lib.check(lib.nrm_fitvar_pinv(ns, nc, 1E-8, now, self.eps, p(self._ws), p(self._mi), p(self._rank), st))
+			_lib.check(lib.nrm_fitvar_moments(p(y), ycode, nt, ns, y.stride(0), p(self._cw), nc, self._cw.stride(0), p(self._a), st))
+			_lib.check(lib.nrm_fitvar_genes(p(y), ycode, nt, ns, y.stride(0), p(self._u), p(self._c), nc, self._c.stride(0), p(self._a), p(self._mi), p(self._b), p(self._mean),
+											p(self._sc), p(self._flags), st))
+			_lib.check(lib.nrm_fitvar_cells(p(y), ycode, nt, ns, y.stride(0), p(self._u), p(self._c), nc, self._c.stride(0), p(self._b), p(self._mean), p(self._sc), p(self._part),
+											p(self._v), st))
+			_lib.check(lib.nrm_fitvar_update(p(self._v), p(self._c), nc, self._c.stride(0), ns, p(self._m2i), p(self._s), p(self._best), now, nxt, self.eps, p(self._ws), st))
+		_lib.check(lib.nrm_fitvar_weights(p(self._best), ns, p(self._ws), p(self.w), p(self._flags), st))
+
+	def step(self):
+		"""All stepmax iterations and the weights on the matrix as it stands in HBM now; the weights in self.w (device fp64, the same tensor every step)."""
+		eng = self.eng
+		with eng.lock, eng.torch.cuda.device(eng.device):
+			self._graph.run(self._launch)
+		return self.w
+
+	def check(self):
+		"""The counters of the steps since the last check (one small read-back): AssertionError as compute_var raises it."""
+		eng = self.eng
+		with eng.lock, eng.torch.cuda.device(eng.device):
+			f = self._flags.cpu().numpy()
+			self._flags.zero_()
+		assert not f[0]  # a gene whose residual is constant: its spread divides (norm.py:108), the result is not finite (norm.py:125)
+		assert not f[1]  # weights finite and positive (norm.py:126-127), `best is not None` (norm.py:122)
+		return True
+
+	def results(self):
+		"""The weights as compute_var returns them; steps_taken and best_change from the last state record, read in the same copy."""
+		self.check()
+		eng = self.eng
+		with eng.lock, eng.torch.cuda.device(eng.device):
+			o = self._out[4 * self.stepmax:].cpu().numpy()
+		self.best_change, self.steps_taken = float(o[0]), int(o[1])
+		return o[4:].copy()
+
+
 assert __name__ != "__main__"
