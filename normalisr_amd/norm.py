@@ -311,9 +311,21 @@ def normcov(dc, c=True):
 	return out
 
 
+def _pinv_gram_unit_rows(x):
+	"""(x x^T)^+ for x (rows, cells) by inv_rank on the Gram matrix of the rows scaled to unit length, D inv_rank(D x x^T D) D with D = diag(1 / |row|): the rank
+	rule, relative to the largest eigenvalue, then does not depend on the units of the rows.  The reference fits with a least-squares solver on the design
+	matrix, centred, beside a separate intercept (norm.py:92,109), so covariates in units of 1e-6 or 1e6 beside the constant-1 row lose nothing there; on the
+	Gram matrix as it stands their eigenvalues fall below 1e-8 of the intercept's (or the intercept's below theirs) and the fit drops them."""
+	d = np.sqrt(np.einsum('ij,ij->i', x, x))
+	d = 1 / np.where(d > 0, d, 1.0)
+	xs = x * d[:, None]
+	mi, r = inv_rank(np.matmul(xs, xs.T))
+	return mi * d[:, None] * d[None, :]
+
+
 def _projector(x):
-	"""x^T (x x^T)^+ x for x (rows, cells): the fitted values of a least-squares regression on the rows of x, whatever their rank."""
-	mi, r = inv_rank(np.matmul(x, x.T))
+	"""x^T (x x^T)^+ x for x (rows, cells): the fitted values of a least-squares regression on the rows of x, whatever their rank and their units."""
+	mi = _pinv_gram_unit_rows(x)
 	return lambda z: np.matmul(np.matmul(mi, np.matmul(x, z)), x)
 
 
@@ -499,7 +511,7 @@ class ComputeVarPlan:
 		self.dt, self.stepmax, self.eps = dt, int(stepmax), float(eps)
 		self.dc = c64 = np.array(dc, dtype=np.float64, order='C')
 		c1 = np.concatenate([c64, np.ones((1, ns))], axis=0)  # the second regression has an intercept (norm.py:92,109-110)
-		m2i = inv_rank(np.matmul(c1, c1.T))[0]
+		m2i = _pinv_gram_unit_rows(c1)
 		self.steps_taken = self.best_change = None
 		self._graph = StepGraph(torch)
 		with eng.lock, torch.cuda.device(eng.device):
