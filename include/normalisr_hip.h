@@ -672,6 +672,46 @@ int nrm_lcpm_csr_write(const int64_t* d_indptr, const int32_t* d_indices, const 
 					   const double* d_table, int64_t table_len, const double* d_t1, void* d_out, int out_dtype, int64_t ldo, void* stream);
 
 /*
+ * Quality control on read counts (reference qc.py:4-85) and the subsetting after it, on a count matrix that stays in HBM.  The matrix is not rewritten between
+ * the iterations of qc_reads: two byte masks, d_gene_alive[rows] and d_cell_alive[n] (0 = removed), say what is left.  Integer arithmetic only: every result is
+ * exact and the same on every run (integer atomics and fixed-order folds; no floating-point atomics).
+ *   nrm_qc_stats:     dense d_x (rows, ld) of dtype NRM_I64 / NRM_I32 / NRM_I16 / NRM_U8.  d_gene_total[g] = sum and d_gene_nnz[g] = number of entries > 0 of an
+ *       alive gene over the alive cells; d_cell_total[k], d_cell_nnz[k] likewise of an alive cell over the alive genes (qc.py:56-71 on the matrix as subset so
+ *       far).  All int64; the value at a removed index is unspecified.  d_info int64[2]: [0] = 1 for a negative alive entry, [1] = 0.  A row tile without an
+ *       alive gene and a chunk of 1024 cells without an alive cell are not loaded.  d_work: nrm_qc_stats_workspace words of scratch.
+ *   nrm_qc_csr_stats: the same over canonical CSR (the format of nrm_lcpm_csr_count; stored zeros are legal and count as zeros).  Only the rows of alive genes
+ *       are walked.  d_info[1] = 1 for a malformed matrix -- d_indptr not 0 = p[0] <= ... <= p[rows] = nnz, or, in a walked row, a column outside [0, n) or
+ *       columns that do not strictly increase.  Such a matrix is never read or written out of bounds; its results mean nothing.
+ *   nrm_qc_decide:    h_thresholds int64[6] on the HOST = (n_gene, nc_gene, nc_gene_prop, n_cell, nt_cell, nt_cell_prop), 0 = disabled.  An alive gene is
+ *       removed when d_gene_total < n_gene or d_gene_nnz < nc_gene or d_gene_nnz < nc_gene_prop, an alive cell likewise; both read the statistics of ONE pass
+ *       (qc.py:52-75).  d_out int64[2] = the genes and the cells still alive.
+ *   nrm_subset_dense: d_out[i, j] = d_x[d_row_idx[i], d_col_idx[j]] for elements of elem = 1, 2, 4 or 8 bytes, ld and ldo in elements.  The lists are int64, in
+ *       any order, with repeats; NULL keeps the axis as it is.  The caller checks the lists: an index outside the matrix reads its nearest edge.
+ *   nrm_subset_csr_count, nrm_subset_csr_scan, nrm_subset_csr_write: a CSR matrix cut down to the alive genes and cells (both in their order), in three steps.
+ *       count: d_row_count[g] = stored entries of row g at alive cells (0 for a removed row); d_info[1] as nrm_qc_csr_stats, over every row.  scan (one workgroup): d_row_count
+ *       becomes, in place, the first output position of every row; d_out_indptr (room for rows + 1) the new indptr; d_cell_map[k] = alive cells before k, the
+ *       new column of an alive cell; d_out int64[3] = (rows kept, cells kept, stored entries kept).  write: the kept entries in their order, columns through
+ *       d_cell_map, values of elem bytes copied (stored zeros stay stored); out_nnz bounds every store.  The result is canonical CSR.
+ */
+int64_t nrm_qc_stats_workspace(int64_t rows, int64_t n);
+int nrm_qc_stats(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld, const uint8_t* d_gene_alive, const uint8_t* d_cell_alive, int64_t* d_gene_total,
+				 int64_t* d_gene_nnz, int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_info /* int64[2] */, int64_t* d_work, void* stream);
+int nrm_qc_csr_stats(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
+					 const uint8_t* d_gene_alive, const uint8_t* d_cell_alive, int64_t* d_gene_total, int64_t* d_gene_nnz, int64_t* d_cell_total, int64_t* d_cell_nnz,
+					 int64_t* d_info /* int64[2] */, int64_t* d_work, void* stream);
+int nrm_qc_decide(const int64_t* d_gene_total, const int64_t* d_gene_nnz, const int64_t* d_cell_total, const int64_t* d_cell_nnz, int64_t rows, int64_t n,
+				  const int64_t* h_thresholds /* int64[6], host */, uint8_t* d_gene_alive, uint8_t* d_cell_alive, int64_t* d_out /* int64[2] */, void* stream);
+int nrm_subset_dense(const void* d_x, int elem, int64_t rows, int64_t n, int64_t ld, const int64_t* d_row_idx, int64_t rows_out, const int64_t* d_col_idx,
+					 int64_t n_out, void* d_out, int64_t ldo, void* stream);
+int nrm_subset_csr_count(const int64_t* d_indptr, const int32_t* d_indices, int64_t rows, int64_t n, int64_t nnz, const uint8_t* d_gene_alive,
+						 const uint8_t* d_cell_alive, int64_t* d_row_count, int64_t* d_info /* int64[2] */, void* stream);
+int nrm_subset_csr_scan(int64_t* d_row_count, int64_t rows, const uint8_t* d_gene_alive, const uint8_t* d_cell_alive, int64_t n, int64_t* d_out_indptr,
+						int32_t* d_cell_map, int64_t* d_out /* int64[3] */, void* stream);
+int nrm_subset_csr_write(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int elem, int64_t rows, int64_t n, int64_t nnz,
+						 const uint8_t* d_gene_alive, const uint8_t* d_cell_alive, const int64_t* d_row_off, const int32_t* d_cell_map, int32_t* d_out_indices,
+						 void* d_out_data, int64_t out_nnz, void* stream);
+
+/*
  * compute_var (reference norm.py:56-128, `normalisr fitvar`): one iteration of the fit with cell weights u (n) -- all ones in the first, 1 / (fitted scale) of
  * the previous one after it (norm.py:98-99).  The reference's two regressions are used for their fitted values only, so the first is b_g = M^+ a_g with
  * M = sum_k u_k^2 C_k C_k^T (its pseudo-inverse d_mi (nc, nc) from the caller: inv_rank) and a_g = sum_k u_k^2 y_gk C_k.  1 <= nc <= 63.

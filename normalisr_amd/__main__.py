@@ -1,16 +1,48 @@
 """`python -m normalisr_amd <cmd>` / `normalisr <cmd>`: command line of the pipeline from read counts to the network.
 Same sub-commands, positionals and flags as the reference CLI for `lcpm` (__main__.py:164-216), `normcov` (:222-245), `fitvar` (:251-272), `normvar` (:311-352),
-`de` (:358-436), `coex` (:442-492) and `binnet` (:498-509), global -v (:14-17), help on stderr + exit 1 without arguments (:649-651)."""
+`de` (:358-436), `coex` (:442-492) and `binnet` (:498-509), and for the quality-control steps `qc_reads` (:24-113), `subset` (:120-158) and `qc_outlier`
+(:275-305); global -v (:14-17), help on stderr + exit 1 without arguments (:649-651)."""
 import argparse
 import logging
 import sys
 
 
 def build_parser():
-	p0 = argparse.ArgumentParser(prog='normalisr', description='Normalisr on AMD MI355X: normalisation (lcpm, normcov, fitvar, normvar), association testing '
-								 '(de, coex) and network binarisation (binnet).  The quality-control and post-processing sub-commands are not provided by this build.')
+	p0 = argparse.ArgumentParser(prog='normalisr', description='Normalisr on AMD MI355X: quality control (qc_reads, subset, qc_outlier), normalisation (lcpm, normcov, '
+								 'fitvar, normvar), association testing (de, coex) and network binarisation (binnet).  The post-processing sub-commands are not provided '
+								 'by this build.')
 	p0.add_argument('-v', dest='verbose', action='store_true', help='Verbose mode.')
 	sub = p0.add_subparsers(help='sub-commands', dest='cmd')
+
+	p = sub.add_parser('qc_reads', help='Quality control of genes and cells by lower bounds on read counts; the defaults suit 10x datasets.')
+	p.add_argument('reads_in', help='Input read-count matrix (genes x cells) without row or column names: TSV if dense (default), Matrix Market (.mtx, .mtx.gz) with -s.')
+	p.add_argument('genes_in', help='Input text file of the gene names (rows of reads_in), one per line.')
+	p.add_argument('cells_in', help='Input text file of the cell names (columns of reads_in), one per line.')
+	p.add_argument('genes_out', help='Output text file of the names of the genes that pass, same format.')
+	p.add_argument('cells_out', help='Output text file of the names of the cells that pass, same format.')
+	p.add_argument('--gene_read_count', dest='n_gene', action='store', type=int, default='0', help='Reads a gene needs. 0 disables. Default: 0.')
+	p.add_argument('--gene_cell_count', dest='nc_gene', action='store', type=int, default='50', help='Cells that must express a gene. 0 disables. Default: 50.')
+	p.add_argument('--gene_cell_prop', dest='ncp_gene', action='store', type=float, default='0.02', help='Share of the cells that must express a gene. 0 disables. Default: 0.02.')
+	p.add_argument('--cell_read_count', dest='n_cell', action='store', type=int, default='500', help='Reads a cell needs. 0 disables. Default: 500.')
+	p.add_argument('--cell_gene_count', dest='nt_cell', action='store', type=int, default='100', help='Genes a cell must express. 0 disables. Default: 100.')
+	p.add_argument('--cell_gene_prop', dest='ntp_cell', action='store', type=float, default='0', help='Share of the genes a cell must express. 0 disables. Default: 0.')
+	p.add_argument('-s', dest='sparse', action='store_true', help='Read reads_in as a sparse Matrix Market (COO) file; needs scipy. The counts stay sparse on the device.')
+
+	p = sub.add_parser('subset', help='Cut a matrix down to the rows and columns named; removes genes and cells after quality control.')
+	p.add_argument('matrix_in', help='Input matrix without row or column names: TSV if dense (default), Matrix Market (.mtx, .mtx.gz) with -s.')
+	p.add_argument('matrix_out', help='Output matrix after subsetting, TSV.')
+	p.add_argument('-r', nargs=2, metavar=('row_before', 'row_after'), help='Text files of the row names before and after subsetting, one per line.')
+	p.add_argument('-c', nargs=2, metavar=('col_before', 'col_after'), help='Text files of the column names before and after subsetting, one per line.')
+	p.add_argument('--nodummy', dest='nodummy', action='store_true', help='Drop single-valued columns / rows when subsetting only the rows / columns.')
+	p.add_argument('-s', dest='sparse', action='store_true', help='Read matrix_in as a sparse Matrix Market (COO) file; needs scipy.')
+
+	p = sub.add_parser('qc_outlier', help='Find outlier cells from the fitted variance.')
+	p.add_argument('weights_in', help='Input vector of the fitted weight of each cell (weights_out of fitvar), TSV.')
+	p.add_argument('cells_in', help='Input text file of the cell names, one per line.')
+	p.add_argument('cells_out', help='Output text file of the names of the cells that pass, same format.')
+	p.add_argument('--pcut', dest='pcut', action='store', type=float, default='1E-10', help='Bonferroni P-value cutoff for outliers. Default: 1E-10.')
+	p.add_argument('--outrate', dest='outrate', action='store', type=float, default='0.02',
+				   help='Largest share of outliers on either tail of the variance distribution: sets the start and bounds the result. Default: 0.02.')
 
 	p = sub.add_parser('de', help='Differential expression analysis.')
 	p.add_argument('design_in', help='Design/predictor matrix (predictors x cells), TSV without row or column names.')

@@ -128,6 +128,14 @@ _SIGNATURES = {
 	'nrm_lcpm_csr_count': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 	'nrm_lcpm_csr_colsum': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _dbl, _vp, _vp, _vp, _vp], _i32),
 	'nrm_lcpm_csr_write': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _vp], _i32),
+	'nrm_qc_stats_workspace': ([_i64, _i64], _i64),
+	'nrm_qc_stats': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_qc_csr_stats': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_qc_decide': ([_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_subset_dense': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp], _i32),
+	'nrm_subset_csr_count': ([_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_subset_csr_scan': ([_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
+	'nrm_subset_csr_write': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp], _i32),
 	'nrm_fitvar_row_tile': ([], _i64),
 	'nrm_fitvar_moments': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _i32),
 	'nrm_fitvar_genes': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),

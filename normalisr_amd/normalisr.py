@@ -1,6 +1,7 @@
 """User API facade: `import normalisr_amd.normalisr as norm` (reference normalisr.py:3-9).
-The pipeline from read counts to the network is provided: lcpm (+ scaling_factor) -> normcov -> compute_var -> normvar -> de / coex -> binnet.  The reference's
-quality-control and post-processing steps (qc_reads, qc_outlier, gotop, pccovt) are outside this build's scope."""
+The pipeline from read counts to the network is provided: lcpm (+ scaling_factor) -> normcov -> compute_var -> normvar -> de / coex -> binnet.  The
+quality-control steps qc_reads and qc_outlier (and subset) live in normalisr_amd.qc and behind the command line; this facade does not export them yet.  The
+reference's post-processing steps (gotop, pccovt) are outside this build's scope."""
 from .de import de
 from .coex import coex
 from .binnet import binnet
@@ -12,6 +13,8 @@ _OUT_OF_SCOPE = ('qc_reads', 'qc_outlier', 'gotop', 'pccovt')
 
 def __getattr__(name):
 	if name in _OUT_OF_SCOPE:
+		if name in ('qc_reads', 'qc_outlier'):
+			raise NotImplementedError('{0} is not exported by this facade: call normalisr_amd.qc.{0} (or `normalisr {0}` on the command line).'.format(name))
 		raise NotImplementedError('normalisr_amd provides the pipeline from lcpm to binnet; '
 								  '{} is not part of this build.'.format(name))
 	raise AttributeError(name)

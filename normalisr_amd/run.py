@@ -1,4 +1,4 @@
-"""Command runners and matrix IO behind `normalisr lcpm | normcov | fitvar | normvar | de | coex | binnet`.
+"""Command runners and matrix IO behind `normalisr qc_reads | subset | lcpm | normcov | fitvar | qc_outlier | normvar | de | coex | binnet`.
 
 Every sub-command is one row of COMMANDS: which files are read (and how they are shaped), which command-line
 options become which keyword arguments, which function runs, and which of its results go to which file.
@@ -292,5 +292,117 @@ def _runner(cmd):
 
 
 de, coex, normvar, binnet, lcpm, normcov, fitvar = (_runner(c) for c in ('de', 'coex', 'normvar', 'binnet', 'lcpm', 'normcov', 'fitvar'))  # module-level entry points, as in the reference's run module
+
+
+# ---- quality control: qc_reads, subset, qc_outlier (reference run.py:48-150,220-234) -----------------------------------------------------------------------
+# These three read and write name lists beside the matrices, so they are functions of their own, not rows of COMMANDS.  They import torch (the engine).
+
+def file_read_txtlist(f, **ka):
+	"""The names in a text file, one per line, as a numpy array of strings: surrounding blanks stripped, empty lines dropped."""
+	logging.debug('Start reading file ' + f)
+	with open(f, 'r', **ka) as fh:
+		names = [line.strip() for line in fh]
+	logging.debug('Finish reading file ' + f)
+	return np.array([v for v in names if v])
+
+
+def file_write_txtlist(f, d, **ka):
+	"""Names to a text file, one per line (no line end after the last, as the reference writes it); returns the text."""
+	import os
+	text = os.linesep.join(d)
+	logging.debug('Start writing file ' + f)
+	with open(f, 'w', **ka) as fh:
+		fh.write(text)
+	logging.debug('Finish writing file ' + f)
+	return text
+
+
+def _read_counts(f):
+	"""A dense count matrix from a text (or .npy) file as int64: the library's parser where every field holds an integer, numpy.loadtxt(dtype=int) -- the
+	reference's call, and its exception -- for anything else."""
+	d = file_read_tsv(f)
+	if d.dtype.kind in 'iu':
+		return d.astype(np.int64, copy=False)
+	if np.isfinite(d).all() and (d == np.rint(d)).all() and (np.abs(d) < 2.0**53).all():
+		return d.astype(np.int64)
+	return file_read_tsv(f, dtype=int)
+
+
+def _read_sparse_counts(f):
+	return file_read_coo(f).astype(int, copy=False)
+
+
+def qc_reads(args):
+	"""normalisr qc_reads: the names of the genes and cells that pass (reference run.py:70-97).  With -s the Matrix Market counts are uploaded as CSR and stay
+	sparse on the device."""
+	from . import qc
+	d = _read_sparse_counts(args['reads_in']) if args['sparse'] else _read_counts(args['reads_in'])
+	nt, ns = d.shape
+	genes = file_read_txtlist(args['genes_in'])
+	if len(genes) != nt:
+		raise ValueError("Gene count in genes_in doesn't match row count in reads_in.")
+	cells = file_read_txtlist(args['cells_in'])
+	if len(cells) != ns:
+		raise ValueError("Cell count in cells_in doesn't match column count in reads_in.")
+	logging.debug('Start calculation.')
+	keep = qc.qc_reads(d, args['n_gene'], args['nc_gene'], args['ncp_gene'], args['n_cell'], args['nt_cell'], args['ntp_cell'])
+	logging.debug('Finish calculation.')
+	file_write_txtlist(args['genes_out'], genes[keep[0]])
+	file_write_txtlist(args['cells_out'], cells[keep[1]])
+
+
+def _name_positions(files, size, what):
+	"""The positions, in the list of names before subsetting, of the names after it (reference run.py:114-123: same checks, same message)."""
+	before, after = (file_read_txtlist(f) for f in files)
+	assert len(before) == size
+	assert len(set(before)) == len(before) and len(set(after)) == len(after)
+	where = {name: i for i, name in enumerate(before)}
+	missing = [name for name in after if name not in where]
+	if missing:
+		raise ValueError('Subset {} names not found: {}...'.format(what, ','.join(missing[:3])))
+	return np.array([where[name] for name in after], dtype=np.int64)
+
+
+def subset(args):
+	"""normalisr subset: matrix_in cut down to the named rows and columns (reference run.py:100-150).  A dense matrix goes through the gather kernel, names in any
+	order; -s with names in their original order goes through the CSR subset and is densified for the text output, -s with any other order is indexed on the
+	host.  --nodummy is applied on the host to the matrix about to be written."""
+	from . import qc
+	if args['r'] is None and args['c'] is None:
+		raise ValueError('Please indicate row (-r) or column (-c) for subsetting.')
+	if args['nodummy'] and args['r'] is not None and args['c'] is not None:
+		raise ValueError('Only supports nodumy when one of row or column needs subsetting.')
+	d = _read_sparse_counts(args['matrix_in']) if args['sparse'] else file_read_tsv(args['matrix_in'])
+	rows = None if args['r'] is None else _name_positions(args['r'], d.shape[0], 'row')
+	cols = None if args['c'] is None else _name_positions(args['c'], d.shape[1], 'column')
+	logging.debug('Start calculation.')
+	if not args['sparse']:
+		out = qc.subset(d, rows, cols)
+	elif all(v is None or (np.diff(v) > 0).all() for v in (rows, cols)):
+		out = qc.subset(d, rows, cols).toarray()
+	else:
+		out = d.tocsr()[slice(None) if rows is None else rows][:, slice(None) if cols is None else cols].toarray()
+	if args['nodummy']:
+		if rows is not None:
+			out = out[:, [len(np.unique(v)) > 1 for v in out.T]]
+		else:
+			out = out[[len(np.unique(v)) > 1 for v in out]]
+	logging.debug('Finish calculation.')
+	if 0 in out.shape:
+		raise RuntimeError('Empty matrix after subsetting, maybe because nodummy option.')
+	file_write_tsv(args['matrix_out'], out, fmt=fmt_int if np.issubdtype(out.dtype, np.integer) else fmt_float)
+
+
+def qc_outlier(args):
+	"""normalisr qc_outlier: the names of the cells whose fitted weight is no outlier (reference run.py:220-234)."""
+	from . import qc
+	w = file_read_tsv(args['weights_in']).ravel()
+	cells = file_read_txtlist(args['cells_in'])
+	if len(cells) != len(w):
+		raise ValueError("Cell count in cells_in doesn't match entry count in weights_in.")
+	logging.debug('Start calculation.')
+	keep = qc.qc_outlier(w, outrate=args['outrate'], pcut=args['pcut'])
+	logging.debug('Finish calculation.')
+	file_write_txtlist(args['cells_out'], cells[keep])
 
 assert __name__ != "__main__"
