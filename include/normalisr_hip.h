@@ -712,6 +712,32 @@ int nrm_subset_csr_write(const int64_t* d_indptr, const int32_t* d_indices, cons
 						 void* d_out_data, int64_t out_nnz, void* stream);
 
 /*
+ * The covariate of the top principal component of chosen genes (reference gocovt.py: the row degrees of gotop, :257-266; pccovt, :271-321, with pc1, :4-25).
+ * The rows are gathered (nrm_subset_dense), residualised against [covariates; 1] by K1, twice (nrm_residualize: the fp64 residual rows Zres (m, ldz), zero padded, and
+ * their sums of squares ss) and contracted by K2 (nrm_gram_f64, symmetric: G = Zres Zres^T, upper tiles only).  The entries below do the rest.  Every sum is
+ * taken in a fixed order (no floating-point atomics): the same bits on every run.
+ *   nrm_net_degree:     d_deg[g] (int64) = the number of non-zero bytes of row g of the (ng, ng) byte matrix d_net with pitch ld >= ng bytes -- net.sum(axis=1) of
+ *       a binary network (gocovt.py:258), any non-zero byte counted once.  One read of the matrix: 16-byte loads from the first aligned address of a row on,
+ *       single bytes before it and in the tail; any base address and pitch.  Exact.
+ *   nrm_pc_correlation: a_g = 1 / (sqrt(ss_g / n) + 1e-200) (pc1's scaling, gocovt.py:21) into d_a (m), and the correlation matrix of the scaled rows
+ *       d_r[g, h] = (G[lo, hi] * a_lo) * a_hi / n with lo = min(g, h), hi = max(g, h): both triangles from the upper one, symmetric to the bit.  A row of
+ *       exact zeros has G = 0 and a = 1e200 and gives a zero row of d_r (the products are taken in that order), not NaN.
+ *   nrm_pc_power:       `iters` steps of the power iteration on d_r (m, ldr): w = R v (a wave per row), lambda = v.w, residual = |w - lambda v|,
+ *       v <- w / |w| (v stays when w == 0); d_v (m) is updated in place, d_w (m) is scratch, d_stat[0..2] = lambda, residual, |w| of the LAST step.
+ *       Replaces the randomized TruncatedSVD of gocovt.py:22-23 (5 power iterations from a random sketch) by the exact component.
+ *   nrm_pc_score:       the sign of svd_flip(u_based_decision=False): the entry of v of largest magnitude (the first of equals) is positive; then
+ *       d_out[j] = sum_g (+-v_g a_g) Zres[g, j], the score Z^T v of gocovt.py:23, as NRM_F64 or NRM_F32 (rounded once).  d_z 16-byte aligned, ldz even and
+ *       >= n rounded up to 2.  The genes are split over workgroups where the cells alone do not fill the device; the partial sums are added in the order of the
+ *       splits.  d_work: nrm_pc_score_workspace(m, n) doubles.  d_sign (int64[2]) = the index of that entry and the sign applied (+-1).
+ */
+int nrm_net_degree(const uint8_t* d_net, int64_t ng, int64_t ld, int64_t* d_deg, void* stream);
+int nrm_pc_correlation(const double* d_g, int64_t ldg, int64_t m, int64_t n, const double* d_ss, double* d_r, int64_t ldr, double* d_a, void* stream);
+int nrm_pc_power(const double* d_r, int64_t ldr, int64_t m, double* d_v, double* d_w, double* d_stat /* double[3] */, int iters, void* stream);
+int64_t nrm_pc_score_workspace(int64_t m, int64_t n);
+int nrm_pc_score(const double* d_z, int64_t ldz, int64_t m, int64_t n, const double* d_v, const double* d_a, void* d_out, int out_dtype, double* d_work,
+				 int64_t* d_sign /* int64[2] */, void* stream);
+
+/*
  * compute_var (reference norm.py:56-128, `normalisr fitvar`): one iteration of the fit with cell weights u (n) -- all ones in the first, 1 / (fitted scale) of
  * the previous one after it (norm.py:98-99).  The reference's two regressions are used for their fitted values only, so the first is b_g = M^+ a_g with
  * M = sum_k u_k^2 C_k C_k^T (its pseudo-inverse d_mi (nc, nc) from the caller: inv_rank) and a_g = sum_k u_k^2 y_gk C_k.  1 <= nc <= 63.

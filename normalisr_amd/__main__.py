@@ -1,7 +1,8 @@
 """`python -m normalisr_amd <cmd>` / `normalisr <cmd>`: command line of the pipeline from read counts to the network.
 Same sub-commands, positionals and flags as the reference CLI for `lcpm` (__main__.py:164-216), `normcov` (:222-245), `fitvar` (:251-272), `normvar` (:311-352),
 `de` (:358-436), `coex` (:442-492) and `binnet` (:498-509), and for the quality-control steps `qc_reads` (:24-113), `subset` (:120-158) and `qc_outlier`
-(:275-305); global -v (:14-17), help on stderr + exit 1 without arguments (:649-651)."""
+(:275-305); global -v (:14-17), help on stderr + exit 1 without arguments (:649-651).  `principal` and `pccovt` are sub-commands of this build's own: the two
+numerical parts of the reference's `gocovt` (:512-597), whose GO enrichment between them is not provided."""
 import argparse
 import logging
 import sys
@@ -9,8 +10,9 @@ import sys
 
 def build_parser():
 	p0 = argparse.ArgumentParser(prog='normalisr', description='Normalisr on AMD MI355X: quality control (qc_reads, subset, qc_outlier), normalisation (lcpm, normcov, '
-								 'fitvar, normvar), association testing (de, coex) and network binarisation (binnet).  The post-processing sub-commands are not provided '
-								 'by this build.')
+								 'fitvar, normvar), association testing (de, coex), network binarisation (binnet) and the covariate of a pathway\'s top principal component '
+								 '(principal, pccovt).  The sub-command gocovt is not provided: its GO enrichment needs goatools and a web service.  Run principal, find the '
+								 'enriched pathway among its genes with any tool, and hand the pathway\'s genes to pccovt.')
 	p0.add_argument('-v', dest='verbose', action='store_true', help='Verbose mode.')
 	sub = p0.add_subparsers(help='sub-commands', dest='cmd')
 
@@ -107,6 +109,21 @@ def build_parser():
 	p.add_argument('pv_in', help='Input P-value matrix of gene pairwise co-expression (genes x genes), TSV.')
 	p.add_argument('net_out', help='Output binary co-expression network (genes x genes, 0/1), TSV.')
 	p.add_argument('qcut', type=float, help='Q-value cutoff for binary network.')
+
+	p = sub.add_parser('principal', help='List the principal genes of a binary co-expression network: the genes with the most co-expressed genes (the selection of '
+					   'the reference\'s gocovt, without its GO enrichment).')
+	p.add_argument('net_in', help='Input binary co-expression network (genes x genes, 0/1), TSV; net_out of binnet.')
+	p.add_argument('genes_in', help='Input text file of the gene names (rows of net_in), one per line.')
+	p.add_argument('master_out', help='Output text file of the names of the principal genes, same format.')
+	p.add_argument('-n', dest='n', action='store', type=int, default='100', help='Number of top principal genes; genes that tie with the last one are kept too. Default: 100.')
+
+	p = sub.add_parser('pccovt', help='Append the top principal component of the chosen genes (a pathway) as a covariate.')
+	p.add_argument('exp_in', help='Normalized expression matrix (genes x cells), TSV.')
+	p.add_argument('cov_in', help='Covariate matrix (covariates x cells), TSV.')
+	p.add_argument('genes_in', help='Input text file of the gene names (rows of exp_in), one per line.')
+	p.add_argument('pathway_in', help='Input text file of the names of the genes whose top principal component is taken, one per line.')
+	p.add_argument('cov_out', help='Output covariate matrix with the new covariate as its last row, same format as cov_in.')
+	p.add_argument('--nocond', dest='nocond', action='store_true', help='Do not remove the existing covariates from the expression before taking the component.')
 	return p0
 
 

@@ -136,6 +136,11 @@ _SIGNATURES = {
 	'nrm_subset_csr_count': ([_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
 	'nrm_subset_csr_scan': ([_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
 	'nrm_subset_csr_write': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp], _i32),
+	'nrm_net_degree': ([_vp, _i64, _i64, _vp, _vp], _i32),
+	'nrm_pc_correlation': ([_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp], _i32),
+	'nrm_pc_power': ([_vp, _i64, _i64, _vp, _vp, _vp, _i32, _vp], _i32),
+	'nrm_pc_score_workspace': ([_i64, _i64], _i64),
+	'nrm_pc_score': ([_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp], _i32),
 	'nrm_fitvar_row_tile': ([], _i64),
 	'nrm_fitvar_moments': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _i32),
 	'nrm_fitvar_genes': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),

@@ -1,4 +1,4 @@
-"""Command runners and matrix IO behind `normalisr qc_reads | subset | lcpm | normcov | fitvar | qc_outlier | normvar | de | coex | binnet`.
+"""Command runners and matrix IO behind `normalisr qc_reads | subset | lcpm | normcov | fitvar | qc_outlier | normvar | de | coex | binnet | principal | pccovt`.
 
 Every sub-command is one row of COMMANDS: which files are read (and how they are shaped), which command-line
 options become which keyword arguments, which function runs, and which of its results go to which file.
@@ -404,5 +404,36 @@ def qc_outlier(args):
 	keep = qc.qc_outlier(w, outrate=args['outrate'], pcut=args['pcut'])
 	logging.debug('Finish calculation.')
 	file_write_txtlist(args['cells_out'], cells[keep])
+
+
+# ---- the covariate of a pathway's top principal component: principal, pccovt (the numerical parts of reference run.py:324-354) ---------------------------------
+# The reference's gocovt runs gotop (selection + GO enrichment) and pccovt in one command; the enrichment is not part of this build, so the two parts are commands
+# of their own and the list of genes between them is a file.
+
+def principal(args):
+	"""normalisr principal: the names of the principal genes of a binary network (what the reference's gocovt writes to --master_out)."""
+	from . import gocovt
+	net = file_read_tsv(args['net_in'], dtype='u1')
+	genes = file_read_txtlist(args['genes_in'])
+	if net.shape != (len(genes), len(genes)):
+		raise ValueError('Wrong shape for net or namet.')
+	logging.debug('Start calculation.')
+	keep = gocovt.principal_genes(net, n=args['n'])
+	logging.debug('Finish calculation.')
+	file_write_txtlist(args['master_out'], genes[keep])
+
+
+def pccovt(args):
+	"""normalisr pccovt: cov_in with the top principal component of the genes named in pathway_in as its last row."""
+	from . import gocovt
+	dt = file_read_tsv(args['exp_in'])
+	dc = file_read_tsv(args['cov_in'])
+	namet = file_read_txtlist(args['genes_in'])
+	pathway = file_read_txtlist(args['pathway_in'])
+	logging.debug('Start calculation.')
+	out = gocovt.pccovt(dt, dc, namet, pathway, condcov=not args['nocond'])
+	logging.debug('Finish calculation.')
+	file_write_tsv(args['cov_out'], out)
+
 
 assert __name__ != "__main__"
