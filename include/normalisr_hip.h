@@ -395,7 +395,8 @@ int nrm_binnet_rows(const void* d_p, int p_dtype, int64_t rows, int64_t ng, int6
  *   nrm_normvar_weights: U = e^2, V = e^2 * y  (fp64, (rows_pad, ldo), zero padded) for the two Gram contractions
  *       M_g = U P^T (P = products C_c*C_c') and a_g = V C^T on nrm_gram_f64;  s1 = sum_k y e, s2 = sum_k (y e)^2.
  *       d_lnw (n) = ln w, d_wt (rows) = wt.
- *   nrm_normvar_apply:   out_gk = scale_g * e_gk * (y_gk - sum_c b_gc C_ck),  b_g = M_g^+ a_g from the host (integer rank).
+ *   nrm_normvar_apply:   out_gk = scale_g * e_gk * (y_gk - sum_c b_gc C_ck),  b_g = M_g^+ a_g from the host (integer rank), or the rows of the basis
+ *       B as d_c with b_g from nrm_normvar_chol.  1 <= nc <= nrm_wide_covariates(): beyond 64 the coefficient table is in dynamic LDS.
  */
 int nrm_normvar_weights(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_lnw, const double* d_wt,
 						double* d_u, double* d_v, int64_t ldo, int64_t rows_pad, double* d_s1, double* d_s2, void* stream);
@@ -413,6 +414,25 @@ int nrm_normvar_exp_probe(const double* d_x, int64_t count, double* d_out, void*
 int64_t nrm_normvar_device_covariates(void);
 int nrm_normvar_solve(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_lnw, const double* d_wt, const double* d_c, int64_t nc,
 					  int64_t ldc, double tol, int keepvar, double* d_mom, double* d_b, double* d_scale, int64_t* d_rank, int32_t* d_flags, void* stream);
+/*
+ * normvar with 64 .. nrm_wide_covariates() covariates (csrc/nrm_normvar_wide.hip), replacing the reference's per-gene pseudo-inverse and projection
+ * (norm.py:154-163, called per gene from norm.py:232-259).  The host gives an orthonormal basis B (r, n) of the covariates' row space (normalisr_amd/norm.py:
+ * _wide_basis); M_g = B diag(e_g^2) B^T is then positive definite and b_g solves M_g b_g = a_g, a_g = B (e_g^2 o y_g).
+ *   nrm_wide_covariates: the largest covariate count of nrm_fitvar_* and nrm_normvar_apply, and the largest r here.
+ *   nrm_normvar_pairs:   d_p (rows_pad, ldp) = rows [pair0, pair0 + count) of P, P_(i,j) = B_i o B_j for i <= j in the order of numpy's triu_indices(r);
+ *       rows count .. rows_pad and cells n .. ldp are written as zeros.  A panel of the operand of  M = U P^T  (nrm_normvar_weights, nrm_gram_f64_whole).
+ *   nrm_normvar_chol:    a workgroup per gene: blocked Cholesky factorisation of the packed upper triangle d_m[g] (ldm >= r (r + 1) / 2; row i holds columns
+ *       i .. r - 1; overwritten by the factor), the two triangular solves for d_b[g] (r), and d_scale[g] = (dv / dv2)^wt_g with dv2^2 = (s2 - a . b) / n
+ *       (norm.py:248-259; keepvar = 0: 1).  d_status (genes, or NULL): 0, 1 = a pivot that is not positive, 2 = a value that is not finite; such a gene gets
+ *       zeros in d_b and d_scale, and d_flags[0] / d_flags[1] count them.
+ *   nrm_gram_f64_whole:  nrm_gram_f64 (not symmetric) with every tile computed whole by one workgroup: an entry's bits do not depend on the launch's shape.
+ */
+int64_t nrm_wide_covariates(void);
+int nrm_normvar_pairs(const double* d_b, int64_t r, int64_t n, int64_t ldb, int64_t pair0, int64_t count, double* d_p, int64_t rows_pad, int64_t ldp, void* stream);
+int nrm_normvar_chol(double* d_m, int64_t ldm, const double* d_a, int64_t lda, int64_t genes, int64_t r, const double* d_s1, const double* d_s2, const double* d_wt,
+					 int64_t n, int keepvar, double* d_b, double* d_scale, int32_t* d_status, int32_t* d_flags /* int32[4] */, void* stream);
+int nrm_gram_f64_whole(const double* d_a, const double* d_b, int64_t m_pad, int64_t n_pad, int64_t k_pad, int64_t lda, int64_t ldb, double* d_dot, int64_t ldd,
+					   int64_t m_rows, int64_t n_rows, void* stream);
 /* normvar1 with explicit per-gene cell weights w2 (rows, ldw) (norm.py:150-153: row g is residualised against dc * w2[g]):
  * out_gk = y_gk - w2_gk * sum_c b_gc C_ck, with b_g = (sum_k w2_gk^2 C_k C_k^T)^+ (sum_k w2_gk y_gk C_k) from the host. */
 int nrm_normvar_apply_w2(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_w2, int64_t ldw,
@@ -740,7 +760,8 @@ int nrm_pc_score(const double* d_z, int64_t ldz, int64_t m, int64_t n, const dou
 /*
  * compute_var (reference norm.py:56-128, `normalisr fitvar`): one iteration of the fit with cell weights u (n) -- all ones in the first, 1 / (fitted scale) of
  * the previous one after it (norm.py:98-99).  The reference's two regressions are used for their fitted values only, so the first is b_g = M^+ a_g with
- * M = sum_k u_k^2 C_k C_k^T (its pseudo-inverse d_mi (nc, nc) from the caller: inv_rank) and a_g = sum_k u_k^2 y_gk C_k.  1 <= nc <= 63.
+ * M = sum_k u_k^2 C_k C_k^T (its pseudo-inverse d_mi (nc, nc) from the caller: inv_rank) and a_g = sum_k u_k^2 y_gk C_k.  1 <= nc <= nrm_wide_covariates() (1024):
+ * up to 63 the workgroup's coefficient table is a static array, beyond it lies in dynamic LDS (4 x nc doubles) and d_mi is read as symmetric.
  *   nrm_fitvar_moments: d_a (rows, nc) = Y Cw^T with d_cw (nc, ldc) = u^2 C                                                       (norm.py:100)
  *   nrm_fitvar_genes:   d_b (rows, nc) = a M^+;  r_gk = u_k (y_gk - sum_c b_gc C_ck);  d_mean[g] = mean_k r_gk,  d_sc[g] = sqrt(mean_k (r_gk - mean)^2)
  *       (norm.py:101-107);  d_flags[0] += genes with d_sc == 0 or not finite (the reference divides by it, norm.py:108, and fails norm.py:125)

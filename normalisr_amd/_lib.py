@@ -142,6 +142,10 @@ _SIGNATURES = {
 	'nrm_pc_score_workspace': ([_i64, _i64], _i64),
 	'nrm_pc_score': ([_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp], _i32),
 	'nrm_fitvar_row_tile': ([], _i64),
+	'nrm_wide_covariates': ([], _i64),
+	'nrm_normvar_pairs': ([_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
+	'nrm_normvar_chol': ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_gram_f64_whole': ([_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp], _i32),
 	'nrm_fitvar_moments': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp], _i32),
 	'nrm_fitvar_genes': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 	'nrm_fitvar_cells': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),

@@ -25,6 +25,8 @@ DEBUG_KEYS = {
 	'single1_stats': "host: single=1 finishes the groupings' statistics (pseudo-inverses, ranks, P-value plans) on the host as rounds 3-5 did",
 	's4_plan': "public: a Single4Plan calls the public function every step (no lean device-only replay)",
 	'normvar': "host: normvar through the Gram launches and the host's batched pseudo-inverses",
+	'nv_gene_block': "normvar with more than 63 covariates: genes per block of the device path (default: from a 1.5 GiB budget)",
+	'nv_panel_rows': "the same: rows of the pair-product operand built per panel (default: from a 256 MiB budget)",
 	'small_svd': "lapack: numpy's stacked SVD instead of the library's threaded Jacobi iteration",
 	'upload': "torch: host -> device copies of half a GB and more through torch instead of the library's staged copy",
 	'upload_block_mb': "staging block size of that copy", 'upload_threads': "host threads filling a staging block",

@@ -41,5 +41,9 @@ static inline int nrm_check_launch(const char* what) {
 	return NRM_OK;
 }
 
+// covariates compute_var and normvar take (nrm_wide_covariates(); csrc/nrm_fitvar.hip, csrc/nrm_normvar_wide.hip): the workgroup's coefficient table,
+// 4 rows of this many doubles in dynamic LDS, is 32 KiB
+#define NRM_WIDE_NC 1024
+
 typedef double d4_t __attribute__((ext_vector_type(4)));
 typedef float f16_t __attribute__((ext_vector_type(16)));

@@ -12,14 +12,19 @@
 //                 residual is constant (sc_g = 0: the reference divides by zero there and fails its assertion, norm.py:125)
 //   k_fv_cells    a workgroup per FV_TR genes x 1024 cells: per-cell partial sums of ((r - m) / sc)^2, one per row tile,
 //   k_fv_finish   added in a fixed order: no floating-point atomics, the same bits every run.
+// Covariates: the three passes are loops over them.  Up to FV_NC the workgroup's coefficient table is a static array of 64 columns; beyond, up to NRM_WIDE_NC
+// (nrm_wide_covariates()), the WIDE instantiations of k_fv_genes and k_fv_cells keep FV_R x nc coefficients in dynamic LDS (32 KiB at 1024: no opt-in) -- the
+// per-cell pass then reloads the table for every FV_R genes of its tile -- and b_g = M^+ a_g reads M^+ by columns (it is symmetric), coalesced over nc x nc.
+// The launchers choose by nc; the instantiations for nc <= FV_NC are the ones the library always had.
 #include "nrm_common.h"
 
 #define FV_R 4    // genes per workgroup of the per-gene passes, and per step of the per-cell pass: they share the loads of the covariates
 #define FV_Q 8    // covariates per sweep of the moments pass
 #define FV_TR 32  // genes per partial sum of the per-cell pass
-#define FV_NC 63  // as normvar
+#define FV_NC 63  // the static coefficient tables (64 columns); beyond: the WIDE instantiations, up to NRM_WIDE_NC
 
 extern "C" int64_t nrm_fitvar_row_tile(void) { return FV_TR; }
+extern "C" int64_t nrm_wide_covariates(void) { return NRM_WIDE_NC; }
 
 // Four consecutive elements of a row as doubles, zero at and beyond n.  ALIGNED (the launcher: 16-byte aligned rows): 16-byte loads.
 template <typename T, bool ALIGNED>
@@ -93,7 +98,7 @@ __global__ void __launch_bounds__(256) k_fv_moments(const T* __restrict__ y, int
 // r[i][j] = u_j (y_ij - sum_c b_ic C_cj) for FV_R rows and the lane's four cells (zero at and beyond n: u reads as zero there)
 template <typename T, bool ALIGNED>
 __device__ __forceinline__ void fv_resid(const T* (&yr)[FV_R], int64_t k, int64_t n, const double* __restrict__ u, const double* __restrict__ c, int nc, int64_t ldc,
-										 const double (*s_b)[64], double (&res)[FV_R][4]) {
+										 const double* s_b, const int ldb, double (&res)[FV_R][4]) {
 	double uv[4], yv[FV_R][4], fit[FV_R][4];
 	fv_ld4<double, ALIGNED>(u, k, n, uv);
 #pragma unroll
@@ -108,7 +113,7 @@ __device__ __forceinline__ void fv_resid(const T* (&yr)[FV_R], int64_t k, int64_
 #pragma unroll
 		for (int r = 0; r < FV_R; r++)
 #pragma unroll
-			for (int j = 0; j < 4; j++) fit[r][j] = fma(s_b[r][q], cv[j], fit[r][j]);
+			for (int j = 0; j < 4; j++) fit[r][j] = fma(s_b[r * ldb + q], cv[j], fit[r][j]);
 	}
 #pragma unroll
 	for (int r = 0; r < FV_R; r++)
@@ -116,23 +121,31 @@ __device__ __forceinline__ void fv_resid(const T* (&yr)[FV_R], int64_t k, int64_
 		for (int j = 0; j < 4; j++) res[r][j] = uv[j] * (yv[r][j] - fit[r][j]);
 }
 
-template <typename T, bool ALIGNED>
+extern __shared__ __attribute__((aligned(16))) double fv_wide_b[];  // WIDE: FV_R x nc coefficients
+
+template <typename T, bool ALIGNED, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_fv_genes(const T* __restrict__ y, int64_t rows, int64_t n, int64_t ldy, const double* __restrict__ u, const double* __restrict__ c,
 												   int nc, int64_t ldc, const double* __restrict__ a, const double* __restrict__ mi, double* __restrict__ b,
 												   double* __restrict__ mean, double* __restrict__ sc, int32_t* __restrict__ flags) {
-	__shared__ double s_b[FV_R][64];
+	__shared__ double s_bn[FV_R][64];
 	__shared__ double sm[4][FV_R];
 	__shared__ double s_mean[FV_R];
+	double* const s_b = WIDE ? fv_wide_b : &s_bn[0][0];
+	const int ldb = WIDE ? nc : 64;
 	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
 	const int64_t row0 = (int64_t)blockIdx.x * FV_R;
 	for (int i = tid; i < FV_R * nc; i += 256) {  // b_g = M^+ a_g
 		const int r = i / nc, q = i % nc;
 		double t = 0.0;
 		if (row0 + r < rows) {
-			for (int d = 0; d < nc; d++) t = fma(mi[q * nc + d], a[(row0 + r) * nc + d], t);
+			if constexpr (WIDE) {  // (M^+ is symmetric: column q, consecutive lanes on consecutive addresses)
+				for (int d = 0; d < nc; d++) t = fma(mi[(int64_t)d * nc + q], a[(row0 + r) * nc + d], t);
+			} else {
+				for (int d = 0; d < nc; d++) t = fma(mi[q * nc + d], a[(row0 + r) * nc + d], t);
+			}
 			b[(row0 + r) * nc + q] = t;
 		}
-		s_b[r][q] = t;
+		s_b[r * ldb + q] = t;
 	}
 	__syncthreads();
 	const T* yr[FV_R];
@@ -153,7 +166,7 @@ __global__ void __launch_bounds__(256) k_fv_genes(const T* __restrict__ y, int64
 	for (int r = 0; r < FV_R; r++) acc[r] = 0.0;
 	for (int64_t k = (int64_t)tid * 4; k < n; k += 1024) {
 		double res[FV_R][4];
-		fv_resid<T, ALIGNED>(yr, k, n, u, c, nc, ldc, s_b, res);
+		fv_resid<T, ALIGNED>(yr, k, n, u, c, nc, ldc, s_b, ldb, res);
 #pragma unroll
 		for (int r = 0; r < FV_R; r++) acc[r] += (res[r][0] + res[r][1]) + (res[r][2] + res[r][3]);
 	}
@@ -167,7 +180,7 @@ __global__ void __launch_bounds__(256) k_fv_genes(const T* __restrict__ y, int64
 	__syncthreads();
 	for (int64_t k = (int64_t)tid * 4; k < n; k += 1024) {  // the second sweep: about the mean (the rows come from L2)
 		double res[FV_R][4];
-		fv_resid<T, ALIGNED>(yr, k, n, u, c, nc, ldc, s_b, res);
+		fv_resid<T, ALIGNED>(yr, k, n, u, c, nc, ldc, s_b, ldb, res);
 #pragma unroll
 		for (int r = 0; r < FV_R; r++)
 #pragma unroll
@@ -185,18 +198,20 @@ __global__ void __launch_bounds__(256) k_fv_genes(const T* __restrict__ y, int64
 	}
 }
 
-template <typename T, bool ALIGNED>
+template <typename T, bool ALIGNED, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_fv_cells(const T* __restrict__ y, int64_t rows, int64_t n, int64_t ldy, const double* __restrict__ u, const double* __restrict__ c,
 												   int nc, int64_t ldc, const double* __restrict__ b, const double* __restrict__ mean, const double* __restrict__ sc,
 												   double* __restrict__ partial) {
-	__shared__ double s_b[FV_TR][64];
+	__shared__ double s_bn[WIDE ? 1 : FV_TR][64];
 	__shared__ double s_m[FV_TR], s_s[FV_TR];
 	const int tid = threadIdx.x;
 	const int64_t k = ((int64_t)blockIdx.x * 256 + tid) * 4, row0 = (int64_t)blockIdx.y * FV_TR;
 	const int nr = (int)(rows - row0 < FV_TR ? rows - row0 : FV_TR);
-	for (int i = tid; i < FV_TR * nc; i += 256) {
-		const int r = i / nc, q = i % nc;
-		s_b[r][q] = r < nr ? b[(row0 + r) * nc + q] : 0.0;
+	if constexpr (!WIDE) {
+		for (int i = tid; i < FV_TR * nc; i += 256) {
+			const int r = i / nc, q = i % nc;
+			s_bn[r][q] = r < nr ? b[(row0 + r) * nc + q] : 0.0;
+		}
 	}
 	if (tid < FV_TR) {
 		s_m[tid] = tid < nr ? mean[row0 + tid] : 0.0;
@@ -209,7 +224,17 @@ __global__ void __launch_bounds__(256) k_fv_cells(const T* __restrict__ y, int64
 #pragma unroll
 		for (int r = 0; r < FV_R; r++) yr[r] = y + (r0 + r < nr ? row0 + r0 + r : rows - 1) * ldy;
 		double res[FV_R][4];
-		fv_resid<T, ALIGNED>(yr, k, n, u, c, nc, ldc, s_b + r0, res);
+		if constexpr (WIDE) {  // the table of these FV_R genes (nr and r0 are the same for every thread of the workgroup: the barriers are uniform)
+			__syncthreads();
+			for (int i = tid; i < FV_R * nc; i += 256) {
+				const int r = i / nc, q = i % nc;
+				fv_wide_b[i] = r0 + r < nr ? b[(row0 + r0 + r) * nc + q] : 0.0;
+			}
+			__syncthreads();
+			fv_resid<T, ALIGNED>(yr, k, n, u, c, nc, ldc, fv_wide_b, nc, res);
+		} else {
+			fv_resid<T, ALIGNED>(yr, k, n, u, c, nc, ldc, &s_bn[r0][0], 64, res);
+		}
 #pragma unroll
 		for (int r = 0; r < FV_R; r++)
 			if (r0 + r < nr) {
@@ -245,7 +270,7 @@ static bool fv_aligned(const void* d_y, int y_dtype, int64_t ldy, const double* 
 static int fv_check(const char* what, const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_c, int64_t nc, int64_t ldc) {
 	NRM_REQUIRE(y_dtype == NRM_F32 || y_dtype == NRM_F64, "%s: bad dtype", what);
 	NRM_REQUIRE(d_y && d_c && rows > 0 && n > 0 && ldy >= n && ldc >= n, "%s: bad shape", what);
-	NRM_REQUIRE(nc >= 1 && nc <= FV_NC, "%s: 1 to %d covariates", what, FV_NC);
+	NRM_REQUIRE(nc >= 1 && nc <= NRM_WIDE_NC, "%s: 1 to %d covariates", what, NRM_WIDE_NC);
 	return NRM_OK;
 }
 
@@ -257,6 +282,19 @@ static int fv_check(const char* what, const void* d_y, int y_dtype, int64_t rows
 		} else {                                                                                              \
 			if (al) hipLaunchKernelGGL((KERNEL<float, true>), GRID, dim3(256), 0, st, (const float*)d_y, __VA_ARGS__);    \
 			else hipLaunchKernelGGL((KERNEL<float, false>), GRID, dim3(256), 0, st, (const float*)d_y, __VA_ARGS__);      \
+		}                                                                                                     \
+	} while (0)
+
+// the WIDE instantiations (nc > FV_NC): FV_R x nc doubles of dynamic LDS
+#define FV_LAUNCH_WIDE(KERNEL, GRID, ...)                                                                     \
+	do {                                                                                                      \
+		const size_t lds = (size_t)FV_R * (size_t)nc * sizeof(double);                                        \
+		if (y_dtype == NRM_F64) {                                                                             \
+			if (al) hipLaunchKernelGGL((KERNEL<double, true, true>), GRID, dim3(256), lds, st, (const double*)d_y, __VA_ARGS__);  \
+			else hipLaunchKernelGGL((KERNEL<double, false, true>), GRID, dim3(256), lds, st, (const double*)d_y, __VA_ARGS__);    \
+		} else {                                                                                              \
+			if (al) hipLaunchKernelGGL((KERNEL<float, true, true>), GRID, dim3(256), lds, st, (const float*)d_y, __VA_ARGS__);    \
+			else hipLaunchKernelGGL((KERNEL<float, false, true>), GRID, dim3(256), lds, st, (const float*)d_y, __VA_ARGS__);      \
 		}                                                                                                     \
 	} while (0)
 
@@ -275,7 +313,8 @@ extern "C" int nrm_fitvar_genes(const void* d_y, int y_dtype, int64_t rows, int6
 	NRM_REQUIRE(d_u && d_a && d_mi && d_b && d_mean && d_sc && d_flags, "nrm_fitvar_genes: null pointer");
 	hipStream_t st = (hipStream_t)stream;
 	const bool al = fv_aligned(d_y, y_dtype, ldy, d_u, d_c, ldc);
-	FV_LAUNCH(k_fv_genes, dim3((unsigned)((rows + FV_R - 1) / FV_R)), rows, n, ldy, d_u, d_c, (int)nc, ldc, d_a, d_mi, d_b, d_mean, d_sc, d_flags);
+	if (nc > FV_NC) FV_LAUNCH_WIDE(k_fv_genes, dim3((unsigned)((rows + FV_R - 1) / FV_R)), rows, n, ldy, d_u, d_c, (int)nc, ldc, d_a, d_mi, d_b, d_mean, d_sc, d_flags);
+	else FV_LAUNCH(k_fv_genes, dim3((unsigned)((rows + FV_R - 1) / FV_R)), rows, n, ldy, d_u, d_c, (int)nc, ldc, d_a, d_mi, d_b, d_mean, d_sc, d_flags);
 	return nrm_check_launch("k_fv_genes");
 }
 
@@ -287,7 +326,8 @@ extern "C" int nrm_fitvar_cells(const void* d_y, int y_dtype, int64_t rows, int6
 	NRM_REQUIRE(tiles <= 65535, "nrm_fitvar_cells: at most %d rows", 65535 * FV_TR);
 	hipStream_t st = (hipStream_t)stream;
 	const bool al = fv_aligned(d_y, y_dtype, ldy, d_u, d_c, ldc);
-	FV_LAUNCH(k_fv_cells, dim3((unsigned)((n + 1023) / 1024), (unsigned)tiles), rows, n, ldy, d_u, d_c, (int)nc, ldc, d_b, d_mean, d_sc, d_partial);
+	if (nc > FV_NC) FV_LAUNCH_WIDE(k_fv_cells, dim3((unsigned)((n + 1023) / 1024), (unsigned)tiles), rows, n, ldy, d_u, d_c, (int)nc, ldc, d_b, d_mean, d_sc, d_partial);
+	else FV_LAUNCH(k_fv_cells, dim3((unsigned)((n + 1023) / 1024), (unsigned)tiles), rows, n, ldy, d_u, d_c, (int)nc, ldc, d_b, d_mean, d_sc, d_partial);
 	NRM_TRY_RC(nrm_check_launch("k_fv_cells"));
 	hipLaunchKernelGGL(k_fv_finish, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_partial, tiles, n, rows, d_v);
 	return nrm_check_launch("k_fv_finish");

@@ -212,3 +212,31 @@ extern "C" int nrm_gram_f64_band(const double* d_a, const double* d_b, int64_t m
 		hipLaunchKernelGGL(k_gram_fixup<0>, dim3((unsigned)(s.tiles_al + s.tiles_sk), GM / GFIX_ROWS), dim3(256), 0, (hipStream_t)stream, d_dot, ldd, symmetric, s);
 	return nrm_check_launch("k_gram_f64");
 }
+
+// The same contraction with EVERY tile computed whole by one workgroup (no K-aligned parts, no stream-K tail, no fix-up): each entry is then one chain of
+// multiply-adds over the cells in a fixed order that depends on nothing but its two rows -- not on how many tiles the launch has, so a caller that cuts one
+// problem into launches of different shapes (normvar with many covariates: gene blocks x panels of pair products, csrc/nrm_normvar_wide.hip) gets the same
+// bits whatever the cut.  The last partial wave of tiles leaves workgroups idle: for launches of many tiles.
+extern "C" int nrm_gram_f64_whole(const double* d_a, const double* d_b, int64_t m_pad, int64_t n_pad, int64_t k_pad, int64_t lda, int64_t ldb, double* d_dot,
+								  int64_t ldd, int64_t m_rows, int64_t n_rows, void* stream) {
+	NRM_REQUIRE(m_pad >= 0 && n_pad >= 0 && k_pad > 0, "nrm_gram_f64_whole: bad sizes");
+	NRM_REQUIRE(m_pad % GM == 0 && n_pad % GN == 0 && k_pad % GK == 0, "nrm_gram_f64_whole: sizes must be padded to %d/%d/%d", GM, GN, GK);
+	NRM_REQUIRE(lda >= k_pad && ldb >= k_pad && ldd >= n_pad, "nrm_gram_f64_whole: pitch too small");
+	NRM_REQUIRE(lda % 2 == 0 && ldb % 2 == 0 && ldd % 2 == 0, "nrm_gram_f64_whole: pitches must be even (16-byte rows)");
+	if (m_pad == 0 || n_pad == 0) return NRM_OK;
+	NRM_REQUIRE(d_a && d_b && d_dot, "nrm_gram_f64_whole: null pointer");
+	NRM_REQUIRE(((uintptr_t)d_a % 16 == 0) && ((uintptr_t)d_b % 16 == 0), "nrm_gram_f64_whole: operands must be 16-byte aligned");
+	if (g_num_cu == 0) {
+		int dev = 0;
+		NRM_HIP(hipGetDevice(&dev));
+		NRM_HIP(hipDeviceGetAttribute(&g_num_cu, hipDeviceAttributeMultiprocessorCount, dev));
+		if (g_num_cu <= 0) g_num_cu = 256;
+	}
+	GramSched s;
+	NRM_TRY_RC(gram_plan(s, m_pad, n_pad, k_pad / GK, 0, m_rows, n_rows, 0, m_pad, 2 * g_num_cu, nullptr));
+	s.tiles_dp += s.tiles_al + s.tiles_sk;  // every tile whole: workgroup p takes tiles p, p + nwg, ...
+	s.tiles_al = s.tiles_sk = s.units_per_wg = 0;
+	s.parts = 1;
+	hipLaunchKernelGGL(k_gram_f64, dim3((unsigned)s.nwg), dim3(256), 0, (hipStream_t)stream, d_a, d_b, lda, ldb, d_dot, ldd, 0, s);
+	return nrm_check_launch("k_gram_f64 (whole tiles)");
+}

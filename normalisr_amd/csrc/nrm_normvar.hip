@@ -129,20 +129,25 @@ __global__ void __launch_bounds__(256) k_nv_weights(const T* __restrict__ y, int
 // pass 2: out = scale_g * e_gk * (y_gk - sum_c b_gc C_ck)      (norm.py:157 per gene, :259)
 // Four cells per thread and iteration, the loads of all NV_R rows, the weights and (batch by batch) the covariates issued before anything is used: the first
 // form loaded one 4-byte value per row and cell and waited for each (see nv_ld4).
-template <typename T, typename OutT, bool ALIGNED>
+// WIDE (more than 64 covariates, up to NRM_WIDE_NC: the rows of the basis B of csrc/nrm_normvar_wide.hip): the coefficients in dynamic LDS, NV_R x nc doubles.
+extern __shared__ __attribute__((aligned(16))) double nv_wide_b[];
+
+template <typename T, typename OutT, bool ALIGNED, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_nv_apply(const T* __restrict__ y, int64_t rows, int64_t n, int64_t ldy, const double* __restrict__ lnw,
 												  const double* __restrict__ wt, const double* __restrict__ c, int nc, int64_t ldc,
 												  const double* __restrict__ b, const double* __restrict__ scale, OutT* __restrict__ out,
 												  int64_t ldo, int32_t* __restrict__ flags) {
-	__shared__ double s_b[NV_R][64];
+	__shared__ double s_bn[NV_R][64];
 	__shared__ double tab[64];
+	double* const s_b = WIDE ? nv_wide_b : &s_bn[0][0];
+	const int ldb = WIDE ? nc : 64;
 	bool bad = false;
 	const int tid = threadIdx.x;
 	nv_exp_table(tab, tid);
 	const int64_t row0 = (int64_t)blockIdx.x * NV_R;
 	for (int i = tid; i < NV_R * nc; i += 256) {
 		const int r = i / nc, q = i % nc;
-		s_b[r][q] = row0 + r < rows ? b[(row0 + r) * nc + q] : 0.0;
+		s_b[r * ldb + q] = row0 + r < rows ? b[(row0 + r) * nc + q] : 0.0;
 	}
 	__syncthreads();
 	double ex[NV_R], sc[NV_R];
@@ -176,7 +181,7 @@ __global__ void __launch_bounds__(256) k_nv_apply(const T* __restrict__ y, int64
 #pragma unroll
 			for (int r = 0; r < NV_R; r++)
 #pragma unroll
-				for (int v = 0; v < 4; v++) fit[r][v] = fma(s_b[r][q], cv[v], fit[r][v]);
+				for (int v = 0; v < 4; v++) fit[r][v] = fma(s_b[r * ldb + q], cv[v], fit[r][v]);
 		}
 #pragma unroll
 		for (int r = 0; r < NV_R; r++) {
@@ -208,7 +213,7 @@ __global__ void __launch_bounds__(256) k_nv_apply(const T* __restrict__ y, int64
 		for (int q = 0; q < nc; q++) {
 			const double cv = c[(int64_t)q * ldc + k];
 #pragma unroll
-			for (int r = 0; r < NV_R; r++) fit[r] = fma(s_b[r][q], cv, fit[r]);
+			for (int r = 0; r < NV_R; r++) fit[r] = fma(s_b[r * ldb + q], cv, fit[r]);
 		}
 #pragma unroll
 		for (int r = 0; r < NV_R; r++)
@@ -280,12 +285,21 @@ extern "C" int nrm_normvar_apply(const void* d_y, int y_dtype, int64_t rows, int
 								 const double* d_c, int64_t nc, int64_t ldc, const double* d_b, const double* d_scale, void* d_out, int out_dtype,
 								 int64_t ldo, int32_t* d_flags, void* stream) {
 	NRM_REQUIRE((y_dtype == NRM_F32 || y_dtype == NRM_F64) && (out_dtype == NRM_F32 || out_dtype == NRM_F64), "nrm_normvar_apply: bad dtype");
-	NRM_REQUIRE(rows > 0 && n > 0 && ldy >= n && ldo >= n && nc > 0 && nc <= 64 && ldc >= n, "Unmatched gene or cell counts.");
+	NRM_REQUIRE(rows > 0 && n > 0 && ldy >= n && ldo >= n && nc > 0 && nc <= NRM_WIDE_NC && ldc >= n, "Unmatched gene or cell counts.");
 	NRM_REQUIRE(d_y && d_lnw && d_wt && d_c && d_b && d_scale && d_out, "nrm_normvar_apply: null pointer");
 	dim3 grid((unsigned)((rows + NV_R - 1) / NV_R));
 	hipStream_t st = (hipStream_t)stream;
 	const bool al = nv_aligned(d_y, y_dtype, ldy, d_lnw, d_c, ldc) && (uintptr_t)d_out % 16 == 0 && (ldo * (out_dtype == NRM_F64 ? 8 : 4)) % 16 == 0;
-#define NV_LAUNCH2(TY, TO, AL) hipLaunchKernelGGL((k_nv_apply<TY, TO, AL>), grid, dim3(256), 0, st, (const TY*)d_y, rows, n, ldy, d_lnw, d_wt, d_c, (int)nc, ldc, d_b, d_scale, (TO*)d_out, ldo, d_flags)
+	const bool wide = nc > 64;  // the coefficient table in dynamic LDS (NV_R x nc doubles: 32 KiB at NRM_WIDE_NC)
+	const size_t lds = wide ? (size_t)NV_R * (size_t)nc * sizeof(double) : 0;
+#define NV_LAUNCH3(TY, TO, AL, WD) hipLaunchKernelGGL((k_nv_apply<TY, TO, AL, WD>), grid, dim3(256), lds, st, (const TY*)d_y, rows, n, ldy, d_lnw, d_wt, d_c, (int)nc, ldc, d_b, d_scale, (TO*)d_out, ldo, d_flags)
+#define NV_LAUNCH2(TY, TO, AL)           \
+	do {                                 \
+		if (wide)                        \
+			NV_LAUNCH3(TY, TO, AL, true);  \
+		else                             \
+			NV_LAUNCH3(TY, TO, AL, false); \
+	} while (0)
 #define NV_LAUNCH(TY, TO)        \
 	do {                         \
 		if (al)                  \
@@ -299,6 +313,7 @@ extern "C" int nrm_normvar_apply(const void* d_y, int y_dtype, int64_t rows, int
 	else NV_LAUNCH(float, float);
 #undef NV_LAUNCH
 #undef NV_LAUNCH2
+#undef NV_LAUNCH3
 	return nrm_check_launch("k_nv_apply");
 }
 

@@ -142,14 +142,141 @@ def _normvar_host_entry(dt, dc, w, wt, dextra, cat, keepvar, tol, out_dtype):
 	return ans
 
 
+WIDE_SAFETY = 4.0  # c of the rank certificate below: the margin for the rounding of the computed eigenvalues ("normvar with hundreds of covariates")
+
+
+def wide_covariates():
+	"""The largest covariate count of compute_var and normvar (nrm_wide_covariates(): the constant lives in the library)."""
+	return int(_lib.load().nrm_wide_covariates())
+
+
+def _check_wide(what, nc, ns):
+	"""More than 63 covariates: more cells than covariates (with as many covariates as cells there is no residual to fit and the reference divides by zero) and
+	at most nrm_wide_covariates() of them.  NotImplementedError before any device call."""
+	if ns <= nc:
+		raise NotImplementedError('{} on the device takes more than 63 covariates only with more cells than covariates ({} covariates, {} cells).'.format(what, nc, ns))
+	lim = wide_covariates()
+	if nc > lim:
+		raise NotImplementedError('{} on the device takes 1 to {} covariates.'.format(what, lim))
+
+
+def _wide_basis(dc, w, wt, tol=1E-8, safety=WIDE_SAFETY):
+	"""(B, r, certified, gaps) for normvar with many covariates.  B (r, n_cell) = Lambda_r^-1/2 U_r^T dc from the eigen-decomposition of dc dc^T, r by the
+	rule of inv_rank (eigenvalues >= tol x the largest): an orthonormal basis of the covariates' row space.  diag(e_g) is invertible (e_gk = w_k^wt_g > 0), so
+	B diag(e_g) spans what dc diag(e_g) spans: one basis serves every gene, and M_g = B diag(e_g^2) B^T is positive definite with condition <= kappa.
+	certified: every gene's matrix dc diag(e_g^2) dc^T has rank r under the reference's own rule (norm.py:154-159 through association.py:77).  By Ostrowski's
+	theorem its eigenvalues lie in [e_min^2 lambda_i, e_max^2 lambda_i], so with kappa = (e_max / e_min)^2 over all genes and cells (e = 1 where wt_g = 0) and
+	the margin c = safety for the rounding of the computed lambda, it is enough that
+	    lambda_r / lambda_1 >= c tol kappa      and      lambda_{r+1} / lambda_1 < tol / (c kappa).
+	False means "no certificate" (nearly collinear covariates, extreme weights), never "rank deficient"; gaps = (lambda_r / lambda_1, lambda_{r+1} / lambda_1, kappa)."""
+	c64 = np.asarray(dc, dtype=np.float64)
+	nc = c64.shape[0]
+	lam, u = np.linalg.eigh(np.matmul(c64, c64.T))
+	lam, u = lam[::-1], u[:, ::-1]
+	assert np.isfinite(lam).all() and lam[0] > 0  # (the reference: 0 / 0 in inv_rank for covariates that are all zero, infs or NaNs refused)
+	r = int((lam >= tol * lam[0]).sum())
+	w, wt = np.asarray(w, dtype=np.float64), np.asarray(wt, dtype=np.float64)
+	lw = np.log(np.array([w.min(), w.max()]))
+	ex = wt[wt != 0]
+	le = np.outer(np.array([ex.min(), ex.max()]), lw).ravel() if ex.size else np.zeros(1)
+	if (wt == 0).any():
+		le = np.append(le, 0.0)
+	with np.errstate(over='ignore'):
+		kappa = float(np.exp(2 * (le.max() - le.min())))
+	hi = float(lam[r - 1] / lam[0])
+	lo = float(max(lam[r], 0.0) / lam[0]) if r < nc else 0.0
+	certified = bool(np.isfinite(kappa) and hi >= safety * tol * kappa and (r == nc or lo < tol / (safety * kappa)))
+	b = (u[:, :r] / np.sqrt(lam[:r])).T @ c64
+	return b, r, certified, (hi, lo, kappa)
+
+
+def _normvar_wide_reference(dt, dc, w, wt, keepvar, tol=1E-8):
+	"""The reference's per-gene algorithm (norm.py:150-163,244-259) in host numpy with inv_rank: one (nc, nc) pseudo-inverse per gene.  What normvar does for
+	covariates without the certificate of _wide_basis -- slow, and the reference's answer."""
+	dt, c64 = np.asarray(dt, dtype=np.float64), np.asarray(dc, dtype=np.float64)
+	w, wt = np.asarray(w, dtype=np.float64), np.asarray(wt, dtype=np.float64)
+	out = np.empty_like(dt)
+	for g in range(dt.shape[0]):
+		e = w**wt[g] if wt[g] != 0 else np.ones_like(w)
+		y, c = dt[g] * e, c64 * e
+		mi, r = inv_rank(np.matmul(c, c.T), tol)
+		if r <= 0:
+			raise RuntimeError('Zero-rank covariates found.')
+		res = y - np.matmul(np.matmul(mi, np.matmul(c, y)), c)
+		if keepvar:
+			with np.errstate(divide='ignore', invalid='ignore'):
+				res = res * (np.sqrt(((y - y.mean())**2).mean()) / np.sqrt((res**2).mean()))**wt[g]
+		out[g] = res
+	return out
+
+
+def _wide_blocks(nt, ns, r):
+	"""(genes per block, pair rows per panel) of the wide normvar path from a byte budget: a gene holds its packed M_g (r (r + 1) / 2 doubles) and its rows of U and
+	V; a panel row is one row of P.  NRM_DEBUG nv_gene_block / nv_panel_rows set them (tests: several blocks and panels at small sizes)."""
+	npair = r * (r + 1) // 2
+	kp = _round_up(ns, K_TILE)
+	per_gene = 8 * (_round_up(npair, ROW_TILE) + ROW_TILE + 2 * kp + _round_up(r, ROW_TILE))
+	gb = max(ROW_TILE, (3 << 29) // per_gene // ROW_TILE * ROW_TILE)  # 1.5 GiB
+	pr = max(ROW_TILE, (1 << 28) // (8 * kp) // ROW_TILE * ROW_TILE)  # 256 MiB
+	gb = int(_opts.debug('nv_gene_block', gb))
+	pr = int(_opts.debug('nv_panel_rows', pr))
+	if gb <= 0 or pr <= 0:
+		raise ValueError('nv_gene_block and nv_panel_rows must be positive.')
+	return min(gb, nt), min(pr, npair)
+
+
+def _normvar_wide(eng, y, ycode, nt, ns, d_lnw, d_wt, basis, r, keepvar, out, ocode):
+	"""normvar's result for many covariates, on the device (csrc/nrm_normvar_wide.hip): per block of genes, U = e^2 and V = e^2 y (nrm_normvar_weights), the
+	packed M_g as rows of U P^T with P built a panel at a time (nrm_normvar_pairs) and a_g = V B^T, both on the fp64 matrix cores with whole tiles (the same bits
+	for every block and panel size), a Cholesky solve per gene (nrm_normvar_chol); then one result pass with B as the covariates (nrm_normvar_apply).
+	Returns the counters of nrm_normvar_chol (int32[4] on the device)."""
+	torch, lib = eng.torch, eng.lib
+	npair = r * (r + 1) // 2
+	kp = _round_up(ns, K_TILE)
+	gb, pr = _wide_blocks(nt, ns, r)
+	gbp, prp, rp = _round_up(gb, ROW_TILE), _round_up(pr, ROW_TILE), _round_up(r, ROW_TILE)
+	ldm = _round_up(npair, ROW_TILE) + ROW_TILE  # (a panel's launch writes whole 16-column groups: up to 15 columns past its last pair, zeros, before the next panel's)
+	f64 = dict(dtype=torch.float64, device=eng.device)
+	st = eng._stream()
+	bp = torch.zeros((rp, kp), **f64)
+	bp[:r, :ns] = eng.upload(np.ascontiguousarray(basis))
+	u, v = torch.empty((gbp, kp), **f64), torch.empty((gbp, kp), **f64)
+	s1, s2 = torch.empty((gbp, ), **f64), torch.empty((gbp, ), **f64)
+	pan = torch.empty((prp, kp), **f64)
+	m, a = torch.empty((gbp, ldm), **f64), torch.empty((gbp, rp), **f64)
+	d_b, d_scale = torch.empty((nt, r), **f64), torch.empty((nt, ), **f64)
+	status = torch.empty((nt, ), dtype=torch.int32, device=eng.device)
+	cflags = eng.zeros((4, ), torch.int32)
+	ysize = y.element_size()
+	with _engine._Span(eng, 'normvar_wide'):
+		for g0 in range(0, nt, gb):
+			g = min(gb, nt - g0)
+			_lib.check(lib.nrm_normvar_weights(y.data_ptr() + g0 * y.stride(0) * ysize, ycode, g, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr() + 8 * g0, u.data_ptr(),
+											   v.data_ptr(), kp, gbp, s1.data_ptr(), s2.data_ptr(), st))
+			for p0 in range(0, npair, pr):
+				cnt = min(pr, npair - p0)
+				cp = _round_up(cnt, ROW_TILE)
+				_lib.check(lib.nrm_normvar_pairs(bp.data_ptr(), r, ns, kp, p0, cnt, pan.data_ptr(), cp, kp, st))
+				_lib.check(lib.nrm_gram_f64_whole(u.data_ptr(), pan.data_ptr(), gbp, cp, kp, kp, kp, m.data_ptr() + 8 * p0, ldm, g, cnt, st))
+			_lib.check(lib.nrm_gram_f64_whole(v.data_ptr(), bp.data_ptr(), gbp, rp, kp, kp, kp, a.data_ptr(), rp, g, r, st))
+			_lib.check(lib.nrm_normvar_chol(m.data_ptr(), ldm, a.data_ptr(), rp, g, r, s1.data_ptr(), s2.data_ptr(), d_wt.data_ptr() + 8 * g0, ns, 1 if keepvar else 0,
+											d_b.data_ptr() + 8 * g0 * r, d_scale.data_ptr() + 8 * g0, status.data_ptr() + 4 * g0, cflags.data_ptr(), st))
+		_lib.check(lib.nrm_normvar_apply(y.data_ptr(), ycode, nt, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr(), bp.data_ptr(), r, kp, d_b.data_ptr(), d_scale.data_ptr(),
+										 out.data_ptr(), ocode, ns, cflags.data_ptr(), st))
+	eng._normvar_wide_last = dict(rank=r, gene_block=gb, panel_rows=pr, status=status)  # (tests)
+	return cflags
+
+
 def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, normmean=False, tol=1E-8, device_out=False):
 	"""Mean and variance normalisation, same contract as reference norm.py:166-289: returns [dtn, dcn] (+ [dextran]).
 	nth and bs are accepted for compatibility and ignored.
 	dt may be a torch CUDA tensor already in HBM; device_out=True leaves dtn there (a torch tensor) -- what coex / de / binnet take next
 	(examples/GSE123139/code/cmd_coex.sh:38-46 chains the three through files): nothing of the expression matrix crosses PCIe.  With up to 8
 	covariates the whole computation stays on the device (csrc/nrm_normvar.hip: per-gene moments in one pass, pseudo-inverses by a thread per
-	gene with the host's Jacobi code, one more pass writes the result); more covariates take the Gram-launch form with the host's batched
-	pseudo-inverses."""
+	gene with the host's Jacobi code, one more pass writes the result); 9 to 63 covariates take the Gram-launch form with the host's batched
+	pseudo-inverses; 64 to nrm_wide_covariates() (1024), with more cells than covariates, the basis form of csrc/nrm_normvar_wide.hip: one orthonormal
+	basis of the covariates' row space for every gene and a Cholesky solve per gene on the device, when _wide_basis certifies that every gene's reference
+	rank is the basis rank -- otherwise (nearly collinear covariates, extreme weights) the reference's per-gene algorithm on the host, under a warning."""
 	if not _is_dev(dt):
 		dt = np.asarray(dt)
 	dc, w, wt = np.asarray(dc), np.asarray(w), np.asarray(wt)
@@ -173,13 +300,14 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 		raise ValueError('wt must be non-negative.')
 	if cat not in (0, 1, 2):
 		raise ValueError('Invalid cat value.')
-	if nc > 63:
-		raise NotImplementedError('normvar on the device supports at most 63 covariates.')
+	wide = nc > 63
+	if wide:
+		_check_wide('normvar', nc, ns)
 	dt_dtype = np.dtype(str(dt.dtype).replace('torch.', '')) if _is_dev(dt) else dt.dtype
 	out_dtype = np.result_type(dt_dtype, dc.dtype, w.dtype, wt.dtype, np.float32)
 	out_dtype = np.dtype(np.float32) if out_dtype == np.float32 else np.dtype(np.float64)
 	from .association import _use_host_entry
-	if not _is_dev(dt) and not device_out and not normmean and _use_host_entry():
+	if not wide and not _is_dev(dt) and not device_out and not normmean and _use_host_entry():
 		# no torch in this process (or the command line / NRM_HOST_ENTRY=1): the library's whole-problem entry, numpy buffers in and out
 		try:
 			return _normvar_host_entry(dt, dc, w, wt, dextra, cat, keepvar, tol, out_dtype)
@@ -187,12 +315,18 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 			from .association import _have_torch
 			if not _have_torch():
 				raise
+	basis = None
+	if wide:
+		basis, rank, certified, gaps = _wide_basis(dc, w, wt, tol)
+		if not certified:
+			logging.warning('normvar: {} covariates of rank {} without a rank certificate for every gene (lambda_r / lambda_1 = {:.3g}, lambda_r+1 / lambda_1 = {:.3g}, '
+							'weight spread kappa = {:.3g}): taking the reference\'s per-gene pseudo-inverses on the host.  Expect a slow call.'.format(nc, rank, *gaps))
 	eng = _engine.get_engine()
 	with eng.lock:  # one call at a time per device (engine scratch, streams and guard state are shared)
 		torch = eng.torch
 		c64 = np.asarray(dc, dtype=np.float64)
 		npair = nc * (nc + 1) // 2
-		iu = np.triu_indices(nc)
+		iu = np.triu_indices(nc) if not wide else None
 		with torch.cuda.device(eng.device):
 			y = dt if _is_dev(dt) else eng.upload(_engine.as_input(dt))
 			if y.dtype not in (torch.float32, torch.float64):
@@ -206,7 +340,17 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 			tdt = torch.float64 if out_dtype == np.float64 else torch.float32
 			flags = eng.zeros((4, ), torch.int32)
 			on_device = nc <= int(eng.lib.nrm_normvar_device_covariates()) and _opts.debug('normvar', 'device') != 'host'
-			if on_device:
+			if wide:
+				out = torch.empty((nt, ns), dtype=tdt, device=eng.device)
+				if certified:
+					wflags = _normvar_wide(eng, y, ycode, nt, ns, d_lnw, d_wt, basis, rank, keepvar, out, _lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32)
+					wf = wflags.cpu().numpy()
+					assert not wf[0] and not wf[1]  # a pivot that is not positive or a value that is not finite (csrc/nrm_normvar_wide.hip): np.isfinite(dtn).all() (norm.py:286)
+				else:
+					ref = _normvar_wide_reference(y.cpu().numpy(), c64, w, wt, keepvar, tol)
+					assert _finite_within(ref)
+					out.copy_(eng.upload(ref))
+			elif on_device:
 				# everything on the device: one pass sums the per-gene moments, a thread per gene solves its small OLS, one pass writes the result
 				mom = torch.empty((nt, npair + nc + 2), dtype=torch.float64, device=eng.device)
 				d_b = torch.empty((nt, nc), dtype=torch.float64, device=eng.device)
@@ -221,7 +365,7 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 														 d_b.data_ptr(), d_scale.data_ptr(), out.data_ptr(), _lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32, ns,
 														 flags.data_ptr(), eng._stream()))
 				eng._normvar_ranks = d_rank  # (tests: the integer ranks of the last call)
-			if not on_device:
+			if not on_device and not wide:
 				rp, kp = _round_up(nt, ROW_TILE), _round_up(ns, K_TILE)
 				u = torch.empty((rp, kp), dtype=torch.float64, device=eng.device)
 				v = torch.empty((rp, kp), dtype=torch.float64, device=eng.device)
@@ -332,7 +476,7 @@ def _projector(x):
 def compute_var(dt, dc, stepmax=1, eps=1E-6):
 	"""Variance-normalisation multiplier of every cell, same contract as reference norm.py:56-128 (`normalisr fitvar`): returns (n_cell,) weights >= 1.
 	dt: (n_gene, n_cell) logCPM, fp32 or fp64, a numpy array or a torch CUDA tensor already in HBM (lcpm(..., device_out=True)); dc (n_cov, n_cell), 1 to 63
-	rows, rank-deficient sets included (both projections take the pseudo-inverse of inv_rank).  AssertionError for a gene whose residual is constant (the
+	rows, or up to nrm_wide_covariates() (1024) with more cells than covariates (csrc/nrm_fitvar.hip: the coefficient table in dynamic LDS), rank-deficient sets included (both projections take the pseudo-inverse of inv_rank).  AssertionError for a gene whose residual is constant (the
 	reference divides by its zero spread, norm.py:108, and fails norm.py:125)."""
 	if eps <= 0 or stepmax <= 0:
 		raise ValueError('eps and stepmax must be positive.')
@@ -345,8 +489,10 @@ def compute_var(dt, dc, stepmax=1, eps=1E-6):
 		raise ValueError('dt and dc must have the same cell count.')
 	nt, ns = dt.shape
 	nc = dc.shape[0]
-	if nc == 0 or nc > 63:
-		raise NotImplementedError('compute_var on the device takes 1 to 63 covariates.')
+	if nc == 0:
+		raise NotImplementedError('compute_var on the device takes at least one covariate.')
+	if nc > 63:
+		_check_wide('compute_var', nc, ns)
 	if nt == 0 or ns == 0:
 		raise ValueError('dt must not be empty.')
 	c64 = np.ascontiguousarray(dc, dtype=np.float64)
