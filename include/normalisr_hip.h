@@ -800,6 +800,37 @@ int nrm_fitvar_update(const double* d_v, const double* d_c, int64_t nc, int64_t 
 int nrm_fitvar_weights(const double* d_best, int64_t n, double* d_ws, double* d_w, int32_t* d_flags, void* stream);
 int nrm_fitvar_pinv_host(const double* m, int64_t n, double tol, double* inv, int64_t* rank);
 
+/*
+ * Gene-set enrichment (normalisr_amd/enrich.py; csrc/nrm_enrich.hip): what stands between the principal genes and pccovt in the reference's gocovt, as
+ * arithmetic alone.  S study sets against T gene sets over G genes, N of them in the background.  Bit matrices hold W = ceil(G / 64) 64-bit words per row with
+ * pitch W, gene g at bit g % 64 of word g / 64, bits at or beyond G zero; word buffers are 8-byte aligned.  Every entry checks its arguments (null pointers,
+ * S, T or G <= 0, ld < G, more than 2^31 - 1 genes, misaligned buffers: NRM_E_ARG) before any device call.  Counts are exact and every floating-point value
+ * is computed by one lane alone: the same bits on every run.
+ *   nrm_enrich_pack:    d_study (S, G) bytes with pitch ld >= G (a binary network: what nrm_binnet writes; any non-zero byte counts once; nothing at or beyond
+ *       G in a row is read) -> d_words (S, W), ANDed with d_bg (W) when that is not NULL, and d_n[s] = popcount of row s.
+ *   nrm_enrich_overlap: d_k[s * T + t] = popcount(d_study[s] & d_sets[t]) over W words (int32; both operands tiled through LDS, no matrix cores) and
+ *       d_K[t] = popcount(d_sets[t] & d_bg) (d_bg NULL: every gene).  At most 65535 x 64 studies per call.
+ *   nrm_enrich_fisher:  one lane per pair: d_p[s * T + t] = the two-sided Fisher exact P-value of the table (k, n - k, K - k, N - K - n + k) in fp64 by the
+ *       recurrence of csrc/nrm_fisher.h (anchored at the mode with weight 1, walked both ways; p = the sum of the weights <= w(k) (1 + 1e-7) over the sum of
+ *       all, at most 1; no lgamma, nothing overflows; relative error <= 8 L u for a support of L values), and d_odds = (k / n) / (K / N), 0 with p = 1 when n
+ *       or K is 0.
+ *   nrm_enrich_top:     per study the set of smallest p among those with odds > 1 and k >= nmin (nmin < 1 means 1), the lower index of equals; d_top (S) records
+ *       of 32 bytes {int64 index (-1: none qualifies), int64 k, int64 K, double p}.
+ *   nrm_enrich_top_host: nrm_enrich_top's rule (the same predicates, csrc/nrm_fisher.h) on host arrays, no device.
+ *   nrm_fisher_host:    nrm_enrich_fisher's P-value for `count` tables on the host, no device: the same code, the same bits.  NRM_E_ARG for a table with
+ *       K or n outside [0, N], N outside [1, 2^31 - 1] or k outside [max(0, n + K - N), min(n, K)].
+ *   nrm_enrich_host:    the whole problem from host buffers, no torch (as nrm_binnet_host; runs on the device of nrm_set_device): h_study (S, G) bytes with
+ *       pitch ld, h_sets (T, W), h_bg (W) or NULL -> h_k (S, T), h_K (T), h_n (S), h_p and h_odds (S, T), h_top (S) records, *h_N = popcount(h_bg) (G without).
+ */
+int nrm_enrich_pack(const uint8_t* d_study, int64_t S, int64_t G, int64_t ld, const uint64_t* d_bg, uint64_t* d_words, int32_t* d_n, void* stream);
+int nrm_enrich_overlap(const uint64_t* d_study, int64_t S, const uint64_t* d_sets, int64_t T, int64_t G, const uint64_t* d_bg, int32_t* d_k, int32_t* d_K, void* stream);
+int nrm_enrich_fisher(const int32_t* d_k, const int32_t* d_n, const int32_t* d_K, int64_t S, int64_t T, int64_t N, double* d_p, double* d_odds, void* stream);
+int nrm_enrich_top(const int32_t* d_k, const int32_t* d_K, const double* d_p, const double* d_odds, int64_t S, int64_t T, int64_t nmin, void* d_top, void* stream);
+int nrm_enrich_top_host(const int32_t* k, const int32_t* K, const double* p, const double* odds, int64_t S, int64_t T, int64_t nmin, void* top);
+int nrm_fisher_host(const int64_t* N, const int64_t* K, const int64_t* n, const int64_t* k, int64_t count, double* out_p);
+int nrm_enrich_host(const uint8_t* h_study, int64_t S, int64_t G, int64_t ld, const uint64_t* h_sets, int64_t T, const uint64_t* h_bg, int64_t nmin, int32_t* h_k,
+					int32_t* h_K, int32_t* h_n, double* h_p, double* h_odds, void* h_top, int64_t* h_N);
+
 #ifdef __cplusplus
 }
 #endif

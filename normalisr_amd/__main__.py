@@ -2,7 +2,8 @@
 Same sub-commands, positionals and flags as the reference CLI for `lcpm` (__main__.py:164-216), `normcov` (:222-245), `fitvar` (:251-272), `normvar` (:311-352),
 `de` (:358-436), `coex` (:442-492) and `binnet` (:498-509), and for the quality-control steps `qc_reads` (:24-113), `subset` (:120-158) and `qc_outlier`
 (:275-305); global -v (:14-17), help on stderr + exit 1 without arguments (:649-651).  `principal` and `pccovt` are sub-commands of this build's own: the two
-numerical parts of the reference's `gocovt` (:512-597), whose GO enrichment between them is not provided."""
+numerical parts of the reference's `gocovt` (:512-597), whose GO enrichment between them is not provided; `enrich`, also this build's own, does that step
+from local gene-set files (normalisr_amd/enrich.py) and writes the pathway's genes for `pccovt`."""
 import argparse
 import logging
 import sys
@@ -12,7 +13,8 @@ def build_parser():
 	p0 = argparse.ArgumentParser(prog='normalisr', description='Normalisr on AMD MI355X: quality control (qc_reads, subset, qc_outlier), normalisation (lcpm, normcov, '
 								 'fitvar, normvar), association testing (de, coex), network binarisation (binnet) and the covariate of a pathway\'s top principal component '
 								 '(principal, pccovt).  The sub-command gocovt is not provided: its GO enrichment needs goatools and a web service.  Run principal, find the '
-								 'enriched pathway among its genes with any tool, and hand the pathway\'s genes to pccovt.')
+								 'enriched pathway among its genes with any tool, and hand the pathway\'s genes to pccovt.  The sub-command enrich does the first two of these steps on the '
+								 'device from local gene-set files (GMT, or GO as OBO + GAF): Fisher exact tests by this build\'s own contract, not goatools\' output.')
 	p0.add_argument('-v', dest='verbose', action='store_true', help='Verbose mode.')
 	sub = p0.add_subparsers(help='sub-commands', dest='cmd')
 
@@ -116,6 +118,22 @@ def build_parser():
 	p.add_argument('genes_in', help='Input text file of the gene names (rows of net_in), one per line.')
 	p.add_argument('master_out', help='Output text file of the names of the principal genes, same format.')
 	p.add_argument('-n', dest='n', action='store', type=int, default='100', help='Number of top principal genes; genes that tie with the last one are kept too. Default: 100.')
+
+	p = sub.add_parser('enrich', help='Find the gene set most enriched among the principal genes of a binary co-expression network, from local gene-set files, and '
+					   'write its genes for pccovt.')
+	p.add_argument('net_in', help='Input binary co-expression network (genes x genes, 0/1), TSV; net_out of binnet.')
+	p.add_argument('genes_in', help='Input text file of the gene names (rows of net_in), one per line; all of them are the background.')
+	p.add_argument('pathway_out', help='Output text file of the names of the genes of the top enriched set, one per line: pathway_in of pccovt.')
+	g = p.add_mutually_exclusive_group(required=True)
+	g.add_argument('--gmt', dest='gmt', action='store', help='Gene sets as a GMT file: name<TAB>description<TAB>gene<TAB>gene... per line.')
+	g.add_argument('--go', dest='go', nargs=2, metavar=('go_obo', 'goa_gaf'), help='Gene sets from a GO ontology (OBO) and an annotation file (GAF 2.x).')
+	p.add_argument('--key', dest='key', action='store', default='id', choices=('id', 'symbol'),
+				   help='With --go: match genes by the annotation file\'s object id ("id", column 2; default) or symbol ("symbol", column 3).')
+	p.add_argument('-n', dest='n', action='store', type=int, default='100', help='Number of top principal genes; genes that tie with the last one are kept too. Default: 100.')
+	p.add_argument('-m', dest='nmin', action='store', type=int, default='5', help='Fewest principal genes the top set must hold. Default: 5.')
+	p.add_argument('--master_out', dest='master_out', action='store', help='Output text file of the names of the principal genes, one per line.')
+	p.add_argument('--goe_out', dest='goe_out', action='store', help='Output enrichment table, TSV with a header line, sorted by P-value.')
+	p.add_argument('--go_out', dest='go_out', action='store', help='Output text file holding the name (GO id) of the top enriched set.')
 
 	p = sub.add_parser('pccovt', help='Append the top principal component of the chosen genes (a pathway) as a covariate.')
 	p.add_argument('exp_in', help='Normalized expression matrix (genes x cells), TSV.')

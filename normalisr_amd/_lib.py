@@ -156,6 +156,13 @@ _SIGNATURES = {
 	'nrm_fitvar_update': ([_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp], _i32),
 	'nrm_fitvar_weights': ([_vp, _i64, _vp, _vp, _vp, _vp], _i32),
 	'nrm_fitvar_pinv_host': ([_vp, _i64, _dbl, _vp, _vp], _i32),
+	'nrm_enrich_pack': ([_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
+	'nrm_enrich_overlap': ([_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
+	'nrm_enrich_fisher': ([_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp], _i32),
+	'nrm_enrich_top': ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp], _i32),
+	'nrm_enrich_top_host': ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp], _i32),
+	'nrm_fisher_host': ([_vp, _vp, _vp, _vp, _i64, _vp], _i32),
+	'nrm_enrich_host': ([_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 }
 
 _lib = None

@@ -3,7 +3,8 @@
 
 principal_genes takes the row degrees of a binary co-expression network (nrm_net_degree) and keeps every gene whose degree reaches that of the n-th ranked
 one: the selection inside the reference's gotop.  The GO enrichment that follows it there (goe: goatools and a web service) is not part of this build; a user
-runs it with any tool on the list of names and hands the pathway's genes to pccovt.
+runs it with any tool on the list of names and hands the pathway's genes to pccovt -- or with normalisr_amd.enrich, which does that step's arithmetic on the
+device from local gene-set files.
 
 pccovt removes the covariates and the mean from the chosen rows, brings every row to mean square 1, takes the top principal component over the cells and
 appends it as a covariate row.  The reference takes the component from a randomized SVD (sklearn's TruncatedSVD: 5 power iterations from an unseeded

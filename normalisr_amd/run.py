@@ -1,4 +1,4 @@
-"""Command runners and matrix IO behind `normalisr qc_reads | subset | lcpm | normcov | fitvar | qc_outlier | normvar | de | coex | binnet | principal | pccovt`.
+"""Command runners and matrix IO behind `normalisr qc_reads | subset | lcpm | normcov | fitvar | qc_outlier | normvar | de | coex | binnet | principal | enrich | pccovt`.
 
 Every sub-command is one row of COMMANDS: which files are read (and how they are shaped), which command-line
 options become which keyword arguments, which function runs, and which of its results go to which file.
@@ -407,8 +407,8 @@ def qc_outlier(args):
 
 
 # ---- the covariate of a pathway's top principal component: principal, pccovt (the numerical parts of reference run.py:324-354) ---------------------------------
-# The reference's gocovt runs gotop (selection + GO enrichment) and pccovt in one command; the enrichment is not part of this build, so the two parts are commands
-# of their own and the list of genes between them is a file.
+# The reference's gocovt runs gotop (selection + GO enrichment) and pccovt in one command; its enrichment (goatools and a web service) is not part of this build, so
+# the two parts are commands of their own and the list of genes between them is a file.  `enrich` (below) writes that file from local gene-set files.
 
 def principal(args):
 	"""normalisr principal: the names of the principal genes of a binary network (what the reference's gocovt writes to --master_out)."""
@@ -434,6 +434,42 @@ def pccovt(args):
 	out = gocovt.pccovt(dt, dc, namet, pathway, condcov=not args['nocond'])
 	logging.debug('Finish calculation.')
 	file_write_tsv(args['cov_out'], out)
+
+
+def enrich(args):
+	"""normalisr enrich: the principal genes of a binary network, their enrichment in gene sets read from local files with every gene of genes_in as the
+	background, and the genes of the top set written for `normalisr pccovt`.  Files in, files out: through the library's whole-problem entry (nrm_enrich_host),
+	torch not imported; the degrees of the network, already on the host, are summed there."""
+	from . import _lib, gocovt
+	from . import enrich as _enrich
+	net = file_read_tsv(args['net_in'], dtype='u1')
+	genes = file_read_txtlist(args['genes_in'])
+	if net.shape != (len(genes), len(genes)):
+		raise ValueError('Wrong shape for net or namet.')
+	gocovt._check_principal_args(net.shape, args['n'])
+	if args.get('gmt') is not None:
+		sets = _enrich.read_gmt(args['gmt'])
+	else:
+		sets = _enrich.read_go(args['go'][0], args['go'][1], key=args.get('key') or 'id')
+	logging.debug('Start calculation.')
+	sel = gocovt._select_principal((net != 0).sum(axis=1), args['n'])
+	prev = _lib.prefer_host_entry(True)
+	try:
+		res = _enrich.enrich(sel, sets, namet=genes, nmin=args['nmin'])
+	finally:
+		_lib.prefer_host_entry(prev)
+	logging.debug('Finish calculation.')
+	if args.get('master_out') is not None:
+		file_write_txtlist(args['master_out'], genes[sel])
+	if args.get('goe_out') is not None:
+		with open(args['goe_out'], 'w') as fh:
+			fh.write('\t'.join(_enrich.COLUMNS) + '\n')
+			for row in res.table(0):
+				fh.write('\t'.join(fmt_float % v if isinstance(v, float) else str(v) for v in row) + '\n')
+	top = res.top_sets(0)  # (ValueError when no set qualifies: the table above is written first, to see why)
+	if args.get('go_out') is not None:
+		file_write_txtlist(args['go_out'], [top])
+	file_write_txtlist(args['pathway_out'], [str(x) for x in res.genes(int(res.top[0]))])
 
 
 assert __name__ != "__main__"
