@@ -831,6 +831,26 @@ int nrm_fisher_host(const int64_t* N, const int64_t* K, const int64_t* n, const 
 int nrm_enrich_host(const uint8_t* h_study, int64_t S, int64_t G, int64_t ld, const uint64_t* h_sets, int64_t T, const uint64_t* h_bg, int64_t nmin, int32_t* h_k,
 					int32_t* h_K, int32_t* h_n, double* h_p, double* h_odds, void* h_top, int64_t* h_N);
 
+/*
+ * One more covariate for a co-expression problem whose Gram matrix stays in HBM (normalisr_amd/levels.py; csrc/nrm_coex_levels.hip): reference association.py:224-235
+ * applied to an enlarged dc, without residualising again.  With q a unit vector orthogonal to the covariates already removed, the Gram matrix of the residual rows
+ * G = X (I - P) X^T changes to G - a a^T with a = X q taken on the RAW rows (q is orthogonal to the covariates), and the sums of squares to ss - a^2.
+ *   nrm_coex_project:  d_a[k * lda + i] = sum_c X[i, c] Q[k, c] for 1 <= k <= 8 directions per launch.  d_x (nt, ns) NRM_F32 or NRM_F64 with pitch ldx >= ns
+ *       elements, aligned to its element only (a row may start anywhere); d_q (k, ns) fp64 with pitch ldq; d_a (k, nt) fp64 with pitch lda.  Every element of X is
+ *       read once for all k.  Products are rounded to fp64; every sum is a compensated one (two-sum pairs) folded in a fixed order -- a lane over its cells, the
+ *       lanes of a wave, the waves of the workgroup that owns the row: |error| <= 8 u sum_c |x_c q_c|, the same bits on every run, no floating-point atomics.
+ *   nrm_coex_downdate: in place, d_g[i * ld + j] -= sum_k a_ki a_kj, the terms taken for k = 0 .. k - 1 in that order, each product with its rounding error (one fma)
+ *       and every sum a two-sum, the entry rounded once at the end: within 2 u (|G| + sum_k |a_ki a_kj|) for any k, where a chain of k rounded fmas carries k
+ *       roundings; d_ss[i] likewise with a_ki^2.  Every step is symmetric in (i, j) to the bit.  VALID AFTERWARDS: the
+ *       64 x 64 tiles with column tile >= row tile, restricted to i, j < nt -- every (i, j) with j / 64 >= i / 64, which holds dot[min(i, j), max(i, j)], what
+ *       nrm_assoc_sweep(symmetric != 0) reads; inside the diagonal tiles both (i, j) and (j, i) are updated and stay equal bit for bit.  Tiles below the diagonal
+ *       and columns >= nt are not touched.  d_counters (int32[2], integer atomics) are incremented: [0] for every row whose new d_ss is not finite or <= 0,
+ *       [1] for every row whose new d_ss < 2^-10 d_ss_ref[i] (d_ss_ref: the sums of squares of the last from-scratch build).
+ */
+int nrm_coex_project(const void* d_x, int x_dtype, int64_t nt, int64_t ns, int64_t ldx, const double* d_q, int64_t k, int64_t ldq, double* d_a, int64_t lda, void* stream);
+int nrm_coex_downdate(double* d_g, int64_t nt, int64_t ld, double* d_ss, const double* d_ss_ref, const double* d_a, int64_t k, int64_t lda, int32_t* d_counters,
+					  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,27 @@ def build_parser():
 	p.add_argument('pathway_in', help='Input text file of the names of the genes whose top principal component is taken, one per line.')
 	p.add_argument('cov_out', help='Output covariate matrix with the new covariate as its last row, same format as cov_in.')
 	p.add_argument('--nocond', dest='nocond', action='store_true', help='Do not remove the existing covariates from the expression before taking the component.')
+
+	p = sub.add_parser('coex_levels', help='Run the co-expression loop (coex, binnet, enrich, pccovt, once per level) in one process with the problem resident on '
+					   'the device: every level appends the top principal component of the top enriched gene set as a covariate.')
+	p.add_argument('exp_in', help='Normalized expression matrix (genes x cells), TSV.')
+	p.add_argument('cov_in', help='Covariate matrix of level 0 (covariates x cells), TSV.')
+	p.add_argument('genes_in', help='Input text file of the gene names (rows of exp_in), one per line; all of them are the background.')
+	p.add_argument('qcut', type=float, help='Q-value cutoff for the binary networks.')
+	p.add_argument('out_dir', help='Output directory: lv{k}_net, lv{k}_master.txt, lv{k}_go.txt, lv{k}_pathway.txt, lv{k}_goe.tsv and lv{k+1}_cov per level k.')
+	g = p.add_mutually_exclusive_group(required=True)
+	g.add_argument('--gmt', dest='gmt', action='store', help='Gene sets as a GMT file: name<TAB>description<TAB>gene<TAB>gene... per line.')
+	g.add_argument('--go', dest='go', nargs=2, metavar=('go_obo', 'goa_gaf'), help='Gene sets from a GO ontology (OBO) and an annotation file (GAF 2.x).')
+	p.add_argument('--key', dest='key', action='store', default='id', choices=('id', 'symbol'),
+				   help='With --go: match genes by the annotation file\'s object id ("id", column 2; default) or symbol ("symbol", column 3).')
+	p.add_argument('-l', dest='lvmax', action='store', type=int, default='5', help='Last level; levels 0 to this one are run. Default: 5.')
+	p.add_argument('-n', dest='n', action='store', type=int, default='100', help='Number of top principal genes; genes that tie with the last one are kept too. Default: 100.')
+	p.add_argument('-m', dest='nmin', action='store', type=int, default='5', help='Fewest principal genes the top set must hold. Default: 5.')
+	p.add_argument('-d', dest='dimr', action='store', type=int, default=None, help='Degrees of freedom removed by preprocessing. Default: 0.')
+	p.add_argument('--ext', dest='ext', action='store', default='.tsv', choices=('.tsv', '.tsv.gz', '.npy'), help='Suffix (and format) of the matrix files. Default: .tsv.')
+	p.add_argument('--pv', dest='pv', action='store_true', help='Also write the P-value matrix of every level, lv{k}_pv.')
+	p.add_argument('--dot', dest='dot', action='store_true', help='Also write the covariance matrix of every level, lv{k}_dot.')
+	p.add_argument('--var', dest='var', action='store_true', help='Also write the variances of every level, lv{k}_var.')
 	return p0
 
 

@@ -163,6 +163,8 @@ _SIGNATURES = {
 	'nrm_enrich_top_host': ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp], _i32),
 	'nrm_fisher_host': ([_vp, _vp, _vp, _vp, _i64, _vp], _i32),
 	'nrm_enrich_host': ([_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+	'nrm_coex_project': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _i32),
+	'nrm_coex_downdate': ([_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp], _i32),
 }
 
 _lib = None
