@@ -246,7 +246,7 @@ def _single0_host_entry(dx, dy, dc64, dci, dcr, dimreduce, return_dot, want_alph
 	ny = nx if samexy else dy.shape[0]
 	nc = dc64.shape[0]
 	odt = np.dtype(out_dtype)
-	code = lambda a: _lib.NRM_F64 if a.dtype == np.float64 else _lib.NRM_F32
+	code = _engine.dtype_code
 	vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 	p, stat = _result((nx, ny), odt), _result((nx, ny), odt)
 	alpha = _result((nx, ny, nc), odt) if (want_alpha and not samexy) else None
@@ -258,7 +258,7 @@ def _single0_host_entry(dx, dy, dc64, dci, dcr, dimreduce, return_dot, want_alph
 	dci = np.ascontiguousarray(dci, dtype=np.float64)
 	_lib.check(lib.nrm_association_tests_host(vp(dx), code(dx), nx, vp(dy), 0 if samexy else code(dy), 0 if samexy else ny, vp(dc64), _lib.NRM_F64, nc, n,
 											  vp(dci), int(dcr), int(dimreduce), 1 if (samexy or return_dot) else 0, vp(p), vp(stat), vp(alpha), vp(varx), vp(vary),
-											  vp(r), vp(t), _lib.NRM_F64 if odt == np.float64 else _lib.NRM_F32))
+											  vp(r), vp(t), _engine.dtype_code(odt)))
 	return dict(p=p, stat=stat, alpha=alpha, varx=varx, vary=vary, r=r, t=t, dof=n - 1 - dcr - dimreduce)
 
 
@@ -312,12 +312,12 @@ def _single14_host_entry(single, dx, dy, dc, lowmem, return_dot, ka):
 	dc64 = np.ascontiguousarray(dc64)
 	dci = np.ascontiguousarray(dci, dtype=np.float64)
 	lib = _lib.load()
-	code = lambda a: _lib.NRM_F64 if a.dtype == np.float64 else _lib.NRM_F32
+	code = _engine.dtype_code
 	vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 	p, stat, vary = (_result((nx, ny), odt) for _ in range(3))
 	varx = np.empty(nx, dtype=odt)
 	alpha = None if lowmem else _result((nx, ny, nc), odt)
-	ocode = _lib.NRM_F64 if odt == np.float64 else _lib.NRM_F32
+	ocode = _engine.dtype_code(odt)
 	if single == 1:
 		_lib.check(lib.nrm_association_tests_single1_host(vp(dx), code(dx), nx, vp(dy), code(dy), ny, vp(dc64), _lib.NRM_F64, nc, n, int(dimreduce), 1 if return_dot else 0,
 														  vp(p), vp(stat), vp(alpha), vp(varx), vp(vary), ocode))

@@ -4,6 +4,8 @@ import logging
 
 import numpy as np
 
+from . import engine as _engine
+
 
 def nodiag(d, split=False):
 	"""Off-diagonal entries of a 2-D matrix, row by row (binnet.py:4-34)."""
@@ -61,7 +63,6 @@ def binnet(net, qcut):
 	thresholded at qcut (binnet.py:134-173).  Returns a boolean (n_gene, n_gene) matrix, diagonal False.
 	A torch CUDA tensor is accepted (and then returned) so that coex -> binnet can stay in HBM."""
 	from . import _lib
-	from . import engine as _engine
 	on_device = hasattr(net, 'is_cuda') and net.is_cuda  # torch tensor already in HBM (e.g. coex(..., device_out=True)[0])
 	if not on_device:
 		net = np.asarray(net)
@@ -79,7 +80,7 @@ def binnet(net, qcut):
 		from .association import _result
 		out = _result((nt, nt), np.uint8)
 		total = ctypes.c_int64(-1)
-		_lib.check(_lib.load().nrm_binnet_host(hp.ctypes.data_as(ctypes.c_void_p), _lib.NRM_F64 if hp.dtype == np.float64 else _lib.NRM_F32, nt, float(qcut),
+		_lib.check(_lib.load().nrm_binnet_host(hp.ctypes.data_as(ctypes.c_void_p), _engine.dtype_code(hp), nt, float(qcut),
 											   out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(total)))
 		if total.value == 0:
 			raise RuntimeError('Empty binary network.')
@@ -94,7 +95,7 @@ def binnet(net, qcut):
 			out = torch.empty((nt, nt), dtype=torch.uint8, device=eng.device)
 			total = torch.zeros(1, dtype=torch.int64, device=eng.device)
 			flags = torch.zeros(2, dtype=torch.int32, device=eng.device)
-			_lib.check(eng.lib.nrm_binnet(d_p.data_ptr(), _lib.NRM_F64 if d_p.dtype == torch.float64 else _lib.NRM_F32, nt, d_p.stride(0),
+			_lib.check(eng.lib.nrm_binnet(d_p.data_ptr(), _engine.dtype_code(d_p), nt, d_p.stride(0),
 										  float(qcut), out.data_ptr(), out.stride(0), total.data_ptr(), flags.data_ptr(), eng._stream()))
 			if int(flags[0].item()):
 				raise AssertionError('P-values must be finite and within [0,1] (binnet.py:151-152).')

@@ -107,7 +107,7 @@ extern "C" int nrm_host_mirror_rows(void* h, int64_t ld_bytes, int elem_bytes, i
 
 extern "C" int nrm_host_pin(void* ptr, int64_t bytes, int threads) {
 	NRM_REQUIRE(ptr != nullptr && bytes > 0, "nrm_host_pin: empty range");
-	NRM_TRY_RC(nrm_bind_device());  // (called from the entries' helper threads too: a fresh thread's current device is 0)
+	NRM_TRY(nrm_bind_device());  // (called from the entries' helper threads too: a fresh thread's current device is 0)
 	const int64_t page = 4096;
 	if (threads <= 0) {
 		threads = (int)std::min<int64_t>(16, std::max<int64_t>(1, bytes / (8 << 20)));
@@ -361,7 +361,7 @@ extern "C" int nrm_association_tests_host(const void* h_dx, int x_dtype, int64_t
 										  int dimreduce, int return_dot, void* h_p, void* h_stat, void* h_alpha, void* h_varx,
 										  void* h_vary, void* h_r, void* h_t, int out_dtype) {
 	std::lock_guard<std::mutex> serial(g_host_entry);
-	NRM_TRY_RC(nrm_bind_device());
+	NRM_TRY(nrm_bind_device());
 	// K2 engine as in the Python host (NRM_GRAM): exact fixed-point contraction on the int8 matrix cores (6 slices = 46 bits; i8x5: 5
 	// slices = 38 bits), or the fp64 matrix-core kernel (f64).  With the integer engine K1 writes the digit planes itself and the
 	// fp64 residuals are never stored.
@@ -437,7 +437,7 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	DevBuf qx, qy, ex, ey, fx, fy;
 	const double guard_tol = guard_tolerance();
 	NRM_TRY(dx.alloc((size_t)nx * n * esize(x_dtype)));
-	NRM_TRY_RC(nrm_upload(h_dx, dx.p, (int64_t)nx * n * esize(x_dtype), 0, (void*)st));  // (from half a GB up: host threads fill page-locked blocks beside the DMA, nrm_upload.hip)
+	NRM_TRY(nrm_upload(h_dx, dx.p, (int64_t)nx * n * esize(x_dtype), 0, (void*)st));  // (from half a GB up: host threads fill page-locked blocks beside the DMA, nrm_upload.hip)
 	// A design matrix with few entries (a CRISPR screen's gRNA incidence): the sparse-design kernels -- the expression rows read once, raw, the
 	// contraction replaced by gathers at the design's entries (nrm_host_entries.hip; what normalisr_amd.engine does for the Python host).
 	// Same size rule as there; NRM_DE_SPARSE=0 switches it off, =force takes it whatever the size.
@@ -453,7 +453,7 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 		const bool off = mode && !strcmp(mode, "0"), force = mode && !strcmp(mode, "force");
 		if (!off && (force || (nx >= 32 && ny >= 64 && n >= 2048 && nx * n >= (1ll << 22)))) {
 			NRM_TRY(dy.alloc((size_t)ny * n * esize(y_dtype)));
-			NRM_TRY_RC(nrm_upload(h_dy, dy.p, (int64_t)ny * n * esize(y_dtype), 0, (void*)st));
+			NRM_TRY(nrm_upload(h_dy, dy.p, (int64_t)ny * n * esize(y_dtype), 0, (void*)st));
 			dy_up = true;
 			int taken = 0;
 			int64_t back = 0;
@@ -483,7 +483,7 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	if (!samexy) {
 		if (!dy_up) {
 			NRM_TRY(dy.alloc((size_t)ny * n * esize(y_dtype)));
-			NRM_TRY_RC(nrm_upload(h_dy, dy.p, (int64_t)ny * n * esize(y_dtype), 0, (void*)st));
+			NRM_TRY(nrm_upload(h_dy, dy.p, (int64_t)ny * n * esize(y_dtype), 0, (void*)st));
 		}
 		NRM_TRY(ssy.alloc((size_t)np_ * 8));
 		if (want_alpha) NRM_TRY(by.alloc((size_t)ny * nc * 8));

@@ -9,25 +9,13 @@
 // tau* is found with counting passes: k <- #{p <= qcut (1+d) k / m} started from above converges to the
 // largest k for which ANY element of rank > k fails the test even with a relative slack d >> rounding error,
 // so only the few distinct values just below that bound need the reference's exact floating-point test.
-#include "nrm_common.h"
+#include "nrm_device.h"
 #include <cstdlib>
 
 #define BN_BINS 1024  // bins of the histogram that tells the threshold search where to start
 
 // Workgroups of BS threads (NW = BS / 64 waves); sm holds 3 NW doubles: [0, NW) for the two-barrier reductions below, [NW, 3 NW) the two
 // alternating slot sets of the one-barrier counting passes.
-template <int NW>
-__device__ __forceinline__ double bn_block_sum(double v, double* sm) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-	__syncthreads();
-	if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-	__syncthreads();
-	double t = 0.0;
-#pragma unroll
-	for (int w = 0; w < NW; w++) t += sm[w];
-	return t;
-}
 template <int NW>
 __device__ __forceinline__ double bn_block_max(double v, double* sm) {
 #pragma unroll
@@ -82,7 +70,7 @@ struct GlobalRow {
 		each([&](double pj) {
 			if (pj <= x) c += 1.0;
 		});
-		return (int64_t)bn_block_sum<BS / 64>(c, sm);
+		return (int64_t)nrm_block_sum<BS / 64, true>(c, sm);
 	}
 	__device__ __forceinline__ double max_le(double x, double* sm) const {
 		double m = -1.0;
@@ -270,7 +258,7 @@ __global__ void __launch_bounds__(Row::THREADS) k_binnet_rows(const T* __restric
 	if (dbg && threadIdx.x == 0) dbg[i * 6] = wall_clock64();
 	Row r(prow, ng, row0 + i);  // row i of this block is gene row0 + i: its diagonal entry sits in that column
 	// validity (binnet.py:151-152): finite and inside [0,1]
-	if (bn_block_sum<NW>(r.bad, sm) > 0 && threadIdx.x == 0) atomicAdd(&flags[0], 1);
+	if (nrm_block_sum<NW, true>(r.bad, sm) > 0 && threadIdx.x == 0) atomicAdd(&flags[0], 1);
 	if (dbg && threadIdx.x == 0) dbg[i * 6 + 1] = wall_clock64();
 	double x = 2.0;       // every entry is a candidate
 	double tau = -1.0;    // tau*: nothing selected yet
@@ -359,7 +347,7 @@ __global__ void __launch_bounds__(Row::THREADS) k_binnet_rows(const T* __restric
 	}
 	__shared__ __attribute__((aligned(16))) unsigned char s_mask[Row::MASK_BYTES];
 	double cnt = r.emit(out + i * ldo, tau, s_mask);
-	cnt = bn_block_sum<NW>(cnt, sm);
+	cnt = nrm_block_sum<NW, true>(cnt, sm);
 	if (threadIdx.x == 0 && cnt > 0) atomicAdd(total, (unsigned long long)cnt);
 	if (dbg && threadIdx.x == 0) dbg[i * 6 + 3] = wall_clock64();
 }

@@ -26,7 +26,7 @@ void nrm_set_error(const char* fmt, ...);
 		}                           \
 	} while (0)
 
-#define NRM_TRY_RC(call)     \
+#define NRM_TRY(call)        \
 	do {                     \
 		int rc_ = (call);    \
 		if (rc_) return rc_; \
@@ -38,6 +38,25 @@ static inline int nrm_check_launch(const char* what) {
 		nrm_set_error("launch of %s failed: %s", what, hipGetErrorString(e));
 		return NRM_E_DEVICE;
 	}
+	return NRM_OK;
+}
+
+// Count matrices (lcpm, qc): bytes of an element of the dtype, 0 for a dtype counts do not come in; GO(type) for the dtype, checked before
+static inline int nrm_count_elem(int dtype) { return dtype == NRM_I64 ? 8 : dtype == NRM_I32 ? 4 : dtype == NRM_I16 ? 2 : dtype == NRM_U8 ? 1 : 0; }
+
+#define NRM_BY_COUNT_DTYPE(GO)           \
+	switch (dtype) {                     \
+		case NRM_I64: GO(int64_t); break; \
+		case NRM_I32: GO(int32_t); break; \
+		case NRM_I16: GO(int16_t); break; \
+		default: GO(uint8_t); break;     \
+	}
+
+// the arrays of a CSR matrix (int64 indptr, int32 indices, data of elem bytes) as every entry that takes one checks them
+static inline int nrm_csr_args_check(const char* what, const void* d_indptr, const void* d_indices, const void* d_data, int elem, int64_t rows, int64_t n, int64_t nnz) {
+	NRM_REQUIRE(d_indptr && rows > 0 && n > 0 && nnz >= 0 && n <= 0x7fffffffLL, "%s: bad shape", what);
+	NRM_REQUIRE(nnz == 0 || (d_indices && d_data), "%s: null pointer", what);
+	NRM_REQUIRE((uintptr_t)d_indptr % 8 == 0 && (uintptr_t)d_indices % 4 == 0 && (uintptr_t)d_data % elem == 0, "%s: misaligned CSR arrays", what);
 	return NRM_OK;
 }
 

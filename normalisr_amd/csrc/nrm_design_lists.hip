@@ -14,7 +14,7 @@
 //                      alone in their cell grouping by grouping, cell codes, the covariates at those cells, the covariate Gram matrix of the
 //                      cells no grouping touches
 // Integer work and byte moves, bound by HBM (two reads of the 200 MB matrix) and launch latency; no matrix cores.
-#include "nrm_common.h"
+#include "nrm_device.h"
 #include "nrm_design.h"
 
 namespace {
@@ -76,8 +76,7 @@ __global__ void __launch_bounds__(256) k_dl_count(const T* __restrict__ X, int64
 				if (x != x) fl |= DL_NAN;
 			}
 		}
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+	mine = nrm_wave_sum(mine);
 	unsigned wfl = 0;
 #pragma unroll
 	for (int b = 0; b < 5; b++)

@@ -189,7 +189,7 @@ extern "C" int nrm_enrich_overlap(const uint64_t* d_study, int64_t S, const uint
 	const int64_t W = (G + 63) / 64;
 	hipStream_t st = (hipStream_t)stream;
 	hipLaunchKernelGGL(k_enrich_setsize, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, (const en_u64*)d_sets, T, W, (const en_u64*)d_bg, d_K);
-	NRM_TRY_RC(nrm_check_launch("k_enrich_setsize"));
+	NRM_TRY(nrm_check_launch("k_enrich_setsize"));
 	hipLaunchKernelGGL(k_enrich_overlap, dim3((unsigned)((T + EN_TILE - 1) / EN_TILE), (unsigned)((S + EN_TILE - 1) / EN_TILE)), dim3(256), 0, st, (const en_u64*)d_study, S,
 					   (const en_u64*)d_sets, T, W, d_k);
 	return nrm_check_launch("k_enrich_overlap");

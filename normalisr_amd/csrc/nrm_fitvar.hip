@@ -16,7 +16,7 @@
 // (nrm_wide_covariates()), the WIDE instantiations of k_fv_genes and k_fv_cells keep FV_R x nc coefficients in dynamic LDS (32 KiB at 1024: no opt-in) -- the
 // per-cell pass then reloads the table for every FV_R genes of its tile -- and b_g = M^+ a_g reads M^+ by columns (it is symmetric), coalesced over nc x nc.
 // The launchers choose by nc; the instantiations for nc <= FV_NC are the ones the library always had.
-#include "nrm_common.h"
+#include "nrm_device.h"
 
 #define FV_R 4    // genes per workgroup of the per-gene passes, and per step of the per-cell pass: they share the loads of the covariates
 #define FV_Q 8    // covariates per sweep of the moments pass
@@ -25,29 +25,6 @@
 
 extern "C" int64_t nrm_fitvar_row_tile(void) { return FV_TR; }
 extern "C" int64_t nrm_wide_covariates(void) { return NRM_WIDE_NC; }
-
-// Four consecutive elements of a row as doubles, zero at and beyond n.  ALIGNED (the launcher: 16-byte aligned rows): 16-byte loads.
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void fv_ld4(const T* __restrict__ row, int64_t k, int64_t n, double (&v)[4]) {
-	if (ALIGNED && k + 4 <= n) {
-		if constexpr (sizeof(T) == 4) {
-			const float4 t = *reinterpret_cast<const float4*>(row + k);
-			v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-		} else {
-			const double2 a = *reinterpret_cast<const double2*>(row + k), b = *reinterpret_cast<const double2*>(row + k + 2);
-			v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-		}
-	} else {
-#pragma unroll
-		for (int j = 0; j < 4; j++) v[j] = k + j < n ? (double)row[k + j] : 0.0;
-	}
-}
-
-__device__ __forceinline__ double fv_wave_sum(double v) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-	return v;
-}
 
 // a (rows, nc): a[g][c] = sum_k y_gk cw_ck, cw = u^2 C
 template <typename T, bool ALIGNED>
@@ -68,11 +45,11 @@ __global__ void __launch_bounds__(256) k_fv_moments(const T* __restrict__ y, int
 		for (int64_t k = (int64_t)tid * 4; k < n; k += 1024) {
 			double yv[FV_R][4];
 #pragma unroll
-			for (int r = 0; r < FV_R; r++) fv_ld4<T, ALIGNED>(yr[r], k, n, yv[r]);
+			for (int r = 0; r < FV_R; r++) nrm_ld4d<T, ALIGNED>(yr[r], k, n, yv[r]);
 #pragma unroll
 			for (int q = 0; q < FV_Q; q++) {
 				double cv[4] = {0.0, 0.0, 0.0, 0.0};
-				if (q0 + q < nc) fv_ld4<double, ALIGNED>(cw + (int64_t)(q0 + q) * ldc, k, n, cv);
+				if (q0 + q < nc) nrm_ld4d<double, ALIGNED>(cw + (int64_t)(q0 + q) * ldc, k, n, cv);
 #pragma unroll
 				for (int r = 0; r < FV_R; r++)
 #pragma unroll
@@ -83,7 +60,7 @@ __global__ void __launch_bounds__(256) k_fv_moments(const T* __restrict__ y, int
 		for (int r = 0; r < FV_R; r++)
 #pragma unroll
 			for (int q = 0; q < FV_Q; q++) {
-				const double t = fv_wave_sum(acc[r][q]);
+				const double t = nrm_wave_sum(acc[r][q]);
 				if (lane == 0) sm[wid][r * FV_Q + q] = t;
 			}
 		__syncthreads();
@@ -100,16 +77,16 @@ template <typename T, bool ALIGNED>
 __device__ __forceinline__ void fv_resid(const T* (&yr)[FV_R], int64_t k, int64_t n, const double* __restrict__ u, const double* __restrict__ c, int nc, int64_t ldc,
 										 const double* s_b, const int ldb, double (&res)[FV_R][4]) {
 	double uv[4], yv[FV_R][4], fit[FV_R][4];
-	fv_ld4<double, ALIGNED>(u, k, n, uv);
+	nrm_ld4d<double, ALIGNED>(u, k, n, uv);
 #pragma unroll
 	for (int r = 0; r < FV_R; r++) {
-		fv_ld4<T, ALIGNED>(yr[r], k, n, yv[r]);
+		nrm_ld4d<T, ALIGNED>(yr[r], k, n, yv[r]);
 #pragma unroll
 		for (int j = 0; j < 4; j++) fit[r][j] = 0.0;
 	}
 	for (int q = 0; q < nc; q++) {
 		double cv[4];
-		fv_ld4<double, ALIGNED>(c + (int64_t)q * ldc, k, n, cv);
+		nrm_ld4d<double, ALIGNED>(c + (int64_t)q * ldc, k, n, cv);
 #pragma unroll
 		for (int r = 0; r < FV_R; r++)
 #pragma unroll
@@ -155,7 +132,7 @@ __global__ void __launch_bounds__(256) k_fv_genes(const T* __restrict__ y, int64
 	auto block_sum = [&](double* dst) {  // dst[r] = the workgroup's sum of acc[r], waves added in order
 #pragma unroll
 		for (int r = 0; r < FV_R; r++) {
-			const double t = fv_wave_sum(acc[r]);
+			const double t = nrm_wave_sum(acc[r]);
 			if (lane == 0) sm[wid][r] = t;
 		}
 		__syncthreads();
@@ -299,7 +276,7 @@ static int fv_check(const char* what, const void* d_y, int y_dtype, int64_t rows
 	} while (0)
 
 extern "C" int nrm_fitvar_moments(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_cw, int64_t nc, int64_t ldc, double* d_a, void* stream) {
-	NRM_TRY_RC(fv_check("nrm_fitvar_moments", d_y, y_dtype, rows, n, ldy, d_cw, nc, ldc));
+	NRM_TRY(fv_check("nrm_fitvar_moments", d_y, y_dtype, rows, n, ldy, d_cw, nc, ldc));
 	NRM_REQUIRE(d_a, "nrm_fitvar_moments: null pointer");
 	hipStream_t st = (hipStream_t)stream;
 	const bool al = fv_aligned(d_y, y_dtype, ldy, nullptr, d_cw, ldc);
@@ -309,7 +286,7 @@ extern "C" int nrm_fitvar_moments(const void* d_y, int y_dtype, int64_t rows, in
 
 extern "C" int nrm_fitvar_genes(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_u, const double* d_c, int64_t nc, int64_t ldc,
 								const double* d_a, const double* d_mi, double* d_b, double* d_mean, double* d_sc, int32_t* d_flags, void* stream) {
-	NRM_TRY_RC(fv_check("nrm_fitvar_genes", d_y, y_dtype, rows, n, ldy, d_c, nc, ldc));
+	NRM_TRY(fv_check("nrm_fitvar_genes", d_y, y_dtype, rows, n, ldy, d_c, nc, ldc));
 	NRM_REQUIRE(d_u && d_a && d_mi && d_b && d_mean && d_sc && d_flags, "nrm_fitvar_genes: null pointer");
 	hipStream_t st = (hipStream_t)stream;
 	const bool al = fv_aligned(d_y, y_dtype, ldy, d_u, d_c, ldc);
@@ -320,7 +297,7 @@ extern "C" int nrm_fitvar_genes(const void* d_y, int y_dtype, int64_t rows, int6
 
 extern "C" int nrm_fitvar_cells(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_u, const double* d_c, int64_t nc, int64_t ldc,
 								const double* d_b, const double* d_mean, const double* d_sc, double* d_partial, double* d_v, void* stream) {
-	NRM_TRY_RC(fv_check("nrm_fitvar_cells", d_y, y_dtype, rows, n, ldy, d_c, nc, ldc));
+	NRM_TRY(fv_check("nrm_fitvar_cells", d_y, y_dtype, rows, n, ldy, d_c, nc, ldc));
 	NRM_REQUIRE(d_u && d_b && d_mean && d_sc && d_partial && d_v, "nrm_fitvar_cells: null pointer");
 	const int64_t tiles = (rows + FV_TR - 1) / FV_TR;
 	NRM_REQUIRE(tiles <= 65535, "nrm_fitvar_cells: at most %d rows", 65535 * FV_TR);
@@ -328,7 +305,7 @@ extern "C" int nrm_fitvar_cells(const void* d_y, int y_dtype, int64_t rows, int6
 	const bool al = fv_aligned(d_y, y_dtype, ldy, d_u, d_c, ldc);
 	if (nc > FV_NC) FV_LAUNCH_WIDE(k_fv_cells, dim3((unsigned)((n + 1023) / 1024), (unsigned)tiles), rows, n, ldy, d_u, d_c, (int)nc, ldc, d_b, d_mean, d_sc, d_partial);
 	else FV_LAUNCH(k_fv_cells, dim3((unsigned)((n + 1023) / 1024), (unsigned)tiles), rows, n, ldy, d_u, d_c, (int)nc, ldc, d_b, d_mean, d_sc, d_partial);
-	NRM_TRY_RC(nrm_check_launch("k_fv_cells"));
+	NRM_TRY(nrm_check_launch("k_fv_cells"));
 	hipLaunchKernelGGL(k_fv_finish, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_partial, tiles, n, rows, d_v);
 	return nrm_check_launch("k_fv_finish");
 }

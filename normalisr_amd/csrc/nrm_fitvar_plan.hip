@@ -260,7 +260,7 @@ extern "C" int64_t nrm_fitvar_plan_workspace(int64_t n, int64_t nc) {
 }
 
 extern "C" int nrm_fitvar_plan_start(int64_t n, double* d_s, double* d_best, double* d_state, void* stream) {
-	NRM_TRY_RC(fvp_check("nrm_fitvar_plan_start", n, 1));
+	NRM_TRY(fvp_check("nrm_fitvar_plan_start", n, 1));
 	NRM_REQUIRE(d_s && d_best && d_state, "nrm_fitvar_plan_start: null pointer");
 	hipLaunchKernelGGL(k_fvp_start, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, d_s, d_best, d_state);
 	return nrm_check_launch("k_fvp_start");
@@ -268,7 +268,7 @@ extern "C" int nrm_fitvar_plan_start(int64_t n, double* d_s, double* d_best, dou
 
 extern "C" int nrm_fitvar_design(const double* d_c, int64_t nc, int64_t ldc, int64_t n, const double* d_s, const double* d_state, double eps, double* d_u, double* d_cw,
 								 double* d_ws, void* stream) {
-	NRM_TRY_RC(fvp_check("nrm_fitvar_design", n, nc));
+	NRM_TRY(fvp_check("nrm_fitvar_design", n, nc));
 	NRM_REQUIRE(d_c && d_s && d_state && d_u && d_cw && d_ws && ldc >= n, "nrm_fitvar_design: bad argument");
 	const FvpScratch w(n, nc, d_ws);
 	hipLaunchKernelGGL(k_fvp_design, dim3((unsigned)w.dchunks), dim3(256), 0, (hipStream_t)stream, d_c, (int)nc, ldc, n, d_s, d_state, eps, d_u, d_cw, w.mpart);
@@ -276,7 +276,7 @@ extern "C" int nrm_fitvar_design(const double* d_c, int64_t nc, int64_t ldc, int
 }
 
 extern "C" int nrm_fitvar_pinv(int64_t n, int64_t nc, double tol, const double* d_state, double eps, const double* d_ws, double* d_mi, int64_t* d_rank, void* stream) {
-	NRM_TRY_RC(fvp_check("nrm_fitvar_pinv", n, nc));
+	NRM_TRY(fvp_check("nrm_fitvar_pinv", n, nc));
 	NRM_REQUIRE(d_state && d_ws && d_mi && d_rank && tol > 0, "nrm_fitvar_pinv: bad argument");
 	const FvpScratch w(n, nc, const_cast<double*>(d_ws));
 	hipLaunchKernelGGL(k_fvp_pinv, dim3(1), dim3(64), 0, (hipStream_t)stream, w.mpart, w.dchunks, (int)nc, tol, d_state, eps, d_mi, d_rank);
@@ -285,27 +285,27 @@ extern "C" int nrm_fitvar_pinv(int64_t n, int64_t nc, double tol, const double* 
 
 extern "C" int nrm_fitvar_update(const double* d_v, const double* d_c, int64_t nc, int64_t ldc, int64_t n, const double* d_m2i, double* d_s, double* d_best,
 								 const double* d_state, double* d_state_next, double eps, double* d_ws, void* stream) {
-	NRM_TRY_RC(fvp_check("nrm_fitvar_update", n, nc));
+	NRM_TRY(fvp_check("nrm_fitvar_update", n, nc));
 	NRM_REQUIRE(d_v && d_c && d_m2i && d_s && d_best && d_state && d_state_next && d_state != d_state_next && d_ws && ldc >= n, "nrm_fitvar_update: bad argument");
 	const FvpScratch w(n, nc, d_ws);
 	hipStream_t st = (hipStream_t)stream;
 	hipLaunchKernelGGL(k_fvp_logsum, dim3((unsigned)w.lchunks), dim3(256), 0, st, d_v, d_c, (int)nc, ldc, n, d_state, eps, w.gpart);
-	NRM_TRY_RC(nrm_check_launch("k_fvp_logsum"));
+	NRM_TRY(nrm_check_launch("k_fvp_logsum"));
 	hipLaunchKernelGGL(k_fvp_new, dim3((unsigned)w.blocks), dim3(256), 0, st, w.gpart, w.lchunks, d_m2i, d_c, (int)nc, ldc, n, d_s, d_state, eps, w.snew, w.minpart);
-	NRM_TRY_RC(nrm_check_launch("k_fvp_new"));
+	NRM_TRY(nrm_check_launch("k_fvp_new"));
 	hipLaunchKernelGGL(k_fvp_apply, dim3((unsigned)w.blocks), dim3(256), 0, st, n, w.blocks, d_s, d_state, eps, w.snew, w.minpart, w.maxpart);
-	NRM_TRY_RC(nrm_check_launch("k_fvp_apply"));
+	NRM_TRY(nrm_check_launch("k_fvp_apply"));
 	hipLaunchKernelGGL(k_fvp_state, dim3((unsigned)w.blocks), dim3(256), 0, st, n, w.blocks, w.snew, w.maxpart, d_state, eps, d_s, d_best, d_state_next);
 	return nrm_check_launch("k_fvp_state");
 }
 
 extern "C" int nrm_fitvar_weights(const double* d_best, int64_t n, double* d_ws, double* d_w, int32_t* d_flags, void* stream) {
-	NRM_TRY_RC(fvp_check("nrm_fitvar_weights", n, 1));
+	NRM_TRY(fvp_check("nrm_fitvar_weights", n, 1));
 	NRM_REQUIRE(d_best && d_ws && d_w && d_flags, "nrm_fitvar_weights: null pointer");
 	const int64_t blocks = (n + FVP_CH - 1) / FVP_CH;
 	hipStream_t st = (hipStream_t)stream;
 	hipLaunchKernelGGL(k_fvp_wmin, dim3((unsigned)blocks), dim3(256), 0, st, n, d_best, d_ws);
-	NRM_TRY_RC(nrm_check_launch("k_fvp_wmin"));
+	NRM_TRY(nrm_check_launch("k_fvp_wmin"));
 	hipLaunchKernelGGL(k_fvp_w, dim3((unsigned)blocks), dim3(256), 0, st, n, blocks, d_best, d_ws, d_w, d_flags);
 	return nrm_check_launch("k_fvp_w");
 }

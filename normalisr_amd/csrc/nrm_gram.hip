@@ -206,7 +206,7 @@ extern "C" int nrm_gram_f64_band(const double* d_a, const double* d_b, int64_t m
 	}
 	NRM_REQUIRE(d_work != nullptr, "nrm_gram_f64: workspace of nrm_gram_workspace_bytes() bytes required");
 	GramSched s;
-	NRM_TRY_RC(gram_plan(s, m_pad, n_pad, k_pad / GK, symmetric, m_rows, n_rows, row0, row1, 2 * g_num_cu, (double*)d_work));
+	NRM_TRY(gram_plan(s, m_pad, n_pad, k_pad / GK, symmetric, m_rows, n_rows, row0, row1, 2 * g_num_cu, (double*)d_work));
 	hipLaunchKernelGGL(k_gram_f64, dim3((unsigned)s.nwg), dim3(256), 0, (hipStream_t)stream, d_a, d_b, lda, ldb, d_dot, ldd, symmetric, s);
 	if (s.tiles_al + s.tiles_sk > 0)
 		hipLaunchKernelGGL(k_gram_fixup<0>, dim3((unsigned)(s.tiles_al + s.tiles_sk), GM / GFIX_ROWS), dim3(256), 0, (hipStream_t)stream, d_dot, ldd, symmetric, s);
@@ -233,7 +233,7 @@ extern "C" int nrm_gram_f64_whole(const double* d_a, const double* d_b, int64_t 
 		if (g_num_cu <= 0) g_num_cu = 256;
 	}
 	GramSched s;
-	NRM_TRY_RC(gram_plan(s, m_pad, n_pad, k_pad / GK, 0, m_rows, n_rows, 0, m_pad, 2 * g_num_cu, nullptr));
+	NRM_TRY(gram_plan(s, m_pad, n_pad, k_pad / GK, 0, m_rows, n_rows, 0, m_pad, 2 * g_num_cu, nullptr));
 	s.tiles_dp += s.tiles_al + s.tiles_sk;  // every tile whole: workgroup p takes tiles p, p + nwg, ...
 	s.tiles_al = s.tiles_sk = s.units_per_wg = 0;
 	s.parts = 1;

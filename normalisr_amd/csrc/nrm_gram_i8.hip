@@ -406,7 +406,7 @@ static int gram_i8_impl(const void* d_qa, const int32_t* d_ea, int64_t plane_a_b
 	NRM_REQUIRE(plane_a >= (m_pad / 32) * nks * 1024 && plane_b >= ((bb.rows ? bb.rows : n_pad) / 32) * nks * 1024,
 				"nrm_gram_i8: plane pitch smaller than the operand");
 	GramSched s;
-	NRM_TRY_RC(gram_plan(s, m_pad, n_pad, nks, symmetric, m_rows, n_rows, row0, row1, g_num_cu_q, (double*)d_work));  // one workgroup per CU
+	NRM_TRY(gram_plan(s, m_pad, n_pad, nks, symmetric, m_rows, n_rows, row0, row1, g_num_cu_q, (double*)d_work));  // one workgroup per CU
 	s.accumulate = accumulate ? 1 : 0;
 	if (nslices == 5)
 		hipLaunchKernelGGL(k_gram_i8<5>, dim3((unsigned)s.nwg), dim3(512), 0, (hipStream_t)stream, (const char*)d_qa, (const char*)d_qb, plane_a,

@@ -66,12 +66,6 @@ struct NrmHostPin {
 	}
 };
 
-#define NRM_TRY(call)        \
-	do {                     \
-		int rc_ = (call);    \
-		if (rc_) return rc_; \
-	} while (0)
-
 static inline int64_t nrm_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 static inline size_t nrm_esize(int dtype) { return dtype == NRM_F64 ? 8 : 4; }
 

@@ -12,7 +12,7 @@
 // when they have at most LC_LDS_TAB entries and are read through L2 otherwise.
 #include <cmath>
 
-#include "nrm_common.h"
+#include "nrm_device.h"
 
 #define LC_TR 32         // rows per workgroup: one partial sum (and one set of per-cell integer atomics) per LC_TR rows
 #define LC_LDS_TAB 4096  // table entries staged in LDS (32 KB: five workgroups per CU)
@@ -68,20 +68,6 @@ extern "C" int nrm_lcpm_digamma(int64_t xmax, double t0, double* h_psi, double* 
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------------------
-// Four consecutive counts of a row as int64; cells at and beyond n read as 0.  ALIGNED (the launcher: every row starts on a 4-element boundary): one load.
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void lc_ld4(const T* __restrict__ row, int64_t k, int64_t n, int64_t (&v)[4]) {
-	if (ALIGNED && k + 4 <= n) {
-		typedef T tv_t __attribute__((ext_vector_type(4)));
-		const tv_t t = *reinterpret_cast<const tv_t*>(row + k);
-#pragma unroll
-		for (int j = 0; j < 4; j++) v[j] = (int64_t)t[j];
-	} else {
-#pragma unroll
-		for (int j = 0; j < 4; j++) v[j] = k + j < n ? (int64_t)row[k + j] : 0;
-	}
-}
-
 // stats[workgroup] = {total, maximum, minimum}; partial[tile][k] = 64 * (the tile's total of cell k) + its non-zero count
 template <typename T, bool ALIGNED>
 __global__ void __launch_bounds__(256) k_lc_count(const T* __restrict__ x, int64_t rows, int64_t n, int64_t ld, int64_t* __restrict__ partial,
@@ -101,7 +87,7 @@ __global__ void __launch_bounds__(256) k_lc_count(const T* __restrict__ x, int64
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
 			const int64_t row = row0 + r0 + u < rows ? row0 + r0 + u : rows - 1;  // (rows past the end repeat the last and count for nothing)
-			lc_ld4<T, ALIGNED>(x + row * ld, k, n, v[u]);
+			nrm_ld4<T, ALIGNED>(x + row * ld, k, n, v[u]);
 		}
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
@@ -209,10 +195,6 @@ __device__ __forceinline__ const double* lc_stage(const double* __restrict__ g_t
 		return g_tab;
 }
 
-__device__ __forceinline__ int64_t lc_index(int64_t v, int64_t tlen) {  // (a count outside the table -- the matrix changed since the count pass -- reads its end)
-	return v < 0 ? 0 : v >= tlen ? tlen - 1 : v;
-}
-
 // partial[tile][k] = sum over the tile's rows of E[x[g,k]], rows added in order
 template <typename T, bool ALIGNED, bool LDS>
 __global__ void __launch_bounds__(256) k_lc_colsum(const T* __restrict__ x, int64_t rows, int64_t n, int64_t ld, const double* __restrict__ g_tab, int64_t tlen,
@@ -226,9 +208,9 @@ __global__ void __launch_bounds__(256) k_lc_colsum(const T* __restrict__ x, int6
 #pragma unroll 4
 	for (int r = 0; r < nr; r++) {
 		int64_t v[4];
-		lc_ld4<T, ALIGNED>(x + (row0 + r) * ld, k, n, v);
+		nrm_ld4<T, ALIGNED>(x + (row0 + r) * ld, k, n, v);
 #pragma unroll
-		for (int j = 0; j < 4; j++) acc[j] += tab[lc_index(v[j], tlen)];
+		for (int j = 0; j < 4; j++) acc[j] += tab[nrm_table_index(v[j], tlen)];
 	}
 #pragma unroll
 	for (int j = 0; j < 4; j++)
@@ -268,10 +250,10 @@ __global__ void __launch_bounds__(256) k_lc_write(const T* __restrict__ x, int64
 #pragma unroll 4
 	for (int r = 0; r < nr; r++) {
 		int64_t v[4];
-		lc_ld4<T, ALIGNED>(x + (row0 + r) * ld, k, n, v);
+		nrm_ld4<T, ALIGNED>(x + (row0 + r) * ld, k, n, v);
 		OutT o[4];
 #pragma unroll
-		for (int j = 0; j < 4; j++) o[j] = (OutT)(tab[lc_index(v[j], tlen)] - sub[j]);
+		for (int j = 0; j < 4; j++) o[j] = (OutT)(tab[nrm_table_index(v[j], tlen)] - sub[j]);
 		OutT* dst = out + (row0 + r) * ldo + k;
 		if (ALIGNED && k + 4 <= n) {
 			typedef OutT ov_t __attribute__((ext_vector_type(16 / sizeof(OutT))));
@@ -291,30 +273,20 @@ __global__ void __launch_bounds__(256) k_lc_write(const T* __restrict__ x, int64
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------------------
-static int lc_elem(int dtype) { return dtype == NRM_I64 ? 8 : dtype == NRM_I32 ? 4 : dtype == NRM_I16 ? 2 : dtype == NRM_U8 ? 1 : 0; }
-
 static int lc_check(const char* what, const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld) {
-	NRM_REQUIRE(lc_elem(dtype) != 0, "%s: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8", what);
+	NRM_REQUIRE(nrm_count_elem(dtype) != 0, "%s: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8", what);
 	NRM_REQUIRE(d_x && rows > 0 && n > 0 && ld >= n, "%s: bad shape", what);
 	NRM_REQUIRE((rows + LC_TR - 1) / LC_TR <= 65535, "%s: at most %d rows", what, 65535 * LC_TR);
 	return NRM_OK;
 }
 
-static bool lc_aligned(const void* d_x, int dtype, int64_t ld) { return (uintptr_t)d_x % (4 * lc_elem(dtype)) == 0 && ld % 4 == 0; }
+static bool lc_aligned(const void* d_x, int dtype, int64_t ld) { return (uintptr_t)d_x % (4 * nrm_count_elem(dtype)) == 0 && ld % 4 == 0; }
 
 static dim3 lc_grid(int64_t rows, int64_t n) { return dim3((unsigned)((n + 1023) / 1024), (unsigned)((rows + LC_TR - 1) / LC_TR)); }
 
-#define LC_BY_DTYPE(GO)                  \
-	switch (dtype) {                     \
-		case NRM_I64: GO(int64_t); break; \
-		case NRM_I32: GO(int32_t); break; \
-		case NRM_I16: GO(int16_t); break; \
-		default: GO(uint8_t); break;     \
-	}
-
 extern "C" int nrm_lcpm_count(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld, int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_gene_zero,
 							  int64_t* d_info, int64_t* d_partial, void* stream) {
-	NRM_TRY_RC(lc_check("nrm_lcpm_count", d_x, dtype, rows, n, ld));
+	NRM_TRY(lc_check("nrm_lcpm_count", d_x, dtype, rows, n, ld));
 	NRM_REQUIRE(d_cell_total && d_cell_nnz && d_gene_zero && d_info && d_partial, "nrm_lcpm_count: null pointer");
 	const bool al = lc_aligned(d_x, dtype, ld);
 	const int64_t tiles = (rows + LC_TR - 1) / LC_TR, nb = tiles * ((n + 1023) / 1024);
@@ -325,17 +297,17 @@ extern "C" int nrm_lcpm_count(const void* d_x, int dtype, int64_t rows, int64_t 
 		if (al) LC_GO2(TY, true); \
 		else LC_GO2(TY, false);  \
 	} while (0)
-	LC_BY_DTYPE(LC_GO)
+	NRM_BY_COUNT_DTYPE(LC_GO)
 #undef LC_GO
 #undef LC_GO2
-	NRM_TRY_RC(nrm_check_launch("k_lc_count"));
+	NRM_TRY(nrm_check_launch("k_lc_count"));
 	hipLaunchKernelGGL(k_lc_count_finish, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, (hipStream_t)stream, d_partial, tiles, n, d_partial + tiles * n, nb, d_cell_total, d_cell_nnz, d_info);
 	return nrm_check_launch("k_lc_count_finish");
 }
 
 extern "C" int nrm_lcpm_colsum(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld, const double* d_exp_table, int64_t table_len, double* d_partial,
 							   double* d_t1, void* stream) {
-	NRM_TRY_RC(lc_check("nrm_lcpm_colsum", d_x, dtype, rows, n, ld));
+	NRM_TRY(lc_check("nrm_lcpm_colsum", d_x, dtype, rows, n, ld));
 	NRM_REQUIRE(d_exp_table && table_len > 0 && table_len <= LC_TAB_CAP && d_partial && d_t1, "nrm_lcpm_colsum: bad arguments");
 	const bool al = lc_aligned(d_x, dtype, ld), lds = table_len <= LC_LDS_TAB;
 	const size_t sh = lds ? (size_t)table_len * 8 : 0;
@@ -348,10 +320,10 @@ extern "C" int nrm_lcpm_colsum(const void* d_x, int dtype, int64_t rows, int64_t
 		else if (lds) LC_GO3(TY, false, true);       \
 		else LC_GO3(TY, false, false);               \
 	} while (0)
-	LC_BY_DTYPE(LC_GO)
+	NRM_BY_COUNT_DTYPE(LC_GO)
 #undef LC_GO
 #undef LC_GO3
-	NRM_TRY_RC(nrm_check_launch("k_lc_colsum"));
+	NRM_TRY(nrm_check_launch("k_lc_colsum"));
 	hipLaunchKernelGGL(k_lc_finish, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_partial, (rows + LC_TR - 1) / LC_TR, n, d_t1);
 	return nrm_check_launch("k_lc_finish");
 }
@@ -377,13 +349,13 @@ static void lc_launch_write(const void* d_x, int64_t rows, int64_t n, int64_t ld
 
 extern "C" int nrm_lcpm_write(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld, const double* d_table, int64_t table_len, const double* d_t1, void* d_out,
 							  int out_dtype, int64_t ldo, void* stream) {
-	NRM_TRY_RC(lc_check("nrm_lcpm_write", d_x, dtype, rows, n, ld));
+	NRM_TRY(lc_check("nrm_lcpm_write", d_x, dtype, rows, n, ld));
 	NRM_REQUIRE(out_dtype == NRM_F32 || out_dtype == NRM_F64, "nrm_lcpm_write: bad dtype");
 	NRM_REQUIRE(d_table && table_len > 0 && table_len <= LC_TAB_CAP && d_out && ldo >= n, "nrm_lcpm_write: bad arguments");
 	const bool al = lc_aligned(d_x, dtype, ld) && (uintptr_t)d_out % 16 == 0 && (ldo * (out_dtype == NRM_F64 ? 8 : 4)) % 16 == 0 &&
 					(d_t1 == nullptr || (uintptr_t)d_t1 % 8 == 0);
 #define LC_GO(TY) lc_launch_write<TY>(d_x, rows, n, ld, d_table, table_len, d_t1, d_out, out_dtype, ldo, al, (hipStream_t)stream)
-	LC_BY_DTYPE(LC_GO)
+	NRM_BY_COUNT_DTYPE(LC_GO)
 #undef LC_GO
 	return nrm_check_launch("k_lc_write");
 }

@@ -15,7 +15,7 @@
 // Nothing here trusts the structure: indptr is clamped to [0, nnz], a column outside the chunk is skipped, a count outside the table reads its end.
 #include <cmath>
 
-#include "nrm_common.h"
+#include "nrm_device.h"
 
 #define LCS_TR 32       // rows per workgroup of the count and sum passes (a wave owns every eighth)
 #define LCS_CW 4096     // cells per chunk: 32 KB of 64-bit accumulators, or two 16 KB images of the write pass
@@ -27,12 +27,6 @@ typedef unsigned long long lcs_u64;
 extern "C" int64_t nrm_lcpm_csr_workspace(int64_t rows, int64_t n) {
 	const int64_t tiles = (rows + LCS_TR - 1) / LCS_TR;
 	return tiles * n + 4 * tiles;
-}
-
-__device__ __forceinline__ int64_t lcs_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-__device__ __forceinline__ int64_t lcs_index(int64_t v, int64_t tlen) {  // (as lc_index of nrm_lcpm.hip: a count outside the table reads its end)
-	return v < 0 ? 0 : v >= tlen ? tlen - 1 : v;
 }
 
 // binary exponent of cell k's fixed point: total * unit bounds the sum of its terms; 2^shift times that bound is below 2^62
@@ -52,40 +46,13 @@ __device__ __forceinline__ int lcs_rows(const int64_t* __restrict__ indptr, int6
 		if (tid < nr) {
 			const int64_t row = row0 + tid, a = indptr[row], b = indptr[row + 1];
 			bad = a < 0 || b < a || b > nnz || (row == 0 && a != 0) || (row == rows - 1 && b != nnz);
-			s = lcs_clamp(a, 0, nnz);
-			e = lcs_clamp(b, s, nnz);
+			s = nrm_clamp(a, 0, nnz);
+			e = nrm_clamp(b, s, nnz);
 		}
 		s_cur[tid] = s;
 		s_end[tid] = e;
 	}
 	return bad;
-}
-
-// One wave, one row, one chunk [c0, cend) of cells: the stored entries from *cur on whose column is below cend, 128 per step (both loads of a step are issued
-// before the first is used); go(column - c0, count) for those inside the chunk.  Returns the position of the first entry left for the next chunk.
-template <typename T, typename F>
-__device__ __forceinline__ int64_t lcs_walk(const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t cur, int64_t e, int64_t c0, int64_t cend, F go) {
-	const int lane = threadIdx.x & 63;
-	for (;;) {
-		int64_t col[2], x[2];
-		bool in[2];
-#pragma unroll
-		for (int u = 0; u < 2; u++) {
-			const int64_t p = cur + u * 64 + lane;
-			const bool ok = p < e;
-			col[u] = ok ? (int64_t)idx[p] : cend;
-			x[u] = ok ? (int64_t)val[p] : 0;
-			in[u] = ok && col[u] < cend;
-		}
-		int cnt = 0;
-#pragma unroll
-		for (int u = 0; u < 2; u++) {
-			if (in[u] && col[u] >= c0) go((int)(col[u] - c0), x[u]);
-			cnt += (int)__popcll(__ballot(in[u]));
-		}
-		cur += cnt;
-		if (cnt < 128) return cur;
-	}
 }
 
 // ---- pass 1: integer totals and the structure check ------------------------------------------------------------------------------------------------------------
@@ -123,7 +90,7 @@ __global__ void __launch_bounds__(512) k_lcs_count(const int64_t* __restrict__ i
 	for (int64_t c0 = 0; c0 < n; c0 += LCS_CW) {
 		const int64_t cend = c0 + LCS_CW < n ? c0 + LCS_CW : n;
 		for (int r = wid; r < nr; r += 8) {
-			const int64_t cur = lcs_walk<T>(idx, val, s_cur[r], s_end[r], c0, cend, [&](int c, int64_t x) {
+			const int64_t cur = nrm_csr_walk<T>(idx, val, s_cur[r], s_end[r], c0, cend, [&](int c, int64_t x) {
 				if (x > 0) atomicAdd(&s_acc[c], ((lcs_u64)x << 8) | 1ull);
 			});
 			if (lane == 0) s_cur[r] = cur;
@@ -236,8 +203,8 @@ __global__ void __launch_bounds__(512) k_lcs_colsum(const int64_t* __restrict__ 
 		}
 		__syncthreads();
 		for (int r = wid; r < nr; r += 8) {
-			const int64_t cur = lcs_walk<T>(idx, val, s_cur[r], s_end[r], c0, cend, [&](int c, int64_t x) {
-				const int64_t xi = lcs_index(x, tlen);
+			const int64_t cur = nrm_csr_walk<T>(idx, val, s_cur[r], s_end[r], c0, cend, [&](int c, int64_t x) {
+				const int64_t xi = nrm_table_index(x, tlen);
 				if (xi > 0) {
 					const double term = tab[xi] - e0;  // >= 0: psi is increasing
 					atomicAdd(&s_acc[c], (lcs_u64)__double2ll_rn(ldexp(term > 0.0 ? term : 0.0, (int)s_shift[c])));
@@ -284,7 +251,7 @@ __global__ void __launch_bounds__(256) k_lcs_write(const int64_t* __restrict__ i
 	const double t0 = tab[0];
 	int b = 0;
 	for (int64_t g = blockIdx.x; g < rows; g += gridDim.x) {
-		const int64_t s = lcs_clamp(indptr[g], 0, nnz), e = lcs_clamp(indptr[g + 1], s, nnz);
+		const int64_t s = nrm_clamp(indptr[g], 0, nnz), e = nrm_clamp(indptr[g + 1], s, nnz);
 		int64_t cur = s;
 		OutT* orow = out + g * ldo;
 		for (int64_t c0 = 0; c0 < n; c0 += LCS_CW, b ^= 1) {
@@ -313,8 +280,8 @@ __global__ void __launch_bounds__(256) k_lcs_write(const int64_t* __restrict__ i
 					x[u] = ok ? (int64_t)val[p] : 0;
 					in[u] = ok && col[u] < cend;
 				}
-				if (in[0] && col[0] >= c0) s_img[b][col[0] - c0] = (int)lcs_index(x[0], tlen);
-				if (in[1] && col[1] >= c0) s_img[b][col[1] - c0] = (int)lcs_index(x[1], tlen);
+				if (in[0] && col[0] >= c0) s_img[b][col[0] - c0] = (int)nrm_table_index(x[0], tlen);
+				if (in[1] && col[1] >= c0) s_img[b][col[1] - c0] = (int)nrm_table_index(x[1], tlen);
 				const int cnt = __syncthreads_count(in[0]) + __syncthreads_count(in[1]);  // (the barrier between scatter and read as well)
 				cur += cnt;
 				if (cnt < 512) break;
@@ -349,36 +316,23 @@ __global__ void __launch_bounds__(256) k_lcs_write(const int64_t* __restrict__ i
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------------------------------
-static int lcs_elem(int dtype) { return dtype == NRM_I64 ? 8 : dtype == NRM_I32 ? 4 : dtype == NRM_I16 ? 2 : dtype == NRM_U8 ? 1 : 0; }
-
 static int lcs_check(const char* what, const void* d_indptr, const void* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz) {
-	NRM_REQUIRE(lcs_elem(dtype) != 0, "%s: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8", what);
-	NRM_REQUIRE(d_indptr && rows > 0 && n > 0 && nnz >= 0 && n <= 0x7fffffffLL, "%s: bad shape", what);
-	NRM_REQUIRE(nnz == 0 || (d_indices && d_data), "%s: null pointer", what);
-	NRM_REQUIRE((uintptr_t)d_indptr % 8 == 0 && (uintptr_t)d_indices % 4 == 0 && (uintptr_t)d_data % lcs_elem(dtype) == 0, "%s: misaligned CSR arrays", what);
-	return NRM_OK;
+	NRM_REQUIRE(nrm_count_elem(dtype) != 0, "%s: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8", what);
+	return nrm_csr_args_check(what, d_indptr, d_indices, d_data, nrm_count_elem(dtype), rows, n, nnz);
 }
-
-#define LCS_BY_DTYPE(GO)                 \
-	switch (dtype) {                     \
-		case NRM_I64: GO(int64_t); break; \
-		case NRM_I32: GO(int32_t); break; \
-		case NRM_I16: GO(int16_t); break; \
-		default: GO(uint8_t); break;     \
-	}
 
 extern "C" int nrm_lcpm_csr_count(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
 								  int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_gene_zero, int64_t* d_info, int64_t* d_partial, void* stream) {
-	NRM_TRY_RC(lcs_check("nrm_lcpm_csr_count", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
+	NRM_TRY(lcs_check("nrm_lcpm_csr_count", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
 	NRM_REQUIRE(d_cell_total && d_cell_nnz && d_gene_zero && d_info && d_partial, "nrm_lcpm_csr_count: null pointer");
 	const int64_t tiles = (rows + LCS_TR - 1) / LCS_TR;
 	NRM_REQUIRE(tiles <= 0x7fffffffLL, "nrm_lcpm_csr_count: too many rows");
 	hipStream_t st = (hipStream_t)stream;
 #define LCS_GO(TY) \
 	hipLaunchKernelGGL((k_lcs_count<TY>), dim3((unsigned)tiles), dim3(512), 0, st, d_indptr, d_indices, (const TY*)d_data, rows, n, nnz, d_partial, d_partial + tiles * n, d_gene_zero)
-	LCS_BY_DTYPE(LCS_GO)
+	NRM_BY_COUNT_DTYPE(LCS_GO)
 #undef LCS_GO
-	NRM_TRY_RC(nrm_check_launch("k_lcs_count"));
+	NRM_TRY(nrm_check_launch("k_lcs_count"));
 	hipLaunchKernelGGL(k_lcs_count_finish, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_partial, tiles, n, d_partial + tiles * n, d_cell_total, d_cell_nnz, d_info);
 	return nrm_check_launch("k_lcs_count_finish");
 }
@@ -386,16 +340,16 @@ extern "C" int nrm_lcpm_csr_count(const int64_t* d_indptr, const int32_t* d_indi
 extern "C" int nrm_lcpm_csr_colsum(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
 								   const double* d_exp_table, int64_t table_len, double unit, const int64_t* d_cell_total, int64_t* d_partial, double* d_t1,
 								   void* stream) {
-	NRM_TRY_RC(lcs_check("nrm_lcpm_csr_colsum", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
+	NRM_TRY(lcs_check("nrm_lcpm_csr_colsum", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
 	NRM_REQUIRE(d_exp_table && table_len > 0 && table_len <= LCS_TAB_CAP && d_cell_total && d_partial && d_t1, "nrm_lcpm_csr_colsum: bad arguments");
 	NRM_REQUIRE(unit >= 0.0 && std::isfinite(unit), "nrm_lcpm_csr_colsum: unit must be the largest (E[x] - E[0]) / x of the table");
 	const int64_t tiles = (rows + LCS_TR - 1) / LCS_TR;
 	hipStream_t st = (hipStream_t)stream;
 #define LCS_GO(TY) \
 	hipLaunchKernelGGL((k_lcs_colsum<TY>), dim3((unsigned)tiles), dim3(512), 0, st, d_indptr, d_indices, (const TY*)d_data, rows, n, nnz, d_exp_table, table_len, unit, d_cell_total, d_partial)
-	LCS_BY_DTYPE(LCS_GO)
+	NRM_BY_COUNT_DTYPE(LCS_GO)
 #undef LCS_GO
-	NRM_TRY_RC(nrm_check_launch("k_lcs_colsum"));
+	NRM_TRY(nrm_check_launch("k_lcs_colsum"));
 	hipLaunchKernelGGL(k_lcs_finish, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_partial, tiles, n, rows, d_exp_table, unit, d_cell_total, d_t1);
 	return nrm_check_launch("k_lcs_finish");
 }
@@ -419,12 +373,12 @@ static void lcs_launch_write(const int64_t* d_indptr, const int32_t* d_indices, 
 
 extern "C" int nrm_lcpm_csr_write(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
 								  const double* d_table, int64_t table_len, const double* d_t1, void* d_out, int out_dtype, int64_t ldo, void* stream) {
-	NRM_TRY_RC(lcs_check("nrm_lcpm_csr_write", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
+	NRM_TRY(lcs_check("nrm_lcpm_csr_write", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
 	NRM_REQUIRE(out_dtype == NRM_F32 || out_dtype == NRM_F64, "nrm_lcpm_csr_write: bad dtype");
 	NRM_REQUIRE(d_table && table_len > 0 && table_len <= LCS_TAB_CAP && d_out && ldo >= n, "nrm_lcpm_csr_write: bad arguments");
 	const bool al = (uintptr_t)d_out % 16 == 0 && (ldo * (out_dtype == NRM_F64 ? 8 : 4)) % 16 == 0 && (d_t1 == nullptr || (uintptr_t)d_t1 % 16 == 0);
 #define LCS_GO(TY) lcs_launch_write<TY>(d_indptr, d_indices, d_data, rows, n, nnz, d_table, table_len, d_t1, d_out, out_dtype, ldo, al, (hipStream_t)stream)
-	LCS_BY_DTYPE(LCS_GO)
+	NRM_BY_COUNT_DTYPE(LCS_GO)
 #undef LCS_GO
 	return nrm_check_launch("k_lcs_write");
 }

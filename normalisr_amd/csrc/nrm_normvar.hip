@@ -4,7 +4,7 @@
 //     M_g = sum_k e_gk^2 C_k C_k^T   and   a_g = sum_k e_gk^2 y_gk C_k
 // are rows of two Gram contractions on the fp64 matrix cores (K2): U P^T and V C^T with U = e^2, V = e^2 y and
 // P = the nc(nc+1)/2 products C_c * C_c'.  This file holds the two HBM-bound element-wise passes around them.
-#include "nrm_common.h"
+#include "nrm_device.h"
 #include "nrm_jacobi.h"
 
 #include "nrm_exp2_tab.h"
@@ -36,19 +36,6 @@ __device__ __forceinline__ double nv_exp(double x, const double* __restrict__ ta
 // a template switch, not a branch.  Either way the four are independent loads: round 6 found both passes of normvar bound by the LATENCY of one dependent
 // 4-byte load per thread and iteration (k_nv_apply waited for HBM once per row and cell: 39 x 4 round trips of ~1.5 us per workgroup = the 0.27 ms it took),
 // not by exp() and the multiply-adds as rounds 4-5 had it; four cells per thread and iteration, every load of an iteration issued before the first use.
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void nv_ld4(const T* __restrict__ p, double (&v)[4]) {
-	if constexpr (ALIGNED && sizeof(T) == 4) {
-		const float4 t = *reinterpret_cast<const float4*>(p);
-		v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-	} else if constexpr (ALIGNED) {
-		const double2 a = *reinterpret_cast<const double2*>(p), b = *reinterpret_cast<const double2*>(p + 2);
-		v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-	} else {
-#pragma unroll
-		for (int j = 0; j < 4; j++) v[j] = (double)p[j];
-	}
-}
 
 __device__ __forceinline__ void nv_exp_table(double* tab, int tid) {  // (before the workgroup's first barrier)
 	if (tid < 64) tab[tid] = kNrmExp2_64[tid];
@@ -66,12 +53,6 @@ extern "C" int nrm_normvar_exp_probe(const double* d_x, int64_t count, double* d
 	NRM_REQUIRE(d_x && d_out && count > 0, "nrm_normvar_exp_probe: bad arguments");
 	hipLaunchKernelGGL(k_nv_exp_probe, dim3(256), dim3(256), 0, (hipStream_t)stream, d_x, count, d_out);
 	return nrm_check_launch("k_nv_exp_probe");
-}
-
-__device__ __forceinline__ double nv_wave_sum(double v) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-	return v;
 }
 
 // pass 1: U = e^2, V = e^2 y (fp64, zero padded), s1 = sum y e, s2 = sum (y e)^2      (norm.py:244-249)
@@ -113,7 +94,7 @@ __global__ void __launch_bounds__(256) k_nv_weights(const T* __restrict__ y, int
 	}
 #pragma unroll
 	for (int r = 0; r < NV_R; r++) {
-		const double x1 = nv_wave_sum(a1[r]), x2 = nv_wave_sum(a2[r]);
+		const double x1 = nrm_wave_sum(a1[r]), x2 = nrm_wave_sum(a2[r]);
 		if (lane == 0) {
 			sm[wid][2 * r] = x1;
 			sm[wid][2 * r + 1] = x2;
@@ -128,7 +109,7 @@ __global__ void __launch_bounds__(256) k_nv_weights(const T* __restrict__ y, int
 
 // pass 2: out = scale_g * e_gk * (y_gk - sum_c b_gc C_ck)      (norm.py:157 per gene, :259)
 // Four cells per thread and iteration, the loads of all NV_R rows, the weights and (batch by batch) the covariates issued before anything is used: the first
-// form loaded one 4-byte value per row and cell and waited for each (see nv_ld4).
+// form loaded one 4-byte value per row and cell and waited for each (see nrm_ld4d).
 // WIDE (more than 64 covariates, up to NRM_WIDE_NC: the rows of the basis B of csrc/nrm_normvar_wide.hip): the coefficients in dynamic LDS, NV_R x nc doubles.
 extern __shared__ __attribute__((aligned(16))) double nv_wide_b[];
 
@@ -168,16 +149,16 @@ __global__ void __launch_bounds__(256) k_nv_apply(const T* __restrict__ y, int64
 	const int64_t n4 = n & ~(int64_t)3;
 	for (int64_t k = (int64_t)tid * 4; k < n4; k += 1024) {
 		double lw[4], yv[NV_R][4], fit[NV_R][4];
-		nv_ld4<double, ALIGNED>(lnw + k, lw);
+		nrm_ld4d<double, ALIGNED>(lnw + k, lw);
 #pragma unroll
 		for (int r = 0; r < NV_R; r++) {
-			nv_ld4<T, ALIGNED>(yr[r] + k, yv[r]);
+			nrm_ld4d<T, ALIGNED>(yr[r] + k, yv[r]);
 #pragma unroll
 			for (int v = 0; v < 4; v++) fit[r][v] = 0.0;
 		}
 		for (int q = 0; q < nc; q++) {
 			double cv[4];
-			nv_ld4<double, ALIGNED>(c + (int64_t)q * ldc + k, cv);
+			nrm_ld4d<double, ALIGNED>(c + (int64_t)q * ldc + k, cv);
 #pragma unroll
 			for (int r = 0; r < NV_R; r++)
 #pragma unroll
@@ -371,11 +352,11 @@ __global__ void __launch_bounds__(256) k_nv_moments(const T* __restrict__ y, int
 	const int64_t n4 = n & ~(int64_t)3;
 	for (int64_t k = (int64_t)tid * 4; k < n4; k += 1024) {  // four cells per thread: 2 + G + 2 NC sixteen-byte loads in flight before the first is used
 		double lw[4], yv[G][4], cq[NC][4];
-		nv_ld4<double, ALIGNED>(lnw + k, lw);
+		nrm_ld4d<double, ALIGNED>(lnw + k, lw);
 #pragma unroll
-		for (int u = 0; u < G; u++) nv_ld4<T, ALIGNED>(row[u] + k, yv[u]);
+		for (int u = 0; u < G; u++) nrm_ld4d<T, ALIGNED>(row[u] + k, yv[u]);
 #pragma unroll
-		for (int q = 0; q < NC; q++) nv_ld4<double, ALIGNED>(c + (int64_t)q * ldc + k, cq[q]);
+		for (int q = 0; q < NC; q++) nrm_ld4d<double, ALIGNED>(c + (int64_t)q * ldc + k, cq[q]);
 #pragma unroll
 		for (int v = 0; v < 4; v++) {
 			double cv[NC];
@@ -396,7 +377,7 @@ __global__ void __launch_bounds__(256) k_nv_moments(const T* __restrict__ y, int
 	for (int u = 0; u < G; u++)
 #pragma unroll
 		for (int j = 0; j < NM; j++) {
-			const double t = nv_wave_sum(acc[u][j]);
+			const double t = nrm_wave_sum(acc[u][j]);
 			if (lane == 0) sm[wid][u * NM + j] = t;
 		}
 	__syncthreads();

@@ -15,7 +15,7 @@
 //                 variance-keeping scale (dv / dv2)^wt_g with dv2^2 = (s2 - a . b) / n (norm.py:248-259; |y' - P y'|^2 = |y'|^2 - a . b).
 //                 A pivot that is not positive, or any value that is not finite, ends that gene: its status is recorded, d_flags counts it, b_g and the
 //                 scale are written as zeros -- never a fault, never a NaN handed on silently.  Every sum is in a fixed order: the same bits every run.
-#include "nrm_common.h"
+#include "nrm_device.h"
 
 #define NVW_NB 16    // rows per block step of the factorisation
 #define NVW_CH 128   // columns per LDS chunk of the trailing update
@@ -45,12 +45,6 @@ __global__ void __launch_bounds__(256) k_nvw_pairs(const double* __restrict__ B,
 	const double* bi = B + i * ldb;
 	const double* bj = B + j * ldb;
 	for (int64_t k = kbeg + threadIdx.x; k < kend; k += 256) dst[k] = k < n ? bi[k] * bj[k] : 0.0;
-}
-
-__device__ __forceinline__ double nvw_wave_sum(double v) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-	return v;
 }
 
 __global__ void __launch_bounds__(256) k_nvw_chol(double* __restrict__ M, int64_t ldm, const double* __restrict__ A, int64_t lda, int r,
@@ -175,7 +169,7 @@ __global__ void __launch_bounds__(256) k_nvw_chol(double* __restrict__ M, int64_
 			const double* row = m + nvw_row(i, r) - i;
 			double part = 0.0;
 			for (int j = i + 1 + tid; j < r; j += 256) part = fma(row[j], s_x[j], part);
-			part = nvw_wave_sum(part);
+			part = nrm_wave_sum(part);
 			if (lane == 0) s_red[wid] = part;
 			__syncthreads();
 			if (tid == 0) s_x[i] = (s_z[i] - (((s_red[0] + s_red[1]) + s_red[2]) + s_red[3])) / s_dg[i];
@@ -188,7 +182,7 @@ __global__ void __launch_bounds__(256) k_nvw_chol(double* __restrict__ M, int64_
 			nf |= !(fabs(bv) <= 1.7976931348623157e308);
 			part = fma(a[i], bv, part);
 		}
-		part = nvw_wave_sum(part);
+		part = nrm_wave_sum(part);
 		if (lane == 0) s_red[wid] = part;
 		if (nf) atomicOr(&s_bad, 1);
 		__syncthreads();

@@ -10,7 +10,7 @@
 //   k_pc_fold         out[j] = the splits' partial sums added in their order, rounded once to the output type
 // All floating-point sums are taken in an order that depends on the shape alone: lanes stride the terms, a shuffle tree folds the lanes, LDS folds the waves in
 // their order.  No floating-point atomics: the same bits on every run.  All four passes are bound by memory.
-#include "nrm_common.h"
+#include "nrm_device.h"
 
 #define PC_SCORE_CELLS 512   // cells per workgroup of k_pc_score: 256 lanes x 2 adjacent cells (one 16-byte load per lane and gene)
 #define PC_SCORE_SHARE 16    // the fewest genes a workgroup of k_pc_score takes
@@ -66,21 +66,6 @@ __global__ void __launch_bounds__(256) k_pc_correlation(const double* __restrict
 }
 
 // ---- power iteration ----------------------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double pc_wave_sum(double s) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-	return s;
-}
-
-// the workgroup's sum of s, in every thread: lanes by the shuffle tree, the four waves in their order
-__device__ __forceinline__ double pc_block_sum(double s, double* sm) {
-	s = pc_wave_sum(s);
-	__syncthreads();  // (sm may still be read from the sum before)
-	if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-	__syncthreads();
-	return ((sm[0] + sm[1]) + sm[2]) + sm[3];
-}
-
 __global__ void __launch_bounds__(256) k_pc_matvec(const double* __restrict__ r, int64_t ldr, int64_t m, const double* __restrict__ v, double* __restrict__ w) {
 	const int lane = threadIdx.x & 63;
 	const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -96,7 +81,7 @@ __global__ void __launch_bounds__(256) k_pc_matvec(const double* __restrict__ r,
 		s3 = fma(r3, v[h + 192], s3);
 	}
 	for (; h < m; h += 64) s0 = fma(row[h], v[h], s0);
-	const double s = pc_wave_sum((s0 + s1) + (s2 + s3));
+	const double s = nrm_wave_sum((s0 + s1) + (s2 + s3));
 	if (lane == 0) w[g] = s;
 }
 
@@ -105,14 +90,14 @@ __global__ void __launch_bounds__(256) k_pc_finish(int64_t m, double* __restrict
 	const int tid = threadIdx.x;
 	double s = 0;
 	for (int64_t g = tid; g < m; g += 256) s = fma(v[g], w[g], s);
-	const double lam = pc_block_sum(s, sm);
+	const double lam = nrm_block_sum<4>(s, sm);
 	double e = 0, q = 0;
 	for (int64_t g = tid; g < m; g += 256) {
 		const double d = w[g] - lam * v[g];
 		e = fma(d, d, e);
 		q = fma(w[g], w[g], q);
 	}
-	const double res = sqrt(pc_block_sum(e, sm)), nw = sqrt(pc_block_sum(q, sm));
+	const double res = sqrt(nrm_block_sum<4>(e, sm)), nw = sqrt(nrm_block_sum<4>(q, sm));
 	if (nw > 0)
 		for (int64_t g = tid; g < m; g += 256) v[g] = w[g] / nw;
 	if (tid == 0) {
@@ -252,9 +237,9 @@ extern "C" int nrm_pc_score(const double* d_z, int64_t ldz, int64_t m, int64_t n
 	double* d_u = d_work;
 	double* d_part = d_work + m;
 	hipLaunchKernelGGL(k_pc_sign, dim3(1), dim3(256), 0, st, m, d_v, d_a, d_u, d_sign);
-	NRM_TRY_RC(nrm_check_launch("k_pc_sign"));
+	NRM_TRY(nrm_check_launch("k_pc_sign"));
 	hipLaunchKernelGGL(k_pc_score, dim3((unsigned)blocks, (unsigned)splits), dim3(256), 0, st, d_z, ldz, m, n, share, d_u, d_part);
-	NRM_TRY_RC(nrm_check_launch("k_pc_score"));
+	NRM_TRY(nrm_check_launch("k_pc_score"));
 	const dim3 fg((unsigned)((n + 255) / 256));
 	if (out_dtype == NRM_F64)
 		hipLaunchKernelGGL((k_pc_fold<double>), fg, dim3(256), 0, st, d_part, splits, n, (double*)d_out);

@@ -12,7 +12,7 @@
 // k_qc_fold); a row's sum goes through a wave reduction and LDS to one 64-bit atomic per statistic, row and workgroup.
 // CSR: as k_lcs_count of nrm_lcpm_sparse.hip -- a workgroup owns QC_TR rows and walks the cells in chunks of QC_CW with the chunk's per-cell accumulators
 // and its share of the cell mask in LDS.  Nothing trusts the structure: indptr is clamped to [0, nnz], a column outside its chunk is skipped.
-#include "nrm_common.h"
+#include "nrm_device.h"
 
 #define QC_TR 32    // rows per workgroup of the statistics passes
 #define QC_CW 4096  // cells per chunk of the CSR pass: 32 KB of 64-bit accumulators
@@ -21,22 +21,6 @@ typedef unsigned long long qc_u64;
 
 // int64 words of scratch of nrm_qc_stats and nrm_qc_csr_stats: one slab of n words per row tile
 extern "C" int64_t nrm_qc_stats_workspace(int64_t rows, int64_t n) { return ((rows + QC_TR - 1) / QC_TR) * n; }
-
-__device__ __forceinline__ int64_t qc_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-// Four consecutive counts of a row as int64; cells at and beyond n read as 0.  ALIGNED (the launcher: every row starts on a 4-element boundary): one load.
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void qc_ld4(const T* __restrict__ row, int64_t k, int64_t n, int64_t (&v)[4]) {
-	if (ALIGNED && k + 4 <= n) {
-		typedef T tv_t __attribute__((ext_vector_type(4)));
-		const tv_t t = *reinterpret_cast<const tv_t*>(row + k);
-#pragma unroll
-		for (int j = 0; j < 4; j++) v[j] = (int64_t)t[j];
-	} else {
-#pragma unroll
-		for (int j = 0; j < 4; j++) v[j] = k + j < n ? (int64_t)row[k + j] : 0;
-	}
-}
 
 // ---- the masked statistics of a dense matrix ----------------------------------------------------------------------------------------------------------------------
 // slab[tile][k] = 256 * (the tile's total of cell k) + its count of positive entries (at most QC_TR); gene_total / gene_nnz are added to (zeroed by the launcher)
@@ -75,7 +59,7 @@ __global__ void __launch_bounds__(256) k_qc_stats(const T* __restrict__ x, int64
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
 			rr[u] = s_list[i0 + u < cnt ? i0 + u : cnt - 1];  // (steps past the list repeat its last row and count for nothing)
-			qc_ld4<T, ALIGNED>(x + (row0 + rr[u]) * ld, k, n, v[u]);
+			nrm_ld4<T, ALIGNED>(x + (row0 + rr[u]) * ld, k, n, v[u]);
 		}
 #pragma unroll
 		for (int u = 0; u < 4; u++) {
@@ -135,33 +119,6 @@ __global__ void __launch_bounds__(256) k_qc_fold(const int64_t* __restrict__ sla
 }
 
 // ---- the masked statistics of a CSR matrix ------------------------------------------------------------------------------------------------------------------------
-// One wave, one row, one chunk [c0, cend) of cells: the stored entries from cur on whose column is below cend, 128 per step; go(column - c0, count) for those
-// inside the chunk.  Returns the position of the first entry left for the next chunk (the walk of nrm_lcpm_sparse.hip).
-template <typename T, typename F>
-__device__ __forceinline__ int64_t qc_walk(const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t cur, int64_t e, int64_t c0, int64_t cend, F go) {
-	const int lane = threadIdx.x & 63;
-	for (;;) {
-		int64_t col[2], x[2];
-		bool in[2];
-#pragma unroll
-		for (int u = 0; u < 2; u++) {
-			const int64_t p = cur + u * 64 + lane;
-			const bool ok = p < e;
-			col[u] = ok ? (int64_t)idx[p] : cend;
-			x[u] = ok ? (int64_t)val[p] : 0;
-			in[u] = ok && col[u] < cend;
-		}
-		int cnt = 0;
-#pragma unroll
-		for (int u = 0; u < 2; u++) {
-			if (in[u] && col[u] >= c0) go((int)(col[u] - c0), x[u]);
-			cnt += (int)__popcll(__ballot(in[u]));
-		}
-		cur += cnt;
-		if (cnt < 128) return cur;
-	}
-}
-
 // gene_total / gene_nnz of the tile's rows are WRITTEN (a tile owns its rows; 0 for a dead row); slab as k_qc_stats; info[0] |= negative, info[1] |= malformed
 template <typename T>
 __global__ void __launch_bounds__(256) k_qc_csr_stats(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t rows, int64_t n,
@@ -181,8 +138,8 @@ __global__ void __launch_bounds__(256) k_qc_csr_stats(const int64_t* __restrict_
 			const int64_t row = row0 + tid, a = indptr[row], b = indptr[row + 1];
 			bad = a < 0 || b < a || b > nnz || (row == 0 && a != 0) || (row == rows - 1 && b != nnz);
 			on = gene_alive[row] != 0;
-			s = qc_clamp(a, 0, nnz);
-			e = on ? qc_clamp(b, s, nnz) : s;
+			s = nrm_clamp(a, 0, nnz);
+			e = on ? nrm_clamp(b, s, nnz) : s;
 		}
 		s_cur[tid] = s;
 		s_end[tid] = e;
@@ -225,7 +182,7 @@ __global__ void __launch_bounds__(256) k_qc_csr_stats(const int64_t* __restrict_
 			if (r < nr && s_on[r]) {
 				int64_t a = 0;
 				int b = 0;
-				const int64_t cur = qc_walk<T>(idx, val, s_cur[r], s_end[r], c0, cend, [&](int c, int64_t x) {
+				const int64_t cur = nrm_csr_walk<T>(idx, val, s_cur[r], s_end[r], c0, cend, [&](int c, int64_t x) {
 					if (s_live[c]) {
 						if (x > 0) atomicAdd(&s_acc[c], ((qc_u64)x << 8) | 1ull);
 						a += x;
@@ -308,12 +265,12 @@ __global__ void __launch_bounds__(256) k_subset_dense(const U* __restrict__ x, i
 													  const int64_t* __restrict__ col_idx, int64_t ro, int64_t no, U* __restrict__ out, int64_t ldo) {
 	const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
 	if (j >= no) return;
-	const int64_t c = qc_clamp(col_idx ? col_idx[j] : j, 0, n - 1);
+	const int64_t c = nrm_clamp(col_idx ? col_idx[j] : j, 0, n - 1);
 	for (int64_t i0 = (int64_t)blockIdx.y * 16; i0 < ro; i0 += (int64_t)gridDim.y * 16) {
 		const int64_t i1 = i0 + 16 < ro ? i0 + 16 : ro;
 #pragma unroll 4
 		for (int64_t i = i0; i < i1; i++) {
-			const int64_t r = qc_clamp(row_idx ? row_idx[i] : i, 0, rows - 1);
+			const int64_t r = nrm_clamp(row_idx ? row_idx[i] : i, 0, rows - 1);
 			out[i * ldo + j] = x[r * ld + c];
 		}
 	}
@@ -329,7 +286,7 @@ __global__ void __launch_bounds__(256) k_subset_csr_count(const int64_t* __restr
 	if (g >= rows) return;
 	const int64_t a = indptr[g], b = indptr[g + 1];
 	bool bad = a < 0 || b < a || b > nnz || (g == 0 && a != 0) || (g == rows - 1 && b != nnz);
-	const int64_t s = qc_clamp(a, 0, nnz), e = qc_clamp(b, s, nnz);
+	const int64_t s = nrm_clamp(a, 0, nnz), e = nrm_clamp(b, s, nnz);
 	const bool on = gene_alive[g] != 0;
 	int64_t cnt = 0;
 	for (int64_t p0 = s; p0 < e; p0 += 64) {  // (every row is read: the structure of the whole matrix is checked, whatever is kept)
@@ -429,7 +386,7 @@ __global__ void __launch_bounds__(256) k_subset_csr_write(const int64_t* __restr
 	const int lane = threadIdx.x & 63;
 	const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (g >= rows || !gene_alive[g]) return;
-	const int64_t s = qc_clamp(indptr[g], 0, nnz), e = qc_clamp(indptr[g + 1], s, nnz);
+	const int64_t s = nrm_clamp(indptr[g], 0, nnz), e = nrm_clamp(indptr[g + 1], s, nnz);
 	int64_t pos = row_off[g];
 	for (int64_t p0 = s; p0 < e; p0 += 64) {
 		const int64_t p = p0 + lane;
@@ -447,23 +404,11 @@ __global__ void __launch_bounds__(256) k_subset_csr_write(const int64_t* __restr
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------------------------------------
-static int qc_elem(int dtype) { return dtype == NRM_I64 ? 8 : dtype == NRM_I32 ? 4 : dtype == NRM_I16 ? 2 : dtype == NRM_U8 ? 1 : 0; }
-
 static int qc_csr_check(const char* what, const void* d_indptr, const void* d_indices, const void* d_data, int elem, int64_t rows, int64_t n, int64_t nnz) {
-	NRM_REQUIRE(d_indptr && rows > 0 && n > 0 && nnz >= 0 && n <= 0x7fffffffLL, "%s: bad shape", what);
-	NRM_REQUIRE(nnz == 0 || (d_indices && d_data), "%s: null pointer", what);
-	NRM_REQUIRE((uintptr_t)d_indptr % 8 == 0 && (uintptr_t)d_indices % 4 == 0 && (uintptr_t)d_data % elem == 0, "%s: misaligned CSR arrays", what);
+	NRM_TRY(nrm_csr_args_check(what, d_indptr, d_indices, d_data, elem, rows, n, nnz));
 	NRM_REQUIRE((rows + 3) / 4 <= 0x7fffffffLL, "%s: too many rows", what);
 	return NRM_OK;
 }
-
-#define QC_BY_DTYPE(GO)                  \
-	switch (dtype) {                     \
-		case NRM_I64: GO(int64_t); break; \
-		case NRM_I32: GO(int32_t); break; \
-		case NRM_I16: GO(int16_t); break; \
-		default: GO(uint8_t); break;     \
-	}
 
 #define QC_BY_SIZE(GO)               \
 	switch (elem) {                  \
@@ -475,17 +420,17 @@ static int qc_csr_check(const char* what, const void* d_indptr, const void* d_in
 
 extern "C" int nrm_qc_stats(const void* d_x, int dtype, int64_t rows, int64_t n, int64_t ld, const uint8_t* d_gene_alive, const uint8_t* d_cell_alive,
 							int64_t* d_gene_total, int64_t* d_gene_nnz, int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_info, int64_t* d_work, void* stream) {
-	NRM_REQUIRE(qc_elem(dtype) != 0, "nrm_qc_stats: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8");
+	NRM_REQUIRE(nrm_count_elem(dtype) != 0, "nrm_qc_stats: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8");
 	NRM_REQUIRE(d_x && rows > 0 && n > 0 && ld >= n, "nrm_qc_stats: bad shape");
 	const int64_t tiles = (rows + QC_TR - 1) / QC_TR;
 	NRM_REQUIRE(tiles <= 65535, "nrm_qc_stats: at most %d rows", 65535 * QC_TR);
 	NRM_REQUIRE(d_gene_alive && d_cell_alive && d_gene_total && d_gene_nnz && d_cell_total && d_cell_nnz && d_info && d_work, "nrm_qc_stats: null pointer");
-	NRM_REQUIRE((uintptr_t)d_x % qc_elem(dtype) == 0, "nrm_qc_stats: misaligned matrix");
+	NRM_REQUIRE((uintptr_t)d_x % nrm_count_elem(dtype) == 0, "nrm_qc_stats: misaligned matrix");
 	hipStream_t st = (hipStream_t)stream;
 	NRM_HIP(hipMemsetAsync(d_gene_total, 0, (size_t)rows * 8, st));
 	NRM_HIP(hipMemsetAsync(d_gene_nnz, 0, (size_t)rows * 8, st));
 	NRM_HIP(hipMemsetAsync(d_info, 0, 16, st));
-	const bool al = (uintptr_t)d_x % (4 * qc_elem(dtype)) == 0 && ld % 4 == 0;
+	const bool al = (uintptr_t)d_x % (4 * nrm_count_elem(dtype)) == 0 && ld % 4 == 0;
 	const dim3 grid((unsigned)((n + 1023) / 1024), (unsigned)tiles);
 #define QC_GO2(TY, AL)                                                                                                                                                \
 	hipLaunchKernelGGL((k_qc_stats<TY, AL>), grid, dim3(256), 0, st, (const TY*)d_x, rows, n, ld, d_gene_alive, d_cell_alive, (qc_u64*)d_gene_total, (qc_u64*)d_gene_nnz, \
@@ -495,10 +440,10 @@ extern "C" int nrm_qc_stats(const void* d_x, int dtype, int64_t rows, int64_t n,
 		if (al) QC_GO2(TY, true); \
 		else QC_GO2(TY, false);  \
 	} while (0)
-	QC_BY_DTYPE(QC_GO)
+	NRM_BY_COUNT_DTYPE(QC_GO)
 #undef QC_GO
 #undef QC_GO2
-	NRM_TRY_RC(nrm_check_launch("k_qc_stats"));
+	NRM_TRY(nrm_check_launch("k_qc_stats"));
 	hipLaunchKernelGGL(k_qc_fold, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_work, tiles, n, d_cell_total, d_cell_nnz);
 	return nrm_check_launch("k_qc_fold");
 }
@@ -506,8 +451,8 @@ extern "C" int nrm_qc_stats(const void* d_x, int dtype, int64_t rows, int64_t n,
 extern "C" int nrm_qc_csr_stats(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
 								const uint8_t* d_gene_alive, const uint8_t* d_cell_alive, int64_t* d_gene_total, int64_t* d_gene_nnz, int64_t* d_cell_total,
 								int64_t* d_cell_nnz, int64_t* d_info, int64_t* d_work, void* stream) {
-	NRM_REQUIRE(qc_elem(dtype) != 0, "nrm_qc_csr_stats: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8");
-	NRM_TRY_RC(qc_csr_check("nrm_qc_csr_stats", d_indptr, d_indices, d_data, qc_elem(dtype), rows, n, nnz));
+	NRM_REQUIRE(nrm_count_elem(dtype) != 0, "nrm_qc_csr_stats: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8");
+	NRM_TRY(qc_csr_check("nrm_qc_csr_stats", d_indptr, d_indices, d_data, nrm_count_elem(dtype), rows, n, nnz));
 	NRM_REQUIRE(d_gene_alive && d_cell_alive && d_gene_total && d_gene_nnz && d_cell_total && d_cell_nnz && d_info && d_work, "nrm_qc_csr_stats: null pointer");
 	const int64_t tiles = (rows + QC_TR - 1) / QC_TR;
 	hipStream_t st = (hipStream_t)stream;
@@ -515,9 +460,9 @@ extern "C" int nrm_qc_csr_stats(const int64_t* d_indptr, const int32_t* d_indice
 #define QC_GO(TY)                                                                                                                                                    \
 	hipLaunchKernelGGL((k_qc_csr_stats<TY>), dim3((unsigned)tiles), dim3(256), 0, st, d_indptr, d_indices, (const TY*)d_data, rows, n, nnz, d_gene_alive, d_cell_alive, \
 					   d_gene_total, d_gene_nnz, d_work, (qc_u64*)d_info)
-	QC_BY_DTYPE(QC_GO)
+	NRM_BY_COUNT_DTYPE(QC_GO)
 #undef QC_GO
-	NRM_TRY_RC(nrm_check_launch("k_qc_csr_stats"));
+	NRM_TRY(nrm_check_launch("k_qc_csr_stats"));
 	hipLaunchKernelGGL(k_qc_fold, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_work, tiles, n, d_cell_total, d_cell_nnz);
 	return nrm_check_launch("k_qc_fold");
 }
@@ -557,7 +502,7 @@ extern "C" int nrm_subset_dense(const void* d_x, int elem, int64_t rows, int64_t
 
 extern "C" int nrm_subset_csr_count(const int64_t* d_indptr, const int32_t* d_indices, int64_t rows, int64_t n, int64_t nnz, const uint8_t* d_gene_alive,
 									const uint8_t* d_cell_alive, int64_t* d_row_count, int64_t* d_info, void* stream) {
-	NRM_TRY_RC(qc_csr_check("nrm_subset_csr_count", d_indptr, d_indices, d_indices, 1, rows, n, nnz));
+	NRM_TRY(qc_csr_check("nrm_subset_csr_count", d_indptr, d_indices, d_indices, 1, rows, n, nnz));
 	NRM_REQUIRE(d_gene_alive && d_cell_alive && d_row_count && d_info, "nrm_subset_csr_count: null pointer");
 	hipStream_t st = (hipStream_t)stream;
 	NRM_HIP(hipMemsetAsync(d_info, 0, 16, st));
@@ -578,7 +523,7 @@ extern "C" int nrm_subset_csr_write(const int64_t* d_indptr, const int32_t* d_in
 									const uint8_t* d_gene_alive, const uint8_t* d_cell_alive, const int64_t* d_row_off, const int32_t* d_cell_map, int32_t* d_out_indices,
 									void* d_out_data, int64_t out_nnz, void* stream) {
 	NRM_REQUIRE(elem == 1 || elem == 2 || elem == 4 || elem == 8, "nrm_subset_csr_write: elements of 1, 2, 4 or 8 bytes");
-	NRM_TRY_RC(qc_csr_check("nrm_subset_csr_write", d_indptr, d_indices, d_data, elem, rows, n, nnz));
+	NRM_TRY(qc_csr_check("nrm_subset_csr_write", d_indptr, d_indices, d_data, elem, rows, n, nnz));
 	NRM_REQUIRE(d_gene_alive && d_cell_alive && d_row_off && d_cell_map && out_nnz >= 0, "nrm_subset_csr_write: bad arguments");
 	NRM_REQUIRE(out_nnz == 0 || (d_out_indices && d_out_data && (uintptr_t)d_out_indices % 4 == 0 && (uintptr_t)d_out_data % elem == 0), "nrm_subset_csr_write: bad output");
 	if (out_nnz == 0) return NRM_OK;

@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(256) k_residualize(const T* __restrict__ x, in
 			for (int r = 0; r < RES_R; r++)
 #pragma unroll
 				for (int q = 0; q < RES_CB; q++) {
-					double v = wave_sum(acc[r][q]);
+					double v = nrm_wave_sum(acc[r][q]);
 					if (lane == 0) s_part[wid][r * RES_CB + q] = v;
 				}
 			__syncthreads();
@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(256) k_residualize(const T* __restrict__ x, in
 	}
 #pragma unroll
 	for (int r = 0; r < RES_R; r++) {
-		double v = wave_sum(sq[r]);
+		double v = nrm_wave_sum(sq[r]);
 		if (lane == 0) s_ss[wid][r] = v;
 	}
 	__syncthreads();
@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 			for (int64_t k = (int64_t)tid * 4; k < n4; k += 1024) {
 				double xv[RES_R][4];
 #pragma unroll
-				for (int r = 0; r < RES_R; r++) RowLoad<T, NT>::ld(xr[r] + k, xv[r]);
+				for (int r = 0; r < RES_R; r++) nrm_ld4<T, true, NT>(xr[r] + k, xv[r]);
 				if (NS && c0 == 0) {
 #pragma unroll
 					for (int r = 0; r < RES_R; r++)
@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 				for (int q = 0; q < CB; q++) {
 					if (c0 + q < nc) {
 						double cv[4];
-						Vec4Load<double>::ld(c + (int64_t)(c0 + q) * ldc + k, cv);
+						nrm_ld4d<double, true>(c + (int64_t)(c0 + q) * ldc + k, cv);
 #pragma unroll
 						for (int r = 0; r < RES_R; r++)
 #pragma unroll
@@ -204,7 +204,7 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 			for (int r = 0; r < RES_R; r++)
 #pragma unroll
 				for (int q = 0; q < CB; q++) {
-					double v = wave_sum(live[r] ? acc[r][q] : 0.0);
+					double v = nrm_wave_sum(live[r] ? acc[r][q] : 0.0);
 					if (lane == 0) s_part[wid][r * CB + q] = v;
 				}
 			__syncthreads();
@@ -227,11 +227,11 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 	auto residual4 = [&](int64_t k, double (&v)[RES_R][4]) {
 		if (k < n4) {
 #pragma unroll
-			for (int r = 0; r < RES_R; r++) RowLoad<T, NT>::ld(xr[r] + k, v[r]);
+			for (int r = 0; r < RES_R; r++) nrm_ld4<T, true, NT>(xr[r] + k, v[r]);
 			if (active) {
 				for (int q = 0; q < nc; q++) {
 					double cv[4];
-					Vec4Load<double>::ld(c + (int64_t)q * ldc + k, cv);
+					nrm_ld4d<double, true>(c + (int64_t)q * ldc + k, cv);
 #pragma unroll
 					for (int r = 0; r < RES_R; r++)
 #pragma unroll
@@ -270,7 +270,7 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 		auto reduce_max = [&]() {
 #pragma unroll
 			for (int r = 0; r < RES_R; r++) {
-				double v = xmax[r], q = wave_sum(xsq[r]);
+				double v = xmax[r], q = nrm_wave_sum(xsq[r]);
 #pragma unroll
 				for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
 				if (lane == 0) {
@@ -359,7 +359,7 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 	auto request = [&](int64_t k, T (&raw)[RES_R][4]) {
 		if (k < n4) {
 #pragma unroll
-			for (int r = 0; r < RES_R; r++) RawLoad<T, NT>::ld(xr[r] + k, raw[r]);
+			for (int r = 0; r < RES_R; r++) nrm_ld4<T, true, NT>(xr[r] + k, raw[r]);
 		} else {
 #pragma unroll
 			for (int r = 0; r < RES_R; r++)
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 			if (k < n4) {
 				for (int q = 0; q < nc; q++) {
 					double cv[4];
-					Vec4Load<double>::ld(c + (int64_t)q * ldc + k, cv);
+					nrm_ld4d<double, true>(c + (int64_t)q * ldc + k, cv);
 #pragma unroll
 					for (int r = 0; r < RES_R; r++)
 #pragma unroll
@@ -446,7 +446,7 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 	}
 #pragma unroll
 	for (int r = 0; r < RES_R; r++) {
-		double v = wave_sum(sq[r]);
+		double v = nrm_wave_sum(sq[r]);
 		if (lane == 0) s_ss[wid][r] = v;
 	}
 	__shared__ long long s_ds[4][RES_R][NP], s_dq[4][RES_R][NP];
@@ -617,8 +617,8 @@ __global__ void __launch_bounds__(256) k_residualize_wide(const T* __restrict__ 
 			sq = fma(v, v, sq);
 		}
 		// per-block partial sums (no atomics: k_rw_sum adds them in block order, bitwise reproducible); the raw rows' squares ride along (k_rw_sum)
-		sq = wave_sum(sq);
-		raw = wave_sum(raw);
+		sq = nrm_wave_sum(sq);
+		raw = nrm_wave_sum(raw);
 		__syncthreads();
 		if (lane == 0) {
 			s_w[tid >> 6] = sq;
@@ -645,8 +645,8 @@ __global__ void __launch_bounds__(256) k_rw_sum(const double* __restrict__ part,
 		acc += part[(int64_t)b * RW_ROWS + r];
 		raw += part[((int64_t)nblocks + b) * RW_ROWS + r];
 	}
-	acc = wave_sum(acc);
-	raw = wave_sum(raw);
+	acc = nrm_wave_sum(acc);
+	raw = nrm_wave_sum(raw);
 	if ((threadIdx.x & 63) == 0) {
 		s_w[threadIdx.x >> 6] = acc;
 		s_r[threadIdx.x >> 6] = raw;
@@ -695,7 +695,7 @@ __global__ void __launch_bounds__(256) k_xc_partial(const T* __restrict__ x, int
 				double acc = 0.0;
 #pragma unroll
 				for (int j = 0; j < 4; j++) acc = fma(xv[j], cv[i][j], acc);
-				acc = wave_sum(acc);
+				acc = nrm_wave_sum(acc);
 				if (lane == 0 && q0 + i < nc) s_w[wid][q0 + i] = acc;
 			}
 		}

@@ -6,6 +6,7 @@
 //     ccy = M_i^+ a                                        association.py:357 (M_i = C_S C_S^T, pseudo-inverse on the host)
 //     |y~|^2 = q - a.ccy,  x~.y~ = xy - a.ccx_i            association.py:358-360 in closed form
 //     gamma = x~.y~ / (ns vx),  R^2 = gamma^2 vx / vy      association.py:367-371,  dof_i = ns_i - 1 - r_i - dimreduce
+#include "nrm_device.h"
 #include "nrm_pvalue.h"
 
 // per-grouping record (doubles): [0] ns, [1] vx (0 -> 1 applied), [2..25] p-value plan, then ccx (nc), then M^+ (nc*nc)
@@ -255,11 +256,6 @@ __global__ void __launch_bounds__(256, 2) k_s1_stream(const T* __restrict__ Y, i
 //   the cells of grouping i; common[c * ny + y] (c < nc), common[qrow * ny + y] from k_s1_stream.
 // NCT: the number of covariates when it is at most 8 (loops unrolled, sums in registers without predicates: the generic form spends
 // its time on 32 compare-and-branch pairs per cell), -1: any number up to S1_NCMAX.
-template <typename OutT>
-__device__ __forceinline__ void s1_put(void* base, int64_t o, double v) {
-	reinterpret_cast<OutT*>(base)[o] = (OutT)v;
-}
-
 template <typename T, int NCT>
 __global__ void __launch_bounds__(256) k_s1_cells(const T* __restrict__ YE, int64_t ldye, const double* __restrict__ CE, const double* __restrict__ xe,
 												   const int64_t* __restrict__ seg, const double* __restrict__ common, int qrow,
@@ -352,13 +348,13 @@ __global__ void __launch_bounds__(256) k_s1_cells(const T* __restrict__ YE, int6
 	const int64_t o = i * ldo + y;
 	const double pv = nrm_pvalue(r2, pl), st = return_dot ? gam * vx : gam;
 	if (out_f64) {
-		s1_put<double>(p_out, o, pv);
-		s1_put<double>(stat_out, o, st);
-		s1_put<double>(vary_out, o, vy);
+		nrm_store_out<double>(p_out, o, pv);
+		nrm_store_out<double>(stat_out, o, st);
+		nrm_store_out<double>(vary_out, o, vy);
 	} else {
-		s1_put<float>(p_out, o, pv);
-		s1_put<float>(stat_out, o, st);
-		s1_put<float>(vary_out, o, vy);
+		nrm_store_out<float>(p_out, o, pv);
+		nrm_store_out<float>(stat_out, o, st);
+		nrm_store_out<float>(vary_out, o, vy);
 	}
 	if (alpha_out) {
 		for (int c = 0; c < nc; c++) {
@@ -374,9 +370,9 @@ __global__ void __launch_bounds__(256) k_s1_cells(const T* __restrict__ YE, int6
 			}
 			const double al = ccy - gam * ccx[c];  // association.py:368-370
 			if (out_f64)
-				s1_put<double>(alpha_out, o * nc + c, al);
+				nrm_store_out<double>(alpha_out, o * nc + c, al);
 			else
-				s1_put<float>(alpha_out, o * nc + c, al);
+				nrm_store_out<float>(alpha_out, o * nc + c, al);
 		}
 	}
 }

@@ -1,6 +1,7 @@
 // single=4 ("other groupings as covariates", association.py:421-576,926-980) in closed form: one multiple
 // regression of every gene on A = [dx; dc] replaces the reference's per-grouping SVD loop.
 // The heavy contractions A A^T, Y A^T and (Y A^T) N run on K2; this file is the per-pair sweep.
+#include "nrm_device.h"
 #include "nrm_pvalue.h"
 #include "nrm_fix.h"
 
@@ -14,8 +15,7 @@ __global__ void __launch_bounds__(256) k_s4_rss(const double* __restrict__ bt, c
 	if (y >= ny) return;
 	double acc = 0.0;
 	for (int64_t k = lane; k < m; k += 64) acc = fma(pt[y * ldb + k], bt[y * ldb + k], acc);
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+	acc = nrm_wave_sum(acc);
 	if (lane == 0) rss[y] = yy[y] - acc;
 }
 

@@ -3,6 +3,7 @@
 // assertion, beta.cdf), :1037-1057 (coef->dot conversion, symmetrise, zero diagonal).
 #include <cmath>
 #include <cstring>
+#include "nrm_device.h"
 #include "nrm_pvalue.h"
 #include "nrm_fix.h"
 #include "nrm_host_logic.h"
@@ -44,10 +45,6 @@ __global__ void __launch_bounds__(256) k_pvalues_from_r2(const double* __restric
 
 #define SW_T 64
 #define SW_T_ 64
-template <typename T>
-__device__ __forceinline__ void store_out(void* base, int64_t idx, double v) {
-	reinterpret_cast<T*>(base)[idx] = (T)v;
-}
 
 // Integer-engine row records (nrm_fix.h) inside a sweep: the x rows of the workgroup's tile staged in LDS, the thread's column
 // The guard's counter saturates instead of wrapping: a wave adds its hits only while the counter is below 2^30 (a plain read first:
@@ -179,10 +176,10 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep(const double* __restrict
 			if (fix.fx && fix.budget > 0.0) nrm_fix_note(facc, sfx[r][5], sfx[r][6], r2);
 		}
 		const int64_t o = gi * ldo + gj;
-		store_out<OutT>(p_out, o, p);
-		store_out<OutT>(stat_out, o, stat);
-		if (r_out) store_out<OutT>(r_out, o, rr);
-		if (t_out) store_out<OutT>(t_out, o, tt);
+		nrm_store_out<OutT>(p_out, o, p);
+		nrm_store_out<OutT>(stat_out, o, stat);
+		if (r_out) nrm_store_out<OutT>(r_out, o, rr);
+		if (t_out) nrm_store_out<OutT>(t_out, o, tt);
 	}
 	if (fix.fx && fix.budget > 0.0 && nrm_fix_screen(fix, facc, fy, sqrt_dof)) {  // rare: the exact test, pair by pair
 #pragma unroll 1

@@ -2,6 +2,7 @@
 import numpy as np
 
 from .association import association_tests
+from . import engine as _engine
 
 
 def _varying_rows(dg):
@@ -41,7 +42,7 @@ def _finite_within(a, lo=None, hi=None):
 		# one threaded pass in the library (numpy's NaN-propagating min / max of 400 MB of fp64 take 35 ms)
 		from . import _lib
 		out = np.empty(3)
-		_lib.check(_lib.load().nrm_host_minmax(a.ctypes.data, _lib.NRM_F64 if a.dtype == np.float64 else _lib.NRM_F32, a.size, 0, out.ctypes.data))
+		_lib.check(_lib.load().nrm_host_minmax(a.ctypes.data, _engine.dtype_code(a), a.size, 0, out.ctypes.data))
 		if out[2] > 0:
 			return False
 		mn, mx = float(out[0]), float(out[1])

@@ -10,12 +10,10 @@ import numpy as np
 
 from . import _lib, _opts
 from ._lib import ROW_TILE
+from . import engine as _engine
 
 MAX_DENSITY = 1.0 / 16  # (break-even against K1 + the integer Gram engine is near one entry in ten)
 
-
-def _round_up(v, m):
-	return (v + m - 1) // m * m
 
 
 def candidate(eng, dx, dy, dc, samexy):
@@ -45,11 +43,11 @@ class Lists:
 		if d_x.stride(1) != 1:
 			d_x = d_x.contiguous()
 		ch = int(eng.lib.nrm_de_sparse_chunk())
-		nslots = _round_up(nx, 64)
+		nslots = _engine.round_up(nx, 64)
 		nch = (n + ch - 1) // ch
 		self.ngroups = nslots // 64
 		i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=eng.device)
-		code = _lib.NRM_F64 if d_x.dtype == torch.float64 else _lib.NRM_F32
+		code = _engine.dtype_code(d_x)
 		st = eng._stream()
 		cnt, coff = i32(nch, nslots), i32(nch, nslots)
 		info = torch.empty(8, dtype=torch.int64, device=eng.device)
@@ -59,9 +57,8 @@ class Lists:
 		if ell:
 			sig, pos, w = i32(nch, nslots), i32(nch, nslots), i32(nch * self.ngroups)
 			base = torch.empty(nch * self.ngroups, dtype=torch.int64, device=eng.device)
-		ptr = lambda t: 0 if t is None else t.data_ptr()
 		_lib.check(eng.lib.nrm_design_count(d_x.data_ptr(), code, nx, n, d_x.stride(0), cnt.data_ptr(), nslots, info.data_ptr(), st))
-		_lib.check(eng.lib.nrm_design_plan(cnt.data_ptr(), nx, n, nslots, ptr(sig), ptr(pos), ptr(w), ptr(base), self.row_ptr.data_ptr(), coff.data_ptr(),
+		_lib.check(eng.lib.nrm_design_plan(cnt.data_ptr(), nx, n, nslots, _engine.ptr(sig), _engine.ptr(pos), _engine.ptr(w), _engine.ptr(base), self.row_ptr.data_ptr(), coff.data_ptr(),
 										   self.slot2x.data_ptr(), info.data_ptr(), st))
 		h = info.cpu().numpy()  # the one synchronisation: the sizes of what follows
 		self.nnz, self.padded, self.bits = int(h[0]), int(h[1]), int(h[2])
@@ -75,8 +72,8 @@ class Lists:
 		if ell:
 			self.ell = torch.empty(max(self.padded, 8), dtype=torch.int16, device=eng.device)
 			self.vals = None if self.binary else torch.empty(max(self.padded, 8), dtype=torch.float64, device=eng.device)
-		_lib.check(eng.lib.nrm_design_fill(d_x.data_ptr(), code, nx, n, d_x.stride(0), nslots, ptr(pos), ptr(w), ptr(base), self.row_ptr.data_ptr(), coff.data_ptr(),
-										   ptr(self.ell), ptr(self.vals), self.cells.data_ptr(), ptr(self.row_vals), 1 if self.binary else 0, st))
+		_lib.check(eng.lib.nrm_design_fill(d_x.data_ptr(), code, nx, n, d_x.stride(0), nslots, _engine.ptr(pos), _engine.ptr(w), _engine.ptr(base), self.row_ptr.data_ptr(), coff.data_ptr(),
+										   _engine.ptr(self.ell), _engine.ptr(self.vals), self.cells.data_ptr(), _engine.ptr(self.row_vals), 1 if self.binary else 0, st))
 		self.sig, self.base, self.w = sig, base, w
 
 
@@ -104,10 +101,9 @@ def design_stats(eng, lists, d_c, d_dci, rank, nx, nc, flags=None):
 	"""|x~_i|^2 and b_i of every design row from its entries (csrc/nrm_de_sparse.hip: k_design_stats) -- K1 would sweep n cells twice
 	for rows that have a few hundred entries.  flags: the call's device counters; [2] counts design rows too close to the span of the
 	covariates for that difference (the caller redoes such a call on the dense path)."""
-	from . import engine as _engine
 	torch = eng.torch
 	ncu = nc if (rank > 0 and nc > 0) else 0
-	ss = eng.zeros((_round_up(nx, ROW_TILE), ), torch.float64)
+	ss = eng.zeros((_engine.round_up(nx, ROW_TILE), ), torch.float64)
 	coef = eng.zeros((nx, nc), torch.float64) if nc else eng.zeros((nx, 1), torch.float64)[:, :0]  # (covariates of rank 0: the coefficients stay zero)
 	with _engine._Span(eng, 'design_stats'):
 		_lib.check(eng.lib.nrm_design_stats(lists.row_ptr.data_ptr(), lists.cells.data_ptr(), 0 if lists.row_vals is None else lists.row_vals.data_ptr(),
@@ -137,16 +133,15 @@ def products(eng, lists, dy, d_c, d_dci, rank, bx, nx, ny, n, nc, want_coef, by_
 	"""x~_i . y~_y for every design row and expression row from the RAW expression rows (csrc/nrm_de_sparse.hip), |y~|^2 and, on request,
 	the expression rows' coefficients b_y.  by_gene: the products as (ny_pad, nx_pad) (single=4 reads them so), else (nx_pad, ny_pad).
 	flags: the call's device counters (engine.new_flags); [2] counts rows too close to the span of the covariates for these differences."""
-	from . import engine as _engine
 	torch = eng.torch
 	active = rank > 0 and nc > 0
 	d_y = dy if not isinstance(dy, np.ndarray) else eng.upload(_engine.as_input(dy))
-	nxp, nyp = _round_up(nx, ROW_TILE), _round_up(ny, ROW_TILE)
+	nxp, nyp = _engine.round_up(nx, ROW_TILE), _engine.round_up(ny, ROW_TILE)
 	dot = eng.zeros((nyp, nxp), torch.float64) if by_gene else torch.empty((nxp, nyp), dtype=torch.float64, device=eng.device)
 	ssy = torch.empty((nyp, ), dtype=torch.float64, device=eng.device)
 	ncu = nc if active else 0  # (covariates of rank 0 -- all zero -- leave the rows as they are: association.py:899-903)
 	coefy = eng.zeros((ny, nc), torch.float64) if want_coef else None
-	ycode = _lib.NRM_F64 if d_y.dtype == torch.float64 else _lib.NRM_F32
+	ycode = _engine.dtype_code(d_y)
 	common = torch.empty((ncu + 1, ny), dtype=torch.float64, device=eng.device)
 	# The rows' products with the covariates and their sums of squares: inside the gather kernel, on the fp64 matrix cores, from the chunk of rows
 	# it holds in LDS anyway -- one pass over the expression matrix -- for up to 8 covariates besides a constant one (csrc/nrm_de_sparse.hip);
@@ -163,7 +158,7 @@ def products(eng, lists, dy, d_c, d_dci, rank, bx, nx, ny, n, nc, want_coef, by_
 			_lib.check(eng.lib.nrm_fill_i32(code.data_ptr(), _lib.NRM_S1_COMMON, n, eng._stream()))
 		with _engine._Span(eng, 'row_sums'):
 			_lib.check(eng.lib.nrm_single1_stream(d_y.data_ptr(), ycode, d_y.stride(0), d_c.data_ptr() if ncu else 0, d_c.stride(0) if ncu else n, ncu, code.data_ptr(), n, ny,
-												  common.data_ptr(), common.data_ptr(), _round_up(ny, 8), eng._stream()))  # (no cell keeps its values: the last buffer is not written)
+												  common.data_ptr(), common.data_ptr(), _engine.round_up(ny, 8), eng._stream()))  # (no cell keeps its values: the last buffer is not written)
 	with _engine._Span(eng, 'de_sparse'):
 		_lib.check(eng.lib.nrm_de_sparse(d_y.data_ptr(), ycode, ny, n, d_y.stride(0), common.data_ptr(), ncu, d_dci.data_ptr() if ncu else 0, lists.ell.data_ptr(),
 										 0 if lists.vals is None else lists.vals.data_ptr(), lists.base.data_ptr(), lists.w.data_ptr(), lists.sig.data_ptr(), lists.ngroups,

@@ -20,10 +20,8 @@ import numpy as np
 from . import _opts
 
 from ._lib import ROW_TILE, K_TILE
+from . import engine as _engine
 
-
-def _round_up(v, m):
-	return (v + m - 1) // m * m
 
 
 def block_pair_schedule(rank, world, rows_pad):
@@ -35,7 +33,7 @@ def block_pair_schedule(rank, world, rows_pad):
 	if world % 2 == 0 and world > 1:
 		other = (rank + world // 2) % world
 		lo, hi = min(rank, other), max(rank, other)
-		half = _round_up(rows_pad // 2, ROW_TILE)
+		half = _engine.round_up(rows_pad // 2, ROW_TILE)
 		if rank == lo:
 			sched.append((lo, hi, 0, half, False))
 		elif half < rows_pad:
@@ -346,8 +344,8 @@ class CoexPlan:
 		self.be = backend if backend is not None else HipBackend(dt_local.device.index)
 		self.x = dt_local
 		self.rows, self.n = dt_local.shape
-		self.rows_pad = _round_up(max(self.rows, 1), ROW_TILE)
-		self.k_pad = _round_up(self.n, K_TILE)
+		self.rows_pad = _engine.round_up(max(self.rows, 1), ROW_TILE)
+		self.k_pad = _engine.round_up(self.n, K_TILE)
 		self.cov = self.be.covariates(dc)
 		self.dof = self.n - 1 - self.cov[2] - dimreduce
 		if self.dof <= 0:
@@ -490,7 +488,7 @@ class CoexPlan:
 			self.all_x[W * R:(W + wrap) * R].copy_(self.all_x[:wrap * R])
 		xs = self.all_x[(self.rank + 1) * R:(self.rank + 1 + K) * R]
 		prev = getattr(self, '_pd', None)  # (the previous step's partner block: overwritten, see _into)
-		pd, pss = self._timed('residualize', timed, lambda: self.be.residualize(xs, self.cov, _round_up(K * R, ROW_TILE),
+		pd, pss = self._timed('residualize', timed, lambda: self.be.residualize(xs, self.cov, _engine.round_up(K * R, ROW_TILE),
 																			   **(dict(into=prev) if prev is not None and isinstance(self.be, HipBackend) else {})))
 		self._pd = pd
 		dot = self._timed('gram', timed, lambda: self.be.gram(self._blk, pd, False, R, K * R))
@@ -743,7 +741,7 @@ class CoexPlan:
 			out = torch.empty((R, ng), dtype=torch.uint8, device=eng.device)
 			total = torch.zeros(1, dtype=torch.int64, device=eng.device)
 			flags = torch.zeros(2, dtype=torch.int32, device=eng.device)
-			_lib.check(eng.lib.nrm_binnet_rows(p_rows.data_ptr(), _lib.NRM_F64 if p_rows.dtype == torch.float64 else _lib.NRM_F32, R, ng,
+			_lib.check(eng.lib.nrm_binnet_rows(p_rows.data_ptr(), _engine.dtype_code(p_rows), R, ng,
 											   p_rows.stride(0), self.rank * R, float(qcut), out.data_ptr(), out.stride(0), total.data_ptr(),
 											   flags.data_ptr(), eng._stream()))
 			stats = torch.stack([total[0], flags[0].to(torch.int64)])

@@ -25,12 +25,26 @@ def _torch():
 	return torch
 
 
-def _round_up(v, m):
+def is_dev(a):
+	"""True for a tensor in device memory (anything else -- numpy, scipy, None -- is the host's)."""
+	return hasattr(a, 'is_cuda') and a.is_cuda
+
+
+def round_up(v, m):
 	return (v + m - 1) // m * m
 
 
-def _code(dtype):
-	return NRM_F64 if np.dtype(dtype) == np.float64 else NRM_F32
+def ptr(t):
+	"""Device address of a tensor for the C ABI; 0 (a null pointer: "not asked for") for None."""
+	return 0 if t is None else t.data_ptr()
+
+
+def dtype_code(t):
+	"""NRM_F64 / NRM_F32 for a tensor or an array (by its dtype), a torch dtype or a numpy dtype; torch need not be importable."""
+	d = t if isinstance(t, (type, np.dtype)) else getattr(t, 'dtype', t)
+	if str(d).startswith('torch.'):
+		return NRM_F64 if str(d) == 'torch.float64' else NRM_F32
+	return NRM_F64 if np.dtype(d) == np.float64 else NRM_F32
 
 
 def as_input(a):
@@ -340,8 +354,8 @@ class Engine:
 				x = self.upload(as_input(x))
 			rows, n = x.shape
 			nc = 0 if d_c is None else d_c.shape[0]
-			rp = _round_up(max(rows, 1), ROW_TILE) if rows_pad is None else rows_pad
-			kp = _round_up(n, K_TILE)
+			rp = round_up(max(rows, 1), ROW_TILE) if rows_pad is None else rows_pad
+			kp = round_up(n, K_TILE)
 			esz = x.element_size()
 			fused = bool(nslices) and rp % ROW_TILE == 0 and self.k1_quantises(x, d_c)
 			if fused:
@@ -389,7 +403,7 @@ class Engine:
 		with torch.cuda.device(self.device):
 			rows, n = x.shape
 			nc = 0 if d_c is None else d_c.shape[0]
-			kp = _round_up(n, K_TILE)
+			kp = round_up(n, K_TILE)
 			nks = (kp + 31) // 32
 			cks = (nks + max(1, chunks) - 1) // max(1, chunks)
 			nchunks = (nks + cks - 1) // cks
@@ -591,7 +605,7 @@ class Engine:
 				dot = self.gram(rx, ry, False, nslices=self.gram_slices(n))
 				_lib.check(self.lib.nrm_assoc_sweep(dot.data_ptr(), dot.stride(0), rx.ss.data_ptr(), ry.ss.data_ptr(), nx, b - a, int(n),
 													float(dof), 0, int(stat_kind), p.data_ptr() + a * esz, stat.data_ptr() + a * esz, 0, 0,
-													_code(out_dtype), ny, flags.data_ptr(), *self.fix_args(rx, ry), self._stream()))
+													dtype_code(out_dtype), ny, flags.data_ptr(), *self.fix_args(rx, ry), self._stream()))
 				_lib.check(self.lib.nrm_copy_rows(ssy.data_ptr() + a * 8, 8 * (b - a), ry.ss.data_ptr(), 8 * (b - a), 8 * (b - a), 1, self._stream()))
 			self.check_flags(flags)
 			return dict(p=self.download(p), stat=self.download(stat), alpha=None, varx=self.variances(rx.ss, nx, n, out_dtype),
@@ -658,7 +672,7 @@ class Engine:
 					self.gram(rx, ry, samexy, dot=dot, rows=(a, rx.rows_pad if b == nx else b), nslices=self.gram_slices(n))
 					_lib.check(self.lib.nrm_assoc_sweep_band(dot.data_ptr(), dot.stride(0), rx.ss.data_ptr(), ry.ss.data_ptr(), nx, ny, int(n),
 															 float(dof), 1 if samexy else 0, int(stat_kind), p.data_ptr(), stat.data_ptr(), 0, 0,
-															 _code(out_dtype), max(ny, 1), flags.data_ptr(), a, b, *self.fix_args(rx, ry), self._stream()))
+															 dtype_code(out_dtype), max(ny, 1), flags.data_ptr(), a, b, *self.fix_args(rx, ry), self._stream()))
 					ev = torch.cuda.Event()
 					ev.record(main)
 					done.append(ev)
@@ -697,9 +711,9 @@ class Engine:
 		ns = self.gram_slices(n)
 		odt = np.dtype(out_dtype)
 		tdt = torch.float64 if odt == np.float64 else torch.float32
-		code = _code(out_dtype)
+		code = dtype_code(out_dtype)
 		esz = odt.itemsize
-		mp, kp = _round_up(ng, ROW_TILE), _round_up(n, K_TILE)
+		mp, kp = round_up(ng, ROW_TILE), round_up(n, K_TILE)
 		nks = (kp + 31) // 32
 		plane = (mp // 32) * nks * 1024
 		cuts = list(range(0, ng, self.BAND)) + [ng]
@@ -791,7 +805,7 @@ class Engine:
 					xc.record_stream(main)
 					if host is None:  # page-lock the result arrays from a helper thread, started after the first upload (see association_single0)
 						host = self.start_host_results(ng, ng, out_dtype, bands=cuts)
-					rpc = _round_up(b - a, ROW_TILE)
+					rpc = round_up(b - a, ROW_TILE)
 					_lib.check(self.lib.nrm_residualize_q(
 						xc.data_ptr(), NRM_F64 if xc.dtype == torch.float64 else NRM_F32, b - a, n, xc.stride(0),
 						0 if d_c is None else d_c.data_ptr(), nc, 0 if d_c is None else d_c.stride(0), 0 if d_dci is None else d_dci.data_ptr(), int(rank),
@@ -848,7 +862,7 @@ class Engine:
 		dof = n - 1 - rank - dimreduce
 		odt = np.dtype(out_dtype)
 		tdt = torch.float64 if odt == np.float64 else torch.float32
-		mp, kp = _round_up(n_genes, ROW_TILE), _round_up(n, K_TILE)
+		mp, kp = round_up(n_genes, ROW_TILE), round_up(n, K_TILE)
 		nks = (kp + 31) // 32
 		plane = (mp // 32) * nks * 1024
 		with torch.cuda.device(self.device):
@@ -874,7 +888,7 @@ class Engine:
 				b = min(n_genes, a + block_rows)
 				x = block_fn(a, b)
 				assert tuple(x.shape) == (b - a, n) and self.k1_quantises(x, d_c)
-				rpc = _round_up(b - a, ROW_TILE)
+				rpc = round_up(b - a, ROW_TILE)
 				with _Span(self, 'residualize'):
 					_lib.check(self.lib.nrm_residualize_q(
 						x.data_ptr(), NRM_F64 if x.dtype == torch.float64 else NRM_F32, b - a, n, x.stride(0),
@@ -893,7 +907,7 @@ class Engine:
 				self.gram(whole, whole, True, dot=dot, rows=(a, mp if b == n_genes else b), nslices=ns)
 				with _Span(self, 'sweep'):
 					_lib.check(self.lib.nrm_assoc_sweep_band(dot.data_ptr(), dot.stride(0), ss.data_ptr(), ss.data_ptr(), n_genes, n_genes, int(n), float(dof), 1, 0,
-															 p.data_ptr(), stat.data_ptr(), 0, 0, _code(out_dtype), n_genes, flags.data_ptr(), a, b,
+															 p.data_ptr(), stat.data_ptr(), 0, 0, dtype_code(out_dtype), n_genes, flags.data_ptr(), a, b,
 															 *self.fix_args(whole, whole), self._stream()))
 			mark('swept')
 			if timings is not None:
@@ -918,7 +932,7 @@ class Engine:
 			_lib.check(self.lib.nrm_assoc_sweep(dot.data_ptr(), dot.stride(0), ssx.data_ptr(), ssy.data_ptr(), nx, ny,
 												int(n_cells), float(dof), 1 if symmetric else 0, int(stat_kind),
 												p.data_ptr(), stat.data_ptr(), 0 if r is None else r.data_ptr(),
-												0 if t is None else t.data_ptr(), _code(out_dtype), max(ny, 1),
+												0 if t is None else t.data_ptr(), dtype_code(out_dtype), max(ny, 1),
 												flags.data_ptr(), *(fix if fix is not None else (0, 0, 0, 0.0)), self._stream()))
 		return p, stat, r, t, flags
 
@@ -967,7 +981,7 @@ class Engine:
 		16-cell slabs without bounds checks).  No copy when n is already a multiple of 16 and the array is on the device."""
 		torch = self.torch
 		rows, n = a.shape
-		n16 = _round_up(n, 16)
+		n16 = round_up(n, 16)
 		if isinstance(a, np.ndarray):
 			t = torch.from_numpy(np.ascontiguousarray(a))
 			if n16 == n:
@@ -1026,7 +1040,7 @@ class Engine:
 				d_cz, d_dciz = d_c, d_dci
 			ncz = nc - (1 if ci >= 0 else 0)  # covariate rows that stay in Z
 			# design rows: a = x C^T through the streaming Gram (all CUs), then x~ = x - (a dci) C spread along the cells
-			k32 = _round_up(n, 128)
+			k32 = round_up(n, 128)
 			# Z = [C; X~; 0], stacked on the device through the C ABI.  The covariate rows do not change between calls on the same
 			# covariates (a DePlan's steps): the buffer is kept and only the rows past the covariates are rewritten.
 			zc = state.get('z')
@@ -1058,7 +1072,7 @@ class Engine:
 			rx = Residualized(nx, n, xt, ssx, coefx)
 			y = self._rows_padded16(dy)
 			ycode = NRM_F64 if y.dtype == torch.float64 else NRM_F32
-			ny_pad = _round_up(ny, 256)
+			ny_pad = round_up(ny, 256)
 			g = torch.empty((ny_pad, 32), dtype=torch.float64, device=self.device)
 			ssraw = torch.empty((ny_pad, ), dtype=torch.float64, device=self.device)
 			with _Span(self, 'gram'):
@@ -1074,7 +1088,7 @@ class Engine:
 			stat_kind = 0 if return_dot else 1
 			_lib.check(self.lib.nrm_de_small_sweep(g.data_ptr(), ssraw.data_ptr(), 0 if d_dciz is None else d_dciz.data_ptr(), nc, int(rank),
 												   rx.ss.data_ptr(), nx, ny, n, float(dof), stat_kind, p.data_ptr(), stat.data_ptr(),
-												   0 if r is None else r.data_ptr(), 0 if t is None else t.data_ptr(), _code(out_dtype),
+												   0 if r is None else r.data_ptr(), 0 if t is None else t.data_ptr(), dtype_code(out_dtype),
 												   ny, ssy.data_ptr(), 0 if by is None else by.data_ptr(), flags.data_ptr(), 1 if ci >= 0 else 0, self._stream()))
 			alpha = None
 			if want_alpha:

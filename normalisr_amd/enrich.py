@@ -22,14 +22,13 @@ import logging
 
 import numpy as np
 
+from . import engine as _engine
+
 # the reference's default evidence codes (gocovt.py:51-53): not expression based, to avoid circular reasoning
 EVIDENCE_SET = frozenset(['EXP', 'IDA', 'IPI', 'IMP', 'IGI', 'HTP', 'HDA', 'HMP', 'HGI', 'IBA', 'IBD', 'IKR', 'IRD', 'ISS', 'ISO', 'ISA', 'ISM'])
 COLUMNS = ('name', 'depth', 'p_uncorrected', 'p_bonferroni', 'odds_ratio', 'ratio_in_study', 'ratio_in_pop', 'id', 'study_items')  # (gocovt.py:182-184; GO -> id)
 TOP_DTYPE = np.dtype([('index', '<i8'), ('k', '<i8'), ('K', '<i8'), ('p', '<f8')])  # the record of nrm_enrich_top
 
-
-def _is_dev(a):
-	return hasattr(a, 'is_cuda') and a.is_cuda
 
 
 class GeneSets:
@@ -262,7 +261,7 @@ class EnrichResult:
 	@property
 	def p_bonferroni(self):
 		"""min(1, p T), T = the number of bound sets."""
-		if _is_dev(self.p):
+		if _engine.is_dev(self.p):
 			return (self.p * self.ntest).clamp_(max=1.0)
 		return np.minimum(1.0, self.p * self.ntest)
 
@@ -279,12 +278,12 @@ class EnrichResult:
 		return self.sets.genes(t)
 
 	def _row(self, a, s):
-		return np.asarray(a[s].cpu().numpy() if _is_dev(a) else a[s])
+		return np.asarray(a[s].cpu().numpy() if _engine.is_dev(a) else a[s])
 
 	def table(self, s=0):
 		"""The enrichment of study s as a list of rows (tuples in the order of COLUMNS, the columns the reference writes) sorted by p, equal p by set index."""
 		k, p, odds = self._row(self.k, s), self._row(self.p, s), self._row(self.odds, s)
-		K = np.asarray(self.K.cpu().numpy() if _is_dev(self.K) else self.K)
+		K = np.asarray(self.K.cpu().numpy() if _engine.is_dev(self.K) else self.K)
 		n = int(self._row(self.n, s))
 		study = np.ascontiguousarray(self._row(self._words, s)).view(np.uint64)
 		pb = np.minimum(1.0, p * self.ntest)
@@ -299,7 +298,7 @@ class EnrichResult:
 def _study_matrix(study, bound):
 	"""The study as an (S, G) byte matrix, numpy or a torch CUDA tensor: a matrix as it is, a list of names or rows as one row."""
 	ng = bound.ng
-	if _is_dev(study) and study.dim() == 2:
+	if _engine.is_dev(study) and study.dim() == 2:
 		import torch
 		if study.dtype not in (torch.bool, torch.uint8):
 			raise TypeError('study must be bool or uint8.')
@@ -307,7 +306,7 @@ def _study_matrix(study, bound):
 			raise ValueError('A study matrix must have one column per gene.')
 		x = study if study.stride(1) == 1 and study.stride(0) >= ng else study.contiguous()
 		return x.view(torch.uint8) if x.dtype == torch.bool else x
-	if _is_dev(study):  # integer rows in HBM (principal_genes(..., device_out=True))
+	if _engine.is_dev(study):  # integer rows in HBM (principal_genes(..., device_out=True))
 		import torch
 		if study.dim() != 1 or study.dtype not in (torch.int32, torch.int64):
 			raise ValueError('A study in HBM is an (S, G) bool / uint8 matrix or a one-dimensional list of integer rows.')
@@ -350,13 +349,12 @@ def _enrich_host(x, bound, nmin):
 
 def _enrich_engine(x, bound, nmin, device_out):
 	from . import _lib
-	from . import engine as _engine
-	eng = _engine.get_engine(x.device.index if _is_dev(x) else None)
+	eng = _engine.get_engine(x.device.index if _engine.is_dev(x) else None)
 	S, T, ng = int(x.shape[0]), len(bound), bound.ng
 	with eng.lock:
 		torch = eng.torch
 		with torch.cuda.device(eng.device):
-			d_x = x if _is_dev(x) else eng.upload(x)
+			d_x = x if _engine.is_dev(x) else eng.upload(x)
 			d_bits, d_bg = bound.device(eng)
 			dev = dict(device=eng.device)
 			words = torch.empty((S, d_bits.shape[1]), dtype=torch.int64, **dev)
@@ -391,7 +389,6 @@ def enrich(study, sets, namet=None, bg=None, nmin=5, device_out=False, device=No
 	nmin: the fewest study genes a top set must hold (below 1 means 1).  device: the GPU's index.
 	Returns an EnrichResult; with device_out=True its k, K, n, p and odds stay in HBM.  With torch it runs on the engine; in a process without torch, or with
 	NRM_HOST_ENTRY=1, through the library's whole-problem entry nrm_enrich_host."""
-	from . import engine as _engine
 	if isinstance(sets, BoundSets):
 		if bg is not None or (namet is not None and (len(namet) != sets.ng or any(str(a) != str(b) for a, b in zip(namet, sets.namet)))):
 			raise ValueError('A BoundSets carries its gene list and background: bind again for others.')
@@ -405,7 +402,7 @@ def enrich(study, sets, namet=None, bg=None, nmin=5, device_out=False, device=No
 	x = _study_matrix(study, bound)
 	with _engine.use_device(device):
 		from .association import _use_host_entry
-		if not _is_dev(x) and not device_out and _use_host_entry():
+		if not _engine.is_dev(x) and not device_out and _use_host_entry():
 			res = _enrich_host(x, bound, nmin)
 		else:
 			res = _enrich_engine(x, bound, nmin, device_out)
@@ -423,7 +420,7 @@ def top_pathway(net, namet, sets, n=100, nmin=5):
 	if namet.ndim != 1 or len(net.shape) < 1 or namet.shape[0] != net.shape[0]:
 		raise ValueError('Wrong shape for net or namet.')
 	sel = gocovt.principal_genes(net, n=n)
-	res = enrich(sel, sets, namet=None if isinstance(sets, BoundSets) else namet, nmin=nmin, device=net.device.index if _is_dev(net) else None)
+	res = enrich(sel, sets, namet=None if isinstance(sets, BoundSets) else namet, nmin=nmin, device=net.device.index if _engine.is_dev(net) else None)
 	name = res.top_sets(0)
 	return [str(x) for x in namet[sel]], res, name, [str(x) for x in res.genes(int(res.top[0]))]
 

@@ -24,13 +24,12 @@ import warnings
 
 import numpy as np
 
+from . import engine as _engine
+
 _POWER_BLOCK = 16  # power steps between two read-backs of (lambda, residual)
 _UNIT = 2.0**-53
 _K1_PASSES = 2  # applications of K1 to the chosen rows (see pccovt)
 
-
-def _is_dev(a):
-	return hasattr(a, 'is_cuda') and a.is_cuda
 
 
 def _check_principal_args(shape, n):
@@ -56,15 +55,14 @@ def net_degree(net, device_out=False):
 	"""Row sums of a binary network on the device: net (n_gene, n_gene), a numpy array or a torch CUDA tensor of bool or uint8 (what binnet returns; any
 	non-zero byte counts once; a pitch larger than the row is allowed).  int64, numpy or -- device_out=True -- a torch CUDA tensor."""
 	from . import _lib
-	from . import engine as _engine
 	if len(net.shape) != 2 or net.shape[0] != net.shape[1] or net.shape[0] < 1:
 		raise ValueError('Wrong shape for net or namet.')
 	ng = int(net.shape[0])
-	eng = _engine.get_engine(net.device.index if _is_dev(net) else None)
+	eng = _engine.get_engine(net.device.index if _engine.is_dev(net) else None)
 	with eng.lock:
 		torch = eng.torch
 		with torch.cuda.device(eng.device):
-			if _is_dev(net):
+			if _engine.is_dev(net):
 				x = net
 				if x.dtype not in (torch.bool, torch.uint8):
 					raise TypeError('net must be bool or uint8.')
@@ -90,8 +88,7 @@ def principal_genes(net, n=100, device_out=False):
 	_check_principal_args(tuple(net.shape), n)
 	sel = _select_principal(net_degree(net), n)
 	if device_out:
-		from . import engine as _engine
-		return _engine.get_engine(net.device.index if _is_dev(net) else None).upload(sel)
+		return _engine.get_engine(net.device.index if _engine.is_dev(net) else None).upload(sel)
 	return sel
 
 
@@ -165,8 +162,7 @@ def pccovt(dt, dc, namet, genes, condcov=True, device_out=False, max_iter=4096, 
 	position in genes of the loading of largest magnitude) and sign.
 	ValueError for an empty expression matrix, incompatible shapes, names that are not found ('Genes not found: a,b,c,...') and an empty genes."""
 	from . import _lib
-	from . import engine as _engine
-	dev = _is_dev(dt)
+	dev = _engine.is_dev(dt)
 	if not dev:
 		dt = np.asarray(dt)
 	dc = np.asarray(dc.cpu() if hasattr(dc, 'data_ptr') else dc)
@@ -230,7 +226,7 @@ def pccovt(dt, dc, namet, genes, condcov=True, device_out=False, max_iter=4096, 
 			sign = torch.empty((2, ), dtype=torch.int64, device=eng.device)
 			with _engine._Span(eng, 'pc_score'):
 				_lib.check(eng.lib.nrm_pc_score(res.data.data_ptr(), res.data.stride(0), m, ns, v.data_ptr(), a.data_ptr(), score.data_ptr(),
-												_lib.NRM_F64 if score_np == np.float64 else _lib.NRM_F32, work.data_ptr(), sign.data_ptr(), stream))
+												_engine.dtype_code(score_np), work.data_ptr(), sign.data_ptr(), stream))
 			info = None
 			if return_info:
 				top, sg = (int(t) for t in sign.cpu().numpy())

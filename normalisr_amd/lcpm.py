@@ -18,9 +18,6 @@ _WARN_LCPM = "Modifying keyword arguments other than nth or seed is neither reco
 _WARN_SF = "Modifying keyword arguments is neither recommended nor supported for function 'scaling_factor'. Do so at your own risk."
 
 
-def _is_dev(a):
-	return hasattr(a, 'is_cuda') and a.is_cuda
-
 
 def _is_sparse(a):
 	try:
@@ -58,6 +55,8 @@ def _host_counts(d):
 	return np.ascontiguousarray(d), neg
 
 
+MALFORMED_CSR = ('Malformed CSR matrix: indptr must rise from 0 to the number of stored entries, and the columns of every row must lie in [0, n_cell) and '
+				 'increase strictly (sum duplicates and sort the indices first).')
 _CODES = {'torch.int64': _lib.NRM_I64, 'torch.int32': _lib.NRM_I32, 'torch.int16': _lib.NRM_I16, 'torch.uint8': _lib.NRM_U8}
 
 # A scipy.sparse input takes the CSR kernels (csrc/nrm_lcpm_sparse.hip) up to this share of stored entries and today's dense route above it.
@@ -144,7 +143,7 @@ def _as_device_csr(d):
 	"""The device forms of a sparse matrix -- a DeviceCSR, a torch tensor of layout torch.sparse_csr in HBM -- as a DeviceCSR; None for anything else."""
 	if isinstance(d, DeviceCSR):
 		return d
-	if _is_dev(d) and str(getattr(d, 'layout', '')) == 'torch.sparse_csr':
+	if _engine.is_dev(d) and str(getattr(d, 'layout', '')) == 'torch.sparse_csr':
 		return DeviceCSR(d.crow_indices(), d.col_indices(), d.values(), d.shape)
 	return None
 
@@ -177,7 +176,7 @@ def _device_counts(eng, d):
 	if isinstance(d, DeviceCSR):
 		x, neg = _ready_csr(eng, d)
 		return x, x.code, neg
-	if not _is_dev(d):
+	if not _engine.is_dev(d):
 		if _is_sparse(d):
 			if _takes_csr(d):
 				x = _Csr(*[eng.upload(a) for a in canonical_csr(d)], d.shape)  # (three arrays of the stored entries: no dense matrix on either side)
@@ -218,8 +217,7 @@ class _Counts:
 		self.h_cell_total, self.h_cell_nnz, self.h_gene_zero = h[:ns], h[ns:2 * ns], h[2 * ns:2 * ns + nt]
 		self.total, self.max, self.negative = int(h[-4]), int(h[-3]), bool(h[-2])
 		if h[-1]:
-			raise ValueError('Malformed CSR matrix: indptr must rise from 0 to the number of stored entries, and the columns of every row must lie in '
-							 '[0, n_cell) and increase strictly (sum duplicates and sort the indices first).')
+			raise ValueError(MALFORMED_CSR)
 
 
 def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=True, nocov=False, device_out=False, out_dtype=None):
@@ -237,7 +235,7 @@ def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=
 	otype = np.dtype(np.float64 if out_dtype is None else out_dtype)
 	if otype not in (np.dtype(np.float32), np.dtype(np.float64)):
 		raise ValueError('out_dtype must be numpy.float32 or numpy.float64.')
-	if not _is_dev(d) and not _is_sparse(d):
+	if not _engine.is_dev(d) and not _is_sparse(d):
 		d, neg = _host_counts(d)
 		if neg:
 			raise ValueError('Negative value in d detected.')
@@ -255,7 +253,7 @@ def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=
 		assert ntot + 2 > 2
 		if nt * ns == 0:
 			raise ValueError('reads must not be empty.')
-	eng = _engine.get_engine(d.device.index if _is_dev(d) else None)
+	eng = _engine.get_engine(d.device.index if _engine.is_dev(d) else None)
 	with eng.lock:
 		torch = eng.torch
 		with torch.cuda.device(eng.device):
@@ -290,7 +288,7 @@ def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=
 						_lib.check(eng.lib.nrm_lcpm_colsum(x.data_ptr(), code, nt, ns, x.stride(0), d_exp.data_ptr(), tab.size, part.data_ptr(), d_t1.data_ptr(), eng._stream()))
 				del part
 			out = torch.empty((nt, ns), dtype=torch.float64 if otype == np.float64 else torch.float32, device=eng.device)
-			tail = (d_tab.data_ptr(), tab.size, 0 if d_t1 is None else d_t1.data_ptr(), out.data_ptr(), _lib.NRM_F64 if otype == np.float64 else _lib.NRM_F32,
+			tail = (d_tab.data_ptr(), tab.size, 0 if d_t1 is None else d_t1.data_ptr(), out.data_ptr(), _engine.dtype_code(otype),
 					out.stride(0), eng._stream())
 			if csr:
 				with _engine._Span(eng, 'lcpm_csr_write'):
@@ -330,7 +328,7 @@ def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
 	if varname not in ('logtpropmean', 'logtmeanprop', 'nt0mean', 'lognt0mean', 'log1-nt0mean'):
 		raise ValueError('Unknown varname: {}'.format(varname))
 	if varname == 'nt0mean':
-		eng = _engine.get_engine(dt.device.index if _is_dev(dt) else None)
+		eng = _engine.get_engine(dt.device.index if _engine.is_dev(dt) else None)
 		with eng.lock, eng.torch.cuda.device(eng.device):
 			x, code, _ = _device_counts(eng, dt)
 			zeros = _Counts(eng, x, code).h_gene_zero
@@ -339,7 +337,7 @@ def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
 		if isinstance(dt, DeviceCSR):  # (these four are whole-matrix numpy expressions: dense on the host)
 			import scipy.sparse
 			dt = scipy.sparse.csr_matrix((dt.data.cpu().numpy(), dt.indices.cpu().numpy(), dt.indptr.cpu().numpy()), shape=dt.shape)
-		h = dt.cpu().numpy() if _is_dev(dt) else (dt.toarray() if _is_sparse(dt) else np.asarray(dt))
+		h = dt.cpu().numpy() if _engine.is_dev(dt) else (dt.toarray() if _is_sparse(dt) else np.asarray(dt))
 		with np.errstate(divide='ignore', invalid='ignore'):
 			if varname == 'logtpropmean':
 				d = h.mean(axis=1)

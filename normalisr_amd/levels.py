@@ -19,6 +19,7 @@ import logging
 import numpy as np
 
 from .association import _check_dimreduce, _prepare_covariates
+from . import engine as _engine
 
 RHO_MIN = 1e-6    # a new row keeping at least this part of its squared length outside the span is a new direction
 RHO_SPAN = 1e-12  # a new row keeping at most this part lies in the span
@@ -29,9 +30,6 @@ class NonFiniteCovariates(AssertionError, ValueError):
 	"""Covariates with a NaN or an infinity.  coex answers them with ValueError('array must not contain infs or NaNs') from inv_rank (the reference: scipy's
 	check_finite, association.py:66); the class is an AssertionError as well, which is what a caller of append is told to expect."""
 
-
-def _is_dev(a):
-	return hasattr(a, 'is_cuda') and a.is_cuda
 
 
 def _host(a):
@@ -118,12 +116,11 @@ class CoexLevels:
 	A dt tensor written in place after construction (torch counts such writes) makes the next append or results rebuild from its current content."""
 
 	def __init__(self, dt, dc, dimreduce=0, device=None):
-		dev = _is_dev(dt)
+		dev = _engine.is_dev(dt)
 		if not dev:
 			dt = np.asarray(dt)
 		dc = _host(dc)
 		dc64, dci, dcr, self.dimreduce = _check_problem(tuple(dt.shape), dc, dimreduce)
-		from . import engine as _engine
 		self._eng = _engine.get_engine(dt.device.index if dev else device)
 		self.nt, self.ns = (int(v) for v in dt.shape)
 		if dev:
@@ -228,7 +225,6 @@ class CoexLevels:
 	def _downdate(self, q):
 		"""G -= a a^T and ss -= a^2 for the orthonormal directions q (m, n_cell); returns the two counters."""
 		from . import _lib
-		from . import engine as _engine
 		eng = self._eng
 		torch = eng.torch
 		m = q.shape[0]
@@ -241,7 +237,7 @@ class CoexLevels:
 			with _engine._Span(eng, 'coex_project'):
 				for k0 in range(0, m, _PROJECT_ROWS):
 					k = min(_PROJECT_ROWS, m - k0)
-					_lib.check(eng.lib.nrm_coex_project(x.data_ptr(), _lib.NRM_F64 if x.dtype == torch.float64 else _lib.NRM_F32, self.nt, self.ns, x.stride(0),
+					_lib.check(eng.lib.nrm_coex_project(x.data_ptr(), _engine.dtype_code(x), self.nt, self.ns, x.stride(0),
 														d_q[k0:].data_ptr(), k, d_q.stride(0), a[k0:].data_ptr(), a.stride(0), stream))
 			with _engine._Span(eng, 'coex_downdate'):
 				_lib.check(eng.lib.nrm_coex_downdate(self._g.data_ptr(), self.nt, self._g.stride(0), self._ss.data_ptr(), self._ss_ref.data_ptr(), a.data_ptr(), m,
@@ -261,7 +257,7 @@ def _iter_levels(dt, dc, namet, sets, qcut, lvmax, n, nmin, dimreduce, condcov, 
 		raise ValueError('lvmax must be a non-negative integer.')
 	if qcut <= 0 or qcut >= 1:
 		raise ValueError('Q-value cutoff must be between 0 and 1.')
-	if not _is_dev(dt):
+	if not _engine.is_dev(dt):
 		dt = np.asarray(dt)
 	dc = _host(dc)
 	_check_problem(tuple(dt.shape), dc, dimreduce)

@@ -23,9 +23,6 @@ from .association import inv_rank
 from .de import _finite_within  # (np.isfinite(a).all() from the array's minimum and maximum: one pass each, no temporary)
 
 
-def _round_up(v, m):
-	return (v + m - 1) // m * m
-
 
 def normvar1(dt, dc, w2=None):
 	"""Remove covariates from every row of dt (norm.py:131-163).  w2 (n_gene, n_cell): row g uses dc * w2[g]."""
@@ -65,14 +62,14 @@ def _normvar1_weighted(dt, dc, w2, tol=1E-8):
 			y = eng.upload(_engine.as_input(dt))
 			d_w = eng.upload(np.asarray(w2, dtype=np.float64))
 			d_c = eng.upload(np.asarray(dc, dtype=np.float64))
-			rp, kp = _round_up(nt, ROW_TILE), _round_up(ns, K_TILE)
+			rp, kp = _engine.round_up(nt, ROW_TILE), _engine.round_up(ns, K_TILE)
 			u = torch.zeros((rp, kp), dtype=torch.float64, device=eng.device)
 			v = torch.zeros((rp, kp), dtype=torch.float64, device=eng.device)
 			u[:nt, :ns] = d_w * d_w
 			v[:nt, :ns] = d_w * y.to(torch.float64)
-			pr = torch.zeros((_round_up(npair, ROW_TILE), kp), dtype=torch.float64, device=eng.device)
+			pr = torch.zeros((_engine.round_up(npair, ROW_TILE), kp), dtype=torch.float64, device=eng.device)
 			pr[:npair, :ns] = d_c[torch.as_tensor(iu[0], device=eng.device)] * d_c[torch.as_tensor(iu[1], device=eng.device)]
-			cp = torch.zeros((_round_up(nc, ROW_TILE), kp), dtype=torch.float64, device=eng.device)
+			cp = torch.zeros((_engine.round_up(nc, ROW_TILE), kp), dtype=torch.float64, device=eng.device)
 			cp[:nc, :ns] = d_c
 			R = _engine.Residualized
 			gm = eng.gram(R(nt, ns, u, None, None), R(npair, ns, pr, None, None), False)[:nt, :npair].cpu().numpy()
@@ -88,16 +85,13 @@ def _normvar1_weighted(dt, dc, w2, tol=1E-8):
 			tdt = torch.float64 if out_dtype == np.float64 else torch.float32
 			out = torch.empty((nt, ns), dtype=tdt, device=eng.device)
 			d_b = eng.upload(b)
-			_lib.check(eng.lib.nrm_normvar_apply_w2(y.data_ptr(), _lib.NRM_F64 if y.dtype == torch.float64 else _lib.NRM_F32, nt, ns, y.stride(0), d_w.data_ptr(),
+			_lib.check(eng.lib.nrm_normvar_apply_w2(y.data_ptr(), _engine.dtype_code(y), nt, ns, y.stride(0), d_w.data_ptr(),
 													d_w.stride(0), d_c.data_ptr(), nc, d_c.stride(0), d_b.data_ptr(), out.data_ptr(),
-													_lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32, ns, eng._stream()))
+													_engine.dtype_code(out_dtype), ns, eng._stream()))
 			dtn = eng.download(out)
 		assert _finite_within(dtn)
 		return dtn
 
-
-def _is_dev(a):
-	return hasattr(a, 'is_cuda') and a.is_cuda
 
 
 def _scaled_covariates(dc, w, cat):
@@ -128,7 +122,7 @@ def _normvar_host_entry(dt, dc, w, wt, dextra, cat, keepvar, tol, out_dtype):
 	out = _result((nt, ns), out_dtype)  # (page-locked, recycled: 400 MB of fresh numpy memory per call cost more than the kernels)
 	zero = ctypes.c_int64(0)
 	vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-	code = lambda a: _lib.NRM_F64 if a.dtype == np.float64 else _lib.NRM_F32
+	code = _engine.dtype_code
 	_lib.check(lib.nrm_normvar_host(vp(y), code(y), nt, ns, vp(lnw), vp(wt64), vp(c64), nc, float(tol), 1 if keepvar else 0, vp(out), code(out), ctypes.byref(zero)))
 	if zero.value:
 		raise RuntimeError('Zero-rank covariates found.')
@@ -214,8 +208,8 @@ def _wide_blocks(nt, ns, r):
 	"""(genes per block, pair rows per panel) of the wide normvar path from a byte budget: a gene holds its packed M_g (r (r + 1) / 2 doubles) and its rows of U and
 	V; a panel row is one row of P.  NRM_DEBUG nv_gene_block / nv_panel_rows set them (tests: several blocks and panels at small sizes)."""
 	npair = r * (r + 1) // 2
-	kp = _round_up(ns, K_TILE)
-	per_gene = 8 * (_round_up(npair, ROW_TILE) + ROW_TILE + 2 * kp + _round_up(r, ROW_TILE))
+	kp = _engine.round_up(ns, K_TILE)
+	per_gene = 8 * (_engine.round_up(npair, ROW_TILE) + ROW_TILE + 2 * kp + _engine.round_up(r, ROW_TILE))
 	gb = max(ROW_TILE, (3 << 29) // per_gene // ROW_TILE * ROW_TILE)  # 1.5 GiB
 	pr = max(ROW_TILE, (1 << 28) // (8 * kp) // ROW_TILE * ROW_TILE)  # 256 MiB
 	gb = int(_opts.debug('nv_gene_block', gb))
@@ -232,10 +226,10 @@ def _normvar_wide(eng, y, ycode, nt, ns, d_lnw, d_wt, basis, r, keepvar, out, oc
 	Returns the counters of nrm_normvar_chol (int32[4] on the device)."""
 	torch, lib = eng.torch, eng.lib
 	npair = r * (r + 1) // 2
-	kp = _round_up(ns, K_TILE)
+	kp = _engine.round_up(ns, K_TILE)
 	gb, pr = _wide_blocks(nt, ns, r)
-	gbp, prp, rp = _round_up(gb, ROW_TILE), _round_up(pr, ROW_TILE), _round_up(r, ROW_TILE)
-	ldm = _round_up(npair, ROW_TILE) + ROW_TILE  # (a panel's launch writes whole 16-column groups: up to 15 columns past its last pair, zeros, before the next panel's)
+	gbp, prp, rp = _engine.round_up(gb, ROW_TILE), _engine.round_up(pr, ROW_TILE), _engine.round_up(r, ROW_TILE)
+	ldm = _engine.round_up(npair, ROW_TILE) + ROW_TILE  # (a panel's launch writes whole 16-column groups: up to 15 columns past its last pair, zeros, before the next panel's)
 	f64 = dict(dtype=torch.float64, device=eng.device)
 	st = eng._stream()
 	bp = torch.zeros((rp, kp), **f64)
@@ -255,7 +249,7 @@ def _normvar_wide(eng, y, ycode, nt, ns, d_lnw, d_wt, basis, r, keepvar, out, oc
 											   v.data_ptr(), kp, gbp, s1.data_ptr(), s2.data_ptr(), st))
 			for p0 in range(0, npair, pr):
 				cnt = min(pr, npair - p0)
-				cp = _round_up(cnt, ROW_TILE)
+				cp = _engine.round_up(cnt, ROW_TILE)
 				_lib.check(lib.nrm_normvar_pairs(bp.data_ptr(), r, ns, kp, p0, cnt, pan.data_ptr(), cp, kp, st))
 				_lib.check(lib.nrm_gram_f64_whole(u.data_ptr(), pan.data_ptr(), gbp, cp, kp, kp, kp, m.data_ptr() + 8 * p0, ldm, g, cnt, st))
 			_lib.check(lib.nrm_gram_f64_whole(v.data_ptr(), bp.data_ptr(), gbp, rp, kp, kp, kp, a.data_ptr(), rp, g, r, st))
@@ -277,7 +271,7 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 	pseudo-inverses; 64 to nrm_wide_covariates() (1024), with more cells than covariates, the basis form of csrc/nrm_normvar_wide.hip: one orthonormal
 	basis of the covariates' row space for every gene and a Cholesky solve per gene on the device, when _wide_basis certifies that every gene's reference
 	rank is the basis rank -- otherwise (nearly collinear covariates, extreme weights) the reference's per-gene algorithm on the host, under a warning."""
-	if not _is_dev(dt):
+	if not _engine.is_dev(dt):
 		dt = np.asarray(dt)
 	dc, w, wt = np.asarray(dc), np.asarray(w), np.asarray(wt)
 	if any(x.ndim != 2 for x in (dt, dc)):
@@ -303,11 +297,11 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 	wide = nc > 63
 	if wide:
 		_check_wide('normvar', nc, ns)
-	dt_dtype = np.dtype(str(dt.dtype).replace('torch.', '')) if _is_dev(dt) else dt.dtype
+	dt_dtype = np.dtype(str(dt.dtype).replace('torch.', '')) if _engine.is_dev(dt) else dt.dtype
 	out_dtype = np.result_type(dt_dtype, dc.dtype, w.dtype, wt.dtype, np.float32)
 	out_dtype = np.dtype(np.float32) if out_dtype == np.float32 else np.dtype(np.float64)
 	from .association import _use_host_entry
-	if not wide and not _is_dev(dt) and not device_out and not normmean and _use_host_entry():
+	if not wide and not _engine.is_dev(dt) and not device_out and not normmean and _use_host_entry():
 		# no torch in this process (or the command line / NRM_HOST_ENTRY=1): the library's whole-problem entry, numpy buffers in and out
 		try:
 			return _normvar_host_entry(dt, dc, w, wt, dextra, cat, keepvar, tol, out_dtype)
@@ -328,12 +322,12 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 		npair = nc * (nc + 1) // 2
 		iu = np.triu_indices(nc) if not wide else None
 		with torch.cuda.device(eng.device):
-			y = dt if _is_dev(dt) else eng.upload(_engine.as_input(dt))
+			y = dt if _engine.is_dev(dt) else eng.upload(_engine.as_input(dt))
 			if y.dtype not in (torch.float32, torch.float64):
 				y = y.to(torch.float64)
 			if y.stride(1) != 1:
 				y = y.contiguous()
-			ycode = _lib.NRM_F64 if y.dtype == torch.float64 else _lib.NRM_F32
+			ycode = _engine.dtype_code(y)
 			d_lnw = eng.upload(np.log(np.asarray(w, dtype=np.float64)))
 			d_wt = eng.upload(np.asarray(wt, dtype=np.float64))
 			d_c = eng.upload(c64)
@@ -343,7 +337,7 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 			if wide:
 				out = torch.empty((nt, ns), dtype=tdt, device=eng.device)
 				if certified:
-					wflags = _normvar_wide(eng, y, ycode, nt, ns, d_lnw, d_wt, basis, rank, keepvar, out, _lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32)
+					wflags = _normvar_wide(eng, y, ycode, nt, ns, d_lnw, d_wt, basis, rank, keepvar, out, _engine.dtype_code(out_dtype))
 					wf = wflags.cpu().numpy()
 					assert not wf[0] and not wf[1]  # a pivot that is not positive or a value that is not finite (csrc/nrm_normvar_wide.hip): np.isfinite(dtn).all() (norm.py:286)
 				else:
@@ -362,11 +356,11 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 				out = torch.empty((nt, ns), dtype=tdt, device=eng.device)
 				with _engine._Span(eng, 'normvar_apply'):
 					_lib.check(eng.lib.nrm_normvar_apply(y.data_ptr(), ycode, nt, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr(), d_c.data_ptr(), nc, d_c.stride(0),
-														 d_b.data_ptr(), d_scale.data_ptr(), out.data_ptr(), _lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32, ns,
+														 d_b.data_ptr(), d_scale.data_ptr(), out.data_ptr(), _engine.dtype_code(out_dtype), ns,
 														 flags.data_ptr(), eng._stream()))
 				eng._normvar_ranks = d_rank  # (tests: the integer ranks of the last call)
 			if not on_device and not wide:
-				rp, kp = _round_up(nt, ROW_TILE), _round_up(ns, K_TILE)
+				rp, kp = _engine.round_up(nt, ROW_TILE), _engine.round_up(ns, K_TILE)
 				u = torch.empty((rp, kp), dtype=torch.float64, device=eng.device)
 				v = torch.empty((rp, kp), dtype=torch.float64, device=eng.device)
 				s1 = torch.empty((rp, ), dtype=torch.float64, device=eng.device)
@@ -374,9 +368,9 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 				_lib.check(eng.lib.nrm_normvar_weights(y.data_ptr(), ycode, nt, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr(), u.data_ptr(),
 													   v.data_ptr(), kp, rp, s1.data_ptr(), s2.data_ptr(), eng._stream()))
 				# operands of the two Gram contractions: P = pairwise products of covariate rows, C itself
-				pr = torch.zeros((_round_up(npair, ROW_TILE), kp), dtype=torch.float64, device=eng.device)
+				pr = torch.zeros((_engine.round_up(npair, ROW_TILE), kp), dtype=torch.float64, device=eng.device)
 				pr[:npair, :ns] = d_c[torch.as_tensor(iu[0], device=eng.device)] * d_c[torch.as_tensor(iu[1], device=eng.device)]
-				cp = torch.zeros((_round_up(nc, ROW_TILE), kp), dtype=torch.float64, device=eng.device)
+				cp = torch.zeros((_engine.round_up(nc, ROW_TILE), kp), dtype=torch.float64, device=eng.device)
 				cp[:nc, :ns] = d_c
 				R = _engine.Residualized
 				gm = eng.gram(R(nt, ns, u, None, None), R(npair, ns, pr, None, None), False)[:nt, :npair].cpu().numpy()
@@ -401,7 +395,7 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 				d_b, d_scale = eng.upload(b), eng.upload(scale)
 				_lib.check(eng.lib.nrm_normvar_apply(y.data_ptr(), ycode, nt, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr(), d_c.data_ptr(), nc,
 													 d_c.stride(0), d_b.data_ptr(), d_scale.data_ptr(), out.data_ptr(),
-													 _lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32, ns, flags.data_ptr(), eng._stream()))
+													 _engine.dtype_code(out_dtype), ns, flags.data_ptr(), eng._stream()))
 			# covariates: continuous rows (and the intercept for cat=1) are scaled by w (norm.py:261-273)
 			dcn = _scaled_covariates(dc, w, cat)
 			if normmean:
@@ -431,7 +425,7 @@ def normcov(dc, c=True):
 	Rows holding only 0 and 1 (one-hot categories) are left as they are.  Host numpy: the matrix is (n_cov, n_cell)."""
 	import warnings
 	assert dc is not None
-	dc = dc.cpu().numpy() if _is_dev(dc) else np.asarray(dc)
+	dc = dc.cpu().numpy() if _engine.is_dev(dc) else np.asarray(dc)
 	if dc.ndim != 2:
 		raise ValueError('Covariates must have 2 dimensions.')
 	ns = dc.shape[1]
@@ -480,9 +474,9 @@ def compute_var(dt, dc, stepmax=1, eps=1E-6):
 	reference divides by its zero spread, norm.py:108, and fails norm.py:125)."""
 	if eps <= 0 or stepmax <= 0:
 		raise ValueError('eps and stepmax must be positive.')
-	if not _is_dev(dt):
+	if not _engine.is_dev(dt):
 		dt = np.asarray(dt)
-	dc = dc.cpu().numpy() if _is_dev(dc) else np.asarray(dc)
+	dc = dc.cpu().numpy() if _engine.is_dev(dc) else np.asarray(dc)
 	if dt.ndim != 2 or dc.ndim != 2:
 		raise ValueError('dt and dc must both have 2 dimensions.')
 	if dt.shape[1] != dc.shape[1]:
@@ -497,16 +491,16 @@ def compute_var(dt, dc, stepmax=1, eps=1E-6):
 		raise ValueError('dt must not be empty.')
 	c64 = np.ascontiguousarray(dc, dtype=np.float64)
 	fit_log = _projector(np.concatenate([c64, np.ones((1, ns))], axis=0))  # the second regression has an intercept (norm.py:92,109-110)
-	eng = _engine.get_engine(dt.device.index if _is_dev(dt) else None)
+	eng = _engine.get_engine(dt.device.index if _engine.is_dev(dt) else None)
 	with eng.lock:
 		torch = eng.torch
 		with torch.cuda.device(eng.device):
-			y = dt if _is_dev(dt) else eng.upload(_engine.as_input(dt))
+			y = dt if _engine.is_dev(dt) else eng.upload(_engine.as_input(dt))
 			if y.dtype not in (torch.float32, torch.float64):
 				y = y.to(torch.float64)
 			if y.stride(1) != 1:
 				y = y.contiguous()
-			ycode = _lib.NRM_F64 if y.dtype == torch.float64 else _lib.NRM_F32
+			ycode = _engine.dtype_code(y)
 			d_c = eng.upload(c64)
 			f64 = dict(dtype=torch.float64, device=eng.device)
 			d_a, d_b = torch.empty((nt, nc), **f64), torch.empty((nt, nc), **f64)
@@ -557,7 +551,7 @@ class NormvarPlan:
 
 	def __init__(self, dt, dc, w, wt, cat=1, keepvar=True, tol=1E-8, eng=None):
 		from .distributed import StepGraph
-		if not _is_dev(dt):
+		if not _engine.is_dev(dt):
 			raise ValueError('NormvarPlan takes an expression matrix resident in HBM (a torch CUDA tensor); normvar() is the call for host arrays.')
 		self.eng = eng = eng or _engine.get_engine(dt.device.index)
 		torch = eng.torch
@@ -586,8 +580,8 @@ class NormvarPlan:
 		eng, y, out = self.eng, self.dt, self.out
 		nt, ns = y.shape
 		nc = self.dc.shape[0]
-		ycode = _lib.NRM_F64 if y.dtype == eng.torch.float64 else _lib.NRM_F32
-		ocode = _lib.NRM_F64 if out.dtype == eng.torch.float64 else _lib.NRM_F32
+		ycode = _engine.dtype_code(y)
+		ocode = _engine.dtype_code(out)
 		_lib.check(eng.lib.nrm_normvar_solve(y.data_ptr(), ycode, nt, ns, y.stride(0), self._lnw.data_ptr(), self._wt.data_ptr(), self._c.data_ptr(), nc, self._c.stride(0), float(self.tol),
 											 1 if self.keepvar else 0, self._mom.data_ptr(), self._b.data_ptr(), self._scale.data_ptr(), self._rank.data_ptr(), self._flags.data_ptr(), eng._stream()))
 		_lib.check(eng.lib.nrm_normvar_apply(y.data_ptr(), ycode, nt, ns, y.stride(0), self._lnw.data_ptr(), self._wt.data_ptr(), self._c.data_ptr(), nc, self._c.stride(0),
@@ -636,8 +630,8 @@ class ComputeVarPlan:
 		from .distributed import StepGraph
 		if eps <= 0 or stepmax <= 0:
 			raise ValueError('eps and stepmax must be positive.')
-		dc = dc.cpu().numpy() if _is_dev(dc) else np.asarray(dc)
-		shape = tuple(dt.shape) if _is_dev(dt) else np.asarray(dt).shape
+		dc = dc.cpu().numpy() if _engine.is_dev(dc) else np.asarray(dc)
+		shape = tuple(dt.shape) if _engine.is_dev(dt) else np.asarray(dt).shape
 		if len(shape) != 2 or dc.ndim != 2:
 			raise ValueError('dt and dc must both have 2 dimensions.')
 		if shape[1] != dc.shape[1]:
@@ -648,7 +642,7 @@ class ComputeVarPlan:
 			raise NotImplementedError('compute_var on the device takes 1 to 63 covariates.')
 		if nt == 0 or ns == 0:
 			raise ValueError('dt must not be empty.')
-		if not _is_dev(dt):
+		if not _engine.is_dev(dt):
 			raise ValueError('ComputeVarPlan takes a logCPM matrix resident in HBM (a torch CUDA tensor); compute_var() is the call for host arrays.')
 		self.eng = eng = eng or _engine.get_engine(dt.device.index)
 		torch = eng.torch
@@ -680,7 +674,7 @@ class ComputeVarPlan:
 		eng, y, lib = self.eng, self.dt, self.eng.lib
 		nt, ns = y.shape
 		nc = self.dc.shape[0]
-		ycode = _lib.NRM_F64 if y.dtype == eng.torch.float64 else _lib.NRM_F32
+		ycode = _engine.dtype_code(y)
 		st, p = eng._stream(), lambda t: t.data_ptr()
 		_lib.check(lib.nrm_fitvar_plan_start(ns, p(self._s), p(self._best), p(self._state[0]), st))
 		for i in range(self.stepmax):

@@ -19,9 +19,6 @@ from . import engine as _engine
 from . import lcpm as _lcpm
 from .lcpm import DeviceCSR
 
-_MALFORMED = ('Malformed CSR matrix: indptr must rise from 0 to the number of stored entries, and the columns of every row must lie in [0, n_cell) and '
-			  'increase strictly (sum duplicates and sort the indices first).')
-
 
 def _check_qc_reads_args(ndim, params):
 	if ndim != 2:
@@ -37,7 +34,7 @@ def _counts_on_device(eng, d):
 	canonical CSR whatever its density.  ValueError for a negative entry seen on the host side."""
 	if _lcpm._is_sparse(d):
 		return _lcpm._Csr(*[eng.upload(a) for a in _lcpm.canonical_csr(d)], d.shape)  # (raises for a negative value)
-	if not _lcpm._is_dev(d):
+	if not _engine.is_dev(d):
 		d, neg = _lcpm._host_counts(d)
 		if neg:
 			raise ValueError('Negative value in reads detected.')
@@ -78,7 +75,7 @@ class _Stats:
 										 ctypes.addressof(thr), self.gene_alive.data_ptr(), self.cell_alive.data_ptr(), self.tail.data_ptr(), eng._stream()))
 		h = self.tail.cpu().numpy()  # (the one read-back of an iteration: four integers)
 		if h[3]:
-			raise ValueError(_MALFORMED)
+			raise ValueError(_lcpm.MALFORMED_CSR)
 		if h[2]:
 			raise ValueError('Negative value in reads detected.')
 		return int(h[0]), int(h[1])
@@ -107,7 +104,7 @@ def qc_reads(reads, n_gene, nc_gene, ncp_gene, n_cell, nt_cell, ntp_cell, device
 	params = (n_gene, nc_gene, ncp_gene, n_cell, nt_cell, ntp_cell)
 	_check_qc_reads_args(d.ndim, params)
 	nt_all, ns_all = (int(v) for v in d.shape)
-	if not _lcpm._is_dev(d):  # (what the host can see is refused before anything touches the device)
+	if not _engine.is_dev(d):  # (what the host can see is refused before anything touches the device)
 		if _lcpm._is_sparse(d):
 			neg = bool(d.nnz and d.dtype.kind not in 'ub' and d.data.min() < 0)
 		else:
@@ -123,7 +120,7 @@ def qc_reads(reads, n_gene, nc_gene, ncp_gene, n_cell, nt_cell, ntp_cell, device
 			sel = tuple(eng.upload(v) for v in sel)
 		mask = sel[0] != 0
 		return sel + ((dict(iterations=0, gene_mask=mask, cell_mask=mask), ) if return_info else ())
-	eng = _engine.get_engine(d.device.index if _lcpm._is_dev(d) else None)
+	eng = _engine.get_engine(d.device.index if _engine.is_dev(d) else None)
 	with eng.lock:
 		torch = eng.torch
 		with torch.cuda.device(eng.device):
@@ -231,7 +228,7 @@ def _subset_csr(eng, c, genes, cells):
 	_lib.check(eng.lib.nrm_subset_csr_scan(rowc.data_ptr(), nt, gmask.data_ptr(), cmask.data_ptr(), ns, indptr.data_ptr(), cmap.data_ptr(), tail.data_ptr(), stream))
 	h = tail.cpu().numpy()  # (one small read-back: the size of the result)
 	if h[4]:
-		raise ValueError(_MALFORMED)
+		raise ValueError(_lcpm.MALFORMED_CSR)
 	assert int(h[0]) == ng and int(h[1]) == nc
 	nnz = int(h[2])
 	oidx = torch.empty((nnz, ), dtype=torch.int32, device=eng.device)
@@ -279,7 +276,7 @@ def subset(m, genes=None, cells=None, device_out=False):
 		for (h, t), what in zip(sel, ('genes', 'cells')):
 			if h is not None and h.size > 1 and not (np.diff(h) > 0).all():
 				raise ValueError('{} of a sparse matrix must increase strictly.'.format(what))
-	eng = _engine.get_engine(src.device.index if _lcpm._is_dev(src) else None)
+	eng = _engine.get_engine(src.device.index if _engine.is_dev(src) else None)
 	with eng.lock:
 		torch = eng.torch
 		with torch.cuda.device(eng.device):
@@ -290,11 +287,11 @@ def subset(m, genes=None, cells=None, device_out=False):
 				out = _subset_csr(eng, d, *sel)
 				if device_out or isinstance(m, DeviceCSR):
 					return out
-				if _lcpm._is_dev(m):
+				if _engine.is_dev(m):
 					return torch.sparse_csr_tensor(out.indptr, out.indices.to(torch.int64), out.data.to(m.values().dtype), size=out.shape)
 				import scipy.sparse
 				return scipy.sparse.csr_matrix((out.data.cpu().numpy().astype(kind, copy=False), out.indices.cpu().numpy(), out.indptr.cpu().numpy()), shape=out.shape)
-			if _lcpm._is_dev(m):
+			if _engine.is_dev(m):
 				x = m if m.stride(1) == 1 else m.contiguous()
 				if x.element_size() not in (1, 2, 4, 8) or x.dtype.is_complex:
 					raise TypeError('subset copies elements of 1, 2, 4 or 8 bytes.')

@@ -23,12 +23,6 @@ from ._lib import ROW_TILE
 from .association import inv_rank, small_pinv
 
 
-def _round_up(v, m):
-	return (v + m - 1) // m * m
-
-
-def _is_dev(a):
-	return hasattr(a, 'is_cuda') and a.is_cuda
 
 
 def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_stats=False, dimreduce=0, chunk=256, device_out=False, **ka):
@@ -64,7 +58,7 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 			return tuple(out)
 		dimreduce = vals[0]
 	dimreduce = int(dimreduce)
-	dx, dy, dc = (dx if _is_dev(dx) else np.asarray(dx)), (dy if _is_dev(dy) else np.asarray(dy)), np.asarray(dc)
+	dx, dy, dc = (dx if _engine.is_dev(dx) else np.asarray(dx)), (dy if _engine.is_dev(dy) else np.asarray(dy)), np.asarray(dc)
 	nx, n = dx.shape
 	ny, nc = dy.shape[0], dc.shape[0]
 	if dy.shape[1] != n or dc.shape[1] != n:
@@ -73,7 +67,7 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 		logging.warning('No covariate dc input.')
 	chunk = max(1, min(chunk, 8192 // (nc + 1)))  # bounds the masked-row operand W (chunk * (nc + 1) rows) for many covariates
 	c64 = np.asarray(dc, dtype=np.float64)
-	if _is_dev(dy):
+	if _engine.is_dev(dy):
 		out_dtype = np.dtype(np.float32 if str(dy.dtype) == 'torch.float32' else np.float64)
 	else:
 		out_dtype = dy.dtype if dy.dtype in (np.float32, np.float64) else np.dtype(np.float64)
@@ -84,7 +78,7 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 		nw = nc + 1
 		with torch.cuda.device(eng.device):
 			# cell selection on the device (association.py:914-918): the design matrix travels once, in its own dtype
-			d_dx = dx if _is_dev(dx) else eng.upload(_engine.as_input(dx))
+			d_dx = dx if _engine.is_dev(dx) else eng.upload(_engine.as_input(dx))
 			lists = None
 			if nc <= 32 and _opts.debug('single1', 'sparse') != 'dense':
 				# the design's entries listed by the library (csrc/nrm_design_lists.hip: one pass counts them and says what they are like, a
@@ -110,7 +104,7 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 			assert bool((hi > lo).all())  # >1 distinct value among the selected cells (:917-918)
 			del lo, hi
 			ns = sel.sum(dim=1).cpu().numpy().astype(np.float64)
-			ry = eng.residualize(dy if _is_dev(dy) else _engine.as_input(dy), None, None, 0)  # fp64 padded copy of Y
+			ry = eng.residualize(dy if _engine.is_dev(dy) else _engine.as_input(dy), None, None, 0)  # fp64 padded copy of Y
 			y2 = Residualized_sq(ry, eng)
 			d_c = eng.upload(c64) if nc else None
 			p = torch.empty((nx, ny), dtype=tdt, device=eng.device)
@@ -122,7 +116,7 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 			pitch = 26 + nc + nc * nc
 			kp = ry.k_pad
 			if nc:
-				cp = eng.zeros((_round_up(nc, ROW_TILE), kp), torch.float64)
+				cp = eng.zeros((_engine.round_up(nc, ROW_TILE), kp), torch.float64)
 				eng.copy_rows(cp, d_c)
 				cpad = _engine.Residualized(nc, n, cp, None, None)
 			for i0 in range(0, nx, chunk):
@@ -130,13 +124,13 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 				m = i1 - i0
 				d_sel = sel[i0:i1].to(torch.float64)  # (m, n)
 				d_x = d_dx[i0:i1].to(torch.float64)
-				wrows = _round_up(m * nw, ROW_TILE)
+				wrows = _engine.round_up(m * nw, ROW_TILE)
 				w = torch.zeros((wrows, kp), dtype=torch.float64, device=eng.device)
 				wv = w[:m * nw].view(m, nw, kp)
 				if nc:
 					wv[:, :nc, :n] = d_sel[:, None, :] * d_c[None, :, :]
 				wv[:, nc, :n] = d_sel * d_x
-				srows = _round_up(m, ROW_TILE)
+				srows = _engine.round_up(m, ROW_TILE)
 				s = torch.zeros((srows, kp), dtype=torch.float64, device=eng.device)
 				s[:m, :n] = d_sel
 				W = _engine.Residualized(m * nw, n, w, None, None)
@@ -167,7 +161,7 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 				dof = np.ascontiguousarray(dof, dtype=np.float64)
 				_lib.check(eng.lib.nrm_pvalue_plan_init_many(dof.ctypes.data, m, info.ctypes.data + 16, pitch))
 				d_info = eng.upload(info)
-				code = _lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32
+				code = _engine.dtype_code(out_dtype)
 				_lib.check(eng.lib.nrm_single1_sweep(g.data_ptr(), g.stride(0), g2.data_ptr(), g2.stride(0), d_info.data_ptr(), pitch, nc, m, ny,
 													 1 if return_dot else 0, p[i0:i1].data_ptr(), stat[i0:i1].data_ptr(), vary[i0:i1].data_ptr(),
 													 0 if alpha is None else alpha[i0:i1].data_ptr(), code, ny, flags.data_ptr(), eng._stream()))
@@ -212,8 +206,8 @@ class Single1Plan:
 		self._c64 = np.ascontiguousarray(np.asarray(dc, dtype=np.float64))
 		self.dimreduce, self.lowmem, self.return_dot = int(dimreduce), lowmem, return_dot
 		with eng.lock, eng.torch.cuda.device(eng.device):
-			self.d_dx = dx if _is_dev(dx) else eng.upload(_engine.as_input(np.asarray(dx)))
-			self.d_y = dy if _is_dev(dy) else eng.upload(_engine.as_input(np.asarray(dy)))
+			self.d_dx = dx if _engine.is_dev(dx) else eng.upload(_engine.as_input(np.asarray(dx)))
+			self.d_y = dy if _engine.is_dev(dy) else eng.upload(_engine.as_input(np.asarray(dy)))
 		self._build(lists)
 
 	def _build(self, lists=None):
@@ -254,13 +248,12 @@ class Single1Plan:
 			gb = int(eng.lib.nrm_single1_select_gram_blocks())
 			self.gpart = f64(1, gb, 64) if nc else None
 			self.gs = f64(nx, nc * (nc + 1) // 2 + nc + 1)
-			self.ldye = _round_up(ny, 8)  # (a multiple of a 128-byte line instead: measured, no difference -- 1.74 ms either way on one box)
+			self.ldye = _engine.round_up(ny, 8)  # (a multiple of a 128-byte line instead: measured, no difference -- 1.74 ms either way on one box)
 			# One row of YE per cell that carries exactly one grouping: the selection is run once here and that count read back (the only read-back of the
 			# plan, at construction: it depends on the design alone).  By the design's entry count instead -- no read-back at all -- the buffer of a design
 			# with a quarter of its entries set would be tens of GB.
-			ptr0 = lambda t: 0 if t is None else t.data_ptr()
-			_lib.check(eng.lib.nrm_single1_select(lists.row_ptr.data_ptr(), lists.cells.data_ptr(), ptr0(lists.row_vals), nx, n, nnz, ptr0(self.d_c), n, nc, self.cnt.data_ptr(),
-												  self.code.data_ptr(), self.seg.data_ptr(), self.idx.data_ptr(), self.xe.data_ptr(), ptr0(self.ce), self.rowinfo.data_ptr(),
+			_lib.check(eng.lib.nrm_single1_select(lists.row_ptr.data_ptr(), lists.cells.data_ptr(), _engine.ptr(lists.row_vals), nx, n, nnz, _engine.ptr(self.d_c), n, nc, self.cnt.data_ptr(),
+												  self.code.data_ptr(), self.seg.data_ptr(), self.idx.data_ptr(), self.xe.data_ptr(), _engine.ptr(self.ce), self.rowinfo.data_ptr(),
 												  0, self.sel_info.data_ptr(), eng._stream()))
 			self.n_kept = int(self.sel_info.cpu()[4])
 			self.ye = torch.empty((max(self.n_kept, 1), self.ldye), dtype=self.d_y.dtype, device=dev)
@@ -278,14 +271,13 @@ class Single1Plan:
 	def _launch(self):
 		eng, lib, L = self.eng, self.eng.lib, self.lists
 		nx, ny, n, nc = self.nx, self.ny, self.n, self.nc
-		ptr = lambda t: 0 if t is None else t.data_ptr()
 		st = eng._stream()
 		d_y = self.d_y
-		ycode = _lib.NRM_F64 if d_y.dtype == eng.torch.float64 else _lib.NRM_F32
+		ycode = _engine.dtype_code(d_y)
 		torch = eng.torch
 		with _engine._Span(eng, 's1_select'):
-			_lib.check(lib.nrm_single1_select(L.row_ptr.data_ptr(), L.cells.data_ptr(), ptr(L.row_vals), nx, n, self.nnz, ptr(self.d_c), n, nc, self.cnt.data_ptr(),
-											  self.code.data_ptr(), self.seg.data_ptr(), self.idx.data_ptr(), self.xe.data_ptr(), ptr(self.ce), self.rowinfo.data_ptr(),
+			_lib.check(lib.nrm_single1_select(L.row_ptr.data_ptr(), L.cells.data_ptr(), _engine.ptr(L.row_vals), nx, n, self.nnz, _engine.ptr(self.d_c), n, nc, self.cnt.data_ptr(),
+											  self.code.data_ptr(), self.seg.data_ptr(), self.idx.data_ptr(), self.xe.data_ptr(), _engine.ptr(self.ce), self.rowinfo.data_ptr(),
 											  0, self.sel_info.data_ptr(), st))  # (the shared cells' Gram matrix: on the second stream, below)
 		# The groupings' own statistics (a wave, then a LANE per grouping: 1000 lanes of Jacobi rotations and P-value plans, 70 us on 16 CUs) need the
 		# selection only, and the stream kernel needs nothing of them: they run beside it on a second stream (a fork and a join of the captured graph)
@@ -298,19 +290,19 @@ class Single1Plan:
 			ss = self._side.cuda_stream
 			if nc:
 				_lib.check(lib.nrm_single1_common_gram(self.cnt.data_ptr(), n, self.d_c.data_ptr(), n, nc, self.gpart.data_ptr(), ss))
-			_lib.check(lib.nrm_single1_group_stats(self.seg.data_ptr(), self.idx.data_ptr(), self.xe.data_ptr(), ptr(self.d_c), n, nc, nx, self.gs.data_ptr(), ss))
-			_lib.check(lib.nrm_single1_group_info(self.gs.data_ptr(), ptr(self.gpart), self.rowinfo.data_ptr(), self.sel_info.data_ptr(), nc, nx, self.dimreduce,
+			_lib.check(lib.nrm_single1_group_stats(self.seg.data_ptr(), self.idx.data_ptr(), self.xe.data_ptr(), _engine.ptr(self.d_c), n, nc, nx, self.gs.data_ptr(), ss))
+			_lib.check(lib.nrm_single1_group_info(self.gs.data_ptr(), _engine.ptr(self.gpart), self.rowinfo.data_ptr(), self.sel_info.data_ptr(), nc, nx, self.dimreduce,
 												  self.info.data_ptr(), self.pitch, self.varx.data_ptr(), self.flags.data_ptr(), ss))
 			joined.record(self._side)
 		with _engine._Span(eng, 's1_stream'):
-			_lib.check(lib.nrm_single1_stream(d_y.data_ptr(), ycode, d_y.stride(0), ptr(self.d_c), n, nc, self.code.data_ptr(), n, ny, self.common.data_ptr(),
+			_lib.check(lib.nrm_single1_stream(d_y.data_ptr(), ycode, d_y.stride(0), _engine.ptr(self.d_c), n, nc, self.code.data_ptr(), n, ny, self.common.data_ptr(),
 											  self.ye.data_ptr(), self.ldye, st))
 		main.wait_event(joined)
-		code_o = _lib.NRM_F64 if self.out_dtype == np.float64 else _lib.NRM_F32
+		code_o = _engine.dtype_code(self.out_dtype)
 		with _engine._Span(eng, 's1_cells'):
-			_lib.check(lib.nrm_single1_cells(self.ye.data_ptr(), ycode, self.ldye, ptr(self.ce), self.xe.data_ptr(), self.seg.data_ptr(), self.common.data_ptr(),
+			_lib.check(lib.nrm_single1_cells(self.ye.data_ptr(), ycode, self.ldye, _engine.ptr(self.ce), self.xe.data_ptr(), self.seg.data_ptr(), self.common.data_ptr(),
 											 self.info.data_ptr(), self.pitch, nc, nx, ny, 1 if self.return_dot else 0, self.p.data_ptr(), self.stat.data_ptr(),
-											 self.vary.data_ptr(), ptr(self.alpha), code_o, ny, self.flags.data_ptr(), st))
+											 self.vary.data_ptr(), _engine.ptr(self.alpha), code_o, ny, self.flags.data_ptr(), st))
 
 	def step(self, timed=False):
 		"""One pass over the screen; results stay in HBM (results() takes them)."""
@@ -386,9 +378,8 @@ def _sparse(eng, lists, dy, c64, nx, ny, n, nc, dimreduce, lowmem, return_dot, o
 	gb = int(eng.lib.nrm_single1_select_gram_blocks())
 	nb = (nc + 7) // 8
 	gpart = torch.empty((nb * (nb + 1) // 2, gb, 64), dtype=torch.float64, device=dev) if nc else None
-	ptr = lambda t: 0 if t is None else t.data_ptr()
-	_lib.check(eng.lib.nrm_single1_select(lists.row_ptr.data_ptr(), lists.cells.data_ptr(), ptr(lists.row_vals), nx, n, nnz, ptr(d_c), n, nc, cnt.data_ptr(),
-										  code.data_ptr(), d_seg.data_ptr(), idx_e.data_ptr(), xe_d.data_ptr(), ptr(d_ce), rowinfo.data_ptr(), ptr(gpart), info.data_ptr(),
+	_lib.check(eng.lib.nrm_single1_select(lists.row_ptr.data_ptr(), lists.cells.data_ptr(), _engine.ptr(lists.row_vals), nx, n, nnz, _engine.ptr(d_c), n, nc, cnt.data_ptr(),
+										  code.data_ptr(), d_seg.data_ptr(), idx_e.data_ptr(), xe_d.data_ptr(), _engine.ptr(d_ce), rowinfo.data_ptr(), _engine.ptr(gpart), info.data_ptr(),
 										  eng._stream()))
 	# The groupings' own sums by a wave each (k_s1_group_stats, <= 8 covariates) are queued at once, and so is the stream kernel when its output can be
 	# sized without the host (at most one row of YE per design entry; beyond 4 GB of that the kept count is waited for): what the host needs of the
@@ -398,10 +389,10 @@ def _sparse(eng, lists, dy, c64, nx, ny, n, nc, dimreduce, lowmem, return_dot, o
 	if on_device:
 		npair = nc * (nc + 1) // 2
 		gs_d = torch.empty((nx, npair + nc + 1), dtype=torch.float64, device=dev)
-		_lib.check(eng.lib.nrm_single1_group_stats(d_seg.data_ptr(), idx_e.data_ptr(), xe_d.data_ptr(), ptr(d_c), n, nc, nx, gs_d.data_ptr(), eng._stream()))
-	d_y = dy if _is_dev(dy) else eng.upload(_engine.as_input(dy))
-	ldye = _round_up(ny, 8)
-	ycode = _lib.NRM_F64 if d_y.dtype == torch.float64 else _lib.NRM_F32
+		_lib.check(eng.lib.nrm_single1_group_stats(d_seg.data_ptr(), idx_e.data_ptr(), xe_d.data_ptr(), _engine.ptr(d_c), n, nc, nx, gs_d.data_ptr(), eng._stream()))
+	d_y = dy if _engine.is_dev(dy) else eng.upload(_engine.as_input(dy))
+	ldye = _engine.round_up(ny, 8)
+	ycode = _engine.dtype_code(d_y)
 	common = torch.empty((nc + 1, ny), dtype=torch.float64, device=eng.device)
 	early = on_device and nnz * ldye * d_y.element_size() <= (4 << 30)
 
@@ -514,7 +505,7 @@ def _sparse(eng, lists, dy, c64, nx, ny, n, nc, dimreduce, lowmem, return_dot, o
 	alpha = None if lowmem else eng.zeros((nx, ny, nc), tdt)
 	flags = eng.zeros((2, ), torch.int32)
 	d_info = eng.upload(info)
-	code_o = _lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32
+	code_o = _engine.dtype_code(out_dtype)
 	with _engine._Span(eng, 's1_cells'):
 		_lib.check(eng.lib.nrm_single1_cells(ye.data_ptr(), ycode, ldye, 0 if d_ce is None else d_ce.data_ptr(), xe_d.data_ptr(), d_seg.data_ptr(),
 											 common.data_ptr(), d_info.data_ptr(), pitch, nc, nx, ny, 1 if return_dot else 0, p.data_ptr(), stat.data_ptr(),

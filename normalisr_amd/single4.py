@@ -30,9 +30,6 @@ from . import engine as _engine
 
 
 
-def _round_up(v, m):
-	return (v + m - 1) // m * m
-
 
 def _pvalues_grouped(eng, r2, dof):
 	"""p = I_{1-R^2}(dof/2, 1/2) on the device for an R^2 matrix whose dof varies per entry (one launch per distinct dof:
@@ -131,7 +128,7 @@ def _gram_host(a, b=None, want_ss=False):
 	numpy.matmul products).  want_ss: also the sums of squares of the rows of the second operand."""
 	a = np.ascontiguousarray(_engine.as_input(a))
 	b = None if b is None else np.ascontiguousarray(_engine.as_input(b))
-	code = lambda v: _lib.NRM_F64 if v.dtype == np.float64 else _lib.NRM_F32
+	code = _engine.dtype_code
 	rb = a.shape[0] if b is None else b.shape[0]
 	out = np.empty((a.shape[0], rb))
 	ss = np.empty(rb) if want_ss else None
@@ -163,7 +160,7 @@ def _single4_samexy(dx, dc, lowmem, return_dot, dimreduce, ka, eng, out_dtype):
 	else:
 		torch = eng.torch
 		from .engine import Residualized
-		mp, kp = _engine._round_up(m, _lib.ROW_TILE), _engine._round_up(n, _lib.K_TILE)
+		mp, kp = _engine.round_up(m, _lib.ROW_TILE), _engine.round_up(n, _lib.K_TILE)
 		with torch.cuda.device(eng.device):
 			a_dev = eng.zeros((mp, kp), torch.float64)
 			a_dev[:nx, :n] = eng.upload(_engine.as_input(dx))
@@ -234,9 +231,6 @@ def _spd_inverse(m):
 		w, v = np.linalg.eigh(m)
 		return (v / w) @ v.T
 
-
-def _is_dev(a):
-	return hasattr(a, 'is_cuda') and a.is_cuda
 
 
 class _Marks:
@@ -390,7 +384,7 @@ class Single4Plan:
 		eng._s4_inverse = eng._s4_path = None
 		out = self._public()
 		path, inv = getattr(eng, '_s4_path', None), getattr(eng, '_s4_inverse', None)
-		ok = (path == 'sparse closed form' and inv is not None and _is_dev(self.dx) and _is_dev(self.dy) and np.ndim(self.dimreduce) == 0 and self.lowmem
+		ok = (path == 'sparse closed form' and inv is not None and _engine.is_dev(self.dx) and _engine.is_dev(self.dy) and np.ndim(self.dimreduce) == 0 and self.lowmem
 			  and _opts.debug('s4_plan', 'lean') != 'public')
 		if ok:
 			from .association import inv_rank
@@ -417,7 +411,7 @@ class Single4Plan:
 		ny, nc = d_y.shape[0], self.dc.shape[0]
 		flags = self.flags  # [0] non-finite, [1] R^2 out of range (the sweep), [2] rows near the span of the covariates (k_design_stats, k_de_sparse), [5] diagonal of N~
 		rx = de_sparse.design_stats(eng, lists, d_c, d_dci, dcr, nx, nc, flags)
-		nxp = _engine._round_up(nx, _lib.ROW_TILE)
+		nxp = _engine.round_up(nx, _lib.ROW_TILE)
 		# The design side (M~ from the design's own entries, its Newton-Schulz inverse: two dozen small launches, the 1024^3 products on 64 of the 256 CUs)
 		# and the gene side (the one pass over the expression matrix) need nothing of each other until B = G N~: a fork and a join of the captured graph --
 		# the design side runs on a second stream beside the gather kernel instead of in front of it.
@@ -438,7 +432,7 @@ class Single4Plan:
 		tdt = d_y.dtype if d_y.dtype in (torch.float32, torch.float64) else torch.float64
 		p, stat, vary = (torch.empty((nx, ny), dtype=tdt, device=eng.device) for _ in range(3))
 		work = torch.empty((ny, ), dtype=torch.float64, device=eng.device)
-		code = _lib.NRM_F64 if tdt == torch.float64 else _lib.NRM_F32
+		code = _engine.dtype_code(tdt)
 		with _engine._Span(eng, 'sweep'):
 			_lib.check(eng.lib.nrm_single4_sweep(bt_d.data_ptr(), g_d.data_ptr(), bt_d.stride(0), ssy.data_ptr(), dxx.data_ptr(), nx, ny, nx, n, float(n - nx - dcr - int(self.dimreduce)),
 												 1 if self.return_dot else 0, p.data_ptr(), stat.data_ptr(), vary.data_ptr(), code, ny, work.data_ptr(), flags.data_ptr(), eng._stream()))
@@ -499,15 +493,15 @@ class Single4Plan:
 		if device_out:
 			return out
 		eng = self.eng
-		dl = lambda t: eng.download(t) if _is_dev(t) else t
-		vx = varx.cpu().numpy().astype(od) if _is_dev(varx) else varx
+		dl = lambda t: eng.download(t) if _engine.is_dev(t) else t
+		vx = varx.cpu().numpy().astype(od) if _engine.is_dev(varx) else varx
 		return (dl(p), dl(stat), alpha, vx, dl(vary))
 
 
 def _check_arguments(dx, dy, dc, dimreduce):
 	"""The argument checks of association_tests(single=4) (association.py:449-470,761-930), shared by the device path and the torch-free one."""
-	dx, dc = dx if _is_dev(dx) else np.asarray(dx), np.asarray(dc)
-	if dy is not None and not _is_dev(dy):
+	dx, dc = dx if _engine.is_dev(dx) else np.asarray(dx), np.asarray(dc)
+	if dy is not None and not _engine.is_dev(dy):
 		dy = np.asarray(dy)
 	nx, n = dx.shape
 	nc = dc.shape[0]
@@ -581,21 +575,21 @@ def association_tests_single4(dx, dy, dc, lowmem=True, return_dot=True, return_s
 	with eng.lock:  # one call at a time per device (engine scratch, streams and guard state are shared)
 		torch = eng.torch
 		if dy is None:
-			if _is_dev(dx):
+			if _engine.is_dev(dx):
 				dx = dx.cpu().numpy()
 			out_dtype = dx.dtype if dx.dtype in (np.float32, np.float64) else np.dtype(np.float64)
 			return _single4_samexy(dx, dc, lowmem, return_dot, dimreduce, ik, eng, out_dtype)
-		if _is_dev(dy):
+		if _engine.is_dev(dy):
 			out_dtype = np.dtype(np.float32 if dy.dtype == torch.float32 else np.float64)
 		else:
 			out_dtype = dy.dtype if dy.dtype in (np.float32, np.float64) else np.dtype(np.float64)
 		m = nx + nc
 		mark = _Marks(eng)
 		from .engine import Residualized
-		mp, kp = _engine._round_up(m, _lib.ROW_TILE), _engine._round_up(n, _lib.K_TILE)
+		mp, kp = _engine.round_up(m, _lib.ROW_TILE), _engine.round_up(n, _lib.K_TILE)
 		eng._s4_path = None
 		with torch.cuda.device(eng.device):
-			d_x = dx if _is_dev(dx) else eng.upload(_engine.as_input(dx))
+			d_x = dx if _engine.is_dev(dx) else eng.upload(_engine.as_input(dx))
 		may_close = mpc == 0 and method in ('auto', 'scipy')
 		# The closed form applies when A A^T (A = [X; C], association.py:935) passes the reference's own rank threshold -- every singular
 		# value >= tol x the largest (association.py:77).  It runs first; the norms of what it computes anyway (M~, its inverse, the
@@ -642,7 +636,7 @@ def association_tests_single4(dx, dy, dc, lowmem=True, return_dot=True, return_s
 			return res
 		del res
 		eng._s4_path = None  # (no closed form: nothing for a Single4Plan to replay)
-		if _is_dev(dy):
+		if _engine.is_dev(dy):
 			dy = dy.cpu().numpy()
 		logging.info('single=4: no closed form (rank-deficient A A^T or truncated inverse); following the per-grouping algorithm on the host.')
 		ry = eng.residualize(_engine.as_input(dy), None, None, 0)  # fp64 padded copy of Y and sum y^2 (association.py:968)
@@ -749,7 +743,7 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 	ns = 0 if force_f64 else eng.gram_slices(n)
 	with torch.cuda.device(eng.device):
 		d_c, d_dci = eng.covariates(dc64, dci) if nc else (None, None)
-		d_y = dy if _is_dev(dy) else eng.upload(_engine.as_input(dy))
+		d_y = dy if _engine.is_dev(dy) else eng.upload(_engine.as_input(dy))
 		if not (eng.k1_quantises(d_x, d_c) and eng.k1_quantises(d_y, d_c)):
 			ns = 0  # (rows K1 cannot quantise itself -- not 16-byte aligned: fp64 all the way)
 		# A design matrix with few entries (gRNA incidence): Y~ X~^T = Y X^T - (Y C^T) b_x^T needs of every expression row only its values
@@ -769,7 +763,7 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 			from . import de_sparse
 			sp_flags = eng.new_flags()  # [2]: rows -- design rows here, expression rows below -- too close to the span of the covariates for these differences
 			rx = de_sparse.design_stats(eng, lists, d_c, d_dci, dcr, nx, nc, sp_flags)
-			nxp = _engine._round_up(nx, _lib.ROW_TILE)
+			nxp = _engine.round_up(nx, _lib.ROW_TILE)
 			mark('design rows')
 			mt_d, _, _, _ = de_sparse.products(eng, lists, d_x, d_c, d_dci, dcr, rx.coef, nx, nx, n, nc, False, False, sp_flags)  # (rows i, columns j; its upper triangle is used)
 		else:
@@ -809,7 +803,7 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 				eng._s4_path = None
 				logging.info('single=4: %d rows (design or expression) too close to the span of the covariates for the sparse-design products; fp64 Gram kernel', int(sp_flags[2]))
 				return _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, out_dtype, force_f64=True, device_out=device_out)
-			ry = Residualized(ny, n, None, ssy, coefy, shape=(g_d.shape[0], _engine._round_up(n, _lib.K_TILE)))
+			ry = Residualized(ny, n, None, ssy, coefy, shape=(g_d.shape[0], _engine.round_up(n, _lib.K_TILE)))
 			mark('Y~ X~^T (sparse design: expression rows read once)')
 			eng._s4_path = 'sparse closed form' if _opts.debug('s4_sparse_m', '1') != '0' and inv is not None else None  # (Single4Plan)
 		else:
@@ -830,7 +824,7 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 		work = torch.empty((ny, ), dtype=torch.float64, device=eng.device)
 		flags = eng.new_flags()
 		d_dxx = eng.upload(dxx)
-		code = _lib.NRM_F64 if out_dtype == np.float64 else _lib.NRM_F32
+		code = _engine.dtype_code(out_dtype)
 		mark('result buffers')
 		guard = ()
 		if ns:
@@ -894,7 +888,7 @@ def _closed_form(eng, d_x, dy, dc64, dci, dcr, dimreduce, lowmem, return_dot, ou
 			# alpha_y = b_y - B_y b_x (nc values per gene, the same for every grouping: association.py:551-553 in the closed form)
 			b_cov = ry.coef[:ny].cpu().numpy()
 			if nx and nc:
-				cxt = eng.zeros((_engine._round_up(nc, _lib.ROW_TILE), nxp), torch.float64)
+				cxt = eng.zeros((_engine.round_up(nc, _lib.ROW_TILE), nxp), torch.float64)
 				cxt[:nc, :nx] = rx.coef[:nx].T
 				bb = eng.gram(Residualized(ny, nxp, bt_d, None, None), Residualized(nc, nxp, cxt, None, None), False)
 				b_cov = b_cov - bb[:ny, :nc].cpu().numpy()

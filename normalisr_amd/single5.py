@@ -49,7 +49,7 @@ def association_tests_single5(dx, dy, dc, mask, bsx=0, bsy=0, lowmem=True, retur
 	eng = _engine.get_engine()
 	with eng.lock:
 		torch = eng.torch
-		mp, kp = _engine._round_up(m, _lib.ROW_TILE), _engine._round_up(n, _lib.K_TILE)
+		mp, kp = _engine.round_up(m, _lib.ROW_TILE), _engine.round_up(n, _lib.K_TILE)
 		with torch.cuda.device(eng.device):
 			a_dev = eng.zeros((mp, kp), torch.float64)
 			eng.copy_rows(a_dev, eng.upload(_engine.as_input(dx)).to(torch.float64) if dx.dtype != np.float64 else eng.upload(_engine.as_input(dx)))

@@ -9,7 +9,7 @@ mkdir -p tools/exp/obj tools/exp/var
 stem=$(basename $SRC .hip)
 for f in normalisr_amd/csrc/*.hip; do
 	o=tools/exp/obj/$(basename $f .hip).o
-	if [ "$(basename $f .hip)" != "$stem" ] && { [ ! -f $o ] || [ $f -nt $o ] || [ normalisr_amd/csrc/nrm_common.h -nt $o ] || [ normalisr_amd/csrc/nrm_gram_sched.h -nt $o ] || [ include/normalisr_hip.h -nt $o ]; }; then
+	if [ "$(basename $f .hip)" != "$stem" ] && { [ ! -f $o ] || [ $f -nt $o ] || [ normalisr_amd/csrc/nrm_common.h -nt $o ] || [ normalisr_amd/csrc/nrm_device.h -nt $o ] || [ normalisr_amd/csrc/nrm_gram_sched.h -nt $o ] || [ include/normalisr_hip.h -nt $o ]; }; then
 		/opt/rocm/bin/hipcc $FLAGS -c $f -o $o &
 	fi
 done

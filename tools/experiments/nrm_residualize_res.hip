@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(256, 2) k_residualize_res(const T* __restrict_
 #pragma unroll
 			for (int q = 0; q < CB; q++) {
 				const int qq = c0 + q < nc ? c0 + q : nc - 1;
-				Vec4Load<double>::ld(c + (int64_t)qq * ldc + k, cv[q]);
+				nrm_ld4d<double, true>(c + (int64_t)qq * ldc + k, cv[q]);
 			}
 		};
 		// fold `count` (<= 256) consecutive slab values of every member, in segment order: thread i < count gets element i.  All threads
