@@ -319,7 +319,7 @@ extern "C" int nrm_last_guard(int64_t* hits, double* worst) {
 
 // NRM_DEBUG="key=value,key=value" read the way normalisr_amd/_opts.py reads it: split on ',', key and value trimmed, the key compared without case --
 // so that a switch means the same to the package's engine and to the library's own entries.  true: `key` is there with exactly `value`.
-static bool nrm_debug_is(const char* key, const char* value) {
+bool nrm_debug_is(const char* key, const char* value) {
 	const char* d = getenv("NRM_DEBUG");
 	if (!d) return false;
 	const size_t kl = strlen(key), vl = strlen(value);

@@ -6,6 +6,7 @@
 #include "../../include/normalisr_hip.h"
 
 void nrm_set_error(const char* fmt, ...);
+bool nrm_debug_is(const char* key, const char* value);  // NRM_DEBUG="key=value,..." holds `key` with exactly `value` (csrc/nrm_api.hip)
 
 #define NRM_HIP(call)                                                                      \
 	do {                                                                                   \

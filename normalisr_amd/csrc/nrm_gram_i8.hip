@@ -165,7 +165,7 @@ template <int NS>
 __device__ __forceinline__ void gram_piece_i8(const char* __restrict__ QA, const char* __restrict__ QB, int64_t plane_a, int64_t plane_b,
 											  int64_t nks, const int* __restrict__ ea, const int* __restrict__ eb, double* __restrict__ C,
 											  int64_t ldc, int ti, int tj, int k0, int k1, double* __restrict__ slab, int m_rows, int n_rows,
-											  int symmetric, int accumulate, BBlocks bb, const char* lds, unsigned lds0) {
+											  int symmetric, int accumulate, int edge_tj, BBlocks bb, const char* lds, unsigned lds0) {
 	constexpr int STAGE = 8 * NS * 1024;
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -178,7 +178,15 @@ __device__ __forceinline__ void gram_piece_i8(const char* __restrict__ QA, const
 		qb_t = QB + wb * bb.stride + ((int64_t)(within / 32) * nks) * 1024;
 		eb_t = eb + wb * bb.rows + within;
 	}
-	const char* src0 = (wid < 4 ? QA + (((int64_t)ti * 4 + wid) * nks) * 1024 : qb_t + ((int64_t)(wid - 4) * nks) * 1024) + lane * 16;
+	// HOST tile (folded launches, gram_plan_fold: edge_tj = GramSched::fold = ntn - 1, else 0): diagonal tile (ti, ti) also computes edge tile (ti, edge_tj), the ragged last
+	// tile column's at most 32 valid columns.  In a diagonal tile the B half of a stage is a second copy of the A half, and waves 4 and 5 (rows 64-127 x
+	// columns 0-63: below the diagonal) only feed the ring while their SIMD partners 0 and 1 compute alone.  So wave 4 fetches 32-row block 0 of tile
+	// column edge_tj into its slot instead of the copy of A block 0 (wave 0 reads that from the A half), and waves 4 and 5 compute rows 0-63 and 64-127 of
+	// the tile row against it: one edge tile's 128 x 32.  Same slots, DMAs per stage, vmcnt accounting and k loop copies; only this prologue knows.
+	const bool host = symmetric && ti == tj && ti < edge_tj;
+	const bool hw = host && wm == 1 && wn < 2;  // waves 4 and 5 of a host tile
+	const char* src0 = (wid < 4 ? QA + (((int64_t)ti * 4 + wid) * nks) * 1024
+								: (host && wid == 4) ? QB + ((int64_t)edge_tj * 4 * nks) * 1024 : qb_t + ((int64_t)(wid - 4) * nks) * 1024) + lane * 16;
 	const int64_t plane = wid < 4 ? plane_a : plane_b;
 	const unsigned dst0 = lds0 + wid * NS * 1024;
 	auto issue_one = [&](int buf, int ks, int s) {
@@ -214,11 +222,12 @@ __device__ __forceinline__ void gram_piece_i8(const char* __restrict__ QA, const
 	// edge treatment is the 4992-gene figure; a launch of its own for the edge (transposed, through this kernel) costs 0.136 ms for the 0.09-0.10 it saves
 	// (tools/k2_edge_exp.py, profiles/r06_k2_edge_split_launch.txt).
 	const bool edge = QI_EDGE && !diag && tj * GN + 32 >= n_rows;
-	const int a_blk = edge ? (wid & 3) : wm * 2, b_blk = edge ? 0 : wn;
+	const int a_blk = edge ? (wid & 3) : hw ? wn * 2 : wm * 2, b_blk = edge ? 0 : wn;
+	const int b_slot = hw ? 4 : (host && wid == 0) ? 0 : 4 + b_blk;  // host tile: the edge block sits in slot 4, wave 0 takes A block 0 for its B
 	const int aoff = a_blk * NS * 1024 + pos;          // + i * NS * 1024 + s * 1024
-	const int boff = (4 + b_blk) * NS * 1024 + pos;    // + s * 1024
+	const int boff = b_slot * NS * 1024 + pos;         // + s * 1024
 	// output addressing of this wave's two 32 x 32 tiles: lane holds column lane & 31, rows (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
-	const int row_w = ti * GM + a_blk * 32, col_w = tj * GN + b_blk * 32;
+	const int row_w = ti * GM + a_blk * 32, col_w = hw ? edge_tj * GN : tj * GN + b_blk * 32;
 	// 32 x 32 sub-tiles that are pure padding, or below the diagonal of a symmetric problem, are neither stored nor -- when both of
 	// a wave's are -- computed (5000 genes: the last tile row and column hold 8 valid rows of 128); nobody reads them (K3 sweeps
 	// valid rows and, symmetric, the upper triangle), also not through the slabs of split tiles
@@ -232,20 +241,24 @@ __device__ __forceinline__ void gram_piece_i8(const char* __restrict__ QA, const
 	double* cbase;
 	int64_t pitch;
 	if (slab) {
-		cbase = slab + (a_blk * 32) * GN + b_blk * 32;
+		// (the edge sub-tile of a host tile: where waves 4 and 5 sit in the slab, rows 64-127 x columns 0-63, which nobody else uses; k_gram_fixup routes it)
+		cbase = slab + ((hw ? wm * 2 : a_blk) * 32) * GN + b_blk * 32;
 		pitch = GN;
 	} else {
 		cbase = C + (int64_t)row_w * ldc + col_w;
 		pitch = ldc;
 	}
-	const int eb_l = eb_t[b_blk * 32 + (lane & 31)];
+	// the lane's own part of the output address and of the row exponents' (column lane & 31, rows + 4 (lane >> 5)), once per piece
+	cbase += (int64_t)(4 * (lane >> 5)) * pitch + (lane & 31);
+	const int* ea_l = ea + row_w + 4 * (lane >> 5);
+	const int eb_l = hw ? eb[edge_tj * GN + (lane & 31)] : eb_t[b_blk * 32 + (lane & 31)];
 	auto flush = [&](bool first) {
 #pragma unroll
 		for (int i = 0; i < 2; i++) {
 			if (!want[i]) continue;
 #pragma unroll
 			for (int q = 0; q < 16; q++) {
-				const int rr = i * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+				const int rr = i * 32 + (q & 3) + 8 * (q >> 2);
 				// sum_w acc_w 256^w as two exact 64-bit integers (weights 0..2 and 3..NS-1: each below 2^49), so that the one
 				// fma that joins them is the only rounding: the chunk's value is the correctly rounded exact integer
 				long long lo = 0, hi = 0;
@@ -257,8 +270,8 @@ __device__ __forceinline__ void gram_piece_i8(const char* __restrict__ QA, const
 						hi += (long long)acc[w][i][q] << (8 * (w - 3));
 				}
 				double v = fma((double)hi, 16777216.0, (double)lo);
-				v = ldexp(v, ea[row_w + rr] + eb_l + 8 * (NS - 1));
-				double* o = cbase + (int64_t)rr * pitch + (lane & 31);
+				v = ldexp(v, ea_l[rr] + eb_l + 8 * (NS - 1));
+				double* o = cbase + (int64_t)rr * pitch;
 				*o = (first && !(accumulate && !slab)) ? v : *o + v;
 			}
 		}
@@ -350,8 +363,9 @@ __global__ void __launch_bounds__(512) k_gram_i8(const char* __restrict__ QA, co
 	const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr_t)lds);
 	gram_for_each_piece(s, [&](int t, int k0, int k1, double* slab) {
 		int ti, tj;
-		gram_tile_coords(s.tile0 + t, symmetric, s.ntm, s.ntn, ti, tj);
-		gram_piece_i8<NS>(QA, QB, plane_a, plane_b, nks, ea, eb, C, ldc, ti, tj, k0, k1, slab, s.m_rows, s.n_rows, symmetric, s.accumulate, bb, lds, lds0);
+		gram_sched_coords(s, t, symmetric, ti, tj);
+		gram_piece_i8<NS>(QA, QB, plane_a, plane_b, nks, ea, eb, C, ldc, ti, tj, k0, k1, slab, s.m_rows, s.n_rows, symmetric, s.accumulate, s.fold,
+						  bb, lds, lds0);
 	});
 }
 
@@ -384,7 +398,7 @@ extern "C" int nrm_quantize_rows(const double* d_x, int64_t rows_pad, int64_t k_
 
 static int gram_i8_impl(const void* d_qa, const int32_t* d_ea, int64_t plane_a_bytes, const void* d_qb, const int32_t* d_eb,
 						int64_t plane_b_bytes, int64_t m_pad, int64_t n_pad, int64_t k_pad, int nslices, double* d_dot, int64_t ldd,
-						int symmetric, int64_t m_rows, int64_t n_rows, int64_t row0, int64_t row1, int accumulate, BBlocks bb, void* d_work, void* stream) {
+						int symmetric, int64_t m_rows, int64_t n_rows, int64_t row0, int64_t row1, int accumulate, BBlocks bb, bool may_fold, void* d_work, void* stream) {
 	NRM_REQUIRE(nslices == 5 || nslices == 6, "nrm_gram_i8: 5 or 6 slices");
 	NRM_REQUIRE(m_pad >= 0 && n_pad >= 0 && k_pad > 0 && m_pad % GM == 0 && n_pad % GN == 0, "nrm_gram_i8: sizes must be padded to %d", GM);
 	NRM_REQUIRE(ldd >= n_pad && ldd % 2 == 0, "nrm_gram_i8: pitch too small");
@@ -406,7 +420,14 @@ static int gram_i8_impl(const void* d_qa, const int32_t* d_ea, int64_t plane_a_b
 	NRM_REQUIRE(plane_a >= (m_pad / 32) * nks * 1024 && plane_b >= ((bb.rows ? bb.rows : n_pad) / 32) * nks * 1024,
 				"nrm_gram_i8: plane pitch smaller than the operand");
 	GramSched s;
-	NRM_TRY(gram_plan(s, m_pad, n_pad, nks, symmetric, m_rows, n_rows, row0, row1, g_num_cu_q, (double*)d_work));  // one workgroup per CU
+	// one workgroup per CU; a whole symmetric matrix with dense B folds a last tile column of at most 32 valid columns into its diagonal tiles
+	// (NRM_DEBUG="gram_fold=0", read at every call: the last tile column keeps its own tiles -- the schedule before the fold, for A/B timing and the tests)
+	// A host tile takes one B operand from the A half of its stage: B must BE A (same planes, exponents and pitch), not only a matrix with a symmetric product.
+	// may_fold: nrm_gram_i8_band only; cell chunks, also the first, non-accumulating one, keep one schedule for all chunks.
+	if (may_fold && symmetric && !accumulate && bb.rows == 0 && d_qa == d_qb && d_ea == d_eb && plane_a == plane_b && !nrm_debug_is("gram_fold", "0"))
+		NRM_TRY(gram_plan_fold(s, m_pad, n_pad, nks, symmetric, m_rows, n_rows, row0, row1, g_num_cu_q, (double*)d_work));
+	else
+		NRM_TRY(gram_plan(s, m_pad, n_pad, nks, symmetric, m_rows, n_rows, row0, row1, g_num_cu_q, (double*)d_work));
 	s.accumulate = accumulate ? 1 : 0;
 	if (nslices == 5)
 		hipLaunchKernelGGL(k_gram_i8<5>, dim3((unsigned)s.nwg), dim3(512), 0, (hipStream_t)stream, (const char*)d_qa, (const char*)d_qb, plane_a,
@@ -423,7 +444,7 @@ extern "C" int nrm_gram_i8_band(const void* d_qa, const int32_t* d_ea, int64_t p
 								int64_t plane_b_bytes, int64_t m_pad, int64_t n_pad, int64_t k_pad, int nslices, double* d_dot, int64_t ldd,
 								int symmetric, int64_t m_rows, int64_t n_rows, int64_t row0, int64_t row1, void* d_work, void* stream) {
 	return gram_i8_impl(d_qa, d_ea, plane_a_bytes, d_qb, d_eb, plane_b_bytes, m_pad, n_pad, k_pad, nslices, d_dot, ldd, symmetric, m_rows, n_rows, row0,
-						row1, 0, BBlocks{0, 0, 1, 0}, d_work, stream);
+						row1, 0, BBlocks{0, 0, 1, 0}, true, d_work, stream);
 }
 
 // One cell chunk of a contraction whose operands arrive in pieces along the cells (sharded coex: the digit planes of the other
@@ -443,5 +464,5 @@ extern "C" int nrm_gram_i8_chunk(const void* d_qa, const int32_t* d_ea, int64_t 
 		bb = BBlocks{(int)b_block_rows, b_first, b_count, b_block_stride_bytes};
 	}
 	return gram_i8_impl(d_qa, d_ea, plane_a_bytes, d_qb, d_eb, plane_b_bytes, m_pad, n_pad, k_pad, nslices, d_dot, ldd, symmetric, m_rows, n_rows, 0,
-						m_pad, accumulate, bb, d_work, stream);
+						m_pad, accumulate, bb, false, d_work, stream);
 }

@@ -26,13 +26,13 @@ __global__ void __launch_bounds__(256) k_gram_fixup(double* __restrict__ C, int6
 	int sk_first_local = 0;
 	const double* base;
 	if (b < s.tiles_al) {
-		gram_tile_coords(s.tile0 + s.tiles_dp + b, symmetric, s.ntm, s.ntn, ti, tj);
+		gram_sched_coords(s, s.tiles_dp + b, symmetric, ti, tj);
 		base = s.work + (int64_t)b * s.parts * (GM * GN);
 		first = 0;
 		count = s.parts;
 	} else {
 		const int ts = b - s.tiles_al;
-		gram_tile_coords(s.tile0 + s.tiles_dp + s.tiles_al + ts, symmetric, s.ntm, s.ntn, ti, tj);
+		gram_sched_coords(s, s.tiles_dp + s.tiles_al + ts, symmetric, ti, tj);
 		const int64_t u0 = (int64_t)ts * s.nkt, u1 = u0 + s.nkt;
 		first = (int)(u0 / s.units_per_wg);
 		int last = (int)((u1 - 1) / s.units_per_wg);
@@ -44,6 +44,7 @@ __global__ void __launch_bounds__(256) k_gram_fixup(double* __restrict__ C, int6
 	}
 	// blockIdx.y selects GFIX_ROWS of the tile's 128 rows: enough workgroups to keep loads in flight (a thread's additions are a chain)
 	double* ct = C + (int64_t)ti * GM * ldc + (int64_t)tj * GN;
+	const bool host = gram_is_host(s, ti, tj);
 	const int e0 = blockIdx.y * (GFIX_ROWS * GN);
 	for (int e = e0 + threadIdx.x * 2; e < e0 + GFIX_ROWS * GN; e += 512) {
 		d2_t acc = (d2_t){0.0, 0.0};
@@ -57,7 +58,11 @@ __global__ void __launch_bounds__(256) k_gram_fixup(double* __restrict__ C, int6
 			src += (int64_t)(2 - sk_first_local) * (GM * GN);
 			for (int q = 1; q < count; q++, src += 2 * (GM * GN)) acc += *reinterpret_cast<const d2_t*>(src);
 		}
-		d2_t* o = reinterpret_cast<d2_t*>(ct + (int64_t)(e / GN) * ldc + (e % GN));
+		const int r = e / GN, c = e % GN;
+		d2_t* o = reinterpret_cast<d2_t*>(ct + (int64_t)r * ldc + c);
+		// a host tile's slab carries the edge sub-tile (ti, ntn - 1) where its own entries lie below the diagonal: rows 64-127 x columns 0-31 are the edge
+		// tile's rows 0-63, columns 32-63 its rows 64-127 (gram_piece_i8); they go there and never into the diagonal tile
+		if (host && r >= 64 && c < 64) o = reinterpret_cast<d2_t*>(C + ((int64_t)ti * GM + (r - 64) + (c >> 5) * 64) * ldc + (int64_t)s.fold * GN + (c & 31));
 		*o = s.accumulate ? *o + acc : acc;
 	}
 }

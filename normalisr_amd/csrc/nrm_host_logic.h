@@ -85,10 +85,27 @@ struct GramSched {
 	int nwg;        // persistent workgroups (multiple of 8)
 	int tile0;      // first tile of this launch in the gram_tile_coords order (band launches)
 	int accumulate; // add to C instead of overwriting it (cell-chunked launches of the sharded path)
+	int fold;       // ntn - 1: the ragged last tile column, this one, rides in the diagonal tiles (gram_plan_fold; integer engine only); 0 for everyone else
 	double* work;   // slabs of partial pieces: [tiles_al*parts] then [2 per workgroup]
 };
 
-
+// Tile t of a launch.  fold == 0: the gram_tile_coords order.  fold == ntn - 1 > 0 (symmetric, whole matrix, at most 32 valid columns in the last
+// tile column): the upper triangle of the leading (ntn - 1) x (ntn - 1) grid in that order, then the corner tile (ntn - 1, ntn - 1).  The
+// off-diagonal tiles (i, ntn - 1) are not listed: diagonal tile (i, i), i < ntn - 1, is the HOST of edge tile (i, ntn - 1) -- its two waves
+// below the diagonal compute the edge tile's 128 rows x one 32-column block (gram_piece_i8).
+NRM_HD inline __attribute__((always_inline)) void gram_sched_coords(const GramSched& s, int t, int symmetric, int& ti, int& tj) {
+	if (!s.fold) {
+		gram_tile_coords(s.tile0 + t, symmetric, s.ntm, s.ntn, ti, tj);
+		return;
+	}
+	const int lead = s.fold;
+	if (t < lead * (lead + 1) / 2)
+		gram_tile_coords(t, 1, lead, lead, ti, tj);
+	else
+		ti = tj = lead;
+}
+// true: tile (ti, tj) of a folded launch also carries edge tile (ti, ntn - 1)
+NRM_HD inline bool gram_is_host(const GramSched& s, int ti, int tj) { return ti == tj && ti < s.fold; }
 
 // The persistent loop of a Gram kernel: calls piece(tile, k0, k1, slab) for every piece of workgroup `block` -- whole tiles
 // first (one per workgroup per wave, K-lockstep), then its K-aligned part, then its share of the stream-K tail.
@@ -153,28 +170,12 @@ static inline int64_t gram_tiles_before(int64_t bi, int symmetric, int64_t ntm, 
 	return t;
 }
 
-
-// Host side: the schedule of one launch over output rows [row0, row1) with nkt K-units per tile on nwg persistent workgroups.
-static inline int gram_plan(GramSched& s, int64_t m_pad, int64_t n_pad, int64_t nkt, int symmetric, int64_t m_rows, int64_t n_rows, int64_t row0,
-							int64_t row1, int nwg, double* work) {
-	const int64_t ntm = m_pad / GM, ntn = n_pad / GN;
-	NRM_REQUIRE((symmetric ? ntn * (ntn + 1) / 2 : ntm * ntn) < (1LL << 30), "nrm_gram: problem too large for one launch");
-	const int64_t tile0 = gram_tiles_before(row0 / (GSB * GM), symmetric, ntm, ntn);
-	const int64_t tiles = gram_tiles_before((row1 + GSB * GM - 1) / (GSB * GM), symmetric, ntm, ntn) - tile0;
-	NRM_REQUIRE(tiles < (1LL << 30) && nkt < (1LL << 30), "nrm_gram: problem too large for one launch");
-	s.tile0 = (int)tile0;
-	s.accumulate = 0;
-	s.m_rows = (int)((m_rows > 0 && m_rows < m_pad) ? m_rows : m_pad);
-	s.n_rows = (int)((n_rows > 0 && n_rows < n_pad) ? n_rows : n_pad);
-	s.ntm = (int)ntm;
-	s.ntn = (int)ntn;
-	s.nkt = (int)nkt;
-	s.nwg = nwg - nwg % 8;
-	// three phases, every workgroup does the same amount of work in each:
-	//  1. whole tiles, one per workgroup per wave (K-lockstep, plain stores);
-	//  2. of the remaining rem < nwg tiles, nwg/parts tiles are cut into `parts` equal K ranges (still K-aligned within a
-	//     part, so workgroups of an XCD keep sharing slabs through L2);
-	//  3. the rest is cut into equal unit ranges (stream-K; different K offsets, no sharing -- kept small).
+// The three phases of `tiles` tiles on s.nwg workgroups (s.nkt, s.nwg set), every workgroup does the same amount of work in each:
+//  1. whole tiles, one per workgroup per wave (K-lockstep, plain stores);
+//  2. of the remaining rem < nwg tiles, nwg/parts tiles are cut into `parts` equal K ranges (still K-aligned within a
+//     part, so workgroups of an XCD keep sharing slabs through L2);
+//  3. the rest is cut into equal unit ranges (stream-K; different K offsets, no sharing -- kept small).
+static inline void gram_split_phases(GramSched& s, int64_t tiles) {
 	const int64_t waves = tiles / s.nwg, rem = tiles - waves * s.nwg;
 	s.tiles_dp = (int)(waves * s.nwg);
 	s.parts = 1;
@@ -188,7 +189,42 @@ static inline int gram_plan(GramSched& s, int64_t m_pad, int64_t n_pad, int64_t 
 	const int64_t sk = rem - s.tiles_al;
 	s.tiles_sk = (int)sk;
 	s.units_per_wg = (int)((sk * s.nkt + s.nwg - 1) / s.nwg);
+}
+
+// Host side: the schedule of one launch over output rows [row0, row1) with nkt K-units per tile on nwg persistent workgroups.
+static inline int gram_plan(GramSched& s, int64_t m_pad, int64_t n_pad, int64_t nkt, int symmetric, int64_t m_rows, int64_t n_rows, int64_t row0,
+							int64_t row1, int nwg, double* work) {
+	const int64_t ntm = m_pad / GM, ntn = n_pad / GN;
+	NRM_REQUIRE((symmetric ? ntn * (ntn + 1) / 2 : ntm * ntn) < (1LL << 30), "nrm_gram: problem too large for one launch");
+	const int64_t tile0 = gram_tiles_before(row0 / (GSB * GM), symmetric, ntm, ntn);
+	const int64_t tiles = gram_tiles_before((row1 + GSB * GM - 1) / (GSB * GM), symmetric, ntm, ntn) - tile0;
+	NRM_REQUIRE(tiles < (1LL << 30) && nkt < (1LL << 30), "nrm_gram: problem too large for one launch");
+	s.tile0 = (int)tile0;
+	s.accumulate = 0;
+	s.fold = 0;
+	s.m_rows = (int)((m_rows > 0 && m_rows < m_pad) ? m_rows : m_pad);
+	s.n_rows = (int)((n_rows > 0 && n_rows < n_pad) ? n_rows : n_pad);
+	s.ntm = (int)ntm;
+	s.ntn = (int)ntn;
+	s.nkt = (int)nkt;
+	s.nwg = nwg - nwg % 8;
+	gram_split_phases(s, tiles);
 	s.work = work;
+	return NRM_OK;
+}
+
+// The same with the ragged last tile column folded into the diagonal tiles where that applies: a symmetric launch over the whole matrix
+// with at least two tile columns whose last one holds 1 to 32 valid columns (5000 genes = 39 x 128 + 8: 781 tiles instead of 820).  The
+// caller vouches for the rest (dense B, not accumulating, a kernel that knows host tiles).  Every other launch gets gram_plan's schedule.
+static inline int gram_plan_fold(GramSched& s, int64_t m_pad, int64_t n_pad, int64_t nkt, int symmetric, int64_t m_rows, int64_t n_rows, int64_t row0,
+								 int64_t row1, int nwg, double* work) {
+	const int rc = gram_plan(s, m_pad, n_pad, nkt, symmetric, m_rows, n_rows, row0, row1, nwg, work);
+	if (rc != NRM_OK) return rc;
+	const int valid = s.n_rows - (s.ntn - 1) * GN;  // valid columns of the last tile column
+	if (symmetric && row0 == 0 && row1 == m_pad && s.ntn >= 2 && s.ntm == s.ntn && s.m_rows == s.n_rows && valid >= 1 && valid <= 32) {
+		s.fold = s.ntn - 1;
+		gram_split_phases(s, (int64_t)(s.ntn - 1) * s.ntn / 2 + 1);
+	}
 	return NRM_OK;
 }
 
