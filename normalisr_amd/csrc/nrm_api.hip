@@ -264,38 +264,14 @@ extern "C" int nrm_copy_rows(void* d_dst, int64_t dst_pitch, const void* d_src, 
 static std::mutex g_host_entry;
 NrmDevPool& nrm_host_pool() { return g_pool; }
 std::mutex& nrm_host_entry_mutex() { return g_host_entry; }
-namespace {
-inline int64_t round_up(int64_t v, int64_t m) { return nrm_round_up(v, m); }
-inline size_t esize(int dtype) { return nrm_esize(dtype); }
-}  // namespace
 
 namespace {
-// Page-lock of a caller-owned result array for the duration of one call; a range that cannot be locked (already
-// registered by the caller, locked-memory limit) is simply copied to at the pageable rate.
-struct HostPin {
-	void* p = nullptr;
-	void try_pin(void* q, int64_t bytes) {
-		if (q && bytes >= (1 << 20) && nrm_host_pin(q, bytes, 0) == NRM_OK) p = q;
-	}
-	~HostPin() {
-		if (p) {
-			(void)hipDeviceSynchronize();
-			(void)hipHostUnregister(p);
-		}
-	}
-};
 struct CopyStream {
 	hipStream_t s = nullptr;
 	std::vector<hipEvent_t> events;
 	~CopyStream() {
 		for (hipEvent_t e : events) (void)hipEventDestroy(e);
 		if (s) (void)hipStreamDestroy(s);
-	}
-};
-struct Joiner {
-	std::thread& t;
-	~Joiner() {
-		if (t.joinable()) t.join();
 	}
 };
 }  // namespace
@@ -404,25 +380,19 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	NRM_REQUIRE(h_p && h_stat && h_vary, "nrm_association_tests_host: null output");
 	const double dof = (double)(n - 1 - rank - dimreduce);
 	hipStream_t st = nullptr;
-	const int64_t kp = round_up(n, NRM_K_TILE), mp = round_up(nx, NRM_ROW_TILE), np_ = round_up(ny, NRM_ROW_TILE);
+	const int64_t kp = nrm_round_up(n, NRM_K_TILE), mp = nrm_round_up(nx, NRM_ROW_TILE), np_ = nrm_round_up(ny, NRM_ROW_TILE);
 
-	DevBuf cmax, dx, dy, dc, dci, rx, ry, ssx, ssy, bx, by, dot, flags, op, ostat, oalpha, orr, ot;
+	DevBuf cmax, dx, dy, dc, dci, rx, ry, ssx, ssy, bx, by, dot, flags, oalpha;
+	NrmAssocOut out;
 	// the caller's result arrays are page-locked in place by a helper thread while K1/K2 run (started after the uploads:
 	// a hipHostRegister racing a pageable H2D copy was measured to stall that copy by ~20 ms)
-	const size_t ob = (size_t)nx * ny * esize(out_dtype);
-	HostPin pin_p, pin_s, pin_r, pin_t;
+	const size_t ob = (size_t)nx * ny * nrm_esize(out_dtype);
+	NrmHostPin pin_p, pin_s, pin_r, pin_t;
 	std::thread pinner;
-	Joiner joiner{pinner};
-	// covariates as fp64
+	NrmJoiner joiner{pinner};
 	std::vector<double> c64;
+	NRM_TRY(covariates_f64(h_dc, c_dtype, nc, n, c64, dc));
 	if (nc > 0) {
-		c64.resize((size_t)nc * n);
-		if (c_dtype == NRM_F64)
-			memcpy(c64.data(), h_dc, c64.size() * 8);
-		else
-			for (size_t i = 0; i < c64.size(); i++) c64[i] = ((const float*)h_dc)[i];
-		NRM_TRY(dc.alloc(c64.size() * 8));
-		NRM_HIP(hipMemcpy(dc.p, c64.data(), c64.size() * 8, hipMemcpyHostToDevice));
 		std::vector<double> cm((size_t)nc, 0.0);  // max |C_c| per covariate row: K1's bound on the residuals it quantises
 		for (int64_t c = 0; c < nc; c++)
 			for (int64_t k = 0; k < n; k++) cm[(size_t)c] = std::max(cm[(size_t)c], std::fabs(c64[(size_t)(c * n + k)]));
@@ -436,11 +406,10 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	NRM_REQUIRE(!(want_alpha && samexy), "alpha is not provided for dy == NULL (meaningless in the reference, association.py:1066-1068)");
 	DevBuf qx, qy, ex, ey, fx, fy;
 	const double guard_tol = guard_tolerance();
-	NRM_TRY(dx.alloc((size_t)nx * n * esize(x_dtype)));
-	NRM_TRY(nrm_upload(h_dx, dx.p, (int64_t)nx * n * esize(x_dtype), 0, (void*)st));  // (from half a GB up: host threads fill page-locked blocks beside the DMA, nrm_upload.hip)
+	NRM_TRY(upload_matrix(h_dx, x_dtype, nx, n, dx, st));
 	// A design matrix with few entries (a CRISPR screen's gRNA incidence): the sparse-design kernels -- the expression rows read once, raw, the
-	// contraction replaced by gathers at the design's entries (nrm_host_entries.hip; what normalisr_amd.engine does for the Python host).
-	// Same size rule as there; NRM_DE_SPARSE=0 switches it off, =force takes it whatever the size.
+	// contraction replaced by gathers at the design's entries (nrm_host_de.hip; what normalisr_amd.engine does for the Python host), for the calls
+	// nrm_de_sparse_wanted (nrm_host_entry.h) names.
 	// de with few design rows (case-control DE, BASELINE configs[2]): the raw expression rows streamed once against [C; X~], as the Python engine does
 	// (engine.association_de_streaming); NRM_DEBUG de_path=general keeps K1 + K2
 	if (allow_sparse && !samexy && nx + nc <= 32 && !de_path_general()) {
@@ -448,26 +417,20 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 									 h_varx, h_vary, h_r, h_t, out_dtype);
 	}
 	bool dy_up = false;
-	if (allow_sparse && !samexy && nc <= nrm_de_sparse_max_covariates()) {
-		const char* mode = getenv("NRM_DE_SPARSE");
-		const bool off = mode && !strcmp(mode, "0"), force = mode && !strcmp(mode, "force");
-		if (!off && (force || (nx >= 32 && ny >= 64 && n >= 2048 && nx * n >= (1ll << 22)))) {
-			NRM_TRY(dy.alloc((size_t)ny * n * esize(y_dtype)));
-			NRM_TRY(nrm_upload(h_dy, dy.p, (int64_t)ny * n * esize(y_dtype), 0, (void*)st));
-			dy_up = true;
-			int taken = 0;
-			int64_t back = 0;
-			NRM_TRY(nrm_host_de_sparse(dx.p, x_dtype, nx, dy.p, y_dtype, ny, dc.as<double>(), c64.data(), nc, n, dci.as<double>(), rank, dof, (return_dot ? 0 : 1), h_p, h_stat,
-									   want_alpha ? h_alpha : nullptr, h_varx, h_vary, h_r, h_t, out_dtype, &taken, &back));
-			if (taken) {
-				if (back > 0 && guard_hits) *guard_hits = back;
-				return NRM_OK;
-			}
+	if (allow_sparse && !samexy && nrm_de_sparse_wanted(nx, ny, n, nc)) {
+		NRM_TRY(upload_matrix(h_dy, y_dtype, ny, n, dy, st));
+		dy_up = true;
+		int taken = 0;
+		int64_t back = 0;
+		NRM_TRY(nrm_host_de_sparse(dx.p, x_dtype, nx, dy.p, y_dtype, ny, dc.as<double>(), c64.data(), nc, n, dci.as<double>(), rank, dof, (return_dot ? 0 : 1), h_p, h_stat,
+								   want_alpha ? h_alpha : nullptr, h_varx, h_vary, h_r, h_t, out_dtype, &taken, &back));
+		if (taken) {
+			if (back > 0 && guard_hits) *guard_hits = back;
+			return NRM_OK;
 		}
 	}
 	NRM_TRY(ssx.alloc((size_t)mp * 8));
-	if (want_alpha) NRM_TRY(bx.alloc((size_t)nx * nc * 8));
-	if (want_alpha) NRM_HIP(hipMemsetAsync(bx.p, 0, (size_t)nx * nc * 8, st));
+	if (want_alpha) NRM_TRY(bx.alloc_zero((size_t)nx * nc * 8, st));
 	if (nslices) {
 		NRM_TRY(qx.alloc((size_t)nrm_quant_bytes(mp, kp, nslices)));
 		NRM_TRY(ex.alloc((size_t)mp * 4));
@@ -481,13 +444,9 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 								ssx.as<double>(), want_alpha ? bx.as<double>() : nullptr, st));
 	}
 	if (!samexy) {
-		if (!dy_up) {
-			NRM_TRY(dy.alloc((size_t)ny * n * esize(y_dtype)));
-			NRM_TRY(nrm_upload(h_dy, dy.p, (int64_t)ny * n * esize(y_dtype), 0, (void*)st));
-		}
+		if (!dy_up) NRM_TRY(upload_matrix(h_dy, y_dtype, ny, n, dy, st));
 		NRM_TRY(ssy.alloc((size_t)np_ * 8));
-		if (want_alpha) NRM_TRY(by.alloc((size_t)ny * nc * 8));
-		if (want_alpha) NRM_HIP(hipMemsetAsync(by.p, 0, (size_t)ny * nc * 8, st));
+		if (want_alpha) NRM_TRY(by.alloc_zero((size_t)ny * nc * 8, st));
 		if (nslices) {
 			NRM_TRY(qy.alloc((size_t)nrm_quant_bytes(np_, kp, nslices)));
 			NRM_TRY(ey.alloc((size_t)np_ * 4));
@@ -514,14 +473,10 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	NRM_TRY(dot.alloc((size_t)mp * np_ * 8));
 	DevBuf gwork;
 	NRM_TRY(gwork.alloc((size_t)nrm_gram_workspace_bytes()));
-	NRM_TRY(flags.alloc(16));
-	NRM_HIP(hipMemsetAsync(flags.p, 0, 16, st));
+	NRM_TRY(flags.alloc_zero(16, st));
 	const double* fxp = nslices ? fx.as<double>() : nullptr;
 	const double* fyp = nslices ? (samexy ? fxp : fy.as<double>()) : nullptr;
-	NRM_TRY(op.alloc(ob));
-	NRM_TRY(ostat.alloc(ob));
-	if (h_r) NRM_TRY(orr.alloc(ob));
-	if (h_t) NRM_TRY(ot.alloc(ob));
+	NRM_TRY(out.alloc(ob, h_r != nullptr, h_t != nullptr));
 	// coex always converts to covariance (association.py:1037-1039); de keeps gamma unless return_dot
 	const int stat_kind = (samexy || return_dot) ? 0 : 1;
 	// K2 -> K3 per band of output rows; finished bands are copied out on a second stream while later bands compute
@@ -536,38 +491,35 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 									 dot.as<double>(), np_, samexy ? 1 : 0, nx, ny, a, b == nx ? mp : b, gwork.p, st));
 		else
 			NRM_TRY(nrm_gram_f64_band(A, B, mp, np_, kp, kp, kp, dot.as<double>(), np_, samexy ? 1 : 0, nx, ny, a, b == nx ? mp : b, gwork.p, st));
-		NRM_TRY(nrm_assoc_sweep_band(dot.as<double>(), np_, sx, sy, nx, ny, n, dof, samexy ? 1 : 0, stat_kind, op.p, ostat.p,
-									 h_r ? orr.p : nullptr, h_t ? ot.p : nullptr, out_dtype, ny, flags.as<int32_t>(), a, b, nslices, fxp, fyp, guard_tol, st));
+		NRM_TRY(nrm_assoc_sweep_band(dot.as<double>(), np_, sx, sy, nx, ny, n, dof, samexy ? 1 : 0, stat_kind, out.p.p, out.stat.p,
+									 out.r.p, out.t.p, out_dtype, ny, flags.as<int32_t>(), a, b, nslices, fxp, fyp, guard_tol, st));
 		hipEvent_t ev;
 		NRM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
 		cs.events.push_back(ev);
 		NRM_HIP(hipEventRecord(ev, st));
 	}
 	if (pinner.joinable()) pinner.join();
-	const size_t row = (size_t)ny * esize(out_dtype);
+	const size_t row = (size_t)ny * nrm_esize(out_dtype);
 	for (int64_t a = 0, i = 0; a < nx; a += band, i++) {
 		const int64_t b = std::min(nx, a + band);
 		NRM_HIP(hipStreamWaitEvent(cs.s, cs.events[(size_t)i], 0));
 		const size_t off = (size_t)a * row, len = (size_t)(b - a) * row;
-		NRM_HIP(hipMemcpyAsync((char*)h_p + off, (const char*)op.p + off, len, hipMemcpyDeviceToHost, cs.s));
-		NRM_HIP(hipMemcpyAsync((char*)h_stat + off, (const char*)ostat.p + off, len, hipMemcpyDeviceToHost, cs.s));
-		if (h_r) NRM_HIP(hipMemcpyAsync((char*)h_r + off, (const char*)orr.p + off, len, hipMemcpyDeviceToHost, cs.s));
-		if (h_t) NRM_HIP(hipMemcpyAsync((char*)h_t + off, (const char*)ot.p + off, len, hipMemcpyDeviceToHost, cs.s));
+		NRM_HIP(hipMemcpyAsync((char*)h_p + off, (const char*)out.p.p + off, len, hipMemcpyDeviceToHost, cs.s));
+		NRM_HIP(hipMemcpyAsync((char*)h_stat + off, (const char*)out.stat.p + off, len, hipMemcpyDeviceToHost, cs.s));
+		if (h_r) NRM_HIP(hipMemcpyAsync((char*)h_r + off, (const char*)out.r.p + off, len, hipMemcpyDeviceToHost, cs.s));
+		if (h_t) NRM_HIP(hipMemcpyAsync((char*)h_t + off, (const char*)out.t.p + off, len, hipMemcpyDeviceToHost, cs.s));
 	}
 	if (want_alpha) {
 		// alpha comes from gamma whatever return_dot says (association.py:238-243 vs :1044-1048)
 		NRM_TRY(oalpha.alloc(ob * nc));
-		NRM_TRY(nrm_alpha(ostat.p, out_dtype, ny, stat_kind, ssx.as<double>(), n, bx.as<double>(), by.as<double>(), nx, ny, nc, oalpha.p,
+		NRM_TRY(nrm_alpha(out.stat.p, out_dtype, ny, stat_kind, ssx.as<double>(), n, bx.as<double>(), by.as<double>(), nx, ny, nc, oalpha.p,
 						  out_dtype, st));
 	}
 	NRM_HIP(hipStreamSynchronize(st));
 	NRM_HIP(hipStreamSynchronize(cs.s));
 	int32_t hf[4];
-	NRM_HIP(hipMemcpy(hf, flags.p, 16, hipMemcpyDeviceToHost));
-	if (hf[0] || hf[1]) {
-		nrm_set_error("association results failed the reference's assertions (association.py:248,252): %d tiles non-finite, %d tiles with R^2 > 1+1e-8", hf[0], hf[1]);
-		return NRM_E_NUMERIC;
-	}
+	NRM_TRY(nrm_read_flags(flags.p, st, hf));
+	NRM_TRY(nrm_assoc_assertions(hf, " tiles"));
 	if (nslices) {
 		float w;
 		memcpy(&w, &hf[3], 4);
@@ -576,21 +528,7 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 		if (hf[2] > 0 && guard_hits) return NRM_OK;  // the caller redoes the call on the fp64 kernel: nothing more to bring back from this pass
 	}
 	if (want_alpha) NRM_HIP(hipMemcpy(h_alpha, oalpha.p, ob * nc, hipMemcpyDeviceToHost));
-	// variances = ss / n with the 0 -> 1 rule (association.py:230-233), cast to the output dtype
-	std::vector<double> hs((size_t)std::max(mp, np_));
-	auto emit_var = [&](const double* d_ss, int64_t cnt, void* h_out) -> int {
-		NRM_HIP(hipMemcpy(hs.data(), d_ss, (size_t)cnt * 8, hipMemcpyDeviceToHost));
-		for (int64_t i = 0; i < cnt; i++) {
-			double v = hs[i] / (double)n;
-			if (v == 0.0) v = 1.0;
-			if (out_dtype == NRM_F64)
-				((double*)h_out)[i] = v;
-			else
-				((float*)h_out)[i] = (float)v;
-		}
-		return NRM_OK;
-	};
-	NRM_TRY(emit_var(sy, ny, h_vary));
-	if (h_varx && !samexy) NRM_TRY(emit_var(sx, nx, h_varx));
+	NRM_TRY(emit_var(sy, ny, n, h_vary, out_dtype));
+	if (h_varx && !samexy) NRM_TRY(emit_var(sx, nx, n, h_varx, out_dtype));
 	return NRM_OK;
 }

@@ -1,11 +1,16 @@
 // What the whole-problem host entries (numpy buffers in, numpy buffers out; no torch) share: the device scratch pool kept between calls, the
-// lock that serialises them per process, a scoped device buffer.  nrm_api.hip owns the pool and the lock; nrm_host_entries.hip (the sparse-design
-// path of nrm_association_tests_host, the single=1 / single=4 / binnet entries) uses them.
+// lock that serialises them per process, a scoped device buffer, the uploads, read-backs and result copies every entry makes.  nrm_api.hip owns the pool
+// and the lock and holds the dense single=0 entry; the others are in nrm_host_de.hip (sparse-design and streaming de), nrm_host_single1.hip,
+// nrm_host_single4.hip (with nrm_gram_host / nrm_pvalues_host) and nrm_host_normvar.hip (with nrm_binnet_host).  Their arithmetic is in nrm_host_math.h.
 #pragma once
+#include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <thread>
+#include <vector>
 #include "nrm_common.h"
 #include "nrm_host_logic.h"
+#include "nrm_host_math.h"
 
 struct NrmHipAlloc {
 	void* alloc(size_t bytes) {
@@ -45,6 +50,11 @@ struct DevBuf {
 		}
 		return NRM_OK;
 	}
+	int alloc_zero(size_t bytes, hipStream_t st) {
+		NRM_TRY(alloc(bytes));
+		NRM_HIP(hipMemsetAsync(p, 0, bytes, st));
+		return NRM_OK;
+	}
 	template <typename T>
 	T* as() const {
 		return reinterpret_cast<T*>(p);
@@ -65,9 +75,106 @@ struct NrmHostPin {
 		}
 	}
 };
+// joins a helper thread on every way out of the scope
+struct NrmJoiner {
+	std::thread& t;
+	~NrmJoiner() {
+		if (t.joinable()) t.join();
+	}
+};
 
 static inline int64_t nrm_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 static inline size_t nrm_esize(int dtype) { return dtype == NRM_F64 ? 8 : 4; }
+
+// host covariates as fp64 (nc, n), on the host and on the device
+static inline int covariates_f64(const void* h_dc, int c_dtype, int64_t nc, int64_t n, std::vector<double>& c64, DevBuf& dc) {
+	if (nc <= 0) return NRM_OK;
+	c64.resize((size_t)nc * n);
+	if (c_dtype == NRM_F64)
+		memcpy(c64.data(), h_dc, c64.size() * 8);
+	else
+		for (size_t i = 0; i < c64.size(); i++) c64[i] = ((const float*)h_dc)[i];
+	NRM_TRY(dc.alloc(c64.size() * 8));
+	NRM_HIP(hipMemcpy(dc.p, c64.data(), c64.size() * 8, hipMemcpyHostToDevice));
+	return NRM_OK;
+}
+
+// (from half a GB up: host threads fill page-locked blocks beside the DMA, nrm_upload.hip)
+static inline int upload_matrix(const void* h, int dtype, int64_t rows, int64_t n, DevBuf& d, hipStream_t st) {
+	NRM_TRY(d.alloc((size_t)rows * n * nrm_esize(dtype)));
+	return nrm_upload(h, d.p, rows * n * (int64_t)nrm_esize(dtype), 0, (void*)st);
+}
+
+template <typename T>
+static inline int download(std::vector<T>& h, const void* d, size_t count) {
+	h.resize(count);
+	NRM_HIP(hipMemcpy(h.data(), d, count * sizeof(T), hipMemcpyDeviceToHost));
+	return NRM_OK;
+}
+
+// results (rows x cols of out_dtype) device -> the caller's array, page-locked for the copy when it is large
+static inline int copy_out(void* h, const void* d, size_t bytes) {
+	if (!h || !bytes) return NRM_OK;
+	NrmHostPin pin;
+	pin.try_pin(h, (int64_t)bytes);
+	NRM_HIP(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost));
+	return NRM_OK;
+}
+
+// the first N words of an entry's result counters, once everything queued on st is done
+template <int N>
+static inline int nrm_read_flags(const void* d_flags, hipStream_t st, int32_t (&hf)[N]) {
+	NRM_HIP(hipMemcpyAsync(hf, d_flags, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+	NRM_HIP(hipStreamSynchronize(st));
+	return NRM_OK;
+}
+// words 0 and 1 as the reference's error; `unit`: what the kernel counted (" tiles" for the tiled sweeps, "" for plain results)
+static inline int nrm_assoc_assertions(const int32_t* hf, const char* unit) {
+	if (hf[0] || hf[1]) {
+		nrm_set_error("association results failed the reference's assertions (association.py:248,252): %d%s non-finite, %d%s with R^2 > 1+1e-8", hf[0], unit, hf[1], unit);
+		return NRM_E_NUMERIC;
+	}
+	return NRM_OK;
+}
+
+// variances = ss / n with the 0 -> 1 rule (association.py:230-233), cast to the output dtype
+static inline int emit_var(const double* d_ss, int64_t cnt, int64_t n, void* h_out, int out_dtype) {
+	std::vector<double> hs;
+	NRM_TRY(download(hs, d_ss, (size_t)cnt));
+	for (double& v : hs) {
+		v /= (double)n;
+		if (v == 0.0) v = 1.0;
+	}
+	nrm_store_as(out_dtype, h_out, hs.data(), cnt);
+	return NRM_OK;
+}
+
+// single=0's result matrices (nx, ny) of out_dtype on the device: P-values and the statistic, r and t on request
+struct NrmAssocOut {
+	DevBuf p, stat, r, t;
+	int alloc(size_t bytes, bool want_r, bool want_t) {
+		NRM_TRY(p.alloc(bytes));
+		NRM_TRY(stat.alloc(bytes));
+		if (want_r) NRM_TRY(r.alloc(bytes));
+		if (want_t) NRM_TRY(t.alloc(bytes));
+		return NRM_OK;
+	}
+	int copy_to(void* h_p, void* h_stat, void* h_r, void* h_t, size_t bytes) const {
+		NRM_HIP(hipMemcpy(h_p, p.p, bytes, hipMemcpyDeviceToHost));
+		NRM_HIP(hipMemcpy(h_stat, stat.p, bytes, hipMemcpyDeviceToHost));
+		if (h_r) NRM_HIP(hipMemcpy(h_r, r.p, bytes, hipMemcpyDeviceToHost));
+		if (h_t) NRM_HIP(hipMemcpy(h_t, t.p, bytes, hipMemcpyDeviceToHost));
+		return NRM_OK;
+	}
+};
+
+// Does a call of this size take the sparse-design kernels, if its design then turns out to have few entries (a CRISPR screen's gRNA incidence)?  Same size
+// rule as normalisr_amd.engine; NRM_DE_SPARSE=0 switches it off, =force takes it whatever the size.
+static inline bool nrm_de_sparse_wanted(int64_t nx, int64_t ny, int64_t n, int64_t nc) {
+	const char* mode = getenv("NRM_DE_SPARSE");
+	const bool off = mode && !strcmp(mode, "0"), force = mode && !strcmp(mode, "force");
+	return !off && nc <= nrm_de_sparse_max_covariates() && (force || (nx >= 32 && ny >= 64 && n >= 2048 && nx * n >= (1ll << 22)));
+}
 
 // The design matrix (already in HBM) as the lists of csrc/nrm_design_lists.hip: CSR always, ELL on request.  ok: 0 < entries <= max_density nx n.
 struct NrmDesignLists {
@@ -78,12 +185,16 @@ struct NrmDesignLists {
 	int build(const void* d_x, int x_dtype, int64_t nx, int64_t n, bool want_ell, double max_density, hipStream_t st);
 };
 
-// the sparse-design form of single=0 de inside nrm_association_tests_host (nrm_host_entries.hip); *taken = 0: the design does not qualify
+// x~ . y~ for every (design row, expression row) through the sparse-design kernels (nrm_host_de.hip): d_dot (nxp, nyp) or, by_gene, (nyp, nxp); the rows' sums
+// with the covariates inside the kernel for up to nrm_de_sparse_fused_covariates() of them, by the stream kernel of single=1 otherwise
+int sparse_products(NrmDesignLists& L, const void* d_y, int y_dtype, int64_t ny, int64_t n, const double* d_c, int64_t ncu, int ci, double cval, const double* d_dci,
+					const double* d_bx, int64_t ldb, double* d_dot, int64_t ldd, int by_gene, double* d_ssy, double* d_coefy, int32_t* d_flags, hipStream_t st);
+// the sparse-design form of single=0 de inside nrm_association_tests_host (nrm_host_de.hip); *taken = 0: the design does not qualify
 // (dense, or empty) and nothing was written; *handed_back = rows too close to the span of the covariates (the caller runs the dense fp64 path)
 int nrm_host_de_sparse(const void* d_x, int x_dtype, int64_t nx, const void* d_y, int y_dtype, int64_t ny, const double* d_c, const double* h_c64, int64_t nc, int64_t n,
 					   const double* d_dci, int rank, double dof, int stat_kind, void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary, void* h_r, void* h_t,
 					   int out_dtype, int* taken, int64_t* handed_back);
-// de with nx + nc <= 32: the streaming kernel (nrm_host_entries.hip); d_x in HBM, h_dy uploaded inside
+// de with nx + nc <= 32: the streaming kernel (nrm_host_de.hip); d_x in HBM, h_dy uploaded inside
 int nrm_host_de_streaming(const void* d_x, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const double* h_c64, int64_t nc, int64_t n,
 						  const double* h_dci, int rank, double dof, int stat_kind, void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary, void* h_r, void* h_t,
 						  int out_dtype);

@@ -92,7 +92,7 @@ extern "C" int nrm_host_minmax(const void* p, int dtype, int64_t count, int thre
 	return NRM_OK;
 }
 
-// eigenvalues (ascending) of one small symmetric matrix (n <= 32): the covariate block of single=4's rank certificate (nrm_host_entries.hip)
+// eigenvalues (ascending) of one small symmetric matrix (n <= 32): the covariate block of single=4's rank certificate (nrm_full_rank_certified, nrm_host_math.h)
 extern "C" int nrm_small_eigvals(const double* m, int64_t n, double* w) {
 	NRM_REQUIRE(m && w && n > 0 && n <= SP_NMAX, "nrm_small_eigvals: bad arguments (matrices up to %d x %d)", SP_NMAX, SP_NMAX);
 	double a[SP_NMAX * SP_NMAX], v[SP_NMAX * SP_NMAX];

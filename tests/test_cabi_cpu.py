@@ -154,7 +154,7 @@ def test_host_logic_under_address_and_ub_sanitizers(tmp_path):
 	assert r.returncode == 0 and 'host logic ok' in r.stdout, r.stdout[-2000:]
 
 
-def _sanitize_build_and_run(tmp_path, hip_source, harness, token):
+def _sanitize_build_and_run(tmp_path, hip_source, harness, token, args=()):
 	import shutil
 	import subprocess
 	gxx = shutil.which('g++')
@@ -168,8 +168,71 @@ def _sanitize_build_and_run(tmp_path, hip_source, harness, token):
 	if r.returncode != 0 and ('asan' in r.stdout or 'ubsan' in r.stdout or 'sanitize' in r.stdout):
 		pytest.skip('sanitizer runtimes not installed: ' + r.stdout[-200:])
 	assert r.returncode == 0, r.stdout[-3000:]
-	r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+	r = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
 	assert r.returncode == 0 and token in r.stdout, r.stdout[-3000:]
+	return r.stdout
+
+
+def _certificate_cases(seed=7, n=64, nx=4, per_kind=4, tol=1e-8):
+	"""Seeded designs for single=4's two rank certificates, each as the closed form hands it over: M~ = X~ X~^T on rows residualised with inv_rank's
+	pseudo-inverse of C C^T gives norm_mt = ||M~||_1, norm_ninv = ||M~^-1||_1, bx, ss_x; with them mcc and inv_rank's rank.  -> (kind name, pinv?, numbers)."""
+	from normalisr_amd.association import inv_rank
+	rng = np.random.default_rng(seed)
+	onehot = lambda: np.eye(3)[:, rng.integers(0, 3, n)]
+	cases = []
+	for kind in ('one-hot batches', 'normal covariates', 'twin design rows', 'design row on a covariate', 'one-hot batches and a twin'):
+		for _ in range(per_kind):
+			x = rng.normal(size=(nx, n))
+			if kind == 'one-hot batches':  # intercept + 3 one-hot batches: rank 3 of 4
+				c = np.vstack([np.ones((1, n)), onehot()])
+			elif kind == 'one-hot batches and a twin':  # ... and a copy of one of them, all but exact: rank 3 of 5
+				c = np.vstack([np.ones((1, n)), onehot()])
+				c = np.vstack([c, c[2] + 1e-7 * rng.normal(size=n)])
+			else:  # intercept + 2 normal rows: full rank
+				c = np.vstack([np.ones((1, n)), rng.normal(size=(2, n))])
+			if kind == 'twin design rows':
+				x[3] = x[1] + 1e-7 * rng.normal(size=n)
+			elif kind == 'design row on a covariate':
+				x[2] = c[1] + 1e-9 * rng.normal(size=n)
+			mcc = c @ c.T
+			dci, rank = inv_rank(mcc, tol=tol)
+			bx = x @ c.T @ dci
+			xt = x - bx @ c
+			mt = xt @ xt.T
+			ninv = np.linalg.inv(mt)
+			cases.append((kind, rank < c.shape[0], dict(nx=nx, nc=c.shape[0], rank=int(rank), norm_mt=float(np.abs(mt).sum(axis=0).max()),
+														 norm_ninv=float(np.abs(ninv).sum(axis=0).max()), bx=bx, ss_x=np.diag(mt).copy(), mcc=mcc)))
+	return cases
+
+
+def test_entry_math_under_address_and_ub_sanitizers(tmp_path):
+	"""csrc/nrm_host_math.h (free of HIP headers): the arithmetic of the whole-problem C entries that decides a route or a rank -- the host's Cholesky inverse, the constant
+	covariate row, C C^T, the streaming de's covariate permutation -- under ASan + UBSan on exact-size buffers (tests/host/entry_math_sanitize.cpp), and single=4's two rank
+	certificates held to the numpy twins the package runs (single4.pinv_rank_certificate, _surely_full_rank) on the same numbers.  A case whose numpy verdict changes between
+	tol / 4 and 4 tol is borderline (the eigenvalues come from Jacobi sweeps there, from LAPACK here) and left out; every kind of design keeps at least one case."""
+	from normalisr_amd import single4
+	tol = 1e-8
+	flat, want, kinds = [], [], []
+	for kind, pinv, c in _certificate_cases(tol=tol):
+		if pinv:
+			twin = lambda t: single4.pinv_rank_certificate(c['norm_mt'], c['norm_ninv'], c['bx'], c['ss_x'], c['mcc'], t)
+		else:
+			twin = lambda t: single4._surely_full_rank((c['norm_mt'], c['norm_ninv'], c['bx']), c['mcc'], None, t)
+		verdicts = {bool(twin(t)) for t in (tol / 4, tol, 4 * tol)}
+		if len(verdicts) != 1:
+			continue
+		kinds.append(kind)
+		want.append(verdicts.pop())
+		flat += [[0. if pinv else 1., c['nx'], c['nc'], c['rank'], c['norm_mt'], c['norm_ninv'], tol], c['bx'].ravel(), c['ss_x'], c['mcc'].ravel()]
+	assert len(set(kinds)) == 5, kinds
+	path = tmp_path / 'certificate_cases.f64'
+	np.concatenate([[float(len(want))]] + [np.asarray(f, dtype=np.float64) for f in flat]).tofile(str(path))
+	out = _sanitize_build_and_run(tmp_path, 'nrm_small_pinv.hip', 'entry_math_sanitize.cpp', 'entry math ok', args=[str(path)])
+	got = [line.split()[1] == '1' for line in out.splitlines() if line.startswith('verdict ')]
+	print('certificates (kind, numpy, C++):', list(zip(kinds, want, got)))
+	assert got == want, list(zip(kinds, want, got))
+	assert {k: w for k, w in zip(kinds, want)} == {'one-hot batches': True, 'normal covariates': True, 'twin design rows': False, 'design row on a covariate': False,
+												   'one-hot batches and a twin': True}
 
 
 def test_small_numerics_under_address_and_ub_sanitizers(tmp_path):

@@ -508,7 +508,7 @@ np.savez(sys.argv[3], **out)
 
 def test_c_entry_streams_case_control_de(tmp_path):
 	"""de with nx + nc <= 32 (BASELINE configs[2]: one grouping, 20 covariates) through nrm_association_tests_host from a process without torch: the
-	entry takes the streaming kernel as the Python engine does (csrc/nrm_host_entries.hip: nrm_host_de_streaming) -- an intercept anywhere among the
+	entry takes the streaming kernel as the Python engine does (csrc/nrm_host_de.hip: nrm_host_de_streaming) -- an intercept anywhere among the
 	covariates (it moves to the end of Z; alpha comes back in the caller's order), none, rank-deficient covariates, cell counts off the 16- and
 	128-cell grids, fp32 and fp64 rows, 32 rows in Z exactly; P, statistic, alpha, variances, r and t against the oracle."""
 	import subprocess
