@@ -451,6 +451,8 @@ int nrm_normvar_apply_w2(const void* d_y, int y_dtype, int64_t rows, int64_t n, 
 /* Frees the device scratch nrm_association_tests_host keeps between calls (it is reused best-fit; calls are
  * serialised per process). */
 int nrm_release_cache(void);
+/* The pool's own accounting: *held = bytes of device memory the pool holds, *in_use = those of them taken by a running entry or a live plan (either may be NULL). */
+int nrm_cache_bytes(int64_t* held, int64_t* in_use);
 /* Verdict of the integer engine's accuracy guard for the last nrm_association_tests_host call of this thread: *hits = pairs it could
  * not certify on the integer pass (> 0: the call was redone on the fp64 Gram kernel before returning), *worst = largest relative
  * error estimate of a P-value among the pairs it looked at.  NRM_I8_GUARD_TOL sets the tolerance (default 2.5e-7; 0 = no guard). */
@@ -603,6 +605,14 @@ int nrm_single1_common_gram(const int32_t* d_cnt, int64_t n, const double* d_c, 
  * zero) -- Jacobi iteration per matrix, the stack dealt to `threads` host threads (0 = choose).  m, inv (count, n, n) fp64; n <= 32.
  */
 int nrm_small_pinv(const double* m, int64_t count, int64_t n, double tol, double* inv, int64_t* rank, int threads);
+
+/*
+ * The covariates' side of a single=0 call for a binder without LAPACK (host only): h_dci (nc, nc) fp64 = the pseudo-inverse of C C^T and *rank its integer rank,
+ * what association.py:899-903 takes from inv_rank(np.matmul(dc, dc.T)) (:77-80: singular values below tol x the largest count as zero; the reference's tol is 1e-8).
+ * C C^T is summed in fp64 cell by cell, in a fixed order; the eigenvalues come from the Jacobi iteration behind nrm_small_pinv.  All-zero covariates are rank 0 with
+ * a zero h_dci (the reference crashes there).  h_dc (nc, n_cells) of c_dtype; nc == 0: rank 0, nothing written; nc > 32: NRM_E_UNSUPPORTED.
+ */
+int nrm_covariates_pinv(const void* h_dc, int c_dtype, int64_t nc, int64_t n_cells, double tol, double* h_dci, int* rank);
 
 /*
  * Host -> device copy of a caller's (pageable) array through a ring of page-locked staging blocks the library owns: host threads fill
@@ -850,6 +860,49 @@ int nrm_enrich_host(const uint8_t* h_study, int64_t S, int64_t G, int64_t ld, co
 int nrm_coex_project(const void* d_x, int x_dtype, int64_t nt, int64_t ns, int64_t ldx, const double* d_q, int64_t k, int64_t ldq, double* d_a, int64_t lda, void* stream);
 int nrm_coex_downdate(double* d_g, int64_t nt, int64_t ld, double* d_ss, const double* d_ss_ref, const double* d_a, int64_t k, int64_t lda, int32_t* d_counters,
 					  void* stream);
+
+/*
+ * Resident coex plan (csrc/nrm_coex_plan.hip): coex(dt, dc) -- reference coex.py:4-48, that is association_tests(dt, None, dc) at association.py:761-1093 with its
+ * tile loop :890-909,997-1057 -- for a caller that repeats it on a matrix of one shape.  The problem stays in HBM; a step is K1 -> K2 -> K3 -> variances
+ * (association.py:224-235,248-249,230-233) on one stream; nothing is allocated, copied or decided on the host between steps.  numpy and this library suffice.
+ *   nrm_coex_plan_create: dt (ng, n_cells) of dt_dtype.  dt_on_device == 0: a contiguous HOST array (ld == n_cells, or 0); the plan owns a device copy, uploaded
+ *       through nrm_upload.  dt_on_device != 0: a DEVICE pointer with row pitch ld elements, adopted: never copied, never freed, and the caller may rewrite it in
+ *       place between steps (in stream order with them); create synchronises the device, so whatever filled it is through.  h_dc (nc, n_cells) of c_dtype, h_dci (nc, nc) fp64 and rank as nrm_association_tests_host takes them;
+ *       h_dci == NULL: the library computes both (nrm_covariates_pinv at tol 1e-8; rank is ignored; nc <= 32).  Every argument check of nrm_association_tests_host
+ *       is made, in the reference's words (association.py:199-216), before any device call: NRM_E_ARG.  The K2 engine is chosen once, by that entry's rule: 6 digit
+ *       planes from 2048 cells (NRM_GRAM=i8|i8x5|f64 overrides) when the matrix has 16-byte aligned rows (base % 16 == 0 and ld % 4 == 0), the fp64 kernel otherwise.
+ *       NRM_I8_GUARD_TOL is read here.  Every buffer a step needs is taken from the scratch pool here and given back by nrm_coex_plan_destroy.  The plan
+ *       remembers its device (nrm_set_device's at create) and binds the calling thread to it on every entry.
+ *   nrm_coex_plan_upload: new values (same shape and dtype) into the plan's own copy; NRM_E_ARG for an adopted matrix.
+ *   nrm_coex_plan_step: stream == NULL: a non-blocking stream the plan created (the legacy stream cannot be captured).  The first step runs eagerly, the second is
+ *       recorded by thread-local stream capture and instantiated, later steps are one hipGraphLaunch.  Does not synchronise.  If the capture fails it is ended and
+ *       discarded, the plan stays eager and nrm_last_error says why (the step itself still runs: NRM_OK).  NRM_DEBUG="graph=0" keeps every step eager.
+ *   nrm_coex_plan_check: synchronises the device (steps may have gone to any streams), reads and clears the step counters.  NRM_E_NUMERIC for the reference's assertions (association.py:248,252).  If the integer
+ *       engine's guard could not certify a pair since the last check, the step is redone now, eagerly, on the fp64 Gram kernel from the matrix as it stands (fp64
+ *       rows allocated for that one pass) and *guard_hits is the count (else 0); *guard_worst the largest relative error estimate of a P-value.  After NRM_OK what
+ *       the plan holds is certified, as after nrm_association_tests_host.  Either pointer may be NULL.
+ *   nrm_coex_plan_results: check, then P-values and covariances (ng, ng) and variances (ng) of out_dtype into the caller's HOST arrays (any may be NULL); large
+ *       arrays are page-locked for the copy.
+ *   nrm_coex_plan_device_results: the same three as DEVICE pointers (row pitch *ld elements), valid until destroy, written by every step: a consumer such as
+ *       nrm_binnet queued on the step's stream (nrm_coex_plan_stream: the plan's own) reads them without anything leaving HBM.
+ *   nrm_coex_plan_info: info[0] engine (0 fp64, 5 or 6 digit planes), [1] captured (0/1), [2] steps run, [3] fp64 reruns, [4] rank, [5] dof, [6] bytes resident, [7] 0.
+ *   nrm_coex_plan_time: `steps` steps between two events on the plan's stream, *ms_per_step their mean (the eager first step and the capture run before, untimed).
+ *   nrm_coex_plan_destroy: accepts NULL.
+ * Threads: create, check, results and destroy take the lock of the whole-problem entries (they use the scratch pool); step, upload and time do not.  A plan is
+ * used by one thread at a time; two plans in one process are fine.  nrm_release_cache leaves a live plan's buffers alone (they are taken, not idle).
+ */
+typedef struct nrm_coex_plan nrm_coex_plan;
+int nrm_coex_plan_create(nrm_coex_plan** plan, const void* dt, int dt_dtype, int64_t ng, int64_t n_cells, int64_t ld, int dt_on_device, const void* h_dc, int c_dtype,
+						 int64_t nc, const double* h_dci, int rank, int dimreduce, int out_dtype);
+int nrm_coex_plan_upload(nrm_coex_plan* plan, const void* h_dt);
+int nrm_coex_plan_step(nrm_coex_plan* plan, void* stream);
+int nrm_coex_plan_check(nrm_coex_plan* plan, int64_t* guard_hits, double* guard_worst);
+int nrm_coex_plan_results(nrm_coex_plan* plan, void* h_p, void* h_dot, void* h_var);
+int nrm_coex_plan_device_results(nrm_coex_plan* plan, void** d_p, void** d_dot, void** d_var, int64_t* ld);
+int nrm_coex_plan_stream(nrm_coex_plan* plan, void** stream);
+int nrm_coex_plan_info(nrm_coex_plan* plan, int64_t info[8]);
+int nrm_coex_plan_time(nrm_coex_plan* plan, int64_t steps, double* ms_per_step);
+int nrm_coex_plan_destroy(nrm_coex_plan* plan);
 
 #ifdef __cplusplus
 }

@@ -281,6 +281,19 @@ extern "C" int nrm_release_cache(void) {
 	return NRM_OK;
 }
 
+// the pool's own accounting: bytes of device memory it holds, and how many of them are taken (by a running entry or a live plan)
+extern "C" int nrm_cache_bytes(int64_t* held, int64_t* in_use) {
+	std::lock_guard<std::mutex> g(g_pool.mu);
+	int64_t h = 0, u = 0;
+	for (const auto& b : g_pool.blocks) {
+		h += (int64_t)b.cap;
+		if (b.used) u += (int64_t)b.cap;
+	}
+	if (held) *held = h;
+	if (in_use) *in_use = u;
+	return NRM_OK;
+}
+
 // Verdict of the integer engine's accuracy guard (csrc/nrm_fix.h) for the last whole-problem call of this thread: pairs it could not
 // certify on the first pass (0: the integer engine's results were returned; > 0: the call was redone on the fp64 Gram kernel),
 // and the largest error estimate of a P-value (relative) among the pairs it looked at.
@@ -322,11 +335,6 @@ static bool de_path_general() {  // NRM_DEBUG="de_path=general" (or NRM_DE_PATH=
 	return e && !strcmp(e, "general");
 }
 
-static double guard_tolerance() {
-	const char* t = getenv("NRM_I8_GUARD_TOL");  // largest relative change of a P-value the integer engine may cause (0: no guard)
-	return t ? atof(t) : 2.5e-7;
-}
-
 static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny,
 										  const void* h_dc, int c_dtype, int64_t nc, int64_t n, const double* h_dci, int rank,
 										  int dimreduce, int return_dot, void* h_p, void* h_stat, void* h_alpha, void* h_varx,
@@ -341,14 +349,8 @@ extern "C" int nrm_association_tests_host(const void* h_dx, int x_dtype, int64_t
 	// K2 engine as in the Python host (NRM_GRAM): exact fixed-point contraction on the int8 matrix cores (6 slices = 46 bits; i8x5: 5
 	// slices = 38 bits), or the fp64 matrix-core kernel (f64).  With the integer engine K1 writes the digit planes itself and the
 	// fp64 residuals are never stored.
-	int nslices = 6;
-	if (n < 2048 || n >= (1 << 22)) nslices = 0;  // small problems stay on the fp64 kernel (the integer engine's error in r grows as 1/sqrt(n))
-	else if (const char* g = getenv("NRM_GRAM")) {
-		if (!strcmp(g, "f64")) nslices = 0;
-		else if (!strcmp(g, "i8x5")) nslices = 5;
-		else NRM_REQUIRE(!strcmp(g, "i8"), "NRM_GRAM must be i8, i8x5 or f64");
-	}
-	if (nslices && (n % 4 != 0)) nslices = 0;  // K1's fused quantiser needs 16-byte aligned rows of the (unpadded) host matrices
+	int nslices = 0;
+	NRM_TRY(nrm_assoc_engine(n, n % 4 == 0, &nslices));  // (K1's fused quantiser needs 16-byte aligned rows of the unpadded host matrices)
 	g_guard_hits = 0;
 	g_guard_worst = 0.0;
 	int64_t hits = 0;
@@ -371,12 +373,7 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 		ny = nx;
 		y_dtype = x_dtype;
 	}
-	NRM_REQUIRE(h_dx && nx > 0 && ny > 0 && n > 0, "Incorrect dx/dy/dc size.");
-	NRM_REQUIRE(nc >= 0 && (nc == 0 || h_dc), "Incorrect dx/dy/dc size.");
-	NRM_REQUIRE(rank >= 0, "Negative dcr detected.");
-	NRM_REQUIRE(rank <= nc, "dcr higher than covariate dimension.");
-	NRM_REQUIRE(n > (int64_t)rank + dimreduce + 1,
-				"Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.");
+	NRM_TRY(nrm_assoc_check_args(h_dx, nx, ny, h_dc, nc, n, rank, dimreduce));
 	NRM_REQUIRE(h_p && h_stat && h_vary, "nrm_association_tests_host: null output");
 	const double dof = (double)(n - 1 - rank - dimreduce);
 	hipStream_t st = nullptr;
@@ -392,20 +389,11 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	NrmJoiner joiner{pinner};
 	std::vector<double> c64;
 	NRM_TRY(covariates_f64(h_dc, c_dtype, nc, n, c64, dc));
-	if (nc > 0) {
-		std::vector<double> cm((size_t)nc, 0.0);  // max |C_c| per covariate row: K1's bound on the residuals it quantises
-		for (int64_t c = 0; c < nc; c++)
-			for (int64_t k = 0; k < n; k++) cm[(size_t)c] = std::max(cm[(size_t)c], std::fabs(c64[(size_t)(c * n + k)]));
-		NRM_TRY(cmax.alloc((size_t)nc * 8));
-		NRM_HIP(hipMemcpy(cmax.p, cm.data(), (size_t)nc * 8, hipMemcpyHostToDevice));
-		NRM_TRY(dci.alloc((size_t)nc * nc * 8));
-		NRM_REQUIRE(h_dci != nullptr || rank == 0, "Unmatching dci dimensions.");
-		if (h_dci) NRM_HIP(hipMemcpy(dci.p, h_dci, (size_t)nc * nc * 8, hipMemcpyHostToDevice));
-	}
+	NRM_TRY(covariate_bounds(c64, nc, n, h_dci, rank, cmax, dci));
 	const bool want_alpha = h_alpha != nullptr && nc > 0;
 	NRM_REQUIRE(!(want_alpha && samexy), "alpha is not provided for dy == NULL (meaningless in the reference, association.py:1066-1068)");
 	DevBuf qx, qy, ex, ey, fx, fy;
-	const double guard_tol = guard_tolerance();
+	const double guard_tol = nrm_guard_tolerance();
 	NRM_TRY(upload_matrix(h_dx, x_dtype, nx, n, dx, st));
 	// A design matrix with few entries (a CRISPR screen's gRNA incidence): the sparse-design kernels -- the expression rows read once, raw, the
 	// contraction replaced by gathers at the design's entries (nrm_host_de.hip; what normalisr_amd.engine does for the Python host), for the calls
@@ -435,14 +423,11 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 		NRM_TRY(qx.alloc((size_t)nrm_quant_bytes(mp, kp, nslices)));
 		NRM_TRY(ex.alloc((size_t)mp * 4));
 		NRM_TRY(fx.alloc((size_t)mp * 8 * 8));
-		NRM_TRY(nrm_residualize_q(dx.p, x_dtype, nx, n, n, dc.as<double>(), nc, n, dci.as<double>(), rank, nullptr, kp, mp, ssx.as<double>(),
-								  want_alpha ? bx.as<double>() : nullptr, nslices, qx.p, ex.as<int32_t>(), 0, nc ? cmax.as<double>() : nullptr,
-								  fx.as<double>(), st));
 	} else {
 		NRM_TRY(rx.alloc((size_t)mp * kp * 8));
-		NRM_TRY(nrm_residualize(dx.p, x_dtype, nx, n, n, dc.as<double>(), nc, n, dci.as<double>(), rank, rx.as<double>(), kp, mp,
-								ssx.as<double>(), want_alpha ? bx.as<double>() : nullptr, st));
 	}
+	NRM_TRY(nrm_assoc_k1(dx.p, x_dtype, nx, n, n, dc.as<double>(), nc, dci.as<double>(), rank, kp, mp, ssx.as<double>(), want_alpha ? bx.as<double>() : nullptr, nslices, qx.p,
+						 ex.as<int32_t>(), cmax.as<double>(), fx.as<double>(), rx.as<double>(), st));
 	if (!samexy) {
 		if (!dy_up) NRM_TRY(upload_matrix(h_dy, y_dtype, ny, n, dy, st));
 		NRM_TRY(ssy.alloc((size_t)np_ * 8));
@@ -451,17 +436,12 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 			NRM_TRY(qy.alloc((size_t)nrm_quant_bytes(np_, kp, nslices)));
 			NRM_TRY(ey.alloc((size_t)np_ * 4));
 			NRM_TRY(fy.alloc((size_t)np_ * 8 * 8));
-			NRM_TRY(nrm_residualize_q(dy.p, y_dtype, ny, n, n, dc.as<double>(), nc, n, dci.as<double>(), rank, nullptr, kp, np_, ssy.as<double>(),
-									  want_alpha ? by.as<double>() : nullptr, nslices, qy.p, ey.as<int32_t>(), 0, nc ? cmax.as<double>() : nullptr,
-									  fy.as<double>(), st));
 		} else {
 			NRM_TRY(ry.alloc((size_t)np_ * kp * 8));
-			NRM_TRY(nrm_residualize(dy.p, y_dtype, ny, n, n, dc.as<double>(), nc, n, dci.as<double>(), rank, ry.as<double>(), kp, np_,
-									ssy.as<double>(), want_alpha ? by.as<double>() : nullptr, st));
 		}
+		NRM_TRY(nrm_assoc_k1(dy.p, y_dtype, ny, n, n, dc.as<double>(), nc, dci.as<double>(), rank, kp, np_, ssy.as<double>(), want_alpha ? by.as<double>() : nullptr, nslices, qy.p,
+							 ey.as<int32_t>(), cmax.as<double>(), fy.as<double>(), ry.as<double>(), st));
 	}
-	const double* A = rx.as<double>();
-	const double* B = samexy ? A : ry.as<double>();
 	const double* sx = ssx.as<double>();
 	const double* sy = samexy ? sx : ssy.as<double>();
 	pinner = std::thread([&] {
@@ -474,25 +454,24 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	DevBuf gwork;
 	NRM_TRY(gwork.alloc((size_t)nrm_gram_workspace_bytes()));
 	NRM_TRY(flags.alloc_zero(16, st));
-	const double* fxp = nslices ? fx.as<double>() : nullptr;
-	const double* fyp = nslices ? (samexy ? fxp : fy.as<double>()) : nullptr;
 	NRM_TRY(out.alloc(ob, h_r != nullptr, h_t != nullptr));
 	// coex always converts to covariance (association.py:1037-1039); de keeps gamma unless return_dot
 	const int stat_kind = (samexy || return_dot) ? 0 : 1;
 	// K2 -> K3 per band of output rows; finished bands are copied out on a second stream while later bands compute
 	// (the reference's gather loop, association.py:997-1034, consumes finished tiles the same way)
-	const int64_t band = 8 * NRM_ROW_TILE;
+	const int64_t band = NRM_ASSOC_BAND;
+	NrmAssocOperands ops;
+	ops.qx = qx.p, ops.ex = ex.as<int32_t>(), ops.fx = fx.as<double>(), ops.rx = rx.as<double>(), ops.ssx = sx;
+	ops.qy = samexy ? qx.p : qy.p, ops.ey = samexy ? ops.ex : ey.as<int32_t>(), ops.fy = samexy ? ops.fx : fy.as<double>(), ops.ry = samexy ? ops.rx : ry.as<double>(), ops.ssy = sy;
+	ops.nx = nx, ops.ny = ny, ops.n = n, ops.mp = mp, ops.np_ = np_, ops.kp = kp;
+	ops.nslices = nslices, ops.samexy = samexy ? 1 : 0, ops.stat_kind = stat_kind, ops.out_dtype = out_dtype, ops.dof = dof, ops.guard_tol = guard_tol;
+	ops.dot = dot.as<double>(), ops.gwork = gwork.p, ops.flags = flags.as<int32_t>();
+	ops.p = out.p.p, ops.stat = out.stat.p, ops.r = out.r.p, ops.t = out.t.p;
 	CopyStream cs;
 	NRM_HIP(hipStreamCreateWithFlags(&cs.s, hipStreamNonBlocking));
 	for (int64_t a = 0; a < nx; a += band) {
 		const int64_t b = std::min(nx, a + band);
-		if (nslices)
-			NRM_TRY(nrm_gram_i8_band(qx.p, ex.as<int32_t>(), 0, samexy ? qx.p : qy.p, samexy ? ex.as<int32_t>() : ey.as<int32_t>(), 0, mp, np_, kp, nslices,
-									 dot.as<double>(), np_, samexy ? 1 : 0, nx, ny, a, b == nx ? mp : b, gwork.p, st));
-		else
-			NRM_TRY(nrm_gram_f64_band(A, B, mp, np_, kp, kp, kp, dot.as<double>(), np_, samexy ? 1 : 0, nx, ny, a, b == nx ? mp : b, gwork.p, st));
-		NRM_TRY(nrm_assoc_sweep_band(dot.as<double>(), np_, sx, sy, nx, ny, n, dof, samexy ? 1 : 0, stat_kind, out.p.p, out.stat.p,
-									 out.r.p, out.t.p, out_dtype, ny, flags.as<int32_t>(), a, b, nslices, fxp, fyp, guard_tol, st));
+		NRM_TRY(nrm_assoc_band(ops, a, b, st));
 		hipEvent_t ev;
 		NRM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
 		cs.events.push_back(ev);

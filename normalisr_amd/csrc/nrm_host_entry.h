@@ -3,6 +3,8 @@
 // and the lock and holds the dense single=0 entry; the others are in nrm_host_de.hip (sparse-design and streaming de), nrm_host_single1.hip,
 // nrm_host_single4.hip (with nrm_gram_host / nrm_pvalues_host) and nrm_host_normvar.hip (with nrm_binnet_host).  Their arithmetic is in nrm_host_math.h.
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -89,11 +91,7 @@ static inline size_t nrm_esize(int dtype) { return dtype == NRM_F64 ? 8 : 4; }
 // host covariates as fp64 (nc, n), on the host and on the device
 static inline int covariates_f64(const void* h_dc, int c_dtype, int64_t nc, int64_t n, std::vector<double>& c64, DevBuf& dc) {
 	if (nc <= 0) return NRM_OK;
-	c64.resize((size_t)nc * n);
-	if (c_dtype == NRM_F64)
-		memcpy(c64.data(), h_dc, c64.size() * 8);
-	else
-		for (size_t i = 0; i < c64.size(); i++) c64[i] = ((const float*)h_dc)[i];
+	nrm_covariates_to_f64(h_dc, c_dtype, (size_t)nc * n, c64);
 	NRM_TRY(dc.alloc(c64.size() * 8));
 	NRM_HIP(hipMemcpy(dc.p, c64.data(), c64.size() * 8, hipMemcpyHostToDevice));
 	return NRM_OK;
@@ -167,6 +165,80 @@ struct NrmAssocOut {
 		return NRM_OK;
 	}
 };
+
+// ---- the launch sequence of dense single=0, shared by nrm_association_tests_host (nrm_api.hip) and the resident coex plan (nrm_coex_plan.hip) ----------------
+// K1 of one operand: the integer engine's digit planes, exponents and row records (nslices 5 or 6; the fp64 residuals never stored), or fp64 residual rows
+static inline int nrm_assoc_k1(const void* d_x, int x_dtype, int64_t rows, int64_t n, int64_t ldx, const double* d_c, int64_t nc, const double* d_dci, int rank, int64_t kp,
+							   int64_t rows_pad, double* d_ss, double* d_coef, int nslices, void* d_q, int32_t* d_exp, const double* d_cmax, double* d_fix, double* d_rows,
+							   hipStream_t st) {
+	if (nslices)
+		return nrm_residualize_q(d_x, x_dtype, rows, n, ldx, d_c, nc, n, d_dci, rank, nullptr, kp, rows_pad, d_ss, d_coef, nslices, d_q, d_exp, 0, nc ? d_cmax : nullptr, d_fix, st);
+	return nrm_residualize(d_x, x_dtype, rows, n, ldx, d_c, nc, n, d_dci, rank, d_rows, kp, rows_pad, d_ss, d_coef, st);
+}
+// what K2 and K3 read and write (samexy: the y side is the x side)
+struct NrmAssocOperands {
+	const void *qx = nullptr, *qy = nullptr;        // digit planes
+	const int32_t *ex = nullptr, *ey = nullptr;     // row exponents
+	const double *fx = nullptr, *fy = nullptr;      // row records (csrc/nrm_fix.h)
+	const double *rx = nullptr, *ry = nullptr;      // fp64 residual rows (nslices == 0)
+	const double *ssx = nullptr, *ssy = nullptr;
+	int64_t nx = 0, ny = 0, n = 0, mp = 0, np_ = 0, kp = 0;
+	int nslices = 0, samexy = 0, stat_kind = 0, out_dtype = NRM_F64;
+	double dof = 0.0, guard_tol = 0.0;
+	double* dot = nullptr;
+	void* gwork = nullptr;
+	int32_t* flags = nullptr;
+	void *p = nullptr, *stat = nullptr, *r = nullptr, *t = nullptr;
+};
+static constexpr int64_t NRM_ASSOC_BAND = 8 * NRM_ROW_TILE;
+// K2 -> K3 for the output rows [a, b), a a multiple of NRM_ASSOC_BAND
+static inline int nrm_assoc_band(const NrmAssocOperands& o, int64_t a, int64_t b, hipStream_t st) {
+	if (o.nslices)
+		NRM_TRY(nrm_gram_i8_band(o.qx, o.ex, 0, o.qy, o.ey, 0, o.mp, o.np_, o.kp, o.nslices, o.dot, o.np_, o.samexy, o.nx, o.ny, a, b == o.nx ? o.mp : b, o.gwork, st));
+	else
+		NRM_TRY(nrm_gram_f64_band(o.rx, o.ry, o.mp, o.np_, o.kp, o.kp, o.kp, o.dot, o.np_, o.samexy, o.nx, o.ny, a, b == o.nx ? o.mp : b, o.gwork, st));
+	return nrm_assoc_sweep_band(o.dot, o.np_, o.ssx, o.ssy, o.nx, o.ny, o.n, o.dof, o.samexy, o.stat_kind, o.p, o.stat, o.r, o.t, o.out_dtype, o.ny, o.flags, a, b, o.nslices,
+								o.nslices ? o.fx : nullptr, o.nslices ? o.fy : nullptr, o.guard_tol, st);
+}
+// the K2 engine of a dense single=0 problem of n cells: 6 digit planes from 2048 cells (the integer engine's error in r grows as 1 / sqrt(n)) when the rows are
+// 16-byte aligned (K1's fused quantiser), NRM_GRAM = i8 | i8x5 | f64 overriding, 0 = the fp64 kernel
+static inline int nrm_assoc_engine(int64_t n, bool aligned_rows, int* nslices) {
+	*nslices = 6;
+	if (n < 2048 || n >= (1 << 22)) *nslices = 0;
+	else if (const char* g = getenv("NRM_GRAM")) {
+		if (!strcmp(g, "f64")) *nslices = 0;
+		else if (!strcmp(g, "i8x5")) *nslices = 5;
+		else NRM_REQUIRE(!strcmp(g, "i8"), "NRM_GRAM must be i8, i8x5 or f64");
+	}
+	if (*nslices && !aligned_rows) *nslices = 0;
+	return NRM_OK;
+}
+static inline double nrm_guard_tolerance() {
+	const char* t = getenv("NRM_I8_GUARD_TOL");  // largest relative change of a P-value the integer engine may cause (0: no guard)
+	return t ? atof(t) : 2.5e-7;
+}
+// the checks of association.py:199-216 on a dense single=0 call, in the reference's words
+static inline int nrm_assoc_check_args(const void* dx, int64_t nx, int64_t ny, const void* h_dc, int64_t nc, int64_t n, int rank, int dimreduce) {
+	NRM_REQUIRE(dx && nx > 0 && ny > 0 && n > 0, "Incorrect dx/dy/dc size.");
+	NRM_REQUIRE(nc >= 0 && (nc == 0 || h_dc), "Incorrect dx/dy/dc size.");
+	NRM_REQUIRE(rank >= 0, "Negative dcr detected.");
+	NRM_REQUIRE(rank <= nc, "dcr higher than covariate dimension.");
+	NRM_REQUIRE(n > (int64_t)rank + dimreduce + 1, "Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.");
+	return NRM_OK;
+}
+// max |C_c| per covariate row (K1's bound on the residuals it quantises) and the pseudo-inverse, uploaded
+static inline int covariate_bounds(const std::vector<double>& c64, int64_t nc, int64_t n, const double* h_dci, int rank, DevBuf& cmax, DevBuf& dci) {
+	if (nc <= 0) return NRM_OK;
+	std::vector<double> cm((size_t)nc, 0.0);
+	for (int64_t c = 0; c < nc; c++)
+		for (int64_t k = 0; k < n; k++) cm[(size_t)c] = std::max(cm[(size_t)c], std::fabs(c64[(size_t)(c * n + k)]));
+	NRM_TRY(cmax.alloc((size_t)nc * 8));
+	NRM_HIP(hipMemcpy(cmax.p, cm.data(), (size_t)nc * 8, hipMemcpyHostToDevice));
+	NRM_TRY(dci.alloc((size_t)nc * nc * 8));
+	NRM_REQUIRE(h_dci != nullptr || rank == 0, "Unmatching dci dimensions.");
+	if (h_dci) NRM_HIP(hipMemcpy(dci.p, h_dci, (size_t)nc * nc * 8, hipMemcpyHostToDevice));
+	return NRM_OK;
+}
 
 // Does a call of this size take the sparse-design kernels, if its design then turns out to have few entries (a CRISPR screen's gRNA incidence)?  Same size
 // rule as normalisr_amd.engine; NRM_DE_SPARSE=0 switches it off, =force takes it whatever the size.

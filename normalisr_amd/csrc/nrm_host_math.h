@@ -49,6 +49,39 @@ static inline void nrm_covariate_gram(const double* c64, int64_t nc, int64_t n, 
 		}
 }
 
+// ---- the covariates' pseudo-inverse for a caller without LAPACK (nrm_covariates_pinv, the resident coex plan) ------------------------------------------------
+// covariates of c_dtype as fp64, the conversion every entry makes
+static inline void nrm_covariates_to_f64(const void* h_dc, int c_dtype, size_t count, std::vector<double>& c64) {
+	c64.resize(count);
+	if (c_dtype == NRM_F64) {
+		if (count) memcpy(c64.data(), h_dc, count * 8);
+	} else
+		for (size_t i = 0; i < count; i++) c64[i] = (double)((const float*)h_dc)[i];
+}
+// dci (nc, nc) = the pseudo-inverse of C C^T and its integer rank by the reference's rule (association.py:77-80: singular values below tol x the largest count as
+// zero), for covariates with a non-zero entry; all-zero covariates are rank 0 with a zero dci (association.py:899-903 as normalisr_amd.association._prepare_covariates
+// reads it).  C C^T is summed cell by cell in fp64 (nrm_covariate_gram), the eigenvalues come from the Jacobi iteration of nrm_small_pinv.  1 <= nc <= 32.
+static inline int nrm_covariates_pinv_f64(const double* c64, int64_t nc, int64_t n, double tol, double* dci, int* rank) {
+	bool any = false;
+	for (size_t i = 0; i < (size_t)(nc * n) && !any; i++) any = c64[i] != 0.0;
+	*rank = 0;
+	if (!any) {
+		for (int64_t i = 0; i < nc * nc; i++) dci[i] = 0.0;
+		return NRM_OK;
+	}
+	std::vector<double> mcc;
+	nrm_covariate_gram(c64, nc, n, mcc);
+	for (double v : mcc)
+		if (!std::isfinite(v)) {
+			nrm_set_error("array must not contain infs or NaNs");
+			return NRM_E_ARG;
+		}
+	int64_t r = 0;
+	nrm_small_pinv_one<32>(mcc.data(), (int)nc, tol, dci, &r);
+	*rank = (int)r;
+	return NRM_OK;
+}
+
 // ---- the streaming de: a constant covariate moves to the end of Z ----------------------------------------------------------------------------
 // perm[j] = the caller's index of Z's covariate j (ci last; ci < 0: the identity)
 static inline std::vector<int64_t> nrm_const_last_perm(int64_t nc, int ci) {

@@ -13,6 +13,7 @@
 
 #include "nrm_common.h"
 #include "nrm_jacobi.h"
+#include "nrm_host_math.h"
 
 #define SP_NMAX 32
 
@@ -38,6 +39,22 @@ extern "C" int nrm_small_pinv(const double* m, int64_t count, int64_t n, double 
 	work(0);
 	for (auto& x : th) x.join();
 	return NRM_OK;
+}
+
+// The covariates' side of a single=0 call for a binder without LAPACK: h_dci (nc, nc) fp64 = the pseudo-inverse of C C^T, *rank its integer rank (what
+// association.py:899-903 takes from inv_rank; csrc/nrm_host_math.h).  nc == 0: rank 0, nothing written.
+extern "C" int nrm_covariates_pinv(const void* h_dc, int c_dtype, int64_t nc, int64_t n_cells, double tol, double* h_dci, int* rank) {
+	NRM_REQUIRE(rank != nullptr && nc >= 0 && n_cells > 0 && (c_dtype == NRM_F32 || c_dtype == NRM_F64) && tol > 0, "nrm_covariates_pinv: bad arguments");
+	*rank = 0;
+	if (nc == 0) return NRM_OK;
+	NRM_REQUIRE(h_dc && h_dci, "nrm_covariates_pinv: null pointer");
+	if (nc > SP_NMAX) {
+		nrm_set_error("nrm_covariates_pinv: at most %d covariates (pass the pseudo-inverse and rank of a LAPACK SVD for more)", SP_NMAX);
+		return NRM_E_UNSUPPORTED;
+	}
+	std::vector<double> c64;
+	nrm_covariates_to_f64(h_dc, c_dtype, (size_t)(nc * n_cells), c64);
+	return nrm_covariates_pinv_f64(c64.data(), nc, n_cells, tol, h_dci, rank);
 }
 
 // ---- minimum, maximum and NaN count of a host array, threaded --------------------------------------------------------------------------
