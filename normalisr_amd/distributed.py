@@ -234,7 +234,7 @@ class HipBackend:
 			r = self.eng.residualize_chunked(x, d_c, d_dci, dcr, rows_pad, ns, chunks, into=into)
 			return r, r.ss
 		r = self.eng.residualize(x, d_c, d_dci, dcr, rows_pad=rows_pad, nslices=ns, keep_fp64=not ns, into=into)
-		if ns and getattr(r, '_quant', None) is None:  # rows K1 could not quantise itself (unaligned): separate pass
+		if ns and r.digits is None:  # rows K1 could not quantise itself (unaligned): separate pass
 			self.eng.quantized(r, ns)
 		return r, r.ss
 
@@ -244,16 +244,13 @@ class HipBackend:
 	def payload(self, blk):
 		"""What travels to the other ranks for this block: its digit planes and row exponents (6 bytes per value at 6 slices
 		against 8 for fp64 residuals), or the fp64 residuals for the fp64 engine."""
-		q = getattr(blk, '_quant', None)
-		return [q[0], q[1], blk.fix] if q is not None else [blk.data]
+		q = blk.digits
+		return [q.planes, q.exps, q.fix] if q is not None else [blk.data]
 
 	def from_payload(self, parts, rows, rows_pad, n, k_pad, ss):
-		from .engine import Residualized
+		from .engine import Residualized, Digits
 		if len(parts) == 3:  # digit planes, row exponents, row records (csrc/nrm_fix.h)
-			blk = Residualized(rows, n, None, ss, None, shape=(rows_pad, k_pad))
-			blk._quant = (parts[0], parts[1], self.eng.gram_slices(n))
-			blk.fix = parts[2]
-			return blk
+			return Residualized(rows, n, None, ss, None, shape=(rows_pad, k_pad), digits=Digits(parts[0], parts[1], parts[2], self.eng.gram_slices(n), k_pad))
 		return Residualized(rows, n, parts[0], ss, None, shape=(rows_pad, k_pad))
 
 	def gram(self, a, b, symmetric, rows_a=None, rows_b=None):
@@ -261,19 +258,17 @@ class HipBackend:
 
 	# cell-chunked blocks (the pipelined exchange): every chunk is an operand of its own, the row exponents are shared
 	def n_chunks(self, blk):
-		return len(blk._quant[0])
+		return len(blk.digits.chunks)
 
 	def chunk_payload(self, blk):
 		"""(tensors of the chunks, in cell order; tensors that travel once: the row exponents and the row records)."""
-		return list(blk._quant[0]), [blk._quant[1], blk.fix]
+		return list(blk.digits.chunks), [blk.digits.exps, blk.digits.fix]
 
 	def from_chunks(self, chunks, once, like, ss):
-		from .engine import Residualized
-		blk = Residualized(like.rows, like.n, None, ss, None, shape=(like.rows_pad, like.k_pad))
-		blk._quant = (list(chunks), once[0], like._quant[2])
-		blk.cks = like.cks
-		blk.fix = once[1]
-		return blk
+		from .engine import Residualized, Digits
+		q = like.digits
+		return Residualized(like.rows, like.n, None, ss, None, shape=(like.rows_pad, like.k_pad),
+							digits=Digits(None, once[0], once[1], q.nslices, q.k_pad, chunks=list(chunks), cks=q.cks))
 
 	def gram_chunk(self, a, b, symmetric, chunk, dot, accumulate):
 		return self.eng.gram_chunk(a, b, symmetric, chunk, dot, accumulate)

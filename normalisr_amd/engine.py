@@ -158,17 +158,92 @@ class GuardHit(Exception):
 		self.hits, self.worst = hits, worst
 
 
-class Residualized:
-	"""Residualised rows resident in HBM -- as fp64 (`data`) and / or as the fixed-point digit planes of the integer Gram
-	engine (`_quant`, with the row records `fix` K3 needs for them: csrc/nrm_fix.h) -- plus their sums of squares and OLS
-	coefficients."""
+def plane_bytes(rows, nks):
+	"""Bytes that `rows` rows (a multiple of 32) take in one digit plane of nks k-steps: 1 KB per 32 rows and 32 cells (csrc/nrm_gram_i8.hip).  Of all the
+	rows of an operand: its dense plane; of its first `lo` rows: where row lo starts in every plane."""
+	return (rows // 32) * nks * 1024
 
-	def __init__(self, rows, n, data, ss, coef, shape=None):
+
+class Digits:
+	"""Rows in the fixed-point form of the integer Gram engine: what K1 (or nrm_quantize_rows) writes and K2 / K3 read.
+	  planes    uint8: the one buffer of the digit planes; None where no one buffer stands for these rows (gathered chunks, a row block of chunks)
+	  chunks    None, or the operands of the cell chunks: views of `planes`, or the chunk tensors received from another rank
+	  exps      int32 [rows_pad] row exponents, shared by the chunks
+	  fix       fp64 [rows_pad][FIX_STRIDE] row records of K3's correction and guard (csrc/nrm_fix.h)
+	  nslices   digit planes per operand (5 / 6)
+	  k_pad     padded cells of the rows (all chunks together)
+	  pitch     bytes between two planes where the rows are a block of a larger operand (row_block); 0 = dense
+	  cks       None, or k-steps (32 cells) per chunk
+	fix comes with every operand (a sweep without it would run uncorrected and unguarded), cks with chunks and only with them, and an operand
+	that owns the one buffer of its chunks is dense."""
+
+	def __init__(self, planes, exps, fix, nslices, k_pad, pitch=0, chunks=None, cks=None):
+		if fix is None or exps is None or (planes is None and chunks is None):
+			raise ValueError('digit planes come with their row exponents and row records (fix)')
+		if (cks is None) != (chunks is None):
+			raise ValueError('cks (k-steps per chunk) is set for chunked digit planes and only for them')
+		if chunks is not None and planes is not None and pitch:
+			raise ValueError('chunked digit planes in one buffer are dense (pitch 0)')
+		self.planes, self.chunks, self.exps, self.fix = planes, chunks, exps, fix
+		self.nslices, self.k_pad, self.pitch, self.cks = int(nslices), int(k_pad), int(pitch), cks
+		self.rows_pad = int(exps.shape[0])
+		self.nks = (self.k_pad + 31) // 32 if cks is None else int(cks)  # k-steps of one operand (of a chunk when chunked)
+		self.plane_bytes = plane_bytes(self.rows_pad, self.nks)  # of a dense plane of these rows
+
+	@classmethod
+	def empty(cls, rows_pad, k_pad, nslices, chunks=None, **where):
+		"""Unwritten dense digits of (rows_pad, k_pad) rows, in (at most) `chunks` cell chunks of equal size when that is given; where: torch.empty's device."""
+		import torch
+		nks = (k_pad + 31) // 32
+		cks = None if chunks is None else cls.chunk_ksteps(k_pad, chunks)
+		one = nslices * plane_bytes(rows_pad, nks if cks is None else cks)
+		nchunks = 1 if cks is None else (nks + cks - 1) // cks
+		planes = torch.empty((nchunks * one, ), dtype=torch.uint8, **where)
+		return cls(planes, torch.empty((rows_pad, ), dtype=torch.int32, **where), torch.empty((rows_pad, FIX_STRIDE), dtype=torch.float64, **where), nslices, k_pad,
+				   chunks=None if cks is None else [planes[c * one:(c + 1) * one] for c in range(nchunks)], cks=cks)
+
+	@staticmethod
+	def chunk_ksteps(k_pad, chunks):
+		"""k-steps per chunk when rows of k_pad cells are cut into (at most) `chunks` cell chunks of equal size."""
+		nks = (k_pad + 31) // 32
+		return (nks + max(1, chunks) - 1) // max(1, chunks)
+
+	def plane_offset(self, lo):
+		"""Byte offset of row lo (a multiple of 32) inside every plane."""
+		return plane_bytes(lo, self.nks)
+
+	def row_block(self, lo, hi):
+		"""Rows [lo, hi) as views: every plane (of every chunk) from the block's first byte on, read through the pitch of the operand the rows lie in."""
+		first = self.plane_offset(lo)
+		return Digits(None if self.chunks is not None else self.planes[first:], self.exps[lo:hi], self.fix[lo:hi], self.nslices, self.k_pad, self.pitch or self.plane_bytes,
+					  None if self.chunks is None else [t[first:] for t in self.chunks], self.cks)
+
+
+class Residualized:
+	"""Residualised rows resident in HBM -- as fp64 (`data`) and / or in the fixed-point form of the integer Gram engine (`digits`, a Digits; None when
+	the rows exist only as fp64) -- plus their sums of squares and OLS coefficients."""
+
+	def __init__(self, rows, n, data, ss, coef, shape=None, digits=None):
 		self.rows, self.n = rows, n
-		self.data, self.ss, self.coef = data, ss, coef
+		self.data, self.ss, self.coef, self.digits = data, ss, coef, digits
 		self.rows_pad, self.k_pad = data.shape if shape is None else shape
-		self.cks = None  # chunked digit planes: k-steps (32 cells) per chunk; _quant[0] is then the list of chunk operands
-		self.fix = None  # (rows_pad, FIX_STRIDE) fp64 row records written next to the digit planes
+
+	@property
+	def fix(self):
+		"""The row records written next to the digit planes; None without digits."""
+		return None if self.digits is None else self.digits.fix
+
+	def row_block(self, lo, hi, rows=None):
+		"""Rows [lo, hi) (multiples of ROW_TILE) as an operand of their own: a view, nothing is copied."""
+		assert lo % ROW_TILE == 0 and hi % ROW_TILE == 0 and 0 <= lo < hi <= self.rows_pad
+		return Residualized(max(0, min(hi, self.rows) - lo) if rows is None else rows, self.n, None if self.data is None else self.data[lo:hi],
+							None if self.ss is None else self.ss[lo:hi], None, shape=(hi - lo, self.k_pad), digits=None if self.digits is None else self.digits.row_block(lo, hi))
+
+	def reusable(self, rows, n, rows_pad, k_pad, nslices, cks=None):
+		"""A K1 call of this shape that keeps no fp64 rows and no coefficients can overwrite these buffers."""
+		q = self.digits
+		return (q is not None and self.data is None and self.coef is None and q.planes is not None and not q.pitch
+				and (self.rows, self.n, self.rows_pad, self.k_pad, q.nslices, q.cks) == (rows, n, rows_pad, k_pad, nslices, cks))
 
 
 class Engine:
@@ -201,6 +276,18 @@ class Engine:
 
 	def _stream(self):
 		return self.torch.cuda.current_stream(self.device).cuda_stream
+
+	def _gram_ws(self):
+		"""Device address of K2's workspace, allocated at the first call."""
+		if self._gram_work is None:
+			self._gram_work = self.torch.empty((int(self.lib.nrm_gram_workspace_bytes()) // 8, ), dtype=self.torch.float64, device=self.device)
+		return self._gram_work.data_ptr()
+
+	def copy_stream(self):
+		"""The engine's stream for uploads and copy-outs beside the kernels, made at the first call."""
+		if self._copy is None:
+			self._copy = self.torch.cuda.Stream(device=self.device)
+		return self._copy
 
 	@serialised
 	def upload(self, a, dtype=None):
@@ -336,16 +423,32 @@ class Engine:
 		with _Span(self, 'residualize'):
 			return self._residualize(x, d_c, d_dci, rank, want_coef, rows_pad, nslices, keep_fp64, into)
 
-	@staticmethod
-	def _reusable(into, rows, n, rp, kp, nslices, plane_bytes, chunked):
-		q = getattr(into, '_quant', None)
-		if into is None or q is None or into.data is not None or into.coef is not None or into.fix is None:
-			return False
-		planes = q[0]
-		if chunked != isinstance(planes, list):
-			return False
-		have = sum(int(t.numel()) for t in planes) if chunked else int(planes.numel())
-		return (into.rows, into.n, into.rows_pad, into.k_pad, q[2]) == (rows, n, rp, kp, nslices) and have == plane_bytes
+	def empty_operand(self, rows, n, nslices, rows_pad=None, chunks=None):
+		"""Unwritten whole-matrix operand of the integer engine for `rows` rows of n cells (ss and digits; no fp64 rows): what K1 fills, at once or block
+		by block (residualize_into)."""
+		torch = self.torch
+		rp = round_up(max(rows, 1), ROW_TILE) if rows_pad is None else rows_pad
+		kp = round_up(n, K_TILE)
+		return Residualized(rows, n, None, torch.empty((rp, ), dtype=torch.float64, device=self.device), None, shape=(rp, kp),
+							digits=Digits.empty(rp, kp, nslices, chunks, device=self.device))
+
+	def _k1_q(self, x, d_c, d_dci, rank, r, rows_pad, row0, pitch):
+		"""nrm_residualize_q of x into rows [row0, row0 + rows_pad) of r: the one place that spells the call and addresses a row block of an operand."""
+		q = r.digits
+		_lib.check(self.lib.nrm_residualize_q(
+			x.data_ptr(), dtype_code(x), x.shape[0], x.shape[1], x.stride(0), ptr(d_c), 0 if d_c is None else d_c.shape[0], 0 if d_c is None else d_c.stride(0),
+			ptr(d_dci), int(rank), ptr(r.data), r.k_pad, rows_pad, r.ss.data_ptr() + row0 * 8, ptr(r.coef), q.nslices, q.planes.data_ptr() + q.plane_offset(row0),
+			q.exps.data_ptr() + row0 * 4, pitch, self.cmax_ptr(d_c), q.fix.data_ptr() + row0 * FIX_STRIDE * 8, self._stream()))
+
+	@serialised
+	def residualize_into(self, whole, row0, x, d_c, d_dci, rank):
+		"""K1 on the device matrix x, residualised and quantised into rows [row0, row0 + rows of x, padded to ROW_TILE) of the whole-matrix operand
+		`whole` (empty_operand) through its plane pitch: the resident coex paths, whose rows arrive block by block."""
+		assert row0 % ROW_TILE == 0 and whole.data is None and whole.coef is None and whole.digits.cks is None and not whole.digits.pitch
+		rp = round_up(x.shape[0], ROW_TILE)
+		assert x.shape[1] == whole.n and row0 + rp <= whole.rows_pad
+		with self.torch.cuda.device(self.device):
+			self._k1_q(x, d_c, d_dci, rank, whole, rp, row0, whole.digits.plane_bytes)
 
 	def _residualize(self, x, d_c, d_dci, rank, want_coef, rows_pad, nslices, keep_fp64, into=None):
 		torch = self.torch
@@ -356,36 +459,18 @@ class Engine:
 			nc = 0 if d_c is None else d_c.shape[0]
 			rp = round_up(max(rows, 1), ROW_TILE) if rows_pad is None else rows_pad
 			kp = round_up(n, K_TILE)
-			esz = x.element_size()
-			fused = bool(nslices) and rp % ROW_TILE == 0 and self.k1_quantises(x, d_c)
-			if fused:
-				coef = self.zeros((rows, nc), torch.float64) if want_coef else None
-				out = torch.empty((rp, kp), dtype=torch.float64, device=self.device) if keep_fp64 else None
-				pb = int(self.lib.nrm_quant_bytes(rp, kp, nslices))
-				if not keep_fp64 and not want_coef and self._reusable(into, rows, n, rp, kp, nslices, pb, False):
-					ss, planes, exps, fix = into.ss, into._quant[0], into._quant[1], into.fix
-				else:
-					ss = torch.empty((rp, ), dtype=torch.float64, device=self.device)
-					planes = torch.empty((pb, ), dtype=torch.uint8, device=self.device)
-					exps = torch.empty((rp, ), dtype=torch.int32, device=self.device)
-					fix = torch.empty((rp, FIX_STRIDE), dtype=torch.float64, device=self.device)
-				_lib.check(self.lib.nrm_residualize_q(
-					x.data_ptr(), NRM_F64 if x.dtype == torch.float64 else NRM_F32, rows, n, x.stride(0),
-					0 if d_c is None else d_c.data_ptr(), nc, 0 if d_c is None else d_c.stride(0),
-					0 if d_dci is None else d_dci.data_ptr(), int(rank), 0 if out is None else out.data_ptr(), kp, rp, ss.data_ptr(),
-					0 if coef is None else coef.data_ptr(), nslices, planes.data_ptr(), exps.data_ptr(), 0, self.cmax_ptr(d_c), fix.data_ptr(), self._stream()))
-				r = Residualized(rows, n, out, ss, coef, shape=(rp, kp))
-				r._quant = (planes, exps, nslices)
-				r.fix = fix
+			coef = self.zeros((rows, nc), torch.float64) if want_coef else None
+			if nslices and rp % ROW_TILE == 0 and self.k1_quantises(x, d_c):  # K1 writes the digits itself
+				lean = not keep_fp64 and not want_coef
+				r = into if lean and into is not None and into.reusable(rows, n, rp, kp, nslices) else self.empty_operand(rows, n, nslices, rp)
+				r.data, r.coef = torch.empty((rp, kp), dtype=torch.float64, device=self.device) if keep_fp64 else None, coef
+				self._k1_q(x, d_c, d_dci, rank, r, rp, 0, 0)
 				return r
 			out = torch.empty((rp, kp), dtype=torch.float64, device=self.device)
 			ss = torch.empty((rp, ), dtype=torch.float64, device=self.device)
-			coef = self.zeros((rows, nc), torch.float64) if want_coef else None
 			_lib.check(self.lib.nrm_residualize(
-				x.data_ptr(), NRM_F64 if x.dtype == torch.float64 else NRM_F32, rows, n, x.stride(0),
-				0 if d_c is None else d_c.data_ptr(), nc, 0 if d_c is None else d_c.stride(0),
-				0 if d_dci is None else d_dci.data_ptr(), int(rank),
-				out.data_ptr(), kp, rp, ss.data_ptr(), 0 if coef is None else coef.data_ptr(), self._stream()))
+				x.data_ptr(), dtype_code(x), rows, n, x.stride(0), ptr(d_c), nc, 0 if d_c is None else d_c.stride(0), ptr(d_dci), int(rank),
+				out.data_ptr(), kp, rp, ss.data_ptr(), ptr(coef), self._stream()))
 		return Residualized(rows, n, out, ss, coef)
 
 	@staticmethod
@@ -399,32 +484,15 @@ class Engine:
 		"""K1 with the digit planes cut along the cells into (at most) `chunks` operands of equal size that share the row
 		exponents (nrm_residualize_q_chunked): what the sharded coex path sends to the other GPUs piece by piece.
 		into: see residualize."""
-		torch = self.torch
-		with torch.cuda.device(self.device):
+		with self.torch.cuda.device(self.device):
 			rows, n = x.shape
-			nc = 0 if d_c is None else d_c.shape[0]
 			kp = round_up(n, K_TILE)
-			nks = (kp + 31) // 32
-			cks = (nks + max(1, chunks) - 1) // max(1, chunks)
-			nchunks = (nks + cks - 1) // cks
-			cb = int(self.lib.nrm_quant_bytes(rows_pad, 32 * cks, nslices))
-			if self._reusable(into, rows, n, rows_pad, kp, nslices, nchunks * cb, True) and into.cks == cks and getattr(into, '_planes', None) is not None:
-				planes, exps, ss, fix = into._planes, into._quant[1], into.ss, into.fix
-			else:
-				planes = torch.empty((nchunks * cb, ), dtype=torch.uint8, device=self.device)
-				exps = torch.empty((rows_pad, ), dtype=torch.int32, device=self.device)
-				ss = torch.empty((rows_pad, ), dtype=torch.float64, device=self.device)
-				fix = torch.empty((rows_pad, FIX_STRIDE), dtype=torch.float64, device=self.device)
+			cks = Digits.chunk_ksteps(kp, chunks)
+			r = into if into is not None and into.reusable(rows, n, rows_pad, kp, nslices, cks) else self.empty_operand(rows, n, nslices, rows_pad, chunks)
+			q = r.digits
 			_lib.check(self.lib.nrm_residualize_q_chunked(
-				x.data_ptr(), NRM_F64 if x.dtype == torch.float64 else NRM_F32, rows, n, x.stride(0),
-				0 if d_c is None else d_c.data_ptr(), nc, 0 if d_c is None else d_c.stride(0),
-				0 if d_dci is None else d_dci.data_ptr(), int(rank), rows_pad, ss.data_ptr(), nslices, planes.data_ptr(), exps.data_ptr(),
-				cks, self.cmax_ptr(d_c), fix.data_ptr(), self._stream()))
-		r = Residualized(rows, n, None, ss, None, shape=(rows_pad, kp))
-		r._quant = ([planes[c * cb:(c + 1) * cb] for c in range(nchunks)], exps, nslices)
-		r._planes = planes  # (the one buffer the chunk operands are views of)
-		r.cks = cks
-		r.fix = fix
+				x.data_ptr(), dtype_code(x), rows, n, x.stride(0), ptr(d_c), 0 if d_c is None else d_c.shape[0], 0 if d_c is None else d_c.stride(0),
+				ptr(d_dci), int(rank), rows_pad, r.ss.data_ptr(), nslices, q.planes.data_ptr(), q.exps.data_ptr(), q.cks, self.cmax_ptr(d_c), q.fix.data_ptr(), self._stream()))
 		return r
 
 	@serialised
@@ -434,14 +502,11 @@ class Engine:
 		with torch.cuda.device(self.device):
 			if dot is None:
 				dot = torch.empty((a.rows_pad, b.rows_pad), dtype=torch.float64, device=self.device)
-			if self._gram_work is None:
-				self._gram_work = torch.empty((int(self.lib.nrm_gram_workspace_bytes()) // 8, ), dtype=torch.float64, device=self.device)
-			qa, qb = a._quant, b._quant
-			assert a.cks is not None and a.cks == b.cks and qa[2] == qb[2]
-			pitch = lambda q: q[3] if len(q) > 3 else 0
-			_lib.check(self.lib.nrm_gram_i8_chunk(qa[0][chunk].data_ptr(), qa[1].data_ptr(), pitch(qa), qb[0][chunk].data_ptr(), qb[1].data_ptr(), pitch(qb),
-												  a.rows_pad, b.rows_pad, 32 * a.cks, qa[2], dot.data_ptr(), dot.stride(0), 1 if symmetric else 0,
-												  int(a.rows), int(b.rows), 1 if accumulate else 0, 0, 0, 0, 1, self._gram_work.data_ptr(), self._stream()))
+			qa, qb = a.digits, b.digits
+			assert qa.cks is not None and qa.cks == qb.cks and qa.nslices == qb.nslices
+			_lib.check(self.lib.nrm_gram_i8_chunk(qa.chunks[chunk].data_ptr(), qa.exps.data_ptr(), qa.pitch, qb.chunks[chunk].data_ptr(), qb.exps.data_ptr(), qb.pitch,
+												  a.rows_pad, b.rows_pad, 32 * qa.cks, qa.nslices, dot.data_ptr(), dot.stride(0), 1 if symmetric else 0,
+												  int(a.rows), int(b.rows), 1 if accumulate else 0, 0, 0, 0, 1, self._gram_ws(), self._stream()))
 		return dot
 
 	@serialised
@@ -454,14 +519,11 @@ class Engine:
 			world, rp = g_exps.shape
 			if dot is None:
 				dot = torch.empty((a.rows_pad, count * rp), dtype=torch.float64, device=self.device)
-			if self._gram_work is None:
-				self._gram_work = torch.empty((int(self.lib.nrm_gram_workspace_bytes()) // 8, ), dtype=torch.float64, device=self.device)
-			qa = a._quant
-			pitch = lambda q: q[3] if len(q) > 3 else 0
-			_lib.check(self.lib.nrm_gram_i8_chunk(qa[0][chunk].data_ptr(), qa[1].data_ptr(), pitch(qa), g_chunk.data_ptr(), g_exps.data_ptr(), 0,
-												  a.rows_pad, count * rp, 32 * a.cks, qa[2], dot.data_ptr(), dot.stride(0), 0, int(a.rows), 0,
+			qa = a.digits
+			_lib.check(self.lib.nrm_gram_i8_chunk(qa.chunks[chunk].data_ptr(), qa.exps.data_ptr(), qa.pitch, g_chunk.data_ptr(), g_exps.data_ptr(), 0,
+												  a.rows_pad, count * rp, 32 * qa.cks, qa.nslices, dot.data_ptr(), dot.stride(0), 0, int(a.rows), 0,
 												  1 if accumulate else 0, rp, g_chunk.stride(0) * g_chunk.element_size(), int(first), int(world),
-												  self._gram_work.data_ptr(), self._stream()))
+												  self._gram_ws(), self._stream()))
 		return dot
 
 	I8_MIN_CELLS = 2048
@@ -482,10 +544,10 @@ class Engine:
 	def fix_args(self, rx, ry):
 		"""(digit planes, row records of the x rows, of the y rows, guard tolerance) for the sweep of a dot product the integer engine
 		made from rx and ry; zeros for the fp64 Gram kernels."""
-		fx, fy = getattr(rx, 'fix', None), getattr(ry, 'fix', None)
-		if fx is None or fy is None or _opts.debug('i8_fix', '1') == '0':  # (the switch exists for the tests that show what the records are for)
+		qx, qy = getattr(rx, 'digits', None), getattr(ry, 'digits', None)
+		if qx is None or qy is None or _opts.debug('i8_fix', '1') == '0':  # (the switch exists for the tests that show what the records are for)
 			return 0, 0, 0, 0.0
-		return int(rx._quant[2]), fx.data_ptr(), fy.data_ptr(), float(self.guard_tol)
+		return qx.nslices, qx.fix.data_ptr(), qy.fix.data_ptr(), float(self.guard_tol)
 
 	def new_flags(self):
 		"""int32[4] device counters of a call: non-finite, R^2 > 1 + 1e-8 (association.py:248,252), guard hits, largest guard estimate."""
@@ -495,35 +557,18 @@ class Engine:
 	def quantized(self, r, nslices):
 		"""Fixed-point digit planes and row exponents of residualised rows (cached on the Residualized object; written by K1
 		itself when it could, see residualize)."""
-		torch = self.torch
-		q = getattr(r, '_quant', None)
-		if q is None or q[2] != nslices:
+		q = r.digits
+		if q is None or q.nslices != nslices:
 			assert r.data is not None, 'no fp64 residuals to quantise'  # (keep_fp64=False rows carry their digit planes)
-			with torch.cuda.device(self.device):
-				planes = torch.empty((int(self.lib.nrm_quant_bytes(r.rows_pad, r.k_pad, nslices)), ), dtype=torch.uint8, device=self.device)
-				exps = torch.empty((r.rows_pad, ), dtype=torch.int32, device=self.device)
-				fix = torch.empty((r.rows_pad, FIX_STRIDE), dtype=torch.float64, device=self.device)
-				_lib.check(self.lib.nrm_quantize_rows(r.data.data_ptr(), r.rows_pad, r.k_pad, r.data.stride(0), nslices, planes.data_ptr(),
-													  exps.data_ptr(), fix.data_ptr(), int(r.n), self._stream()))
-			q = (planes, exps, nslices)
-			r._quant = q
-			r.fix = fix
+			with self.torch.cuda.device(self.device):
+				q = Digits.empty(r.rows_pad, r.k_pad, nslices, device=self.device)
+				_lib.check(self.lib.nrm_quantize_rows(r.data.data_ptr(), r.rows_pad, r.k_pad, r.data.stride(0), nslices, q.planes.data_ptr(),
+													  q.exps.data_ptr(), q.fix.data_ptr(), int(r.n), self._stream()))
+			r.digits = q
 		return q
 
 	def row_block(self, r, lo, hi, rows=None):
-		"""Rows [lo, hi) (multiples of ROW_TILE) of residualised rows as an operand of their own: a view, nothing is copied."""
-		assert lo % ROW_TILE == 0 and hi % ROW_TILE == 0 and 0 <= lo < hi <= r.rows_pad
-		sub = Residualized(max(0, min(hi, r.rows) - lo) if rows is None else rows, r.n, None if r.data is None else r.data[lo:hi],
-						   None if r.ss is None else r.ss[lo:hi], None, shape=(hi - lo, r.k_pad))
-		q = getattr(r, '_quant', None)
-		if q is not None:
-			nks = (r.k_pad + 31) // 32 if r.cks is None else r.cks
-			dense = (r.rows_pad // 32) * nks * 1024
-			first = (lo // 32) * nks * 1024
-			sub._quant = (q[0][first:] if r.cks is None else [t[first:] for t in q[0]], q[1][lo:hi], q[2], q[3] if len(q) > 3 else dense)
-			sub.cks = r.cks
-			sub.fix = None if r.fix is None else r.fix[lo:hi]
-		return sub
+		return r.row_block(lo, hi, rows)
 
 	@serialised
 	def gram(self, a, b, symmetric, dot=None, rows=None, nslices=0):
@@ -538,21 +583,18 @@ class Engine:
 		with torch.cuda.device(self.device):
 			if dot is None:
 				dot = torch.empty((a.rows_pad, b.rows_pad), dtype=torch.float64, device=self.device)
-			if self._gram_work is None:
-				self._gram_work = torch.empty((int(self.lib.nrm_gram_workspace_bytes()) // 8, ), dtype=torch.float64, device=self.device)
 			row0, row1 = (0, a.rows_pad) if rows is None else rows
 			if nslices:
 				qa = self.quantized(a, nslices)
 				qb = qa if b is a else self.quantized(b, nslices)
-				pitch = lambda q: q[3] if len(q) > 3 else 0  # plane pitch of a row block of a larger quantised matrix (0 = dense)
-				_lib.check(self.lib.nrm_gram_i8_band(qa[0].data_ptr(), qa[1].data_ptr(), pitch(qa), qb[0].data_ptr(), qb[1].data_ptr(), pitch(qb),
+				_lib.check(self.lib.nrm_gram_i8_band(qa.planes.data_ptr(), qa.exps.data_ptr(), qa.pitch, qb.planes.data_ptr(), qb.exps.data_ptr(), qb.pitch,
 													 a.rows_pad, b.rows_pad, a.k_pad, nslices, dot.data_ptr(), dot.stride(0), 1 if symmetric else 0,
-													 int(a.rows), int(b.rows), int(row0), int(row1), self._gram_work.data_ptr(), self._stream()))
+													 int(a.rows), int(b.rows), int(row0), int(row1), self._gram_ws(), self._stream()))
 				return dot
 			_lib.check(self.lib.nrm_gram_f64_band(a.data.data_ptr(), b.data.data_ptr(), a.rows_pad, b.rows_pad, a.k_pad,
 												  a.data.stride(0), b.data.stride(0), dot.data_ptr(), dot.stride(0),
 												  1 if symmetric else 0, int(a.rows), int(b.rows), int(row0), int(row1),
-												  self._gram_work.data_ptr(), self._stream()))
+												  self._gram_ws(), self._stream()))
 		return dot
 
 	BAND = 8 * ROW_TILE  # rows per band of the pipelined path (one row of K2's 8x8 super-blocks)
@@ -584,8 +626,7 @@ class Engine:
 		rows = max(ROW_TILE, (self.CHUNK_BYTES // (n * dy.itemsize)) // ROW_TILE * ROW_TILE)
 		with torch.cuda.device(self.device):
 			main = torch.cuda.current_stream(self.device)
-			if self._copy is None:
-				self._copy = torch.cuda.Stream(device=self.device)
+			self.copy_stream()
 			d_c, d_dci = self.covariates(dc, dci) if cov is None else cov
 			rx = self.residualize(dx, d_c, d_dci, rank, nslices=self.gram_slices(n))
 			p = torch.empty((nx, ny), dtype=tdt, device=self.device)
@@ -658,8 +699,7 @@ class Engine:
 		cuts = list(range(0, nx, self.BAND)) + [nx]
 		with torch.cuda.device(self.device):
 			main = torch.cuda.current_stream(self.device)
-			if self._copy is None:
-				self._copy = torch.cuda.Stream(device=self.device)
+			self.copy_stream()
 			odt = np.dtype(out_dtype)
 			hp, hs, th = host['p'], host['stat'], host['thread']
 			try:
@@ -713,9 +753,6 @@ class Engine:
 		tdt = torch.float64 if odt == np.float64 else torch.float32
 		code = dtype_code(out_dtype)
 		esz = odt.itemsize
-		mp, kp = round_up(ng, ROW_TILE), round_up(n, K_TILE)
-		nks = (kp + 31) // 32
-		plane = (mp // 32) * nks * 1024
 		cuts = list(range(0, ng, self.BAND)) + [ng]
 		import time
 		trace = [] if _opts.debug('trace') else None
@@ -723,22 +760,15 @@ class Engine:
 		mark('start')
 		with torch.cuda.device(self.device):
 			main = torch.cuda.current_stream(self.device)
-			if self._copy is None:
-				self._copy = torch.cuda.Stream(device=self.device)
+			self.copy_stream()
 			if getattr(self, '_copy_out', None) is None:
 				self._copy_out = torch.cuda.Stream(device=self.device)
 			d_c, d_dci = self.covariates(dc, dci) if cov is None else cov
-			nc = 0 if d_c is None else d_c.shape[0]
-			planes = torch.empty((plane * ns, ), dtype=torch.uint8, device=self.device)
-			exps = torch.empty((mp, ), dtype=torch.int32, device=self.device)
-			ss = torch.empty((mp, ), dtype=torch.float64, device=self.device)
-			fixt = torch.empty((mp, FIX_STRIDE), dtype=torch.float64, device=self.device)
+			whole = self.empty_operand(ng, n, ns)
+			ss = whole.ss
 			p = torch.empty((ng, ng), dtype=tdt, device=self.device)
 			stat = torch.empty((ng, ng), dtype=tdt, device=self.device)
 			flags = self.new_flags()
-			whole = Residualized(ng, n, None, ss, None, shape=(mp, kp))
-			whole._quant = (planes, exps, ns)
-			whole.fix = fixt
 			host = None
 			pending = []
 			row = ng * esz
@@ -806,11 +836,7 @@ class Engine:
 					if host is None:  # page-lock the result arrays from a helper thread, started after the first upload (see association_single0)
 						host = self.start_host_results(ng, ng, out_dtype, bands=cuts)
 					rpc = round_up(b - a, ROW_TILE)
-					_lib.check(self.lib.nrm_residualize_q(
-						xc.data_ptr(), NRM_F64 if xc.dtype == torch.float64 else NRM_F32, b - a, n, xc.stride(0),
-						0 if d_c is None else d_c.data_ptr(), nc, 0 if d_c is None else d_c.stride(0), 0 if d_dci is None else d_dci.data_ptr(), int(rank),
-						0, kp, rpc, ss.data_ptr() + a * 8, 0, ns, planes.data_ptr() + (a // 32) * nks * 1024, exps.data_ptr() + a * 4, plane, self.cmax_ptr(d_c),
-						fixt.data_ptr() + a * FIX_STRIDE * 8, self._stream()))
+					self.residualize_into(whole, a, xc, d_c, d_dci, rank)
 					blk = self.row_block(whole, a, a + rpc, rows=b - a)
 					dot = self.gram(blk, blk, True, nslices=ns)
 					_lib.check(self.lib.nrm_assoc_sweep(dot.data_ptr(), dot.stride(0), blk.ss.data_ptr(), blk.ss.data_ptr(), b - a, b - a, int(n), float(dof), 1, 0,
@@ -862,9 +888,6 @@ class Engine:
 		dof = n - 1 - rank - dimreduce
 		odt = np.dtype(out_dtype)
 		tdt = torch.float64 if odt == np.float64 else torch.float32
-		mp, kp = round_up(n_genes, ROW_TILE), round_up(n, K_TILE)
-		nks = (kp + 31) // 32
-		plane = (mp // 32) * nks * 1024
 		with torch.cuda.device(self.device):
 			ev = lambda: torch.cuda.Event(enable_timing=True)
 			marks = []
@@ -875,26 +898,15 @@ class Engine:
 					e.record()
 					marks.append((name, e))
 			d_c, d_dci = self.covariates(dc, dci)
-			nc = 0 if d_c is None else d_c.shape[0]
-			planes = torch.empty((plane * ns, ), dtype=torch.uint8, device=self.device)
-			exps = torch.empty((mp, ), dtype=torch.int32, device=self.device)
-			ss = torch.empty((mp, ), dtype=torch.float64, device=self.device)
-			fixt = torch.empty((mp, FIX_STRIDE), dtype=torch.float64, device=self.device)
-			whole = Residualized(n_genes, n, None, ss, None, shape=(mp, kp))
-			whole._quant = (planes, exps, ns)
-			whole.fix = fixt
+			whole = self.empty_operand(n_genes, n, ns)
+			ss, mp = whole.ss, whole.rows_pad
 			mark('start')
 			for a in range(0, n_genes, block_rows):
 				b = min(n_genes, a + block_rows)
 				x = block_fn(a, b)
 				assert tuple(x.shape) == (b - a, n) and self.k1_quantises(x, d_c)
-				rpc = round_up(b - a, ROW_TILE)
 				with _Span(self, 'residualize'):
-					_lib.check(self.lib.nrm_residualize_q(
-						x.data_ptr(), NRM_F64 if x.dtype == torch.float64 else NRM_F32, b - a, n, x.stride(0),
-						0 if d_c is None else d_c.data_ptr(), nc, 0 if d_c is None else d_c.stride(0), 0 if d_dci is None else d_dci.data_ptr(), int(rank),
-						0, kp, rpc, ss.data_ptr() + a * 8, 0, ns, planes.data_ptr() + (a // 32) * nks * 1024, exps.data_ptr() + a * 4, plane, self.cmax_ptr(d_c),
-						fixt.data_ptr() + a * FIX_STRIDE * 8, self._stream()))
+					self.residualize_into(whole, a, x, d_c, d_dci, rank)
 				torch.cuda.current_stream(self.device).synchronize()  # the block is released before the next one is made
 				del x
 			mark('residualised')

@@ -180,9 +180,9 @@ def test_k1_grid_against_longdouble(case):
 	assert (r.rows_pad, r.k_pad) == (k1.round_up(rows, 128), k1.round_up(n, 16))
 	if fused:
 		g = k1.geometry(n, r.rows_pad, ns)
-		assert r._quant[0].numel() == g['total']
-		dev.update(geo=g, planes=np.append(r._quant[0].cpu().numpy().view(np.int8), np.full(1024, 0x5A, dtype=np.int8)), pitch=0, first=0,
-				   exps=np.append(r._quant[1].cpu().numpy(), np.int32(EXP_SENTINEL)), fix=np.vstack([r.fix.cpu().numpy(), np.full((1, 8), np.nan)]))
+		assert r.digits.planes.numel() == g['total']
+		dev.update(geo=g, planes=np.append(r.digits.planes.cpu().numpy().view(np.int8), np.full(1024, 0x5A, dtype=np.int8)), pitch=0, first=0,
+				   exps=np.append(r.digits.exps.cpu().numpy(), np.int32(EXP_SENTINEL)), fix=np.vstack([r.fix.cpu().numpy(), np.full((1, k1.FIX_STRIDE), np.nan)]))
 	check(dev, ref, 'v4' if aligned else 'scalar', cid + ' (engine)')
 
 
@@ -228,7 +228,7 @@ def test_k1_exponent_paths(ns):
 		assert (eng.cmax_ptr(d_c) != 0) == cmax
 		r = eng.residualize(xd, d_c, d_dci, rank, nslices=ns, keep_fp64=True)
 		_, true_sh = model.quantise(r.data.cpu().numpy()[:16], ns)
-		assert np.array_equal(r._quant[1].cpu().numpy()[:16].astype(np.int64), true_sh + (np.arange(16) < 4) if cmax else true_sh)
+		assert np.array_equal(r.digits.exps.cpu().numpy()[:16].astype(np.int64), true_sh + (np.arange(16) < 4) if cmax else true_sh)
 
 
 # ---- the same bits in every form ------------------------------------------------------------------------------------------------------------------------------------------
@@ -247,28 +247,28 @@ def test_k1_same_bits_across_forms(dtype, ns):
 	full = eng.residualize(xd, d_c, d_dci, rank, nslices=ns, keep_fp64=True)
 	g = k1.geometry(2050, 128, ns)
 	pack = lambda r: dict(rows=33, n=2050, rows_pad=128, ns=ns, kp=2064, geo=g, pitch=0, first=0, coef=None, out=None, ss=np.append(r.ss.cpu().numpy(), np.nan),
-						  planes=np.append(r._quant[0].cpu().numpy().view(np.int8), np.full(1024, 0x5A, dtype=np.int8)),
-						  exps=np.append(r._quant[1].cpu().numpy(), np.int32(EXP_SENTINEL)), fix=np.vstack([r.fix.cpu().numpy(), np.full((1, 8), np.nan)]))
+						  planes=np.append(r.digits.planes.cpu().numpy().view(np.int8), np.full(1024, 0x5A, dtype=np.int8)),
+						  exps=np.append(r.digits.exps.cpu().numpy(), np.int32(EXP_SENTINEL)), fix=np.vstack([r.fix.cpu().numpy(), np.full((1, k1.FIX_STRIDE), np.nan)]))
 	base = pack(full)
 	base['out'] = np.vstack([full.data.cpu().numpy(), np.full((1, 2064), np.nan)])
 	check(base, ref, 'v4', 'forms %s ns%d' % (dtype, ns))
-	same = lambda r: (torch.equal(r.ss, full.ss) and torch.equal(r._quant[1], full._quant[1]) and torch.equal(r.fix, full.fix))
+	same = lambda r: (torch.equal(r.ss, full.ss) and torch.equal(r.digits.exps, full.digits.exps) and torch.equal(r.fix, full.fix))
 	lean = eng.residualize(xd, d_c, d_dci, rank, nslices=ns, keep_fp64=False)
-	assert lean.data is None and same(lean) and torch.equal(lean._quant[0], full._quant[0])
+	assert lean.data is None and same(lean) and torch.equal(lean.digits.planes, full.digits.planes)
 	check(pack(lean), ref, 'v4', 'forms %s ns%d keep_fp64=False' % (dtype, ns), out_of=base['out'][:128])
 	again = eng.residualize(xd, d_c, d_dci, rank, nslices=ns, keep_fp64=True)
-	assert same(again) and torch.equal(again._quant[0], full._quant[0]) and torch.equal(again.data, full.data)
+	assert same(again) and torch.equal(again.digits.planes, full.digits.planes) and torch.equal(again.data, full.data)
 	plain = eng.residualize(xd, d_c, d_dci, rank, nslices=0)
 	assert torch.equal(plain.data, full.data) and torch.equal(plain.ss, full.ss)
 	d_full = k1.decode_planes(base['planes'], ns, 128, g['nks'])
 	for chunks in (1, 2, 3):
 		ch = eng.residualize_chunked(xd, d_c, d_dci, rank, 128, ns, chunks)
 		gc = k1.geometry(2050, 128, ns, chunks)
-		assert ch.cks == gc['cks'] and len(ch._quant[0]) == gc['nchunks'] == chunks and ch._planes.numel() == gc['total'] and same(ch)
-		d = k1.decode_planes(ch._planes.cpu().numpy(), ns, 128, gc['nchunks'] * gc['cks'], gc['cks'])
+		assert ch.digits.cks == gc['cks'] and len(ch.digits.chunks) == gc['nchunks'] == chunks and ch.digits.planes.numel() == gc['total'] and same(ch)
+		d = k1.decode_planes(ch.digits.planes.cpu().numpy(), ns, 128, gc['nchunks'] * gc['cks'], gc['cks'])
 		assert np.array_equal(d[:, :, :g['nks'] * 32], d_full) and not d[:, :, g['nks'] * 32:].any(), chunks
 		dev = run_k1(x, C64, dci, rank, ns, keep=False, chunks=chunks)  # (the direct entry into sentinel-filled buffers: every byte of every chunk is written)
-		assert np.array_equal(dev['planes'][:gc['total']], ch._planes.cpu().numpy().view(np.int8))
+		assert np.array_equal(dev['planes'][:gc['total']], ch.digits.planes.cpu().numpy().view(np.int8))
 		check(dev, ref, 'v4', 'forms %s ns%d %d chunks' % (dtype, ns, chunks), out_of=base['out'][:128])
 
 
@@ -288,20 +288,46 @@ def test_k1_row_block_equals_the_rows_alone(dtype, ns):
 	assert whole.rows_pad == 256 and alone.rows_pad == 128
 	blk = eng.row_block(whole, 128, 256)
 	g, gw = k1.geometry(n, 128, ns), k1.geometry(n, 256, ns)
-	assert blk.rows == 72 and blk._quant[3] == gw['plane_bytes']
-	d_alone = k1.decode_planes(alone._quant[0].cpu().numpy(), ns, 128, g['nks'])
-	d_blk = k1.decode_planes(blk._quant[0].cpu().numpy(), ns, 128, g['nks'], plane_pitch=blk._quant[3])
+	assert blk.rows == 72 and blk.digits.pitch == gw['plane_bytes']
+	d_alone = k1.decode_planes(alone.digits.planes.cpu().numpy(), ns, 128, g['nks'])
+	d_blk = k1.decode_planes(blk.digits.planes.cpu().numpy(), ns, 128, g['nks'], plane_pitch=blk.digits.pitch)
 	assert np.array_equal(d_blk, d_alone)
-	assert torch.equal(blk._quant[1], alone._quant[1]) and torch.equal(blk.ss, alone.ss) and torch.equal(blk.fix, alone.fix)
+	assert torch.equal(blk.digits.exps, alone.digits.exps) and torch.equal(blk.ss, alone.ss) and torch.equal(blk.fix, alone.fix)
 	ref = k1.reference(x[128:], C64, dci, rank)
 	dev = run_k1(x[128:], C64, dci, rank, ns, block=(128, 384))
 	check(dev, ref, 'v4', 'row block %s ns%d' % (dtype, ns))
 	assert np.array_equal(k1.decode_planes(dev['planes'], ns, 128, g['nks'], plane_pitch=dev['pitch'], offset=dev['first']), d_alone)
-	assert np.array_equal(dev['exps'][:128], alone._quant[1].cpu().numpy()) and np.array_equal(dev['ss'][:128], alone.ss.cpu().numpy())
+	assert np.array_equal(dev['exps'][:128], alone.digits.exps.cpu().numpy()) and np.array_equal(dev['ss'][:128], alone.ss.cpu().numpy())
 	assert np.array_equal(dev['fix'][:128], alone.fix.cpu().numpy()) and np.array_equal(dev['out'][:128], alone.data.cpu().numpy())
 	g3 = k1.geometry(n, 384, ns)
 	img = dev['planes'][:g3['total']].reshape(ns, 384 // 32, g3['nks'] * 1024)
 	assert (img[:, :4] == 0x5A).all() and (img[:, 8:] == 0x5A).all() and (img[:, 4:8] != 0x5A).any()
+
+
+@pytest.mark.parametrize('dtype,ns', [('float32', 6), ('float64', 5)])
+def test_k1_block_by_block_into_an_empty_operand_equals_one_call(dtype, ns):
+	"""The same 200 rows x 1026 cells as Engine.empty_operand (256 rows) filled by two Engine.residualize_into calls -- rows 0-127, then the ragged block
+	128-199 at a non-zero row-group offset, both through the whole operand's plane pitch -- against one Engine.residualize call: planes, exps, ss and
+	fix bit for bit, padding rows included (every byte of the sentinel-filled operand is written: K1 writes all rows_pad rows of a call)."""
+	torch, _lib, eng = _env()
+	n = 1026
+	x, C = k1.case_inputs((200, n, 2, dtype, ns))
+	C64, dci, rank = k1.prepare(C)
+	d_c, d_dci = eng.covariates(C64, dci)
+	xd, _ = _place(x, 1040)
+	once = eng.residualize(xd, d_c, d_dci, rank, nslices=ns, keep_fp64=False)
+	whole = eng.empty_operand(200, n, ns)
+	q = whole.digits
+	gw = k1.geometry(n, 256, ns)
+	assert (whole.rows, whole.n, whole.rows_pad, whole.k_pad, whole.data, whole.coef) == (200, n, 256, 1040, None, None)
+	assert (q.planes.numel(), q.plane_bytes, q.pitch, q.nslices, q.cks) == (gw['total'], gw['plane_bytes'], 0, ns, None)
+	q.planes.fill_(0x5A), q.exps.fill_(EXP_SENTINEL), q.fix.fill_(float('nan')), whole.ss.fill_(float('nan'))
+	eng.residualize_into(whole, 0, xd[:128], d_c, d_dci, rank)
+	img = q.planes.cpu().numpy().reshape(ns, 256 // 32, gw['nks'] * 1024)
+	assert (img[:, 4:] == 0x5A).all() and (q.exps[128:] == EXP_SENTINEL).all() and torch.isnan(whole.ss[128:]).all() and torch.isnan(q.fix[128:]).all(), 'written outside the block'
+	eng.residualize_into(whole, 128, xd[128:], d_c, d_dci, rank)
+	assert torch.equal(q.planes, once.digits.planes) and torch.equal(q.exps, once.digits.exps) and torch.equal(whole.ss, once.ss) and torch.equal(q.fix, once.digits.fix)
+	assert torch.equal(whole.fix, once.fix)
 
 
 # ---- the cell-parallel variant ----------------------------------------------------------------------------------------------------------------------------------------

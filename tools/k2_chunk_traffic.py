@@ -17,7 +17,7 @@ dot = torch.empty((rows, rows), dtype=torch.float64, device='cuda')
 eng.gram(a, a, False, dot=dot, nslices=6)
 torch.cuda.synchronize()
 ac = eng.residualize_chunked(x, d_c, d_dci, dcr, rows, 6, S)
-for c in range(len(ac._quant[0])):
+for c in range(len(ac.digits.chunks)):
 	eng.gram_chunk(ac, ac, False, c, dot, c > 0)
 torch.cuda.synchronize()
 print('done')

@@ -40,7 +40,7 @@ print('%d x %d rows, %d cells: one launch %.3f ms; K1 %.3f ms' % (rows, rows, n,
 for S in Ss:
 	ac = eng.residualize_chunked(x, d_c, d_dci, dcr, rp, 6, S)
 	bc = eng.residualize_chunked(y, d_c, d_dci, dcr, rp, 6, S)
-	nch = len(ac._quant[0])
+	nch = len(ac.digits.chunks)
 
 	def run():
 		for c in range(nch):
@@ -48,17 +48,17 @@ for S in Ss:
 	run()
 	err = ((dot[:rows, :rows] - ref[:rows, :rows]).abs().max() / ref[:rows, :rows].abs().max()).item()
 	tkc = timeit(lambda: eng.residualize_chunked(x, d_c, d_dci, dcr, rp, 6, S))
-	print('  %d chunks of %d k-steps: %.3f ms (%.2fx), K1 chunked %.3f ms, max rel diff %.1e' % (nch, ac.cks, timeit(run), timeit(run) / t1, tkc, err))
+	print('  %d chunks of %d k-steps: %.3f ms (%.2fx), K1 chunked %.3f ms, max rel diff %.1e' % (nch, ac.digits.cks, timeit(run), timeit(run) / t1, tkc, err))
 
 # all K full partner blocks of a rank in one launch per chunk (gram_chunk_blocks), as CoexPlan does from 5 ranks on
 K = 3
 print('merged: %d x (%d x %d) block pairs per launch' % (K, rows, rows))
 for S in Ss:
 	ac = eng.residualize_chunked(x, d_c, d_dci, dcr, rp, 6, S)
-	nch = len(ac._quant[0])
+	nch = len(ac.digits.chunks)
 	world = K + 1
-	g_chunks = [torch.stack([ac._quant[0][c]] * world) for c in range(nch)]
-	g_exps = torch.stack([ac._quant[1]] * world)
+	g_chunks = [torch.stack([ac.digits.chunks[c]] * world) for c in range(nch)]
+	g_exps = torch.stack([ac.digits.exps] * world)
 	md = torch.empty((rp, K * rp), dtype=torch.float64, device='cuda')
 
 	def runm():
