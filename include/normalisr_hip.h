@@ -582,6 +582,32 @@ int nrm_design_fill(const void* d_x, int x_dtype, int64_t nx, int64_t n, int64_t
 					const int64_t* d_base, const int64_t* d_row_ptr, const int32_t* d_coff, int16_t* d_ell, double* d_ellv, int32_t* d_cells,
 					double* d_row_vals, int binary, void* stream);
 /*
+ * The same lists from a design that is SPARSE already (csrc/nrm_design_csr.hip): the design side of association.py:224-235, and what association.py:914-918
+ * selects cells from, without the dense (groupings x cells) matrix anywhere.  The design is canonical CSR over its rows, in HBM: d_indptr (nx + 1) int64,
+ * d_indices int32 (the cell of every stored entry, strictly increasing inside a row), d_data (NRM_F32 / NRM_F64 by data_dtype) or NULL: every stored entry is 1.
+ * A stored zero is legal and is NOT an entry; a NaN is one (value != 0, as nrm_design_count counts).
+ *   nrm_design_csr_count: d_cnt (nch, nslots) exactly as nrm_design_count writes it for the same design given dense; d_info (int64[8]) is zeroed by the call.
+ *     It also checks the structure -- d_indptr[0] == 0, d_indptr[nx] == nnz, d_indptr does not decrease, every column lies in [0, n) and increases strictly
+ *     inside a row -- and sets d_info[NRM_DESIGN_CSR_BAD] (a slot neither nrm_design_plan nor nrm_single1_select writes) to non-zero for a violation.  Nothing
+ *     is addressed through an unchecked value: the row bounds are clamped to [0, nnz] and a column outside [0, n) is not used.  A malformed matrix is the
+ *     caller's error to report (its counts mean nothing): do not go on to fill.
+ *   nrm_design_plan as above, unchanged: it reads d_cnt only.
+ *   nrm_design_csr_fill: the second pass, for a matrix nrm_design_csr_count accepted.  d_cells / d_row_vals (the library's CSR form: stored zeros dropped)
+ *     and d_ell / d_ellv (padding included) as nrm_design_fill writes them, either of d_cells / d_ell may be NULL; no atomics: the same bits run to run.
+ *     d_coff is taken for the likeness of the two argument lists and not read.  Every store is checked against the sizes the plan allotted.
+ *   nrm_design_csr_dense: d_out (nx, ldo), NRM_F32 / NRM_F64 by out_dtype, is zeroed (padding too) and the stored entries are written into it -- for the
+ *     routes that read the design as a matrix.  For a matrix nrm_design_csr_count accepted; columns outside [0, n) are skipped.
+ * For every canonical CSR design every array these entries and nrm_design_plan produce is byte for byte what the dense entries produce from the densified matrix.
+ */
+#define NRM_DESIGN_CSR_BAD 5    /* index into d_info: non-zero for a malformed CSR design */
+int nrm_design_csr_count(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int data_dtype, int64_t nx, int64_t n, int64_t nnz,
+						 int32_t* d_cnt, int64_t nslots, int64_t* d_info, void* stream);
+int nrm_design_csr_fill(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int data_dtype, int64_t nx, int64_t n, int64_t nslots,
+						const int32_t* d_pos, const int32_t* d_w, const int64_t* d_base, const int64_t* d_row_ptr, const int32_t* d_coff, int16_t* d_ell,
+						double* d_ellv, int32_t* d_cells, double* d_row_vals, int binary, void* stream);
+int nrm_design_csr_dense(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int data_dtype, int64_t nx, int64_t n, void* d_out,
+						 int out_dtype, int64_t ldo, void* stream);
+/*
  * single=1's cell selection (association.py:914-918) for a design with entries >= 0, from its CSR form: cell k is selected for grouping i
  * when i's entry is the only one of the cell, and for every grouping when the cell has none.
  *   d_cnt (n) int32 scratch (entries per cell); d_code (n): the cell codes nrm_single1_stream reads; d_seg (nx + 1): grouping i owns the

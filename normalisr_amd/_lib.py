@@ -12,6 +12,7 @@ NRM_TSV_I64, NRM_TSV_I32, NRM_TSV_U8 = 16, 17, 18  # integer dtypes of nrm_tsv_f
 NRM_I64, NRM_I32, NRM_U8, NRM_I16 = 16, 17, 18, 19  # count dtypes of nrm_lcpm_*
 NRM_S1_COMMON, NRM_S1_SKIP = -2, -1  # cell codes of nrm_single1_stream (include/normalisr_hip.h)
 DESIGN_NOTONE, DESIGN_NEG, DESIGN_GT1, DESIGN_HAS1, DESIGN_NAN = 1, 2, 4, 8, 16  # bits of nrm_design_count's d_info[2]
+DESIGN_CSR_BAD = 5  # the slot of d_info nrm_design_csr_count flags a malformed CSR design in
 NRM_E_ARG, NRM_E_DEVICE, NRM_E_NUMERIC, NRM_E_UNSUPPORTED = -1, -2, -3, -4
 ROW_TILE, K_TILE, PCOEF, FIX_STRIDE = 128, 16, 20, 8
 
@@ -82,6 +83,9 @@ _SIGNATURES = {
 	'nrm_design_count': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp], _i32),
 	'nrm_design_plan': ([_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 	'nrm_design_fill': ([_vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
+	'nrm_design_csr_count': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp], _i32),
+	'nrm_design_csr_fill': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
+	'nrm_design_csr_dense': ([_vp, _vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _vp], _i32),
 	'nrm_single1_select_gram_blocks': ([], _i64),
 	'nrm_single1_select': ([_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 	'nrm_single1_common_gram': ([_vp, _i64, _vp, _i64, _i64, _vp, _vp], _i32),

@@ -372,6 +372,8 @@ def association_tests(dx, dy, dc, bsx=0, bsy=0, nth=1, lowmem=True, return_dot=T
 	With return_stats=True a sixth element {'r':..., 't':..., 'dof':...} is appended.  With device_out=True (single=0 only)
 	the two (n_x, n_y) matrices are returned as torch tensors resident in HBM (e.g. to feed binnet without crossing PCIe).
 	device=<index> runs the call on that GPU instead of the current one (also engine.use_device, NORMALISR_DEVICE).
+	dx may be sparse for single = 0, 1, 4 -- a scipy.sparse matrix, a de_sparse.DesignCSR, a torch.sparse_csr CUDA tensor -- with the results of the densified
+	matrix; dy and dc are dense.
 	"""
 	device = ka.pop('device', None)
 	if device is not None:
@@ -388,6 +390,21 @@ def association_tests(dx, dy, dc, bsx=0, bsy=0, nth=1, lowmem=True, return_dot=T
 		raise ValueError('Unknown value single={}'.format(single))
 	# dx / dy may be torch CUDA tensors already in HBM (what normvar(..., device_out=True) returns; a resident pipeline normvar -> coex -> binnet)
 	is_dev = lambda a: hasattr(a, 'is_cuda') and a.is_cuda
+	from . import de_sparse
+	de_sparse.refuse_sparse(dy, 'dy')
+	de_sparse.refuse_sparse(dc, 'dc')
+	if de_sparse.is_sparse_design(dx):
+		# a sparse design (scipy.sparse, de_sparse.DesignCSR, a torch.sparse_csr CUDA tensor) goes on as a DesignCSR in HBM: the routes that read entry lists take
+		# them from its entries, the others scatter it on the device (DesignCSR.dense()); the dense matrix is never formed on the host
+		if single == 5:
+			raise TypeError('single=5 takes a dense design: DesignCSR.dense() / toarray() give one.')
+		design = de_sparse.as_design_csr(dx)
+		if _use_host_entry():
+			# (the library's whole-problem entries take dense host buffers)
+			logging.debug('normalisr_amd: sparse design densified on the host for the whole-problem C entries.')
+			dx = dx.toarray() if design is None else design.dense().cpu().numpy()
+		else:
+			dx = design if design is not None else de_sparse.DesignCSR.from_scipy(dx)
 	if not is_dev(dx):
 		dx = np.asarray(dx)
 	dc = np.asarray(dc)

@@ -31,6 +31,114 @@ def _varying_rows(dg):
 	return varying
 
 
+def _full_row_varies(v):
+	"""Whether the values of a row with every cell set are not all equal (NaNs compare equal, as for np.unique)."""
+	return bool(((v != v[0]) & ~(np.isnan(v) & np.isnan(v[0]))).any())
+
+
+def _varying_rows_entries(k, n, full_varies):
+	"""_varying_rows from the entries of a sparse design: k[i] = non-zero entries of row i among n cells.  No entry: constant (all zeros); some cells
+	set, some not: two values; every cell set: full_varies(i) looks at the values."""
+	k = np.asarray(k)
+	varying = (k > 0) & (k < n)
+	for i in np.nonzero((k == n) & (n > 1))[0]:  # (the exceptional rows)
+		varying[i] = full_varies(int(i))
+	return varying
+
+
+def _varying_rows_scipy(m):
+	"""_varying_rows(m.toarray()) of a canonical scipy CSR matrix (no stored zeros, no duplicates) in O(stored entries)."""
+	ip = m.indptr
+	data = m.data if m.data.dtype.kind == 'f' else m.data.astype(np.float64)
+	return _varying_rows_entries(np.diff(ip), m.shape[1], lambda i: _full_row_varies(data[ip[i]:ip[i + 1]]))
+
+
+def _varying_rows_device(design):
+	"""_varying_rows of a DesignCSR (stored zeros are not entries): one read-back -- indptr and the non-zero entries before every row -- and, for a row with
+	every cell set, a torch min / max on its segment.  The structure is checked first (torch indexing does not clamp)."""
+	design.check()
+	import torch
+	ip = design.indptr.to(torch.int64)
+	if design.data is None:
+		h = ip.cpu().numpy()
+		k = np.diff(h)
+	else:
+		nz = torch.cat([torch.zeros(1, dtype=torch.int64, device=ip.device), torch.cumsum(design.data != 0, 0)])  # (NaN != 0: an entry)
+		h = torch.stack([ip, nz[ip]]).cpu().numpy()
+		k, h = np.diff(h[1]), h[0]
+
+	def full(i):
+		if design.data is None:
+			return False
+		v = design.data[int(h[i]):int(h[i + 1])]
+		v = v[v != 0].to(torch.float64)
+		nan = torch.isnan(v)
+		if bool(nan.any()):
+			return not bool(nan.all())
+		return bool(v.min() != v.max())
+	return _varying_rows_entries(k, design.shape[1], full), h
+
+
+def _device_rows(design, gid, h):
+	"""The rows gid (a boolean mask) of a DesignCSR as a new DesignCSR: a gather of the kept rows' segments on the device.  h: indptr on the host."""
+	import torch
+	from . import de_sparse
+	dev = design.indptr.device
+	lens = np.diff(h)[gid]
+	new_ip = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+	shift = torch.from_numpy((h[:-1][gid] - new_ip[:-1]).astype(np.int64)).to(dev)
+	src = torch.repeat_interleave(shift, torch.from_numpy(lens.astype(np.int64)).to(dev)) + torch.arange(int(new_ip[-1]), dtype=torch.int64, device=dev)
+	return de_sparse.DesignCSR(torch.from_numpy(new_ip).to(dev), design.indices[src], None if design.data is None else design.data[src], (int(gid.sum()), design.shape[1]))
+
+
+def _de_sparse_design(dg, dt, dc, bs, ka):
+	"""de for a sparse design (scipy.sparse, de_sparse.DesignCSR, a torch.sparse_csr CUDA tensor): the row filter of de.py:93 from the entries, the rows kept
+	as a sparse matrix again -- no dense design on the host."""
+	from . import de_sparse
+	de_sparse.refuse_sparse(dt, 'dt')
+	de_sparse.refuse_sparse(dc, 'dc')
+	dt, dc = np.asarray(dt), np.asarray(dc)
+	if dg.ndim != 2 or dt.ndim != 2 or dc.ndim != 2:
+		raise ValueError('Incorrect dx/dy/dc size.')
+	design = de_sparse.as_design_csr(dg)
+	if design is None:
+		import scipy.sparse
+		m = scipy.sparse.csr_matrix((de_sparse.canonical_design_csr(dg)[2::-1]), shape=dg.shape)  # (data, indices, indptr)
+		gid = _varying_rows_scipy(m)
+		sub = m if gid.all() else m[gid]
+	else:
+		gid, h = _varying_rows_device(design)
+		sub = design if gid.all() else _device_rows(design, gid, h)
+	res = association_tests(sub, dt, dc, bsx=bs, bsy=bs, return_dot=False, **ka)
+	return _inflate(gid, res, dg.shape[0], dt, dc.shape[0])
+
+
+def _inflate(gid, res, ng0, dt, nc):
+	"""The results of the tested rows put back among all groupings (de.py:107-122) and the reference's assertions on them (de.py:124-131)."""
+	p, gam, alpha, varg, vart = res
+	nt = dt.shape[0]
+	odt = dt.dtype if dt.dtype in (np.float32, np.float64) else np.dtype(np.float64)
+	if bool(gid.all()) and p.dtype == odt:  # nothing to re-inflate (de.py:107-122 is the identity then)
+		P, G, A, VG = p, gam, alpha, varg
+		VT = vart if np.ndim(vart) == 2 else np.broadcast_to(vart, (ng0, nt)).copy()  # single=0: (n_gene,) for every row (SURVEY Q5)
+		assert _finite_within(P, 0, 1) and _finite_within(G) and _finite_within(VG, 0) and _finite_within(VT, 0)
+		return (P, G, A, VG, VT)
+	P = np.ones((ng0, nt), dtype=odt)
+	P[gid] = p
+	G = np.zeros((ng0, nt), dtype=odt)
+	G[gid] = gam
+	A = None
+	if alpha is not None:
+		A = np.zeros((ng0, nt, nc), dtype=odt)
+		A[gid] = alpha
+	VG = np.zeros((ng0, ), dtype=odt)
+	VG[gid] = varg
+	VT = np.zeros((ng0, nt), dtype=odt)
+	VT[gid] = vart  # (n_gene,) for single=0 broadcasts to every tested row (SURVEY Q5)
+	assert _finite_within(P, 0, 1) and _finite_within(G) and _finite_within(VG, 0) and _finite_within(VT, 0)
+	return (P, G, A, VG, VT)
+
+
 def _finite_within(a, lo=None, hi=None):
 	"""np.isfinite(a).all() and (a >= lo).all() and (a <= hi).all() (the reference's assertions on its results, de.py:124-131) from the
 	array's minimum, maximum and NaN count: one threaded pass in the library for large arrays (numpy's min and max for small ones: a NaN
@@ -59,36 +167,21 @@ def de(dg, dt, dc, bs=0, **ka):
 	varg (n_group,), vart (n_group,n_gene)).  Keyword arguments single, lowmem, nth, dimreduce, tol, ...
 	are passed to association_tests.  Single-valued grouping rows are not tested and come back with
 	p=1, gamma=0, alpha=0, varg=0, vart=0 (de.py:107-122).
+	dg may be sparse -- a scipy.sparse matrix, a de_sparse.DesignCSR or a torch.sparse_csr CUDA tensor: the results are those of the densified
+	matrix, and the dense matrix is never formed on the host (DESIGN.md section 4c says which routes scatter it on the device).
 	"""
+	from . import de_sparse
+	if de_sparse.is_sparse_design(dg):
+		return _de_sparse_design(dg, dt, dc, bs, ka)
 	dg0 = np.asarray(dg)
 	dt = np.asarray(dt)
 	dc = np.asarray(dc)
 	if dg0.ndim != 2 or dt.ndim != 2 or dc.ndim != 2:
 		raise ValueError('Incorrect dx/dy/dc size.')
 	gid = _varying_rows(dg0)
-	nt, nc, ng0 = dt.shape[0], dc.shape[0], dg0.shape[0]
-	odt = dt.dtype if dt.dtype in (np.float32, np.float64) else np.dtype(np.float64)
 	allrows = bool(gid.all())
-	p, gam, alpha, varg, vart = association_tests(dg0 if allrows else dg0[gid], dt, dc, bsx=bs, bsy=bs, return_dot=False, **ka)
-	if allrows and p.dtype == odt:  # nothing to re-inflate (de.py:107-122 is the identity then)
-		P, G, A, VG = p, gam, alpha, varg
-		VT = vart if np.ndim(vart) == 2 else np.broadcast_to(vart, (ng0, nt)).copy()  # single=0: (n_gene,) for every row (SURVEY Q5)
-		assert _finite_within(P, 0, 1) and _finite_within(G) and _finite_within(VG, 0) and _finite_within(VT, 0)
-		return (P, G, A, VG, VT)
-	P = np.ones((ng0, nt), dtype=odt)
-	P[gid] = p
-	G = np.zeros((ng0, nt), dtype=odt)
-	G[gid] = gam
-	A = None
-	if alpha is not None:
-		A = np.zeros((ng0, nt, nc), dtype=odt)
-		A[gid] = alpha
-	VG = np.zeros((ng0, ), dtype=odt)
-	VG[gid] = varg
-	VT = np.zeros((ng0, nt), dtype=odt)
-	VT[gid] = vart  # (n_gene,) for single=0 broadcasts to every tested row (SURVEY Q5)
-	assert _finite_within(P, 0, 1) and _finite_within(G) and _finite_within(VG, 0) and _finite_within(VT, 0)
-	return (P, G, A, VG, VT)
+	res = association_tests(dg0 if allrows else dg0[gid], dt, dc, bsx=bs, bsy=bs, return_dot=False, **ka)
+	return _inflate(gid, res, dg0.shape[0], dt, dc.shape[0])
 
 
 assert __name__ != "__main__"

@@ -994,6 +994,9 @@ def de(dg, dt_local, dc, group=None, dimreduce=0, out_dir=None, single=0, **ka):
 	re-inflated), other ranks get None.  single = 0 (resident DePlan), 1 or 4 (see _de_other_methods)."""
 	if single not in (0, 1, 4):
 		raise ValueError('Unknown value single={}'.format(single))
+	from . import de_sparse
+	if de_sparse.is_sparse_design(dg):
+		raise TypeError('distributed.de takes a dense design: DesignCSR.dense() / toarray() give one.')
 	if single:
 		return _de_other_methods(dg, dt_local, dc, group, dimreduce, out_dir, single, ka)
 	if ka:

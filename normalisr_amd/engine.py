@@ -1168,11 +1168,15 @@ class Engine:
 
 	def _association_single0(self, dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, state=None):
 		samexy = dy is None
+		from . import de_sparse
+		# a DesignCSR (a sparse design in HBM): the sparse-design kernel reads its entry lists and no matrix; every other route reads design.dense(), one scatter on the device
+		csr = isinstance(dx, de_sparse.DesignCSR)
 		if self.de_streaming_ok(dx, dy, dc):
+			if csr:
+				dx = dx.dense()
 			self._tls.path = 'the streaming de kernel (fp64 matrix cores, raw rows read once)'
 			return self.association_de_streaming(dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov,
 												 resident=resident and not (want_alpha or want_rt), state=state)
-		from . import de_sparse
 		if de_sparse.candidate(self, dx, dy, dc, samexy):
 			# a design matrix with few entries (gRNA incidence): the expression rows are read once, raw (csrc/nrm_de_sparse.hip)
 			with self.torch.cuda.device(self.device):
@@ -1188,6 +1192,8 @@ class Engine:
 			if lists[2].ok and not (state is not None and state.get('sparse_refused') is dx):
 				self._tls.path = 'the sparse-design kernel (expression rows read once, %d design entries)' % lists[2].nnz
 				return self._association_de_sparse(dx, lists[2], dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident)
+		if csr:
+			dx = dx.dense()
 		nx, n = dx.shape
 		ny = nx if samexy else dy.shape[0]
 		nc = dc.shape[0]

@@ -58,6 +58,11 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 			return tuple(out)
 		dimreduce = vals[0]
 	dimreduce = int(dimreduce)
+	from . import de_sparse
+	de_sparse.refuse_sparse(dy, 'dy')
+	de_sparse.refuse_sparse(dc, 'dc')
+	if de_sparse.is_sparse_design(dx):  # (a scipy.sparse design is canonicalised and uploaded as CSR: no dense matrix on the host)
+		dx = de_sparse.as_design_csr(dx) or de_sparse.DesignCSR.from_scipy(dx)
 	dx, dy, dc = (dx if _engine.is_dev(dx) else np.asarray(dx)), (dy if _engine.is_dev(dy) else np.asarray(dy)), np.asarray(dc)
 	nx, n = dx.shape
 	ny, nc = dy.shape[0], dc.shape[0]
@@ -79,12 +84,12 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 		with torch.cuda.device(eng.device):
 			# cell selection on the device (association.py:914-918): the design matrix travels once, in its own dtype
 			d_dx = dx if _engine.is_dev(dx) else eng.upload(_engine.as_input(dx))
+			csr = isinstance(d_dx, de_sparse.DesignCSR)  # (the list path below never forms the matrix; the masked Gram contraction takes design.dense())
 			lists = None
 			if nc <= 32 and _opts.debug('single1', 'sparse') != 'dense':
 				# the design's entries listed by the library (csrc/nrm_design_lists.hip: one pass counts them and says what they are like, a
 				# second writes them row by row) -- unless more than a quarter of the matrix is set, which no design of this method is
-				from . import de_sparse
-				lists = de_sparse.Lists(eng, d_dx, ell=False, max_density=0.25)
+				lists = de_sparse.Lists.from_csr(eng, d_dx, ell=False, max_density=0.25) if csr else de_sparse.Lists(eng, d_dx, ell=False, max_density=0.25)
 				b = lists.bits
 				assert (b & _lib.DESIGN_HAS1) and not (b & (_lib.DESIGN_GT1 | _lib.DESIGN_NAN))  # dx.max() == 1 (association.py:914)
 				if lists.ok and not (b & _lib.DESIGN_NEG):
@@ -95,7 +100,11 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 						plan.step()
 						return plan.results(device_out=device_out)
 					return _sparse(eng, lists, dy, c64, nx, ny, n, nc, dimreduce, lowmem, return_dot, out_dtype, tdt, device_out)
+				if csr:
+					d_dx = d_dx.dense()
 			else:
+				if csr:
+					d_dx = d_dx.dense()
 				assert float(torch.amax(d_dx)) == 1  # association.py:914
 			sel = d_dx == torch.sum(d_dx, dim=0, dtype=torch.float64)  # association.py:915-916
 			big = torch.finfo(d_dx.dtype).max
@@ -174,16 +183,10 @@ _S1_DEVICE_NC = 8  # covariates up to which the groupings' statistics are finish
 
 
 def _lists_for(eng, d_dx):
-	"""The design's CSR lists, kept for the next call on the SAME device tensor as long as it has not been written to (as de_sparse.lists_for
+	"""The design's CSR lists, kept for the next call on the SAME device tensor (or DesignCSR) as long as it has not been written to (as de_sparse.lists_for
 	does for single=0 / single=4: a resident screen pays for its lists once; bench.py reports a cold call beside the resident step)."""
-	import weakref
 	from . import de_sparse
-	hit = getattr(eng, '_s1_lists', None)
-	if hit is not None and hit[0]() is d_dx and hit[1] == d_dx._version:
-		return hit[2]
-	lists = de_sparse.Lists(eng, d_dx, ell=False, max_density=0.25)
-	eng._s1_lists = (weakref.ref(d_dx), d_dx._version, lists)
-	return lists
+	return de_sparse.cached_lists(eng, '_s1_lists', d_dx, ell=False, max_density=0.25)
 
 
 class Single1Plan:
@@ -202,6 +205,11 @@ class Single1Plan:
 	dx / dy: torch CUDA tensors resident in HBM (numpy arrays are uploaded once); dc: host array."""
 
 	def __init__(self, dx, dy, dc, dimreduce=0, lowmem=True, return_dot=True, lists=None, eng=None):
+		from . import de_sparse
+		if lists is None and de_sparse.is_sparse_design(dx):
+			raise TypeError('Single1Plan takes a dense design: DesignCSR.dense() gives one (association_tests(..., single=1) takes the sparse design itself).')
+		de_sparse.refuse_sparse(dy, 'dy')
+		de_sparse.refuse_sparse(dc, 'dc')
 		eng = self.eng = eng or _engine.get_engine()
 		self._c64 = np.ascontiguousarray(np.asarray(dc, dtype=np.float64))
 		self.dimreduce, self.lowmem, self.return_dot = int(dimreduce), lowmem, return_dot

@@ -358,6 +358,11 @@ class Single4Plan:
 	public call on the new values, the one after it decides anew and the graph is captured again -- the old one is never replayed."""
 
 	def __init__(self, dx, dy, dc, dimreduce=0, lowmem=True, return_dot=True, eng=None):
+		from . import de_sparse
+		if de_sparse.is_sparse_design(dx):
+			raise TypeError('Single4Plan takes a dense design: DesignCSR.dense() gives one (association_tests(..., single=4) takes the sparse design itself).')
+		de_sparse.refuse_sparse(dy, 'dy')
+		de_sparse.refuse_sparse(dc, 'dc')
 		eng = self.eng = eng or _engine.get_engine()
 		self.dx, self.dy = dx, dy
 		self.dc = np.ascontiguousarray(np.asarray(dc, dtype=np.float64))
@@ -566,6 +571,13 @@ def association_tests_single4(dx, dy, dc, lowmem=True, return_dot=True, return_s
 		raise TypeError("association_test_4() got an unexpected keyword argument '{}'".format(next(iter(ka))))
 	if return_stats:
 		raise NotImplementedError('return_stats is only available for single=0.')
+	from . import de_sparse
+	de_sparse.refuse_sparse(dy, 'dy')
+	de_sparse.refuse_sparse(dc, 'dc')
+	if de_sparse.is_sparse_design(dx):
+		# a sparse design: the entry lists come from its entries (de_sparse.lists_for finds the DesignCSR behind the tensor), and what reads the matrix itself
+		# -- the sparse M~ product, the dense closed form, the per-grouping algorithm, the rank-deficient route -- reads ONE scatter of it on the device
+		dx = (de_sparse.as_design_csr(dx) or de_sparse.DesignCSR.from_scipy(dx)).dense()
 	dx, dy, dc, dimreduce = _check_arguments(dx, dy, dc, dimreduce)
 	nx, n = dx.shape
 	nc = dc.shape[0]

@@ -26,6 +26,11 @@ from .association import inv_rank
 def association_tests_single5(dx, dy, dc, mask, bsx=0, bsy=0, lowmem=True, return_dot=True, dimreduce=0, **ka):
 	"""Device path of association_tests(..., single=5, mask=mask); returns (p, gamma|dot, alpha|None, varx (n_x, n_y), vary (n_x, n_y))."""
 	from .single4 import _pvalues_grouped
+	from . import de_sparse
+	if de_sparse.is_sparse_design(dx):
+		raise TypeError('single=5 takes a dense design: DesignCSR.dense() / toarray() give one.')
+	de_sparse.refuse_sparse(dy, 'dy')
+	de_sparse.refuse_sparse(dc, 'dc')
 	dx, dc, mask = np.asarray(dx), np.asarray(dc), np.asarray(mask)
 	nx, n = dx.shape
 	nc = dc.shape[0]
