@@ -391,6 +391,35 @@ int nrm_binnet_rows(const void* d_p, int p_dtype, int64_t rows, int64_t ng, int6
 					unsigned char* d_out, int64_t ldo, unsigned long long* d_total, int32_t* d_flags, void* stream);
 
 /*
+ * bh -- Benjamini-Hochberg q-values over ALL entries of a P-value matrix that lies in HBM (reference binnet.py:77-131 with weight=None; csrc/nrm_bh.hip): what
+ * a screen's de step delivers, computed where de left its P-values.  Contract: for N valid entries (finite, in [0, 1]) with u the sorted distinct values (-0.0
+ * counts as 0.0) and c(u) the exact number of entries <= u:  w = fl(c / N), q(u) = fl(u / w), a non-finite q -> 1, clipped to [0, 1], q(u) <- min over u' >= u
+ * of q(u'); the output is q of every entry, in the input's dtype, and equals the reference's BIT FOR BIT: fp64 divides in IEEE fp64, fp32 divides in fp64 and
+ * rounds each quotient once to fp32 (the correctly rounded fp32 quotient while c and N are exact in fp32, N <= 2^24).  Departure: beyond 2^24 fp32 entries the
+ * reference's fp32 cumsum of ones stalls at 2^24; the counts here stay exact.  Weighted bh is not provided (the reference's sequential sums have no parallel form).
+ *   nrm_bh_workspace_bytes: bytes of d_work for n entries (two key buffers, the q array, the histogram tables, the look-up's sampled keys: about 3.1 n elements); a negative NRM_E_* code for n <= 0 (NRM_E_ARG:
+ *       the reference asserts size > 0), n > 2^31 - 1 (NRM_E_UNSUPPORTED) or a bad dtype.
+ *   nrm_bh_tile:   keys per workgroup of the sort and scan kernels (the tests size themselves by it).
+ *   nrm_bh:        d_p (rows, cols) of p_dtype with pitch ldp, flattened row-major (a vector: rows = 1) -> d_q (rows, cols) with pitch ldq, same dtype; d_q may equal
+ *       d_p when the pitches are equal.  d_work: 256-byte aligned.  d_flags int32[2], zeroed by the call itself on `stream`: [0] = entries that are NaN, infinite,
+ *       < 0 or > 1 (the reference's assertion :104; d_q is then meaningless, no access leaves the buffers), [1] = 1 when there is more than one distinct value, else 0
+ *       (the reference warns "Identical p-value in all entries.").  Does not synchronise and reads nothing back: the launch sequence depends on (n, dtype) only, so
+ *       the call can be queued behind a plan's step and captured into a HIP graph.  No kernel waits for another workgroup.
+ *   nrm_bh_layout: byte offsets into d_work of what a finished call leaves there: [0] the sorted keys (the entries' bit patterns: uint32 / uint64), [1] c per sorted
+ *       position (uint32), [2] q per sorted position after the suffix minimum (p_dtype), [3] 0.  For the stage tests.
+ *   nrm_bh_host:   the whole problem from host buffers (as nrm_binnet_host: no torch, the library's scratch pool, the device of nrm_set_device): h_p (n) -> h_q (n);
+ *       *identical = 1 when every entry holds the same value; NRM_E_NUMERIC "P-values must be finite and within [0, 1]" for entries that are not.
+ * Threads: the device-pointer entries keep no state (any thread, the caller orders work by its streams and owns d_work for the duration); the host entry takes the
+ * lock all whole-problem entries share -- one such call at a time per process.
+ */
+int64_t nrm_bh_workspace_bytes(int64_t n, int p_dtype);
+int64_t nrm_bh_tile(void);
+int nrm_bh(const void* d_p, int p_dtype, int64_t rows, int64_t cols, int64_t ldp, void* d_q, int64_t ldq, void* d_work, int64_t work_bytes,
+		   int32_t* d_flags /* [2] */, void* stream);
+int nrm_bh_layout(int64_t n, int p_dtype, int64_t offsets[4]);
+int nrm_bh_host(const void* h_p, int p_dtype, int64_t n, void* h_q, int32_t* identical);
+
+/*
  * normvar (reference norm.py:131-289): per-gene weighted covariate removal, e_gk = w_k^wt_g.
  *   nrm_normvar_weights: U = e^2, V = e^2 * y  (fp64, (rows_pad, ldo), zero padded) for the two Gram contractions
  *       M_g = U P^T (P = products C_c*C_c') and a_g = V C^T on nrm_gram_f64;  s1 = sum_k y e, s2 = sum_k (y e)^2.

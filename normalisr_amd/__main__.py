@@ -3,7 +3,8 @@ Same sub-commands, positionals and flags as the reference CLI for `lcpm` (__main
 `de` (:358-436), `coex` (:442-492) and `binnet` (:498-509), and for the quality-control steps `qc_reads` (:24-113), `subset` (:120-158) and `qc_outlier`
 (:275-305); global -v (:14-17), help on stderr + exit 1 without arguments (:649-651).  `principal` and `pccovt` are sub-commands of this build's own: the two
 numerical parts of the reference's `gocovt` (:512-597), whose GO enrichment between them is not provided; `enrich`, also this build's own, does that step
-from local gene-set files (normalisr_amd/enrich.py) and writes the pathway's genes for `pccovt`."""
+from local gene-set files (normalisr_amd/enrich.py) and writes the pathway's genes for `pccovt`; `bh`, this build's own too, turns de's P-value matrix into
+Benjamini-Hochberg q-values over all its entries (the reference has the function, binnet.py:77-131, and no command for it)."""
 import argparse
 import logging
 import sys
@@ -11,7 +12,7 @@ import sys
 
 def build_parser():
 	p0 = argparse.ArgumentParser(prog='normalisr', description='Normalisr on AMD MI355X: quality control (qc_reads, subset, qc_outlier), normalisation (lcpm, normcov, '
-								 'fitvar, normvar), association testing (de, coex), network binarisation (binnet) and the covariate of a pathway\'s top principal component '
+								 'fitvar, normvar), association testing (de, coex), network binarisation (binnet), q-values over a result matrix (bh) and the covariate of a pathway\'s top principal component '
 								 '(principal, pccovt).  The sub-command gocovt is not provided: its GO enrichment needs goatools and a web service.  Run principal, find the '
 								 'enriched pathway among its genes with any tool, and hand the pathway\'s genes to pccovt.  The sub-command enrich does the first two of these steps on the '
 								 'device from local gene-set files (GMT, or GO as OBO + GAF): Fisher exact tests by this build\'s own contract, not goatools\' output.')
@@ -111,6 +112,10 @@ def build_parser():
 	p.add_argument('pv_in', help='Input P-value matrix of gene pairwise co-expression (genes x genes), TSV.')
 	p.add_argument('net_out', help='Output binary co-expression network (genes x genes, 0/1), TSV.')
 	p.add_argument('qcut', type=float, help='Q-value cutoff for binary network.')
+
+	p = sub.add_parser('bh', help='Benjamini-Hochberg q-values over all entries of a P-value matrix (pv_out of de); a sub-command of this build\'s own.')
+	p.add_argument('pv_in', help='Input P-value matrix or vector, TSV.')
+	p.add_argument('q_out', help='Output q-values in the same shape, TSV.')
 
 	p = sub.add_parser('principal', help='List the principal genes of a binary co-expression network: the genes with the most co-expressed genes (the selection of '
 					   'the reference\'s gocovt, without its GO enrichment).')

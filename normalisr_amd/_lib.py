@@ -104,6 +104,11 @@ _SIGNATURES = {
 	'nrm_single1_cells': ([_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp], _i32),
 	'nrm_binnet': ([_vp, _i32, _i64, _i64, _dbl, _vp, _i64, _vp, _vp, _vp], _i32),
 	'nrm_binnet_rows': ([_vp, _i32, _i64, _i64, _i64, _i64, _dbl, _vp, _i64, _vp, _vp, _vp], _i32),
+	'nrm_bh_workspace_bytes': ([_i64, _i32], _i64),
+	'nrm_bh_tile': ([], _i64),
+	'nrm_bh': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
+	'nrm_bh_layout': ([_i64, _i32, ctypes.POINTER(_i64)], _i32),
+	'nrm_bh_host': ([_vp, _i32, _i64, _vp, ctypes.POINTER(_i32)], _i32),
 	'nrm_normvar_weights': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp], _i32),
 	'nrm_normvar_apply': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp], _i32),
 	'nrm_normvar_device_covariates': ([], _i64),

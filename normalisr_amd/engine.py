@@ -256,6 +256,7 @@ class Engine:
 		self._tls = threading.local()
 		self._gram_work = None
 		self._skinny_ws = None
+		self._bh_ws = None
 		self._copy = None
 		self.pool = PinnedPool(self.lib)
 		self._cmax = {}
@@ -982,6 +983,13 @@ class Engine:
 		v = ss[:count].cpu().numpy() / float(n_cells)
 		v[v == 0] = 1
 		return v.astype(out_dtype, copy=False)
+
+	def bh_work(self, nbytes):
+		"""The workspace of nrm_bh (binnet.bh on the device): kept between calls, regrown when a call needs more."""
+		if self._bh_ws is None or self._bh_ws.numel() < nbytes:
+			self._bh_ws = None  # (the old block goes back to the allocator before the larger one is asked for)
+			self._bh_ws = self.torch.empty((int(nbytes), ), dtype=self.torch.uint8, device=self.device)
+		return self._bh_ws
 
 	def _skinny_work(self):
 		if self._skinny_ws is None:

@@ -1,4 +1,4 @@
-"""Command runners and matrix IO behind `normalisr qc_reads | subset | lcpm | normcov | fitvar | qc_outlier | normvar | de | coex | binnet | principal | enrich | pccovt | coex_levels`.
+"""Command runners and matrix IO behind `normalisr qc_reads | subset | lcpm | normcov | fitvar | qc_outlier | normvar | de | coex | binnet | bh | principal | enrich | pccovt | coex_levels`.
 
 Every sub-command is one row of COMMANDS: which files are read (and how they are shaped), which command-line
 options become which keyword arguments, which function runs, and which of its results go to which file.
@@ -223,6 +223,12 @@ def _call_binnet(m, ka):
 	return (binnet(m['pv_in'], ka['qcut']).astype('u1', copy=False), )
 
 
+def _call_bh(m, ka):
+	"""Benjamini-Hochberg q-values over ALL entries of the matrix (what de's pv_out holds), in its shape; on the device (nrm_bh_host)."""
+	from .binnet import bh
+	return (bh(m['pv_in'], on_device=True), )
+
+
 # name -> inputs (matrix arguments), options (argument key -> (keyword, converter)), call, outputs (argument key ->
 # (index into the result tuple, transform, format); written when the argument was given)
 COMMANDS = {
@@ -238,6 +244,7 @@ COMMANDS = {
 	'normvar': dict(inputs=('lcpm_in', 'cov_in', 'weights_in', 'scale_in'), options=dict(nth=('nth', int), bs=('bs', int)), call=_call_normvar,
 					outputs=dict(exp_out=(0, None, fmt_float), cov_out=(1, None, fmt_float))),
 	'binnet': dict(inputs=('pv_in', ), options=dict(qcut=('qcut', float)), call=_call_binnet, outputs=dict(net_out=(0, None, fmt_int))),
+	'bh': dict(inputs=('pv_in', ), options={}, call=_call_bh, outputs=dict(q_out=(0, None, fmt_float))),
 	# the reference passes var=None to its writer when --var_out is given (lowmem stays True, run.py:175,188-189) and fails: asking for the file asks for lowmem=False
 	'lcpm': dict(inputs=('reads_in', 'cov_in'), options=dict(nth=('nth', _nth), rseed=('seed', int), var_out=('lowmem', lambda name: False)), call=_call_lcpm,
 				 outputs=dict(lcpm_out=(0, None, fmt_float), cov_out=(2, None, fmt_float), scale_out=(1, None, fmt_float), var_out=(3, None, fmt_float))),
@@ -249,7 +256,7 @@ COMMANDS = {
 def run(cmd, args):
 	"""Run sub-command `cmd` with the parsed command line `args` (a dict of argparse destinations)."""
 	spec = COMMANDS[cmd]
-	if cmd in ('de', 'coex', 'binnet', 'normvar'):
+	if cmd in ('de', 'coex', 'binnet', 'bh', 'normvar'):
 		# files in, files out, one GPU: the library's whole-problem entries (include/normalisr_hip.h) do everything these commands need -- same kernels,
 		# same results -- and torch's import (1.0 of a 1.3 s call) is not paid; NRM_HOST_ENTRY=0 keeps the torch engine.  Calls the entries do not
 		# cover fall back to it by themselves.
@@ -291,7 +298,7 @@ def _runner(cmd):
 	return f
 
 
-de, coex, normvar, binnet, lcpm, normcov, fitvar = (_runner(c) for c in ('de', 'coex', 'normvar', 'binnet', 'lcpm', 'normcov', 'fitvar'))  # module-level entry points, as in the reference's run module
+de, coex, normvar, binnet, bh, lcpm, normcov, fitvar = (_runner(c) for c in ('de', 'coex', 'normvar', 'binnet', 'bh', 'lcpm', 'normcov', 'fitvar'))  # module-level entry points, as in the reference's run module
 
 
 # ---- quality control: qc_reads, subset, qc_outlier (reference run.py:48-150,220-234) -----------------------------------------------------------------------
