@@ -959,6 +959,58 @@ int nrm_coex_plan_info(nrm_coex_plan* plan, int64_t info[8]);
 int nrm_coex_plan_time(nrm_coex_plan* plan, int64_t steps, double* ms_per_step);
 int nrm_coex_plan_destroy(nrm_coex_plan* plan);
 
+/*
+ * Resident de plan (csrc/nrm_de_plan.hip): de(dg, dt, dc) with single=0 -- reference de.py:4-132 over association.py:224-249 -- on the sparse-design kernels, for a
+ * caller that repeats a screen of one shape.  The plan is the sparse-design route by declaration: no size or density threshold (what NRM_DE_SPARSE=force takes).
+ * The design, the expression matrix, the covariates and every result stay in HBM; a step is launches on one stream, from the second step on one hipGraphLaunch.
+ *   nrm_de_plan_create: the design (ng0, n_cells) by design_form.  0: a dense matrix dg of dg_dtype (NRM_F32 / NRM_F64) with row pitch ldg elements (0: n_cells), on
+ *       the host (contiguous) or, dg_on_device != 0, in HBM.  1: canonical CSR as nrm_design_csr_count takes it -- indptr (ng0 + 1) int64, indices int32, dg the nnz
+ *       values of dg_dtype or NULL for all ones -- host arrays (uploaded) or, dg_on_device != 0, device arrays; its structure is checked by nrm_design_csr_count and a
+ *       malformed matrix is NRM_E_ARG.  Either way the design is read here only (and by nrm_de_plan_design): the plan keeps lists, not the matrix.
+ *       de's row filter (de.py:93) runs on the device: a row is tested when it holds more than one distinct value among its n_cells cells (NaNs count as equal; a
+ *       stored zero of a CSR matrix is not an entry; with n_cells < 2 no row varies).  The rows kept are compacted on the device (nrm_subset_dense; nrm_subset_csr_count
+ *       / scan / write) and the lists are built from them by nrm_design_count / nrm_design_csr_count, nrm_design_plan and nrm_design_fill / nrm_design_csr_fill: the
+ *       bytes de builds for the same input.  A row that is dropped reaches neither nrm_design_stats nor the guard.  No row left to test: NRM_E_ARG.
+ *       dt (nt, n_cells) of dt_dtype: a contiguous HOST array (the plan owns a device copy; nrm_de_plan_upload re-fills it) or, dt_on_device != 0, a DEVICE pointer with
+ *       row pitch ldt, adopted: never copied, rewritten in place by its owner between steps.  h_dc, c_dtype, nc, h_dci, rank as nrm_coex_plan_create takes them
+ *       (h_dci == NULL: nrm_covariates_pinv, nc <= 32); more than nrm_de_sparse_max_covariates() covariates: NRM_E_UNSUPPORTED.  want_alpha: lowmem=False;
+ *       want_q: Benjamini-Hochberg q-values of all ng0 * nt P-values by nrm_bh inside every step.  Every argument check, those of association.py:199-216 in the
+ *       reference's words included, is made before any device call.  Every buffer of a step is taken from the scratch pool here, sized for ng0 rows.
+ *   nrm_de_plan_design: another design of the same shape (any form) in place of the present one; drops the captured graph and a remembered hand-back.
+ *   nrm_de_plan_upload: new values (same shape and dtype) into the plan's own copy of dt; NRM_E_ARG for an adopted matrix.
+ *   nrm_de_plan_step: nrm_design_stats -> the products (nrm_de_sparse, behind nrm_single1_stream beyond nrm_de_sparse_fused_covariates()) -> nrm_assoc_sweep (gamma)
+ *       -> nrm_alpha on request: the launches of the whole-problem entry; then the re-inflation of de.py:107-122 (rows not tested: p = 1, gamma = alpha = varg = 0),
+ *       the variances ss / n with the 0 -> 1 rule, the count of entries outside the ranges de.py:124-131 asserts, and nrm_bh on request.  Nothing is read back,
+ *       allocated or waited for.  stream == NULL: the plan's own.  The first step on a route runs eagerly, the second is captured (thread-local) and instantiated,
+ *       later ones are one hipGraphLaunch; a failed capture leaves the plan eager with the reason in nrm_last_error (NRM_OK).  NRM_DEBUG="graph=0": always eager.
+ *   nrm_de_plan_check: synchronises the device, reads and clears the counters.  NRM_E_NUMERIC for the reference's assertions (association.py:248,252; de.py:124-131).
+ *       *handed_back: expression or design rows that have all but vanished against the covariates' span since the last check (else 0): the step was then redone, now,
+ *       on K1 and the fp64 Gram kernel (nrm_residualize, nrm_gram_f64_band) on the compacted design written out dense from its lists, and that is the plan's route for later steps
+ *       until the design is replaced.  The dense route's buffers are taken from the pool at this moment.
+ *   nrm_de_plan_results: check, then de's outputs of the last step into HOST arrays of out_dtype, any of them NULL: P (ng0, nt), gamma (ng0, nt), alpha (ng0, nt, nc),
+ *       varg (ng0), vart (ng0, nt: the genes' variances on every tested row, zero on the others, written out here from the vector and the mask), q (ng0, nt).
+ *   nrm_de_plan_device_results: P, gamma, alpha, varg, q as full-size DEVICE arrays (row pitch *ld = nt), the vart vector (nt), the byte mask of tested rows (ng0);
+ *       NULL for what the plan was created without.  Valid until destroy, written by every step.
+ *   nrm_de_plan_info: info[0] route (0 sparse-design kernels, 1 K1 + fp64 Gram), [1] captured, [2] steps, [3] reruns, [4] rank, [5] dof, [6] bytes resident, [7] rows kept.
+ *   nrm_de_plan_time: as nrm_coex_plan_time.  nrm_de_plan_destroy: accepts NULL.
+ * Threads: create, design, check, results and destroy take the lock of the whole-problem entries; step, upload and time do not.  One thread at a time per plan.
+ */
+typedef struct nrm_de_plan nrm_de_plan;
+int nrm_de_plan_create(nrm_de_plan** plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
+					   int dg_on_device, int64_t ng0, const void* dt, int dt_dtype, int64_t nt, int64_t n_cells, int64_t ldt, int dt_on_device, const void* h_dc,
+					   int c_dtype, int64_t nc, const double* h_dci, int rank, int dimreduce, int out_dtype, int want_alpha, int want_q);
+int nrm_de_plan_design(nrm_de_plan* plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
+					   int dg_on_device);
+int nrm_de_plan_upload(nrm_de_plan* plan, const void* h_dt);
+int nrm_de_plan_step(nrm_de_plan* plan, void* stream);
+int nrm_de_plan_check(nrm_de_plan* plan, int64_t* handed_back);
+int nrm_de_plan_results(nrm_de_plan* plan, void* h_p, void* h_gamma, void* h_alpha, void* h_varg, void* h_vart, void* h_q);
+int nrm_de_plan_device_results(nrm_de_plan* plan, void** d_p, void** d_gamma, void** d_alpha, void** d_varg, void** d_q, void** d_vart, void** d_mask, int64_t* ld);
+int nrm_de_plan_stream(nrm_de_plan* plan, void** stream);
+int nrm_de_plan_info(nrm_de_plan* plan, int64_t info[8]);
+int nrm_de_plan_time(nrm_de_plan* plan, int64_t steps, double* ms_per_step);
+int nrm_de_plan_destroy(nrm_de_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,9 @@ never imports torch.  The matrix stays in HBM, a step is K1 -> K2 -> K3 as one H
 		plan.step()
 		p, dot, var = plan.results()      # == normalisr.coex(dt, dc)
 		plan.update(dt2); plan.step()     # same shape, new values: no allocation, one graph launch
+
+DePlan (nrm_de_plan_*) is the same for de(dg, dt, dc) with single=0 on the sparse-design kernels: the design dense or sparse, de's row filter, re-inflation and
+assertions and, on request, alpha and Benjamini-Hochberg q-values on the device; `results()` is `de`'s contract.
 """
 import ctypes
 
@@ -168,6 +171,255 @@ class CoexPlan:
 		h, self._h = self._h, None
 		if h is not None:
 			_lib.check(self._lib.nrm_coex_plan_destroy(h))
+		self._keep = None
+
+	def __enter__(self):
+		return self
+
+	def __exit__(self, *exc):
+		self.close()
+		return False
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001 -- interpreter shutdown
+			pass
+
+
+DE_INFO_FIELDS = ('route', 'captured', 'steps', 'reruns', 'rank', 'dof', 'bytes', 'rows_kept')
+
+
+class DeviceCSR:
+	"""A canonical CSR design (n_grouping, n_cell) in device-visible memory by its three addresses: indptr (n_grouping + 1) int64, indices (nnz) int32 -- the cell of
+	every stored entry, strictly increasing inside a row --, data (nnz) of `dtype` (float32 / float64) or None for all ones.  What a caller without an array library
+	hands to DePlan; the library checks the structure (ValueError for a malformed matrix)."""
+
+	def __init__(self, indptr, indices, data, shape, nnz, dtype=np.float64):
+		self.indptr, self.indices, self.data = int(indptr), int(indices) if indices else None, int(data) if data else None
+		self.shape, self.nnz, self.dtype = (int(shape[0]), int(shape[1])), int(nnz), np.dtype(dtype)
+		if self.dtype not in (np.float32, np.float64):
+			raise ValueError('DeviceCSR: data must be float32 or float64')
+		if self.nnz < 0 or (self.nnz > 0 and self.indices is None):
+			raise ValueError('DeviceCSR: indices are missing')
+
+
+def varying_rows(dg):
+	"""The rows of a design that de tests (de.py:93: more than one distinct value, NaNs equal), stated as the plan's kernels decide it.  dg: a dense matrix, or a
+	scipy.sparse matrix in CSR form whose stored zeros are not entries.  k entries among n cells: 0 < k < n varies, k == 0 does not, k == n varies when the values
+	differ; with n < 2 no row varies."""
+	from . import de_sparse
+	if de_sparse._is_scipy_sparse(dg):
+		m = dg.tocsr()
+		rows, n = m.shape
+		out = np.zeros(rows, dtype=bool)
+		for i in range(rows):
+			v = np.asarray(m.data[m.indptr[i]:m.indptr[i + 1]], dtype=np.float64)
+			v = v[v != 0]  # (a NaN != 0: an entry)
+			k = v.size
+			full = k == n and n > 1 and bool(((v != v[0]) & ~(np.isnan(v) & np.isnan(v[0]))).any())
+			out[i] = (0 < k < n) or full
+		return out
+	dg = np.asarray(dg)
+	rows, n = dg.shape
+	if n < 2:
+		return np.zeros(rows, dtype=bool)
+	first = dg[:, :1]
+	diff = dg != first
+	if dg.dtype.kind == 'f':
+		diff &= ~(np.isnan(dg) & np.isnan(first))
+	return diff.any(axis=1)
+
+
+def _design(dg):
+	"""The arguments nrm_de_plan_create / nrm_de_plan_design take for a design, its shape, and what must stay alive while the library reads it."""
+	from . import de_sparse
+	if isinstance(dg, DeviceCSR):
+		return (1, dg.data, _code(dg.dtype), 0, dg.indptr, dg.indices, dg.nnz, 1), dg.shape, dg
+	csr = de_sparse.as_design_csr(dg)
+	if csr is not None:
+		from . import engine as _engine
+		indptr, indices, data, code, nnz = csr._ready(_engine.get_engine(csr.device.index))
+		return (1, None if data is None else data.data_ptr(), code, 0, indptr.data_ptr(), indices.data_ptr() if nnz else None, nnz, 1), tuple(csr.shape), (indptr, indices, data)
+	if de_sparse._is_scipy_sparse(dg):
+		if len(dg.shape) != 2:
+			raise ValueError('Incorrect dx/dy/dc size.')
+		indptr, indices, data = (np.ascontiguousarray(a) for a in de_sparse.canonical_design_csr(dg))
+		return (1, data.ctypes.data, _code(data.dtype), 0, indptr.ctypes.data, indices.ctypes.data, int(indices.size), 0), tuple(int(v) for v in dg.shape), (indptr, indices, data)
+	dev = _adopt(dg)
+	if dev is not None:
+		ptr, shape, dtype, ld = dev
+		if dtype not in (np.float32, np.float64):
+			raise ValueError('DePlan: a device matrix must be float32 or float64')
+		return (0, ptr, _code(dtype), ld, None, None, 0, 1), (int(shape[0]), int(shape[1])), dg
+	dg = np.asarray(dg)
+	if dg.ndim != 2:
+		raise ValueError('Incorrect dx/dy/dc size.')
+	if dg.dtype.kind not in 'iufb':
+		raise TypeError('the design matrix must hold real numbers.')
+	if dg.dtype not in (np.float32, np.float64):
+		dg = dg.astype(np.float64)
+	dg = np.ascontiguousarray(dg)
+	return (0, dg.ctypes.data, _code(dg.dtype), dg.shape[1], None, None, 0, 0), dg.shape, dg
+
+
+class DePlan:
+	"""de(dg, dt, dc) with single=0 resident on the GPU, on the sparse-design kernels whatever the size (include/normalisr_hip.h: nrm_de_plan_*):
+
+		with cplan.DePlan(dg, dt, dc, lowmem=False, q=True) as plan:
+			plan.step()
+			p, gamma, alpha, varg, vart = plan.results()   # == normalisr.de(dg, dt, dc, lowmem=False)
+			q = plan.qvalues()                              # == binnet.bh(p)
+			plan.update(dt2); plan.step()                   # same shape, new values: one graph launch
+			plan.set_design(dg2); plan.step()               # another design of the same shape
+
+	dg: a numpy matrix, a scipy.sparse matrix (canonicalised by de_sparse.canonical_design_csr), a de_sparse.DesignCSR, a DeviceCSR, or a dense device matrix (anything
+	CoexPlan adopts); it is read when it is set and not kept.  dt: a numpy array (the plan keeps its own device copy; `update` re-uploads) or a device matrix, adopted
+	and rewritten in place by its owner.  lowmem=False adds alpha; q=True adds the q-values of all P-values to every step.  out_dtype: dt's by default, as de.
+	pinv as for CoexPlan."""
+
+	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None, pinv='numpy'):
+		self._h = None
+		lib = self._lib = _lib.load()
+		from . import de_sparse
+		if pinv not in ('numpy', 'library'):
+			raise ValueError("pinv must be 'numpy' or 'library'")
+		if np.ndim(dimreduce) != 0 or int(dimreduce) != dimreduce:
+			raise ValueError('dimreduce must be an integer.')
+		de_sparse.refuse_sparse(dt, 'dt')
+		de_sparse.refuse_sparse(dc, 'dc')
+		dev = _adopt(dt)
+		if dev is None:
+			dt = np.asarray(dt)
+			if dt.ndim != 2:
+				raise ValueError('Incorrect dx/dy/dc size.')
+			if dt.dtype not in (np.float32, np.float64):
+				dt = dt.astype(np.float64)
+			dt = np.ascontiguousarray(dt)
+			ptr, shape, dtype, ld = dt.ctypes.data, dt.shape, dt.dtype, dt.shape[1]
+		else:
+			ptr, shape, dtype, ld = dev
+			if dtype not in (np.float32, np.float64):
+				raise ValueError('DePlan: a device matrix must be float32 or float64')
+		dc = np.asarray(dc)
+		if dc.ndim != 2:
+			raise ValueError('Incorrect dx/dy/dc size.')
+		gargs, gshape, gkeep = _design(dg)
+		if dc.shape[1] != shape[1] or gshape[1] != shape[1]:
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		self.shape, self.dtype, self.adopted = (int(gshape[0]), int(shape[0]), int(shape[1])), np.dtype(dtype), dev is not None
+		self.out_dtype = np.dtype(dtype if out_dtype is None else out_dtype)
+		if self.out_dtype not in (np.float32, np.float64):
+			raise ValueError('out_dtype must be float32 or float64')
+		nc = self.nc = int(dc.shape[0])
+		self.lowmem, self.q = bool(lowmem), bool(q)
+		if pinv == 'numpy':
+			from .association import _prepare_covariates
+			dc, dci, dcr = _prepare_covariates(dc)
+			dci = np.ascontiguousarray(dci, dtype=np.float64)
+		else:
+			dc = dc if dc.dtype in (np.float32, np.float64) else dc.astype(np.float64)
+			dci, dcr = None, 0
+		dc = np.ascontiguousarray(dc)
+		if device is not None:
+			_lib.check(lib.nrm_set_device(int(device)))
+		h = _vp()
+		_lib.check(lib.nrm_de_plan_create(ctypes.byref(h), *gargs, self.shape[0], ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0,
+										  dc.ctypes.data if nc else None, _code(dc.dtype), nc, None if dci is None or not nc else dci.ctypes.data, int(dcr), int(dimreduce),
+										  _code(self.out_dtype), 0 if self.lowmem else 1, 1 if self.q else 0))
+		self._h = h
+		self._keep = dt if self.adopted else None  # (an adopted matrix lives as long as the plan reads it)
+		del gkeep  # (the design was read inside create)
+
+	def _handle(self):
+		if self._h is None:
+			raise ValueError('DePlan: the plan is closed')
+		return self._h
+
+	def step(self, stream=None):
+		"""One de on the matrices as they stand, queued on `stream` (a hipStream_t as an integer; None: the plan's own).  Does not wait."""
+		_lib.check(self._lib.nrm_de_plan_step(self._handle(), stream))
+		return self
+
+	def check(self):
+		"""Waits for the queued steps and tests what they counted: AssertionError for the reference's assertions (association.py:248,252; de.py:124-131).  Returns the rows
+		handed back since the last check -- > 0: rows all but inside the covariates' span; the step was redone on K1 and the fp64 Gram kernel before returning, and the
+		plan stays on that route until set_design."""
+		back = _i64(0)
+		_lib.check(self._lib.nrm_de_plan_check(self._handle(), ctypes.byref(back)))
+		return int(back.value)
+
+	def _fetch(self, want_q):
+		ng0, nt, _ = self.shape
+		o = self.out_dtype
+		if want_q:
+			qv = np.empty((ng0, nt), o)
+			_lib.check(self._lib.nrm_de_plan_results(self._handle(), None, None, None, None, None, qv.ctypes.data))
+			return qv
+		p, gam, varg, vart = np.empty((ng0, nt), o), np.empty((ng0, nt), o), np.empty(ng0, o), np.empty((ng0, nt), o)
+		alpha = None if self.lowmem else np.zeros((ng0, nt, self.nc), o)
+		_lib.check(self._lib.nrm_de_plan_results(self._handle(), p.ctypes.data, gam.ctypes.data, alpha.ctypes.data if (alpha is not None and self.nc) else None, varg.ctypes.data,
+												 vart.ctypes.data, None))
+		return p, gam, alpha, varg, vart
+
+	def results(self):
+		"""(P-values (n_group, n_gene), gamma (n_group, n_gene), alpha (n_group, n_gene, n_cov) | None, varg (n_group,), vart (n_group, n_gene)) of the last step as numpy
+		arrays of out_dtype: de's return value."""
+		return self._fetch(False)
+
+	def qvalues(self):
+		"""The Benjamini-Hochberg q-values (n_group, n_gene) of the last step's P-values: binnet.bh of them, bit for bit (a plan created with q=True)."""
+		if not self.q:
+			raise ValueError('DePlan.qvalues: the plan was created without q=True')
+		return self._fetch(True)
+
+	def device_results(self):
+		"""dict(p=, gamma=, alpha=, varg=, q= full-size device addresses (None for what the plan was created without), vart= the genes' variances (n_gene), mask= one byte
+		per grouping (1: tested), ld= row pitch in elements, dtype=, stream= the plan's own stream): for a consumer queued behind the step."""
+		v = [_vp() for _ in range(7)]
+		st, ld = _vp(), _i64(0)
+		_lib.check(self._lib.nrm_de_plan_device_results(self._handle(), *[ctypes.byref(x) for x in v], ctypes.byref(ld)))
+		_lib.check(self._lib.nrm_de_plan_stream(self._handle(), ctypes.byref(st)))
+		out = dict(zip(('p', 'gamma', 'alpha', 'varg', 'q', 'vart', 'mask'), (x.value for x in v)))
+		out.update(ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
+		return out
+
+	def update(self, dt):
+		"""New values of the same shape and dtype into the plan's own copy of dt (ValueError for an adopted matrix: its owner rewrites it in place)."""
+		if self.adopted:
+			raise ValueError('DePlan.update: the plan adopted a device matrix; its owner rewrites it in place')
+		dt = np.ascontiguousarray(np.asarray(dt), dtype=self.dtype)
+		if dt.shape != self.shape[1:]:
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		_lib.check(self._lib.nrm_de_plan_upload(self._handle(), dt.ctypes.data))
+		return self
+
+	def set_design(self, dg):
+		"""Another design of the same shape, in any of the forms the constructor takes: the row filter, the compaction and the lists again, and a new graph from the
+		second step on it."""
+		gargs, gshape, gkeep = _design(dg)
+		if tuple(int(v) for v in gshape) != (self.shape[0], self.shape[2]):
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		_lib.check(self._lib.nrm_de_plan_design(self._handle(), *gargs))
+		del gkeep
+		return self
+
+	def time(self, steps):
+		"""Milliseconds per step over `steps` steps, between two device events on the plan's stream."""
+		ms = _dbl(0.)
+		_lib.check(self._lib.nrm_de_plan_time(self._handle(), int(steps), ctypes.byref(ms)))
+		return float(ms.value)
+
+	def info(self):
+		"""route (0: the sparse-design kernels, 1: K1 and the fp64 Gram kernel after a hand-back), captured, steps, reruns, rank, dof, bytes, rows_kept."""
+		v = (_i64 * 8)()
+		_lib.check(self._lib.nrm_de_plan_info(self._handle(), v))
+		return dict(zip(DE_INFO_FIELDS, (int(x) for x in v)))
+
+	def close(self):
+		h, self._h = self._h, None
+		if h is not None:
+			_lib.check(self._lib.nrm_de_plan_destroy(h))
 		self._keep = None
 
 	def __enter__(self):

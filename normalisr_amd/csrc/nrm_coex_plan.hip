@@ -9,20 +9,6 @@
 #include "nrm_device.h"
 #include "nrm_host_entry.h"
 
-namespace {
-
-// variances = ss / n with the 0 -> 1 rule (association.py:230-233), stored once as the output dtype: emit_var (nrm_host_entry.h) for results that stay in HBM
-template <typename T>
-__global__ void k_plan_var(const double* __restrict__ ss, int64_t cnt, double n, void* __restrict__ out) {
-	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= cnt) return;
-	double v = ss[i] / n;
-	if (v == 0.0) v = 1.0;
-	nrm_store_out<T>(out, i, v);
-}
-
-}  // namespace
-
 struct nrm_coex_plan {
 	int device = 0;
 	int64_t ng = 0, n = 0, ld = 0, nc = 0, mp = 0, kp = 0;

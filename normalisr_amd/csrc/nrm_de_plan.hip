@@ -1,0 +1,755 @@
+// Resident de plan behind the C ABI (include/normalisr_hip.h: nrm_de_plan_*): de(dg, dt, dc) with single=0 on a sparse design (reference de.py:4-132 over
+// association.py:224-249) for a caller that repeats it on a screen of one shape -- numpy and the library are all it needs.  The design is filtered (de.py:93), compacted
+// and turned into the lists of csrc/nrm_design_lists.hip when it is set; a step is nrm_design_stats -> the products -> nrm_assoc_sweep -> nrm_alpha, the launch sequence
+// of nrm_host_de_sparse (nrm_host_de.hip), then the kernels of this file: the re-inflation of de.py:107-122, the variances, the assertions of de.py:124-131 as a count,
+// and nrm_bh.  One stream, launches and memset nodes only; from the second step on a route one hipGraphLaunch.
+//
+// Every buffer a step needs is taken from the scratch pool at create (sized for all ng0 design rows, so a new design of the same shape fits); the lists are sized by the
+// design's entries and are retaken by nrm_de_plan_design.  The buffers of the dense route (K1 + the fp64 Gram kernel, after a hand-back) are taken when check first needs them.
+#include <memory>
+#include "nrm_device.h"
+#include "nrm_host_entry.h"
+#include "nrm_design.h"
+#include "nrm_de_plan_args.h"
+
+namespace {
+
+// ---- de's row filter (de.py:93): a design row is tested when it has more than one distinct value, NaNs counting as equal ---------------------------------------
+// A wave per row, four rows per workgroup.  The row is read 256 cells at a time (four loads in flight per lane) until a value differs from its first cell: an
+// incidence row is settled by its first entry.
+template <typename T>
+__global__ __launch_bounds__(256) void k_de_vary_dense(const T* __restrict__ x, int64_t rows, int64_t n, int64_t ld, uint8_t* __restrict__ mask) {
+	const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	const int lane = threadIdx.x & 63;
+	if (r >= rows) return;  // (whole waves leave: no barrier follows)
+	const T* row = x + r * ld;
+	const T first = row[0];
+	const bool fnan = first != first;
+	bool varies = false;
+	for (int64_t k0 = 0; k0 < n && !varies; k0 += 256) {
+		bool d = false;
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int64_t k = k0 + u * 64 + lane;
+			if (k < n) {
+				const T v = row[k];
+				d |= (v != first) && !(fnan && v != v);
+			}
+		}
+		varies = __ballot(d) != 0ull;
+	}
+	if (lane == 0) mask[r] = varies ? 1 : 0;
+}
+
+// The same from canonical CSR (a stored zero is not an entry, a NaN is one): k entries among n cells -- 0 < k < n: the row holds zero and something else; k == 0: all
+// zeros; k == n: every cell is set and the values decide.  The row bounds are clamped to [0, nnz]; no column is used as an address.  data == NULL: every entry is 1.
+template <typename T>
+__global__ __launch_bounds__(256) void k_de_vary_csr(const int64_t* __restrict__ indptr, const T* __restrict__ data, int64_t rows, int64_t n, int64_t nnz,
+													 uint8_t* __restrict__ mask) {
+	const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	const int lane = threadIdx.x & 63;
+	if (r >= rows) return;
+	const int64_t a = nrm_clamp(indptr[r], 0, nnz), e = nrm_clamp(indptr[r + 1], a, nnz);
+	int64_t k = e - a;
+	bool differ = false;
+	if (data != nullptr && k > 0) {
+		const T first = data[a];
+		const bool fnan = first != first;
+		int cnt = 0;
+		bool d = false;
+		for (int64_t p = a + lane; p < e; p += 64) {
+			const T v = data[p];
+			cnt += v != (T)0 ? 1 : 0;
+			d |= (v != first) && !(fnan && v != v);
+		}
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+		k = cnt;
+		differ = __ballot(d) != 0ull;
+	}
+	const bool varies = (k > 0 && k < n) || (k == n && n > 1 && differ);
+	if (lane == 0) mask[r] = varies ? 1 : 0;
+}
+
+// The row map from the mask, by one workgroup in row order: c2f[c] = the design row of compact row c (int64: the index list nrm_subset_dense reads), f2c[i] = the
+// compact row of design row i or -1, *kept = the rows tested.
+__global__ __launch_bounds__(256) void k_de_row_map(const uint8_t* __restrict__ mask, int64_t rows, int64_t* __restrict__ c2f, int32_t* __restrict__ f2c, int64_t* __restrict__ kept) {
+	__shared__ int wsum[4];
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	int64_t base = 0;
+	for (int64_t i0 = 0; i0 < rows; i0 += 256) {
+		const int64_t i = i0 + threadIdx.x;
+		const bool m = i < rows && mask[i] != 0;
+		const unsigned long long b = __ballot(m);
+		if (lane == 0) wsum[w] = (int)__popcll(b);
+		__syncthreads();
+		int before = 0, total = 0;
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			before += j < w ? wsum[j] : 0;
+			total += wsum[j];
+		}
+		const int64_t c = base + before + (int64_t)__popcll(b & ((1ull << lane) - 1ull));
+		if (m) c2f[c] = i;
+		if (i < rows) f2c[i] = m ? (int32_t)c : -1;
+		base += total;
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) *kept = base;
+}
+
+// ---- the finish kernel: de._inflate on the device (de.py:107-122) ----------------------------------------------------------------------------------------------
+// Design row i = blockIdx.y (strided): its nt P-values and gammas and its nt * nc coefficients come from compact row f2c[i], or are 1, 0 and 0 for a row that was
+// not tested.  Every element of the three full-size arrays is written once.  (A plan that tests every row has the sweep write the full-size arrays itself.)
+template <typename T>
+__global__ __launch_bounds__(256) void k_de_inflate(const T* __restrict__ cp, const T* __restrict__ cg, const T* __restrict__ ca, const int32_t* __restrict__ f2c, int64_t ng0,
+													int64_t nt, int64_t nc, T* __restrict__ P, T* __restrict__ G, T* __restrict__ A) {
+	const int64_t j0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+	for (int64_t i = blockIdx.y; i < ng0; i += gridDim.y) {
+		const int64_t c = f2c[i];
+		for (int64_t j = j0; j < nt; j += step) {
+			P[i * nt + j] = c >= 0 ? cp[c * nt + j] : (T)1;
+			G[i * nt + j] = c >= 0 ? cg[c * nt + j] : (T)0;
+		}
+		if (A != nullptr) {
+			const int64_t wide = nt * nc;
+			for (int64_t j = j0; j < wide; j += step) A[i * wide + j] = c >= 0 ? ca[c * wide + j] : (T)0;
+		}
+	}
+}
+
+// varg (ng0) = ss / n with the 0 -> 1 rule for a tested row, 0 for the others, rounded once to the output dtype (the genes' variances: k_plan_var, nrm_host_entry.h)
+template <typename T>
+__global__ void k_de_varg(const double* __restrict__ ssx, const int32_t* __restrict__ f2c, int64_t ng0, double n, T* __restrict__ varg) {
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= ng0) return;
+	const int64_t c = f2c[i];
+	double v = 0.0;
+	if (c >= 0) {
+		v = ssx[c] / n;
+		if (v == 0.0) v = 1.0;
+	}
+	varg[i] = (T)v;
+}
+
+// ---- the bounds kernel: the assertions of de.py:124-131 as a count ---------------------------------------------------------------------------------------------
+// P finite within [0, 1], gamma finite, varg and the vart vector finite and >= 0.  Entries that fail are counted by wave and added with one integer atomic per wave
+// that found any: the count does not depend on the order.
+template <typename T>
+__global__ __launch_bounds__(256) void k_de_bounds(const T* __restrict__ P, const T* __restrict__ G, int64_t cnt, const T* __restrict__ varg, int64_t ng0,
+												   const T* __restrict__ vart, int64_t nt, int32_t* __restrict__ counter) {
+	const T inf = (T)INFINITY;
+	const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+	int bad = 0;
+	for (int64_t i = t0; i < cnt; i += step) {
+		const T p = P[i], g = G[i];
+		bad += !(p >= (T)0 && p <= (T)1) ? 1 : 0;
+		bad += !(g > -inf && g < inf) ? 1 : 0;
+	}
+	for (int64_t i = t0; i < ng0; i += step) bad += !(varg[i] >= (T)0 && varg[i] < inf) ? 1 : 0;
+	for (int64_t i = t0; i < nt; i += step) bad += !(vart[i] >= (T)0 && vart[i] < inf) ? 1 : 0;
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+	if ((threadIdx.x & 63) == 0 && bad > 0) atomicAdd(counter, bad);
+}
+
+}  // namespace
+
+struct nrm_de_plan {
+	int device = 0;
+	int64_t ng0 = 0, nt = 0, n = 0, ldt = 0, nc = 0, ncu = 0, ngk = 0;
+	int g_dtype = NRM_F64, t_dtype = NRM_F64, out_dtype = NRM_F64, rank = 0, dimreduce = 0, ci = -1;
+	bool adopted = false, eager_only = false, want_alpha = false, want_q = false, dense_route = false, dense_ready = false;
+	double dof = 0.0, cval = 0.0, guard_tol = 0.0;
+	const void* dt = nullptr;  // the matrix a step reads: own_dt, or the caller's
+	int64_t nxp0 = 0, nyp = 0, kp = 0, bh_bytes = 0;
+	std::unique_ptr<NrmDesignLists> L;
+	// set at create, for all ng0 rows
+	DevBuf own_dt, dc, dci, cmax, mask, c2f, f2c, flags, ssx, bx, ssy, by, dot, common, ct, code, cp, cg, ca, P, G, A, varg, vart, q, bhwork;
+	// the dense route
+	DevBuf gd, rx, ry, gwork;
+	hipStream_t own = nullptr, last = nullptr;
+	hipGraph_t graph = nullptr;
+	hipGraphExec_t exec = nullptr;
+	int64_t steps = 0, fresh = 0, reruns = 0, bytes = 0, list_bytes = 0;
+	void drop_graph() {
+		if (exec) (void)hipGraphExecDestroy(exec);
+		if (graph) (void)hipGraphDestroy(graph);
+		exec = nullptr, graph = nullptr;
+	}
+	~nrm_de_plan() {
+		(void)hipSetDevice(device);
+		(void)hipDeviceSynchronize();
+		drop_graph();
+		if (own) (void)hipStreamDestroy(own);
+	}
+	int take(DevBuf& b, size_t bytes_) {
+		NRM_TRY(b.alloc(bytes_));
+		bytes += (int64_t)bytes_;
+		return NRM_OK;
+	}
+	bool all_rows() const { return ngk == ng0; }
+	// what the sweep and nrm_alpha write: the full-size arrays when every row is tested, the compact ones otherwise
+	void* sweep_p() const { return all_rows() ? P.p : cp.p; }
+	void* sweep_g() const { return all_rows() ? G.p : cg.p; }
+	void* sweep_a() const { return all_rows() ? A.p : ca.p; }
+};
+
+namespace {
+
+// NrmDesignLists::build (nrm_host_de.hip) with the two passes over the design handed in, so that a CSR design builds the same fields: count(cnt, nslots, info),
+// fill(nslots, pos, w, base, row_ptr, coff, ell, ellv, cells, row_vals, binary).  *bad: the count pass found the CSR arrays malformed.
+template <typename Count, typename Fill>
+int plan_build_lists(NrmDesignLists& L, int64_t nx, int64_t n, Count count, Fill fill, hipStream_t st, bool* bad, int64_t* bytes) {
+	L.nslots = nrm_round_up(nx, 64);
+	L.ngroups = L.nslots / 64;
+	L.nch = (n + DS_CH - 1) / DS_CH;
+	const size_t cs = (size_t)L.nch * L.nslots * 4;
+	NRM_TRY(L.cnt.alloc(cs));
+	NRM_TRY(L.coff.alloc(cs));
+	NRM_TRY(L.info.alloc(8 * sizeof(int64_t)));
+	NRM_TRY(L.row_ptr.alloc((size_t)(nx + 1) * 8));
+	NRM_TRY(L.slot2x.alloc((size_t)L.nslots * 4));
+	NRM_TRY(L.sig.alloc(cs));
+	NRM_TRY(L.pos.alloc(cs));
+	NRM_TRY(L.w.alloc((size_t)L.nch * L.ngroups * 4));
+	NRM_TRY(L.base.alloc((size_t)L.nch * L.ngroups * 8));
+	NRM_TRY(count(L.cnt.as<int32_t>(), L.nslots, L.info.as<int64_t>()));
+	NRM_TRY(nrm_design_plan(L.cnt.as<int32_t>(), nx, n, L.nslots, L.sig.as<int32_t>(), L.pos.as<int32_t>(), L.w.as<int32_t>(), L.base.as<int64_t>(), L.row_ptr.as<int64_t>(),
+							L.coff.as<int32_t>(), L.slot2x.as<int32_t>(), L.info.as<int64_t>(), st));
+	int64_t h[8];
+	NRM_HIP(hipMemcpyAsync(h, L.info.p, sizeof(h), hipMemcpyDeviceToHost, st));
+	NRM_HIP(hipStreamSynchronize(st));
+	*bad = h[NRM_DESIGN_CSR_BAD] != 0;
+	if (*bad) return NRM_OK;
+	L.nnz = h[0];
+	L.padded = h[1];
+	L.bits = (int)h[2];
+	L.binary = !(L.bits & NRM_DESIGN_NOTONE);
+	L.ok = L.nnz > 0;
+	if (!L.ok) return NRM_OK;
+	const size_t pad = (size_t)(L.padded > 8 ? L.padded : 8);
+	NRM_TRY(L.cells.alloc((size_t)L.nnz * 4));
+	if (!L.binary) NRM_TRY(L.row_vals.alloc((size_t)L.nnz * 8));
+	NRM_TRY(L.ell.alloc(pad * 2));
+	if (!L.binary) NRM_TRY(L.ellv.alloc(pad * 8));
+	*bytes = (int64_t)(4 * cs + (size_t)(nx + 1) * 8 + (size_t)L.nslots * 4 + (size_t)L.nch * L.ngroups * 12 + (size_t)L.nnz * (L.binary ? 4 : 12) + pad * (L.binary ? 2 : 10) + 64);
+	return fill(L.nslots, L.pos.as<int32_t>(), L.w.as<int32_t>(), L.base.as<int64_t>(), L.row_ptr.as<int64_t>(), L.coff.as<int32_t>(), L.ell.as<int16_t>(), L.ellv.as<double>(),
+				L.cells.as<int32_t>(), L.row_vals.as<double>(), L.binary ? 1 : 0);
+}
+
+int plan_malformed() {
+	nrm_set_error("Malformed CSR design matrix: indptr must rise from 0 to the number of stored entries, and the columns of every row must lie in [0, n_cell) and increase "
+				  "strictly (sum duplicates and sort the indices first).");
+	return NRM_E_ARG;
+}
+
+int plan_upload_to(const void* h, DevBuf& d, size_t bytes, hipStream_t st) {
+	NRM_TRY(d.alloc(bytes));
+	if (bytes) NRM_TRY(nrm_upload(h, d.p, (int64_t)bytes, 0, (void*)st));
+	return NRM_OK;
+}
+
+// The design of the plan from `in`: the row filter, the row map, the rows kept compacted, their lists.  Reads the size records back (a few words, three times at
+// the most); everything it takes besides the lists returns to the pool on the way out.  The caller has synchronised the device and dropped the graph.
+int plan_set_design(nrm_de_plan* pl, const NrmDePlanDesign& in) {
+	hipStream_t st = pl->own;
+	const int64_t ng0 = pl->ng0, n = pl->n;
+	const size_t es = nrm_esize(in.dtype);
+	DevBuf up_v, up_p, up_i, kept, cnt0, info0;
+	NRM_TRY(kept.alloc(8));
+	const void* values = in.values;
+	const int64_t* indptr = in.indptr;
+	const int32_t* indices = in.indices;
+	int64_t ld = in.ld;
+	if (in.form == 0) {
+		if (!in.on_device) {
+			NRM_TRY(plan_upload_to(in.values, up_v, (size_t)ng0 * n * es, st));
+			values = up_v.p, ld = n;
+		}
+		const dim3 grid((unsigned)((ng0 + 3) / 4));
+		if (in.dtype == NRM_F64)
+			hipLaunchKernelGGL(k_de_vary_dense<double>, grid, dim3(256), 0, st, (const double*)values, ng0, n, ld, pl->mask.as<uint8_t>());
+		else
+			hipLaunchKernelGGL(k_de_vary_dense<float>, grid, dim3(256), 0, st, (const float*)values, ng0, n, ld, pl->mask.as<uint8_t>());
+		NRM_TRY(nrm_check_launch("k_de_vary_dense"));
+	} else {
+		if (!in.on_device) {
+			NRM_TRY(plan_upload_to(in.indptr, up_p, (size_t)(ng0 + 1) * 8, st));
+			NRM_TRY(plan_upload_to(in.indices, up_i, (size_t)in.nnz * 4, st));
+			if (in.values) NRM_TRY(plan_upload_to(in.values, up_v, (size_t)in.nnz * es, st));
+			indptr = up_p.as<int64_t>(), indices = in.nnz ? up_i.as<int32_t>() : nullptr, values = in.values ? up_v.p : nullptr;
+		}
+		// the structure check of nrm_design_csr_count over all ng0 rows, before anything else reads the arrays
+		const int64_t nslots0 = nrm_round_up(ng0, 64), nch = (n + DS_CH - 1) / DS_CH;
+		NRM_TRY(cnt0.alloc((size_t)nch * nslots0 * 4));
+		NRM_TRY(info0.alloc(8 * sizeof(int64_t)));
+		NRM_TRY(nrm_design_csr_count(indptr, indices, values, in.dtype, ng0, n, in.nnz, cnt0.as<int32_t>(), nslots0, info0.as<int64_t>(), st));
+		int64_t h[8];
+		NRM_HIP(hipMemcpyAsync(h, info0.p, sizeof(h), hipMemcpyDeviceToHost, st));
+		NRM_HIP(hipStreamSynchronize(st));
+		if (h[NRM_DESIGN_CSR_BAD]) return plan_malformed();
+		cnt0.release();
+		const dim3 grid((unsigned)((ng0 + 3) / 4));
+		if (in.dtype == NRM_F64)
+			hipLaunchKernelGGL(k_de_vary_csr<double>, grid, dim3(256), 0, st, indptr, (const double*)values, ng0, n, in.nnz, pl->mask.as<uint8_t>());
+		else
+			hipLaunchKernelGGL(k_de_vary_csr<float>, grid, dim3(256), 0, st, indptr, (const float*)values, ng0, n, in.nnz, pl->mask.as<uint8_t>());
+		NRM_TRY(nrm_check_launch("k_de_vary_csr"));
+	}
+	hipLaunchKernelGGL(k_de_row_map, dim3(1), dim3(256), 0, st, pl->mask.as<uint8_t>(), ng0, pl->c2f.as<int64_t>(), pl->f2c.as<int32_t>(), kept.as<int64_t>());
+	NRM_TRY(nrm_check_launch("k_de_row_map"));
+	int64_t ngk = 0;
+	NRM_HIP(hipMemcpyAsync(&ngk, kept.p, 8, hipMemcpyDeviceToHost, st));
+	NRM_HIP(hipStreamSynchronize(st));
+	NRM_REQUIRE(ngk > 0 && ngk <= ng0, "nrm_de_plan: no design row has more than one distinct value (de.py:93 leaves nothing to test)");
+	const bool all = ngk == ng0;
+	std::unique_ptr<NrmDesignLists> L(new NrmDesignLists);
+	bool bad = false;
+	int64_t lb = 0;
+	DevBuf sub_v, sub_p, sub_i, alive, rcount, cmap, out3, info2;
+	if (in.form == 0) {
+		// the rows kept, gathered into a matrix of their own (nrm_qc.hip): a dropped row never reaches the lists, nrm_design_stats or the guard
+		const void* src = values;
+		int64_t lds = ld;
+		if (!all) {
+			NRM_TRY(sub_v.alloc((size_t)ngk * n * es));
+			NRM_TRY(nrm_subset_dense(values, (int)es, ng0, n, ld, pl->c2f.as<int64_t>(), ngk, nullptr, n, sub_v.p, n, st));
+			src = sub_v.p, lds = n;
+		}
+		const int dtype = in.dtype;
+		NRM_TRY(plan_build_lists(
+			*L, ngk, n, [&](int32_t* c, int64_t nslots, int64_t* info) { return nrm_design_count(src, dtype, ngk, n, lds, c, nslots, info, st); },
+			[&](int64_t nslots, const int32_t* pos, const int32_t* w, const int64_t* base, const int64_t* row_ptr, const int32_t* coff, int16_t* ell, double* ellv, int32_t* cells,
+				double* row_vals, int binary) { return nrm_design_fill(src, dtype, ngk, n, lds, nslots, pos, w, base, row_ptr, coff, ell, ellv, cells, row_vals, binary, st); },
+			st, &bad, &lb));
+	} else {
+		const int64_t* ip = indptr;
+		const int32_t* ix = indices;
+		const void* dv = values;
+		int64_t nnzk = in.nnz;
+		if (!all) {
+			// count / scan / write of nrm_qc.hip with every cell alive: the rows kept as canonical CSR again
+			NRM_TRY(alive.alloc((size_t)n));
+			NRM_HIP(hipMemsetAsync(alive.p, 1, (size_t)n, st));
+			NRM_TRY(rcount.alloc((size_t)ng0 * 8));
+			NRM_TRY(info2.alloc(16));
+			NRM_TRY(sub_p.alloc((size_t)(ng0 + 1) * 8));
+			NRM_TRY(cmap.alloc((size_t)n * 4));
+			NRM_TRY(out3.alloc(24));
+			NRM_TRY(nrm_subset_csr_count(indptr, indices, ng0, n, in.nnz, pl->mask.as<uint8_t>(), alive.as<uint8_t>(), rcount.as<int64_t>(), info2.as<int64_t>(), st));
+			NRM_TRY(nrm_subset_csr_scan(rcount.as<int64_t>(), ng0, pl->mask.as<uint8_t>(), alive.as<uint8_t>(), n, sub_p.as<int64_t>(), cmap.as<int32_t>(), out3.as<int64_t>(), st));
+			int64_t h3[3];
+			NRM_HIP(hipMemcpyAsync(h3, out3.p, sizeof(h3), hipMemcpyDeviceToHost, st));
+			NRM_HIP(hipStreamSynchronize(st));
+			NRM_REQUIRE(h3[0] == ngk && h3[2] >= 0 && h3[2] <= in.nnz, "nrm_de_plan: the compacted design does not match its row map");
+			nnzk = h3[2];
+			NRM_TRY(sub_i.alloc((size_t)nnzk * 4));
+			NRM_TRY(sub_v.alloc((size_t)nnzk * (values ? es : 4)));
+			// (an all-ones design has no values to move: its columns stand in for them)
+			NRM_TRY(nrm_subset_csr_write(indptr, indices, values ? values : (const void*)indices, values ? (int)es : 4, ng0, n, in.nnz, pl->mask.as<uint8_t>(), alive.as<uint8_t>(),
+										 rcount.as<int64_t>(), cmap.as<int32_t>(), sub_i.as<int32_t>(), sub_v.p, nnzk, st));
+			ip = sub_p.as<int64_t>(), ix = sub_i.as<int32_t>(), dv = values ? sub_v.p : nullptr;
+		}
+		const int dtype = in.dtype;
+		NRM_TRY(plan_build_lists(
+			*L, ngk, n, [&](int32_t* c, int64_t nslots, int64_t* info) { return nrm_design_csr_count(ip, ix, dv, dtype, ngk, n, nnzk, c, nslots, info, st); },
+			[&](int64_t nslots, const int32_t* pos, const int32_t* w, const int64_t* base, const int64_t* row_ptr, const int32_t* coff, int16_t* ell, double* ellv, int32_t* cells,
+				double* row_vals, int binary) { return nrm_design_csr_fill(ip, ix, dv, dtype, ngk, n, nslots, pos, w, base, row_ptr, coff, ell, ellv, cells, row_vals, binary, st); },
+			st, &bad, &lb));
+	}
+	if (bad) return plan_malformed();
+	NRM_REQUIRE(L->ok, "nrm_de_plan: the design has no entries");
+	NRM_HIP(hipStreamSynchronize(st));  // (the fill read buffers that leave with this scope)
+	if (!all && !pl->cp.p) {  // the compact results the finish kernel re-inflates: only a plan that drops rows needs them
+		const size_t ob = (size_t)pl->ng0 * pl->nt * nrm_esize(pl->out_dtype);
+		NRM_TRY(pl->take(pl->cp, ob));
+		NRM_TRY(pl->take(pl->cg, ob));
+		if (pl->want_alpha) NRM_TRY(pl->take(pl->ca, ob * pl->nc));
+	}
+	pl->bytes += lb - pl->list_bytes;
+	pl->list_bytes = lb;
+	pl->L = std::move(L);
+	pl->ngk = ngk;
+	pl->g_dtype = (in.form == 0 || in.values) ? in.dtype : NRM_F64;
+	pl->dense_route = false;
+	pl->dense_ready = false;
+	pl->fresh = 0;
+	return NRM_OK;
+}
+
+// design_stats -> products -> sweep -> alpha: nrm_host_de_sparse's launches, on the plan's buffers
+int plan_enqueue_sparse(nrm_de_plan* pl, hipStream_t st) {
+	NrmDesignLists& L = *pl->L;
+	const int64_t nc = pl->nc, ncu = pl->ncu, n = pl->n, nt = pl->nt, nx = pl->ngk;
+	const double* d_c = pl->dc.as<double>();
+	const double* d_dci = pl->dci.as<double>();
+	int32_t* flags = pl->flags.as<int32_t>();
+	NRM_HIP(hipMemsetAsync(pl->ssx.p, 0, (size_t)pl->nxp0 * 8, st));
+	NRM_HIP(hipMemsetAsync(pl->bx.p, 0, (size_t)pl->ng0 * (nc > 0 ? nc : 1) * 8, st));
+	NRM_TRY(nrm_design_stats(L.row_ptr.as<int64_t>(), L.cells.as<int32_t>(), L.row_vals.as<double>(), ncu ? d_c : nullptr, n, ncu, ncu ? d_dci : nullptr, nx, pl->ssx.as<double>(),
+							 ncu ? pl->bx.as<double>() : nullptr, flags, st));
+	if (pl->want_alpha) NRM_HIP(hipMemsetAsync(pl->by.p, 0, (size_t)nt * nc * 8, st));
+	const bool fused = pl->ct.p != nullptr;
+	if (!fused)
+		NRM_TRY(nrm_single1_stream(pl->dt, pl->t_dtype, pl->ldt, d_c, n, ncu, pl->code.as<int32_t>(), n, nt, pl->common.as<double>(), pl->common.p, nrm_round_up(nt, 8), st));
+	NRM_TRY(nrm_de_sparse(pl->dt, pl->t_dtype, nt, n, pl->ldt, pl->common.as<double>(), ncu, d_dci, L.ell.as<int16_t>(), L.ellv.as<double>(), L.base.as<int64_t>(), L.w.as<int32_t>(),
+						  L.sig.as<int32_t>(), L.ngroups, L.slot2x.as<int32_t>(), pl->bx.as<double>(), nc > 0 ? nc : 1, pl->dot.as<double>(), pl->nyp, 0, pl->ssy.as<double>(),
+						  (pl->want_alpha && ncu) ? pl->by.as<double>() : nullptr, flags, d_c, n, pl->ci, pl->cval, fused ? pl->ct.as<double>() : nullptr, st));
+	NRM_TRY(nrm_assoc_sweep(pl->dot.as<double>(), pl->nyp, pl->ssx.as<double>(), pl->ssy.as<double>(), nx, nt, n, pl->dof, 0, 1, pl->sweep_p(), pl->sweep_g(), nullptr, nullptr,
+							pl->out_dtype, nt, flags, 0, nullptr, nullptr, 0.0, st));
+	if (pl->want_alpha)
+		NRM_TRY(nrm_alpha(pl->sweep_g(), pl->out_dtype, nt, 1, pl->ssx.as<double>(), n, pl->bx.as<double>(), pl->by.as<double>(), nx, nt, nc, pl->sweep_a(), pl->out_dtype, st));
+	return NRM_OK;
+}
+
+// the same step on K1 and the fp64 Gram kernel (nrm_association_tests_host's second pass): the rows residualised first, no digit planes
+int plan_enqueue_dense(nrm_de_plan* pl, hipStream_t st) {
+	const int64_t nc = pl->nc, n = pl->n, nt = pl->nt, nx = pl->ngk, mp = nrm_round_up(nx, NRM_ROW_TILE);
+	if (pl->want_alpha) {
+		NRM_HIP(hipMemsetAsync(pl->bx.p, 0, (size_t)nx * nc * 8, st));
+		NRM_HIP(hipMemsetAsync(pl->by.p, 0, (size_t)nt * nc * 8, st));
+	}
+	NRM_TRY(nrm_assoc_k1(pl->gd.p, pl->g_dtype, nx, n, n, pl->dc.as<double>(), nc, pl->dci.as<double>(), pl->rank, pl->kp, mp, pl->ssx.as<double>(),
+						 pl->want_alpha ? pl->bx.as<double>() : nullptr, 0, nullptr, nullptr, pl->cmax.as<double>(), nullptr, pl->rx.as<double>(), st));
+	NRM_TRY(nrm_assoc_k1(pl->dt, pl->t_dtype, nt, n, pl->ldt, pl->dc.as<double>(), nc, pl->dci.as<double>(), pl->rank, pl->kp, pl->nyp, pl->ssy.as<double>(),
+						 pl->want_alpha ? pl->by.as<double>() : nullptr, 0, nullptr, nullptr, pl->cmax.as<double>(), nullptr, pl->ry.as<double>(), st));
+	NrmAssocOperands o;
+	o.rx = pl->rx.as<double>(), o.ry = pl->ry.as<double>(), o.ssx = pl->ssx.as<double>(), o.ssy = pl->ssy.as<double>();
+	o.nx = nx, o.ny = nt, o.n = n, o.mp = mp, o.np_ = pl->nyp, o.kp = pl->kp;
+	o.nslices = 0, o.samexy = 0, o.stat_kind = 1, o.out_dtype = pl->out_dtype, o.dof = pl->dof, o.guard_tol = pl->guard_tol;
+	o.dot = pl->dot.as<double>(), o.gwork = pl->gwork.p, o.flags = pl->flags.as<int32_t>();
+	o.p = pl->sweep_p(), o.stat = pl->sweep_g();
+	for (int64_t a = 0; a < nx; a += NRM_ASSOC_BAND) NRM_TRY(nrm_assoc_band(o, a, std::min(nx, a + NRM_ASSOC_BAND), st));
+	if (pl->want_alpha)
+		NRM_TRY(nrm_alpha(pl->sweep_g(), pl->out_dtype, nt, 1, pl->ssx.as<double>(), n, pl->bx.as<double>(), pl->by.as<double>(), nx, nt, nc, pl->sweep_a(), pl->out_dtype, st));
+	return NRM_OK;
+}
+
+template <typename T>
+int plan_finish(nrm_de_plan* pl, hipStream_t st) {
+	const int64_t ng0 = pl->ng0, nt = pl->nt;
+	if (!pl->all_rows()) {
+		const int64_t wide = pl->want_alpha ? nt * pl->nc : nt, gx = std::min<int64_t>((wide + 255) / 256, 64);
+		const dim3 grid((unsigned)gx, (unsigned)std::min<int64_t>(ng0, 65535));
+		hipLaunchKernelGGL(k_de_inflate<T>, grid, dim3(256), 0, st, pl->cp.as<T>(), pl->cg.as<T>(), pl->want_alpha ? pl->ca.as<T>() : (const T*)nullptr, pl->f2c.as<int32_t>(), ng0,
+						   nt, pl->nc, pl->P.as<T>(), pl->G.as<T>(), pl->want_alpha ? pl->A.as<T>() : (T*)nullptr);
+		NRM_TRY(nrm_check_launch("k_de_inflate"));
+	}
+	hipLaunchKernelGGL(k_de_varg<T>, dim3((unsigned)((ng0 + 255) / 256)), dim3(256), 0, st, pl->ssx.as<double>(), pl->f2c.as<int32_t>(), ng0, (double)pl->n, pl->varg.as<T>());
+	NRM_TRY(nrm_check_launch("k_de_varg"));
+	hipLaunchKernelGGL(k_plan_var<T>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, pl->ssy.as<double>(), nt, (double)pl->n, pl->vart.p);
+	NRM_TRY(nrm_check_launch("k_plan_var"));
+	const int64_t cnt = ng0 * nt, blocks = std::min<int64_t>((cnt + 1023) / 1024, 2048);
+	hipLaunchKernelGGL(k_de_bounds<T>, dim3((unsigned)blocks), dim3(256), 0, st, pl->P.as<T>(), pl->G.as<T>(), cnt, pl->varg.as<T>(), ng0, pl->vart.as<T>(), nt,
+					   pl->flags.as<int32_t>() + 4);
+	NRM_TRY(nrm_check_launch("k_de_bounds"));
+	if (pl->want_q)
+		NRM_TRY(nrm_bh(pl->P.p, pl->out_dtype, ng0, nt, nt, pl->q.p, nt, pl->bhwork.p, pl->bh_bytes, pl->flags.as<int32_t>() + 6, (void*)st));
+	return NRM_OK;
+}
+
+int plan_enqueue(nrm_de_plan* pl, hipStream_t st) {
+	NRM_TRY(pl->dense_route ? plan_enqueue_dense(pl, st) : plan_enqueue_sparse(pl, st));
+	return pl->out_dtype == NRM_F64 ? plan_finish<double>(pl, st) : plan_finish<float>(pl, st);
+}
+
+int plan_bind(nrm_de_plan* pl, const char* who) {
+	NRM_REQUIRE(pl != nullptr, "%s: null plan", who);
+	NRM_REQUIRE(pl->L != nullptr, "%s: the plan has no design (the last nrm_de_plan_design was refused)", who);
+	NRM_HIP(hipSetDevice(pl->device));
+	return NRM_OK;
+}
+
+int plan_upload(nrm_de_plan* pl, const void* h_dt) {
+	NRM_TRY(nrm_upload(h_dt, pl->own_dt.p, pl->nt * pl->n * (int64_t)nrm_esize(pl->t_dtype), 0, (void*)pl->own));
+	NRM_HIP(hipStreamSynchronize(pl->own));
+	return NRM_OK;
+}
+
+// the step stays eager from here on; nrm_last_error keeps the reason (plan_stay_eager of nrm_coex_plan.hip)
+int plan_stay_eager(nrm_de_plan* pl, const char* what, hipError_t e, hipStream_t st) {
+	(void)hipGetLastError();
+	pl->eager_only = true;
+	char why[256];
+	snprintf(why, sizeof(why), "nrm_de_plan_step: not captured as a HIP graph (%s: %s); the plan runs eagerly", what, e == hipSuccess ? nrm_last_error() : hipGetErrorString(e));
+	NRM_TRY(plan_enqueue(pl, st));
+	nrm_set_error("%s", why);
+	return NRM_OK;
+}
+
+// the dense route's buffers, once, and the compacted design as a matrix: written from the entries of the lists (their CSR form holds every entry of the rows kept)
+int plan_dense_ready(nrm_de_plan* pl, hipStream_t st) {
+	const int64_t mp0 = pl->nxp0;
+	if (!pl->rx.p) {
+		NRM_TRY(pl->take(pl->gd, (size_t)pl->ng0 * pl->n * 8));  // (room for fp64: a later design of the plan may be one)
+		NRM_TRY(pl->take(pl->rx, (size_t)mp0 * pl->kp * 8));
+		NRM_TRY(pl->take(pl->ry, (size_t)pl->nyp * pl->kp * 8));
+		NRM_TRY(pl->take(pl->gwork, (size_t)nrm_gram_workspace_bytes()));
+	}
+	NrmDesignLists& L = *pl->L;
+	NRM_TRY(nrm_design_csr_dense(L.row_ptr.as<int64_t>(), L.cells.as<int32_t>(), L.row_vals.p, NRM_F64, pl->ngk, pl->n, pl->gd.p, pl->g_dtype, pl->n, st));
+	pl->dense_ready = true;
+	return NRM_OK;
+}
+
+int plan_counters(nrm_de_plan* pl, hipStream_t st, int32_t (&hf)[8]) {
+	NRM_TRY(nrm_read_flags(pl->flags.p, st, hf));
+	NRM_TRY(nrm_fill_zero(pl->flags.p, 32, (void*)st));
+	NRM_HIP(hipStreamSynchronize(st));
+	NRM_TRY(nrm_assoc_assertions(hf, " tiles"));
+	if (hf[4] > 0) {
+		nrm_set_error("de results failed the reference's assertions (de.py:124-131): %d entries of P, gamma, varg or vart not finite or out of range", hf[4]);
+		return NRM_E_NUMERIC;
+	}
+	return NRM_OK;
+}
+
+// reads and clears the counters once the queued steps are through; the hand-back's rerun; caller holds nrm_host_entry_mutex
+int plan_check(nrm_de_plan* pl, int64_t* handed_back) {
+	hipStream_t st = pl->last ? pl->last : pl->own;
+	if (handed_back) *handed_back = 0;
+	int32_t hf[8];
+	NRM_HIP(hipDeviceSynchronize());
+	NRM_TRY(plan_counters(pl, st, hf));
+	if (pl->dense_route || pl->steps == 0 || hf[2] <= 0) return NRM_OK;
+	// rows all but inside the span of the covariates since the last check: the step again on K1 and the fp64 Gram kernel from the matrices as they stand, and that
+	// route from here on, until the design is replaced
+	if (handed_back) *handed_back = hf[2];
+	NRM_TRY(plan_dense_ready(pl, st));
+	pl->drop_graph();
+	pl->dense_route = true;
+	pl->fresh = 1;
+	NRM_TRY(plan_enqueue(pl, st));
+	pl->reruns++;
+	return plan_counters(pl, st, hf);
+}
+
+}  // namespace
+
+extern "C" int nrm_de_plan_create(nrm_de_plan** plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
+								  int dg_on_device, int64_t ng0, const void* dt, int dt_dtype, int64_t nt, int64_t n_cells, int64_t ldt, int dt_on_device, const void* h_dc,
+								  int c_dtype, int64_t nc, const double* h_dci, int rank, int dimreduce, int out_dtype, int want_alpha, int want_q) {
+	NRM_REQUIRE(plan != nullptr, "nrm_de_plan_create: null plan pointer");
+	*plan = nullptr;
+	const int64_t n = n_cells;
+	if (ldt == 0) ldt = n;
+	NrmDePlanDesign g;
+	g.form = design_form, g.values = dg, g.dtype = dg_dtype, g.ld = ldg ? ldg : n, g.indptr = indptr, g.indices = indices, g.nnz = nnz, g.on_device = dg_on_device;
+	// every check, the covariates' pseudo-inverse and rank when the caller has none included (host arithmetic, nrm_de_plan_args.h): all before any device call
+	std::vector<double> c64, own_dci;
+	NRM_TRY(nrm_de_plan_create_args(g, ng0, dt, dt_dtype, nt, n, ldt, dt_on_device, h_dc, c_dtype, nc, &h_dci, &rank, dimreduce, out_dtype, nrm_de_sparse_max_covariates(), c64,
+									own_dci));
+	const int64_t bh_bytes = want_q ? nrm_bh_workspace_bytes(ng0 * nt, out_dtype) : 0;
+	if (bh_bytes < 0) {
+		nrm_set_error("nrm_de_plan_create: q-values of %lld P-values are not provided (nrm_bh takes at most 2^31 - 1)", (long long)(ng0 * nt));
+		return (int)bh_bytes;
+	}
+
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_TRY(nrm_bind_device());
+	std::unique_ptr<nrm_de_plan> pl(new nrm_de_plan);
+	NRM_HIP(hipGetDevice(&pl->device));
+	pl->ng0 = ng0, pl->nt = nt, pl->n = n, pl->ldt = ldt, pl->nc = nc, pl->t_dtype = dt_dtype, pl->out_dtype = out_dtype, pl->rank = rank, pl->dimreduce = dimreduce;
+	pl->adopted = dt_on_device != 0;
+	pl->want_alpha = want_alpha != 0 && nc > 0, pl->want_q = want_q != 0;
+	pl->dof = (double)(n - 1 - rank - dimreduce);
+	pl->guard_tol = nrm_guard_tolerance();
+	pl->ncu = (rank > 0 && nc > 0) ? nc : 0;  // (covariates of rank 0 -- all zero -- leave the rows as they are: association.py:899-903)
+	pl->ci = pl->ncu ? nrm_constant_row(c64.data(), nc, n, &pl->cval) : -1;
+	pl->nxp0 = nrm_round_up(ng0, NRM_ROW_TILE), pl->nyp = nrm_round_up(nt, NRM_ROW_TILE), pl->kp = nrm_round_up(n, NRM_K_TILE);
+	pl->bh_bytes = bh_bytes;
+	NRM_HIP(hipStreamCreateWithFlags(&pl->own, hipStreamNonBlocking));
+	hipStream_t st = pl->own;
+	if (pl->adopted)
+		pl->dt = dt;
+	else {
+		NRM_TRY(pl->take(pl->own_dt, (size_t)nt * n * nrm_esize(dt_dtype)));
+		pl->dt = pl->own_dt.p;
+	}
+	if (nc > 0) {
+		NRM_TRY(pl->take(pl->dc, c64.size() * 8));
+		NRM_HIP(hipMemcpy(pl->dc.p, c64.data(), c64.size() * 8, hipMemcpyHostToDevice));
+		NRM_TRY(covariate_bounds(c64, nc, n, h_dci, rank, pl->cmax, pl->dci));
+		pl->bytes += nc * 8 + nc * nc * 8;
+	}
+	const size_t es = nrm_esize(out_dtype), ob = (size_t)ng0 * nt * es;
+	NRM_TRY(pl->take(pl->mask, (size_t)ng0));
+	NRM_TRY(pl->take(pl->c2f, (size_t)ng0 * 8));
+	NRM_TRY(pl->take(pl->f2c, (size_t)ng0 * 4));
+	NRM_TRY(pl->take(pl->flags, 32));
+	NRM_TRY(pl->take(pl->ssx, (size_t)pl->nxp0 * 8));
+	NRM_TRY(pl->take(pl->bx, (size_t)ng0 * (nc > 0 ? nc : 1) * 8));
+	NRM_TRY(pl->take(pl->ssy, (size_t)pl->nyp * 8));
+	if (pl->want_alpha) NRM_TRY(pl->take(pl->by, (size_t)nt * nc * 8));
+	NRM_TRY(pl->take(pl->dot, (size_t)pl->nxp0 * pl->nyp * 8));
+	NRM_TRY(pl->take(pl->common, (size_t)(pl->ncu + 1) * nt * 8));
+	if (pl->ncu - (pl->ci >= 0 ? 1 : 0) <= nrm_de_sparse_fused_covariates())
+		NRM_TRY(pl->take(pl->ct, (size_t)nrm_de_sparse_ct_doubles(n, pl->ncu, pl->ci) * 8));
+	else {
+		NRM_TRY(pl->take(pl->code, (size_t)n * 4));
+		NRM_TRY(nrm_fill_i32(pl->code.p, NRM_S1_COMMON, n, (void*)st));
+	}
+	NRM_TRY(pl->take(pl->P, ob));
+	NRM_TRY(pl->take(pl->G, ob));
+	if (pl->want_alpha) NRM_TRY(pl->take(pl->A, ob * nc));
+	NRM_TRY(pl->take(pl->varg, (size_t)ng0 * es));
+	NRM_TRY(pl->take(pl->vart, (size_t)nt * es));
+	if (pl->want_q) {
+		NRM_TRY(pl->take(pl->q, ob));
+		NRM_TRY(pl->take(pl->bhwork, (size_t)bh_bytes));
+	}
+	NRM_TRY(nrm_fill_zero(pl->flags.p, 32, (void*)st));
+	if (pl->adopted || dg_on_device) NRM_HIP(hipDeviceSynchronize());  // (whatever the caller queued to fill its matrices is through before they are read)
+	NRM_TRY(plan_set_design(pl.get(), g));
+	if (!pl->adopted) NRM_TRY(plan_upload(pl.get(), dt));
+	NRM_HIP(hipStreamSynchronize(st));
+	*plan = pl.release();
+	return NRM_OK;
+}
+
+extern "C" int nrm_de_plan_design(nrm_de_plan* plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
+								  int dg_on_device) {
+	NRM_REQUIRE(plan != nullptr, "nrm_de_plan_design: null plan");
+	NrmDePlanDesign g;
+	g.form = design_form, g.values = dg, g.dtype = dg_dtype, g.ld = ldg ? ldg : plan->n, g.indptr = indptr, g.indices = indices, g.nnz = nnz, g.on_device = dg_on_device;
+	NRM_TRY(nrm_de_plan_design_args("nrm_de_plan_design", g, plan->ng0, plan->n));
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_HIP(hipSetDevice(plan->device));
+	NRM_HIP(hipDeviceSynchronize());  // (the steps queued on the old lists are through, and so is whatever filled the caller's arrays)
+	plan->drop_graph();
+	const int rc = plan_set_design(plan, g);
+	if (rc != NRM_OK) plan->L.reset();  // (the row map may already be the refused design's: the plan has none until a design is accepted)
+	return rc;
+}
+
+extern "C" int nrm_de_plan_upload(nrm_de_plan* plan, const void* h_dt) {
+	NRM_TRY(plan_bind(plan, "nrm_de_plan_upload"));
+	NRM_REQUIRE(!plan->adopted, "nrm_de_plan_upload: the plan adopted the caller's device matrix (rewrite it in place)");
+	NRM_REQUIRE(h_dt != nullptr, "nrm_de_plan_upload: null matrix");
+	if (plan->last && plan->last != plan->own) NRM_HIP(hipStreamSynchronize(plan->last));  // (a step on the caller's stream may still read the copy)
+	return plan_upload(plan, h_dt);
+}
+
+extern "C" int nrm_de_plan_step(nrm_de_plan* plan, void* stream) {
+	NRM_TRY(plan_bind(plan, "nrm_de_plan_step"));
+	hipStream_t st = stream ? (hipStream_t)stream : plan->own;
+	plan->last = st;
+	plan->steps++;
+	plan->fresh++;
+	if (plan->exec) {
+		NRM_HIP(hipGraphLaunch(plan->exec, st));
+		return NRM_OK;
+	}
+	if (plan->eager_only || plan->fresh < 2 || nrm_debug_is("graph", "0")) return plan_enqueue(plan, st);
+	// the second step on a route: recorded, not run (thread-local capture), instantiated, launched
+	hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+	if (e != hipSuccess) return plan_stay_eager(plan, "hipStreamBeginCapture", e, st);
+	const int rc = plan_enqueue(plan, st);
+	hipGraph_t g = nullptr;
+	e = hipStreamEndCapture(st, &g);
+	if (rc != NRM_OK || e != hipSuccess || !g) {
+		if (g) (void)hipGraphDestroy(g);
+		return plan_stay_eager(plan, rc != NRM_OK ? "a launch inside the capture" : "hipStreamEndCapture", rc != NRM_OK ? hipSuccess : (e != hipSuccess ? e : hipErrorUnknown), st);
+	}
+	hipGraphExec_t x = nullptr;
+	e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
+	if (e != hipSuccess || !x) {
+		(void)hipGraphDestroy(g);
+		return plan_stay_eager(plan, "hipGraphInstantiate", e != hipSuccess ? e : hipErrorUnknown, st);
+	}
+	plan->graph = g, plan->exec = x;
+	NRM_HIP(hipGraphLaunch(plan->exec, st));
+	return NRM_OK;
+}
+
+extern "C" int nrm_de_plan_check(nrm_de_plan* plan, int64_t* handed_back) {
+	NRM_REQUIRE(plan != nullptr, "nrm_de_plan_check: null plan");
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_TRY(plan_bind(plan, "nrm_de_plan_check"));
+	return plan_check(plan, handed_back);
+}
+
+extern "C" int nrm_de_plan_results(nrm_de_plan* plan, void* h_p, void* h_gamma, void* h_alpha, void* h_varg, void* h_vart, void* h_q) {
+	NRM_REQUIRE(plan != nullptr, "nrm_de_plan_results: null plan");
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_TRY(plan_bind(plan, "nrm_de_plan_results"));
+	NRM_REQUIRE(plan->steps > 0, "nrm_de_plan_results: no step has run");
+	NRM_REQUIRE(!h_alpha || plan->want_alpha, "nrm_de_plan_results: the plan was created without alpha");
+	NRM_REQUIRE(!h_q || plan->want_q, "nrm_de_plan_results: the plan was created without q-values");
+	NRM_TRY(plan_check(plan, nullptr));
+	const size_t es = nrm_esize(plan->out_dtype), ob = (size_t)plan->ng0 * plan->nt * es;
+	NRM_TRY(copy_out(h_p, plan->P.p, ob));
+	NRM_TRY(copy_out(h_gamma, plan->G.p, ob));
+	NRM_TRY(copy_out(h_alpha, plan->A.p, ob * plan->nc));
+	NRM_TRY(copy_out(h_varg, plan->varg.p, (size_t)plan->ng0 * es));
+	NRM_TRY(copy_out(h_q, plan->q.p, ob));
+	if (h_vart) {  // the broadcast of de.py:120-122: the genes' variances on every tested row, zero on the others
+		std::vector<char> vec, m;
+		NRM_TRY(download(vec, plan->vart.p, (size_t)plan->nt * es));
+		NRM_TRY(download(m, plan->mask.p, (size_t)plan->ng0));
+		const size_t row = (size_t)plan->nt * es;
+		for (int64_t i = 0; i < plan->ng0; i++) {
+			if (m[(size_t)i])
+				memcpy((char*)h_vart + (size_t)i * row, vec.data(), row);
+			else
+				memset((char*)h_vart + (size_t)i * row, 0, row);
+		}
+	}
+	return NRM_OK;
+}
+
+extern "C" int nrm_de_plan_device_results(nrm_de_plan* plan, void** d_p, void** d_gamma, void** d_alpha, void** d_varg, void** d_q, void** d_vart, void** d_mask, int64_t* ld) {
+	NRM_REQUIRE(plan != nullptr, "nrm_de_plan_device_results: null plan");
+	if (d_p) *d_p = plan->P.p;
+	if (d_gamma) *d_gamma = plan->G.p;
+	if (d_alpha) *d_alpha = plan->A.p;
+	if (d_varg) *d_varg = plan->varg.p;
+	if (d_q) *d_q = plan->q.p;
+	if (d_vart) *d_vart = plan->vart.p;
+	if (d_mask) *d_mask = plan->mask.p;
+	if (ld) *ld = plan->nt;
+	return NRM_OK;
+}
+
+extern "C" int nrm_de_plan_stream(nrm_de_plan* plan, void** stream) {
+	NRM_REQUIRE(plan != nullptr && stream != nullptr, "nrm_de_plan_stream: null pointer");
+	*stream = (void*)plan->own;
+	return NRM_OK;
+}
+
+extern "C" int nrm_de_plan_info(nrm_de_plan* plan, int64_t info[8]) {
+	NRM_REQUIRE(plan != nullptr && info != nullptr, "nrm_de_plan_info: null pointer");
+	info[0] = plan->dense_route ? 1 : 0, info[1] = plan->exec ? 1 : 0, info[2] = plan->steps, info[3] = plan->reruns, info[4] = plan->rank, info[5] = (int64_t)plan->dof,
+	info[6] = plan->bytes, info[7] = plan->ngk;
+	return NRM_OK;
+}
+
+extern "C" int nrm_de_plan_time(nrm_de_plan* plan, int64_t steps, double* ms_per_step) {
+	NRM_TRY(plan_bind(plan, "nrm_de_plan_time"));
+	NRM_REQUIRE(steps > 0 && ms_per_step != nullptr, "nrm_de_plan_time: bad arguments");
+	while (plan->fresh < 2) NRM_TRY(nrm_de_plan_step(plan, nullptr));  // (the eager step and the capture are not what is timed)
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	NRM_HIP(hipEventCreate(&t0));
+	hipError_t e = hipEventCreate(&t1);
+	int rc = NRM_OK;
+	float ms = 0.f;
+	if (e == hipSuccess) e = hipEventRecord(t0, plan->own);
+	for (int64_t i = 0; i < steps && e == hipSuccess && rc == NRM_OK; i++) rc = nrm_de_plan_step(plan, nullptr);
+	if (e == hipSuccess && rc == NRM_OK) e = hipEventRecord(t1, plan->own);
+	if (e == hipSuccess && rc == NRM_OK) e = hipEventSynchronize(t1);
+	if (e == hipSuccess && rc == NRM_OK) e = hipEventElapsedTime(&ms, t0, t1);
+	(void)hipEventDestroy(t0);
+	if (t1) (void)hipEventDestroy(t1);
+	NRM_TRY(rc);
+	NRM_HIP(e);
+	*ms_per_step = (double)ms / (double)steps;
+	return NRM_OK;
+}
+
+extern "C" int nrm_de_plan_destroy(nrm_de_plan* plan) {
+	if (!plan) return NRM_OK;
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	delete plan;  // (synchronises the device, then the buffers go back to the pool)
+	return NRM_OK;
+}

@@ -147,6 +147,16 @@ static inline int emit_var(const double* d_ss, int64_t cnt, int64_t n, void* h_o
 	return NRM_OK;
 }
 
+// the same for results that stay in HBM (the resident plans: nrm_coex_plan.hip, nrm_de_plan.hip): stored once as the output dtype
+template <typename T>
+__global__ void k_plan_var(const double* __restrict__ ss, int64_t cnt, double n, void* __restrict__ out) {
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= cnt) return;
+	double v = ss[i] / n;
+	if (v == 0.0) v = 1.0;
+	reinterpret_cast<T*>(out)[i] = (T)v;
+}
+
 // single=0's result matrices (nx, ny) of out_dtype on the device: P-values and the statistic, r and t on request
 struct NrmAssocOut {
 	DevBuf p, stat, r, t;
@@ -217,15 +227,7 @@ static inline double nrm_guard_tolerance() {
 	const char* t = getenv("NRM_I8_GUARD_TOL");  // largest relative change of a P-value the integer engine may cause (0: no guard)
 	return t ? atof(t) : 2.5e-7;
 }
-// the checks of association.py:199-216 on a dense single=0 call, in the reference's words
-static inline int nrm_assoc_check_args(const void* dx, int64_t nx, int64_t ny, const void* h_dc, int64_t nc, int64_t n, int rank, int dimreduce) {
-	NRM_REQUIRE(dx && nx > 0 && ny > 0 && n > 0, "Incorrect dx/dy/dc size.");
-	NRM_REQUIRE(nc >= 0 && (nc == 0 || h_dc), "Incorrect dx/dy/dc size.");
-	NRM_REQUIRE(rank >= 0, "Negative dcr detected.");
-	NRM_REQUIRE(rank <= nc, "dcr higher than covariate dimension.");
-	NRM_REQUIRE(n > (int64_t)rank + dimreduce + 1, "Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.");
-	return NRM_OK;
-}
+// (the checks of association.py:199-216 on a dense single=0 call: nrm_assoc_check_args, nrm_host_logic.h)
 // max |C_c| per covariate row (K1's bound on the residuals it quantises) and the pseudo-inverse, uploaded
 static inline int covariate_bounds(const std::vector<double>& c64, int64_t nc, int64_t n, const double* h_dci, int rank, DevBuf& cmax, DevBuf& dci) {
 	if (nc <= 0) return NRM_OK;

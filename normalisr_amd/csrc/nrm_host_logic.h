@@ -30,6 +30,16 @@ void nrm_set_error(const char* fmt, ...);
 
 NRM_HD inline int nrm_imin(int a, int b) { return a < b ? a : b; }
 
+// the checks of association.py:199-216 on a dense single=0 call, in the reference's words (the whole-problem entry and the resident plans, before any device call)
+static inline int nrm_assoc_check_args(const void* dx, int64_t nx, int64_t ny, const void* h_dc, int64_t nc, int64_t n, int rank, int dimreduce) {
+	NRM_REQUIRE(dx && nx > 0 && ny > 0 && n > 0, "Incorrect dx/dy/dc size.");
+	NRM_REQUIRE(nc >= 0 && (nc == 0 || h_dc), "Incorrect dx/dy/dc size.");
+	NRM_REQUIRE(rank >= 0, "Negative dcr detected.");
+	NRM_REQUIRE(rank <= nc, "dcr higher than covariate dimension.");
+	NRM_REQUIRE(n > (int64_t)rank + dimreduce + 1, "Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.");
+	return NRM_OK;
+}
+
 #define GM 128
 #define GN 128
 
