@@ -52,21 +52,18 @@
 typedef int i4_t __attribute__((ext_vector_type(4)));
 typedef int i16_t __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ void q_dma16(const void* gsrc, unsigned lds_dst) {
-	unsigned keep;
-	asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-				 : "=&s"(keep)
-				 : "v"(gsrc), "s"(lds_dst)
-				 : "memory");
-}
-
-// the same without the compiler-level memory clobber, for use between sched_barriers inside the MFMA stream (ordering against
-// the LDS reads of later k-steps is carried by the vmcnt wait and the workgroup barrier, both of which clobber memory)
-__device__ __forceinline__ void q_dma16_nc(const void* gsrc, unsigned lds_dst) {
-	unsigned keep;
-	asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-				 : "=&s"(keep)
-				 : "v"(gsrc), "s"(lds_dst));
+// The refill of k_gram_i8: a wave's 64 source addresses differ only by the constant 16 * lane, so the 64-bit part -- operand block, digit plane (planes
+// can lie more than 4 GB apart) and k-step -- is a wave-uniform base in a scalar register pair, stepped by scalar adds, and the lane's offset is ONE
+// vector register for the whole piece (the `saddr` form).  A per-lane 64-bit source address (the recipe of nrm_gram_skinny.hip, and this kernel's until the base
+// went scalar) costs a 64-bit vector add per DMA and two live address registers in a kernel that sits at the register cap.  M0 is declared clobbered instead of saved and restored: nothing else in that kernel uses it.
+// HAZARD = true opens with the wait states a scalar base fresh from v_readfirstlane needs before a memory instruction reads it (the prologue's DMAs; in
+// the k loop the base comes from scalar adds, which need none).
+template <bool HAZARD>
+__device__ __forceinline__ void q_dma16_s(const char* sbase, unsigned lane16, unsigned lds_dst) {
+	if (HAZARD)
+		asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(lane16), "s"(lds_dst) : "m0");
+	else
+		asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(lane16), "s"(lds_dst) : "m0");
 }
 
 // ---- quantiser: fp64 rows -> NS digit planes in the tiled layout + one exponent per row ----------------------------
@@ -185,18 +182,24 @@ __device__ __forceinline__ void gram_piece_i8(const char* __restrict__ QA, const
 	// the tile row against it: one edge tile's 128 x 32.  Same slots, DMAs per stage, vmcnt accounting and k loop copies; only this prologue knows.
 	const bool host = symmetric && ti == tj && ti < edge_tj;
 	const bool hw = host && wm == 1 && wn < 2;  // waves 4 and 5 of a host tile
-	const char* src0 = (wid < 4 ? QA + (((int64_t)ti * 4 + wid) * nks) * 1024
-								: (host && wid == 4) ? QB + ((int64_t)edge_tj * 4 * nks) * 1024 : qb_t + ((int64_t)(wid - 4) * nks) * 1024) + lane * 16;
+	const char* src_w = wid < 4 ? QA + (((int64_t)ti * 4 + wid) * nks) * 1024
+								: (host && wid == 4) ? QB + ((int64_t)edge_tj * 4 * nks) * 1024 : qb_t + ((int64_t)(wid - 4) * nks) * 1024;
+	// the wave's source base in scalar registers, the lane's 16 bytes of an image in one vector register (q_dma16_s)
+	// (readfirstlane returns a signed int: each half goes through unsigned before it is widened)
+	const unsigned src_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)((uint64_t)src_w >> 32)),
+				   src_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(uint64_t)src_w);
+	const char* src0 = reinterpret_cast<const char*>((uint64_t)src_hi << 32 | (uint64_t)src_lo);
+	const unsigned lane16 = lane * 16;
 	const int64_t plane = wid < 4 ? plane_a : plane_b;
 	const unsigned dst0 = lds0 + wid * NS * 1024;
-	auto issue_one = [&](int buf, int ks, int s) {
+	auto issue_one = [&](int buf, int ks, int s, auto hazard) {
 		if (QI_EXP & 1) return;
 		if (QI_EXP & 2) ks &= 3;
-		q_dma16_nc(src0 + s * plane + (int64_t)ks * 1024, dst0 + buf * STAGE + s * 1024);
+		q_dma16_s<decltype(hazard)::value>(src0 + s * plane + (int64_t)ks * 1024, lane16, dst0 + buf * STAGE + s * 1024);
 	};
 	auto issue = [&](int buf, int ks) {
 #pragma unroll
-		for (int s = 0; s < NS; s++) issue_one(buf, ks, s);
+		for (int s = 0; s < NS; s++) issue_one(buf, ks, s, std::true_type{});
 	};
 	i16_t acc[NS][2];
 	auto clear = [&]() {
@@ -317,7 +320,7 @@ __device__ __forceinline__ void gram_piece_i8(const char* __restrict__ QA, const
 		};
 		auto dma = [&](int j) {
 			__builtin_amdgcn_sched_barrier(0);
-			issue_one(nbuf, nks, j);
+			issue_one(nbuf, nks, j, std::false_type{});
 			__builtin_amdgcn_sched_barrier(0);
 		};
 		if (MASK) {

@@ -40,6 +40,25 @@ static inline int nrm_assoc_check_args(const void* dx, int64_t nx, int64_t ny, c
 	return NRM_OK;
 }
 
+// ---- K1 routing (csrc/nrm_residualize.hip, launch_residualize) -------------------------------------------------------------------------------------------------
+// vec: the 16-byte row loads of k_residualize_v4 / _v8 apply (aligned pointers and pitches; otherwise the scalar k_residualize runs).
+static inline bool nrm_k1_vec(uint64_t x_addr, int64_t x_elem_bytes, int64_t ldx, bool has_out, uint64_t out_addr, int64_t ldo, int active, uint64_t c_addr,
+							  int64_t ldc) {
+	const int64_t xa = 16 / x_elem_bytes;
+	return (ldx % xa == 0) && (x_addr % 16 == 0) && (!has_out || ((ldo % 4 == 0) && (out_addr % 16 == 0))) && (!active || (ldc % 2 == 0 && c_addr % 16 == 0));
+}
+// stream_rows: input rows loaded non-temporally -- fp32 rows against at least 8 MB of covariates, which then stay in L2
+static inline bool nrm_k1_stream_rows(int active, int64_t x_elem_bytes, int64_t nc, int64_t n) { return active && x_elem_bytes == 4 && nc * n * 8 >= (8 << 20); }
+// rows8: k_residualize_v8, eight rows per workgroup with the covariate slices staged in LDS, CAN run
+static inline bool nrm_k1_rows8(bool vec, int active, int64_t nc, int64_t rows_pad, bool stream_rows) {
+	return vec && active && nc <= 8 && rows_pad % 8 == 0 && !stream_rows;
+}
+// ... and pays: rows of at least 16 384 cells.  Measured, alternating with k_residualize_v4 in one process (profiles/k1_rows8_ab.txt, k1_rows8_cross.txt), fp32 rows
+// with 3 covariates: 5000 x 10 000 0.180 -> 0.213 ms (625 workgroups, one per CU, are 2.4 rounds of 256 with nothing to fill the last, where the old kernel's
+// 1250 half-size ones pack it), x 16 384 0.322 -> 0.324, x 24 576 0.487 -> 0.444, x 32 768 0.641 -> 0.611; 16 000 x 50 000 with 5: 3.27 -> 3.08; the
+// 3840 x 500 000 fp64 slice: 9.83 -> 8.22.  NRM_DEBUG="k1_rows8=1" runs it wherever it can (the tests' small shapes), "k1_rows8=0" nowhere.
+static inline bool nrm_k1_rows8_pays(int64_t n) { return n >= 16384; }
+
 #define GM 128
 #define GN 128
 

@@ -1,4 +1,4 @@
-// Pieces shared by the K1 kernels (nrm_residualize.hip: k_residualize, k_residualize_v4; tools/experiments/nrm_residualize_res.hip: k_residualize_res).
+// Pieces shared by the K1 kernels (nrm_residualize.hip: k_residualize, k_residualize_v4, k_residualize_v8; tools/experiments/nrm_residualize_res.hip: k_residualize_res).
 #pragma once
 #include "nrm_device.h"
 #include "nrm_digits.h"

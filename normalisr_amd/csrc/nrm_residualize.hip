@@ -13,6 +13,7 @@
 // One workgroup (256 threads) owns RES_R consecutive rows so that every covariate element fetched
 // from L2 is used RES_R times; covariates are swept in chunks of RES_CB to bound registers.
 #include "nrm_k1.h"
+#include "nrm_host_logic.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -478,6 +479,414 @@ __global__ void __launch_bounds__(256, K1_MINW) k_residualize_v4(const T* __rest
 	}
 }
 
+// Eight rows per workgroup: two groups of 256 threads, each of which IS a k_residualize_v4 workgroup on four consecutive rows -- the same thread -> cell map
+// with tid & 255 for tid, the same order of every sum and reduction, its own bound, s_loose decision and extra sweep, the same digits, record sums and
+// store addresses: every output is bit for bit what k_residualize_v4 writes.  What the groups share is the covariates.  k_residualize_v4 reads all nc x n
+// covariate values from L2 twice per four rows, inside the step that consumes them (C2: 1250 workgroups x 2 x 240 KB = 600 MB for a 200 MB matrix); here
+// the 512 threads stage the slice C[q][k0 .. k0 + 1024) of every step in LDS once -- two buffers, the slice of step j + 1 loaded into registers before step
+// j is computed and written to the other buffer after it, one barrier per step -- and both groups take their cv[4] from LDS.  The rows of step j + 1 are
+// requested ahead in the product sweep too: a step ends in a barrier, so nothing else keeps two steps of loads in flight.
+// LDS image of a slice and covariate: 512 units of 16 bytes, unit h * 256 + t holding cells 4 t + 2 h, 4 t + 2 h + 1: reader t takes units t and 256 + t (every
+// wave reads 1 KB contiguous twice), loader wave w moves cells [128 w, 128 w + 128) -- lanes 0-31 the even pairs, 32-63 the odd ones, 1 KB contiguous in global
+// memory.  Only cells of the vector path (k < n4) are staged; a loader past them re-reads the last pair below n4 of the same covariate row, so no address
+// at or beyond c + q * ldc + n is formed; the scalar tail reads global memory as before.  nc <= CB (one covariate chunk).
+template <typename T, int CB, int NS>
+__global__ void __launch_bounds__(512) k_residualize_v8(const T* __restrict__ x, int64_t rows, int64_t n, int64_t ldx,
+														 const double* __restrict__ c, int nc, int64_t ldc,
+														 const double* __restrict__ dci, int active, double* __restrict__ out,
+														 int64_t ldo, double* __restrict__ ss, double* __restrict__ coef, QuantOut qo) {
+	__shared__ double s_part[2][4][RES_R * CB];
+	extern __shared__ double2 s_dyn8[];  // (16-byte aligned: the slices are written and read 16 bytes at a time)
+	double* const s_dyn = reinterpret_cast<double*>(s_dyn8);
+	__shared__ double s_ss[2][4][RES_R];
+	const int g = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);  // the group: rows 4 g .. 4 g + 3 of the workgroup's eight
+	const int tid = threadIdx.x & 255, lane = tid & 63, wid = tid >> 6;
+	double* const ta = s_dyn + (size_t)g * 2 * RES_R * nc;  // [RES_R][nc]  x_i C^T
+	double* const tb = ta + (size_t)RES_R * nc;              // [RES_R][nc]  (x_i C^T) dci
+	double* const cst = s_dyn + (size_t)4 * RES_R * (nc > 0 ? nc : 1);  // [2][nc][1024] covariate slices
+	const int64_t row0 = (int64_t)blockIdx.x * (2 * RES_R) + g * RES_R;
+	const int64_t n4 = n & ~(int64_t)3;
+	const int64_t nst = active ? (n4 + 1023) >> 10 : 0;  // slices that hold cells of the vector path
+	const T* xr[RES_R];
+	bool live[RES_R];
+#pragma unroll
+	for (int r = 0; r < RES_R; r++) {
+		live[r] = row0 + r < rows;
+		xr[r] = x + (live[r] ? (row0 + r) : 0) * ldx;
+	}
+	// loader role of this thread, and the slice pipeline
+	const int w8 = (int)threadIdx.x >> 6;
+	const int ld_cell = 128 * w8 + 4 * (lane & 31) + 2 * (lane >> 5), ld_unit = (lane >> 5) * 256 + 32 * w8 + (lane & 31);
+	typedef double d2_t __attribute__((ext_vector_type(2)));
+	d2_t creg[CB];
+	auto stage_load = [&](int64_t j) {
+		if (j < nst) {
+			int64_t kk = j * 1024 + ld_cell;
+			kk = kk < n4 ? kk : n4 - 2;
+#pragma unroll
+			for (int q = 0; q < CB; q++)
+				if (q < nc) creg[q] = *reinterpret_cast<const d2_t*>(c + (int64_t)q * ldc + kk);
+		}
+	};
+	auto stage_write = [&](int64_t j) {
+		if (j < nst) {
+			double* b = cst + (size_t)(j & 1) * nc * 1024 + 2 * ld_unit;
+#pragma unroll
+			for (int q = 0; q < CB; q++)
+				if (q < nc) *reinterpret_cast<d2_t*>(b + q * 1024) = creg[q];
+		}
+	};
+	auto cov4 = [&](int64_t j, int q, double (&cv)[4]) {
+		const double* b = cst + ((size_t)(j & 1) * nc + q) * 1024 + 2 * tid;
+		const d2_t lo = *reinterpret_cast<const d2_t*>(b), hi = *reinterpret_cast<const d2_t*>(b + 512);
+		cv[0] = lo[0], cv[1] = lo[1], cv[2] = hi[0], cv[3] = hi[1];
+	};
+	// nsteps steps of 1024 cells; body(j, k) runs between the request for slice j + 1 and its write into the free buffer
+	auto steps = [&](int64_t nsteps, auto body) {
+		stage_load(0);
+		stage_write(0);
+		__syncthreads();
+		for (int64_t j = 0; j < nsteps; j++) {
+			stage_load(j + 1);
+			body(j, (int64_t)tid * 4 + j * 1024);
+			stage_write(j + 1);
+			__syncthreads();
+		}
+	};
+	double xmax[RES_R], xsq[RES_R];
+#pragma unroll
+	for (int r = 0; r < RES_R; r++) xmax[r] = xsq[r] = 0.0;
+	if (active) {
+		double acc[RES_R][CB];
+#pragma unroll
+		for (int r = 0; r < RES_R; r++)
+#pragma unroll
+			for (int q = 0; q < CB; q++) acc[r][q] = 0.0;
+		T xnext[RES_R][4];
+		if ((int64_t)tid * 4 < n4) {
+#pragma unroll
+			for (int r = 0; r < RES_R; r++) nrm_ld4<T, true, false>(xr[r] + (int64_t)tid * 4, xnext[r]);
+		}
+		steps(nst, [&](int64_t j, int64_t k) {
+			if (k < n4) {
+				double xv[RES_R][4];
+#pragma unroll
+				for (int r = 0; r < RES_R; r++)
+#pragma unroll
+					for (int i = 0; i < 4; i++) xv[r][i] = (double)xnext[r][i];
+				if (k + 1024 < n4) {
+#pragma unroll
+					for (int r = 0; r < RES_R; r++) nrm_ld4<T, true, false>(xr[r] + k + 1024, xnext[r]);
+				}
+				if (NS) {
+#pragma unroll
+					for (int r = 0; r < RES_R; r++)
+#pragma unroll
+						for (int i = 0; i < 4; i++) {
+							xmax[r] = fmax(xmax[r], fabs(xv[r][i]));
+							xsq[r] = fma(xv[r][i], xv[r][i], xsq[r]);
+						}
+				}
+#pragma unroll
+				for (int q = 0; q < CB; q++) {
+					if (q < nc) {
+						double cv[4];
+						cov4(j, q, cv);
+#pragma unroll
+						for (int r = 0; r < RES_R; r++)
+#pragma unroll
+							for (int i = 0; i < 4; i++) acc[r][q] = fma(xv[r][i], cv[i], acc[r][q]);
+					}
+				}
+			}
+		});
+		for (int64_t k = n4 + tid; k < n; k += 256) {  // tail cells when n % 4 != 0
+			if (NS) {
+#pragma unroll
+				for (int r = 0; r < RES_R; r++) {
+					xmax[r] = fmax(xmax[r], fabs((double)xr[r][k]));
+					xsq[r] = fma((double)xr[r][k], (double)xr[r][k], xsq[r]);
+				}
+			}
+#pragma unroll
+			for (int q = 0; q < CB; q++) {
+				if (q < nc) {
+					double cv = c[(int64_t)q * ldc + k];
+#pragma unroll
+					for (int r = 0; r < RES_R; r++) acc[r][q] = fma((double)xr[r][k], cv, acc[r][q]);
+				}
+			}
+		}
+#pragma unroll
+		for (int r = 0; r < RES_R; r++)
+#pragma unroll
+			for (int q = 0; q < CB; q++) {
+				double v = nrm_wave_sum(live[r] ? acc[r][q] : 0.0);
+				if (lane == 0) s_part[g][wid][r * CB + q] = v;
+			}
+		__syncthreads();
+		if (tid < RES_R * CB) {
+			int r = tid / CB, q = tid % CB;
+			if (q < nc) ta[r * nc + q] = s_part[g][0][tid] + s_part[g][1][tid] + s_part[g][2][tid] + s_part[g][3][tid];
+		}
+		__syncthreads();
+		for (int i = tid; i < RES_R * nc; i += 256) {
+			int r = i / nc, q = i % nc;
+			double v = 0.0;
+			for (int e = 0; e < nc; e++) v = fma(dci[(int64_t)q * nc + e], ta[r * nc + e], v);
+			tb[r * nc + q] = v;
+			if (coef && live[r]) coef[(row0 + r) * nc + q] = v;
+		}
+		__syncthreads();
+	}
+	// residual of 4 consecutive cells k..k+3 of the group's rows in step j (zeros past the end of the row and for padding rows)
+	auto residual4 = [&](int64_t j, int64_t k, double (&v)[RES_R][4]) {
+		if (k < n4) {
+#pragma unroll
+			for (int r = 0; r < RES_R; r++) nrm_ld4<T, true, false>(xr[r] + k, v[r]);
+			if (active) {
+				for (int q = 0; q < nc; q++) {
+					double cv[4];
+					cov4(j, q, cv);
+#pragma unroll
+					for (int r = 0; r < RES_R; r++)
+#pragma unroll
+						for (int i = 0; i < 4; i++) v[r][i] = fma(-tb[r * nc + q], cv[i], v[r][i]);
+				}
+			}
+		} else {
+#pragma unroll
+			for (int i = 0; i < 4; i++) {
+				const int64_t kk = k + i;
+#pragma unroll
+				for (int r = 0; r < RES_R; r++) v[r][i] = (kk < n) ? (double)xr[r][kk] : 0.0;
+				if (active && kk < n) {
+					for (int q = 0; q < nc; q++) {
+						double cv = c[(int64_t)q * ldc + kk];
+#pragma unroll
+						for (int r = 0; r < RES_R; r++) v[r][i] = fma(-tb[r * nc + q], cv, v[r][i]);
+					}
+				}
+			}
+		}
+#pragma unroll
+		for (int r = 0; r < RES_R; r++)
+			if (!live[r]) v[r][0] = v[r][1] = v[r][2] = v[r][3] = 0.0;
+	};
+	// fixed-point scale of each row: k_residualize_v4's bound and decision, per group
+	__shared__ double s_mx[2][4][RES_R], s_sq[2][4][RES_R];
+	__shared__ int s_sh[2][RES_R], s_loose[2];
+	int sh[RES_R];
+	if (NS) {
+		constexpr int B = 8 * NS - 2;
+		const bool bounded = active && qo.cmax != nullptr;
+		auto reduce_max = [&]() {
+#pragma unroll
+			for (int r = 0; r < RES_R; r++) {
+				double v = xmax[r], q = nrm_wave_sum(xsq[r]);
+#pragma unroll
+				for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+				if (lane == 0) {
+					s_mx[g][wid][r] = v;
+					s_sq[g][wid][r] = q;
+				}
+			}
+		};
+		if (tid == 0) s_loose[g] = 0;
+		if (bounded) {
+			reduce_max();
+			__syncthreads();
+			if (tid < RES_R) {
+				double m = fmax(fmax(s_mx[g][0][tid], s_mx[g][1][tid]), fmax(s_mx[g][2][tid], s_mx[g][3][tid]));
+				const double sq = (s_sq[g][0][tid] + s_sq[g][1][tid]) + (s_sq[g][2][tid] + s_sq[g][3][tid]);
+				double proj = 0.0;
+				for (int q = 0; q < nc; q++) {
+					m = fma(fabs(tb[tid * nc + q]), qo.cmax[q], m);
+					proj = fma(ta[tid * nc + q], tb[tid * nc + q], proj);
+				}
+				const double est = sq - proj;
+				if (live[tid] && !(est > 1e-8 * sq && m * m * (double)n <= (RES_LOOSE * RES_LOOSE) * est)) s_loose[g] = 1;
+				s_mx[g][0][tid] = m;
+			}
+			__syncthreads();
+		}
+		const bool sweep = !bounded || s_loose[g] != 0;                          // this group's decision, as k_residualize_v4 takes it for its four rows
+		const bool any = !bounded || s_loose[0] != 0 || s_loose[1] != 0;  // both groups walk the slices when either sweeps
+		if (any) {
+			__syncthreads();
+#pragma unroll
+			for (int r = 0; r < RES_R; r++) xmax[r] = xsq[r] = 0.0;
+			const int64_t kmax = (n + 3) & ~(int64_t)3;
+			steps((kmax + 1023) >> 10, [&](int64_t j, int64_t k) {
+				if (sweep && k < kmax) {
+					double v[RES_R][4];
+					residual4(j, k, v);
+#pragma unroll
+					for (int r = 0; r < RES_R; r++)
+#pragma unroll
+						for (int i = 0; i < 4; i++) xmax[r] = fmax(xmax[r], fabs(v[r][i]));
+				}
+			});
+			if (sweep) reduce_max();
+			__syncthreads();
+			if (sweep && tid < RES_R) s_mx[g][0][tid] = fmax(fmax(s_mx[g][0][tid], s_mx[g][1][tid]), fmax(s_mx[g][2][tid], s_mx[g][3][tid]));
+			__syncthreads();
+		}
+		if (tid < RES_R) {
+			const double m = s_mx[g][0][tid];
+			int e = 0;
+			if (m > 0.0 && m < INFINITY) (void)frexp(m, &e);
+			s_sh[g][tid] = e - B;
+			qo.exps[row0 + tid] = e - B;
+		}
+		__syncthreads();
+#pragma unroll
+		for (int r = 0; r < RES_R; r++) sh[r] = s_sh[g][r];
+	}
+	char* qrow[RES_R];
+	int flip[RES_R];
+#pragma unroll
+	for (int r = 0; r < RES_R; r++) {
+		const int64_t row = row0 + r;
+		const int rr = (int)(row & 31);
+		qrow[r] = NS ? qo.q + ((row >> 5) * qo.cks) * 1024 + (2 * rr) * 16 : nullptr;
+		flip[r] = (rr >> 3) & 1;
+	}
+	double sq[RES_R];
+#pragma unroll
+	for (int r = 0; r < RES_R; r++) sq[r] = 0.0;
+	constexpr int NP = NS >= 2 ? NS - 1 : 1;
+	int dsum[RES_R][NP];
+	unsigned dsq[RES_R][NP];
+#pragma unroll
+	for (int r = 0; r < RES_R; r++)
+#pragma unroll
+		for (int s = 0; s < NP; s++) {
+			dsum[r][s] = 0;
+			dsq[r][s] = 0u;
+		}
+	const int64_t kres = out ? ldo : ((n + 3) & ~(int64_t)3), kq = NS ? qo.nks * 32 : 0;
+	T xnext[RES_R][4];
+	auto request = [&](int64_t k, T (&raw)[RES_R][4]) {
+		if (k < n4) {
+#pragma unroll
+			for (int r = 0; r < RES_R; r++) nrm_ld4<T, true, false>(xr[r] + k, raw[r]);
+		} else {
+#pragma unroll
+			for (int r = 0; r < RES_R; r++)
+#pragma unroll
+				for (int i = 0; i < 4; i++) raw[r][i] = (k + i < n) ? xr[r][k + i] : (T)0;
+		}
+	};
+	auto residual_of = [&](int64_t j, int64_t k, const T (&raw)[RES_R][4], double (&v)[RES_R][4]) {
+#pragma unroll
+		for (int r = 0; r < RES_R; r++)
+#pragma unroll
+			for (int i = 0; i < 4; i++) v[r][i] = (double)raw[r][i];
+		if (active && k < n) {
+			if (k < n4) {
+				for (int q = 0; q < nc; q++) {
+					double cv[4];
+					cov4(j, q, cv);
+#pragma unroll
+					for (int r = 0; r < RES_R; r++)
+#pragma unroll
+						for (int i = 0; i < 4; i++) v[r][i] = fma(-tb[r * nc + q], cv[i], v[r][i]);
+				}
+			} else {
+				for (int q = 0; q < nc; q++)
+#pragma unroll
+					for (int i = 0; i < 4; i++) {
+						const double cv = (k + i < n) ? c[(int64_t)q * ldc + k + i] : 0.0;
+#pragma unroll
+						for (int r = 0; r < RES_R; r++) v[r][i] = fma(-tb[r * nc + q], cv, v[r][i]);
+					}
+			}
+		}
+#pragma unroll
+		for (int r = 0; r < RES_R; r++)
+			if (!live[r]) v[r][0] = v[r][1] = v[r][2] = v[r][3] = 0.0;
+	};
+	constexpr bool AHEAD = sizeof(T) == 4;  // (as k_residualize_v4 measured it for this sweep)
+	const int64_t kend = kres > kq ? kres : kq;
+	if (AHEAD && (int64_t)tid * 4 < kend) request((int64_t)tid * 4, xnext);
+	steps((kend + 1023) >> 10, [&](int64_t j, int64_t k) {
+		if (k < kend) {
+			T xcur[RES_R][4];
+			if (AHEAD) {
+#pragma unroll
+				for (int r = 0; r < RES_R; r++)
+#pragma unroll
+					for (int i = 0; i < 4; i++) xcur[r][i] = xnext[r][i];
+				if (k + 1024 < kend) request(k + 1024, xnext);
+			} else
+				request(k, xcur);
+			double v[RES_R][4];
+			residual_of(j, k, xcur, v);
+#pragma unroll
+			for (int r = 0; r < RES_R; r++) {
+				if (out && k < ldo) {
+					double* o = out + (row0 + r) * ldo + k;
+					*reinterpret_cast<double2*>(o) = make_double2(v[r][0], v[r][1]);
+					*reinterpret_cast<double2*>(o + 2) = make_double2(v[r][2], v[r][3]);
+				}
+#pragma unroll
+				for (int i = 0; i < 4; i++) sq[r] = fma(v[r][i], v[r][i], sq[r]);
+			}
+			if (NS && k < kq) {
+				const int kk = (int)(k & 31);
+				const int ks_all = (int)(k >> 5), chunk = ks_all / (int)qo.cks;
+				const int64_t ks = (int64_t)(ks_all - chunk * (int)qo.cks) + chunk * (qo.chunk_bytes >> 10);
+#pragma unroll
+				for (int r = 0; r < RES_R; r++) {
+					unsigned w[NS ? NS : 1];
+					nrm_digits4<(NS ? NS : 1)>(v[r], sh[r], w);
+					char* dst = qrow[r] + ks * 1024 + (((kk >> 4) ^ flip[r]) << 4) + (kk & 15);
+#pragma unroll
+					for (int s = 0; s < (NS ? NS : 1); s++) *reinterpret_cast<unsigned*>(dst + s * qo.plane_bytes) = w[s];
+#pragma unroll
+					for (int s = 0; s < NP; s++) {
+						dsum[r][s] = __builtin_amdgcn_sdot4((int)w[s], 0x01010101, dsum[r][s], false);
+						dsq[r][s] = (unsigned)__builtin_amdgcn_sdot4((int)w[s], (int)w[s], (int)dsq[r][s], false);
+					}
+				}
+			}
+		}
+	});
+#pragma unroll
+	for (int r = 0; r < RES_R; r++) {
+		double v = nrm_wave_sum(sq[r]);
+		if (lane == 0) s_ss[g][wid][r] = v;
+	}
+	__shared__ long long s_ds[2][4][RES_R][NP], s_dq[2][4][RES_R][NP];
+	if (NS && qo.fix) {
+#pragma unroll
+		for (int r = 0; r < RES_R; r++)
+#pragma unroll
+			for (int s = 0; s < NP; s++) {
+				const long long a = wave_sum_i32(dsum[r][s]), b = wave_sum_u32(dsq[r][s]);
+				if (lane == 0) {
+					s_ds[g][wid][r][s] = a;
+					s_dq[g][wid][r][s] = b;
+				}
+			}
+	}
+	__syncthreads();
+	if (tid < RES_R) {
+		const double ssr = s_ss[g][0][tid] + s_ss[g][1][tid] + s_ss[g][2][tid] + s_ss[g][3][tid];
+		ss[row0 + tid] = ssr;
+		if (NS && qo.fix) {
+			double S[5] = {0, 0, 0, 0, 0}, Q[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+			for (int s = 0; s < NP; s++) {
+				S[s] = (double)((s_ds[g][0][tid][s] + s_ds[g][1][tid][s]) + (s_ds[g][2][tid][s] + s_ds[g][3][tid][s]));
+				Q[s] = (double)((s_dq[g][0][tid][s] + s_dq[g][1][tid][s]) + (s_dq[g][2][tid][s] + s_dq[g][3][tid][s]));
+			}
+			nrm_fix_record<NS>(qo.fix + (row0 + tid) * NRM_FIX_STRIDE, S, Q, s_sh[g][tid], ssr, (double)n);
+		}
+	}
+}
+
 template <typename T>
 static void launch_residualize(bool vec, const T* x, int64_t rows, int64_t n, int64_t ldx, const double* c, int nc, int64_t ldc,
 							   const double* dci, int active, double* out, int64_t ldo, int64_t rows_pad, double* ss, double* coef,
@@ -485,7 +894,24 @@ static void launch_residualize(bool vec, const T* x, int64_t rows, int64_t n, in
 	dim3 grid((unsigned)(rows_pad / RES_R));
 	const size_t lds = (size_t)2 * RES_R * (nc > 0 ? nc : 1) * sizeof(double);
 	// input rows loaded non-temporally (nrm_k1.h): fp32 rows against at least 8 MB of covariates, which then stay in L2
-	const bool stream_rows = active && sizeof(T) == 4 && (int64_t)nc * n * 8 >= (8 << 20);
+	const bool stream_rows = nrm_k1_stream_rows(active, sizeof(T), nc, n);
+	// eight rows per workgroup, covariate slices through LDS: where it can run and rows are long enough to pay (nrm_host_logic.h).  NRM_DEBUG="k1_rows8=0" / "=1",
+	// read at every launch: nowhere / wherever it can, for A/B timing and the tests
+	if (nrm_k1_rows8(vec, active, nc, rows_pad, stream_rows) && !nrm_debug_is("k1_rows8", "0") && (nrm_k1_rows8_pays(n) || nrm_debug_is("k1_rows8", "1"))) {
+		const size_t lds8 = ((size_t)4 * RES_R * nc + (size_t)2 * nc * 1024) * sizeof(double);  // both groups' tables, two slices of nc x 1024 covariate values
+		auto go8 = [&](auto kern) {
+			if (lds8 > 48 * 1024)
+				(void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
+			hipLaunchKernelGGL(kern, dim3((unsigned)(rows_pad / (2 * RES_R))), dim3(512), lds8, st, x, rows, n, ldx, c, nc, ldc, dci, active, out, ldo, ss, coef, qo);
+		};
+		if (nslices == 6)
+			nc <= 4 ? go8(k_residualize_v8<T, 4, 6>) : go8(k_residualize_v8<T, 8, 6>);
+		else if (nslices == 5)
+			nc <= 4 ? go8(k_residualize_v8<T, 4, 5>) : go8(k_residualize_v8<T, 8, 5>);
+		else
+			nc <= 4 ? go8(k_residualize_v8<T, 4, 0>) : go8(k_residualize_v8<T, 8, 0>);
+		return;
+	}
 	auto go = [&](auto kern, auto... extra) {
 		if (lds > 48 * 1024)  // beyond the default dynamic-LDS window (more than 768 covariates)
 			(void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -516,9 +942,7 @@ static int residualize_impl(const void* d_x, int x_dtype, int64_t rows, int64_t 
 	NRM_REQUIRE(d_x || rows == 0, "nrm_residualize: null input");
 	int active = (rank > 0 && nc > 0) ? 1 : 0;
 	NRM_REQUIRE(!active || (d_c && d_dci && ldc >= n), "Unmatching dx/dy/dc dimensions.");
-	const int64_t xa = 16 / (x_dtype == NRM_F64 ? 8 : 4);
-	const bool vec = (ldx % xa == 0) && ((uintptr_t)d_x % 16 == 0) && (!d_out || ((ldo % 4 == 0) && ((uintptr_t)d_out % 16 == 0))) &&
-					 (!active || (ldc % 2 == 0 && (uintptr_t)d_c % 16 == 0));
+	const bool vec = nrm_k1_vec((uintptr_t)d_x, x_dtype == NRM_F64 ? 8 : 4, ldx, d_out != nullptr, (uintptr_t)d_out, ldo, active, (uintptr_t)d_c, ldc);
 	QuantOut qo = {nullptr, 0, 0, 0, 0, nullptr, d_cmax, d_fix};
 	if (nslices) {
 		NRM_REQUIRE(nslices == 5 || nslices == 6, "nrm_residualize_q: 5 or 6 slices");
