@@ -374,6 +374,21 @@ int nrm_single1_group_stats(const int64_t* d_seg, const int64_t* d_cells, const 
  * [2] groupings with a single value on their selected cells (:917-918), [3] groupings with dof <= 0, [4] groupings whose M_i is not finite.  nc <= 8. */
 int nrm_single1_group_info(const double* d_gs, const double* d_gram_part, const double* d_rowinfo, const int64_t* d_sel_info, int64_t nc, int64_t nx,
 						   int dimreduce, double* d_info, int64_t info_pitch, double* d_varx, int32_t* d_flags, void* stream);
+/* The same two steps for 1 <= nc <= 32 covariates, a wave per grouping (association.py:350-374).
+ *   nrm_single1_group_stats_wide: d_out in the packing of nrm_single1_group_stats, from d_ce (d_seg[nx], nc) -- the covariates at the groupings' own cells
+ *     in segment order, as nrm_single1_select writes them; it takes the place of (d_cells, d_c, ldc): nothing is gathered -- and d_xe.  Every output is one
+ *     fma chain over the segment's cells in their order, starting from 0 (len roundings): the same bits every run.  Empty segments give zeros.
+ *   nrm_single1_group_info_wide: the arguments, records (d_info (nx, info_pitch >= 26 + nc + nc nc)), d_varx and counters d_flags[2], [3], [4] of
+ *     nrm_single1_group_info.  M_i = (the shared cells' matrix: all nb (nb + 1) / 2 blocks of d_gram_part, nb = ceil(nc / 8), each added up over its
+ *     partial sums in block order) + (the grouping's own, d_gs); pseudo-inverse and INTEGER rank by cyclic Jacobi with the lanes of the wave sharing a
+ *     rotation, |eigenvalue| >= 1e-8 x the largest kept (association.py:77-80,350-351); ccx_i, vx_i (0 -> 1, :362-364), dof_i = ns_i - 1 - rank_i -
+ *     dimreduce and its P-value plan (:372-374).  A non-finite M_i counts into d_flags[4] and continues on the identity.
+ *   nrm_single1_group_info_wide_host: the same routine with one lane on HOST arrays (flags int32[8], counted into) -- no device, no HIP call. */
+int nrm_single1_group_stats_wide(const int64_t* d_seg, const double* d_xe, const double* d_ce, int64_t nc, int64_t nx, double* d_out, void* stream);
+int nrm_single1_group_info_wide(const double* d_gs, const double* d_gram_part, const double* d_rowinfo, const int64_t* d_sel_info, int64_t nc, int64_t nx,
+								int dimreduce, double* d_info, int64_t info_pitch, double* d_varx, int32_t* d_flags, void* stream);
+int nrm_single1_group_info_wide_host(const double* gs, const double* gram_part, const double* rowinfo, const int64_t* sel_info, int64_t nc, int64_t nx,
+									 int dimreduce, double* info, int64_t pitch, double* varx, int32_t* flags);
 
 /*
  * binnet -- binarise a (ng, ng) co-expression P-value matrix at a per-row Benjamini-Hochberg q-value cutoff
@@ -502,7 +517,9 @@ int nrm_association_tests_host(const void* h_dx, int x_dtype, int64_t nx,
  * and out, no torch.  Outputs as the reference returns them: h_p, h_stat (gamma, or gamma * varx when return_dot), h_vary (nx, ny), h_varx (nx),
  * h_alpha (nx, ny, nc) or NULL -- all of out_dtype.  NRM_E_UNSUPPORTED (nrm_last_error says why) for calls outside what the entry covers:
  *   nrm_association_tests_single1_host (`-m single`, association.py:263-390,911-925): design entries >= 0 of which at most a quarter are set,
- *     at most 32 covariates (the gRNA incidence of a screen; the package's masked-Gram path takes the rest);
+ *     at most 32 covariates (the gRNA incidence of a screen; the package's masked-Gram path takes the rest); the groupings' statistics stay on the device
+ *     at every covariate count (nrm_single1_group_stats[_wide] + nrm_single1_group_info[_wide]), NRM_DEBUG="single1_stats=host" finishes them on the host
+ *     from 9 covariates as before, and NRM_DEBUG="s1_trace=1" says on stderr which of the two a call with 9 .. 32 covariates took;
  *   nrm_association_tests_single4_host (`-m covariate`, association.py:421-576,926-980): the closed form for full-rank designs -- rank == nc
  *     (h_dci, rank from the host's inv_rank of C C^T) and A A^T certified full rank at `tol` (association.py:77) from norms at hand; a sparse design
  *     goes through the sparse-design kernels, any other through nrm_residualize + nrm_gram_f64;

@@ -20,9 +20,9 @@ DEBUG_KEYS = {
 	's4_inverse': "host: single=4 inverts M~ with LAPACK instead of the on-device Newton-Schulz iteration",
 	's4_start': "norm: that iteration from I / ||M~||_1 only",
 	's4_sparse_m': "0: single=4 on a sparse design takes M~ from K1's residuals and the fp64 Gram kernel",
-	's4_trace': "1: phase times of a single=4 call", 's1_trace': "1: phase times of a single=1 call",
+	's4_trace': "1: phase times of a single=4 call", 's1_trace': "1: phase times of a single=1 call (the C entry: where it finishes the groupings' statistics)",
 	'single1': "dense: single=1 through the masked Gram contractions whatever the design",
-	'single1_stats': "host: single=1 finishes the groupings' statistics (pseudo-inverses, ranks, P-value plans) on the host as rounds 3-5 did",
+	'single1_stats': "host: single=1 finishes the groupings' statistics (pseudo-inverses, ranks, P-value plans) on the host as rounds 3-5 did, at any covariate count (the C entry: from 9 covariates)",
 	's4_plan': "public: a Single4Plan calls the public function every step (no lean device-only replay)",
 	'normvar': "host: normvar through the Gram launches and the host's batched pseudo-inverses",
 	'nv_gene_block': "normvar with more than 63 covariates: genes per block of the device path (default: from a 1.5 GiB budget)",

@@ -1,6 +1,7 @@
 // nrm_association_tests_single1_host (`normalisr de -m single`: association.py:263-390,911-925), numpy buffers in, numpy buffers out, no torch: the kernels
 // normalisr_amd/single1.py drives through the device-pointer entries, sequenced here in C++ with the library's own scratch pool.
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -72,8 +73,18 @@ extern "C" int nrm_association_tests_single1_host(const void* h_dx, int x_dtype,
 		NRM_TRY(nrm_single1_group_info(gsd.as<double>(), gpart.as<double>(), rowinfo.as<double>(), info.as<int64_t>(), nc, nx, dimreduce, drec.as<double>(), pitch,
 									   dvarx.as<double>(), flags.as<int32_t>(), st));
 		NRM_HIP(hipStreamSynchronize(st));  // (gsd is released at the end of this block)
+	} else if (!nrm_debug_is("single1_stats", "host")) {
+		// 9 .. 32 covariates: the same two steps with a wave per grouping (nrm_single1_group_stats_wide + nrm_single1_group_info_wide)
+		if (nrm_debug_is("s1_trace", "1")) fprintf(stderr, "single=1: the groupings' statistics on the device (wide), %lld covariates\n", (long long)nc);
+		DevBuf gsd;
+		NRM_TRY(gsd.alloc((size_t)nx * gsw * 8));
+		NRM_TRY(nrm_single1_group_stats_wide(seg.as<int64_t>(), xe.as<double>(), ce.as<double>(), nc, nx, gsd.as<double>(), st));
+		NRM_TRY(nrm_single1_group_info_wide(gsd.as<double>(), gpart.as<double>(), rowinfo.as<double>(), info.as<int64_t>(), nc, nx, dimreduce, drec.as<double>(), pitch,
+											dvarx.as<double>(), flags.as<int32_t>(), st));
+		NRM_HIP(hipStreamSynchronize(st));
 	} else {
-		// more than 8 covariates: the statistics on the host, as in rounds 4-5 (nrm_host_math.h)
+		// NRM_DEBUG=single1_stats=host: the statistics on the host, as in rounds 4-5 (nrm_host_math.h)
+		if (nrm_debug_is("s1_trace", "1")) fprintf(stderr, "single=1: the groupings' statistics on the host, %lld covariates\n", (long long)nc);
 		std::vector<double> hrows, hpart, ns, mcc, gs, rec, dof, hxe;
 		std::vector<int64_t> hseg, hidx;
 		NRM_TRY(download(hrows, rowinfo.p, (size_t)nx * 3));

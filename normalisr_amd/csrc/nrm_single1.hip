@@ -542,6 +542,7 @@ extern "C" int nrm_single1_group_stats(const int64_t* d_seg, const int64_t* d_ce
 //     flags[2] groupings with a single value on their selected cells (association.py:917-918, AssertionError)
 //     flags[3] groupings with dof <= 0 ("Insufficient number of cells")        flags[4] groupings whose M_i is not finite (the SVD's ValueError)
 #include "nrm_jacobi.h"
+#include "nrm_jacobi_lanes.h"
 #include "nrm_pvalue_plan.h"
 
 template <int NC>
@@ -630,6 +631,192 @@ extern "C" int nrm_single1_group_info(const double* d_gs, const double* d_gram_p
 	}
 #undef S1_GI
 	return nrm_check_launch("k_s1_group_info");
+}
+
+// ---- 9 .. 32 covariates: the same two steps with a WAVE per grouping ----------------------------------------------------------------------------
+// Up to 32 * 33 / 2 + 32 + 1 = 561 sums and a 32 x 32 matrix per grouping do not fit one lane's registers (the two kernels above), so the lanes of a wave
+// share them.  Neither kernel is on the path the expression matrix sets: Single1Plan runs them beside k_s1_stream.
+//
+// k_s1_group_stats_wide: the packed sums of k_s1_group_stats from ce (entries, nc) -- the covariates at the groupings' own cells as nrm_single1_select left
+// them, in segment order: no gather -- and xe.  The segment passes through LDS in chunks of 64 cells, a row [ce_0 .. ce_{nc-1}, x] per cell; output j is the
+// product of two columns of that row (C_c C_d: c, d; C_c x: c, nc; x x: nc, nc), lane l owns outputs l, l + 64, ... and adds to each of them, starting from
+// 0, ONE product per cell by fma IN THE ORDER OF THE CELLS of the segment: a chain of len roundings per output, no tree, no atomics, the same bits every run.
+#define S1_GSW_SLOTS ((S1_NCMAX * (S1_NCMAX + 1) / 2 + S1_NCMAX + 1 + 63) / 64)
+__global__ void __launch_bounds__(64) k_s1_group_stats_wide(const int64_t* __restrict__ seg, const double* __restrict__ xe, const double* __restrict__ ce, int nc, int64_t nx,
+															 double* __restrict__ out) {
+	__shared__ double row[64 * (S1_NCMAX + 1)];
+	const int64_t i = blockIdx.x;
+	const int lane = threadIdx.x, ld = nc + 1, npair = nc * (nc + 1) / 2, np = npair + nc + 1;
+	int ca[S1_GSW_SLOTS], cb[S1_GSW_SLOTS];
+	double acc[S1_GSW_SLOTS];
+#pragma unroll
+	for (int s = 0; s < S1_GSW_SLOTS; s++) {
+		const int j = lane + 64 * s;
+		int c = 0, d = 0;
+		if (j < npair) {
+			int off = 0;  // row c of the packed triangle starts at off and holds nc - c products
+			while (j >= off + nc - c) off += nc - c, c++;
+			d = c + (j - off);
+		} else if (j < npair + nc) {
+			c = j - npair, d = nc;
+		} else if (j < np) {
+			c = d = nc;
+		}
+		ca[s] = c, cb[s] = d, acc[s] = 0.0;
+	}
+	const int64_t k0 = seg[i], k1 = seg[i + 1];
+	for (int64_t k = k0; k < k1; k += 64) {
+		const int cnt = (int)(k1 - k < 64 ? k1 - k : 64);
+		for (int e = lane; e < cnt * nc; e += 64) row[e / nc * ld + e % nc] = ce[k * nc + e];
+		if (lane < cnt) row[lane * ld + nc] = xe[k + lane];
+		__syncthreads();
+		for (int u = 0; u < cnt; u++) {
+#pragma unroll
+			for (int s = 0; s < S1_GSW_SLOTS; s++) acc[s] = fma(row[u * ld + ca[s]], row[u * ld + cb[s]], acc[s]);
+		}
+		__syncthreads();
+	}
+#pragma unroll
+	for (int s = 0; s < S1_GSW_SLOTS; s++)
+		if (lane + 64 * s < np) out[i * np + lane + 64 * s] = acc[s];
+}
+
+// d_seg, d_xe as for nrm_single1_group_stats; d_ce (d_seg[nx], nc) from nrm_single1_select takes the place of (d_cells, d_c, ldc); d_out (nx, nc (nc + 1) / 2 + nc + 1)
+// in the same packing.  1 <= nc <= 32.
+extern "C" int nrm_single1_group_stats_wide(const int64_t* d_seg, const double* d_xe, const double* d_ce, int64_t nc, int64_t nx, double* d_out, void* stream) {
+	NRM_REQUIRE(nx > 0 && nc >= 1 && nc <= S1_NCMAX, "nrm_single1_group_stats_wide: bad sizes (1 to %d covariates)", S1_NCMAX);
+	NRM_REQUIRE(d_seg && d_xe && d_ce && d_out, "nrm_single1_group_stats_wide: null pointer");
+	hipLaunchKernelGGL(k_s1_group_stats_wide, dim3((unsigned)nx), dim3(64), 0, (hipStream_t)stream, d_seg, d_xe, d_ce, (int)nc, nx, d_out);
+	return nrm_check_launch("k_s1_group_stats_wide");
+}
+
+// One grouping's record by cooperating lanes (X: NrmSerialLanes on the host, a wave on the device; nrm_jacobi_lanes.h), the steps of k_s1_group_info:
+//   M_i = (the shared cells' matrix: EVERY 8 x 8 block pair (bi <= bj) of gpart, its gb partial sums added in block order -- the order of
+//          nrm_single1_reduce_gram) + (the grouping's own sums, o);  not finite: the identity instead, bit 4 of the result
+//   M_i^+ and the integer rank by nrm_pinv_lanes at tol 1e-8 (association.py:77-80,350-351); rank 0: M_i^+ = 0
+//   ccx = M_i^+ xc (a row per lane, each row's sum in the order of its columns), dot = xc . ccx added in the order of the covariates by every lane
+//   vx = (xx - dot) / ns, 0 -> 1 (:362-364); dof = ns - 1 - rank - dimreduce, <= 0: bit 2 and dof = 1; the plan (nrm_pvalue_plan_fill); a single value on the
+//   selected cells: bit 1 (:917-918)
+// a, v, inv (nc x nc each), w (nc), red (2 nc), rk (1): scratch every lane sees.  Every branch depends on shared values only, so all lanes reach every sync()
+// and return the same bits.
+template <class X>
+NRM_HD inline int s1_group_info_wide_one(const X& x, const double* o, const double* gpart, int gb, const double* rows, double n_common, int nc, int dimreduce, double* a, double* v,
+										 double* inv, double* w, double* red, int64_t* rk, double* rec, double* varx) {
+	const int lane = x.lane(), nl = x.lanes(), nb = (nc + 7) / 8, npair = nc * (nc + 1) / 2;
+	int bits = 0;
+	const double ns = n_common + rows[0];
+	double lo = rows[1], hi = rows[2];
+	if (n_common > 0) {  // 0 on the shared cells, if there are any, and its own values on its own
+		lo = fmin(lo, 0.0);
+		hi = fmax(hi, 0.0);
+	}
+	if (!(hi > lo)) bits |= 1;
+	for (int e = lane; e < nc * nc; e += nl) {
+		const int c = e / nc, d = e % nc;
+		if (d < c) continue;
+		const int bi = c / 8, bj = d / 8;
+		const double* blk = gpart + ((int64_t)(bi * nb - bi * (bi - 1) / 2 + (bj - bi)) * gb) * 64 + (c % 8) * 8 + d % 8;
+		double t = 0.0;
+		for (int g = 0; g < gb; g++) t += blk[(int64_t)g * 64];
+		a[c * nc + d] = a[d * nc + c] = o[c * nc - c * (c - 1) / 2 + (d - c)] + t;
+	}
+	x.sync();
+	bool finite = true;
+	for (int e = 0; e < nc * nc; e++) finite = finite && fabs(a[e]) <= 1.7976931348623157e308;  // (false for NaN too)
+	x.sync();
+	if (!finite) {
+		bits |= 4;
+		for (int e = lane; e < nc * nc; e += nl) a[e] = e % (nc + 1) == 0 ? 1.0 : 0.0;
+		x.sync();
+	}
+	nrm_pinv_lanes(x, a, v, w, red, nc, 1e-8, inv, rk);  // association.py:350-351
+	x.sync();
+	const int64_t rank = *rk;
+	if (rank == 0) {
+		for (int e = lane; e < nc * nc; e += nl) inv[e] = 0.0;
+		x.sync();
+	}
+	const double* xc = o + npair;
+	for (int c = lane; c < nc; c += nl) {
+		double t = 0.0;
+		for (int d = 0; d < nc; d++) t += inv[c * nc + d] * xc[d];
+		rec[S1_HEAD + c] = t;  // ccx
+		red[c] = xc[c] * t;
+	}
+	for (int e = lane; e < nc * nc; e += nl) rec[S1_HEAD + nc + e] = inv[e];
+	x.sync();
+	double dot = 0.0;
+	for (int c = 0; c < nc; c++) dot += red[c];
+	double vx = (o[npair + nc] - dot) / ns;
+	if (vx == 0.0) vx = 1.0;  // association.py:362-364
+	double dof = ns - 1.0 - (double)rank - (double)dimreduce;
+	if (!(dof > 0.0)) {
+		bits |= 2;
+		dof = 1.0;  // (the call raises; the sweep still gets a plan it can evaluate)
+	}
+	if (lane == 0) {
+		rec[0] = ns;
+		rec[1] = vx;
+		nrm_pvalue_plan_fill(dof, rec + 2);
+		*varx = vx;
+	}
+	return bits;
+}
+
+struct S1Wave {
+	__device__ int lane() const { return threadIdx.x; }
+	__device__ int lanes() const { return 64; }
+	__device__ void sync() const { __syncthreads(); }  // (a workgroup of one wave)
+};
+
+__global__ void __launch_bounds__(64) k_s1_group_info_wide(const double* __restrict__ gs, const double* __restrict__ gpart, int gb, const double* __restrict__ rowinfo,
+															const int64_t* __restrict__ sel_info, int nc, int64_t nx, int dimreduce, double* __restrict__ info, int64_t pitch,
+															double* __restrict__ varx, int32_t* __restrict__ flags) {
+	__shared__ double a[S1_NCMAX * S1_NCMAX], v[S1_NCMAX * S1_NCMAX], inv[S1_NCMAX * S1_NCMAX], w[S1_NCMAX], red[2 * S1_NCMAX];
+	__shared__ int64_t rk;
+	const int64_t i = blockIdx.x;
+	const int bits = s1_group_info_wide_one(S1Wave(), gs + i * (nc * (nc + 1) / 2 + nc + 1), gpart, gb, rowinfo + i * 3, (double)sel_info[3], nc, dimreduce, a, v, inv, w, red, &rk,
+											info + i * pitch, varx + i);
+	if (threadIdx.x == 0) {
+		if (bits & 1) atomicAdd(&flags[2], 1);
+		if (bits & 2) atomicAdd(&flags[3], 1);
+		if (bits & 4) atomicAdd(&flags[4], 1);
+	}
+}
+
+static int s1_group_info_wide_check(const char* who, const void* gs, const void* gram_part, const void* rowinfo, const void* sel_info, int64_t nc, int64_t nx, const void* info,
+									int64_t pitch, const void* varx, const void* flags) {
+	NRM_REQUIRE(nx > 0 && nc >= 1 && nc <= S1_NCMAX && pitch >= S1_HEAD + nc + nc * nc, "%s: bad sizes (1 to %d covariates)", who, S1_NCMAX);
+	NRM_REQUIRE(gs && gram_part && rowinfo && sel_info && info && varx && flags, "%s: null pointer", who);
+	return NRM_OK;
+}
+
+// The arguments, the records, d_varx and the counters d_flags[2], [3], [4] of nrm_single1_group_info, for 1 <= nc <= 32; d_gram_part (nb (nb + 1) / 2,
+// nrm_single1_select_gram_blocks(), 64), nb = ceil(nc / 8), as nrm_single1_select leaves it.  Reference: association.py:350-374.
+extern "C" int nrm_single1_group_info_wide(const double* d_gs, const double* d_gram_part, const double* d_rowinfo, const int64_t* d_sel_info, int64_t nc, int64_t nx,
+											int dimreduce, double* d_info, int64_t info_pitch, double* d_varx, int32_t* d_flags, void* stream) {
+	NRM_TRY(s1_group_info_wide_check("nrm_single1_group_info_wide", d_gs, d_gram_part, d_rowinfo, d_sel_info, nc, nx, d_info, info_pitch, d_varx, d_flags));
+	hipLaunchKernelGGL(k_s1_group_info_wide, dim3((unsigned)nx), dim3(64), 0, (hipStream_t)stream, d_gs, d_gram_part, (int)nrm_single1_select_gram_blocks(), d_rowinfo, d_sel_info,
+					   (int)nc, nx, dimreduce, d_info, info_pitch, d_varx, d_flags);
+	return nrm_check_launch("k_s1_group_info_wide");
+}
+
+// The host twin: s1_group_info_wide_one with one lane on host arrays -- no device, no HIP call (the CPU tests hold the arithmetic with it).
+extern "C" int nrm_single1_group_info_wide_host(const double* gs, const double* gram_part, const double* rowinfo, const int64_t* sel_info, int64_t nc, int64_t nx, int dimreduce,
+												 double* info, int64_t pitch, double* varx, int32_t* flags) {
+	NRM_TRY(s1_group_info_wide_check("nrm_single1_group_info_wide_host", gs, gram_part, rowinfo, sel_info, nc, nx, info, pitch, varx, flags));
+	const int m = (int)nc, gb = (int)nrm_single1_select_gram_blocks();
+	double* a = new double[3 * m * m + 3 * m];
+	int64_t rk = 0;
+	for (int64_t i = 0; i < nx; i++) {
+		const int bits = s1_group_info_wide_one(NrmSerialLanes(), gs + i * (m * (m + 1) / 2 + m + 1), gram_part, gb, rowinfo + i * 3, (double)sel_info[3], m, dimreduce, a, a + m * m,
+												a + 2 * m * m, a + 3 * m * m, a + 3 * m * m + m, &rk, info + i * pitch, varx + i);
+		flags[2] += bits & 1;
+		flags[3] += (bits >> 1) & 1;
+		flags[4] += (bits >> 2) & 1;
+	}
+	delete[] a;
+	return NRM_OK;
 }
 
 // The double-precision plans of nrm_pvalue_plan.h on the host (the code the device runs, compiled for the host: tests hold it to nrm_pvalue_plan_init_many)

@@ -95,7 +95,7 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 				if lists.ok and not (b & _lib.DESIGN_NEG):
 					# entries >= 0: the selection follows from the LIST of the design's entries (a cell is selected for grouping i when i is its
 					# only entry, and for every grouping when it has none) -- no (groupings x cells) selection matrix, no passes over one
-					if nc <= int(_S1_DEVICE_NC) and _opts.debug('single1_stats', 'device') != 'host':
+					if _opts.debug('single1_stats', 'device') != 'host':
 						plan = Single1Plan(d_dx, dy, c64, dimreduce=dimreduce, lowmem=lowmem, return_dot=return_dot, lists=lists, eng=eng)
 						plan.step()
 						return plan.results(device_out=device_out)
@@ -179,7 +179,8 @@ def association_tests_single1(dx, dy, dc, lowmem=True, return_dot=True, return_s
 					eng.download(vary))
 
 
-_S1_DEVICE_NC = 8  # covariates up to which the groupings' statistics are finished on the device (csrc/nrm_single1.hip: S1_GS_NC)
+_S1_DEVICE_NC = 32  # covariates up to which the groupings' statistics are finished on the device (csrc/nrm_single1.hip: S1_NCMAX; a lane per grouping up to
+# S1_GS_NC = 8 of them, a wave per grouping beyond)
 
 
 def _lists_for(eng, d_dx):
@@ -190,14 +191,15 @@ def _lists_for(eng, d_dx):
 
 
 class Single1Plan:
-	"""single=1 for a design with entries >= 0 and at most 8 covariates, with NOTHING of a step on the host (round 6; rounds 3-5 finished the
+	"""single=1 for a design with entries >= 0 and at most 32 covariates, with NOTHING of a step on the host (round 6; rounds 3-5 finished the
 	groupings' statistics there: five read-backs, 1000 pseudo-inverses, 1000 P-value plans and an upload per call, and a step took 2 ms on one
 	box and 18 on another).  A step is seven launches on the engine's stream --
 
 	    nrm_single1_select       the cell selection from the design's entry lists (association.py:914-918)
-	    nrm_single1_group_stats  each grouping's sums over its own cells (a wave per grouping)
+	    nrm_single1_group_stats  each grouping's sums over its own cells (a wave per grouping; more than 8 covariates: nrm_single1_group_stats_wide)
 	    nrm_single1_stream       the expression matrix read ONCE: sums over the shared cells, the values at the groupings' own cells
 	    nrm_single1_group_info   per grouping: pseudo-inverse + integer rank (Jacobi, the rule of inv_rank), ccx, vx, dof, the P-value plan (:350-374)
+	                             (a lane per grouping; more than 8 covariates: nrm_single1_group_info_wide, a wave per grouping)
 	    nrm_single1_cells        the sweep
 
 	-- into buffers the plan owns (no allocation inside a step), replayed as ONE HIP graph from the third step on; what the reference asserts or
@@ -254,7 +256,8 @@ class Single1Plan:
 			self.rowinfo = f64(nx, 3)
 			self.sel_info = torch.empty(8, dtype=torch.int64, device=dev)
 			gb = int(eng.lib.nrm_single1_select_gram_blocks())
-			self.gpart = f64(1, gb, 64) if nc else None
+			nb = (nc + 7) // 8
+			self.gpart = f64(nb * (nb + 1) // 2, gb, 64) if nc else None  # (an 8 x 8 block of covariates per pair bi <= bj: nrm_single1_common_gram)
 			self.gs = f64(nx, nc * (nc + 1) // 2 + nc + 1)
 			self.ldye = _engine.round_up(ny, 8)  # (a multiple of a 128-byte line instead: measured, no difference -- 1.74 ms either way on one box)
 			# One row of YE per cell that carries exactly one grouping: the selection is run once here and that count read back (the only read-back of the
@@ -298,9 +301,14 @@ class Single1Plan:
 			ss = self._side.cuda_stream
 			if nc:
 				_lib.check(lib.nrm_single1_common_gram(self.cnt.data_ptr(), n, self.d_c.data_ptr(), n, nc, self.gpart.data_ptr(), ss))
-			_lib.check(lib.nrm_single1_group_stats(self.seg.data_ptr(), self.idx.data_ptr(), self.xe.data_ptr(), _engine.ptr(self.d_c), n, nc, nx, self.gs.data_ptr(), ss))
-			_lib.check(lib.nrm_single1_group_info(self.gs.data_ptr(), _engine.ptr(self.gpart), self.rowinfo.data_ptr(), self.sel_info.data_ptr(), nc, nx, self.dimreduce,
-												  self.info.data_ptr(), self.pitch, self.varx.data_ptr(), self.flags.data_ptr(), ss))
+			if nc > 8:  # (a wave per grouping: the sums from ce as the selection left it, a 32 x 32 Jacobi in LDS)
+				_lib.check(lib.nrm_single1_group_stats_wide(self.seg.data_ptr(), self.xe.data_ptr(), self.ce.data_ptr(), nc, nx, self.gs.data_ptr(), ss))
+				group_info = lib.nrm_single1_group_info_wide
+			else:
+				_lib.check(lib.nrm_single1_group_stats(self.seg.data_ptr(), self.idx.data_ptr(), self.xe.data_ptr(), _engine.ptr(self.d_c), n, nc, nx, self.gs.data_ptr(), ss))
+				group_info = lib.nrm_single1_group_info
+			_lib.check(group_info(self.gs.data_ptr(), _engine.ptr(self.gpart), self.rowinfo.data_ptr(), self.sel_info.data_ptr(), nc, nx, self.dimreduce,
+								  self.info.data_ptr(), self.pitch, self.varx.data_ptr(), self.flags.data_ptr(), ss))
 			joined.record(self._side)
 		with _engine._Span(eng, 's1_stream'):
 			_lib.check(lib.nrm_single1_stream(d_y.data_ptr(), ycode, d_y.stride(0), _engine.ptr(self.d_c), n, nc, self.code.data_ptr(), n, ny, self.common.data_ptr(),
