@@ -1028,6 +1028,57 @@ int nrm_de_plan_info(nrm_de_plan* plan, int64_t info[8]);
 int nrm_de_plan_time(nrm_de_plan* plan, int64_t steps, double* ms_per_step);
 int nrm_de_plan_destroy(nrm_de_plan* plan);
 
+/*
+ * Resident single=1 plan (csrc/nrm_single1_plan.hip): de(dg, dt, dc, single=1), a low-MOI screen in which every grouping is tested on the cells that carry no other
+ * grouping -- reference de.py:4-132 over association.py:263-390, 911-925 -- for a caller that repeats a screen of one shape.  Names, argument order and semantics are
+ * those of nrm_de_plan_* wherever the two coincide; there is no h_dci / rank, because single=1 takes a pseudo-inverse per grouping, on the device.  The domain is that
+ * of nrm_association_tests_single1_host: entries >= 0 with the largest equal to 1, at most a quarter of them set, at most 32 covariates.
+ *   nrm_single1_plan_create: the design (ng0, n_cells) by design_form, dt, ldt, dt_on_device, h_dc, c_dtype, nc, out_dtype, want_alpha (lowmem=False) and want_q exactly as
+ *       nrm_de_plan_create takes them; dimreduce a scalar >= 0.  Every argument check -- dtypes, sizes ("Incorrect dx/dy/dc size.", "Unmatching dx/dy/dc dimensions."),
+ *       dimreduce, rows and cells <= 2^31 - 1, row pitches: NRM_E_ARG; nc > 32: NRM_E_UNSUPPORTED -- is made before any device call.  The design is then set on the
+ *       device, in this order: de's row filter (de.py:93) and the row map; the rows kept compacted (nrm_subset_dense; nrm_subset_csr_count / scan / write); their entry
+ *       lists as nrm_association_tests_single1_host builds them (no ELL form; filled while at most a quarter of the entries is set); nrm_single1_select once, whose count
+ *       of cells that carry exactly one grouping is the only size read back; the stream kernel's transposed output, sized from that count.  A row de drops never reaches
+ *       the selection (an all-ones row left in would leave no cell with exactly one grouping).  Refused, in the words of the host entry: the largest entry of the rows
+ *       kept is not 1, or a NaN: NRM_E_NUMERIC (association.py:914); negative entries or more than a quarter of the entries set: NRM_E_UNSUPPORTED; a malformed CSR
+ *       matrix or no row left to test: NRM_E_ARG.  Every buffer of a step is taken from the scratch pool here.
+ *   nrm_single1_plan_design: another design of the same shape (any form) in place of the present one; drops the captured graph.  After a refusal the plan has no design.
+ *   nrm_single1_plan_upload: new values (same shape and dtype) into the plan's own copy of dt; NRM_E_ARG for an adopted matrix.
+ *   nrm_single1_plan_step: nrm_single1_select; then, on a side stream the plan owns (forked and joined by events, so that a capture records both branches),
+ *       nrm_single1_common_gram and nrm_single1_group_stats + nrm_single1_group_info (nc <= 8) or their _wide forms (9 .. 32), beside nrm_single1_stream on the step's
+ *       stream; after the join nrm_single1_cells (gamma, alpha on request); then one pass that puts the compact P, gamma, alpha and vary rows back among all ng0 rows
+ *       (rows not tested: p = 1, gamma = alpha = varg = vart = 0; when every row is tested the sweep writes the full-size arrays itself), rounds varx once to out_dtype
+ *       and counts the entries outside the ranges de.py:124-131 asserts; nrm_bh over all ng0 * nt P-values on request.  Nothing is read back, allocated or waited for.
+ *       stream == NULL: the plan's own.  The first step on a design runs eagerly, the second is captured (thread-local) and instantiated, later ones are one
+ *       hipGraphLaunch; a failed capture leaves the plan eager with the reason in nrm_last_error (NRM_OK).  NRM_DEBUG="graph=0": always eager.
+ *   nrm_single1_plan_check: synchronises the device, reads and clears the counters, and answers in the reference's order: groupings with a single value on the cells
+ *       selected for them (association.py:917-918): NRM_E_NUMERIC; "array must not contain infs or NaNs": NRM_E_ARG; "Insufficient number of cells ...": NRM_E_DEVICE;
+ *       the result assertions (association.py:248,252) and de's (de.py:124-131): NRM_E_NUMERIC.  single=1 has no hand-back route.
+ *   nrm_single1_plan_results: check, then de's outputs of the last step into HOST arrays of out_dtype, any of them NULL: P (ng0, nt), gamma (ng0, nt), alpha (ng0, nt, nc),
+ *       varg (ng0), vart (ng0, nt: per grouping here), q (ng0, nt).
+ *   nrm_single1_plan_device_results: the same arrays as full-size DEVICE pointers (row pitch *ld = nt; vart (ng0, nt)) and the byte mask of tested rows (ng0); NULL for
+ *       what the plan was created without.  Valid until destroy, written by every step.
+ *   nrm_single1_plan_info: info[0] 0, [1] captured, [2] steps, [3] cells kept by the selection, [4] covariates, [5] 0, [6] bytes resident, [7] rows kept.
+ *   nrm_single1_plan_stream, nrm_single1_plan_time, nrm_single1_plan_destroy (accepts NULL): as nrm_de_plan_*.
+ * Threads: create, design, check, results and destroy take the lock of the whole-problem entries; step, upload and time do not.  One thread at a time per plan.
+ */
+typedef struct nrm_single1_plan nrm_single1_plan;
+int nrm_single1_plan_create(nrm_single1_plan** plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
+							int dg_on_device, int64_t ng0, const void* dt, int dt_dtype, int64_t nt, int64_t n_cells, int64_t ldt, int dt_on_device, const void* h_dc,
+							int c_dtype, int64_t nc, int dimreduce, int out_dtype, int want_alpha, int want_q);
+int nrm_single1_plan_design(nrm_single1_plan* plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
+							int dg_on_device);
+int nrm_single1_plan_upload(nrm_single1_plan* plan, const void* h_dt);
+int nrm_single1_plan_step(nrm_single1_plan* plan, void* stream);
+int nrm_single1_plan_check(nrm_single1_plan* plan);
+int nrm_single1_plan_results(nrm_single1_plan* plan, void* h_p, void* h_gamma, void* h_alpha, void* h_varg, void* h_vart, void* h_q);
+int nrm_single1_plan_device_results(nrm_single1_plan* plan, void** d_p, void** d_gamma, void** d_alpha, void** d_varg, void** d_q, void** d_vart, void** d_mask,
+									int64_t* ld);
+int nrm_single1_plan_stream(nrm_single1_plan* plan, void** stream);
+int nrm_single1_plan_info(nrm_single1_plan* plan, int64_t info[8]);
+int nrm_single1_plan_time(nrm_single1_plan* plan, int64_t steps, double* ms_per_step);
+int nrm_single1_plan_destroy(nrm_single1_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@ never imports torch.  The matrix stays in HBM, a step is K1 -> K2 -> K3 as one H
 		plan.update(dt2); plan.step()     # same shape, new values: no allocation, one graph launch
 
 DePlan (nrm_de_plan_*) is the same for de(dg, dt, dc) with single=0 on the sparse-design kernels: the design dense or sparse, de's row filter, re-inflation and
-assertions and, on request, alpha and Benjamini-Hochberg q-values on the device; `results()` is `de`'s contract.
+assertions and, on request, alpha and Benjamini-Hochberg q-values on the device; `results()` is `de`'s contract.  Single1Plan (nrm_single1_plan_*) is the same
+for single=1, a low-MOI screen: the row filter runs in front of the cell selection, the variances are per grouping.
 """
 import ctypes
 
@@ -420,6 +421,171 @@ class DePlan:
 		h, self._h = self._h, None
 		if h is not None:
 			_lib.check(self._lib.nrm_de_plan_destroy(h))
+		self._keep = None
+
+	def __enter__(self):
+		return self
+
+	def __exit__(self, *exc):
+		self.close()
+		return False
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001 -- interpreter shutdown
+			pass
+
+
+S1_INFO_FIELDS = ('route', 'captured', 'steps', 'cells_kept', 'covariates', 'reserved', 'bytes', 'rows_kept')
+
+
+class Single1Plan:
+	"""de(dg, dt, dc, single=1) -- a low-MOI screen: every grouping tested on the cells that carry no other grouping -- resident on the GPU (include/normalisr_hip.h:
+	nrm_single1_plan_*):
+
+		with cplan.Single1Plan(dg, dt, dc, lowmem=False, q=True) as plan:
+			plan.step()
+			p, gamma, alpha, varg, vart = plan.results()   # == normalisr.de(dg, dt, dc, single=1, lowmem=False)
+			q = plan.qvalues()                              # == binnet.bh(p)
+			plan.update(dt2); plan.step()                   # same shape, new values: one graph launch
+			plan.set_design(dg2); plan.step()               # another design of the same shape
+
+	dg, dt, lowmem, q and out_dtype as DePlan takes them.  The design's entries are >= 0 with the largest equal to 1 and at most a quarter of them set, dc has at most
+	32 covariates (NotImplementedError otherwise); dimreduce is a scalar.  The pseudo-inverses are per grouping and taken on the device: there is no `pinv`."""
+
+	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None):
+		self._h = None
+		lib = self._lib = _lib.load()
+		from . import de_sparse
+		if np.ndim(dimreduce) != 0:
+			raise NotImplementedError('Single1Plan: one dimreduce for all genes (association_tests(..., single=1) takes one per gene)')
+		if int(dimreduce) != dimreduce:
+			raise ValueError('dimreduce must be an integer.')
+		de_sparse.refuse_sparse(dt, 'dt')
+		de_sparse.refuse_sparse(dc, 'dc')
+		dev = _adopt(dt)
+		if dev is None:
+			dt = np.asarray(dt)
+			if dt.ndim != 2:
+				raise ValueError('Incorrect dx/dy/dc size.')
+			if dt.dtype not in (np.float32, np.float64):
+				dt = dt.astype(np.float64)
+			dt = np.ascontiguousarray(dt)
+			ptr, shape, dtype, ld = dt.ctypes.data, dt.shape, dt.dtype, dt.shape[1]
+		else:
+			ptr, shape, dtype, ld = dev
+			if dtype not in (np.float32, np.float64):
+				raise ValueError('Single1Plan: a device matrix must be float32 or float64')
+		dc = np.asarray(dc)
+		if dc.ndim != 2:
+			raise ValueError('Incorrect dx/dy/dc size.')
+		gargs, gshape, gkeep = _design(dg)
+		if dc.shape[1] != shape[1] or gshape[1] != shape[1]:
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		self.shape, self.dtype, self.adopted = (int(gshape[0]), int(shape[0]), int(shape[1])), np.dtype(dtype), dev is not None
+		self.out_dtype = np.dtype(dtype if out_dtype is None else out_dtype)
+		if self.out_dtype not in (np.float32, np.float64):
+			raise ValueError('out_dtype must be float32 or float64')
+		nc = self.nc = int(dc.shape[0])
+		self.lowmem, self.q = bool(lowmem), bool(q)
+		dc = np.ascontiguousarray(dc if dc.dtype in (np.float32, np.float64) else dc.astype(np.float64))
+		if device is not None:
+			_lib.check(lib.nrm_set_device(int(device)))
+		h = _vp()
+		_lib.check(lib.nrm_single1_plan_create(ctypes.byref(h), *gargs, self.shape[0], ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0,
+											   dc.ctypes.data if nc else None, _code(dc.dtype), nc, int(dimreduce), _code(self.out_dtype), 0 if self.lowmem else 1, 1 if self.q else 0))
+		self._h = h
+		self._keep = dt if self.adopted else None  # (an adopted matrix lives as long as the plan reads it)
+		del gkeep  # (the design was read inside create)
+
+	def _handle(self):
+		if self._h is None:
+			raise ValueError('Single1Plan: the plan is closed')
+		return self._h
+
+	def step(self, stream=None):
+		"""One de on the matrices as they stand, queued on `stream` (a hipStream_t as an integer; None: the plan's own).  Does not wait."""
+		_lib.check(self._lib.nrm_single1_plan_step(self._handle(), stream))
+		return self
+
+	def check(self):
+		"""Waits for the queued steps and tests what they counted, as the reference would have raised it: AssertionError for a grouping with a single value on the cells
+		selected for it (association.py:917-918) and for the result assertions (association.py:248,252; de.py:124-131), ValueError for covariates that are not finite,
+		RuntimeError for too few cells."""
+		_lib.check(self._lib.nrm_single1_plan_check(self._handle()))
+
+	def _fetch(self, want_q):
+		ng0, nt, _ = self.shape
+		o = self.out_dtype
+		if want_q:
+			qv = np.empty((ng0, nt), o)
+			_lib.check(self._lib.nrm_single1_plan_results(self._handle(), None, None, None, None, None, qv.ctypes.data))
+			return qv
+		p, gam, varg, vart = np.empty((ng0, nt), o), np.empty((ng0, nt), o), np.empty(ng0, o), np.empty((ng0, nt), o)
+		alpha = None if self.lowmem else np.zeros((ng0, nt, self.nc), o)
+		_lib.check(self._lib.nrm_single1_plan_results(self._handle(), p.ctypes.data, gam.ctypes.data, alpha.ctypes.data if (alpha is not None and self.nc) else None,
+													  varg.ctypes.data, vart.ctypes.data, None))
+		return p, gam, alpha, varg, vart
+
+	def results(self):
+		"""(P-values (n_group, n_gene), gamma (n_group, n_gene), alpha (n_group, n_gene, n_cov) | None, varg (n_group,), vart (n_group, n_gene)) of the last step as numpy
+		arrays of out_dtype: de's return value."""
+		return self._fetch(False)
+
+	def qvalues(self):
+		"""The Benjamini-Hochberg q-values (n_group, n_gene) of the last step's P-values: binnet.bh of them, bit for bit (a plan created with q=True)."""
+		if not self.q:
+			raise ValueError('Single1Plan.qvalues: the plan was created without q=True')
+		return self._fetch(True)
+
+	def device_results(self):
+		"""dict(p=, gamma=, alpha=, varg=, q=, vart= full-size device addresses (None for what the plan was created without; vart is (n_group, n_gene) here), mask= one
+		byte per grouping (1: tested), ld= row pitch in elements, dtype=, stream= the plan's own stream): for a consumer queued behind the step."""
+		v = [_vp() for _ in range(7)]
+		st, ld = _vp(), _i64(0)
+		_lib.check(self._lib.nrm_single1_plan_device_results(self._handle(), *[ctypes.byref(x) for x in v], ctypes.byref(ld)))
+		_lib.check(self._lib.nrm_single1_plan_stream(self._handle(), ctypes.byref(st)))
+		out = dict(zip(('p', 'gamma', 'alpha', 'varg', 'q', 'vart', 'mask'), (x.value for x in v)))
+		out.update(ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
+		return out
+
+	def update(self, dt):
+		"""New values of the same shape and dtype into the plan's own copy of dt (ValueError for an adopted matrix: its owner rewrites it in place)."""
+		if self.adopted:
+			raise ValueError('Single1Plan.update: the plan adopted a device matrix; its owner rewrites it in place')
+		dt = np.ascontiguousarray(np.asarray(dt), dtype=self.dtype)
+		if dt.shape != self.shape[1:]:
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		_lib.check(self._lib.nrm_single1_plan_upload(self._handle(), dt.ctypes.data))
+		return self
+
+	def set_design(self, dg):
+		"""Another design of the same shape, in any of the forms the constructor takes: the row filter, the compaction, the lists and the cell selection again, and a new
+		graph from the second step on it."""
+		gargs, gshape, gkeep = _design(dg)
+		if tuple(int(v) for v in gshape) != (self.shape[0], self.shape[2]):
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		_lib.check(self._lib.nrm_single1_plan_design(self._handle(), *gargs))
+		del gkeep
+		return self
+
+	def time(self, steps):
+		"""Milliseconds per step over `steps` steps, between two device events on the plan's stream."""
+		ms = _dbl(0.)
+		_lib.check(self._lib.nrm_single1_plan_time(self._handle(), int(steps), ctypes.byref(ms)))
+		return float(ms.value)
+
+	def info(self):
+		"""route (0), captured, steps, cells_kept (cells that carry exactly one grouping), covariates, reserved (0), bytes, rows_kept."""
+		v = (_i64 * 8)()
+		_lib.check(self._lib.nrm_single1_plan_info(self._handle(), v))
+		return dict(zip(S1_INFO_FIELDS, (int(x) for x in v)))
+
+	def close(self):
+		h, self._h = self._h, None
+		if h is not None:
+			_lib.check(self._lib.nrm_single1_plan_destroy(h))
 		self._keep = None
 
 	def __enter__(self):

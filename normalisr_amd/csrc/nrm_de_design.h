@@ -1,0 +1,21 @@
+// What the resident plans of de (nrm_de_plan.hip: single=0; nrm_single1_plan.hip: single=1) do to a design when it is set, in nrm_de_design.hip: de's row filter
+// (de.py:93), the row map, the rows kept compacted on the device, and their lists (csrc/nrm_design_lists.hip, csrc/nrm_design_csr.hip).
+#pragma once
+#include <memory>
+#include "nrm_host_entry.h"
+#include "nrm_de_plan_args.h"
+
+struct NrmDeDesign {
+	std::unique_ptr<NrmDesignLists> L;  // the lists of the rows kept (L->ok says whether they were filled)
+	int64_t ngk = 0, list_bytes = 0;    // rows kept; bytes the lists hold
+};
+
+// "Malformed CSR design matrix ...": NRM_E_ARG
+int nrm_de_design_malformed();
+
+// The design `in` (ng0, n) of a plan called `who`: d_mask (ng0) one byte per row (1: tested), d_c2f (ng0) int64 the design row of every compact row, d_f2c (ng0)
+// the compact row of every design row or -1, and out: the lists of the rows kept, with the ELL form on request; max_density > 0: the lists are filled only while at
+// most that share of the rows kept is set (NrmDesignLists::build's rule), 0: always.  Reads the size records back (a few words, three times at the most) and waits
+// for the fill; everything it takes besides the lists returns to the pool on the way out.  The caller has synchronised the device.  No row left: NRM_E_ARG.
+int nrm_de_design_set(const char* who, const NrmDePlanDesign& in, int64_t ng0, int64_t n, uint8_t* d_mask, int64_t* d_c2f, int32_t* d_f2c, bool want_ell, double max_density,
+					  hipStream_t st, NrmDeDesign& out);
