@@ -63,115 +63,98 @@ def _adopt(dt):
 	return None
 
 
-class CoexPlan:
-	"""coex(dt, dc) resident on the GPU.  dt: a numpy array (the plan keeps its own device copy; `update` re-uploads) or a device matrix -- anything with data_ptr() or
-	__cuda_array_interface__, fp32 / fp64 with contiguous rows -- which is adopted: never copied, rewritten in place by its owner between steps.  dc (nc, n) covariates.
-	out_dtype: dt's by default, as coex.  device: GPU index (nrm_set_device), default the process's.  pinv='numpy' takes the pseudo-inverse and rank of dc dc^T from
-	association._prepare_covariates, the function coex calls; pinv='library' leaves both to the library (nrm_covariates_pinv: no LAPACK, at most 32 covariates)."""
-
-	def __init__(self, dt, dc, dimreduce=0, out_dtype=None, device=None, pinv='numpy'):
-		self._h = None
-		lib = self._lib = _lib.load()
-		if pinv not in ('numpy', 'library'):
-			raise ValueError("pinv must be 'numpy' or 'library'")
-		if np.ndim(dimreduce) != 0 or int(dimreduce) != dimreduce:
-			raise ValueError('dimreduce must be an integer.')
-		dev = _adopt(dt)
-		if dev is None:
-			dt = np.asarray(dt)
-			if dt.ndim != 2:
-				raise ValueError('Incorrect dx/dy/dc size.')
-			if dt.dtype not in (np.float32, np.float64):
-				dt = dt.astype(np.float64)
-			dt = np.ascontiguousarray(dt)
-			ptr, shape, dtype, ld = dt.ctypes.data, dt.shape, dt.dtype, dt.shape[1]
-		else:
-			ptr, shape, dtype, ld = dev
-			if dtype not in (np.float32, np.float64):
-				raise ValueError('CoexPlan: a device matrix must be float32 or float64')
-		dc = np.asarray(dc)
-		if dc.ndim != 2:
+def _matrix(dt, cls):
+	"""(the array to keep alive, pointer, shape, numpy dtype, row pitch, adopted) of a plan's matrix: a host array made fp32 / fp64 and contiguous, or a device matrix as
+	_adopt finds it; cls: the plan's class, for what it says of a device matrix."""
+	dev = _adopt(dt)
+	if dev is None:
+		dt = np.asarray(dt)
+		if dt.ndim != 2:
 			raise ValueError('Incorrect dx/dy/dc size.')
-		if dc.shape[1] != shape[1]:
-			raise ValueError('Unmatching dx/dy/dc dimensions.')
-		self.shape, self.dtype, self.adopted = (int(shape[0]), int(shape[1])), np.dtype(dtype), dev is not None
-		self.out_dtype = np.dtype(dtype if out_dtype is None else out_dtype)
+		if dt.dtype not in (np.float32, np.float64):
+			dt = dt.astype(np.float64)
+		dt = np.ascontiguousarray(dt)
+		return dt, dt.ctypes.data, dt.shape, dt.dtype, dt.shape[1], False
+	ptr, shape, dtype, ld = dev
+	if dtype not in (np.float32, np.float64):
+		raise ValueError(cls + ': a device matrix must be float32 or float64')
+	return dt, ptr, shape, dtype, ld, True
+
+
+def _covariates(dc, pinv):
+	"""(dc contiguous, its pseudo-inverse or None, its rank) as nrm_coex_plan_create and nrm_de_plan_create take them."""
+	if pinv == 'numpy':
+		from .association import _prepare_covariates
+		dc, dci, dcr = _prepare_covariates(dc)
+		dci = np.ascontiguousarray(dci, dtype=np.float64)
+	else:
+		dc = dc if dc.dtype in (np.float32, np.float64) else dc.astype(np.float64)
+		dci, dcr = None, 0
+	return np.ascontiguousarray(dc), dci, int(dcr)
+
+
+class _Plan:
+	"""What the three plans share: the handle and its entries.  A class names its entries' prefix and the fields of its info()."""
+	_prefix = None
+	_info_fields = None
+
+	def __init__(self):
+		self._h = self._keep = None
+		self._lib = _lib.load()
+
+	def _set_out_dtype(self, out_dtype):
+		self.out_dtype = np.dtype(self.dtype if out_dtype is None else out_dtype)
 		if self.out_dtype not in (np.float32, np.float64):
 			raise ValueError('out_dtype must be float32 or float64')
-		nc = dc.shape[0]
-		if pinv == 'numpy':
-			from .association import _prepare_covariates
-			dc, dci, dcr = _prepare_covariates(dc)
-			dci = np.ascontiguousarray(dci, dtype=np.float64)
-		else:
-			dc = dc if dc.dtype in (np.float32, np.float64) else dc.astype(np.float64)
-			dci, dcr = None, 0
-		dc = np.ascontiguousarray(dc)
+
+	def _open(self, device, keep, *args):
+		"""The handle from the create entry, on `device` when one is named; keep: the matrix as _matrix returned it."""
 		if device is not None:
-			_lib.check(lib.nrm_set_device(int(device)))
+			_lib.check(self._lib.nrm_set_device(int(device)))
 		h = _vp()
-		_lib.check(lib.nrm_coex_plan_create(ctypes.byref(h), ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0, dc.ctypes.data if nc else None, _code(dc.dtype),
-											nc, None if dci is None or not nc else dci.ctypes.data, int(dcr), int(dimreduce), _code(self.out_dtype)))
+		_lib.check(getattr(self._lib, self._prefix + 'create')(ctypes.byref(h), *args))
 		self._h = h
-		self._keep = dt if self.adopted else None  # (an adopted matrix lives as long as the plan reads it)
+		self._keep = keep if self.adopted else None  # (an adopted matrix lives as long as the plan reads it)
 
 	def _handle(self):
 		if self._h is None:
-			raise ValueError('CoexPlan: the plan is closed')
+			raise ValueError(type(self).__name__ + ': the plan is closed')
 		return self._h
 
+	def _call(self, entry, *args):
+		_lib.check(getattr(self._lib, self._prefix + entry)(self._handle(), *args))
+
 	def step(self, stream=None):
-		"""One coex on the matrix as it stands, queued on `stream` (a hipStream_t as an integer; None: the plan's own).  Does not wait."""
-		_lib.check(self._lib.nrm_coex_plan_step(self._handle(), stream))
+		"""One step on the matrices as they stand, queued on `stream` (a hipStream_t as an integer; None: the plan's own).  Does not wait."""
+		self._call('step', stream)
 		return self
 
-	def check(self):
-		"""Waits for the queued steps and tests what they counted: AssertionError for the reference's assertions; (guard_hits, guard_worst) otherwise -- guard_hits > 0:
-		the integer engine could not certify that many pairs and the step was redone on the fp64 kernel before returning."""
-		hits, worst = _i64(0), _dbl(0.)
-		_lib.check(self._lib.nrm_coex_plan_check(self._handle(), ctypes.byref(hits), ctypes.byref(worst)))
-		return int(hits.value), float(worst.value)
-
-	def results(self):
-		"""(P-values (ng, ng), dot (ng, ng), var (ng,)) of the last step as numpy arrays of out_dtype: coex's return value."""
-		ng = self.shape[0]
-		p, dot, var = np.empty((ng, ng), self.out_dtype), np.empty((ng, ng), self.out_dtype), np.empty(ng, self.out_dtype)
-		_lib.check(self._lib.nrm_coex_plan_results(self._handle(), p.ctypes.data, dot.ctypes.data, var.ctypes.data))
-		return p, dot, var
-
-	def device_results(self):
-		"""dict(p=, dot=, var= device addresses, ld= row pitch in elements, dtype=, stream= the plan's own stream): for a consumer queued behind the step, such as nrm_binnet."""
-		p, dot, var, st, ld = _vp(), _vp(), _vp(), _vp(), _i64(0)
-		_lib.check(self._lib.nrm_coex_plan_device_results(self._handle(), ctypes.byref(p), ctypes.byref(dot), ctypes.byref(var), ctypes.byref(ld)))
-		_lib.check(self._lib.nrm_coex_plan_stream(self._handle(), ctypes.byref(st)))
-		return dict(p=p.value, dot=dot.value, var=var.value, ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
-
 	def update(self, dt):
-		"""New values of the same shape and dtype into the plan's own copy of the matrix (ValueError for an adopted matrix: its owner rewrites it in place)."""
+		"""New values of the same shape and dtype into the plan's own copy of dt (ValueError for an adopted matrix: its owner rewrites it in place)."""
 		if self.adopted:
-			raise ValueError('CoexPlan.update: the plan adopted a device matrix; its owner rewrites it in place')
+			raise ValueError(type(self).__name__ + '.update: the plan adopted a device matrix; its owner rewrites it in place')
 		dt = np.ascontiguousarray(np.asarray(dt), dtype=self.dtype)
-		if dt.shape != self.shape:
+		if dt.shape != self.shape[-2:]:
 			raise ValueError('Unmatching dx/dy/dc dimensions.')
-		_lib.check(self._lib.nrm_coex_plan_upload(self._handle(), dt.ctypes.data))
+		self._call('upload', dt.ctypes.data)
 		return self
 
 	def time(self, steps):
 		"""Milliseconds per step over `steps` steps, between two device events on the plan's stream."""
 		ms = _dbl(0.)
-		_lib.check(self._lib.nrm_coex_plan_time(self._handle(), int(steps), ctypes.byref(ms)))
+		self._call('time', int(steps), ctypes.byref(ms))
 		return float(ms.value)
 
 	def info(self):
-		"""engine (0: fp64 kernel, 5 / 6: digit planes of the integer engine), captured, steps, reruns, rank, dof, bytes."""
+		"""The plan's counters by name (the class's docstring says which)."""
 		v = (_i64 * 8)()
-		_lib.check(self._lib.nrm_coex_plan_info(self._handle(), v))
-		return dict(zip(INFO_FIELDS, (int(x) for x in v)))
+		self._call('info', v)
+		return dict(zip(self._info_fields, (int(x) for x in v)))
 
 	def close(self):
 		h, self._h = self._h, None
 		if h is not None:
-			_lib.check(self._lib.nrm_coex_plan_destroy(h))
+			_lib.check(getattr(self._lib, self._prefix + 'destroy')(h))
 		self._keep = None
 
 	def __enter__(self):
@@ -186,6 +169,55 @@ class CoexPlan:
 			self.close()
 		except Exception:  # noqa: BLE001 -- interpreter shutdown
 			pass
+
+
+class CoexPlan(_Plan):
+	"""coex(dt, dc) resident on the GPU.  dt: a numpy array (the plan keeps its own device copy; `update` re-uploads) or a device matrix -- anything with data_ptr() or
+	__cuda_array_interface__, fp32 / fp64 with contiguous rows -- which is adopted: never copied, rewritten in place by its owner between steps.  dc (nc, n) covariates.
+	out_dtype: dt's by default, as coex.  device: GPU index (nrm_set_device), default the process's.  pinv='numpy' takes the pseudo-inverse and rank of dc dc^T from
+	association._prepare_covariates, the function coex calls; pinv='library' leaves both to the library (nrm_covariates_pinv: no LAPACK, at most 32 covariates).
+	info(): engine (0: fp64 kernel, 5 / 6: digit planes of the integer engine), captured, steps, reruns, rank, dof, bytes."""
+	_prefix, _info_fields = 'nrm_coex_plan_', INFO_FIELDS
+
+	def __init__(self, dt, dc, dimreduce=0, out_dtype=None, device=None, pinv='numpy'):
+		super().__init__()
+		if pinv not in ('numpy', 'library'):
+			raise ValueError("pinv must be 'numpy' or 'library'")
+		if np.ndim(dimreduce) != 0 or int(dimreduce) != dimreduce:
+			raise ValueError('dimreduce must be an integer.')
+		dt, ptr, shape, dtype, ld, self.adopted = _matrix(dt, 'CoexPlan')
+		dc = np.asarray(dc)
+		if dc.ndim != 2:
+			raise ValueError('Incorrect dx/dy/dc size.')
+		if dc.shape[1] != shape[1]:
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		self.shape, self.dtype = (int(shape[0]), int(shape[1])), np.dtype(dtype)
+		self._set_out_dtype(out_dtype)
+		nc = dc.shape[0]
+		dc, dci, dcr = _covariates(dc, pinv)
+		self._open(device, dt, ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0, dc.ctypes.data if nc else None, _code(dc.dtype), nc,
+				   None if dci is None or not nc else dci.ctypes.data, dcr, int(dimreduce), _code(self.out_dtype))
+
+	def check(self):
+		"""Waits for the queued steps and tests what they counted: AssertionError for the reference's assertions; (guard_hits, guard_worst) otherwise -- guard_hits > 0:
+		the integer engine could not certify that many pairs and the step was redone on the fp64 kernel before returning."""
+		hits, worst = _i64(0), _dbl(0.)
+		self._call('check', ctypes.byref(hits), ctypes.byref(worst))
+		return int(hits.value), float(worst.value)
+
+	def results(self):
+		"""(P-values (ng, ng), dot (ng, ng), var (ng,)) of the last step as numpy arrays of out_dtype: coex's return value."""
+		ng = self.shape[0]
+		p, dot, var = np.empty((ng, ng), self.out_dtype), np.empty((ng, ng), self.out_dtype), np.empty(ng, self.out_dtype)
+		self._call('results', p.ctypes.data, dot.ctypes.data, var.ctypes.data)
+		return p, dot, var
+
+	def device_results(self):
+		"""dict(p=, dot=, var= device addresses, ld= row pitch in elements, dtype=, stream= the plan's own stream): for a consumer queued behind the step, such as nrm_binnet."""
+		p, dot, var, st, ld = _vp(), _vp(), _vp(), _vp(), _i64(0)
+		self._call('device_results', ctypes.byref(p), ctypes.byref(dot), ctypes.byref(var), ctypes.byref(ld))
+		self._call('stream', ctypes.byref(st))
+		return dict(p=p.value, dot=dot.value, var=var.value, ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
 
 
 DE_INFO_FIELDS = ('route', 'captured', 'steps', 'reruns', 'rank', 'dof', 'bytes', 'rows_kept')
@@ -264,7 +296,75 @@ def _design(dg):
 	return (0, dg.ctypes.data, _code(dg.dtype), dg.shape[1], None, None, 0, 0), dg.shape, dg
 
 
-class DePlan:
+class _DesignPlan(_Plan):
+	"""What DePlan and Single1Plan share: a design beside the matrix, de's five results and the q-values."""
+
+	def _problem(self, dg, dt, dc, lowmem, q, out_dtype):
+		"""The constructors' common part: sets shape, dtype, adopted, out_dtype, nc, lowmem and q; returns the design's arguments, the matrix as _matrix returns it
+		without `adopted`, and dc as an array."""
+		from . import de_sparse
+		de_sparse.refuse_sparse(dt, 'dt')
+		de_sparse.refuse_sparse(dc, 'dc')
+		dt, ptr, shape, dtype, ld, self.adopted = _matrix(dt, type(self).__name__)
+		dc = np.asarray(dc)
+		if dc.ndim != 2:
+			raise ValueError('Incorrect dx/dy/dc size.')
+		gargs, gshape, gkeep = _design(dg)  # (gkeep lives until create has read the design: the caller holds gargs no longer than that)
+		if dc.shape[1] != shape[1] or gshape[1] != shape[1]:
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		self.shape, self.dtype = (int(gshape[0]), int(shape[0]), int(shape[1])), np.dtype(dtype)
+		self._set_out_dtype(out_dtype)
+		self.nc = int(dc.shape[0])
+		self.lowmem, self.q = bool(lowmem), bool(q)
+		return (gargs, gkeep), (dt, ptr, shape, dtype, ld), dc
+
+	def _fetch(self, want_q):
+		ng0, nt, _ = self.shape
+		o = self.out_dtype
+		if want_q:
+			qv = np.empty((ng0, nt), o)
+			self._call('results', None, None, None, None, None, qv.ctypes.data)
+			return qv
+		p, gam, varg, vart = np.empty((ng0, nt), o), np.empty((ng0, nt), o), np.empty(ng0, o), np.empty((ng0, nt), o)
+		alpha = None if self.lowmem else np.zeros((ng0, nt, self.nc), o)
+		self._call('results', p.ctypes.data, gam.ctypes.data, alpha.ctypes.data if (alpha is not None and self.nc) else None, varg.ctypes.data, vart.ctypes.data, None)
+		return p, gam, alpha, varg, vart
+
+	def results(self):
+		"""(P-values (n_group, n_gene), gamma (n_group, n_gene), alpha (n_group, n_gene, n_cov) | None, varg (n_group,), vart (n_group, n_gene)) of the last step as numpy
+		arrays of out_dtype: de's return value."""
+		return self._fetch(False)
+
+	def qvalues(self):
+		"""The Benjamini-Hochberg q-values (n_group, n_gene) of the last step's P-values: binnet.bh of them, bit for bit (a plan created with q=True)."""
+		if not self.q:
+			raise ValueError(type(self).__name__ + '.qvalues: the plan was created without q=True')
+		return self._fetch(True)
+
+	def device_results(self):
+		"""dict(p=, gamma=, alpha=, varg=, q= full-size device addresses (None for what the plan was created without), vart= the genes' variances -- (n_gene) for DePlan,
+		full-size (n_group, n_gene) for Single1Plan --, mask= one byte per grouping (1: tested), ld= row pitch in elements, dtype=, stream= the plan's own stream): for a
+		consumer queued behind the step."""
+		v = [_vp() for _ in range(7)]
+		st, ld = _vp(), _i64(0)
+		self._call('device_results', *[ctypes.byref(x) for x in v], ctypes.byref(ld))
+		self._call('stream', ctypes.byref(st))
+		out = dict(zip(('p', 'gamma', 'alpha', 'varg', 'q', 'vart', 'mask'), (x.value for x in v)))
+		out.update(ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
+		return out
+
+	def set_design(self, dg):
+		"""Another design of the same shape, in any of the forms the constructor takes: the row filter, the compaction and the lists (for Single1Plan the cell selection
+		too) again, and a new graph from the second step on it."""
+		gargs, gshape, gkeep = _design(dg)
+		if tuple(int(v) for v in gshape) != (self.shape[0], self.shape[2]):
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		self._call('design', *gargs)
+		del gkeep
+		return self
+
+
+class DePlan(_DesignPlan):
 	"""de(dg, dt, dc) with single=0 resident on the GPU, on the sparse-design kernels whatever the size (include/normalisr_hip.h: nrm_de_plan_*):
 
 		with cplan.DePlan(dg, dt, dc, lowmem=False, q=True) as plan:
@@ -277,170 +377,36 @@ class DePlan:
 	dg: a numpy matrix, a scipy.sparse matrix (canonicalised by de_sparse.canonical_design_csr), a de_sparse.DesignCSR, a DeviceCSR, or a dense device matrix (anything
 	CoexPlan adopts); it is read when it is set and not kept.  dt: a numpy array (the plan keeps its own device copy; `update` re-uploads) or a device matrix, adopted
 	and rewritten in place by its owner.  lowmem=False adds alpha; q=True adds the q-values of all P-values to every step.  out_dtype: dt's by default, as de.
-	pinv as for CoexPlan."""
+	pinv as for CoexPlan.
+	info(): route (0: the sparse-design kernels, 1: K1 and the fp64 Gram kernel after a hand-back), captured, steps, reruns, rank, dof, bytes, rows_kept."""
+	_prefix, _info_fields = 'nrm_de_plan_', DE_INFO_FIELDS
 
 	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None, pinv='numpy'):
-		self._h = None
-		lib = self._lib = _lib.load()
-		from . import de_sparse
+		super().__init__()
 		if pinv not in ('numpy', 'library'):
 			raise ValueError("pinv must be 'numpy' or 'library'")
 		if np.ndim(dimreduce) != 0 or int(dimreduce) != dimreduce:
 			raise ValueError('dimreduce must be an integer.')
-		de_sparse.refuse_sparse(dt, 'dt')
-		de_sparse.refuse_sparse(dc, 'dc')
-		dev = _adopt(dt)
-		if dev is None:
-			dt = np.asarray(dt)
-			if dt.ndim != 2:
-				raise ValueError('Incorrect dx/dy/dc size.')
-			if dt.dtype not in (np.float32, np.float64):
-				dt = dt.astype(np.float64)
-			dt = np.ascontiguousarray(dt)
-			ptr, shape, dtype, ld = dt.ctypes.data, dt.shape, dt.dtype, dt.shape[1]
-		else:
-			ptr, shape, dtype, ld = dev
-			if dtype not in (np.float32, np.float64):
-				raise ValueError('DePlan: a device matrix must be float32 or float64')
-		dc = np.asarray(dc)
-		if dc.ndim != 2:
-			raise ValueError('Incorrect dx/dy/dc size.')
-		gargs, gshape, gkeep = _design(dg)
-		if dc.shape[1] != shape[1] or gshape[1] != shape[1]:
-			raise ValueError('Unmatching dx/dy/dc dimensions.')
-		self.shape, self.dtype, self.adopted = (int(gshape[0]), int(shape[0]), int(shape[1])), np.dtype(dtype), dev is not None
-		self.out_dtype = np.dtype(dtype if out_dtype is None else out_dtype)
-		if self.out_dtype not in (np.float32, np.float64):
-			raise ValueError('out_dtype must be float32 or float64')
-		nc = self.nc = int(dc.shape[0])
-		self.lowmem, self.q = bool(lowmem), bool(q)
-		if pinv == 'numpy':
-			from .association import _prepare_covariates
-			dc, dci, dcr = _prepare_covariates(dc)
-			dci = np.ascontiguousarray(dci, dtype=np.float64)
-		else:
-			dc = dc if dc.dtype in (np.float32, np.float64) else dc.astype(np.float64)
-			dci, dcr = None, 0
-		dc = np.ascontiguousarray(dc)
-		if device is not None:
-			_lib.check(lib.nrm_set_device(int(device)))
-		h = _vp()
-		_lib.check(lib.nrm_de_plan_create(ctypes.byref(h), *gargs, self.shape[0], ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0,
-										  dc.ctypes.data if nc else None, _code(dc.dtype), nc, None if dci is None or not nc else dci.ctypes.data, int(dcr), int(dimreduce),
-										  _code(self.out_dtype), 0 if self.lowmem else 1, 1 if self.q else 0))
-		self._h = h
-		self._keep = dt if self.adopted else None  # (an adopted matrix lives as long as the plan reads it)
+		(gargs, gkeep), (dt, ptr, shape, dtype, ld), dc = self._problem(dg, dt, dc, lowmem, q, out_dtype)
+		nc = self.nc
+		dc, dci, dcr = _covariates(dc, pinv)
+		self._open(device, dt, *gargs, self.shape[0], ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0, dc.ctypes.data if nc else None, _code(dc.dtype), nc,
+				   None if dci is None or not nc else dci.ctypes.data, dcr, int(dimreduce), _code(self.out_dtype), 0 if self.lowmem else 1, 1 if self.q else 0)
 		del gkeep  # (the design was read inside create)
-
-	def _handle(self):
-		if self._h is None:
-			raise ValueError('DePlan: the plan is closed')
-		return self._h
-
-	def step(self, stream=None):
-		"""One de on the matrices as they stand, queued on `stream` (a hipStream_t as an integer; None: the plan's own).  Does not wait."""
-		_lib.check(self._lib.nrm_de_plan_step(self._handle(), stream))
-		return self
 
 	def check(self):
 		"""Waits for the queued steps and tests what they counted: AssertionError for the reference's assertions (association.py:248,252; de.py:124-131).  Returns the rows
 		handed back since the last check -- > 0: rows all but inside the covariates' span; the step was redone on K1 and the fp64 Gram kernel before returning, and the
 		plan stays on that route until set_design."""
 		back = _i64(0)
-		_lib.check(self._lib.nrm_de_plan_check(self._handle(), ctypes.byref(back)))
+		self._call('check', ctypes.byref(back))
 		return int(back.value)
-
-	def _fetch(self, want_q):
-		ng0, nt, _ = self.shape
-		o = self.out_dtype
-		if want_q:
-			qv = np.empty((ng0, nt), o)
-			_lib.check(self._lib.nrm_de_plan_results(self._handle(), None, None, None, None, None, qv.ctypes.data))
-			return qv
-		p, gam, varg, vart = np.empty((ng0, nt), o), np.empty((ng0, nt), o), np.empty(ng0, o), np.empty((ng0, nt), o)
-		alpha = None if self.lowmem else np.zeros((ng0, nt, self.nc), o)
-		_lib.check(self._lib.nrm_de_plan_results(self._handle(), p.ctypes.data, gam.ctypes.data, alpha.ctypes.data if (alpha is not None and self.nc) else None, varg.ctypes.data,
-												 vart.ctypes.data, None))
-		return p, gam, alpha, varg, vart
-
-	def results(self):
-		"""(P-values (n_group, n_gene), gamma (n_group, n_gene), alpha (n_group, n_gene, n_cov) | None, varg (n_group,), vart (n_group, n_gene)) of the last step as numpy
-		arrays of out_dtype: de's return value."""
-		return self._fetch(False)
-
-	def qvalues(self):
-		"""The Benjamini-Hochberg q-values (n_group, n_gene) of the last step's P-values: binnet.bh of them, bit for bit (a plan created with q=True)."""
-		if not self.q:
-			raise ValueError('DePlan.qvalues: the plan was created without q=True')
-		return self._fetch(True)
-
-	def device_results(self):
-		"""dict(p=, gamma=, alpha=, varg=, q= full-size device addresses (None for what the plan was created without), vart= the genes' variances (n_gene), mask= one byte
-		per grouping (1: tested), ld= row pitch in elements, dtype=, stream= the plan's own stream): for a consumer queued behind the step."""
-		v = [_vp() for _ in range(7)]
-		st, ld = _vp(), _i64(0)
-		_lib.check(self._lib.nrm_de_plan_device_results(self._handle(), *[ctypes.byref(x) for x in v], ctypes.byref(ld)))
-		_lib.check(self._lib.nrm_de_plan_stream(self._handle(), ctypes.byref(st)))
-		out = dict(zip(('p', 'gamma', 'alpha', 'varg', 'q', 'vart', 'mask'), (x.value for x in v)))
-		out.update(ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
-		return out
-
-	def update(self, dt):
-		"""New values of the same shape and dtype into the plan's own copy of dt (ValueError for an adopted matrix: its owner rewrites it in place)."""
-		if self.adopted:
-			raise ValueError('DePlan.update: the plan adopted a device matrix; its owner rewrites it in place')
-		dt = np.ascontiguousarray(np.asarray(dt), dtype=self.dtype)
-		if dt.shape != self.shape[1:]:
-			raise ValueError('Unmatching dx/dy/dc dimensions.')
-		_lib.check(self._lib.nrm_de_plan_upload(self._handle(), dt.ctypes.data))
-		return self
-
-	def set_design(self, dg):
-		"""Another design of the same shape, in any of the forms the constructor takes: the row filter, the compaction and the lists again, and a new graph from the
-		second step on it."""
-		gargs, gshape, gkeep = _design(dg)
-		if tuple(int(v) for v in gshape) != (self.shape[0], self.shape[2]):
-			raise ValueError('Unmatching dx/dy/dc dimensions.')
-		_lib.check(self._lib.nrm_de_plan_design(self._handle(), *gargs))
-		del gkeep
-		return self
-
-	def time(self, steps):
-		"""Milliseconds per step over `steps` steps, between two device events on the plan's stream."""
-		ms = _dbl(0.)
-		_lib.check(self._lib.nrm_de_plan_time(self._handle(), int(steps), ctypes.byref(ms)))
-		return float(ms.value)
-
-	def info(self):
-		"""route (0: the sparse-design kernels, 1: K1 and the fp64 Gram kernel after a hand-back), captured, steps, reruns, rank, dof, bytes, rows_kept."""
-		v = (_i64 * 8)()
-		_lib.check(self._lib.nrm_de_plan_info(self._handle(), v))
-		return dict(zip(DE_INFO_FIELDS, (int(x) for x in v)))
-
-	def close(self):
-		h, self._h = self._h, None
-		if h is not None:
-			_lib.check(self._lib.nrm_de_plan_destroy(h))
-		self._keep = None
-
-	def __enter__(self):
-		return self
-
-	def __exit__(self, *exc):
-		self.close()
-		return False
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001 -- interpreter shutdown
-			pass
 
 
 S1_INFO_FIELDS = ('route', 'captured', 'steps', 'cells_kept', 'covariates', 'reserved', 'bytes', 'rows_kept')
 
 
-class Single1Plan:
+class Single1Plan(_DesignPlan):
 	"""de(dg, dt, dc, single=1) -- a low-MOI screen: every grouping tested on the cells that carry no other grouping -- resident on the GPU (include/normalisr_hip.h:
 	nrm_single1_plan_*):
 
@@ -452,154 +418,28 @@ class Single1Plan:
 			plan.set_design(dg2); plan.step()               # another design of the same shape
 
 	dg, dt, lowmem, q and out_dtype as DePlan takes them.  The design's entries are >= 0 with the largest equal to 1 and at most a quarter of them set, dc has at most
-	32 covariates (NotImplementedError otherwise); dimreduce is a scalar.  The pseudo-inverses are per grouping and taken on the device: there is no `pinv`."""
+	32 covariates (NotImplementedError otherwise); dimreduce is a scalar.  The pseudo-inverses are per grouping and taken on the device: there is no `pinv`.
+	info(): route (0), captured, steps, cells_kept (cells that carry exactly one grouping), covariates, reserved (0), bytes, rows_kept."""
+	_prefix, _info_fields = 'nrm_single1_plan_', S1_INFO_FIELDS
 
 	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None):
-		self._h = None
-		lib = self._lib = _lib.load()
-		from . import de_sparse
+		super().__init__()
 		if np.ndim(dimreduce) != 0:
 			raise NotImplementedError('Single1Plan: one dimreduce for all genes (association_tests(..., single=1) takes one per gene)')
 		if int(dimreduce) != dimreduce:
 			raise ValueError('dimreduce must be an integer.')
-		de_sparse.refuse_sparse(dt, 'dt')
-		de_sparse.refuse_sparse(dc, 'dc')
-		dev = _adopt(dt)
-		if dev is None:
-			dt = np.asarray(dt)
-			if dt.ndim != 2:
-				raise ValueError('Incorrect dx/dy/dc size.')
-			if dt.dtype not in (np.float32, np.float64):
-				dt = dt.astype(np.float64)
-			dt = np.ascontiguousarray(dt)
-			ptr, shape, dtype, ld = dt.ctypes.data, dt.shape, dt.dtype, dt.shape[1]
-		else:
-			ptr, shape, dtype, ld = dev
-			if dtype not in (np.float32, np.float64):
-				raise ValueError('Single1Plan: a device matrix must be float32 or float64')
-		dc = np.asarray(dc)
-		if dc.ndim != 2:
-			raise ValueError('Incorrect dx/dy/dc size.')
-		gargs, gshape, gkeep = _design(dg)
-		if dc.shape[1] != shape[1] or gshape[1] != shape[1]:
-			raise ValueError('Unmatching dx/dy/dc dimensions.')
-		self.shape, self.dtype, self.adopted = (int(gshape[0]), int(shape[0]), int(shape[1])), np.dtype(dtype), dev is not None
-		self.out_dtype = np.dtype(dtype if out_dtype is None else out_dtype)
-		if self.out_dtype not in (np.float32, np.float64):
-			raise ValueError('out_dtype must be float32 or float64')
-		nc = self.nc = int(dc.shape[0])
-		self.lowmem, self.q = bool(lowmem), bool(q)
+		(gargs, gkeep), (dt, ptr, shape, dtype, ld), dc = self._problem(dg, dt, dc, lowmem, q, out_dtype)
+		nc = self.nc
 		dc = np.ascontiguousarray(dc if dc.dtype in (np.float32, np.float64) else dc.astype(np.float64))
-		if device is not None:
-			_lib.check(lib.nrm_set_device(int(device)))
-		h = _vp()
-		_lib.check(lib.nrm_single1_plan_create(ctypes.byref(h), *gargs, self.shape[0], ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0,
-											   dc.ctypes.data if nc else None, _code(dc.dtype), nc, int(dimreduce), _code(self.out_dtype), 0 if self.lowmem else 1, 1 if self.q else 0))
-		self._h = h
-		self._keep = dt if self.adopted else None  # (an adopted matrix lives as long as the plan reads it)
+		self._open(device, dt, *gargs, self.shape[0], ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0, dc.ctypes.data if nc else None, _code(dc.dtype), nc,
+				   int(dimreduce), _code(self.out_dtype), 0 if self.lowmem else 1, 1 if self.q else 0)
 		del gkeep  # (the design was read inside create)
-
-	def _handle(self):
-		if self._h is None:
-			raise ValueError('Single1Plan: the plan is closed')
-		return self._h
-
-	def step(self, stream=None):
-		"""One de on the matrices as they stand, queued on `stream` (a hipStream_t as an integer; None: the plan's own).  Does not wait."""
-		_lib.check(self._lib.nrm_single1_plan_step(self._handle(), stream))
-		return self
 
 	def check(self):
 		"""Waits for the queued steps and tests what they counted, as the reference would have raised it: AssertionError for a grouping with a single value on the cells
 		selected for it (association.py:917-918) and for the result assertions (association.py:248,252; de.py:124-131), ValueError for covariates that are not finite,
 		RuntimeError for too few cells."""
-		_lib.check(self._lib.nrm_single1_plan_check(self._handle()))
-
-	def _fetch(self, want_q):
-		ng0, nt, _ = self.shape
-		o = self.out_dtype
-		if want_q:
-			qv = np.empty((ng0, nt), o)
-			_lib.check(self._lib.nrm_single1_plan_results(self._handle(), None, None, None, None, None, qv.ctypes.data))
-			return qv
-		p, gam, varg, vart = np.empty((ng0, nt), o), np.empty((ng0, nt), o), np.empty(ng0, o), np.empty((ng0, nt), o)
-		alpha = None if self.lowmem else np.zeros((ng0, nt, self.nc), o)
-		_lib.check(self._lib.nrm_single1_plan_results(self._handle(), p.ctypes.data, gam.ctypes.data, alpha.ctypes.data if (alpha is not None and self.nc) else None,
-													  varg.ctypes.data, vart.ctypes.data, None))
-		return p, gam, alpha, varg, vart
-
-	def results(self):
-		"""(P-values (n_group, n_gene), gamma (n_group, n_gene), alpha (n_group, n_gene, n_cov) | None, varg (n_group,), vart (n_group, n_gene)) of the last step as numpy
-		arrays of out_dtype: de's return value."""
-		return self._fetch(False)
-
-	def qvalues(self):
-		"""The Benjamini-Hochberg q-values (n_group, n_gene) of the last step's P-values: binnet.bh of them, bit for bit (a plan created with q=True)."""
-		if not self.q:
-			raise ValueError('Single1Plan.qvalues: the plan was created without q=True')
-		return self._fetch(True)
-
-	def device_results(self):
-		"""dict(p=, gamma=, alpha=, varg=, q=, vart= full-size device addresses (None for what the plan was created without; vart is (n_group, n_gene) here), mask= one
-		byte per grouping (1: tested), ld= row pitch in elements, dtype=, stream= the plan's own stream): for a consumer queued behind the step."""
-		v = [_vp() for _ in range(7)]
-		st, ld = _vp(), _i64(0)
-		_lib.check(self._lib.nrm_single1_plan_device_results(self._handle(), *[ctypes.byref(x) for x in v], ctypes.byref(ld)))
-		_lib.check(self._lib.nrm_single1_plan_stream(self._handle(), ctypes.byref(st)))
-		out = dict(zip(('p', 'gamma', 'alpha', 'varg', 'q', 'vart', 'mask'), (x.value for x in v)))
-		out.update(ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
-		return out
-
-	def update(self, dt):
-		"""New values of the same shape and dtype into the plan's own copy of dt (ValueError for an adopted matrix: its owner rewrites it in place)."""
-		if self.adopted:
-			raise ValueError('Single1Plan.update: the plan adopted a device matrix; its owner rewrites it in place')
-		dt = np.ascontiguousarray(np.asarray(dt), dtype=self.dtype)
-		if dt.shape != self.shape[1:]:
-			raise ValueError('Unmatching dx/dy/dc dimensions.')
-		_lib.check(self._lib.nrm_single1_plan_upload(self._handle(), dt.ctypes.data))
-		return self
-
-	def set_design(self, dg):
-		"""Another design of the same shape, in any of the forms the constructor takes: the row filter, the compaction, the lists and the cell selection again, and a new
-		graph from the second step on it."""
-		gargs, gshape, gkeep = _design(dg)
-		if tuple(int(v) for v in gshape) != (self.shape[0], self.shape[2]):
-			raise ValueError('Unmatching dx/dy/dc dimensions.')
-		_lib.check(self._lib.nrm_single1_plan_design(self._handle(), *gargs))
-		del gkeep
-		return self
-
-	def time(self, steps):
-		"""Milliseconds per step over `steps` steps, between two device events on the plan's stream."""
-		ms = _dbl(0.)
-		_lib.check(self._lib.nrm_single1_plan_time(self._handle(), int(steps), ctypes.byref(ms)))
-		return float(ms.value)
-
-	def info(self):
-		"""route (0), captured, steps, cells_kept (cells that carry exactly one grouping), covariates, reserved (0), bytes, rows_kept."""
-		v = (_i64 * 8)()
-		_lib.check(self._lib.nrm_single1_plan_info(self._handle(), v))
-		return dict(zip(S1_INFO_FIELDS, (int(x) for x in v)))
-
-	def close(self):
-		h, self._h = self._h, None
-		if h is not None:
-			_lib.check(self._lib.nrm_single1_plan_destroy(h))
-		self._keep = None
-
-	def __enter__(self):
-		return self
-
-	def __exit__(self, *exc):
-		self.close()
-		return False
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001 -- interpreter shutdown
-			pass
+		self._call('check')
 
 
 assert __name__ != "__main__"

@@ -1,5 +1,5 @@
 // Resident coex plan behind the C ABI (include/normalisr_hip.h: nrm_coex_plan_*): the problem of coex (dy = dx, single=0; reference coex.py:4-48 over
-// association.py:761-1093) stays in HBM, a step is K1 -> K2 -> K3 -> variances enqueued on one stream, and from the third step on one hipGraphLaunch.  numpy and
+// association.py:761-1093) stays in HBM, a step is K1 -> K2 -> K3 -> variances enqueued on one stream, and from the second step on one hipGraphLaunch (nrm_plan_core.h).  numpy and
 // the library are all a caller needs: no torch, no LAPACK (nrm_covariates_pinv).  The launch sequence is the one nrm_association_tests_host runs
 // (nrm_assoc_k1 / nrm_assoc_band, nrm_host_entry.h), so a step's results are that entry's results.
 //
@@ -8,31 +8,17 @@
 #include <memory>
 #include "nrm_device.h"
 #include "nrm_host_entry.h"
+#include "nrm_plan_core.h"
 
-struct nrm_coex_plan {
-	int device = 0;
+struct nrm_coex_plan : NrmPlanCore {
 	int64_t ng = 0, n = 0, ld = 0, nc = 0, mp = 0, kp = 0;
 	int x_dtype = NRM_F64, out_dtype = NRM_F64, nslices = 0, rank = 0, dimreduce = 0;
-	bool adopted = false, eager_only = false;
+	bool adopted = false;
 	double dof = 0.0, guard_tol = 0.0;
 	const void* dt = nullptr;  // the matrix a step reads: own_dt, or the caller's
 	DevBuf own_dt, dc, dci, cmax, q, e, fix, rows, ss, dot, gwork, flags, p, stat, var;
-	hipStream_t own = nullptr, last = nullptr;
-	hipGraph_t graph = nullptr;
-	hipGraphExec_t exec = nullptr;
-	int64_t steps = 0, reruns = 0, bytes = 0;
-	~nrm_coex_plan() {
-		(void)hipSetDevice(device);
-		(void)hipDeviceSynchronize();
-		if (exec) (void)hipGraphExecDestroy(exec);
-		if (graph) (void)hipGraphDestroy(graph);
-		if (own) (void)hipStreamDestroy(own);
-	}
-	int take(DevBuf& b, size_t bytes_) {
-		NRM_TRY(b.alloc(bytes_));
-		bytes += (int64_t)bytes_;
-		return NRM_OK;
-	}
+	int64_t reruns = 0;
+	~nrm_coex_plan() { shutdown(); }  // (its body runs before the DevBuf members go back to the pool: NrmPlanCore::shutdown)
 };
 
 namespace {
@@ -62,21 +48,8 @@ int plan_bind(nrm_coex_plan* pl, const char* who) {
 	return NRM_OK;
 }
 
-int plan_upload(nrm_coex_plan* pl, const void* h_dt) {
-	NRM_TRY(nrm_upload(h_dt, pl->own_dt.p, pl->ng * pl->n * (int64_t)nrm_esize(pl->x_dtype), 0, (void*)pl->own));
-	NRM_HIP(hipStreamSynchronize(pl->own));
-	return NRM_OK;
-}
-
-// the step stays eager from here on; nrm_last_error keeps the reason (StepGraph's rule, normalisr_amd/distributed.py)
-int plan_stay_eager(nrm_coex_plan* pl, const char* what, hipError_t e, hipStream_t st) {
-	(void)hipGetLastError();
-	pl->eager_only = true;
-	char why[256];
-	snprintf(why, sizeof(why), "nrm_coex_plan_step: not captured as a HIP graph (%s: %s); the plan runs eagerly", what, e == hipSuccess ? nrm_last_error() : hipGetErrorString(e));
-	NRM_TRY(plan_enqueue(pl, pl->nslices, pl->rows.as<double>(), st));
-	nrm_set_error("%s", why);
-	return NRM_OK;
+int plan_upload(nrm_coex_plan* pl, const char* who, const void* h_dt) {
+	return nrm_plan_upload(*pl, who, pl->adopted, h_dt, pl->own_dt.p, pl->ng * pl->n * (int64_t)nrm_esize(pl->x_dtype));
 }
 
 // reads and clears the counters once the last step is through; the guard's rerun; caller holds nrm_host_entry_mutex
@@ -177,48 +150,19 @@ extern "C" int nrm_coex_plan_create(nrm_coex_plan** plan, const void* dt, int dt
 	if (pl->adopted)
 		NRM_HIP(hipDeviceSynchronize());  // (whatever the caller queued to fill its matrix is through before the first step reads it)
 	else
-		NRM_TRY(plan_upload(pl.get(), dt));
+		NRM_TRY(plan_upload(pl.get(), "nrm_coex_plan_create", dt));
 	*plan = pl.release();
 	return NRM_OK;
 }
 
 extern "C" int nrm_coex_plan_upload(nrm_coex_plan* plan, const void* h_dt) {
 	NRM_TRY(plan_bind(plan, "nrm_coex_plan_upload"));
-	NRM_REQUIRE(!plan->adopted, "nrm_coex_plan_upload: the plan adopted the caller's device matrix (rewrite it in place)");
-	NRM_REQUIRE(h_dt != nullptr, "nrm_coex_plan_upload: null matrix");
-	if (plan->last && plan->last != plan->own) NRM_HIP(hipStreamSynchronize(plan->last));  // (a step on the caller's stream may still read the copy)
-	return plan_upload(plan, h_dt);
+	return plan_upload(plan, "nrm_coex_plan_upload", h_dt);
 }
 
 extern "C" int nrm_coex_plan_step(nrm_coex_plan* plan, void* stream) {
 	NRM_TRY(plan_bind(plan, "nrm_coex_plan_step"));
-	hipStream_t st = stream ? (hipStream_t)stream : plan->own;
-	plan->last = st;
-	plan->steps++;
-	if (plan->exec) {
-		NRM_HIP(hipGraphLaunch(plan->exec, st));
-		return NRM_OK;
-	}
-	if (plan->eager_only || plan->steps < 2 || nrm_debug_is("graph", "0")) return plan_enqueue(plan, plan->nslices, plan->rows.as<double>(), st);
-	// the second step: recorded, not run (thread-local capture: other threads' HIP calls are none of its business), instantiated, launched
-	hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-	if (e != hipSuccess) return plan_stay_eager(plan, "hipStreamBeginCapture", e, st);
-	const int rc = plan_enqueue(plan, plan->nslices, plan->rows.as<double>(), st);
-	hipGraph_t g = nullptr;
-	e = hipStreamEndCapture(st, &g);
-	if (rc != NRM_OK || e != hipSuccess || !g) {
-		if (g) (void)hipGraphDestroy(g);
-		return plan_stay_eager(plan, rc != NRM_OK ? "a launch inside the capture" : "hipStreamEndCapture", rc != NRM_OK ? hipSuccess : (e != hipSuccess ? e : hipErrorUnknown), st);
-	}
-	hipGraphExec_t x = nullptr;
-	e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-	if (e != hipSuccess || !x) {
-		(void)hipGraphDestroy(g);
-		return plan_stay_eager(plan, "hipGraphInstantiate", e != hipSuccess ? e : hipErrorUnknown, st);
-	}
-	plan->graph = g, plan->exec = x;
-	NRM_HIP(hipGraphLaunch(plan->exec, st));
-	return NRM_OK;
+	return nrm_plan_step(*plan, "nrm_coex_plan_step", stream, [plan](hipStream_t st) { return plan_enqueue(plan, plan->nslices, plan->rows.as<double>(), st); });
 }
 
 extern "C" int nrm_coex_plan_check(nrm_coex_plan* plan, int64_t* guard_hits, double* guard_worst) {
@@ -250,9 +194,7 @@ extern "C" int nrm_coex_plan_device_results(nrm_coex_plan* plan, void** d_p, voi
 }
 
 extern "C" int nrm_coex_plan_stream(nrm_coex_plan* plan, void** stream) {
-	NRM_REQUIRE(plan != nullptr && stream != nullptr, "nrm_coex_plan_stream: null pointer");
-	*stream = (void*)plan->own;
-	return NRM_OK;
+	return nrm_plan_stream(plan, "nrm_coex_plan_stream", stream);
 }
 
 extern "C" int nrm_coex_plan_info(nrm_coex_plan* plan, int64_t info[8]) {
@@ -263,29 +205,7 @@ extern "C" int nrm_coex_plan_info(nrm_coex_plan* plan, int64_t info[8]) {
 
 extern "C" int nrm_coex_plan_time(nrm_coex_plan* plan, int64_t steps, double* ms_per_step) {
 	NRM_TRY(plan_bind(plan, "nrm_coex_plan_time"));
-	NRM_REQUIRE(steps > 0 && ms_per_step != nullptr, "nrm_coex_plan_time: bad arguments");
-	while (plan->steps < 2) NRM_TRY(nrm_coex_plan_step(plan, nullptr));  // (the eager step and the capture are not what is timed)
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	NRM_HIP(hipEventCreate(&t0));
-	hipError_t e = hipEventCreate(&t1);
-	int rc = NRM_OK;
-	float ms = 0.f;
-	if (e == hipSuccess) e = hipEventRecord(t0, plan->own);
-	for (int64_t i = 0; i < steps && e == hipSuccess && rc == NRM_OK; i++) rc = nrm_coex_plan_step(plan, nullptr);
-	if (e == hipSuccess && rc == NRM_OK) e = hipEventRecord(t1, plan->own);
-	if (e == hipSuccess && rc == NRM_OK) e = hipEventSynchronize(t1);
-	if (e == hipSuccess && rc == NRM_OK) e = hipEventElapsedTime(&ms, t0, t1);
-	(void)hipEventDestroy(t0);
-	if (t1) (void)hipEventDestroy(t1);
-	NRM_TRY(rc);
-	NRM_HIP(e);
-	*ms_per_step = (double)ms / (double)steps;
-	return NRM_OK;
+	return nrm_plan_time(*plan, "nrm_coex_plan_time", steps, ms_per_step, [plan] { return nrm_coex_plan_step(plan, nullptr); });
 }
 
-extern "C" int nrm_coex_plan_destroy(nrm_coex_plan* plan) {
-	if (!plan) return NRM_OK;
-	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
-	delete plan;  // (synchronises the device, then the buffers go back to the pool)
-	return NRM_OK;
-}
+extern "C" int nrm_coex_plan_destroy(nrm_coex_plan* plan) { return nrm_plan_destroy(plan); }

@@ -19,3 +19,35 @@ int nrm_de_design_malformed();
 // for the fill; everything it takes besides the lists returns to the pool on the way out.  The caller has synchronised the device.  No row left: NRM_E_ARG.
 int nrm_de_design_set(const char* who, const NrmDePlanDesign& in, int64_t ng0, int64_t n, uint8_t* d_mask, int64_t* d_c2f, int32_t* d_f2c, bool want_ell, double max_density,
 					  hipStream_t st, NrmDeDesign& out);
+
+// ---- what the entries of the two plans do alike around a design.  Plan: nrm_de_plan or nrm_single1_plan -- L, device, drop_graph() and name, "nrm_de_plan" or
+// "nrm_single1_plan" ----------------------------------------------------------------------------------------------------------------------------------------------
+template <typename Plan>
+int plan_bind(Plan* pl, const char* who) {
+	NRM_REQUIRE(pl != nullptr, "%s: null plan", who);
+	NRM_REQUIRE(pl->L != nullptr, "%s: the plan has no design (the last %s_design was refused)", who, Plan::name);
+	NRM_HIP(hipSetDevice(pl->device));
+	return NRM_OK;
+}
+
+// *_plan_design once the arguments are checked; set_design(plan, g): the plan's own plan_set_design
+template <typename Plan, typename SetDesign>
+int nrm_plan_new_design(Plan* plan, const NrmDePlanDesign& g, SetDesign set_design) {
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_HIP(hipSetDevice(plan->device));
+	NRM_HIP(hipDeviceSynchronize());  // (the steps queued on the old lists are through, and so is whatever filled the caller's arrays)
+	plan->drop_graph();
+	const int rc = set_design(plan, g);
+	if (rc != NRM_OK) plan->L.reset();  // (the row map may already be the refused design's: the plan has none until a design is accepted)
+	return rc;
+}
+
+// *bh_bytes: nrm_bh's workspace for the q-values of count P-values, 0 without want_q; who: the create entry
+static inline int nrm_plan_bh_bytes(const char* who, int want_q, int64_t count, int out_dtype, int64_t* bh_bytes) {
+	*bh_bytes = want_q ? nrm_bh_workspace_bytes(count, out_dtype) : 0;
+	if (*bh_bytes < 0) {
+		nrm_set_error("%s: q-values of %lld P-values are not provided (nrm_bh takes at most 2^31 - 1)", who, (long long)count);
+		return (int)*bh_bytes;
+	}
+	return NRM_OK;
+}

@@ -11,6 +11,7 @@
 #include "nrm_host_entry.h"
 #include "nrm_design.h"
 #include "nrm_de_design.h"
+#include "nrm_plan_core.h"
 
 namespace {
 
@@ -71,11 +72,11 @@ __global__ __launch_bounds__(256) void k_de_bounds(const T* __restrict__ P, cons
 
 }  // namespace
 
-struct nrm_de_plan {
-	int device = 0;
+struct nrm_de_plan : NrmPlanCore {
+	static constexpr const char* name = "nrm_de_plan";
 	int64_t ng0 = 0, nt = 0, n = 0, ldt = 0, nc = 0, ncu = 0, ngk = 0;
 	int g_dtype = NRM_F64, t_dtype = NRM_F64, out_dtype = NRM_F64, rank = 0, dimreduce = 0, ci = -1;
-	bool adopted = false, eager_only = false, want_alpha = false, want_q = false, dense_route = false, dense_ready = false;
+	bool adopted = false, want_alpha = false, want_q = false, dense_route = false, dense_ready = false;
 	double dof = 0.0, cval = 0.0, guard_tol = 0.0;
 	const void* dt = nullptr;  // the matrix a step reads: own_dt, or the caller's
 	int64_t nxp0 = 0, nyp = 0, kp = 0, bh_bytes = 0;
@@ -84,26 +85,8 @@ struct nrm_de_plan {
 	DevBuf own_dt, dc, dci, cmax, mask, c2f, f2c, flags, ssx, bx, ssy, by, dot, common, ct, code, cp, cg, ca, P, G, A, varg, vart, q, bhwork;
 	// the dense route
 	DevBuf gd, rx, ry, gwork;
-	hipStream_t own = nullptr, last = nullptr;
-	hipGraph_t graph = nullptr;
-	hipGraphExec_t exec = nullptr;
-	int64_t steps = 0, fresh = 0, reruns = 0, bytes = 0, list_bytes = 0;
-	void drop_graph() {
-		if (exec) (void)hipGraphExecDestroy(exec);
-		if (graph) (void)hipGraphDestroy(graph);
-		exec = nullptr, graph = nullptr;
-	}
-	~nrm_de_plan() {
-		(void)hipSetDevice(device);
-		(void)hipDeviceSynchronize();
-		drop_graph();
-		if (own) (void)hipStreamDestroy(own);
-	}
-	int take(DevBuf& b, size_t bytes_) {
-		NRM_TRY(b.alloc(bytes_));
-		bytes += (int64_t)bytes_;
-		return NRM_OK;
-	}
+	int64_t reruns = 0, list_bytes = 0;
+	~nrm_de_plan() { shutdown(); }  // (its body runs before the DevBuf members go back to the pool: NrmPlanCore::shutdown)
 	bool all_rows() const { return ngk == ng0; }
 	// what the sweep and nrm_alpha write: the full-size arrays when every row is tested, the compact ones otherwise
 	void* sweep_p() const { return all_rows() ? P.p : cp.p; }
@@ -212,28 +195,8 @@ int plan_enqueue(nrm_de_plan* pl, hipStream_t st) {
 	return pl->out_dtype == NRM_F64 ? plan_finish<double>(pl, st) : plan_finish<float>(pl, st);
 }
 
-int plan_bind(nrm_de_plan* pl, const char* who) {
-	NRM_REQUIRE(pl != nullptr, "%s: null plan", who);
-	NRM_REQUIRE(pl->L != nullptr, "%s: the plan has no design (the last nrm_de_plan_design was refused)", who);
-	NRM_HIP(hipSetDevice(pl->device));
-	return NRM_OK;
-}
-
-int plan_upload(nrm_de_plan* pl, const void* h_dt) {
-	NRM_TRY(nrm_upload(h_dt, pl->own_dt.p, pl->nt * pl->n * (int64_t)nrm_esize(pl->t_dtype), 0, (void*)pl->own));
-	NRM_HIP(hipStreamSynchronize(pl->own));
-	return NRM_OK;
-}
-
-// the step stays eager from here on; nrm_last_error keeps the reason (plan_stay_eager of nrm_coex_plan.hip)
-int plan_stay_eager(nrm_de_plan* pl, const char* what, hipError_t e, hipStream_t st) {
-	(void)hipGetLastError();
-	pl->eager_only = true;
-	char why[256];
-	snprintf(why, sizeof(why), "nrm_de_plan_step: not captured as a HIP graph (%s: %s); the plan runs eagerly", what, e == hipSuccess ? nrm_last_error() : hipGetErrorString(e));
-	NRM_TRY(plan_enqueue(pl, st));
-	nrm_set_error("%s", why);
-	return NRM_OK;
+int plan_upload(nrm_de_plan* pl, const char* who, const void* h_dt) {
+	return nrm_plan_upload(*pl, who, pl->adopted, h_dt, pl->own_dt.p, pl->nt * pl->n * (int64_t)nrm_esize(pl->t_dtype));
 }
 
 // the dense route's buffers, once, and the compacted design as a matrix: written from the entries of the lists (their CSR form holds every entry of the rows kept)
@@ -292,17 +255,13 @@ extern "C" int nrm_de_plan_create(nrm_de_plan** plan, int design_form, const voi
 	*plan = nullptr;
 	const int64_t n = n_cells;
 	if (ldt == 0) ldt = n;
-	NrmDePlanDesign g;
-	g.form = design_form, g.values = dg, g.dtype = dg_dtype, g.ld = ldg ? ldg : n, g.indptr = indptr, g.indices = indices, g.nnz = nnz, g.on_device = dg_on_device;
+	const NrmDePlanDesign g = nrm_de_plan_design_of(design_form, dg, dg_dtype, ldg, indptr, indices, nnz, dg_on_device, n);
 	// every check, the covariates' pseudo-inverse and rank when the caller has none included (host arithmetic, nrm_de_plan_args.h): all before any device call
 	std::vector<double> c64, own_dci;
 	NRM_TRY(nrm_de_plan_create_args(g, ng0, dt, dt_dtype, nt, n, ldt, dt_on_device, h_dc, c_dtype, nc, &h_dci, &rank, dimreduce, out_dtype, nrm_de_sparse_max_covariates(), c64,
 									own_dci));
-	const int64_t bh_bytes = want_q ? nrm_bh_workspace_bytes(ng0 * nt, out_dtype) : 0;
-	if (bh_bytes < 0) {
-		nrm_set_error("nrm_de_plan_create: q-values of %lld P-values are not provided (nrm_bh takes at most 2^31 - 1)", (long long)(ng0 * nt));
-		return (int)bh_bytes;
-	}
+	int64_t bh_bytes = 0;
+	NRM_TRY(nrm_plan_bh_bytes("nrm_de_plan_create", want_q, ng0 * nt, out_dtype, &bh_bytes));
 
 	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
 	NRM_TRY(nrm_bind_device());
@@ -360,7 +319,7 @@ extern "C" int nrm_de_plan_create(nrm_de_plan** plan, int design_form, const voi
 	NRM_TRY(nrm_fill_zero(pl->flags.p, 32, (void*)st));
 	if (pl->adopted || dg_on_device) NRM_HIP(hipDeviceSynchronize());  // (whatever the caller queued to fill its matrices is through before they are read)
 	NRM_TRY(plan_set_design(pl.get(), g));
-	if (!pl->adopted) NRM_TRY(plan_upload(pl.get(), dt));
+	if (!pl->adopted) NRM_TRY(plan_upload(pl.get(), "nrm_de_plan_create", dt));
 	NRM_HIP(hipStreamSynchronize(st));
 	*plan = pl.release();
 	return NRM_OK;
@@ -369,56 +328,20 @@ extern "C" int nrm_de_plan_create(nrm_de_plan** plan, int design_form, const voi
 extern "C" int nrm_de_plan_design(nrm_de_plan* plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
 								  int dg_on_device) {
 	NRM_REQUIRE(plan != nullptr, "nrm_de_plan_design: null plan");
-	NrmDePlanDesign g;
-	g.form = design_form, g.values = dg, g.dtype = dg_dtype, g.ld = ldg ? ldg : plan->n, g.indptr = indptr, g.indices = indices, g.nnz = nnz, g.on_device = dg_on_device;
+	const NrmDePlanDesign g = nrm_de_plan_design_of(design_form, dg, dg_dtype, ldg, indptr, indices, nnz, dg_on_device, plan->n);
 	NRM_TRY(nrm_de_plan_design_args("nrm_de_plan_design", g, plan->ng0, plan->n));
-	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
-	NRM_HIP(hipSetDevice(plan->device));
-	NRM_HIP(hipDeviceSynchronize());  // (the steps queued on the old lists are through, and so is whatever filled the caller's arrays)
-	plan->drop_graph();
-	const int rc = plan_set_design(plan, g);
-	if (rc != NRM_OK) plan->L.reset();  // (the row map may already be the refused design's: the plan has none until a design is accepted)
-	return rc;
+	return nrm_plan_new_design(plan, g, plan_set_design);
 }
 
 extern "C" int nrm_de_plan_upload(nrm_de_plan* plan, const void* h_dt) {
 	NRM_TRY(plan_bind(plan, "nrm_de_plan_upload"));
-	NRM_REQUIRE(!plan->adopted, "nrm_de_plan_upload: the plan adopted the caller's device matrix (rewrite it in place)");
-	NRM_REQUIRE(h_dt != nullptr, "nrm_de_plan_upload: null matrix");
-	if (plan->last && plan->last != plan->own) NRM_HIP(hipStreamSynchronize(plan->last));  // (a step on the caller's stream may still read the copy)
-	return plan_upload(plan, h_dt);
+	return plan_upload(plan, "nrm_de_plan_upload", h_dt);
 }
 
+// (the graph is of one route: plan_check drops it when it hands back, and the second step on the dense route is captured anew)
 extern "C" int nrm_de_plan_step(nrm_de_plan* plan, void* stream) {
 	NRM_TRY(plan_bind(plan, "nrm_de_plan_step"));
-	hipStream_t st = stream ? (hipStream_t)stream : plan->own;
-	plan->last = st;
-	plan->steps++;
-	plan->fresh++;
-	if (plan->exec) {
-		NRM_HIP(hipGraphLaunch(plan->exec, st));
-		return NRM_OK;
-	}
-	if (plan->eager_only || plan->fresh < 2 || nrm_debug_is("graph", "0")) return plan_enqueue(plan, st);
-	// the second step on a route: recorded, not run (thread-local capture), instantiated, launched
-	hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-	if (e != hipSuccess) return plan_stay_eager(plan, "hipStreamBeginCapture", e, st);
-	const int rc = plan_enqueue(plan, st);
-	hipGraph_t g = nullptr;
-	e = hipStreamEndCapture(st, &g);
-	if (rc != NRM_OK || e != hipSuccess || !g) {
-		if (g) (void)hipGraphDestroy(g);
-		return plan_stay_eager(plan, rc != NRM_OK ? "a launch inside the capture" : "hipStreamEndCapture", rc != NRM_OK ? hipSuccess : (e != hipSuccess ? e : hipErrorUnknown), st);
-	}
-	hipGraphExec_t x = nullptr;
-	e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-	if (e != hipSuccess || !x) {
-		(void)hipGraphDestroy(g);
-		return plan_stay_eager(plan, "hipGraphInstantiate", e != hipSuccess ? e : hipErrorUnknown, st);
-	}
-	plan->graph = g, plan->exec = x;
-	NRM_HIP(hipGraphLaunch(plan->exec, st));
-	return NRM_OK;
+	return nrm_plan_step(*plan, "nrm_de_plan_step", stream, [plan](hipStream_t st) { return plan_enqueue(plan, st); });
 }
 
 extern "C" int nrm_de_plan_check(nrm_de_plan* plan, int64_t* handed_back) {
@@ -471,9 +394,7 @@ extern "C" int nrm_de_plan_device_results(nrm_de_plan* plan, void** d_p, void** 
 }
 
 extern "C" int nrm_de_plan_stream(nrm_de_plan* plan, void** stream) {
-	NRM_REQUIRE(plan != nullptr && stream != nullptr, "nrm_de_plan_stream: null pointer");
-	*stream = (void*)plan->own;
-	return NRM_OK;
+	return nrm_plan_stream(plan, "nrm_de_plan_stream", stream);
 }
 
 extern "C" int nrm_de_plan_info(nrm_de_plan* plan, int64_t info[8]) {
@@ -485,29 +406,7 @@ extern "C" int nrm_de_plan_info(nrm_de_plan* plan, int64_t info[8]) {
 
 extern "C" int nrm_de_plan_time(nrm_de_plan* plan, int64_t steps, double* ms_per_step) {
 	NRM_TRY(plan_bind(plan, "nrm_de_plan_time"));
-	NRM_REQUIRE(steps > 0 && ms_per_step != nullptr, "nrm_de_plan_time: bad arguments");
-	while (plan->fresh < 2) NRM_TRY(nrm_de_plan_step(plan, nullptr));  // (the eager step and the capture are not what is timed)
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	NRM_HIP(hipEventCreate(&t0));
-	hipError_t e = hipEventCreate(&t1);
-	int rc = NRM_OK;
-	float ms = 0.f;
-	if (e == hipSuccess) e = hipEventRecord(t0, plan->own);
-	for (int64_t i = 0; i < steps && e == hipSuccess && rc == NRM_OK; i++) rc = nrm_de_plan_step(plan, nullptr);
-	if (e == hipSuccess && rc == NRM_OK) e = hipEventRecord(t1, plan->own);
-	if (e == hipSuccess && rc == NRM_OK) e = hipEventSynchronize(t1);
-	if (e == hipSuccess && rc == NRM_OK) e = hipEventElapsedTime(&ms, t0, t1);
-	(void)hipEventDestroy(t0);
-	if (t1) (void)hipEventDestroy(t1);
-	NRM_TRY(rc);
-	NRM_HIP(e);
-	*ms_per_step = (double)ms / (double)steps;
-	return NRM_OK;
+	return nrm_plan_time(*plan, "nrm_de_plan_time", steps, ms_per_step, [plan] { return nrm_de_plan_step(plan, nullptr); });
 }
 
-extern "C" int nrm_de_plan_destroy(nrm_de_plan* plan) {
-	if (!plan) return NRM_OK;
-	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
-	delete plan;  // (synchronises the device, then the buffers go back to the pool)
-	return NRM_OK;
-}
+extern "C" int nrm_de_plan_destroy(nrm_de_plan* plan) { return nrm_plan_destroy(plan); }

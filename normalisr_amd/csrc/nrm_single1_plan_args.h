@@ -9,18 +9,13 @@
 // Every check of create, in the order nrm_de_plan_create_args makes them.  c64: the covariates as fp64.
 static inline int nrm_single1_plan_create_args(const NrmDePlanDesign& g, int64_t ng0, const void* dt, int dt_dtype, int64_t nt, int64_t n, int64_t ldt, int dt_on_device,
 											   const void* h_dc, int c_dtype, int64_t nc, int dimreduce, int out_dtype, std::vector<double>& c64) {
-	NRM_REQUIRE((dt_dtype == NRM_F32 || dt_dtype == NRM_F64) && (out_dtype == NRM_F32 || out_dtype == NRM_F64) && (nc <= 0 || c_dtype == NRM_F32 || c_dtype == NRM_F64),
-				"nrm_single1_plan_create: bad dtype");
-	NRM_REQUIRE(ng0 > 0 && nt > 0 && n > 0 && dt != nullptr, "Incorrect dx/dy/dc size.");
-	NRM_REQUIRE(n <= 0x7fffffffLL && ng0 <= 0x7fffffffLL && nt <= 0x7fffffffLL, "nrm_single1_plan_create: more than 2^31 - 1 rows or cells");
-	NRM_TRY_ARGS(nrm_de_plan_design_args("nrm_single1_plan_create", g, ng0, n));
+	NRM_TRY_ARGS(nrm_plan_create_args_open("nrm_single1_plan_create", g, ng0, dt, dt_dtype, nt, n, c_dtype, nc, out_dtype));
 	NRM_REQUIRE(nc >= 0 && (nc == 0 || h_dc), "Unmatching dx/dy/dc dimensions.");  // (the words of nrm_association_tests_single1_host for covariates that are not there)
 	if (nc > NRM_SINGLE1_PLAN_MAX_COVARIATES) {
 		nrm_set_error("nrm_single1_plan_create covers up to %d covariates (the package's masked-Gram path takes more)", NRM_SINGLE1_PLAN_MAX_COVARIATES);
 		return NRM_E_UNSUPPORTED;
 	}
-	NRM_REQUIRE(dimreduce >= 0, "dimreduce must be a non-negative integer.");
-	NRM_REQUIRE(dt_on_device ? ldt >= n : ldt == n, "nrm_single1_plan_create: row pitch smaller than the row (a host matrix is contiguous)");
+	NRM_TRY_ARGS(nrm_plan_create_args_close("nrm_single1_plan_create", dimreduce, n, ldt, dt_on_device));
 	nrm_covariates_to_f64(h_dc, c_dtype, (size_t)(nc * n), c64);
 	return NRM_OK;
 }

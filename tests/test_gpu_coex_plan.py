@@ -147,6 +147,28 @@ def test_coex_plan_c_entry_replay_is_the_step(tmp_path):
 		assert scale_close(d, dr, tol) and scale_close(v, vr, tol)
 
 
+def debug_with(switch):
+	"""NRM_DEBUG for a child: the keys this process has, and `switch`."""
+	return ','.join([p for p in os.environ.get('NRM_DEBUG', '').split(',') if p.strip()] + [switch])
+
+
+def test_coex_plan_c_entry_graph_switch_off(golden, tmp_path):
+	"""NRM_DEBUG graph=0 in the child: three steps on G1, none of them captured, and the same bits as the three steps -- eager, captured, replayed -- without it."""
+	g1 = golden('G1_c1')
+	ns = int(g1['coex_n'])
+	arrays = dict(dt=g1['dt'][:ns], dc=g1['dc'])
+	job = dict(cases=[dict(name='g1', dt='dt', dc='dc', steps=3, snaps=[3])])
+	(tmp_path / 'on').mkdir(), (tmp_path / 'off').mkdir()
+	out, info = run_child(tmp_path / 'on', 'cases', arrays, job)
+	out0, info0 = run_child(tmp_path / 'off', 'cases', arrays, job, env={'NRM_DEBUG': debug_with('graph=0')})
+	print(info['g1'], info0['g1'])
+	assert info['g1']['captured'] == 1 and info['g1']['steps'] == 3
+	assert info0['g1']['captured'] == 0 and info0['g1']['steps'] == 3
+	for a, b in zip(got(out0, 'g1', 3), got(out, 'g1', 3)):
+		assert a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True)
+	assert p_close(got(out0, 'g1', 3)[0], g1['coex_p'])
+
+
 def test_coex_plan_c_entry_in_place_rewrite(golden, tmp_path):
 	import normalisr_amd.normalisr as norm
 	g = golden('G11_i8hard')

@@ -219,6 +219,23 @@ def test_de_plan_c_entry_qvalues(tmp_path, dtype):
 	assert (q >= p).all() and (q <= 1).all()
 
 
+def test_de_plan_c_entry_graph_switch_off(tmp_path):
+	"""NRM_DEBUG graph=0 in the child: three steps on the 70 x 64 screen with alpha and q-values, none of them captured, and the same bits as the three steps --
+	eager, captured, replayed -- without it."""
+	job = dict(cases=[dict(name='g', lowmem=False, q=True, steps=3, forms=['dense'], screen=dict(seed=51, dtype='float64', nc=3, valued=True))])
+	(tmp_path / 'on').mkdir(), (tmp_path / 'off').mkdir()
+	out, info = run_child(tmp_path / 'on', 'cases', {}, job)
+	debug = ','.join([p for p in os.environ.get('NRM_DEBUG', '').split(',') if p.strip()] + ['graph=0'])
+	out0, info0 = run_child(tmp_path / 'off', 'cases', {}, job, env={'NRM_DEBUG': debug})
+	print(info['g.dense'], info0['g.dense'])
+	assert info['g.dense']['captured'] == 1 and info['g.dense']['steps'] == 3
+	assert info0['g.dense']['captured'] == 0 and info0['g.dense']['steps'] == 3 and info0['g.dense']['rows_kept'] == 69
+	res = got(out0, 'g.dense')
+	assert all(v is not None for v in res) and (res[0][9] == 1).all() and (res[0] < 1).any()
+	same(res, got(out, 'g.dense'), 'graph=0')
+	assert out0['g.dense.q'].dtype == out['g.dense.q'].dtype and np.array_equal(out0['g.dense.q'], out['g.dense.q'])
+
+
 def test_de_plan_c_entry_bounds(tmp_path):
 	"""A NaN planted in one expression value: check() raises AssertionError (the reference's assertions, counted on the device); update and a step later the plan
 	is clean and equals a fresh one."""

@@ -31,10 +31,11 @@ SEEDS, NCS = child.SEEDS, child.NCS
 FORMS = ['dense', 'scipy', 'devcsr', 'devcsr_data']  # (devcsr: no data array, every entry is 1; devcsr_data: with one)
 
 
-def run_child(tmp_path, scenario, arrays, job, timeout=240):
+def run_child(tmp_path, scenario, arrays, job, env=None, timeout=240):
 	src, dst = str(tmp_path / (scenario + '_in.npz')), str(tmp_path / (scenario + '_out.npz'))
 	np.savez(src, job=np.array(json.dumps(job)), **arrays)
-	r = subprocess.run([sys.executable, os.path.join(HERE, 'single1_plan_child.py'), scenario, src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
+	r = subprocess.run([sys.executable, os.path.join(HERE, 'single1_plan_child.py'), scenario, src, dst], env=dict(os.environ, **(env or {})), stdout=subprocess.PIPE,
+					   stderr=subprocess.STDOUT, text=True, timeout=timeout)
 	assert r.returncode == 0 and 'child ok' in r.stdout, r.stdout[-3000:]
 	out = np.load(dst)
 	return out, json.loads(str(out['notes']))
@@ -178,6 +179,24 @@ def test_single1_plan_c_entry_qvalues(tmp_path, dtype):
 	assert q.dtype == p.dtype == np.dtype(dtype) and q.shape == p.shape and want.dtype == q.dtype
 	assert np.array_equal(q.ravel(), want)
 	assert (q >= p).all() and (q <= 1).all()
+
+
+def test_single1_plan_c_entry_graph_switch_off(tmp_path):
+	"""NRM_DEBUG graph=0 in the child: three steps on the 67 x 69 x 2051 screen with 3 covariates, alpha and q-values, none of them captured, and the same bits as the
+	three steps -- eager, captured, replayed -- without it."""
+	job = dict(cases=[dict(name='g', lowmem=False, q=True, steps=3, forms=['dense'], screen=dict(seed=SEEDS['q'], dtype='float64', nc=3))])
+	(tmp_path / 'on').mkdir(), (tmp_path / 'off').mkdir()
+	out, info = run_child(tmp_path / 'on', 'cases', {}, job)
+	debug = ','.join([p for p in os.environ.get('NRM_DEBUG', '').split(',') if p.strip()] + ['graph=0'])
+	out0, info0 = run_child(tmp_path / 'off', 'cases', {}, job, env={'NRM_DEBUG': debug})
+	print(info['g.dense'], info0['g.dense'])
+	assert info['g.dense']['captured'] == 1 and info['g.dense']['steps'] == 3
+	assert info0['g.dense']['captured'] == 0 and info0['g.dense']['steps'] == 3 and info0['g.dense']['rows_kept'] == 65
+	assert info0['g.dense']['cells_kept'] == info['g.dense']['cells_kept'] > 0
+	res = got(out0, 'g.dense')
+	assert all(v is not None for v in res) and (res[0][DROPPED] == 1).all() and (res[0] < 1).any()
+	same(res, got(out, 'g.dense'), 'graph=0')
+	assert out0['g.dense.q'].dtype == out['g.dense.q'].dtype and np.array_equal(out0['g.dense.q'], out['g.dense.q'])
 
 
 def test_single1_plan_c_entry_raises_what_the_reference_raises(tmp_path):
