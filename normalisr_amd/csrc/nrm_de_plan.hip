@@ -1,8 +1,8 @@
 // Resident de plan behind the C ABI (include/normalisr_hip.h: nrm_de_plan_*): de(dg, dt, dc) with single=0 on a sparse design (reference de.py:4-132 over
 // association.py:224-249) for a caller that repeats it on a screen of one shape -- numpy and the library are all it needs.  The design is filtered (de.py:93), compacted
-// and turned into the lists of csrc/nrm_design_lists.hip when it is set (nrm_de_design.hip, shared with the single=1 plan); a step is nrm_design_stats -> the products -> nrm_assoc_sweep -> nrm_alpha, the launch sequence
-// of nrm_host_de_sparse (nrm_host_de.hip), then the kernels of this file: the re-inflation of de.py:107-122, the variances, the assertions of de.py:124-131 as a count,
-// and nrm_bh.  One stream, launches and memset nodes only; from the second step on a route one hipGraphLaunch.
+// and turned into the lists of csrc/nrm_design_lists.hip when it is set (nrm_de_design.hip, shared with the single=1 plan); a step is NrmDeSparseStep
+// (nrm_de_sparse_step.h: the record nrm_host_de_sparse runs too), then the kernels of this file: the re-inflation of de.py:107-122, the variances, the assertions of
+// de.py:124-131 as a count, and nrm_bh.  One stream, launches and memset nodes only; from the second step on a route one hipGraphLaunch.
 //
 // Every buffer a step needs is taken from the scratch pool at create (sized for all ng0 design rows, so a new design of the same shape fits); the lists are sized by the
 // design's entries and are retaken by nrm_de_plan_design.  The buffers of the dense route (K1 + the fp64 Gram kernel, after a hand-back) are taken when check first needs them.
@@ -12,6 +12,7 @@
 #include "nrm_design.h"
 #include "nrm_de_design.h"
 #include "nrm_plan_core.h"
+#include "nrm_de_sparse_step.h"
 
 namespace {
 
@@ -74,15 +75,16 @@ __global__ __launch_bounds__(256) void k_de_bounds(const T* __restrict__ P, cons
 
 struct nrm_de_plan : NrmPlanCore {
 	static constexpr const char* name = "nrm_de_plan";
-	int64_t ng0 = 0, nt = 0, n = 0, ldt = 0, nc = 0, ncu = 0, ngk = 0;
-	int g_dtype = NRM_F64, t_dtype = NRM_F64, out_dtype = NRM_F64, rank = 0, dimreduce = 0, ci = -1;
+	int64_t ng0 = 0, nt = 0, n = 0, ldt = 0, nc = 0, ngk = 0;
+	int g_dtype = NRM_F64, t_dtype = NRM_F64, out_dtype = NRM_F64, rank = 0, dimreduce = 0;
 	bool adopted = false, want_alpha = false, want_q = false, dense_route = false, dense_ready = false;
-	double dof = 0.0, cval = 0.0, guard_tol = 0.0;
+	double guard_tol = 0.0;
 	const void* dt = nullptr;  // the matrix a step reads: own_dt, or the caller's
-	int64_t nxp0 = 0, nyp = 0, kp = 0, bh_bytes = 0;
+	int64_t kp = 0, bh_bytes = 0;
 	std::unique_ptr<NrmDesignLists> L;
+	NrmDeSparseStep s;  // the sparse step's sizes, buffers and launches; the dense route writes the same ssx, bx, ssy, by, dot and counters
 	// set at create, for all ng0 rows
-	DevBuf own_dt, dc, dci, cmax, mask, c2f, f2c, flags, ssx, bx, ssy, by, dot, common, ct, code, cp, cg, ca, P, G, A, varg, vart, q, bhwork;
+	DevBuf own_dt, dc, dci, cmax, mask, c2f, f2c, cp, cg, ca, P, G, A, varg, vart, q, bhwork;
 	// the dense route
 	DevBuf gd, rx, ry, gwork;
 	int64_t reruns = 0, list_bytes = 0;
@@ -111,7 +113,8 @@ int plan_set_design(nrm_de_plan* pl, const NrmDePlanDesign& in) {
 	pl->bytes += d.list_bytes - pl->list_bytes;
 	pl->list_bytes = d.list_bytes;
 	pl->L = std::move(d.L);
-	pl->ngk = d.ngk;
+	pl->s.L = pl->L.get();
+	pl->s.nx = pl->ngk = d.ngk;
 	pl->g_dtype = (in.form == 0 || in.values) ? in.dtype : NRM_F64;
 	pl->dense_route = false;
 	pl->dense_ready = false;
@@ -119,51 +122,32 @@ int plan_set_design(nrm_de_plan* pl, const NrmDePlanDesign& in) {
 	return NRM_OK;
 }
 
-// design_stats -> products -> sweep -> alpha: nrm_host_de_sparse's launches, on the plan's buffers
+// the record's step, into the full-size arrays or the compact ones
 int plan_enqueue_sparse(nrm_de_plan* pl, hipStream_t st) {
-	NrmDesignLists& L = *pl->L;
-	const int64_t nc = pl->nc, ncu = pl->ncu, n = pl->n, nt = pl->nt, nx = pl->ngk;
-	const double* d_c = pl->dc.as<double>();
-	const double* d_dci = pl->dci.as<double>();
-	int32_t* flags = pl->flags.as<int32_t>();
-	NRM_HIP(hipMemsetAsync(pl->ssx.p, 0, (size_t)pl->nxp0 * 8, st));
-	NRM_HIP(hipMemsetAsync(pl->bx.p, 0, (size_t)pl->ng0 * (nc > 0 ? nc : 1) * 8, st));
-	NRM_TRY(nrm_design_stats(L.row_ptr.as<int64_t>(), L.cells.as<int32_t>(), L.row_vals.as<double>(), ncu ? d_c : nullptr, n, ncu, ncu ? d_dci : nullptr, nx, pl->ssx.as<double>(),
-							 ncu ? pl->bx.as<double>() : nullptr, flags, st));
-	if (pl->want_alpha) NRM_HIP(hipMemsetAsync(pl->by.p, 0, (size_t)nt * nc * 8, st));
-	const bool fused = pl->ct.p != nullptr;
-	if (!fused)
-		NRM_TRY(nrm_single1_stream(pl->dt, pl->t_dtype, pl->ldt, d_c, n, ncu, pl->code.as<int32_t>(), n, nt, pl->common.as<double>(), pl->common.p, nrm_round_up(nt, 8), st));
-	NRM_TRY(nrm_de_sparse(pl->dt, pl->t_dtype, nt, n, pl->ldt, pl->common.as<double>(), ncu, d_dci, L.ell.as<int16_t>(), L.ellv.as<double>(), L.base.as<int64_t>(), L.w.as<int32_t>(),
-						  L.sig.as<int32_t>(), L.ngroups, L.slot2x.as<int32_t>(), pl->bx.as<double>(), nc > 0 ? nc : 1, pl->dot.as<double>(), pl->nyp, 0, pl->ssy.as<double>(),
-						  (pl->want_alpha && ncu) ? pl->by.as<double>() : nullptr, flags, d_c, n, pl->ci, pl->cval, fused ? pl->ct.as<double>() : nullptr, st));
-	NRM_TRY(nrm_assoc_sweep(pl->dot.as<double>(), pl->nyp, pl->ssx.as<double>(), pl->ssy.as<double>(), nx, nt, n, pl->dof, 0, 1, pl->sweep_p(), pl->sweep_g(), nullptr, nullptr,
-							pl->out_dtype, nt, flags, 0, nullptr, nullptr, 0.0, st));
-	if (pl->want_alpha)
-		NRM_TRY(nrm_alpha(pl->sweep_g(), pl->out_dtype, nt, 1, pl->ssx.as<double>(), n, pl->bx.as<double>(), pl->by.as<double>(), nx, nt, nc, pl->sweep_a(), pl->out_dtype, st));
-	return NRM_OK;
+	NRM_TRY(pl->s.enqueue_products(st));
+	return pl->s.enqueue_sweep(st, pl->sweep_p(), pl->sweep_g(), nullptr, nullptr, pl->sweep_a(), 1);
 }
 
 // the same step on K1 and the fp64 Gram kernel (nrm_association_tests_host's second pass): the rows residualised first, no digit planes
 int plan_enqueue_dense(nrm_de_plan* pl, hipStream_t st) {
 	const int64_t nc = pl->nc, n = pl->n, nt = pl->nt, nx = pl->ngk, mp = nrm_round_up(nx, NRM_ROW_TILE);
 	if (pl->want_alpha) {
-		NRM_HIP(hipMemsetAsync(pl->bx.p, 0, (size_t)nx * nc * 8, st));
-		NRM_HIP(hipMemsetAsync(pl->by.p, 0, (size_t)nt * nc * 8, st));
+		NRM_HIP(hipMemsetAsync(pl->s.bx.p, 0, (size_t)nx * nc * 8, st));
+		NRM_HIP(hipMemsetAsync(pl->s.by.p, 0, (size_t)nt * nc * 8, st));
 	}
-	NRM_TRY(nrm_assoc_k1(pl->gd.p, pl->g_dtype, nx, n, n, pl->dc.as<double>(), nc, pl->dci.as<double>(), pl->rank, pl->kp, mp, pl->ssx.as<double>(),
-						 pl->want_alpha ? pl->bx.as<double>() : nullptr, 0, nullptr, nullptr, pl->cmax.as<double>(), nullptr, pl->rx.as<double>(), st));
-	NRM_TRY(nrm_assoc_k1(pl->dt, pl->t_dtype, nt, n, pl->ldt, pl->dc.as<double>(), nc, pl->dci.as<double>(), pl->rank, pl->kp, pl->nyp, pl->ssy.as<double>(),
-						 pl->want_alpha ? pl->by.as<double>() : nullptr, 0, nullptr, nullptr, pl->cmax.as<double>(), nullptr, pl->ry.as<double>(), st));
+	NRM_TRY(nrm_assoc_k1(pl->gd.p, pl->g_dtype, nx, n, n, pl->dc.as<double>(), nc, pl->dci.as<double>(), pl->rank, pl->kp, mp, pl->s.ssx.as<double>(),
+						 pl->want_alpha ? pl->s.bx.as<double>() : nullptr, 0, nullptr, nullptr, pl->cmax.as<double>(), nullptr, pl->rx.as<double>(), st));
+	NRM_TRY(nrm_assoc_k1(pl->dt, pl->t_dtype, nt, n, pl->ldt, pl->dc.as<double>(), nc, pl->dci.as<double>(), pl->rank, pl->kp, pl->s.nyp, pl->s.ssy.as<double>(),
+						 pl->want_alpha ? pl->s.by.as<double>() : nullptr, 0, nullptr, nullptr, pl->cmax.as<double>(), nullptr, pl->ry.as<double>(), st));
 	NrmAssocOperands o;
-	o.rx = pl->rx.as<double>(), o.ry = pl->ry.as<double>(), o.ssx = pl->ssx.as<double>(), o.ssy = pl->ssy.as<double>();
-	o.nx = nx, o.ny = nt, o.n = n, o.mp = mp, o.np_ = pl->nyp, o.kp = pl->kp;
-	o.nslices = 0, o.samexy = 0, o.stat_kind = 1, o.out_dtype = pl->out_dtype, o.dof = pl->dof, o.guard_tol = pl->guard_tol;
-	o.dot = pl->dot.as<double>(), o.gwork = pl->gwork.p, o.flags = pl->flags.as<int32_t>();
+	o.rx = pl->rx.as<double>(), o.ry = pl->ry.as<double>(), o.ssx = pl->s.ssx.as<double>(), o.ssy = pl->s.ssy.as<double>();
+	o.nx = nx, o.ny = nt, o.n = n, o.mp = mp, o.np_ = pl->s.nyp, o.kp = pl->kp;
+	o.nslices = 0, o.samexy = 0, o.stat_kind = 1, o.out_dtype = pl->out_dtype, o.dof = pl->s.dof, o.guard_tol = pl->guard_tol;
+	o.dot = pl->s.dot.as<double>(), o.gwork = pl->gwork.p, o.flags = pl->s.flags.as<int32_t>();
 	o.p = pl->sweep_p(), o.stat = pl->sweep_g();
 	for (int64_t a = 0; a < nx; a += NRM_ASSOC_BAND) NRM_TRY(nrm_assoc_band(o, a, std::min(nx, a + NRM_ASSOC_BAND), st));
 	if (pl->want_alpha)
-		NRM_TRY(nrm_alpha(pl->sweep_g(), pl->out_dtype, nt, 1, pl->ssx.as<double>(), n, pl->bx.as<double>(), pl->by.as<double>(), nx, nt, nc, pl->sweep_a(), pl->out_dtype, st));
+		NRM_TRY(nrm_alpha(pl->sweep_g(), pl->out_dtype, nt, 1, pl->s.ssx.as<double>(), n, pl->s.bx.as<double>(), pl->s.by.as<double>(), nx, nt, nc, pl->sweep_a(), pl->out_dtype, st));
 	return NRM_OK;
 }
 
@@ -177,16 +161,16 @@ int plan_finish(nrm_de_plan* pl, hipStream_t st) {
 						   nt, pl->nc, pl->P.as<T>(), pl->G.as<T>(), pl->want_alpha ? pl->A.as<T>() : (T*)nullptr);
 		NRM_TRY(nrm_check_launch("k_de_inflate"));
 	}
-	hipLaunchKernelGGL(k_de_varg<T>, dim3((unsigned)((ng0 + 255) / 256)), dim3(256), 0, st, pl->ssx.as<double>(), pl->f2c.as<int32_t>(), ng0, (double)pl->n, pl->varg.as<T>());
+	hipLaunchKernelGGL(k_de_varg<T>, dim3((unsigned)((ng0 + 255) / 256)), dim3(256), 0, st, pl->s.ssx.as<double>(), pl->f2c.as<int32_t>(), ng0, (double)pl->n, pl->varg.as<T>());
 	NRM_TRY(nrm_check_launch("k_de_varg"));
-	hipLaunchKernelGGL(k_plan_var<T>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, pl->ssy.as<double>(), nt, (double)pl->n, pl->vart.p);
+	hipLaunchKernelGGL(k_plan_var<T>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, pl->s.ssy.as<double>(), nt, (double)pl->n, pl->vart.p);
 	NRM_TRY(nrm_check_launch("k_plan_var"));
 	const int64_t cnt = ng0 * nt, blocks = std::min<int64_t>((cnt + 1023) / 1024, 2048);
 	hipLaunchKernelGGL(k_de_bounds<T>, dim3((unsigned)blocks), dim3(256), 0, st, pl->P.as<T>(), pl->G.as<T>(), cnt, pl->varg.as<T>(), ng0, pl->vart.as<T>(), nt,
-					   pl->flags.as<int32_t>() + 4);
+					   pl->s.flags.as<int32_t>() + 4);
 	NRM_TRY(nrm_check_launch("k_de_bounds"));
 	if (pl->want_q)
-		NRM_TRY(nrm_bh(pl->P.p, pl->out_dtype, ng0, nt, nt, pl->q.p, nt, pl->bhwork.p, pl->bh_bytes, pl->flags.as<int32_t>() + 6, (void*)st));
+		NRM_TRY(nrm_bh(pl->P.p, pl->out_dtype, ng0, nt, nt, pl->q.p, nt, pl->bhwork.p, pl->bh_bytes, pl->s.flags.as<int32_t>() + 6, (void*)st));
 	return NRM_OK;
 }
 
@@ -201,11 +185,11 @@ int plan_upload(nrm_de_plan* pl, const char* who, const void* h_dt) {
 
 // the dense route's buffers, once, and the compacted design as a matrix: written from the entries of the lists (their CSR form holds every entry of the rows kept)
 int plan_dense_ready(nrm_de_plan* pl, hipStream_t st) {
-	const int64_t mp0 = pl->nxp0;
+	const int64_t mp0 = pl->s.nxp;
 	if (!pl->rx.p) {
 		NRM_TRY(pl->take(pl->gd, (size_t)pl->ng0 * pl->n * 8));  // (room for fp64: a later design of the plan may be one)
 		NRM_TRY(pl->take(pl->rx, (size_t)mp0 * pl->kp * 8));
-		NRM_TRY(pl->take(pl->ry, (size_t)pl->nyp * pl->kp * 8));
+		NRM_TRY(pl->take(pl->ry, (size_t)pl->s.nyp * pl->kp * 8));
 		NRM_TRY(pl->take(pl->gwork, (size_t)nrm_gram_workspace_bytes()));
 	}
 	NrmDesignLists& L = *pl->L;
@@ -215,8 +199,8 @@ int plan_dense_ready(nrm_de_plan* pl, hipStream_t st) {
 }
 
 int plan_counters(nrm_de_plan* pl, hipStream_t st, int32_t (&hf)[8]) {
-	NRM_TRY(nrm_read_flags(pl->flags.p, st, hf));
-	NRM_TRY(nrm_fill_zero(pl->flags.p, 32, (void*)st));
+	NRM_TRY(nrm_read_flags(pl->s.flags.p, st, hf));
+	NRM_TRY(nrm_fill_zero(pl->s.flags.p, 32, (void*)st));
 	NRM_HIP(hipStreamSynchronize(st));
 	NRM_TRY(nrm_assoc_assertions(hf, " tiles"));
 	if (hf[4] > 0) {
@@ -270,11 +254,13 @@ extern "C" int nrm_de_plan_create(nrm_de_plan** plan, int design_form, const voi
 	pl->ng0 = ng0, pl->nt = nt, pl->n = n, pl->ldt = ldt, pl->nc = nc, pl->t_dtype = dt_dtype, pl->out_dtype = out_dtype, pl->rank = rank, pl->dimreduce = dimreduce;
 	pl->adopted = dt_on_device != 0;
 	pl->want_alpha = want_alpha != 0 && nc > 0, pl->want_q = want_q != 0;
-	pl->dof = (double)(n - 1 - rank - dimreduce);
 	pl->guard_tol = nrm_guard_tolerance();
-	pl->ncu = (rank > 0 && nc > 0) ? nc : 0;  // (covariates of rank 0 -- all zero -- leave the rows as they are: association.py:899-903)
-	pl->ci = pl->ncu ? nrm_constant_row(c64.data(), nc, n, &pl->cval) : -1;
-	pl->nxp0 = nrm_round_up(ng0, NRM_ROW_TILE), pl->nyp = nrm_round_up(nt, NRM_ROW_TILE), pl->kp = nrm_round_up(n, NRM_K_TILE);
+	pl->kp = nrm_round_up(n, NRM_K_TILE);
+	NrmDeSparseStep& s = pl->s;
+	s.rows = ng0, s.ny = nt, s.n = n, s.ldy = ldt, s.nc = nc, s.y_dtype = dt_dtype, s.out_dtype = out_dtype, s.want_alpha = pl->want_alpha;
+	s.dof = (double)(n - 1 - rank - dimreduce);
+	s.ncu = (rank > 0 && nc > 0) ? nc : 0;  // (covariates of rank 0 -- all zero -- leave the rows as they are: association.py:899-903)
+	s.ci = s.ncu ? nrm_constant_row(c64.data(), nc, n, &s.cval) : -1;
 	pl->bh_bytes = bh_bytes;
 	NRM_HIP(hipStreamCreateWithFlags(&pl->own, hipStreamNonBlocking));
 	hipStream_t st = pl->own;
@@ -290,33 +276,16 @@ extern "C" int nrm_de_plan_create(nrm_de_plan** plan, int design_form, const voi
 		NRM_TRY(covariate_bounds(c64, nc, n, h_dci, rank, pl->cmax, pl->dci));
 		pl->bytes += nc * 8 + nc * nc * 8;
 	}
+	s.d_y = pl->dt, s.d_c = pl->dc.as<double>(), s.d_dci = pl->dci.as<double>();
+	auto take = [&pl](DevBuf& b, size_t bytes) { return pl->take(b, bytes); };
+	NRM_TRY(s.alloc(take, st));
 	const size_t es = nrm_esize(out_dtype), ob = (size_t)ng0 * nt * es;
-	NRM_TRY(pl->take(pl->mask, (size_t)ng0));
-	NRM_TRY(pl->take(pl->c2f, (size_t)ng0 * 8));
-	NRM_TRY(pl->take(pl->f2c, (size_t)ng0 * 4));
-	NRM_TRY(pl->take(pl->flags, 32));
-	NRM_TRY(pl->take(pl->ssx, (size_t)pl->nxp0 * 8));
-	NRM_TRY(pl->take(pl->bx, (size_t)ng0 * (nc > 0 ? nc : 1) * 8));
-	NRM_TRY(pl->take(pl->ssy, (size_t)pl->nyp * 8));
-	if (pl->want_alpha) NRM_TRY(pl->take(pl->by, (size_t)nt * nc * 8));
-	NRM_TRY(pl->take(pl->dot, (size_t)pl->nxp0 * pl->nyp * 8));
-	NRM_TRY(pl->take(pl->common, (size_t)(pl->ncu + 1) * nt * 8));
-	if (pl->ncu - (pl->ci >= 0 ? 1 : 0) <= nrm_de_sparse_fused_covariates())
-		NRM_TRY(pl->take(pl->ct, (size_t)nrm_de_sparse_ct_doubles(n, pl->ncu, pl->ci) * 8));
-	else {
-		NRM_TRY(pl->take(pl->code, (size_t)n * 4));
-		NRM_TRY(nrm_fill_i32(pl->code.p, NRM_S1_COMMON, n, (void*)st));
-	}
-	NRM_TRY(pl->take(pl->P, ob));
-	NRM_TRY(pl->take(pl->G, ob));
+	NRM_TRY(nrm_take_all(take, {{&pl->mask, ng0}, {&pl->c2f, ng0 * 8}, {&pl->f2c, ng0 * 4}, {&pl->P, ob}, {&pl->G, ob}, {&pl->varg, ng0 * es}, {&pl->vart, nt * es}}));
 	if (pl->want_alpha) NRM_TRY(pl->take(pl->A, ob * nc));
-	NRM_TRY(pl->take(pl->varg, (size_t)ng0 * es));
-	NRM_TRY(pl->take(pl->vart, (size_t)nt * es));
 	if (pl->want_q) {
 		NRM_TRY(pl->take(pl->q, ob));
 		NRM_TRY(pl->take(pl->bhwork, (size_t)bh_bytes));
 	}
-	NRM_TRY(nrm_fill_zero(pl->flags.p, 32, (void*)st));
 	if (pl->adopted || dg_on_device) NRM_HIP(hipDeviceSynchronize());  // (whatever the caller queued to fill its matrices is through before they are read)
 	NRM_TRY(plan_set_design(pl.get(), g));
 	if (!pl->adopted) NRM_TRY(plan_upload(pl.get(), "nrm_de_plan_create", dt));
@@ -399,7 +368,7 @@ extern "C" int nrm_de_plan_stream(nrm_de_plan* plan, void** stream) {
 
 extern "C" int nrm_de_plan_info(nrm_de_plan* plan, int64_t info[8]) {
 	NRM_REQUIRE(plan != nullptr && info != nullptr, "nrm_de_plan_info: null pointer");
-	info[0] = plan->dense_route ? 1 : 0, info[1] = plan->exec ? 1 : 0, info[2] = plan->steps, info[3] = plan->reruns, info[4] = plan->rank, info[5] = (int64_t)plan->dof,
+	info[0] = plan->dense_route ? 1 : 0, info[1] = plan->exec ? 1 : 0, info[2] = plan->steps, info[3] = plan->reruns, info[4] = plan->rank, info[5] = (int64_t)plan->s.dof,
 	info[6] = plan->bytes, info[7] = plan->ngk;
 	return NRM_OK;
 }

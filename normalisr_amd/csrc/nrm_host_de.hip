@@ -1,13 +1,11 @@
 // single=0 de beyond the dense path, inside nrm_association_tests_host (numpy buffers in, numpy buffers out, no torch): the sparse-design form
 // (association.py:224-235 for a design with few entries: a CRISPR screen's gRNA incidence, BASELINE configs[3]) and the streaming form for few design
 // rows (case-control DE, BASELINE configs[2]) -- the same kernels the Python host (normalisr_amd/de_sparse.py, engine.association_de_streaming) drives
-// through the device-pointer entries, sequenced here in C++ with the library's own scratch pool.
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+// through the device-pointer entries, sequenced here in C++ with the library's own scratch pool.  The sparse-design sequence itself is NrmDeSparseStep
+// (nrm_de_sparse_step.h), which the resident de plan runs too.
 #include "nrm_host_entry.h"
 #include "nrm_design.h"
+#include "nrm_de_sparse_step.h"
 
 int NrmDesignLists::build(const void* d_x, int x_dtype, int64_t nx, int64_t n, bool want_ell, double max_density, hipStream_t st) {
 	nslots = nrm_round_up(nx, 64);
@@ -46,22 +44,13 @@ int NrmDesignLists::build(const void* d_x, int x_dtype, int64_t nx, int64_t n, b
 						   ell.as<int16_t>(), ellv.as<double>(), cells.as<int32_t>(), row_vals.as<double>(), binary ? 1 : 0, st);
 }
 
+// (a temporary workspace per call; the scratch returns to the pool with this scope, hence the synchronise)
 int sparse_products(NrmDesignLists& L, const void* d_y, int y_dtype, int64_t ny, int64_t n, const double* d_c, int64_t ncu, int ci, double cval, const double* d_dci,
 					const double* d_bx, int64_t ldb, double* d_dot, int64_t ldd, int by_gene, double* d_ssy, double* d_coefy, int32_t* d_flags, hipStream_t st) {
-	DevBuf common, ct, code;
-	NRM_TRY(common.alloc((size_t)(ncu + 1) * ny * 8));
-	const bool fused = ncu - (ci >= 0 ? 1 : 0) <= nrm_de_sparse_fused_covariates();
-	if (fused) {
-		NRM_TRY(ct.alloc((size_t)nrm_de_sparse_ct_doubles(n, ncu, ci) * 8));
-	} else {
-		NRM_TRY(code.alloc((size_t)n * 4));
-		NRM_TRY(nrm_fill_i32(code.p, NRM_S1_COMMON, n, st));
-		NRM_TRY(nrm_single1_stream(d_y, y_dtype, n, d_c, n, ncu, code.as<int32_t>(), n, ny, common.as<double>(), common.p, nrm_round_up(ny, 8), st));
-	}
-	NRM_TRY(nrm_de_sparse(d_y, y_dtype, ny, n, n, common.as<double>(), ncu, d_dci, L.ell.as<int16_t>(), L.ellv.as<double>(), L.base.as<int64_t>(), L.w.as<int32_t>(),
-						  L.sig.as<int32_t>(), L.ngroups, L.slot2x.as<int32_t>(), d_bx, ldb, d_dot, ldd, by_gene, d_ssy, d_coefy, d_flags, d_c, n, ci, cval,
-						  fused ? ct.as<double>() : nullptr, st));
-	NRM_HIP(hipStreamSynchronize(st));  // (the scratch returns to the pool with this scope)
+	NrmSparseProducts work;
+	NRM_TRY(work.alloc(ny, n, ncu, ci, nrm_take_plain, st));
+	NRM_TRY(work.enqueue(L, d_y, y_dtype, ny, n, n, d_c, ncu, ci, cval, d_dci, d_bx, ldb, d_dot, ldd, by_gene, d_ssy, d_coefy, d_flags, st));
+	NRM_HIP(hipStreamSynchronize(st));
 	return NRM_OK;
 }
 
@@ -75,23 +64,15 @@ int nrm_host_de_sparse(const void* d_x, int x_dtype, int64_t nx, const void* d_y
 	NRM_TRY(L.build(d_x, x_dtype, nx, n, true, 1.0 / 16, st));
 	if (!L.ok) return NRM_OK;
 	*taken = 1;
-	const int64_t ncu = (rank > 0 && nc > 0) ? nc : 0;  // (covariates of rank 0 -- all zero -- leave the rows as they are: association.py:899-903)
-	double cval = 0.0;
-	const int ci = ncu ? nrm_constant_row(h_c64, nc, n, &cval) : -1;
-	const int64_t nxp = nrm_round_up(nx, NRM_ROW_TILE), nyp = nrm_round_up(ny, NRM_ROW_TILE);
-	DevBuf flags, ssx, bx, ssy, by, dot, oalpha;
-	NrmAssocOut out;
-	NRM_TRY(flags.alloc_zero(16, st));
-	NRM_TRY(ssx.alloc_zero((size_t)nxp * 8, st));
-	NRM_TRY(bx.alloc_zero((size_t)nx * (nc > 0 ? nc : 1) * 8, st));
-	NRM_TRY(nrm_design_stats(L.row_ptr.as<int64_t>(), L.cells.as<int32_t>(), L.row_vals.as<double>(), ncu ? d_c : nullptr, n, ncu, ncu ? d_dci : nullptr, nx, ssx.as<double>(),
-							 ncu ? bx.as<double>() : nullptr, flags.as<int32_t>(), st));
-	NRM_TRY(ssy.alloc((size_t)nyp * 8));
-	const bool want_alpha = h_alpha != nullptr && nc > 0;
-	if (want_alpha) NRM_TRY(by.alloc_zero((size_t)ny * nc * 8, st));
-	NRM_TRY(dot.alloc((size_t)nxp * nyp * 8));
-	NRM_TRY(sparse_products(L, d_y, y_dtype, ny, n, d_c, ncu, ci, cval, d_dci, bx.as<double>(), nc > 0 ? nc : 1, dot.as<double>(), nyp, 0, ssy.as<double>(),
-							(want_alpha && ncu) ? by.as<double>() : nullptr, flags.as<int32_t>(), st));
+	// the step record (nrm_de_sparse_step.h): sizes, buffers and launches, shared with the resident plan
+	NrmDeSparseStep s;
+	s.rows = s.nx = nx, s.ny = ny, s.n = s.ldy = n, s.nc = nc, s.y_dtype = y_dtype, s.out_dtype = out_dtype, s.dof = dof;
+	s.ncu = (rank > 0 && nc > 0) ? nc : 0;  // (covariates of rank 0 -- all zero -- leave the rows as they are: association.py:899-903)
+	s.ci = s.ncu ? nrm_constant_row(h_c64, nc, n, &s.cval) : -1;
+	s.want_alpha = h_alpha != nullptr && nc > 0;
+	s.L = &L, s.d_y = d_y, s.d_c = d_c, s.d_dci = d_dci;
+	NRM_TRY(s.alloc(nrm_take_plain, st));
+	NRM_TRY(s.enqueue_products(st));
 	const size_t ob = (size_t)nx * ny * nrm_esize(out_dtype);
 	// the caller's result arrays are page-locked in place by a helper thread while the kernels run
 	NrmHostPin pin_p, pin_s, pin_r, pin_t;
@@ -102,15 +83,13 @@ int nrm_host_de_sparse(const void* d_x, int x_dtype, int64_t nx, const void* d_y
 		pin_t.try_pin(h_t, (int64_t)ob);
 	});
 	NrmJoiner join{pinner};
+	NrmAssocOut out;
+	DevBuf oalpha;
 	NRM_TRY(out.alloc(ob, h_r != nullptr, h_t != nullptr));
-	NRM_TRY(nrm_assoc_sweep(dot.as<double>(), nyp, ssx.as<double>(), ssy.as<double>(), nx, ny, n, dof, 0, stat_kind, out.p.p, out.stat.p, out.r.p, out.t.p, out_dtype, ny,
-							flags.as<int32_t>(), 0, nullptr, nullptr, 0.0, st));
-	if (want_alpha) {
-		NRM_TRY(oalpha.alloc(ob * nc));
-		NRM_TRY(nrm_alpha(out.stat.p, out_dtype, ny, stat_kind, ssx.as<double>(), n, bx.as<double>(), by.as<double>(), nx, ny, nc, oalpha.p, out_dtype, st));
-	}
+	if (s.want_alpha) NRM_TRY(oalpha.alloc(ob * nc));
+	NRM_TRY(s.enqueue_sweep(st, out.p.p, out.stat.p, out.r.p, out.t.p, oalpha.p, stat_kind));
 	int32_t hf[4];
-	NRM_TRY(nrm_read_flags(flags.p, st, hf));
+	NRM_TRY(nrm_read_flags(s.flags.p, st, hf));
 	NRM_TRY(nrm_assoc_assertions(hf, " tiles"));
 	if (hf[2] > 0) {  // rows all but inside the span of the covariates: the caller redoes the call on K1 and the fp64 Gram kernel
 		*handed_back = hf[2];
@@ -118,9 +97,9 @@ int nrm_host_de_sparse(const void* d_x, int x_dtype, int64_t nx, const void* d_y
 	}
 	pinner.join();
 	NRM_TRY(out.copy_to(h_p, h_stat, h_r, h_t, ob));
-	if (want_alpha) NRM_HIP(hipMemcpy(h_alpha, oalpha.p, ob * nc, hipMemcpyDeviceToHost));
-	NRM_TRY(emit_var(ssy.as<double>(), ny, n, h_vary, out_dtype));
-	if (h_varx) NRM_TRY(emit_var(ssx.as<double>(), nx, n, h_varx, out_dtype));
+	if (s.want_alpha) NRM_HIP(hipMemcpy(h_alpha, oalpha.p, ob * nc, hipMemcpyDeviceToHost));
+	NRM_TRY(emit_var(s.ssy.as<double>(), ny, n, h_vary, out_dtype));
+	if (h_varx) NRM_TRY(emit_var(s.ssx.as<double>(), nx, n, h_varx, out_dtype));
 	return NRM_OK;
 }
 

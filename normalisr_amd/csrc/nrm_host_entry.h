@@ -62,6 +62,13 @@ struct DevBuf {
 		return reinterpret_cast<T*>(p);
 	}
 };
+// the `take` of a step record (nrm_single1_step.h, nrm_de_sparse_step.h) for a caller that keeps no count of its pool bytes; a table of buffers through a `take`
+static inline int nrm_take_plain(DevBuf& b, size_t bytes) { return b.alloc(bytes); }
+template <typename Take>
+int nrm_take_all(Take take, std::initializer_list<std::pair<DevBuf*, int64_t>> table) {
+	for (const auto& e : table) NRM_TRY(take(*e.first, (size_t)e.second));
+	return NRM_OK;
+}
 
 // Page-lock of a caller-owned result array for the duration of one call (a pageable device-to-host copy runs at a tenth of the PCIe rate); a
 // range that cannot be locked (already registered by the caller, locked-memory limit) is simply copied to at the pageable rate.
@@ -124,14 +131,6 @@ template <int N>
 static inline int nrm_read_flags(const void* d_flags, hipStream_t st, int32_t (&hf)[N]) {
 	NRM_HIP(hipMemcpyAsync(hf, d_flags, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 	NRM_HIP(hipStreamSynchronize(st));
-	return NRM_OK;
-}
-// words 0 and 1 as the reference's error; `unit`: what the kernel counted (" tiles" for the tiled sweeps, "" for plain results)
-static inline int nrm_assoc_assertions(const int32_t* hf, const char* unit) {
-	if (hf[0] || hf[1]) {
-		nrm_set_error("association results failed the reference's assertions (association.py:248,252): %d%s non-finite, %d%s with R^2 > 1+1e-8", hf[0], unit, hf[1], unit);
-		return NRM_E_NUMERIC;
-	}
 	return NRM_OK;
 }
 

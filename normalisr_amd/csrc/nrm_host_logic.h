@@ -39,6 +39,14 @@ static inline int nrm_assoc_check_args(const void* dx, int64_t nx, int64_t ny, c
 	NRM_REQUIRE(n > (int64_t)rank + dimreduce + 1, "Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.");
 	return NRM_OK;
 }
+// words 0 and 1 of an entry's result counters as the reference's error; `unit`: what the kernel counted (" tiles" for the tiled sweeps, "" for plain results)
+static inline int nrm_assoc_assertions(const int32_t* hf, const char* unit) {
+	if (hf[0] || hf[1]) {
+		nrm_set_error("association results failed the reference's assertions (association.py:248,252): %d%s non-finite, %d%s with R^2 > 1+1e-8", hf[0], unit, hf[1], unit);
+		return NRM_E_NUMERIC;
+	}
+	return NRM_OK;
+}
 
 // ---- K1 routing (csrc/nrm_residualize.hip, launch_residualize) -------------------------------------------------------------------------------------------------
 // vec: the 16-byte row loads of k_residualize_v4 / _v8 apply (aligned pointers and pitches; otherwise the scalar k_residualize runs).

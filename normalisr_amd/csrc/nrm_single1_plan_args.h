@@ -19,3 +19,21 @@ static inline int nrm_single1_plan_create_args(const NrmDePlanDesign& g, int64_t
 	nrm_covariates_to_f64(h_dc, c_dtype, (size_t)(nc * n), c64);
 	return NRM_OK;
 }
+
+// single=1's counters ([0], [1] nrm_single1_cells; [2], [3], [4] nrm_single1_group_info) as what the reference asserts or raises, in this order: the selection
+// (association.py:917-918), the SVD's finiteness check, the cell count, the results (:248,252).  The whole-problem entry and the plan's check both say it through here.
+static inline int nrm_single1_status(const int32_t hf[8]) {
+	if (hf[2]) {
+		nrm_set_error("%d groupings take a single value on the cells selected for them (association.py:917-918)", hf[2]);
+		return NRM_E_NUMERIC;
+	}
+	if (hf[4]) {
+		nrm_set_error("array must not contain infs or NaNs");
+		return NRM_E_ARG;
+	}
+	if (hf[3]) {
+		nrm_set_error("Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.");
+		return NRM_E_DEVICE;
+	}
+	return nrm_assoc_assertions(hf, "");
+}

@@ -35,6 +35,19 @@ def screen(seed, dtype, nc, intercept=True, valued=False, full_rows=False, nx=70
 	return dg, dt, dc
 
 
+def small_screen(nc, intercept, dtype='float32'):
+	"""5 design rows x 19 genes x 130 cells: six entries in each design row but row 3, which is empty (de drops it).  The 24 entries of the 4 x 130 rows kept are fewer
+	than one in sixteen, the density up to which the whole-problem entry takes the sparse-design kernels -- once it gets there: with so few rows and covariates
+	(nx + nc <= 32) it takes the streaming kernel first unless NRM_DE_PATH=general, and the size rule wants NRM_DE_SPARSE=force."""
+	rng = np.random.default_rng([61, nc])
+	dg = np.zeros((5, 130))
+	for i in (0, 1, 2, 4):
+		dg[i, rng.choice(130, 6, replace=False)] = 1.0
+	dt = (rng.normal(size=(19, 130)) + 0.5 * dg[0]).astype(dtype)
+	dc = np.vstack([rng.normal(size=(nc - 1, 130)), np.ones((1, 130))]) if intercept else rng.normal(size=(nc, 130))
+	return dg, dt, dc
+
+
 def handback_inputs():
 	"""The design of tests/test_gpu_round5.py:199-206: row 5 all but equal to a batch covariate, 40 x 70 x 6000."""
 	rng = np.random.default_rng(77)
@@ -97,6 +110,8 @@ def _design(form, dg, lib, _lib, cplan):
 
 
 def _inputs(c, arr):
+	if 'small' in c:
+		return small_screen(**c['small'])
 	if 'screen' in c:
 		s = dict(c['screen'])
 		s['dtype'] = np.dtype(s['dtype'])

@@ -39,6 +39,24 @@ def screen(seed, dtype, nc):
 	return dg, dt.astype(dtype), dc
 
 
+ENTRY_NCS = [0, 3, 9]  # none; a lane per grouping; a wave per grouping
+ENTRY_CONST_ROW = 4
+
+
+def entry_screen(dtype, nc):
+	"""The smallest screen on which the whole-problem entry and the plan can differ: 7 design rows over 203 cells, cells 0 .. 159 in one row each and cells 160 .. 202 in
+	none; row 4 emptied, so that de drops it, the plan compacts and re-inflates, and its cells are shared ones too; 37 genes; nc covariates, the intercept last."""
+	rng = np.random.default_rng([11, nc, 203])
+	dg = np.zeros((7, 203))
+	dg[rng.integers(0, 7, 160), np.arange(160)] = 1.0
+	dg[ENTRY_CONST_ROW] = 0.0
+	assert dg.sum(axis=0).max() == 1 and not dg[:, 160:].any() and (np.delete(dg, ENTRY_CONST_ROW, axis=0).sum(axis=1) > 3).all()
+	dt = rng.normal(size=(37, 203))
+	dt[:5] += 0.5 * dg[0]
+	dc = np.vstack([rng.normal(size=(nc - 1, 203)), np.ones((1, 203))]) if nc else np.zeros((0, 203))
+	return dg, dt.astype(dtype), dc
+
+
 def kept_rows():
 	return np.array([i for i in range(NG0) if i not in (ZERO_ROW, ONES_ROW)])
 
@@ -81,6 +99,20 @@ def scenario_cases(job, arr, out, lib, _lib, cplan):
 					out[name + '.q'] = plan.qvalues()
 				infos[name] = plan.info()
 			dpc._free(lib, _lib, held)
+	return infos
+
+
+def scenario_entry(job, arr, out, lib, _lib, cplan):
+	"""de(..., single=1) of the package -- with no torch in this process that is the whole-problem entry nrm_association_tests_single1_host on the rows de keeps -- and
+	one step of a plan on the same arrays."""
+	import normalisr_amd.normalisr as norm
+	infos = {}
+	for c in job['cases']:
+		dg, dt, dc = entry_screen(np.dtype(c['dtype']), c['nc'])
+		dpc._store(out, c['name'] + '.entry', norm.de(dg, dt, dc, single=1, lowmem=False))
+		with cplan.Single1Plan(dg, dt, dc, lowmem=False) as plan:
+			dpc._store(out, c['name'] + '.plan', plan.step().results())
+			infos[c['name']] = plan.info()
 	return infos
 
 

@@ -236,6 +236,44 @@ def test_de_plan_c_entry_graph_switch_off(tmp_path):
 	assert out0['g.dense.q'].dtype == out['g.dense.q'].dtype and np.array_equal(out0['g.dense.q'], out['g.dense.q'])
 
 
+@pytest.mark.parametrize('dtype', ['float32', 'float64'])
+def test_de_plan_c_entry_graph_switch_off_same_bytes_as_the_host_entry(parent_route, monkeypatch, tmp_path, dtype):
+	"""The whole-problem entry and the plan run one step record (csrc/nrm_de_sparse_step.h): NRM_DEBUG graph=0 in the child, 5 design rows (one empty) x 19 genes x
+	130 cells, three eager steps against norm.de on the same arrays, bit for bit.  One covariate, the intercept: the fused table with a constant covariate.  Six
+	without an intercept: the fused table without one (six is within nrm_de_sparse_fused_covariates() = 8).  Nine without: the rows' sums from the stream kernel of
+	single=1.  fp32 is the issue's case; fp64 is there because rounding to fp32 can hide another algorithm's last bits.
+
+	The entry's route.  With 4 rows kept and at most 9 covariates nrm_association_tests_host would take the streaming kernel (nx + nc <= 32) and never reach
+	nrm_host_de_sparse: NRM_DE_PATH=general switches that off, NRM_DE_SPARSE=force overrides the size rule, the density is under one in sixteen and nothing is handed
+	back (nrm_last_guard).  That it then ran the sparse-design kernels shows in fp64: under NRM_DE_SPARSE=0, K1 and the fp64 Gram kernel, gamma has other bits."""
+	import ctypes
+	from normalisr_amd import _lib
+	lib = _lib.load()
+	assert 6 <= int(lib.nrm_de_sparse_fused_covariates()) < 9 <= int(lib.nrm_de_sparse_max_covariates())
+	monkeypatch.setenv('NRM_DE_PATH', 'general')
+	cases = [dict(name='c{}{}'.format(nc, 'i' if intercept else 'n'), lowmem=False, steps=3, forms=['dense'], small=dict(nc=nc, intercept=intercept, dtype=dtype))
+			 for nc, intercept in ((1, True), (6, False), (9, False))]
+	debug = ','.join([p for p in os.environ.get('NRM_DEBUG', '').split(',') if p.strip()] + ['graph=0'])
+	out, info = run_child(tmp_path, 'cases', {}, dict(cases=cases), env={'NRM_DEBUG': debug})
+	for c in cases:
+		name = c['name'] + '.dense'
+		print(name, info[name])
+		assert info[name]['captured'] == 0 and info[name]['steps'] == 3 and info[name]['route'] == 0 and info[name]['reruns'] == 0 and info[name]['rows_kept'] == 4
+		dg, dt, dc = child.small_screen(**c['small'])
+		assert 16 * int((dg != 0).sum()) <= 4 * dg.shape[1]
+		want = parent_route.de(dg, dt, dc, lowmem=False)
+		hits = ctypes.c_int64(-1)
+		_lib.check(lib.nrm_last_guard(ctypes.byref(hits), None))
+		assert hits.value == 0, 'the entry handed rows back to the dense kernels'
+		assert want[0].dtype == np.dtype(dtype) and (want[0][3] == 1).all() and (want[0] < 1).any() and want[2].shape == (5, 19, c['small']['nc'])
+		same(got(out, name), want, name)
+		if dtype == 'float64':
+			monkeypatch.setenv('NRM_DE_SPARSE', '0')
+			dense = parent_route.de(dg, dt, dc, lowmem=False)
+			monkeypatch.setenv('NRM_DE_SPARSE', 'force')
+			assert np.allclose(dense[1], want[1], rtol=1e-6, atol=1e-12) and not np.array_equal(dense[1], want[1]), name
+
+
 def test_de_plan_c_entry_bounds(tmp_path):
 	"""A NaN planted in one expression value: check() raises AssertionError (the reference's assertions, counted on the device); update and a step later the plan
 	is clean and equals a fresh one."""

@@ -139,6 +139,25 @@ def test_single1_plan_c_entry_same_bytes_as_the_torch_plan(tmp_path, dtype):
 			held((res[0][KEPT], res[1][KEPT], res[2][KEPT], res[3][KEPT], res[4][KEPT]), (ref[0], ref[1], alpha, ref[3], ref[4]), np.dtype(dtype), nc)
 
 
+@pytest.mark.parametrize('dtype', ['float32', 'float64'])
+def test_single1_plan_c_entry_same_bytes_as_the_host_entry(tmp_path, dtype):
+	"""The whole-problem entry and the plan run one step record (csrc/nrm_single1_step.h): norm.de(..., single=1, lowmem=False) in a process without torch
+	(NRM_HOST_ENTRY=1: nrm_association_tests_single1_host) and cplan.Single1Plan on the same arrays give P, gamma, alpha, varg and vart equal bit for bit.
+	7 design rows over 203 cells, each cell in at most one row and 43 in none, row 4 constant (the plan compacts and re-inflates); 37 genes; 0, 3 (a lane per
+	grouping) and 9 (a wave per grouping) covariates."""
+	cases = [dict(name='c{}'.format(nc), nc=nc, dtype=dtype) for nc in child.ENTRY_NCS]
+	out, info = run_child(tmp_path, 'entry', {}, dict(cases=cases), env={'NRM_HOST_ENTRY': '1'})
+	for c in cases:
+		v = info[c['name']]
+		print(c['name'], v)
+		assert v['rows_kept'] == 6 and v['cells_kept'] == int(child.entry_screen(np.dtype(dtype), c['nc'])[0].sum()) and v['covariates'] == c['nc'] and v['steps'] == 1
+		entry, plan = got(out, c['name'] + '.entry'), got(out, c['name'] + '.plan')
+		assert all(x is not None and x.dtype == np.dtype(dtype) for x in entry) and entry[2].shape == (7, 37, c['nc'])
+		assert np.isfinite(entry[0]).all() and (entry[0][np.arange(7) != child.ENTRY_CONST_ROW] < 1).any()
+		untested_rows_exact(entry, [child.ENTRY_CONST_ROW])
+		same(plan, entry, c['name'])
+
+
 @pytest.mark.parametrize('design_form', ['dense', 'coo'])
 def test_single1_plan_c_entry_replays(tmp_path, design_form):
 	"""Three steps, update(dt2) and two more, set_design(dg2) -- another number of cells with exactly one grouping, so that the stream kernel's transposed output

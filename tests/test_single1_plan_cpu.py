@@ -151,18 +151,29 @@ def test_single1_plan_constructor_validation():
 		cplan.Single1Plan(dg33, dt33, dc33)
 
 
-def test_single1_plan_argument_checks_under_address_and_ub_sanitizers(tmp_path):
-	"""csrc/nrm_single1_plan_args.h -- every check create makes before a device call -- built by g++ with -fsanitize=address,undefined beside a program with its own
-	main (tests/host/single1_plan_args_sanitize.cpp) and run directly: nothing loaded into python runs under a sanitizer."""
+def _sanitized_program(tmp_path, name, says):
+	"""tests/host/NAME.cpp -- a program with its own main over csrc/nrm_single1_plan_args.h -- built by g++ with -fsanitize=address,undefined and run directly: nothing
+	loaded into python runs under a sanitizer."""
 	gxx = shutil.which('g++')
 	assert gxx is not None, 'g++ is needed to build the host arithmetic'
-	exe = str(tmp_path / 'single1_plan_args_sanitize')
+	exe = str(tmp_path / name)
 	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-pthread', '-w',
-						'-x', 'c++', os.path.join(ROOT, 'normalisr_amd', 'csrc', 'nrm_small_pinv.hip'), os.path.join(ROOT, 'tests', 'host', 'single1_plan_args_sanitize.cpp'), '-o', exe],
+						'-x', 'c++', os.path.join(ROOT, 'normalisr_amd', 'csrc', 'nrm_small_pinv.hip'), os.path.join(ROOT, 'tests', 'host', name + '.cpp'), '-o', exe],
 					   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
 	assert r.returncode == 0, r.stdout[-3000:]
 	r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-	assert r.returncode == 0 and 'single1 plan args ok' in r.stdout, r.stdout[-3000:]
+	assert r.returncode == 0 and says in r.stdout, r.stdout[-3000:]
+
+
+def test_single1_plan_argument_checks_under_address_and_ub_sanitizers(tmp_path):
+	"""csrc/nrm_single1_plan_args.h -- every check create makes before a device call -- beside tests/host/single1_plan_args_sanitize.cpp."""
+	_sanitized_program(tmp_path, 'single1_plan_args_sanitize', 'single1 plan args ok')
+
+
+def test_single1_status_under_address_and_ub_sanitizers(tmp_path):
+	"""nrm_single1_status, the one reading of single=1's counters for the whole-problem entry and the plan (tests/host/single1_status_sanitize.cpp): all 32
+	combinations of counters [0..4] give the status and message of [2] over [4] over [3] over [0] / [1], and NRM_OK for none."""
+	_sanitized_program(tmp_path, 'single1_status_sanitize', 'single1 status ok')
 
 
 def test_single1_plan_gpu_screens_are_well_posed():
@@ -179,5 +190,11 @@ def test_single1_plan_gpu_screens_are_well_posed():
 		assert dg.max() == 1 and dg.min() == 0 and 0 < child.exclusive_cells(dg) < child.N
 		p, gam, _, vx, vy = oracle.association_tests(dg[keep], dt, dc, single=1, return_dot=False)
 		assert p.shape == (child.NX, child.NY) and np.isfinite(p).all() and np.isfinite(gam).all() and (vx > 0).all() and (vy > 0).all(), (seed, nc)
+	for nc in child.ENTRY_NCS:  # the screen of test_single1_plan_c_entry_same_bytes_as_the_host_entry
+		dg, dt, dc = child.entry_screen(np.float64, nc)
+		keep = cplan.varying_rows(dg)
+		assert (np.nonzero(~keep)[0] == [child.ENTRY_CONST_ROW]).all()
+		p, gam, _, vx, vy = oracle.association_tests(dg[keep], dt, dc, single=1, return_dot=False)
+		assert p.shape == (6, 37) and np.isfinite(p).all() and np.isfinite(gam).all() and (vx > 0).all() and (vy > 0).all(), nc
 	dg, dg2 = child.screen(child.SEEDS['replays'], np.float64, 3)[0], child.screen(child.SEEDS['replays'] + 1, np.float64, 3)[0]
 	assert child.exclusive_cells(dg) != child.exclusive_cells(dg2)  # (set_design changes the size of the stream kernel's transposed output)
