@@ -1079,6 +1079,66 @@ int nrm_single1_plan_info(nrm_single1_plan* plan, int64_t info[8]);
 int nrm_single1_plan_time(nrm_single1_plan* plan, int64_t steps, double* ms_per_step);
 int nrm_single1_plan_destroy(nrm_single1_plan* plan);
 
+/*
+ * Resident single=4 plan (csrc/nrm_single4_plan.hip): de(dg, dt, dc, single=4), a high-MOI screen in which every grouping is tested with all the others as
+ * covariates -- reference de.py:4-132 over association.py:421-576, 926-980, in closed form -- for a caller that repeats a screen of one shape.  Names, argument
+ * order and semantics are those of nrm_de_plan_* wherever the two coincide.  Nothing of the design side depends on the expression matrix, and the plan reads its
+ * design only when it is set: M~ = X~ X~^T, its inverse N~, dxx, varx and the rank decision are taken ONCE PER DESIGN, and a step keeps what depends on dt.  The
+ * domain is that of nrm_association_tests_single4_host / _pinv_host: designs for which the closed form has a certificate; scalar dimreduce; no mpc / method / qr.
+ *   nrm_single4_plan_create: the design (ng0, n_cells) by design_form, dt, ldt, dt_on_device, h_dc, c_dtype, nc, h_dci, rank (h_dci == NULL: nrm_covariates_pinv at
+ *       `tol`, nc <= 32), dimreduce, out_dtype, want_alpha (lowmem=False) and want_q exactly as nrm_de_plan_create takes them; tol, 0 < tol < 1: the threshold of the
+ *       rank certificates (association.py:77; the reference's default is 1e-8).  Every argument check -- dtypes, sizes ("Incorrect dx/dy/dc size.", "Unmatching
+ *       dx/dy/dc dimensions."), dimreduce, tol, rows and cells <= 2^31 - 1, row pitches, rank: NRM_E_ARG; more than nrm_de_sparse_max_covariates() covariates, or
+ *       covariates of rank 0: NRM_E_UNSUPPORTED -- is made before any device call.  The design is then set on the device, in this order: de's row filter (de.py:93),
+ *       the row map, the rows kept compacted and their lists with the ELL form (as nrm_de_plan_create); the rows kept written out dense once from the lists
+ *       (nrm_design_csr_dense; returned to the pool afterwards); the design side, eagerly and with its read-backs: nrm_design_stats; M~ by nrm_de_sparse with the
+ *       dense design rows in the place of the expression rows; N~ by Newton-Schulz iteration on nrm_gram_f64 (nrm_spd_*; the host's Cholesky factorisation when it
+ *       does not converge); dxx = 1 / (n N~_ii), varx, ||M~||_1, ||N~||_1; the certificate (full-rank covariates: A A^T passes the reference's rank test;
+ *       rank-deficient ones: every grouping has the rank nx - 1 + rank).  A design row all but inside the covariates' span sends the design side, and the plan, to K1
+ *       + nrm_gram_f64 (route 1) at once.  Refused: n_cells <= rows kept + rank + dimreduce: "Insufficient number of cells ...", NRM_E_DEVICE; no certificate, or
+ *       M~ not positive definite: NRM_E_UNSUPPORTED in the words of the host entry (the caller takes norm.de(..., single=4), which looks at the spectrum of A A^T and
+ *       follows the per-grouping algorithm if need be); a malformed CSR matrix or no row left to test: NRM_E_ARG.
+ *   nrm_single4_plan_design: another design of the same shape (any form) in place of the present one: all of the above again; drops the captured graph and a
+ *       remembered hand-back.  After a refusal the plan has no design.
+ *   nrm_single4_plan_upload: new values (same shape and dtype) into the plan's own copy of dt; NRM_E_ARG for an adopted matrix.
+ *   nrm_single4_plan_step: G = Y~ X~^T, |y~|^2 and b_y on request (route 0: nrm_de_sparse, behind nrm_single1_stream beyond nrm_de_sparse_fused_covariates(); route
+ *       1: nrm_residualize + nrm_gram_f64) -> B^T = G N~ (nrm_gram_f64) -> nrm_single4_sweep (gamma): the launches of the whole-problem entry; then alpha on request
+ *       -- alpha_y = b_y - B_y b_x as an (nt, nc) fp64 matrix summed in a fixed order, then written to all ng0 rows (zeros for rows not tested) --, one pass that
+ *       puts the compact P, gamma and vart rows back among all ng0 rows (rows not tested: p = 1, gamma = varg = vart = 0; when every row is tested the sweep writes
+ *       the full-size arrays itself), rounds varx once to out_dtype and counts the entries outside the ranges de.py:124-131 asserts; nrm_bh over all ng0 * nt
+ *       P-values on request.  Nothing is read back, allocated or waited for.  stream == NULL: the plan's own.  The first step on a route runs eagerly, the second
+ *       is captured (thread-local) and instantiated, later ones are one hipGraphLaunch; a failed capture leaves the plan eager with the reason in nrm_last_error
+ *       (NRM_OK).  NRM_DEBUG="graph=0": always eager.
+ *   nrm_single4_plan_check: synchronises the device, reads and clears the counters.  *handed_back: expression rows with |y~|^2 < 1e-4 |y|^2 since the last check
+ *       (else 0): the design side and the step were then redone, now, on route 1 -- whose residual rows are taken from the pool at this moment, each matrix in one
+ *       piece; a refusal of the pool is reported as such --, and that is the plan's route until the design is replaced.  Then NRM_E_NUMERIC for the reference's
+ *       assertions on what stands (association.py:557; de.py:124-131).
+ *   nrm_single4_plan_results: check, then de's outputs of the last step into HOST arrays of out_dtype, any of them NULL: P (ng0, nt), gamma (ng0, nt), alpha (ng0, nt,
+ *       nc), varg (ng0), vart (ng0, nt: per grouping), q (ng0, nt).
+ *   nrm_single4_plan_device_results: the same arrays as full-size DEVICE pointers (row pitch *ld = nt) and the byte mask of tested rows (ng0); NULL for what the plan
+ *       was created without.  Valid until destroy, written by every step.
+ *   nrm_single4_plan_info: info[0] route (0 sparse-design kernels, 1 K1 + fp64 Gram), [1] captured, [2] steps, [3] reruns, [4] covariate rank, [5] dof = n_cells -
+ *       rows kept - rank - dimreduce, [6] bytes resident, [7] rows kept.
+ *   nrm_single4_plan_stream, nrm_single4_plan_time, nrm_single4_plan_destroy (accepts NULL): as nrm_de_plan_*.
+ * Threads: create, design, check, results and destroy take the lock of the whole-problem entries; step, upload and time do not.  One thread at a time per plan.
+ */
+typedef struct nrm_single4_plan nrm_single4_plan;
+int nrm_single4_plan_create(nrm_single4_plan** plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
+							int dg_on_device, int64_t ng0, const void* dt, int dt_dtype, int64_t nt, int64_t n_cells, int64_t ldt, int dt_on_device, const void* h_dc,
+							int c_dtype, int64_t nc, const double* h_dci, int rank, int dimreduce, int out_dtype, int want_alpha, int want_q, double tol);
+int nrm_single4_plan_design(nrm_single4_plan* plan, int design_form, const void* dg, int dg_dtype, int64_t ldg, const int64_t* indptr, const int32_t* indices, int64_t nnz,
+							int dg_on_device);
+int nrm_single4_plan_upload(nrm_single4_plan* plan, const void* h_dt);
+int nrm_single4_plan_step(nrm_single4_plan* plan, void* stream);
+int nrm_single4_plan_check(nrm_single4_plan* plan, int64_t* handed_back);
+int nrm_single4_plan_results(nrm_single4_plan* plan, void* h_p, void* h_gamma, void* h_alpha, void* h_varg, void* h_vart, void* h_q);
+int nrm_single4_plan_device_results(nrm_single4_plan* plan, void** d_p, void** d_gamma, void** d_alpha, void** d_varg, void** d_q, void** d_vart, void** d_mask,
+									int64_t* ld);
+int nrm_single4_plan_stream(nrm_single4_plan* plan, void** stream);
+int nrm_single4_plan_info(nrm_single4_plan* plan, int64_t info[8]);
+int nrm_single4_plan_time(nrm_single4_plan* plan, int64_t steps, double* ms_per_step);
+int nrm_single4_plan_destroy(nrm_single4_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ never imports torch.  The matrix stays in HBM, a step is K1 -> K2 -> K3 as one H
 
 DePlan (nrm_de_plan_*) is the same for de(dg, dt, dc) with single=0 on the sparse-design kernels: the design dense or sparse, de's row filter, re-inflation and
 assertions and, on request, alpha and Benjamini-Hochberg q-values on the device; `results()` is `de`'s contract.  Single1Plan (nrm_single1_plan_*) is the same
-for single=1, a low-MOI screen: the row filter runs in front of the cell selection, the variances are per grouping.
+for single=1, a low-MOI screen: the row filter runs in front of the cell selection, the variances are per grouping.  Single4Plan (nrm_single4_plan_*) is the same
+for single=4, a high-MOI screen in closed form: what depends on the design alone is computed when the design is set, not in a step.
 """
 import ctypes
 
@@ -94,7 +95,7 @@ def _covariates(dc, pinv):
 
 
 class _Plan:
-	"""What the three plans share: the handle and its entries.  A class names its entries' prefix and the fields of its info()."""
+	"""What the four plans share: the handle and its entries.  A class names its entries' prefix and the fields of its info()."""
 	_prefix = None
 	_info_fields = None
 
@@ -297,7 +298,7 @@ def _design(dg):
 
 
 class _DesignPlan(_Plan):
-	"""What DePlan and Single1Plan share: a design beside the matrix, de's five results and the q-values."""
+	"""What DePlan, Single1Plan and Single4Plan share: a design beside the matrix, de's five results and the q-values."""
 
 	def _problem(self, dg, dt, dc, lowmem, q, out_dtype):
 		"""The constructors' common part: sets shape, dtype, adopted, out_dtype, nc, lowmem and q; returns the design's arguments, the matrix as _matrix returns it
@@ -343,7 +344,7 @@ class _DesignPlan(_Plan):
 
 	def device_results(self):
 		"""dict(p=, gamma=, alpha=, varg=, q= full-size device addresses (None for what the plan was created without), vart= the genes' variances -- (n_gene) for DePlan,
-		full-size (n_group, n_gene) for Single1Plan --, mask= one byte per grouping (1: tested), ld= row pitch in elements, dtype=, stream= the plan's own stream): for a
+		full-size (n_group, n_gene) for Single1Plan and Single4Plan --, mask= one byte per grouping (1: tested), ld= row pitch in elements, dtype=, stream= the plan's own stream): for a
 		consumer queued behind the step."""
 		v = [_vp() for _ in range(7)]
 		st, ld = _vp(), _i64(0)
@@ -440,6 +441,57 @@ class Single1Plan(_DesignPlan):
 		selected for it (association.py:917-918) and for the result assertions (association.py:248,252; de.py:124-131), ValueError for covariates that are not finite,
 		RuntimeError for too few cells."""
 		self._call('check')
+
+
+class Single4Plan(_DesignPlan):
+	"""de(dg, dt, dc, single=4) -- a high-MOI screen: every grouping tested with all the others as covariates, in closed form -- resident on the GPU
+	(include/normalisr_hip.h: nrm_single4_plan_*):
+
+		with cplan.Single4Plan(dg, dt, dc, lowmem=False, q=True) as plan:
+			plan.step()
+			p, gamma, alpha, varg, vart = plan.results()   # == normalisr.de(dg, dt, dc, single=4, lowmem=False)
+			q = plan.qvalues()                              # == binnet.bh(p)
+			plan.update(dt2); plan.step()                   # same shape, new values: one graph launch
+			plan.set_design(dg2); plan.step()               # another design of the same shape: the design side again, once
+
+	dg, dt, lowmem, q, out_dtype and pinv as DePlan takes them; dimreduce is a scalar.  Everything that depends on the design and the covariates alone -- M~, its
+	inverse, the design scalars, the rank decision at `tol` -- is computed when the design is set, not in a step.  NotImplementedError where the closed form has no
+	certificate (design rows dependent given the covariates, covariates of rank 0, more covariates than the sparse-design kernel takes): normalisr.de(..., single=4)
+	covers those.
+	info(): route (0: the sparse-design kernels, 1: K1 and the fp64 Gram kernel after a hand-back), captured, steps, reruns, rank, dof, bytes, rows_kept."""
+	_prefix, _info_fields = 'nrm_single4_plan_', DE_INFO_FIELDS
+
+	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None, pinv='numpy', tol=1e-8):
+		super().__init__()
+		if pinv not in ('numpy', 'library'):
+			raise ValueError("pinv must be 'numpy' or 'library'")
+		if np.ndim(dimreduce) != 0:
+			raise NotImplementedError('Single4Plan: one dimreduce for all genes (association_tests(..., single=4) takes one per gene)')
+		if int(dimreduce) != dimreduce:
+			raise ValueError('dimreduce must be an integer.')
+		(gargs, gkeep), (dt, ptr, shape, dtype, ld), dc = self._problem(dg, dt, dc, lowmem, q, out_dtype)
+		nc = self.nc
+		if pinv == 'numpy' and nc:  # the reference's own pseudo-inverse and rank of dc dc^T at `tol` (association.py:527-528)
+			from .association import inv_rank
+			dc = np.ascontiguousarray(dc, dtype=np.float64)
+			if (dc != 0).any():
+				dci, dcr = inv_rank(np.matmul(dc, dc.T), tol=tol)
+			else:
+				dci, dcr = np.zeros((nc, nc)), 0
+			dci = np.ascontiguousarray(dci, dtype=np.float64)
+		else:
+			dc, dci, dcr = _covariates(dc, 'library')
+		self._open(device, dt, *gargs, self.shape[0], ptr, _code(dtype), shape[0], shape[1], ld, 1 if self.adopted else 0, dc.ctypes.data if nc else None, _code(dc.dtype), nc,
+				   None if dci is None or not nc else dci.ctypes.data, int(dcr), int(dimreduce), _code(self.out_dtype), 0 if self.lowmem else 1, 1 if self.q else 0, float(tol))
+		del gkeep  # (the design was read inside create)
+
+	def check(self):
+		"""Waits for the queued steps and tests what they counted.  Returns the expression rows handed back since the last check -- > 0: rows all but inside the
+		covariates' span; the design side and the step were redone on K1 and the fp64 Gram kernel before returning, and the plan stays on that route until
+		set_design.  AssertionError for the reference's assertions on what then stands (association.py:557; de.py:124-131)."""
+		back = _i64(0)
+		self._call('check', ctypes.byref(back))
+		return int(back.value)
 
 
 assert __name__ != "__main__"

@@ -1,4 +1,4 @@
-// What the resident plans of de (nrm_de_plan.hip: single=0; nrm_single1_plan.hip: single=1) do to a design when it is set, in nrm_de_design.hip: de's row filter
+// What the resident plans of de (nrm_de_plan.hip: single=0; nrm_single1_plan.hip: single=1; nrm_single4_plan.hip: single=4) do to a design when it is set, in nrm_de_design.hip: de's row filter
 // (de.py:93), the row map, the rows kept compacted on the device, and their lists (csrc/nrm_design_lists.hip, csrc/nrm_design_csr.hip).
 #pragma once
 #include <memory>
@@ -20,8 +20,8 @@ int nrm_de_design_malformed();
 int nrm_de_design_set(const char* who, const NrmDePlanDesign& in, int64_t ng0, int64_t n, uint8_t* d_mask, int64_t* d_c2f, int32_t* d_f2c, bool want_ell, double max_density,
 					  hipStream_t st, NrmDeDesign& out);
 
-// ---- what the entries of the two plans do alike around a design.  Plan: nrm_de_plan or nrm_single1_plan -- L, device, drop_graph() and name, "nrm_de_plan" or
-// "nrm_single1_plan" ----------------------------------------------------------------------------------------------------------------------------------------------
+// ---- what the entries of these plans do alike around a design.  Plan: nrm_de_plan, nrm_single1_plan or nrm_single4_plan -- L, device, drop_graph() and name, "nrm_de_plan"
+// and so on ----------------------------------------------------------------------------------------------------------------------------------------------
 template <typename Plan>
 int plan_bind(Plan* pl, const char* who) {
 	NRM_REQUIRE(pl != nullptr, "%s: null plan", who);

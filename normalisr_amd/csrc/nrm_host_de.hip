@@ -45,7 +45,7 @@ int NrmDesignLists::build(const void* d_x, int x_dtype, int64_t nx, int64_t n, b
 }
 
 // (a temporary workspace per call; the scratch returns to the pool with this scope, hence the synchronise)
-int sparse_products(NrmDesignLists& L, const void* d_y, int y_dtype, int64_t ny, int64_t n, const double* d_c, int64_t ncu, int ci, double cval, const double* d_dci,
+int sparse_products(const NrmDesignLists& L, const void* d_y, int y_dtype, int64_t ny, int64_t n, const double* d_c, int64_t ncu, int ci, double cval, const double* d_dci,
 					const double* d_bx, int64_t ldb, double* d_dot, int64_t ldd, int by_gene, double* d_ssy, double* d_coefy, int32_t* d_flags, hipStream_t st) {
 	NrmSparseProducts work;
 	NRM_TRY(work.alloc(ny, n, ncu, ci, nrm_take_plain, st));

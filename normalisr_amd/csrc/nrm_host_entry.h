@@ -260,7 +260,7 @@ struct NrmDesignLists {
 
 // x~ . y~ for every (design row, expression row) through the sparse-design kernels (nrm_host_de.hip): d_dot (nxp, nyp) or, by_gene, (nyp, nxp); the rows' sums
 // with the covariates inside the kernel for up to nrm_de_sparse_fused_covariates() of them, by the stream kernel of single=1 otherwise
-int sparse_products(NrmDesignLists& L, const void* d_y, int y_dtype, int64_t ny, int64_t n, const double* d_c, int64_t ncu, int ci, double cval, const double* d_dci,
+int sparse_products(const NrmDesignLists& L, const void* d_y, int y_dtype, int64_t ny, int64_t n, const double* d_c, int64_t ncu, int ci, double cval, const double* d_dci,
 					const double* d_bx, int64_t ldb, double* d_dot, int64_t ldd, int by_gene, double* d_ssy, double* d_coefy, int32_t* d_flags, hipStream_t st);
 // the sparse-design form of single=0 de inside nrm_association_tests_host (nrm_host_de.hip); *taken = 0: the design does not qualify
 // (dense, or empty) and nothing was written; *handed_back = rows too close to the span of the covariates (the caller runs the dense fp64 path)

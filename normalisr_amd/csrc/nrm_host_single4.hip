@@ -9,6 +9,7 @@
 #include <vector>
 #include "nrm_host_entry.h"
 #include "nrm_design.h"
+#include "nrm_single4_step.h"
 
 // ---- the two pieces the package needs to follow the reference's per-grouping algorithm of single=4 WITHOUT torch ------------------------------------------
 // (association.py:926-980 forms the Gram matrices of A = [dx; dc] and of dy against A with numpy.matmul and hands them to association_test_4; for designs the closed
@@ -65,60 +66,8 @@ extern "C" int nrm_pvalues_host(const double* h_r2, int64_t count, double dof, d
 // ---- single=4 (association.py:421-576,926-980) in closed form, for full-rank designs --------------------------------------------------------
 namespace {
 
-// Inverse of the symmetric positive definite matrix whose upper tiles are in d_m (nxp x nxp) by Newton-Schulz iteration on the fp64 Gram kernel
-// (normalisr_amd/single4.py: _spd_inverse_device); d_n receives the inverse (zero padding), small (3, nx) its diagonal / kappa numerators / absolute
-// row sums; *norm1 = ||M||_1.  *ok = 0: not converged (the caller takes the host's Cholesky factorisation).
-int spd_inverse_device(const double* d_m, int64_t nx, int64_t nxp, const double* d_ss, DevBuf& d_n, std::vector<double>& small, double* norm1, int* ok, void* gwork,
-					   hipStream_t st) {
-	*ok = 0;
-	DevBuf mp, t, tt, xt, x, scal, work, res, dsmall;
-	const size_t mb = (size_t)nxp * nxp * 8;
-	for (DevBuf* b : {&mp, &t, &tt, &xt, &x}) NRM_TRY(b->alloc(mb));
-	NRM_TRY(scal.alloc(16));
-	NRM_TRY(work.alloc((size_t)std::max<int64_t>(2 * nxp, (nxp / 32) * (nxp / 32)) * 8));
-	NRM_TRY(res.alloc(8));
-	NRM_TRY(nrm_spd_prepare(d_m, nxp, nx, nxp, mp.as<double>(), scal.as<double>(), work.as<double>(), st));
-	double hs[2];
-	NRM_HIP(hipMemcpyAsync(hs, scal.p, 16, hipMemcpyDeviceToHost, st));
-	NRM_HIP(hipStreamSynchronize(st));
-	*norm1 = hs[0];
-	if (!std::isfinite(hs[0]) || hs[0] <= 0) return NRM_OK;
-	bool done = false;
-	for (int start = 0; start < 2 && !done; start++) {  // diag(1 / M_ii) first (nearly orthogonal rows: five steps), then I / ||M||_1 (always converges)
-		NRM_TRY(nrm_spd_start(mp.as<double>(), nxp, start == 0 ? 1 : 0, scal.as<double>(), x.as<double>(), st));
-		const int look_from = start == 0 ? 2 : 4;
-		bool diverged = false;
-		for (int it = 0; it < 60; it++) {
-			NRM_TRY(nrm_gram_f64(mp.as<double>(), x.as<double>(), nxp, nxp, nxp, nxp, nxp, t.as<double>(), nxp, 0, 0, 0, gwork, st));  // T = M X
-			NRM_TRY(nrm_spd_transpose_residual(t.as<double>(), nxp, tt.as<double>(), res.as<double>(), work.as<double>(), st));
-			double r = INFINITY;
-			if (it >= look_from) {
-				NRM_HIP(hipMemcpyAsync(&r, res.p, 8, hipMemcpyDeviceToHost, st));
-				NRM_HIP(hipStreamSynchronize(st));
-			}
-			if (std::isnan(r) || (start == 0 && it == look_from && !(r < 1.0))) {
-				diverged = true;
-				break;
-			}
-			NRM_TRY(nrm_gram_f64(x.as<double>(), tt.as<double>(), nxp, nxp, nxp, nxp, nxp, xt.as<double>(), nxp, 0, 0, 0, gwork, st));  // X T
-			NRM_TRY(nrm_spd_update(x.as<double>(), xt.as<double>(), nxp * nxp, st));
-			if (r < 1e-7) {
-				done = true;
-				break;
-			}
-		}
-		if (start == 1 && diverged) return NRM_OK;
-	}
-	if (!done) return NRM_OK;
-	NRM_TRY(d_n.alloc(mb));
-	NRM_TRY(dsmall.alloc((size_t)3 * nx * 8));
-	NRM_TRY(nrm_spd_finish(x.as<double>(), nx, nxp, d_ss, d_n.as<double>(), dsmall.as<double>(), st));
-	NRM_TRY(download(small, dsmall.p, (size_t)3 * nx));
-	*ok = 1;
-	return NRM_OK;
-}
-
-// single=4's closed form, both entries: rank == nc (full-rank covariates, A A^T certified full rank) or 0 < rank < nc (nrm_pinv_rank_certified)
+// single=4's closed form, both entries: rank == nc (full-rank covariates, A A^T certified full rank) or 0 < rank < nc (nrm_pinv_rank_certified).  The design side and
+// the gene side are NrmSingle4Step's (nrm_single4_step.h: the record the resident plan runs too); alpha and the assertions are taken on the host here.
 int single4_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const void* h_dc, int c_dtype, int64_t nc, int64_t n,
 				 const double* h_dci, int rank, int dimreduce, int return_dot, double tol, void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary,
 				 int out_dtype, bool full_rank_only) {
@@ -140,8 +89,7 @@ int single4_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, in
 		return NRM_E_DEVICE;
 	}
 	hipStream_t st = nullptr;
-	const int64_t kp = nrm_round_up(n, NRM_K_TILE), nxp = nrm_round_up(nx, NRM_ROW_TILE), nyp = nrm_round_up(ny, NRM_ROW_TILE);
-	DevBuf dx, dy, dc, dci, gwork, flags;
+	DevBuf dx, dy, dc, dci, op, ostat, ovary;
 	std::vector<double> c64;
 	NRM_TRY(upload_matrix(h_dx, x_dtype, nx, n, dx, st));
 	NRM_TRY(upload_matrix(h_dy, y_dtype, ny, n, dy, st));
@@ -150,152 +98,63 @@ int single4_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, in
 		NRM_TRY(dci.alloc((size_t)nc * nc * 8));
 		NRM_HIP(hipMemcpy(dci.p, h_dci, (size_t)nc * nc * 8, hipMemcpyHostToDevice));
 	}
-	NRM_TRY(gwork.alloc((size_t)nrm_gram_workspace_bytes()));
-	NRM_TRY(flags.alloc_zero(16, st));
-	double cval = 0.0;
-	const int ci = nc ? nrm_constant_row(c64.data(), nc, n, &cval) : -1;
+	NrmSingle4Step s;
+	s.rows = s.nx = nx, s.ny = ny, s.n = n, s.ldx = s.ldy = n, s.nc = nc;
+	s.x_dtype = x_dtype, s.y_dtype = y_dtype, s.out_dtype = out_dtype, s.rank = rank, s.dimreduce = dimreduce, s.return_dot = return_dot, s.tol = tol;
+	s.want_alpha = h_alpha != nullptr && nc > 0;
+	s.ci = nc ? nrm_constant_row(c64.data(), nc, n, &s.cval) : -1;
+	s.who = rank < nc ? "nrm_association_tests_single4_pinv_host" : "nrm_association_tests_single4_host";
+	s.d_x = dx.p, s.d_y = dy.p, s.d_c = dc.as<double>(), s.d_dci = dci.as<double>(), s.h_c64 = c64.data();
+	NRM_TRY(s.alloc_fixed(nrm_take_plain, st));
+	const size_t ob = (size_t)nx * ny * nrm_esize(out_dtype);
+	NRM_TRY(op.alloc(ob));
+	NRM_TRY(ostat.alloc(ob));
+	NRM_TRY(ovary.alloc(ob));
+	s.p = op.p, s.stat = ostat.p, s.vary = ovary.p;
 	// the design rows: from their entries when there are few (gRNA incidence), else K1's fp64 residuals
-	DevBuf ssx, bx, mt, rxd;
-	NRM_TRY(ssx.alloc_zero((size_t)nxp * 8, st));
-	NRM_TRY(bx.alloc_zero((size_t)nx * (nc > 0 ? nc : 1) * 8, st));
-	NRM_TRY(mt.alloc((size_t)nxp * nxp * 8));
-	auto residualize_design = [&]() -> int {  // K1 on the design rows: x~ (nxp, kp), |x~|^2, b_x
-		NRM_TRY(rxd.alloc((size_t)nxp * kp * 8));
-		return nrm_residualize(dx.p, x_dtype, nx, n, n, dc.as<double>(), nc, n, dci.as<double>(), rank, rxd.as<double>(), kp, nxp, ssx.as<double>(), nc ? bx.as<double>() : nullptr,
-							   st);
-	};
 	NrmDesignLists L;
-	bool sparse = false;
 	if (nrm_de_sparse_wanted(nx, ny, n, nc)) {
 		NRM_TRY(L.build(dx.p, x_dtype, nx, n, true, 1.0 / 16, st));
-		sparse = L.ok;
+		s.sparse = L.ok;
+		s.L = &L;
 	}
 	for (int pass = 0; pass < 2; pass++) {  // (a second pass only when the sparse-design kernels hand rows back: the same on K1 and the fp64 Gram kernel)
+		if (s.sparse)
+			NRM_TRY(s.alloc_sparse(nrm_take_plain, st));
+		else
+			NRM_TRY(s.alloc_dense(nrm_take_plain));
+		int64_t handed = 0;
+		NRM_TRY(s.alloc_design_side(st, &handed));
+		if (handed > 0) {
+			s.sparse = false;
+			continue;
+		}
+		NRM_TRY(s.enqueue(st));
 		int32_t hf[4];
-		if (sparse) {
-			NRM_TRY(nrm_design_stats(L.row_ptr.as<int64_t>(), L.cells.as<int32_t>(), L.row_vals.as<double>(), dc.as<double>(), n, nc, dci.as<double>(), nx, ssx.as<double>(),
-									 nc ? bx.as<double>() : nullptr, flags.as<int32_t>(), st));
-			DevBuf ss2;  // (|x~|^2 again, as the product kernel computes it for its rows: not used)
-			NRM_TRY(ss2.alloc((size_t)nxp * 8));
-			// M~ = X~ X~^T: the same product with the design rows in the place of the expression rows
-			NRM_TRY(sparse_products(L, dx.p, x_dtype, nx, n, dc.as<double>(), nc, ci, cval, dci.as<double>(), bx.as<double>(), nc > 0 ? nc : 1, mt.as<double>(), nxp, 0,
-									ss2.as<double>(), nullptr, flags.as<int32_t>(), st));
-			// a design row all but inside the span of the covariates is known HERE: looked at before the inverse and the genes' products, which a
-			// handed-back call would only repeat (round-5 advisory)
-			NRM_TRY(nrm_read_flags(flags.p, st, hf));
-			if (hf[2] > 0) {
-				sparse = false;
-				NRM_HIP(hipMemsetAsync(flags.p, 0, 16, st));
-				continue;
-			}
-		} else {
-			NRM_TRY(residualize_design());
-			NRM_TRY(nrm_gram_f64(rxd.as<double>(), rxd.as<double>(), nxp, nxp, kp, kp, kp, mt.as<double>(), nxp, 1, nx, nx, gwork.p, st));
+		NRM_TRY(nrm_read_flags(s.flags.p, st, hf));
+		if (s.sparse && hf[2] > 0) {  // rows all but inside the span of the covariates: K1's two sweeps and the fp64 Gram kernel for this call
+			s.sparse = false;
+			NRM_HIP(hipMemsetAsync(s.flags.p, 0, 32, st));
+			continue;
 		}
-		// N~ = M~^-1
-		DevBuf dn;
-		std::vector<double> small;
-		double norm_mt = 0.0;
-		int okdev = 0;
-		NRM_TRY(spd_inverse_device(mt.as<double>(), nx, nxp, ssx.as<double>(), dn, small, &norm_mt, &okdev, gwork.p, st));
-		if (!okdev) {  // the host's Cholesky factorisation
-			std::vector<double> hm, hss, npad;
-			NRM_TRY(download(hm, mt.p, (size_t)nxp * nxp));
-			NRM_TRY(download(hss, ssx.p, (size_t)nx));
-			if (!nrm_spd_inverse_fallback(hm.data(), hss.data(), nx, nxp, &norm_mt, npad, small)) {
-				nrm_set_error("design rows are linearly dependent given the covariates");
-				return NRM_E_UNSUPPORTED;
-			}
-			NRM_TRY(dn.alloc(npad.size() * 8));
-			NRM_HIP(hipMemcpy(dn.p, npad.data(), npad.size() * 8, hipMemcpyHostToDevice));
-		}
-		double norm_ninv = 0.0;
-		std::vector<double> dxx((size_t)nx);
-		for (int64_t i = 0; i < nx; i++) {
-			const double d = small[(size_t)i];
-			if (!std::isfinite(d) || !std::isfinite(small[(size_t)(nx + i)]) || !std::isfinite(small[(size_t)(2 * nx + i)]) || !(d > 0)) {
-				nrm_set_error("design rows are linearly dependent given the covariates");
-				return NRM_E_UNSUPPORTED;
-			}
-			norm_ninv = small[(size_t)(2 * nx + i)] > norm_ninv ? small[(size_t)(2 * nx + i)] : norm_ninv;
-			dxx[(size_t)i] = 1.0 / ((double)n * d);
-		}
-		// the genes: Y~ X~^T (as (genes, design rows)), |y~|^2, b_y on request
-		const bool want_alpha = h_alpha != nullptr && nc > 0;
-		DevBuf g, ssy, by, ryd;
-		NRM_TRY(g.alloc_zero((size_t)nyp * nxp * 8, st));
-		NRM_TRY(ssy.alloc((size_t)nyp * 8));
-		if (want_alpha) NRM_TRY(by.alloc_zero((size_t)ny * nc * 8, st));
-		if (sparse) {
-			NRM_TRY(sparse_products(L, dy.p, y_dtype, ny, n, dc.as<double>(), nc, ci, cval, dci.as<double>(), bx.as<double>(), nc > 0 ? nc : 1, g.as<double>(), nxp, 1,
-									ssy.as<double>(), want_alpha ? by.as<double>() : nullptr, flags.as<int32_t>(), st));
-			NRM_TRY(nrm_read_flags(flags.p, st, hf));
-			if (hf[2] > 0) {  // rows all but inside the span of the covariates: K1's two sweeps and the fp64 Gram kernel for this call
-				sparse = false;
-				NRM_HIP(hipMemsetAsync(flags.p, 0, 16, st));
-				continue;
-			}
-		} else {
-			if (!rxd.p) NRM_TRY(residualize_design());  // (handed back from the sparse kernels: the design rows' residuals are needed after all)
-			NRM_TRY(ryd.alloc((size_t)nyp * kp * 8));
-			NRM_TRY(nrm_residualize(dy.p, y_dtype, ny, n, n, dc.as<double>(), nc, n, dci.as<double>(), rank, ryd.as<double>(), kp, nyp, ssy.as<double>(),
-									want_alpha ? by.as<double>() : nullptr, st));
-			NRM_TRY(nrm_gram_f64(ryd.as<double>(), rxd.as<double>(), nyp, nxp, kp, kp, kp, g.as<double>(), nxp, 0, ny, nx, gwork.p, st));
-			ryd.release();
-		}
-		// B^T = (Y~ X~^T) N~, the sweep
-		DevBuf bt, ddxx, op, ostat, ovary, work;
-		NRM_TRY(bt.alloc((size_t)nyp * nxp * 8));
-		NRM_TRY(nrm_gram_f64(g.as<double>(), dn.as<double>(), nyp, nxp, nxp, nxp, nxp, bt.as<double>(), nxp, 0, ny, nx, gwork.p, st));
-		NRM_TRY(ddxx.alloc((size_t)nx * 8));
-		NRM_HIP(hipMemcpyAsync(ddxx.p, dxx.data(), (size_t)nx * 8, hipMemcpyHostToDevice, st));
-		const size_t ob = (size_t)nx * ny * nrm_esize(out_dtype);
-		NRM_TRY(op.alloc(ob));
-		NRM_TRY(ostat.alloc(ob));
-		NRM_TRY(ovary.alloc(ob));
-		NRM_TRY(work.alloc((size_t)ny * 8));
-		NRM_TRY(nrm_single4_sweep(bt.as<double>(), g.as<double>(), nxp, ssy.as<double>(), ddxx.as<double>(), nx, ny, nx, n, (double)(n - nx - rank - dimreduce), return_dot, op.p, ostat.p,
-								  ovary.p, out_dtype, ny, work.as<double>(), flags.as<int32_t>(), st));
-		// (the reference's assertions on the closed form's results speak only if the closed form applies: a nearly rank-deficient design can fail them
-		//  where the per-grouping algorithm -- which the package then takes -- returns results; association.py:421-576.  Round-5 advisory.)
-		int32_t hf2[2];
-		NRM_TRY(nrm_read_flags(flags.p, st, hf2));
-		const int flag_rc = nrm_assoc_assertions(hf2, "");
-		// Does the closed form apply?  Every grouping's rank nx - 1 + rank for rank-deficient covariates, else the reference's own rank test on A A^T (nrm_host_math.h)
-		std::vector<double> hbx, mcc;
-		nrm_covariate_gram(c64.data(), nc, n, mcc);
-		if (rank < nc) {
-			std::vector<double> hss;
-			NRM_TRY(download(hbx, bx.p, (size_t)nx * nc));
-			NRM_TRY(download(hss, ssx.p, (size_t)nx));
-			if (!nrm_pinv_rank_certified(mcc, nc, rank, hbx.data(), hss.data(), nx, norm_mt, norm_ninv, tol)) {
-				nrm_set_error("nrm_association_tests_single4_pinv_host: some grouping may not have the rank nx - 1 + %d at tol = %g (no certificate from the norms); the package takes the spectrum of A A^T and, if need be, the per-grouping algorithm", rank, tol);
-				return NRM_E_UNSUPPORTED;
-			}
-		} else {
-			bool certified = false;
-			if (nc) NRM_TRY(download(hbx, bx.p, (size_t)nx * nc));
-			NRM_TRY(nrm_full_rank_certified(norm_mt, norm_ninv, hbx.data(), mcc.data(), nx, nc, tol, &certified));
-			if (!certified) {
-				nrm_set_error("nrm_association_tests_single4_host: the design may be rank deficient at tol = %g (no certificate from the norms); the package takes the spectrum of A A^T and, if need be, the per-grouping algorithm", tol);
-				return NRM_E_UNSUPPORTED;
-			}
-		}
-		if (flag_rc) {
+		// (the reference's assertions on the closed form's results speak only if the closed form applies -- the design side has certified that by now: a nearly
+		//  rank-deficient design can fail them where the per-grouping algorithm, which the package then takes, returns results; association.py:421-576)
+		if (nrm_assoc_assertions(hf, "")) {
 			nrm_set_error("association results failed the reference's assertions (association.py:557): non-finite values or R^2 > 1+1e-8 in the closed form of a full-rank design");
-			return flag_rc;
+			return NRM_E_NUMERIC;
 		}
 		NRM_TRY(copy_out(h_p, op.p, ob));
 		NRM_TRY(copy_out(h_stat, ostat.p, ob));
 		NRM_TRY(copy_out(h_vary, ovary.p, ob));
-		for (double& v : dxx)
+		std::vector<double> varx = s.dxx;
+		for (double& v : varx)
 			if (v == 0.0) v = 1.0;
-		nrm_store_as(out_dtype, h_varx, dxx.data(), nx);
-		if (want_alpha) {
+		nrm_store_as(out_dtype, h_varx, varx.data(), nx);
+		if (s.want_alpha) {
 			std::vector<double> hbt, hby;
-			NRM_TRY(download(hbt, bt.p, (size_t)nyp * nxp));
-			NRM_TRY(download(hby, by.p, (size_t)ny * nc));
-			nrm_single4_alpha(hbt.data(), nxp, hby.data(), hbx.data(), nx, ny, nc, out_dtype, h_alpha);
+			NRM_TRY(download(hbt, s.bt.p, (size_t)s.nyp * s.nxp));
+			NRM_TRY(download(hby, s.by.p, (size_t)ny * nc));
+			nrm_single4_alpha(hbt.data(), s.nxp, hby.data(), s.hbx.data(), nx, ny, nc, out_dtype, h_alpha);
 		}
 		return NRM_OK;
 	}

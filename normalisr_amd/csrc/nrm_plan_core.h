@@ -1,4 +1,4 @@
-// What every resident plan behind the C ABI has and does alike (nrm_coex_plan.hip, nrm_de_plan.hip, nrm_single1_plan.hip): its device and streams, the graph of its
+// What every resident plan behind the C ABI has and does alike (nrm_coex_plan.hip, nrm_de_plan.hip, nrm_single1_plan.hip, nrm_single4_plan.hip): its device and streams, the graph of its
 // step, the counts of steps and pool bytes -- and, written once, the step (eager first, captured second, replayed from then on, eager for good when a capture fails),
 // the timing between device events, the upload behind the barrier on `last`, and the teardown.  A plan's struct derives from NrmPlanCore and adds its own fields; what
 // it enqueues comes in as a callable.

@@ -1,0 +1,151 @@
+"""The resident single=4 step through the library's own plan handle (nrm_single4_plan_*, normalisr_amd/cplan.py: Single4Plan) against the step the project is quoted
+on (normalisr_amd.single4.Single4Plan.step, what bench.py's de_c4_single4 times), at BASELINE configs[3] as bench.py builds it for single=4: 1000 gRNAs x 15 000 genes
+x 50 000 cells fp32, five covariates, the high-MOI design (one entry in a hundred, seed 4).  Two kinds of child process, one on the GPU at a time, alternating
+`--rounds` times:
+
+  yardstick   imports torch; single4.Single4Plan on the matrices in HBM; `--warmup` steps, then `--reps` times `--steps` steps between two device events;
+  c_plan      cannot import torch; cplan.Single4Plan on a plan-owned copy of the same values; the same warm-up, then `--reps` times Single4Plan.time(`--steps`)
+              (nrm_single4_plan_time) -- without alpha or q --, and the same with lowmem=False (alpha) and with q=True.
+
+A child's figure is the median of its reps (ms per step).  The yardstick works at the level of association_tests: it runs neither de's re-inflation nor its
+assertions -- and it repeats the design side in every step, which the C plan runs once per design.  The expectation: the plan's median <= the yardstick's median +
+the yardstick's own min-max spread in this run + the time of the kernels only the C plan runs (k_s4_de_finish; k_s4_alpha and k_s4_alpha_rows with alpha), which
+comes from a kernel trace of the c_plan child by itself (`--kernel-stats` names its CSV); if it is not met, that trace says where the difference goes:
+    python tools/time_single4_c_plan.py --child yardstick --data DIR/c4      (writes DIR/c4.*.npy, which the other child reads)
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/time_single4_c_plan.py --child c_plan --data DIR/c4
+
+Usage: time_single4_c_plan.py [--rounds 3] [--steps 20] [--reps 5] [--warmup 20] [--kernel-stats CSV] [--out profiles/single4_c_plan.json]"""
+import argparse
+import csv
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+NX, NY, N, NC, SEED = 1000, 15000, 50000, 5, 4
+OWN_KERNELS = ('k_s4_de_finish', )  # (the step timed against the yardstick carries no alpha)
+
+
+def child_yardstick(args):
+	import torch
+	from normalisr_amd.single4 import Single4Plan
+	dev = torch.device('cuda', 0)
+	g = torch.Generator(device=dev)  # (bench.py: bench_de_method, single == 4, one rank)
+	g.manual_seed(SEED)
+	dc = torch.cat([torch.randn((NC - 1, N), generator=g, device=dev, dtype=torch.float32), torch.ones((1, N), device=dev, dtype=torch.float32)])
+	dx = (torch.rand((NX, N), generator=g, device=dev) < 0.01).to(torch.float32)
+	g2 = torch.Generator(device=dev)
+	g2.manual_seed(SEED * 7919)
+	dy = torch.randn((NY, N), generator=g2, device=dev, dtype=torch.float32)
+	dy[:16] += 0.2 * dx[0]
+	if not os.path.exists(args.data + '.dt.npy'):  # the values the other side reads
+		np.save(args.data + '.dc.npy', dc.cpu().numpy())
+		np.save(args.data + '.dg.npy', dx.cpu().numpy())
+		np.save(args.data + '.dt.npy', dy.cpu().numpy())
+	plan = Single4Plan(dx, dy, dc.cpu().numpy().astype(np.float64), return_dot=False)
+	for _ in range(args.warmup):
+		plan.step()
+	torch.cuda.synchronize()
+	ms = []
+	for _ in range(args.reps):
+		t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+		t0.record()
+		for _ in range(args.steps):
+			plan.step()
+		t1.record()
+		t1.synchronize()
+		ms.append(t0.elapsed_time(t1) / args.steps)
+	assert plan.check()
+	return dict(ms_per_step=ms, lean=bool(plan.lean), fallbacks=int(plan.fallbacks))
+
+
+def child_c_plan(args):
+	sys.modules['torch'] = None  # `import torch` raises ImportError here
+	from normalisr_amd import cplan
+	dg, dt, dc = (np.load(args.data + '.{}.npy'.format(k)) for k in ('dg', 'dt', 'dc'))
+	out = {}
+	for key, lowmem, q in (('step', True, False), ('step_alpha', False, False), ('step_q', True, True)):
+		with cplan.Single4Plan(dg, dt, dc.astype(np.float64), lowmem=lowmem, q=q) as plan:
+			for _ in range(args.warmup):
+				plan.step()
+			plan.check()
+			out[key] = [plan.time(args.steps) for _ in range(args.reps)]
+			plan.check()
+			out[key + '_info'] = plan.info()
+	assert sys.modules['torch'] is None
+	return out
+
+
+def run_child(kind, args):
+	cmd = [sys.executable, os.path.abspath(__file__), '--child', kind, '--data', args.data, '--steps', str(args.steps), '--reps', str(args.reps), '--warmup', str(args.warmup)]
+	r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.child_timeout)
+	if r.returncode != 0:
+		raise RuntimeError('{} child failed ({}):\n{}'.format(kind, r.returncode, r.stderr[-3000:]))
+	return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def side(runs, key):
+	fig = [float(np.median(r[key])) for r in runs]
+	return dict(rounds_ms=[round(v, 4) for v in fig], median_ms=round(float(np.median(fig)), 4), min_ms=round(min(fig), 4), max_ms=round(max(fig), 4),
+				reps_ms=[[round(v, 4) for v in r[key]] for r in runs])
+
+
+def own_kernels_ms(path):
+	"""Mean time per launch of the plan's own kernels (one launch of each per step) from a `rocprofv3 --kernel-trace --stats` CSV of the c_plan child."""
+	per = {}
+	with open(path) as f:
+		for row in csv.DictReader(f):
+			for k in OWN_KERNELS:
+				if k + '<' in row['Name'] or k + '(' in row['Name']:
+					per[k] = per.get(k, 0.0) + float(row['AverageNs']) / 1e6
+	return per
+
+
+def main():
+	ap = argparse.ArgumentParser()
+	ap.add_argument('--rounds', type=int, default=3)
+	ap.add_argument('--steps', type=int, default=20)
+	ap.add_argument('--reps', type=int, default=5)
+	ap.add_argument('--warmup', type=int, default=20)
+	ap.add_argument('--out', default='profiles/single4_c_plan.json')
+	ap.add_argument('--kernel-stats', default=None, help='kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of the c_plan child')
+	ap.add_argument('--child', default=None)
+	ap.add_argument('--data', default=None)
+	ap.add_argument('--child-timeout', type=int, default=300)
+	args = ap.parse_args()
+	if args.child:
+		print(json.dumps(dict(yardstick=child_yardstick, c_plan=child_c_plan)[args.child](args)))
+		return
+	with tempfile.TemporaryDirectory() as tmp:
+		args.data = os.path.join(tmp, 'c4')
+		ys, cs = [], []
+		for _ in range(args.rounds):
+			ys.append(run_child('yardstick', args))
+			cs.append(run_child('c_plan', args))
+	y, c, ca, cq = side(ys, 'ms_per_step'), side(cs, 'step'), side(cs, 'step_alpha'), side(cs, 'step_q')
+	c['info'], ca['info'], cq['info'] = cs[-1]['step_info'], cs[-1]['step_alpha_info'], cs[-1]['step_q_info']
+	spread = y['max_ms'] - y['min_ms']
+	own = own_kernels_ms(args.kernel_stats) if args.kernel_stats else None
+	own_ms = None if own is None else round(sum(own.values()), 4)
+	rec = dict(shape=dict(groupings=NX, genes=NY, cells=N, dtype='float32', covariates=NC, seed=SEED, density=0.01, yardstick_lean=ys[-1]['lean'], yardstick_fallbacks=ys[-1]['fallbacks']), rounds=args.rounds, steps=args.steps,
+			   reps=args.reps, warmup=args.warmup,
+			   yardstick=dict(what='normalisr_amd.single4.Single4Plan.step (torch), device events around the steps', **y),
+			   c_plan=dict(what='cplan.Single4Plan.time without alpha or q: nrm_single4_plan_time, one hipGraphLaunch per step, no torch in the process', **c),
+			   c_plan_alpha=dict(what='the same with lowmem=False: k_s4_alpha and the full-size alpha array inside the step', **ca),
+			   c_plan_q=dict(what='the same with q=True: nrm_bh over all P-values inside the step', **cq),
+			   yardstick_spread_ms=round(spread, 4), own_kernels_ms=own, own_kernels_from=args.kernel_stats,
+			   margin_ms=None if own_ms is None else round(spread + own_ms, 4),
+			   within_margin=None if own_ms is None else bool(c['median_ms'] <= y['median_ms'] + spread + own_ms))
+	os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+	with open(args.out, 'w') as f:
+		f.write(json.dumps(rec, indent=1) + '\n')
+	print(json.dumps(rec))
+
+
+if __name__ == '__main__':
+	main()
