@@ -319,7 +319,7 @@ int nrm_single4_sweep_guarded(const double* d_bt, const double* d_pt, int64_t ld
  *       its padding rows carrying mean(diag) on the diagonal; d_scal[0] = ||M||_1, d_scal[1] = mean(diag); d_work: 2 nxp doubles.
  *   nrm_spd_start: d_x = diag(1 / M_ii) (diagonal != 0) or I / ||M||_1.
  *   nrm_spd_transpose_residual: d_tt = d_t^T, d_res[0] = ||I - d_t||_F; d_work: (nxp / 32)^2 doubles.
- *   nrm_spd_update: d_x = 2 d_x - d_xt.
+ *   nrm_spd_update: d_x = 2 d_x - d_xt (both 16-byte aligned: anything else is refused).
  *   nrm_spd_finish: d_n = (d_x + d_x^T) / 2 inside nx x nx, 0 in the padding; d_small (3, nx) = diag(N), sum_j |N_ij| sqrt(d_ss[j]), sum_j |N_ij|.
  */
 int nrm_spd_prepare(const double* d_m, int64_t ldm, int64_t nx, int64_t nxp, double* d_mp, double* d_scal, double* d_work, void* stream);

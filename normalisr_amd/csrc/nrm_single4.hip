@@ -380,6 +380,7 @@ extern "C" int nrm_spd_transpose_residual(const double* d_t, int64_t nxp, double
 // d_x = 2 d_x - d_xt (count doubles, 16-byte aligned)
 extern "C" int nrm_spd_update(double* d_x, const double* d_xt, int64_t count, void* stream) {
 	NRM_REQUIRE(d_x && d_xt && count > 0, "nrm_spd_update: bad arguments");
+	NRM_REQUIRE(((uintptr_t)d_x % 16 == 0) && ((uintptr_t)d_xt % 16 == 0), "nrm_spd_update: d_x and d_xt must be 16-byte aligned");
 	hipLaunchKernelGGL(k_spd_update, dim3((unsigned)((count / 2 + 256) / 256)), dim3(256), 0, (hipStream_t)stream, d_x, d_xt, count);
 	return nrm_check_launch("k_spd_update");
 }
