@@ -883,6 +883,45 @@ int nrm_fitvar_weights(const double* d_best, int64_t n, double* d_ws, double* d_
 int nrm_fitvar_pinv_host(const double* m, int64_t n, double tol, double* inv, int64_t* rank);
 
 /*
+ * The front half of the pipeline as WHOLE-PROBLEM entries (csrc/nrm_host_front.hip): HOST buffers in, HOST buffers out, no torch -- the kernels above, sequenced
+ * as normalisr_amd/lcpm.py, norm.py and qc.py sequence them, uploads and scratch inside the library.  One call at a time per process, on the device of
+ * nrm_set_device.  Every argument is checked before any device call; the messages are the reference's.  The host arithmetic is csrc/nrm_host_math.h.
+ *
+ *   nrm_lcpm_host (lcpm.lcpm with varscale = 0, lcpm.py:21-208; scaling_factor's default variable, lcpm.py:258): h_x (rows, n) dense counts of dtype NRM_I64 /
+ *       NRM_I32 / NRM_I16 / NRM_U8.  nrm_lcpm_count, one read-back, nrm_lcpm_digamma and exp() of the table on the host, nrm_lcpm_colsum (normalize != 0),
+ *       nrm_lcpm_write, copy out.  ntot < 0: None (t0 = sum + 2, lcpm.py:94-95), else t0 = ntot + 2.  h_out (rows, n) of out_dtype NRM_F32 / NRM_F64, or NULL:
+ *       the integer pass alone.  h_cov (3, n) fp64 or NULL: ln total, genes without a read, ln^2 total of every cell (lcpm.py:194-200).  h_gene_zero int64[rows]
+ *       or NULL: the zero entries of every gene -- one upload serves lcpm and scaling_factor.  h_info int64[2] = sum, maximum.
+ *       NRM_E_ARG: a negative entry when h_out or h_cov is given (lcpm.py:85-86), an empty matrix, a cell without a read when h_cov is given (lcpm.py:196), ntot == 0.  NRM_E_NUMERIC: no read
+ *       at all (the assertion of lcpm.py:95).  NRM_E_UNSUPPORTED: a count at or beyond nrm_lcpm_table_cap.
+ *   nrm_lcpm_csr_host: the same over canonical CSR host arrays (the format of nrm_lcpm_csr_count) through nrm_lcpm_csr_count / colsum / write: the dense counts
+ *       are never formed.  NRM_E_ARG for a malformed matrix.
+ *   nrm_compute_var_host (norm.compute_var, norm.py:56-128): h_y (rows, n) fp32 / fp64 logCPM, h_c (nc, n) fp64, 1 <= nc <= 63 (NRM_E_UNSUPPORTED outside,
+ *       before any device call) -> h_w fp64[n], the weights >= 1.  The pseudo-inverse of [C;1][C;1]^T on rows of unit length comes from the Jacobi routine of
+ *       nrm_fitvar_pinv_host on the host; then the device-only sequence: nrm_fitvar_plan_start, per iteration design, pinv, moments, genes, cells, update -- all
+ *       stepmax iterations enqueued, iterations past `best change <= eps` leave the state as it is --, nrm_fitvar_weights, and ONE read-back of the counters,
+ *       the last state record and the weights.  h_state double[2] = the best change (the reference's bestv) and the steps taken.  NRM_E_NUMERIC: a gene with a
+ *       constant residual (norm.py:108,125), weights that are not finite and positive (norm.py:125-127).  NRM_E_ARG: stepmax <= 0, eps <= 0, covariates with
+ *       infs or NaNs.
+ *   nrm_qc_reads_host, nrm_qc_reads_csr_host (qc.qc_reads, qc.py:4-85): the reference's loop (qc.py:49-81) -- nrm_qc_stats / nrm_qc_csr_stats, the thresholds
+ *       of the CURRENT numbers of genes and cells (ceil of the double; the proportional bounds of the current numbers), nrm_qc_decide, one read-back -- until
+ *       neither count changes.  h_gene_alive[rows], h_cell_alive[n]: byte masks, 1 = kept.  h_info int64[3] = iterations, genes left, cells left; the loop stops
+ *       where no gene or no cell is left and the entry returns NRM_OK: the caller raises qc.py:78-81 (genes first).  NRM_E_ARG: negative parameters,
+ *       proportions above 1, a negative entry, a malformed matrix.
+ */
+int nrm_lcpm_host(const void* h_x, int dtype, int64_t rows, int64_t n, int normalize, int64_t ntot, void* h_out, int out_dtype, double* h_cov /* (3, n) or NULL */,
+				  int64_t* h_gene_zero /* rows or NULL */, int64_t* h_info /* int64[2] */);
+int nrm_lcpm_csr_host(const int64_t* h_indptr, const int32_t* h_indices, const void* h_data, int dtype, int64_t rows, int64_t n, int64_t nnz, int normalize, int64_t ntot,
+					  void* h_out, int out_dtype, double* h_cov, int64_t* h_gene_zero, int64_t* h_info /* int64[2] */);
+int nrm_compute_var_host(const void* h_y, int y_dtype, int64_t rows, int64_t n, const double* h_c, int64_t nc, int64_t stepmax, double eps, double* h_w,
+						 double* h_state /* double[2] */);
+int nrm_qc_reads_host(const void* h_x, int dtype, int64_t rows, int64_t n, double n_gene, double nc_gene, double ncp_gene, double n_cell, double nt_cell, double ntp_cell,
+					  uint8_t* h_gene_alive, uint8_t* h_cell_alive, int64_t* h_info /* int64[3] */);
+int nrm_qc_reads_csr_host(const int64_t* h_indptr, const int32_t* h_indices, const void* h_data, int dtype, int64_t rows, int64_t n, int64_t nnz, double n_gene,
+						  double nc_gene, double ncp_gene, double n_cell, double nt_cell, double ntp_cell, uint8_t* h_gene_alive, uint8_t* h_cell_alive,
+						  int64_t* h_info /* int64[3] */);
+
+/*
  * Gene-set enrichment (normalisr_amd/enrich.py; csrc/nrm_enrich.hip): what stands between the principal genes and pccovt in the reference's gocovt, as
  * arithmetic alone.  S study sets against T gene sets over G genes, N of them in the background.  Bit matrices hold W = ceil(G / 64) 64-bit words per row with
  * pitch W, gene g at bit g % 64 of word g / 64, bits at or beyond G zero; word buffers are 8-byte aligned.  Every entry checks its arguments (null pointers,

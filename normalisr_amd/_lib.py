@@ -168,6 +168,11 @@ _SIGNATURES = {
 	'nrm_fitvar_update': ([_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp], _i32),
 	'nrm_fitvar_weights': ([_vp, _i64, _vp, _vp, _vp, _vp], _i32),
 	'nrm_fitvar_pinv_host': ([_vp, _i64, _dbl, _vp, _vp], _i32),
+	'nrm_lcpm_host': ([_vp, _i32, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp], _i32),
+	'nrm_lcpm_csr_host': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp], _i32),
+	'nrm_compute_var_host': ([_vp, _i32, _i64, _i64, _vp, _i64, _i64, _dbl, _vp, _vp], _i32),
+	'nrm_qc_reads_host': ([_vp, _i32, _i64, _i64] + [_dbl] * 6 + [_vp, _vp, _vp], _i32),
+	'nrm_qc_reads_csr_host': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64] + [_dbl] * 6 + [_vp, _vp, _vp], _i32),
 	'nrm_enrich_pack': ([_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
 	'nrm_enrich_overlap': ([_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
 	'nrm_enrich_fisher': ([_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp], _i32),

@@ -1,7 +1,8 @@
 // What the whole-problem host entries (numpy buffers in, numpy buffers out; no torch) share: the device scratch pool kept between calls, the
 // lock that serialises them per process, a scoped device buffer, the uploads, read-backs and result copies every entry makes.  nrm_api.hip owns the pool
 // and the lock and holds the dense single=0 entry; the others are in nrm_host_de.hip (sparse-design and streaming de), nrm_host_single1.hip,
-// nrm_host_single4.hip (with nrm_gram_host / nrm_pvalues_host) and nrm_host_normvar.hip (with nrm_binnet_host).  Their arithmetic is in nrm_host_math.h.
+// nrm_host_single4.hip (with nrm_gram_host / nrm_pvalues_host), nrm_host_normvar.hip (with nrm_binnet_host) and nrm_host_front.hip (lcpm, compute_var, qc_reads).
+// Their arithmetic is in nrm_host_math.h.
 #pragma once
 #include <algorithm>
 #include <cmath>

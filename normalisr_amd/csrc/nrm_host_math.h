@@ -1,6 +1,6 @@
 // The host arithmetic of the whole-problem entries (nrm_host_*.hip, nrm_api.hip): whatever decides a route or a rank, and the small dense algebra between two
 // kernel launches.  Like nrm_host_logic.h it is kept free of HIP headers, so that g++ can build it with -fsanitize=address,undefined for the CPU test-suite
-// (tests/host/entry_math_sanitize.cpp).  Every loop keeps the summation order it had inside the entries: their results are compared bit for bit.
+// (tests/host/entry_math_sanitize.cpp, tests/host/front_entry_math_sanitize.cpp).  Every loop keeps the summation order it had inside the entries: their results are compared bit for bit.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/normalisr_hip.h"
 #include "nrm_jacobi.h"
+#include "nrm_jacobi_lanes.h"
 
 void nrm_set_error(const char* fmt, ...);
 
@@ -378,4 +379,62 @@ static inline void nrm_single4_alpha(const double* hbt, int64_t ldbt, const doub
 			for (int64_t i = 0; i < nx; i++) s -= hbt[(size_t)(y * ldbt + i)] * hbx[(size_t)(i * nc + c)];
 			for (int64_t i = 0; i < nx; i++) nrm_store_one(out_dtype, h_alpha, (size_t)(i * ny + y) * nc + c, s);
 		}
+}
+
+// ---- the front half: lcpm, compute_var, qc_reads (nrm_host_front.hip) ---------------------------------------------------------------------------------------
+// lcpm's two tables from the digamma values (lcpm.py:107,158): tab[x] = psi(1 + x) - psi(t0), etab[x] = exp(tab[x]) -- exp() once per table entry -- and
+// unit = max over x >= 1 of (etab[x] - etab[0]) / x, the bound of one stored entry's term in nrm_lcpm_csr_colsum's fixed-point sum (0 for a table of one entry)
+static inline double nrm_lcpm_tables(const double* psi, double psi_t0, int64_t len, std::vector<double>& tab, std::vector<double>& etab) {
+	tab.resize((size_t)len);
+	etab.resize((size_t)len);
+	for (int64_t x = 0; x < len; x++) {
+		tab[(size_t)x] = psi[x] - psi_t0;
+		etab[(size_t)x] = std::exp(tab[(size_t)x]);
+	}
+	double unit = 0.0;
+	for (int64_t x = 1; x < len; x++) {
+		const double u = (etab[(size_t)x] - etab[0]) / (double)x;
+		unit = u > unit ? u : unit;
+	}
+	return unit;
+}
+// lcpm's three covariate rows from the integer totals (lcpm.py:194-200): cov (3, n) = ln total, genes without a read, ln^2 total.  Returns the first cell
+// without a read (lcpm.py:196 raises for it; its column is left unwritten), -1 when every cell has one
+static inline int64_t nrm_lcpm_cov_rows(const int64_t* cell_total, const int64_t* cell_nnz, int64_t rows, int64_t n, double* cov) {
+	for (int64_t k = 0; k < n; k++) {
+		if (cell_total[k] <= 0) return k;
+		const double t = std::log((double)cell_total[k]);
+		cov[k] = t;
+		cov[n + k] = (double)(rows - cell_nnz[k]);
+		cov[2 * n + k] = t * t;
+	}
+	return -1;
+}
+// (x x^T)^+ for x (r, n), 1 <= r <= 64, on rows scaled to unit length: D pinv(D x x^T D) D with D = diag(1 / |row|), all-zero rows left as they are
+// (norm._pinv_gram_unit_rows: the rank rule, relative to the largest eigenvalue, then does not depend on the units of the rows).  The Jacobi routine of
+// nrm_fitvar_pinv_host, one lane.  *rank = the eigenvalues kept
+static inline void nrm_pinv_gram_unit_rows(const double* x, int64_t r, int64_t n, double tol, double* inv, int64_t* rank) {
+	std::vector<double> d((size_t)r), xs((size_t)r * n), a((size_t)(2 * r * r + 3 * r));
+	for (int64_t i = 0; i < r; i++) {
+		double s = 0.0;
+		for (int64_t k = 0; k < n; k++) s += x[i * n + k] * x[i * n + k];
+		s = std::sqrt(s);
+		d[(size_t)i] = 1.0 / (s > 0 ? s : 1.0);
+		for (int64_t k = 0; k < n; k++) xs[(size_t)(i * n + k)] = x[i * n + k] * d[(size_t)i];
+	}
+	nrm_covariate_gram(xs.data(), r, n, a);
+	a.resize((size_t)(2 * r * r + 3 * r));
+	nrm_pinv_lanes(NrmSerialLanes(), a.data(), a.data() + r * r, a.data() + 2 * r * r, a.data() + 2 * r * r + r, (int)r, tol, inv, rank);
+	for (int64_t i = 0; i < r; i++)
+		for (int64_t j = 0; j < r; j++) inv[i * r + j] *= d[(size_t)i] * d[(size_t)j];  // (symmetric to the bit, as the routine's own result)
+}
+// the six integer thresholds of one qc_reads iteration on nt genes x ns cells still alive (qc.py:56-71): a count is an integer, so `count >= bound` with a
+// double bound is `count >= ceil(bound)`; the proportional bounds are taken of the CURRENT numbers.  params = n_gene, nc_gene, ncp_gene, n_cell, nt_cell, ntp_cell
+static inline void nrm_qc_thresholds(const double* params, int64_t nt, int64_t ns, int64_t* thr) {
+	thr[0] = (int64_t)std::ceil(params[0]);
+	thr[1] = (int64_t)std::ceil(params[1]);
+	thr[2] = (int64_t)std::ceil(params[2] * (double)ns);
+	thr[3] = (int64_t)std::ceil(params[3]);
+	thr[4] = (int64_t)std::ceil(params[4]);
+	thr[5] = (int64_t)std::ceil(params[5] * (double)nt);
 }

@@ -156,6 +156,54 @@ def _takes_csr(d):
 	return d.nnz <= SPARSE_MAX_DENSITY * d.shape[0] * d.shape[1]
 
 
+_NP_CODES = {'int64': _lib.NRM_I64, 'int32': _lib.NRM_I32, 'int16': _lib.NRM_I16, 'uint8': _lib.NRM_U8}
+
+
+def _entry_counts(d, check=True):
+	"""A host count matrix as the whole-problem entries read it (include/normalisr_hip.h: nrm_lcpm_host, nrm_qc_reads_host and their CSR forms): the three arrays
+	of canonical_csr for a scipy.sparse matrix that takes the CSR kernels (_takes_csr), else a C-contiguous dense array of int64 / int32 / int16 / uint8 -- those
+	four as they are, anything else through _host_counts.  ValueError for a negative entry seen here (check=False: a dense matrix is not looked at, as
+	scaling_factor does not look: lcpm.py:258 counts zeros whatever else the matrix holds)."""
+	if _is_sparse(d):
+		if _takes_csr(d):
+			return canonical_csr(d)
+		if check and d.data.size and d.dtype.kind not in 'ub' and d.data.min() < 0:
+			raise ValueError('Negative value in d detected.')
+		d = d.toarray()  # (densified on the host, as lcpm.py:134-137 does)
+	d = np.asarray(d)
+	if str(d.dtype) in _NP_CODES:
+		return np.ascontiguousarray(d)
+	d, neg = _host_counts(d)
+	if neg and check:
+		raise ValueError('Negative value in d detected.')
+	return d
+
+
+def _vp(a):
+	return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _lcpm_host_entry(d, shape, normalize=True, ntot=None, otype=None, nocov=True, want_zero=False):
+	"""lcpm and scaling_factor's zero counts through nrm_lcpm_host / nrm_lcpm_csr_host: host buffers in and out, no torch, one upload for both.  d: what
+	_entry_counts returns; otype None: the integer pass alone.  Returns (lcpm or None, cov or None, zero entries per gene or None, sum, maximum)."""
+	lib = _lib.load()
+	nt, ns = (int(v) for v in shape)
+	out = None
+	if otype is not None:
+		from .association import _result
+		out = _result((nt, ns), otype)  # (page-locked, recycled)
+	cov = None if nocov else np.empty((3, ns), dtype=np.float64)
+	zero = np.empty(nt, dtype=np.int64) if want_zero else None
+	info = np.zeros(2, dtype=np.int64)
+	tail = (1 if normalize else 0, -1 if ntot is None else int(ntot), _vp(out), _engine.dtype_code(np.float64 if otype is None else otype), _vp(cov), _vp(zero), _vp(info))
+	if isinstance(d, tuple):
+		indptr, indices, data = d
+		_lib.check(lib.nrm_lcpm_csr_host(_vp(indptr), _vp(indices), _vp(data), _NP_CODES[str(data.dtype)], nt, ns, int(data.size), *tail))
+	else:
+		_lib.check(lib.nrm_lcpm_host(_vp(d), _NP_CODES[str(d.dtype)], nt, ns, *tail))
+	return out, cov, zero, int(info[0]), int(info[1])
+
+
 def _ready_csr(eng, c):
 	"""(_Csr, has a negative entry on this side) of a DeviceCSR: index tensors cast on the device to the widths the kernels read, the values to a count dtype."""
 	torch = eng.torch
@@ -220,13 +268,15 @@ class _Counts:
 			raise ValueError(MALFORMED_CSR)
 
 
-def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=True, nocov=False, device_out=False, out_dtype=None):
+def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=True, nocov=False, device_out=False, out_dtype=None, _scale=False):
 	"""Bayesian logCPM from raw read counts, same contract as reference lcpm.py:21-208: returns (lcpm, mean, var, cov).
 	reads: (n_gene, n_cell) counts -- a numpy array of any integer dtype (or floats holding integers), a scipy.sparse matrix (densified on the host) or a torch
 	CUDA integer tensor already in HBM.  nth and seed are accepted for compatibility and ignored.  varscale != 0 resamples from numpy's global random stream in
 	the reference and is not provided: NotImplementedError.
 	out_dtype: None / numpy.float64 (the reference's) or numpy.float32 (the fp64 value rounded once, at the store).  device_out=True leaves lcpm (and mean, var)
-	in HBM as torch tensors -- what compute_var and normvar take next; cov is always a (3, n_cell) numpy array (None with nocov)."""
+	in HBM as torch tensors -- what compute_var and normvar take next; cov is always a (3, n_cell) numpy array (None with nocov).
+	Host input in a process without torch (or with NRM_HOST_ENTRY=1, or from the command line) goes through the library's whole-problem entries (nrm_lcpm_host,
+	nrm_lcpm_csr_host): numpy and the library suffice.  _scale=True (the command line, on that route only) appends scaling_factor(reads) from the same call."""
 	d = _as_device_csr(reads) or reads
 	if d.ndim != 2:
 		raise ValueError('reads must have 2 dimensions.')
@@ -253,6 +303,16 @@ def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=
 		assert ntot + 2 > 2
 		if nt * ns == 0:
 			raise ValueError('reads must not be empty.')
+	if not _engine.is_dev(d):
+		from .association import _use_host_entry
+		if _use_host_entry():
+			# no torch in this process (or the command line / NRM_HOST_ENTRY=1): the library's whole-problem entries, numpy buffers in and out
+			if device_out:
+				raise RuntimeError('device_out=True returns torch tensors: torch is needed for it.')
+			raw = reads if not _is_sparse(reads) and str(getattr(reads, 'dtype', '')) in _NP_CODES else d  # (int16 and uint8 counts go as they are)
+			dtn, dcov, zeros = _lcpm_host_entry(_entry_counts(raw), (nt, ns), normalize, ntot, otype, nocov, want_zero=_scale)[:3]
+			ans = (dtn, None, None, dcov) if lowmem else (dtn, dtn.copy(), np.zeros((nt, ns), dtype=otype), dcov)
+			return ans + (_rescale(zeros / float(ns), 0, 'max', nt), ) if _scale else ans
 	eng = _engine.get_engine(d.device.index if _engine.is_dev(d) else None)
 	with eng.lock:
 		torch = eng.torch
@@ -319,7 +379,8 @@ def lcpm(reads, normalize=True, nth=0, ntot=None, varscale=0, seed=None, lowmem=
 def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
 	"""Scaling factor of variance normalisation for every gene, same contract as reference lcpm.py:211-283.
 	dt: the read-count matrix, a numpy array or a torch CUDA integer tensor.  The default variable (the share of zero entries per gene) is counted on the
-	device (nrm_lcpm_count); the other four are whole-matrix numpy expressions and run on the host."""
+	device (nrm_lcpm_count; for host input without torch through nrm_lcpm_host / nrm_lcpm_csr_host); the other four are whole-matrix numpy expressions and run on
+	the host, without torch for host input."""
 	dt = _as_device_csr(dt) or dt
 	if dt.ndim != 2:
 		raise ValueError('dt must have 2 dimensions.')
@@ -328,10 +389,14 @@ def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
 	if varname not in ('logtpropmean', 'logtmeanprop', 'nt0mean', 'lognt0mean', 'log1-nt0mean'):
 		raise ValueError('Unknown varname: {}'.format(varname))
 	if varname == 'nt0mean':
-		eng = _engine.get_engine(dt.device.index if _engine.is_dev(dt) else None)
-		with eng.lock, eng.torch.cuda.device(eng.device):
-			x, code, _ = _device_counts(eng, dt)
-			zeros = _Counts(eng, x, code).h_gene_zero
+		from .association import _use_host_entry
+		if not _engine.is_dev(dt) and dt.shape[0] * dt.shape[1] > 0 and _use_host_entry():
+			zeros = _lcpm_host_entry(_entry_counts(dt, check=False), dt.shape, want_zero=True)[2]  # (the integer pass alone)
+		else:
+			eng = _engine.get_engine(dt.device.index if _engine.is_dev(dt) else None)
+			with eng.lock, eng.torch.cuda.device(eng.device):
+				x, code, _ = _device_counts(eng, dt)
+				zeros = _Counts(eng, x, code).h_gene_zero
 		d = zeros / float(dt.shape[1])  # (dt == 0).mean(axis=1)
 	else:
 		if isinstance(dt, DeviceCSR):  # (these four are whole-matrix numpy expressions: dense on the host)
@@ -349,6 +414,11 @@ def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
 				d = np.log((h == 0).mean(axis=1))
 			else:
 				d = np.log(1 - (h == 0).mean(axis=1))
+	return _rescale(d, v0, v1, dt.shape[0])
+
+
+def _rescale(d, v0, v1, nt):
+	"""scaling_factor's variable d (n_gene,) mapped linearly so that v0 -> 0 and v1 -> 1 ('max' / 'min': of d; lcpm.py:268-283)."""
 	ans = []
 	for v in [v0, v1]:
 		if isinstance(v, str) and v == 'max':
@@ -360,7 +430,7 @@ def scaling_factor(dt, varname='nt0mean', v0=0, v1='max'):
 	v0, v1 = ans
 	assert v1 != v0
 	ans = (d - v0) / (v1 - v0)
-	assert ans.shape == (dt.shape[0], )
+	assert ans.shape == (nt, )
 	assert np.isfinite(ans).all()
 	return ans
 

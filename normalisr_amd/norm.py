@@ -467,11 +467,33 @@ def _projector(x):
 	return lambda z: np.matmul(np.matmul(mi, np.matmul(x, z)), x)
 
 
+def _compute_var_host_entry(dt, c64, stepmax, eps):
+	"""compute_var through nrm_compute_var_host (include/normalisr_hip.h): host buffers in and out, no torch, the pseudo-inverse of [dc;1][dc;1]^T from the
+	library's Jacobi routine -- what `normalisr fitvar` needs in a process that has numpy and the library only.  Returns (weights, best change, steps taken).
+	NotImplementedError beyond 63 covariates (a pseudo-inverse larger than that routine takes; the caller then takes the torch engine if there is one);
+	AssertionError for what compute_var asserts (norm.py:125-127)."""
+	import ctypes
+	lib = _lib.load()
+	y = _engine.as_input(dt)
+	nt, ns = y.shape
+	nc = c64.shape[0]
+	if nc > 63:
+		raise NotImplementedError('compute_var without torch takes 1 to 63 covariates ({} given): the pseudo-inverse of [dc;1][dc;1]^T comes from the library\'s Jacobi '
+								  'routine of at most 64 rows.'.format(nc))
+	w, state = np.empty(ns, dtype=np.float64), np.zeros(2, dtype=np.float64)
+	vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+	_lib.check(lib.nrm_compute_var_host(vp(y), _engine.dtype_code(y), nt, ns, vp(c64), nc, int(stepmax), float(eps), vp(w), vp(state)))
+	logging.debug('Step {}, best maximum relative difference: {}'.format(int(state[1]), state[0]))
+	return w, float(state[0]), int(state[1])
+
+
 def compute_var(dt, dc, stepmax=1, eps=1E-6):
 	"""Variance-normalisation multiplier of every cell, same contract as reference norm.py:56-128 (`normalisr fitvar`): returns (n_cell,) weights >= 1.
 	dt: (n_gene, n_cell) logCPM, fp32 or fp64, a numpy array or a torch CUDA tensor already in HBM (lcpm(..., device_out=True)); dc (n_cov, n_cell), 1 to 63
 	rows, or up to nrm_wide_covariates() (1024) with more cells than covariates (csrc/nrm_fitvar.hip: the coefficient table in dynamic LDS), rank-deficient sets included (both projections take the pseudo-inverse of inv_rank).  AssertionError for a gene whose residual is constant (the
-	reference divides by its zero spread, norm.py:108, and fails norm.py:125)."""
+	reference divides by its zero spread, norm.py:108, and fails norm.py:125).
+	Host input in a process without torch (or with NRM_HOST_ENTRY=1, or from the command line) goes through the library's whole-problem entry
+	nrm_compute_var_host, 1 to 63 covariates: numpy and the library suffice; beyond 63 it needs the torch engine."""
 	if eps <= 0 or stepmax <= 0:
 		raise ValueError('eps and stepmax must be positive.')
 	if not _engine.is_dev(dt):
@@ -490,6 +512,16 @@ def compute_var(dt, dc, stepmax=1, eps=1E-6):
 	if nt == 0 or ns == 0:
 		raise ValueError('dt must not be empty.')
 	c64 = np.ascontiguousarray(dc, dtype=np.float64)
+	if not _engine.is_dev(dt):
+		from .association import _use_host_entry
+		if _use_host_entry():
+			# no torch in this process (or the command line / NRM_HOST_ENTRY=1): the library's whole-problem entry, numpy buffers in and out
+			try:
+				return _compute_var_host_entry(dt, c64, stepmax, eps)[0]
+			except NotImplementedError:
+				from .association import _have_torch
+				if not _have_torch():
+					raise
 	fit_log = _projector(np.concatenate([c64, np.ones((1, ns))], axis=0))  # the second regression has an intercept (norm.py:92,109-110)
 	eng = _engine.get_engine(dt.device.index if _engine.is_dev(dt) else None)
 	with eng.lock:

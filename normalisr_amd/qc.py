@@ -89,6 +89,33 @@ def qc_thresholds(params, nt, ns):
 	return (math.ceil(n_gene), math.ceil(nc_gene), math.ceil(ncp_gene * ns), math.ceil(n_cell), math.ceil(nt_cell), math.ceil(ntp_cell * nt))
 
 
+def _qc_reads_host_entry(d, params, return_info):
+	"""qc_reads through nrm_qc_reads_host / nrm_qc_reads_csr_host (include/normalisr_hip.h): host buffers in and out, no torch.  d: a dense count array as
+	_host_counts leaves it, or a scipy.sparse matrix (canonical CSR whatever its density, never densified)."""
+	lib = _lib.load()
+	nt_all, ns_all = (int(v) for v in d.shape)
+	gm, cm = np.empty(nt_all, dtype=np.uint8), np.empty(ns_all, dtype=np.uint8)
+	info = np.zeros(3, dtype=np.int64)
+	vp = _lcpm._vp
+	tail = tuple(float(v) for v in params) + (vp(gm), vp(cm), vp(info))
+	if _lcpm._is_sparse(d):
+		indptr, indices, data = _lcpm.canonical_csr(d)
+		_lib.check(lib.nrm_qc_reads_csr_host(vp(indptr), vp(indices), vp(data), _lcpm._NP_CODES[str(data.dtype)], nt_all, ns_all, int(data.size), *tail))
+	else:
+		_lib.check(lib.nrm_qc_reads_host(vp(d), _lcpm._NP_CODES[str(d.dtype)], nt_all, ns_all, *tail))
+	it, nt, ns = (int(v) for v in info)
+	if nt == 0:
+		raise RuntimeError('All genes removed in QC.')
+	if ns == 0:
+		raise RuntimeError('All cells removed in QC.')
+	gm, cm = gm != 0, cm != 0
+	genes, cells = np.flatnonzero(gm).astype(np.int64), np.flatnonzero(cm).astype(np.int64)
+	logging.info('Removed {}/{} genes and {}/{} cells in QC.'.format(nt_all - nt, nt_all, ns_all - ns, ns_all))
+	if return_info:
+		return (genes, cells, dict(iterations=it, gene_mask=gm, cell_mask=cm))
+	return (genes, cells)
+
+
 def qc_reads(reads, n_gene, nc_gene, ncp_gene, n_cell, nt_cell, ntp_cell, device_out=False, return_info=False):
 	"""Quality control by lower bounds on read counts, same contract as reference qc.py:4-85: returns (genes_select, cells_select), the int64 indices of the
 	genes and cells that pass.  A gene needs n_gene reads, nc_gene expressing cells and the share ncp_gene of the cells expressing it; a cell needs n_cell
@@ -99,7 +126,9 @@ def qc_reads(reads, n_gene, nc_gene, ncp_gene, n_cell, nt_cell, ntp_cell, device
 	device_out=True returns the two index arrays as torch CUDA tensors.  return_info=True appends a dict: iterations (passes over the matrix), gene_mask and
 	cell_mask (the final boolean masks, numpy or torch as the indices).
 	Deviation from the reference: a negative entry raises ValueError (the reference sums it silently; lcpm rejects such a matrix anyway).
-	RuntimeError when no gene or no cell is left, genes checked first (qc.py:78-81)."""
+	RuntimeError when no gene or no cell is left, genes checked first (qc.py:78-81).
+	Host input in a process without torch (or with NRM_HOST_ENTRY=1, or from the command line) goes through the library's whole-problem entries
+	nrm_qc_reads_host / nrm_qc_reads_csr_host: numpy and the library suffice."""
 	d = _lcpm._as_device_csr(reads) or reads
 	params = (n_gene, nc_gene, ncp_gene, n_cell, nt_cell, ntp_cell)
 	_check_qc_reads_args(d.ndim, params)
@@ -120,6 +149,13 @@ def qc_reads(reads, n_gene, nc_gene, ncp_gene, n_cell, nt_cell, ntp_cell, device
 			sel = tuple(eng.upload(v) for v in sel)
 		mask = sel[0] != 0
 		return sel + ((dict(iterations=0, gene_mask=mask, cell_mask=mask), ) if return_info else ())
+	if not _engine.is_dev(d):
+		from .association import _use_host_entry
+		if _use_host_entry():
+			# no torch in this process (or the command line / NRM_HOST_ENTRY=1): the library's whole-problem entries, numpy buffers in and out
+			if device_out:
+				raise RuntimeError('device_out=True returns torch tensors: torch is needed for it.')
+			return _qc_reads_host_entry(d, params, return_info)
 	eng = _engine.get_engine(d.device.index if _engine.is_dev(d) else None)
 	with eng.lock:
 		torch = eng.torch
@@ -256,6 +292,23 @@ def _subset_dense(eng, x, genes, cells):
 	return out
 
 
+def _subset_host(m, rows, cols, sparse_in):
+	"""subset of a host matrix by numpy / scipy indexing, for a process without torch: the same checks, errors and results as the device route (a scipy matrix
+	goes through canonical_csr first, as there).  rows, cols: int64 index arrays already checked by _selection, None = the whole axis."""
+	rows = slice(None) if rows is None else rows
+	cols = slice(None) if cols is None else cols
+	if sparse_in:
+		import scipy.sparse
+		indptr, indices, data = _lcpm.canonical_csr(m)
+		out = scipy.sparse.csr_matrix((data, indices, indptr), shape=m.shape)[rows][:, cols].tocsr()
+		out.sort_indices()
+		return out.astype(m.dtype, copy=False)
+	a = np.ascontiguousarray(m)
+	if a.dtype.itemsize not in (1, 2, 4, 8) or a.dtype.kind not in 'biuf':
+		raise TypeError('subset copies integer and floating-point elements of 1, 2, 4 or 8 bytes.')
+	return np.ascontiguousarray(a[rows][:, cols])
+
+
 def subset(m, genes=None, cells=None, device_out=False):
 	"""m[genes][:, cells] on the device: what follows qc_reads and qc_outlier in the pipeline.
 	m: a dense (n_gene, n_cell) matrix -- a numpy array or a torch CUDA tensor of int64, int32, int16, uint8, float32 or float64 (any dtype of 1, 2, 4 or 8
@@ -264,7 +317,9 @@ def subset(m, genes=None, cells=None, device_out=False):
 	matrix both selections must increase strictly -- what qc_reads returns -- and ValueError otherwise; the result is canonical CSR and stored zeros stay
 	stored.
 	Returns the input's kind: numpy for numpy, a torch tensor for a torch tensor, scipy CSR for scipy, torch.sparse_csr for torch.sparse_csr, DeviceCSR for
-	DeviceCSR.  device_out=True leaves the result in HBM instead: a torch tensor, or a DeviceCSR for every sparse form."""
+	DeviceCSR.  device_out=True leaves the result in HBM instead: a torch tensor, or a DeviceCSR for every sparse form.
+	Host input with host selections in a process without torch (or with NRM_HOST_ENTRY=1, or from the command line) is indexed on the host by numpy / scipy,
+	with the same checks, errors and results; it needs no device."""
 	d = _lcpm._as_device_csr(m)
 	sparse_in = d is not None or _lcpm._is_sparse(m)
 	src = d if d is not None else m
@@ -276,6 +331,10 @@ def subset(m, genes=None, cells=None, device_out=False):
 		for (h, t), what in zip(sel, ('genes', 'cells')):
 			if h is not None and h.size > 1 and not (np.diff(h) > 0).all():
 				raise ValueError('{} of a sparse matrix must increase strictly.'.format(what))
+	if not _engine.is_dev(src) and not device_out and all(t is None for _, t in sel):
+		from .association import _have_torch
+		if _lib.host_entry_preferred() or not _have_torch():
+			return _subset_host(m, sel[0][0], sel[1][0], sparse_in)  # (no torch in this process, or the command line: indexing on the host needs no device)
 	eng = _engine.get_engine(src.device.index if _engine.is_dev(src) else None)
 	with eng.lock:
 		torch = eng.torch

@@ -199,21 +199,32 @@ def file_read_coo(f):
 
 def _call_lcpm(m, ka):
 	"""lcpm and scaling_factor on one upload of the counts; the covariates of -c come first in cov_out (run.py:153-189)."""
-	from .lcpm import lcpm, scaling_factor, DeviceCSR, _takes_csr
-	from . import engine as _engine
+	from .lcpm import lcpm, scaling_factor, _takes_csr
+	from .association import _use_host_entry
 	d = m['reads_in']
-	if hasattr(d, 'toarray') and _takes_csr(d):
-		x = DeviceCSR.from_scipy(d)  # (`lcpm -s`: the stored entries only, uploaded once for both calls)
+	if _use_host_entry():
+		# one call of the library's whole-problem entry per input: lcpm and the zero counts scaling_factor needs, torch not imported
+		if not hasattr(d, 'toarray'):
+			d = np.asarray(d)
+			if d.dtype.kind == 'f':
+				d = d.astype(np.int64)  # the reference reads the file with dtype=int (run.py:157-159)
+		ans = lcpm(d, _scale=True, **ka)
+		sf = ans[4]
 	else:
-		if hasattr(d, 'toarray'):
-			d = d.toarray()
-		d = np.asarray(d)
-		if d.dtype.kind == 'f':
-			d = d.astype(np.int64)  # the reference reads the file with dtype=int (run.py:157-159)
-		eng = _engine.get_engine()
-		x = eng.upload(d if d.dtype in (np.int32, np.int64) else d.astype(np.int64))
-	ans = lcpm(x, **ka)
-	sf = scaling_factor(x)
+		from .lcpm import DeviceCSR
+		from . import engine as _engine
+		if hasattr(d, 'toarray') and _takes_csr(d):
+			x = DeviceCSR.from_scipy(d)  # (`lcpm -s`: the stored entries only, uploaded once for both calls)
+		else:
+			if hasattr(d, 'toarray'):
+				d = d.toarray()
+			d = np.asarray(d)
+			if d.dtype.kind == 'f':
+				d = d.astype(np.int64)  # the reference reads the file with dtype=int (run.py:157-159)
+			eng = _engine.get_engine()
+			x = eng.upload(d if d.dtype in (np.int32, np.int64) else d.astype(np.int64))
+		ans = lcpm(x, **ka)
+		sf = scaling_factor(x)
 	cov = ans[3] if m.get('cov_in') is None else np.concatenate([m['cov_in'], ans[3]], axis=0)
 	return (ans[0], sf, cov, ans[2])
 
@@ -256,7 +267,7 @@ COMMANDS = {
 def run(cmd, args):
 	"""Run sub-command `cmd` with the parsed command line `args` (a dict of argparse destinations)."""
 	spec = COMMANDS[cmd]
-	if cmd in ('de', 'coex', 'binnet', 'bh', 'normvar'):
+	if cmd in ('de', 'coex', 'binnet', 'bh', 'normvar', 'lcpm', 'normcov', 'fitvar'):
 		# files in, files out, one GPU: the library's whole-problem entries (include/normalisr_hip.h) do everything these commands need -- same kernels,
 		# same results -- and torch's import (1.0 of a 1.3 s call) is not paid; NRM_HOST_ENTRY=0 keeps the torch engine.  Calls the entries do not
 		# cover fall back to it by themselves.
@@ -302,7 +313,22 @@ de, coex, normvar, binnet, bh, lcpm, normcov, fitvar = (_runner(c) for c in ('de
 
 
 # ---- quality control: qc_reads, subset, qc_outlier (reference run.py:48-150,220-234) -----------------------------------------------------------------------
-# These three read and write name lists beside the matrices, so they are functions of their own, not rows of COMMANDS.  They import torch (the engine).
+# These three read and write name lists beside the matrices, so they are functions of their own, not rows of COMMANDS.  Like run() they prefer the library's
+# whole-problem entries (nrm_qc_reads_host, nrm_qc_reads_csr_host; subset and qc_outlier are numpy on the host): torch is not imported unless NRM_HOST_ENTRY=0.
+
+def _prefers_host_entry(f):
+	import functools
+
+	@functools.wraps(f)
+	def g(args):
+		from . import _lib
+		prev = _lib.prefer_host_entry(True)
+		try:
+			return f(args)
+		finally:
+			_lib.prefer_host_entry(prev)
+	return g
+
 
 def file_read_txtlist(f, **ka):
 	"""The names in a text file, one per line, as a numpy array of strings: surrounding blanks stripped, empty lines dropped."""
@@ -339,6 +365,7 @@ def _read_sparse_counts(f):
 	return file_read_coo(f).astype(int, copy=False)
 
 
+@_prefers_host_entry
 def qc_reads(args):
 	"""normalisr qc_reads: the names of the genes and cells that pass (reference run.py:70-97).  With -s the Matrix Market counts are uploaded as CSR and stay
 	sparse on the device."""
@@ -370,6 +397,7 @@ def _name_positions(files, size, what):
 	return np.array([where[name] for name in after], dtype=np.int64)
 
 
+@_prefers_host_entry
 def subset(args):
 	"""normalisr subset: matrix_in cut down to the named rows and columns (reference run.py:100-150).  A dense matrix goes through the gather kernel, names in any
 	order; -s with names in their original order goes through the CSR subset and is densified for the text output, -s with any other order is indexed on the
@@ -400,6 +428,7 @@ def subset(args):
 	file_write_tsv(args['matrix_out'], out, fmt=fmt_int if np.issubdtype(out.dtype, np.integer) else fmt_float)
 
 
+@_prefers_host_entry
 def qc_outlier(args):
 	"""normalisr qc_outlier: the names of the cells whose fitted weight is no outlier (reference run.py:220-234)."""
 	from . import qc
