@@ -1,14 +1,15 @@
 """The child side of tests/test_gpu_coex_plan.py: a process in which torch cannot be imported makes every call on the library's resident coex plan
 (normalisr_amd.cplan, normalisr_amd._lib) and writes what it got to an .npz; the parent compares.  `python tests/coex_plan_child.py SCENARIO IN.npz OUT.npz`.
-The input generators at the top are shared with the parent (which imports this module; nothing here touches torch)."""
+The input generators at the top are shared with the parent (which imports this module; nothing here touches torch); the frame of the child and the adopted matrix
+are those of tests/cabi_harness.py."""
 import ctypes
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cabi_harness as h
+
+ROOT = h.ROOT
 
 
 def spike_rows(rng, rows, n):
@@ -37,27 +38,7 @@ def expression(seed, ng, n, dtype):
 
 # ---- the child ------------------------------------------------------------------------------------------------------------------------------------------------
 def _store(out, name, tag, res):
-	for k, v in zip(('p', 'dot', 'var'), res):
-		out['{}.{}{}'.format(name, k, tag)] = v
-
-
-def _pinned(lib, _lib, nbytes):
-	p = ctypes.c_void_p()
-	_lib.check(lib.nrm_host_alloc(ctypes.byref(p), nbytes))
-	return p.value
-
-
-def _adopted(lib, _lib, cplan, a, ld, stream):
-	"""`a` in device-visible memory of the library (nrm_host_alloc), filled through nrm_upload, with row pitch ld -> (DeviceMatrix, rewrite(values, stream))."""
-	rows, n = a.shape
-	ptr = _pinned(lib, _lib, rows * ld * a.itemsize)
-
-	def fill(values, st):
-		h = np.zeros((rows, ld), dtype=a.dtype)
-		h[:, :n] = values
-		_lib.check(lib.nrm_upload(h.ctypes.data, ptr, h.nbytes, 0, st))
-	fill(a, stream)
-	return cplan.DeviceMatrix(ptr, (rows, n), a.dtype, ld), fill
+	h.store(out, name, res, h.COEX_KEYS, tag)
 
 
 def scenario_cases(job, arr, out, lib, _lib, cplan):
@@ -77,7 +58,7 @@ def scenario_rewrite(job, arr, out, lib, _lib, cplan):
 	infos = {}
 	# an adopted matrix, rewritten in place behind the third step on the plan's stream
 	a, b, dc = arr['a'], arr['b'], arr['dc']
-	dm, fill = _adopted(lib, _lib, cplan, a, a.shape[1], None)
+	dm, fill = h.adopted_matrix(a, a.shape[1], None)
 	with cplan.CoexPlan(dm, dc) as plan:
 		for _ in range(3):
 			plan.step()
@@ -86,25 +67,21 @@ def scenario_rewrite(job, arr, out, lib, _lib, cplan):
 		plan.step()
 		_store(out, 'adopted', '_new', plan.results())
 		infos['adopted'] = plan.info()
-		try:
-			plan.update(b)
-			infos['adopted_update'] = 'accepted'
-		except ValueError as e:
-			infos['adopted_update'] = str(e)
+		infos['adopted_update'] = h.update_refused(plan, b)
 		infos['adopted_upload_rc'] = int(lib.nrm_coex_plan_upload(plan._handle(), np.ascontiguousarray(b).ctypes.data))  # the library's own refusal
 		infos['adopted_upload_msg'] = lib.nrm_last_error().decode()
 	with cplan.CoexPlan(b, dc) as plan:
 		_store(out, 'adopted', '_fresh', plan.step().results())
-	_lib.check(lib.nrm_host_free(dm.ptr))
+	h.free([dm.ptr])
 	# an adopted matrix whose rows are 16-byte aligned but not contiguous (ld = n + 4): still the integer engine
 	a, b, dc = arr['a'], arr['b'], arr['dc']
-	dm, fill = _adopted(lib, _lib, cplan, b, b.shape[1] + 4, None)
+	dm, fill = h.adopted_matrix(b, b.shape[1] + 4, None)
 	with cplan.CoexPlan(dm, dc) as plan:
 		for _ in range(3):
 			plan.step()
 		_store(out, 'padded', '', plan.results())
 		infos['padded'] = plan.info()
-	_lib.check(lib.nrm_host_free(dm.ptr))
+	h.free([dm.ptr])
 	# update() on a plan-owned copy
 	a, b, dc = arr['a2'], arr['b2'], arr['dc2']
 	with cplan.CoexPlan(a, dc) as plan:
@@ -117,13 +94,13 @@ def scenario_rewrite(job, arr, out, lib, _lib, cplan):
 		_store(out, 'owned', '_fresh', plan.step().results())
 	# a pitch that is no multiple of 4: the fp64 kernel even at 4096 cells
 	a, dc = arr['a3'], arr['dc3']
-	dm, fill = _adopted(lib, _lib, cplan, a, a.shape[1] + 2, None)
+	dm, fill = h.adopted_matrix(a, a.shape[1] + 2, None)
 	with cplan.CoexPlan(dm, dc) as plan:
 		for _ in range(3):
 			plan.step()
 		_store(out, 'pitched', '', plan.results())
 		infos['pitched'] = plan.info()
-	_lib.check(lib.nrm_host_free(dm.ptr))
+	h.free([dm.ptr])
 	return infos
 
 
@@ -148,19 +125,19 @@ def scenario_chain(job, arr, out, lib, _lib, cplan):
 	ng = dt.shape[0]
 	with cplan.CoexPlan(dt, dc) as plan:
 		res = plan.device_results()
-		h = _pinned(lib, _lib, ng * ng + 32)  # the network, then the total (8 bytes) and, at +16, the flags
-		h_cnt = h + ng * ng
+		mem = h.pinned(ng * ng + 32)  # the network, then the total (8 bytes) and, at +16, the flags
+		h_cnt = mem + ng * ng
 		for _ in range(3):  # the third is a replay
 			plan.step()
 			_lib.check(lib.nrm_fill_zero(h_cnt, 32, res['stream']))
-			_lib.check(lib.nrm_binnet(res['p'], _lib.NRM_F64 if res['dtype'] == np.float64 else _lib.NRM_F32, ng, res['ld'], qcut, h, ng, h_cnt, h_cnt + 16, res['stream']))
+			_lib.check(lib.nrm_binnet(res['p'], _lib.NRM_F64 if res['dtype'] == np.float64 else _lib.NRM_F32, ng, res['ld'], qcut, mem, ng, h_cnt, h_cnt + 16, res['stream']))
 		plan.check()  # (waits for everything queued)
-		out['net'] = np.frombuffer(ctypes.string_at(h, ng * ng), dtype=np.uint8).reshape(ng, ng).copy()
+		out['net'] = np.frombuffer(ctypes.string_at(mem, ng * ng), dtype=np.uint8).reshape(ng, ng).copy()
 		tail = ctypes.string_at(h_cnt, 32)
 		out['total'] = np.frombuffer(tail[:8], dtype=np.uint64).copy()
 		out['flags'] = np.frombuffer(tail[16:24], dtype=np.int32).copy()
 		info = plan.info()
-	_lib.check(lib.nrm_host_free(h))
+	h.free([mem])
 	return info
 
 
@@ -171,11 +148,7 @@ def scenario_errors(job, arr, out, lib, _lib, cplan):
 	bad[3, 7] = np.nan
 	with cplan.CoexPlan(bad, dc) as plan:
 		plan.step().step().step()
-		try:
-			plan.check()
-			notes['nan'] = 'accepted'
-		except AssertionError as e:
-			notes['nan'] = 'AssertionError: ' + str(e)
+		notes['nan'] = h.raised(plan.check, catch=AssertionError)
 		plan.update(a).step()
 		_store(out, 'after_nan', '', plan.results())
 		notes['after_nan'] = plan.info()
@@ -221,21 +194,5 @@ def scenario_teardown(job, arr, out, lib, _lib, cplan):
 	return notes
 
 
-def main(argv):
-	sys.modules['torch'] = None  # `import torch` raises ImportError in this process
-	sys.path.insert(0, ROOT)
-	from normalisr_amd import _lib, cplan
-	scenario, src, dst = argv[1:4]
-	arr = np.load(src)
-	job = json.loads(str(arr['job']))
-	lib = _lib.load()
-	out = {}
-	notes = globals()['scenario_' + scenario](job, arr, out, lib, _lib, cplan)
-	assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]
-	out['notes'] = np.array(json.dumps(notes))
-	np.savez(dst, **out)
-	print('child ok')
-
-
 if __name__ == '__main__':
-	main(sys.argv)
+	h.child_main(sys.argv, globals())

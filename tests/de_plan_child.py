@@ -1,15 +1,14 @@
 """The child side of tests/test_gpu_de_plan.py: a process in which torch cannot be imported makes every call on the library's resident de plan
 (normalisr_amd.cplan.DePlan over nrm_de_plan_*) and writes what it got to an .npz; the parent compares.  `python tests/de_plan_child.py SCENARIO IN.npz OUT.npz`.
-The input generators at the top are shared with the parent (which imports this module; nothing here touches torch)."""
-import ctypes
-import json
-import os
+The input generators at the top are shared with the parent (which imports this module; nothing here touches torch); the frame of the child, the design forms and
+the cases / replays / handback scenarios are those of tests/cabi_harness.py."""
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KEYS = ('p', 'gamma', 'alpha', 'varg', 'vart')
+import cabi_harness as h
+
+ROOT, KEYS = h.ROOT, h.KEYS
 
 
 def screen(seed, dtype, nc, intercept=True, valued=False, full_rows=False, nx=70, ny=64, n=4100, const_rows=(9, )):
@@ -62,53 +61,6 @@ def handback_inputs():
 
 
 # ---- the child ------------------------------------------------------------------------------------------------------------------------------------------------
-def _store(out, name, res):
-	for k, v in zip(KEYS, res):
-		if v is not None:
-			out['{}.{}'.format(name, k)] = v
-
-
-def _pinned(lib, _lib, nbytes):
-	p = ctypes.c_void_p()
-	_lib.check(lib.nrm_host_alloc(ctypes.byref(p), max(int(nbytes), 16)))
-	return p.value
-
-
-def _device_copy(lib, _lib, a):
-	"""`a` in device-visible memory of the library (nrm_host_alloc), filled through nrm_upload: its address."""
-	a = np.ascontiguousarray(a)
-	ptr = _pinned(lib, _lib, a.nbytes)
-	if a.nbytes:
-		_lib.check(lib.nrm_upload(a.ctypes.data, ptr, a.nbytes, 0, None))
-	return ptr
-
-
-def _device_csr(lib, _lib, cplan, dg, ones):
-	"""The design as a cplan.DeviceCSR: canonical CSR from scipy, the three arrays uploaded by the library.  ones: no data array (every entry is 1)."""
-	import scipy.sparse
-	from normalisr_amd import de_sparse
-	indptr, indices, data = de_sparse.canonical_design_csr(scipy.sparse.csr_matrix(dg))
-	ptrs = [_device_copy(lib, _lib, indptr), _device_copy(lib, _lib, indices), None if ones else _device_copy(lib, _lib, data)]
-	return cplan.DeviceCSR(ptrs[0], ptrs[1], ptrs[2], dg.shape, indices.size, data.dtype), [p for p in ptrs if p]
-
-
-def _free(lib, _lib, ptrs):
-	for p in ptrs:
-		_lib.check(lib.nrm_host_free(p))
-
-
-def _design(form, dg, lib, _lib, cplan):
-	import scipy.sparse
-	if form == 'dense':
-		return dg, []
-	if form == 'scipy':
-		return scipy.sparse.csr_matrix(dg), []
-	if form == 'coo':
-		return scipy.sparse.coo_matrix(dg), []
-	binary = bool(((dg == 0) | (dg == 1)).all())
-	return _device_csr(lib, _lib, cplan, dg, ones=binary and form == 'devcsr')
-
-
 def _inputs(c, arr):
 	if 'small' in c:
 		return small_screen(**c['small'])
@@ -123,91 +75,19 @@ def _inputs(c, arr):
 
 
 def scenario_cases(job, arr, out, lib, _lib, cplan):
-	"""Every case: a plan on (dg, dt, dc) in each of the forms named, `steps` steps, the results (and q-values) of the last, info() at the end."""
-	infos = {}
-	for c in job['cases']:
-		dg, dt, dc = _inputs(c, arr)
-		for form in c.get('forms', ['dense']):
-			d, held = _design(form, dg, lib, _lib, cplan)
-			name = '{}.{}'.format(c['name'], form)
-			with cplan.DePlan(d, dt, dc, dimreduce=c.get('dimreduce', 0), lowmem=c.get('lowmem', True), q=c.get('q', False), out_dtype=c.get('out_dtype'),
-							  pinv=c.get('pinv', 'numpy')) as plan:
-				for _ in range(c.get('steps', 1)):
-					plan.step()
-				back = plan.check()
-				_store(out, name, plan.results())
-				if c.get('q'):
-					out[name + '.q'] = plan.qvalues()
-				infos[name] = dict(plan.info(), handed_back=back)
-			_free(lib, _lib, held)
-	return infos
+	return h.cases(cplan.DePlan, job, arr, out, _inputs, pinv=True)
 
 
 def scenario_replays(job, arr, out, lib, _lib, cplan):
-	"""Three steps, update(dt2) and two more, set_design(dg2) and two more: every step's results and info; fresh plans on the same inputs; an adopted expression
-	matrix rewritten in place behind a captured step."""
+	"""Three steps, update(dt2) and two more, set_design(dg2) and two more (cabi_harness.replays)."""
 	s = dict(job['screen'])
 	s['dtype'] = np.dtype(s['dtype'])
-	dg, dt, dc = screen(**s)
 	dg2, dt2, _ = screen(**dict(s, seed=s['seed'] + 1, const_rows=(20, 33)))
-	infos = {}
-	with cplan.DePlan(dg, dt, dc, lowmem=False) as plan:
-		k = 0
-		for what in ('step', 'step', 'step', 'update', 'step', 'design', 'step'):
-			if what == 'update':
-				plan.update(dt2)
-			elif what == 'design':
-				plan.set_design(_design(job['design_form'], dg2, lib, _lib, cplan)[0])
-			plan.step()
-			k += 1
-			_store(out, 'run{}'.format(k), plan.results())
-			infos['run{}'.format(k)] = plan.info()
-	for name, (g, t) in dict(fresh_a=(dg, dt), fresh_b=(dg, dt2), fresh_c=(dg2, dt2)).items():
-		with cplan.DePlan(g, t, dc, lowmem=False) as plan:
-			_store(out, name, plan.step().results())
-			infos[name] = plan.info()
-	# an adopted expression matrix with a row pitch, rewritten in place on the plan's stream
-	ny, n = dt.shape
-	ld = n + 4
-	ptr = _pinned(lib, _lib, ny * ld * dt.itemsize)
-
-	def fill(values, st):
-		h = np.zeros((ny, ld), dtype=dt.dtype)
-		h[:, :n] = values
-		_lib.check(lib.nrm_upload(h.ctypes.data, ptr, h.nbytes, 0, st))
-	fill(dt, None)
-	with cplan.DePlan(dg, cplan.DeviceMatrix(ptr, (ny, n), dt.dtype, ld), dc, lowmem=False) as plan:
-		for _ in range(3):
-			plan.step()
-		_store(out, 'adopted_old', plan.results())
-		infos['adopted_old'] = plan.info()
-		fill(dt2, plan.device_results()['stream'])
-		plan.step()
-		_store(out, 'adopted_new', plan.results())
-		infos['adopted_new'] = plan.info()
-		try:
-			plan.update(dt2)
-			infos['adopted_update'] = 'accepted'
-		except ValueError as e:
-			infos['adopted_update'] = str(e)
-	_lib.check(lib.nrm_host_free(ptr))
-	return infos
+	return h.replays(cplan.DePlan, ('step', 'step', 'step', 'update', 'step', 'design', 'step'), screen(**s), (dg2, dt2), job['design_form'], out)
 
 
 def scenario_handback(job, arr, out, lib, _lib, cplan):
-	dx, dy, dc = handback_inputs()
-	infos = {}
-	with cplan.DePlan(dx, dy, dc) as plan:
-		plan.step()
-		infos['first_check'] = plan.check()
-		infos['after_first'] = plan.info()
-		_store(out, 'first', plan.results())
-		for k in range(3):
-			plan.step()
-			infos['check{}'.format(k)] = plan.check()
-			_store(out, 'later{}'.format(k), plan.results())
-			infos['later{}'.format(k)] = plan.info()
-	return infos
+	return h.handback(cplan.DePlan, handback_inputs(), out)
 
 
 def scenario_bounds(job, arr, out, lib, _lib, cplan):
@@ -219,35 +99,15 @@ def scenario_bounds(job, arr, out, lib, _lib, cplan):
 	notes = {}
 	with cplan.DePlan(dg, bad, dc) as plan:
 		plan.step().step().step()
-		try:
-			plan.check()
-			notes['nan'] = 'accepted'
-		except AssertionError as e:
-			notes['nan'] = 'AssertionError: ' + str(e)
+		notes['nan'] = h.raised(plan.check, catch=AssertionError)
 		plan.update(dt).step()
 		notes['clean_check'] = plan.check()
-		_store(out, 'after_nan', plan.results())
+		h.store(out, 'after_nan', plan.results())
 		notes['after_nan'] = plan.info()
 	with cplan.DePlan(dg, dt, dc) as plan:
-		_store(out, 'fresh', plan.step().results())
+		h.store(out, 'fresh', plan.step().results())
 	return notes
 
 
-def main(argv):
-	sys.modules['torch'] = None  # `import torch` raises ImportError in this process
-	sys.path.insert(0, ROOT)
-	from normalisr_amd import _lib, cplan
-	scenario, src, dst = argv[1:4]
-	arr = np.load(src)
-	job = json.loads(str(arr['job']))
-	lib = _lib.load()
-	out = {}
-	notes = globals()['scenario_' + scenario](job, arr, out, lib, _lib, cplan)
-	assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]
-	out['notes'] = np.array(json.dumps(notes))
-	np.savez(dst, **out)
-	print('child ok')
-
-
 if __name__ == '__main__':
-	main(sys.argv)
+	h.child_main(sys.argv, globals())

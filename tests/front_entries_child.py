@@ -2,14 +2,15 @@
 the command line on host arrays -- through the library's whole-problem entries (nrm_lcpm_host, nrm_lcpm_csr_host, nrm_compute_var_host, nrm_qc_reads_host,
 nrm_qc_reads_csr_host) -- and writes what it got to an .npz and, for the command line, to files in a directory; the parent compares with the golden fixtures.
 `python tests/front_entries_child.py OUT.npz WORKDIR`.  The input generators at the top are shared with the parent and with tests/test_front_entries_cpu.py (which
-import this module; nothing here touches torch)."""
-import json
+import this module; nothing here touches torch); the frame of the child is cabi_harness.without_torch."""
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cabi_harness as h
+
+ROOT = h.ROOT
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 NTOT = 1E9  # (what tests/golden/make_g18.py and make_g19.py passed for the ntot_* arrays)
 LCPM_TILE, FITVAR_TILE = 32, 32  # nrm_lcpm_row_tile(), nrm_fitvar_row_tile(): the parent asserts both
@@ -64,12 +65,7 @@ def golden(name):
 
 
 # ---- the child ------------------------------------------------------------------------------------------------------------------------------------------------
-def _raised(f, *a, **ka):
-	try:
-		f(*a, **ka)
-		return 'no error'
-	except Exception as e:
-		return '{}: {}'.format(type(e).__name__, e)
+_raised = lambda f, *a, **ka: h.raised(lambda: f(*a, **ka), 'no error', Exception)
 
 
 def _debug(value):
@@ -241,22 +237,20 @@ def command_line(out, notes, work):
 
 
 def main(argv):
-	sys.modules['torch'] = None  # `import torch` raises ImportError in this process
-	sys.path.insert(0, ROOT)
-	os.environ.pop('NRM_HOST_ENTRY', None)
-	import normalisr_amd.lcpm as lcpm
-	import normalisr_amd.norm as norm
-	import normalisr_amd.qc  # noqa: F401
-	import normalisr_amd.run  # noqa: F401
 	dst, work = argv[1:3]
-	out, notes = {}, {}
-	for part in (dense_lcpm, sparse_lcpm, small_shapes, fitvar, qc_reads):
-		part(out, notes, lcpm, norm)
-	command_line(out, notes, work)
-	assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]
-	out['notes'] = np.array(json.dumps(notes))
-	np.savez(dst, **out)
-	print('child ok')
+
+	def run(out):
+		os.environ.pop('NRM_HOST_ENTRY', None)
+		import normalisr_amd.lcpm as lcpm
+		import normalisr_amd.norm as norm
+		import normalisr_amd.qc  # noqa: F401
+		import normalisr_amd.run  # noqa: F401
+		notes = {}
+		for part in (dense_lcpm, sparse_lcpm, small_shapes, fitvar, qc_reads):
+			part(out, notes, lcpm, norm)
+		command_line(out, notes, work)
+		return notes
+	h.without_torch(dst, run)
 
 
 if __name__ == '__main__':

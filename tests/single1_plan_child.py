@@ -1,18 +1,16 @@
 """The child side of tests/test_gpu_single1_plan.py: a process in which torch cannot be imported makes every call on the library's resident single=1 plan
 (normalisr_amd.cplan.Single1Plan over nrm_single1_plan_*) and writes what it got to an .npz; the parent compares.
 `python tests/single1_plan_child.py SCENARIO IN.npz OUT.npz`.  The input generators at the top are shared with the parent (which imports this module; nothing here
-touches torch); the design forms, the device copies and the result keys are those of tests/de_plan_child.py."""
+touches torch); the frame of the child, the design forms, the device copies, the result keys and the cases / replays scenarios are those of tests/cabi_harness.py."""
 import ctypes
-import json
 import sys
 
 import numpy as np
 
-import de_plan_child as dpc
+import cabi_harness as h
 import s1_wide
 
-ROOT = dpc.ROOT
-KEYS = dpc.KEYS
+ROOT, KEYS = h.ROOT, h.KEYS
 NX, NY, N = (s1_wide.s1.CHAIN[k] for k in ('nx', 'ny', 'n'))  # 65 groupings x 69 genes x 2051 cells
 ZERO_ROW, ONES_ROW = 10, 40  # where the two rows de drops stand among the NX + 2 design rows
 NG0 = NX + 2
@@ -83,23 +81,8 @@ def _screen_of(c):
 
 
 def scenario_cases(job, arr, out, lib, _lib, cplan):
-	"""Every case: a plan on (dg, dt, dc) in each of the forms named, `steps` steps, the results (and q-values) of the last, info() at the end."""
-	infos = {}
-	for c in job['cases']:
-		dg, dt, dc = _screen_of(c) if 'screen' in c else (arr[c['dg']], arr[c['dt']], arr[c['dc']])
-		for form in c.get('forms', ['dense']):
-			d, held = dpc._design(form, dg, lib, _lib, cplan)
-			name = '{}.{}'.format(c['name'], form)
-			with cplan.Single1Plan(d, dt, dc, dimreduce=c.get('dimreduce', 0), lowmem=c.get('lowmem', True), q=c.get('q', False), out_dtype=c.get('out_dtype')) as plan:
-				for _ in range(c.get('steps', 1)):
-					plan.step()
-				plan.check()
-				dpc._store(out, name, plan.results())
-				if c.get('q'):
-					out[name + '.q'] = plan.qvalues()
-				infos[name] = plan.info()
-			dpc._free(lib, _lib, held)
-	return infos
+	inputs = lambda c, arr: _screen_of(c) if 'screen' in c else (arr[c['dg']], arr[c['dt']], arr[c['dc']])
+	return h.cases(cplan.Single1Plan, job, arr, out, inputs, handed_back=False)
 
 
 def scenario_entry(job, arr, out, lib, _lib, cplan):
@@ -109,68 +92,17 @@ def scenario_entry(job, arr, out, lib, _lib, cplan):
 	infos = {}
 	for c in job['cases']:
 		dg, dt, dc = entry_screen(np.dtype(c['dtype']), c['nc'])
-		dpc._store(out, c['name'] + '.entry', norm.de(dg, dt, dc, single=1, lowmem=False))
+		h.store(out, c['name'] + '.entry', norm.de(dg, dt, dc, single=1, lowmem=False))
 		with cplan.Single1Plan(dg, dt, dc, lowmem=False) as plan:
-			dpc._store(out, c['name'] + '.plan', plan.step().results())
+			h.store(out, c['name'] + '.plan', plan.step().results())
 			infos[c['name']] = plan.info()
 	return infos
 
 
 def scenario_replays(job, arr, out, lib, _lib, cplan):
-	"""Three steps, update(dt2) and two more, set_design(dg2) and two more: every step's results and info; fresh plans on the same inputs; an adopted expression
-	matrix rewritten in place behind a captured step."""
-	dg, dt, dc = _screen_of(job)
+	"""Three steps, update(dt2) and two more, set_design(dg2) and two more (cabi_harness.replays)."""
 	dg2, dt2, _ = _screen_of(dict(screen=dict(job['screen'], seed=job['screen']['seed'] + 1)))
-	infos = {}
-	with cplan.Single1Plan(dg, dt, dc, lowmem=False) as plan:
-		k = 0
-		for what in ('step', 'step', 'step', 'update', 'step', 'design', 'step'):
-			if what == 'update':
-				plan.update(dt2)
-			elif what == 'design':
-				plan.set_design(dpc._design(job['design_form'], dg2, lib, _lib, cplan)[0])
-			plan.step()
-			k += 1
-			dpc._store(out, 'run{}'.format(k), plan.results())
-			infos['run{}'.format(k)] = plan.info()
-	for name, (g, t) in dict(fresh_a=(dg, dt), fresh_b=(dg, dt2), fresh_c=(dg2, dt2)).items():
-		with cplan.Single1Plan(g, t, dc, lowmem=False) as plan:
-			dpc._store(out, name, plan.step().results())
-			infos[name] = plan.info()
-	# an adopted expression matrix with a row pitch, rewritten in place on the plan's stream
-	ny, n = dt.shape
-	ld = n + 4
-	ptr = dpc._pinned(lib, _lib, ny * ld * dt.itemsize)
-
-	def fill(values, st):
-		h = np.zeros((ny, ld), dtype=dt.dtype)
-		h[:, :n] = values
-		_lib.check(lib.nrm_upload(h.ctypes.data, ptr, h.nbytes, 0, st))
-	fill(dt, None)
-	with cplan.Single1Plan(dg, cplan.DeviceMatrix(ptr, (ny, n), dt.dtype, ld), dc, lowmem=False) as plan:
-		for _ in range(3):
-			plan.step()
-		dpc._store(out, 'adopted_old', plan.results())
-		infos['adopted_old'] = plan.info()
-		fill(dt2, plan.device_results()['stream'])
-		plan.step()
-		dpc._store(out, 'adopted_new', plan.results())
-		infos['adopted_new'] = plan.info()
-		try:
-			plan.update(dt2)
-			infos['adopted_update'] = 'accepted'
-		except ValueError as e:
-			infos['adopted_update'] = str(e)
-	_lib.check(lib.nrm_host_free(ptr))
-	return infos
-
-
-def _raised(call):
-	try:
-		call()
-		return 'accepted'
-	except (AssertionError, ValueError, RuntimeError, NotImplementedError) as e:  # (NotImplementedError is a RuntimeError: the class name tells them apart)
-		return '{}: {}'.format(type(e).__name__, e)
+	return h.replays(cplan.Single1Plan, ('step', 'step', 'step', 'update', 'step', 'design', 'step'), _screen_of(job), (dg2, dt2), job['design_form'], out)
 
 
 def scenario_raises(job, arr, out, lib, _lib, cplan):
@@ -178,30 +110,30 @@ def scenario_raises(job, arr, out, lib, _lib, cplan):
 	dg, dt, dc = _screen_of(job)
 	notes = {}
 	with cplan.Single1Plan(dg, dt, dc, dimreduce=N) as plan:
-		notes['dimreduce'] = _raised(lambda: plan.step().step().step().check())
+		notes['dimreduce'] = h.raised(lambda: plan.step().step().step().check())
 	bad = dc.copy()
 	bad[0, np.nonzero(dg[kept_rows()].sum(axis=0) == 0)[0][0]] = np.nan  # (at a cell every grouping shares)
 	with cplan.Single1Plan(dg, dt, bad) as plan:
-		notes['nan_covariate'] = _raised(lambda: plan.step().step().step().check())
+		notes['nan_covariate'] = h.raised(lambda: plan.step().step().step().check())
 	with cplan.Single1Plan(one_grouping_per_cell(), dt, dc) as plan:
-		notes['one_per_cell'] = _raised(lambda: plan.step().step().step().check())
+		notes['one_per_cell'] = h.raised(lambda: plan.step().step().step().check())
 	own = np.nonzero((dg[kept_rows()] != 0).sum(axis=0) == 1)[0][0]  # a cell that belongs to exactly one grouping
 	nan = dt.copy()
 	nan[3, own] = np.nan
 	with cplan.Single1Plan(dg, nan, dc) as plan:
-		notes['nan_expression'] = _raised(lambda: plan.step().step().step().check())
+		notes['nan_expression'] = h.raised(lambda: plan.step().step().step().check())
 		plan.update(dt).step()
-		notes['clean_check'] = _raised(plan.check)
-		dpc._store(out, 'after_nan', plan.results())
+		notes['clean_check'] = h.raised(plan.check)
+		h.store(out, 'after_nan', plan.results())
 		notes['after_nan'] = plan.info()
 	with cplan.Single1Plan(dg, dt, dc) as plan:
-		dpc._store(out, 'fresh', plan.step().results())
+		h.store(out, 'fresh', plan.step().results())
 	return notes
 
 
 def _raw_create(lib, _lib, dt, dc, dense=None, csr=None):
 	"""nrm_single1_plan_create on host arrays as they are (no canonicalisation): (what _lib.check raises, whether the handle stayed NULL)."""
-	h = ctypes.c_void_p()
+	handle = ctypes.c_void_p()
 	vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 	nt, n = dt.shape
 	if dense is not None:
@@ -209,11 +141,11 @@ def _raw_create(lib, _lib, dt, dc, dense=None, csr=None):
 	else:
 		indptr, indices = csr
 		g = (1, None, _lib.NRM_F64, 0, vp(indptr), vp(indices), int(indices.size), 0, int(indptr.size) - 1)
-	rc = lib.nrm_single1_plan_create(ctypes.byref(h), *g, vp(dt), _lib.NRM_F64, nt, n, n, 0, vp(dc), _lib.NRM_F64, dc.shape[0], 0, _lib.NRM_F64, 0, 0)
-	what = _raised(lambda: _lib.check(rc))
-	null = h.value is None
+	rc = lib.nrm_single1_plan_create(ctypes.byref(handle), *g, vp(dt), _lib.NRM_F64, nt, n, n, 0, vp(dc), _lib.NRM_F64, dc.shape[0], 0, _lib.NRM_F64, 0, 0)
+	what = h.raised(lambda: _lib.check(rc))
+	null = handle.value is None
 	if not null:
-		lib.nrm_single1_plan_destroy(h)
+		lib.nrm_single1_plan_destroy(handle)
 	return [what, null]
 
 
@@ -241,37 +173,21 @@ def scenario_refusals(job, arr, out, lib, _lib, cplan):
 	def works():
 		with cplan.Single1Plan(dg, dt, dc) as plan:
 			return plan.step().results()
-	dpc._store(out, 'first', works())
+	h.store(out, 'first', works())
 	for name, d in designs.items():
 		notes[name] = _raw_create(lib, _lib, dt, dc, dense=np.ascontiguousarray(d))
-		dpc._store(out, 'after_' + name, works())
+		h.store(out, 'after_' + name, works())
 	for name, c in dict(falls=(falls, indices), beyond=(indptr, beyond)).items():
 		notes[name] = _raw_create(lib, _lib, dt, dc, csr=c)
-		dpc._store(out, 'after_' + name, works())
+		h.store(out, 'after_' + name, works())
 	notes['good_csr'] = _raw_create(lib, _lib, dt, dc, csr=(indptr, indices))
 	# a refused set_design leaves the plan without a design until one is accepted
 	with cplan.Single1Plan(dg, dt, dc) as plan:
-		notes['set_design'] = _raised(lambda: plan.set_design(designs['two']))
-		notes['step_without_design'] = _raised(plan.step)
-		dpc._store(out, 'after_set_design', plan.set_design(dg).step().results())
+		notes['set_design'] = h.raised(lambda: plan.set_design(designs['two']))
+		notes['step_without_design'] = h.raised(plan.step)
+		h.store(out, 'after_set_design', plan.set_design(dg).step().results())
 	return notes
 
 
-def main(argv):
-	sys.modules['torch'] = None  # `import torch` raises ImportError in this process
-	sys.path.insert(0, ROOT)
-	from normalisr_amd import _lib, cplan
-	scenario, src, dst = argv[1:4]
-	arr = np.load(src)
-	job = json.loads(str(arr['job']))
-	lib = _lib.load()
-	out = {}
-	notes = globals()['scenario_' + scenario](job, arr, out, lib, _lib, cplan)
-	assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]
-	out['notes'] = np.array(json.dumps(notes))
-	np.savez(dst, **out)
-	print('child ok')
-
-
 if __name__ == '__main__':
-	main(sys.argv)
+	h.child_main(sys.argv, globals())

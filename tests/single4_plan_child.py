@@ -1,19 +1,17 @@
 """The child side of tests/test_gpu_single4_plan.py: a process in which torch cannot be imported makes every call on the library's resident single=4 plan
 (normalisr_amd.cplan.Single4Plan over nrm_single4_plan_*) and writes what it got to an .npz; the parent compares.
-`python tests/single4_plan_child.py SCENARIO IN.npz OUT.npz`.  The screen is tests/single1_plan_child.py::screen; the design forms, the device copies and the result
-keys are those of tests/de_plan_child.py.  What the top of this file defines is shared with the parent and with tests/test_single4_plan_cpu.py (which import this
+`python tests/single4_plan_child.py SCENARIO IN.npz OUT.npz`.  The screen is tests/single1_plan_child.py::screen; the frame of the child, the design forms, the device copies, the
+result keys and the cases / replays / handback scenarios are those of tests/cabi_harness.py.  What the top of this file defines is shared with the parent and with tests/test_single4_plan_cpu.py (which import this
 module; nothing here touches torch)."""
 import ctypes
-import json
 import sys
 
 import numpy as np
 
-import de_plan_child as dpc
+import cabi_harness as h
 import single1_plan_child as s1c
 
-ROOT = dpc.ROOT
-KEYS = dpc.KEYS
+ROOT, KEYS = h.ROOT, h.KEYS
 NX, NY, N, NG0 = s1c.NX, s1c.NY, s1c.N, s1c.NG0
 ZERO_ROW, ONES_ROW = s1c.ZERO_ROW, s1c.ONES_ROW
 NCS = s1c.NCS
@@ -94,96 +92,18 @@ def _entry(lib, _lib, dg, dt, dc):
 
 
 def scenario_cases(job, arr, out, lib, _lib, cplan):
-	"""Every case: a plan on (dg, dt, dc) in each of the forms named, `steps` steps, the results (and q-values) of the last, info() at the end; `entry`: the
-	whole-problem entry on the rows kept too."""
-	infos = {}
-	for c in job['cases']:
-		dg, dt, dc = _inputs(c, arr)
-		for form in c.get('forms', ['dense']):
-			d, held = dpc._design(form, dg, lib, _lib, cplan)
-			name = '{}.{}'.format(c['name'], form)
-			with cplan.Single4Plan(d, dt, dc, dimreduce=c.get('dimreduce', 0), lowmem=c.get('lowmem', True), q=c.get('q', False), out_dtype=c.get('out_dtype')) as plan:
-				for _ in range(c.get('steps', 1)):
-					plan.step()
-				back = plan.check()
-				dpc._store(out, name, plan.results())
-				if c.get('q'):
-					out[name + '.q'] = plan.qvalues()
-				infos[name] = dict(plan.info(), handed_back=back)
-			dpc._free(lib, _lib, held)
-		if c.get('entry'):
-			dpc._store(out, c['name'] + '.entry', _entry(lib, _lib, dg[kept_rows()], dt, dc))
-	return infos
+	"""cabi_harness.cases; `entry`: the whole-problem entry on the rows kept too."""
+	return h.cases(cplan.Single4Plan, job, arr, out, _inputs, entry=lambda dg, dt, dc: _entry(lib, _lib, dg[kept_rows()], dt, dc))
 
 
 def scenario_replays(job, arr, out, lib, _lib, cplan):
-	"""Five steps, update(dt2) and one more, set_design(dg2) and two more: every step's results and info; fresh plans on the same inputs; an adopted expression
-	matrix rewritten in place behind a captured step."""
-	nc = job['nc']
-	dg, dt, dc = screen(nc)
-	dg2, dt2, _ = second_screen(nc)
-	infos = {}
-	with cplan.Single4Plan(dg, dt, dc, lowmem=False) as plan:
-		k = 0
-		for what in ('step', 'step', 'step', 'step', 'step', 'update', 'design', 'step'):
-			if what == 'update':
-				plan.update(dt2)
-			elif what == 'design':
-				plan.set_design(dpc._design(job['design_form'], dg2, lib, _lib, cplan)[0])
-				infos['after_design'] = plan.info()
-			plan.step()
-			k += 1
-			dpc._store(out, 'run{}'.format(k), plan.results())
-			infos['run{}'.format(k)] = plan.info()
-	for name, (g, t) in dict(fresh_a=(dg, dt), fresh_b=(dg, dt2), fresh_c=(dg2, dt2)).items():
-		with cplan.Single4Plan(g, t, dc, lowmem=False) as plan:
-			dpc._store(out, name, plan.step().results())
-			infos[name] = plan.info()
-	# an adopted expression matrix with a row pitch, rewritten in place on the plan's stream
-	ny, n = dt.shape
-	ld = n + 4
-	ptr = dpc._pinned(lib, _lib, ny * ld * dt.itemsize)
-
-	def fill(values, st):
-		h = np.zeros((ny, ld), dtype=dt.dtype)
-		h[:, :n] = values
-		_lib.check(lib.nrm_upload(h.ctypes.data, ptr, h.nbytes, 0, st))
-	fill(dt, None)
-	with cplan.Single4Plan(dg, cplan.DeviceMatrix(ptr, (ny, n), dt.dtype, ld), dc, lowmem=False) as plan:
-		for _ in range(3):
-			plan.step()
-		dpc._store(out, 'adopted_old', plan.results())
-		infos['adopted_old'] = plan.info()
-		fill(dt2, plan.device_results()['stream'])
-		plan.step()
-		dpc._store(out, 'adopted_new', plan.results())
-		infos['adopted_new'] = plan.info()
-		try:
-			plan.update(dt2)
-			infos['adopted_update'] = 'accepted'
-		except ValueError as e:
-			infos['adopted_update'] = str(e)
-	_lib.check(lib.nrm_host_free(ptr))
-	return infos
+	"""Five steps, update(dt2) and one more, set_design(dg2) and two more, info() after set_design kept (cabi_harness.replays)."""
+	return h.replays(cplan.Single4Plan, ('step', 'step', 'step', 'step', 'step', 'update', 'design', 'step'), screen(job['nc']), second_screen(job['nc'])[:2], job['design_form'], out,
+					 info_after_design=True)
 
 
 def scenario_handback(job, arr, out, lib, _lib, cplan):
-	dg, dt, dc = handback_screen()
-	infos = {}
-	with cplan.Single4Plan(dg, dt, dc, lowmem=False) as plan:
-		plan.step()
-		infos['first_check'] = plan.check()
-		infos['after_first'] = plan.info()
-		dpc._store(out, 'first', plan.results())
-		for k in range(3):
-			plan.step()
-			infos['check{}'.format(k)] = plan.check()
-			dpc._store(out, 'later{}'.format(k), plan.results())
-			infos['later{}'.format(k)] = plan.info()
-	return infos
-
-
-_raised = s1c._raised
+	return h.handback(cplan.Single4Plan, handback_screen(), out, lowmem=False)
 
 
 def scenario_refusals(job, arr, out, lib, _lib, cplan):
@@ -192,44 +112,28 @@ def scenario_refusals(job, arr, out, lib, _lib, cplan):
 	dc, designs = refused_designs()
 	notes = {}
 	with cplan.Single4Plan(dg, dt, dc) as plan:
-		dpc._store(out, 'first', plan.step().results())
+		h.store(out, 'first', plan.step().results())
 		notes['first'] = plan.info()
 	for name, d in designs.items():
-		notes['create_' + name] = _raised(lambda: cplan.Single4Plan(d, dt, dc).close())
+		notes['create_' + name] = h.raised(lambda: cplan.Single4Plan(d, dt, dc).close())
 		with cplan.Single4Plan(dg, dt, dc) as plan:
 			plan.step().step()
-			notes['design_' + name] = _raised(lambda: plan.set_design(d))
-			notes['step_after_' + name] = _raised(plan.step)
-			dpc._store(out, 'after_' + name, plan.set_design(dg).step().results())
+			notes['design_' + name] = h.raised(lambda: plan.set_design(d))
+			notes['step_after_' + name] = h.raised(plan.step)
+			h.store(out, 'after_' + name, plan.set_design(dg).step().results())
 			notes['after_' + name] = plan.info()
-	notes['cells'] = _raised(lambda: cplan.Single4Plan(dg, dt, dc, dimreduce=N - NX - 3).close())  # n == nx + rank + dimreduce
+	notes['cells'] = h.raised(lambda: cplan.Single4Plan(dg, dt, dc, dimreduce=N - NX - 3).close())  # n == nx + rank + dimreduce
 	bad = dt.copy()
 	bad[3, 11] = np.nan
 	with cplan.Single4Plan(dg, bad, dc) as plan:
 		plan.step().step().step()
-		notes['nan'] = _raised(plan.results)
+		notes['nan'] = h.raised(plan.results)
 		plan.update(dt).step()
-		notes['clean_check'] = _raised(plan.check)
-		dpc._store(out, 'after_nan', plan.results())
+		notes['clean_check'] = h.raised(plan.check)
+		h.store(out, 'after_nan', plan.results())
 		notes['after_nan'] = plan.info()
 	return notes
 
 
-def main(argv):
-	sys.modules['torch'] = None  # `import torch` raises ImportError in this process
-	sys.path.insert(0, ROOT)
-	from normalisr_amd import _lib, cplan
-	scenario, src, dst = argv[1:4]
-	arr = np.load(src)
-	job = json.loads(str(arr['job']))
-	lib = _lib.load()
-	out = {}
-	notes = globals()['scenario_' + scenario](job, arr, out, lib, _lib, cplan)
-	assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]
-	out['notes'] = np.array(json.dumps(notes))
-	np.savez(dst, **out)
-	print('child ok')
-
-
 if __name__ == '__main__':
-	main(sys.argv)
+	h.child_main(sys.argv, globals())

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle
+from cabi_harness import build_and_run_host_program
 from conftest import ROOT, relerr
 from normalisr_amd import _lib
 
@@ -138,39 +139,11 @@ def test_host_logic_under_address_and_ub_sanitizers(tmp_path):
 	slabs inside the workspace, bands tiling the problem), the scratch pool of the whole-problem entry, the P-value plan -- built by
 	g++ with -fsanitize=address,undefined and run on the CPU (csrc/nrm_host_logic.h is free of HIP headers for this purpose; GPU
 	sanitizers are not available on the pool)."""
-	import shutil
-	import subprocess
-	gxx = shutil.which('g++')
-	if gxx is None:
-		pytest.skip('no g++')
-	exe = str(tmp_path / 'host_sanitize')
-	src = os.path.join(ROOT, 'tests', 'host', 'host_sanitize.cpp')
-	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-o', exe, src],
-					   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-	if r.returncode != 0 and ('asan' in r.stdout or 'ubsan' in r.stdout or 'sanitize' in r.stdout):
-		pytest.skip('sanitizer runtimes not installed: ' + r.stdout[-200:])
-	assert r.returncode == 0, r.stdout
-	r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-	assert r.returncode == 0 and 'host logic ok' in r.stdout, r.stdout[-2000:]
+	build_and_run_host_program(tmp_path, ['tests/host/host_sanitize.cpp'], 'host logic ok', may_skip=True)
 
 
-def _sanitize_build_and_run(tmp_path, hip_source, harness, token, args=()):
-	import shutil
-	import subprocess
-	gxx = shutil.which('g++')
-	hip_inc = '/opt/rocm/include'
-	if gxx is None or not os.path.exists(os.path.join(hip_inc, 'hip', 'hip_runtime.h')):
-		pytest.skip('no g++ / HIP headers')
-	exe = str(tmp_path / 'sanitize_exe')
-	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-D__HIP_PLATFORM_AMD__', '-I' + hip_inc, '-pthread', '-w',
-						'-x', 'c++', os.path.join(ROOT, 'normalisr_amd', 'csrc', hip_source), os.path.join(ROOT, 'tests', 'host', harness), '-o', exe],
-					   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-	if r.returncode != 0 and ('asan' in r.stdout or 'ubsan' in r.stdout or 'sanitize' in r.stdout):
-		pytest.skip('sanitizer runtimes not installed: ' + r.stdout[-200:])
-	assert r.returncode == 0, r.stdout[-3000:]
-	r = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-	assert r.returncode == 0 and token in r.stdout, r.stdout[-3000:]
-	return r.stdout
+def _sanitize_build_and_run(tmp_path, hip_source, harness, token, args=(), timeout=900):
+	return build_and_run_host_program(tmp_path, ['normalisr_amd/csrc/' + hip_source, 'tests/host/' + harness], token, args=args, timeout=timeout, may_skip=True)
 
 
 def _certificate_cases(seed=7, n=64, nx=4, per_kind=4, tol=1e-8):
@@ -245,21 +218,7 @@ def test_text_parser_and_printer_under_address_and_ub_sanitizers(tmp_path):
 	"""The command line's text parser / printer (csrc/nrm_tsv.hip: host code) reads what users hand it: built by g++ with -fsanitize=address,undefined beside a
 	harness (tests/host/tsv_sanitize.cpp) that round-trips random matrices of every magnitude through '%.8G' / '%i' text in 1 .. 7 threads and feeds it hostile text
 	(random bytes from the alphabet of numbers, valid text truncated at every length) from exact-size heap buffers."""
-	import shutil
-	import subprocess
-	gxx = shutil.which('g++')
-	hip_inc = '/opt/rocm/include'
-	if gxx is None or not os.path.exists(os.path.join(hip_inc, 'hip', 'hip_runtime.h')):
-		pytest.skip('no g++ / HIP headers')
-	exe = str(tmp_path / 'tsv_sanitize')
-	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-D__HIP_PLATFORM_AMD__', '-I' + hip_inc, '-pthread', '-w',
-						'-x', 'c++', os.path.join(ROOT, 'normalisr_amd', 'csrc', 'nrm_tsv.hip'), os.path.join(ROOT, 'tests', 'host', 'tsv_sanitize.cpp'), '-o', exe],
-					   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-	if r.returncode != 0 and ('asan' in r.stdout or 'ubsan' in r.stdout or 'sanitize' in r.stdout):
-		pytest.skip('sanitizer runtimes not installed: ' + r.stdout[-200:])
-	assert r.returncode == 0, r.stdout[-3000:]
-	r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-	assert r.returncode == 0 and 'text io ok' in r.stdout, r.stdout[-3000:]
+	_sanitize_build_and_run(tmp_path, 'nrm_tsv.hip', 'tsv_sanitize.cpp', 'text io ok', timeout=600)
 
 
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])

@@ -4,34 +4,21 @@ pseudo-inverse of dc dc^T agrees with association.inv_rank on the covariates of 
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from cabi_harness import ROOT, assert_plan_names, binds_without_torch, build_and_run_host_program
+from cabi_harness import vp as _vp
 from normalisr_amd import _lib
 from normalisr_amd.association import inv_rank
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_CALLS = ('create', 'upload', 'step', 'check', 'results', 'device_results', 'stream', 'info', 'time', 'destroy')
-NEW_NAMES = tuple('nrm_coex_plan_' + c for c in PLAN_CALLS) + ('nrm_covariates_pinv', 'nrm_cache_bytes')
-
-
-def _vp(a):
-	return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def test_c_entry_plan_names_declared_and_exported():
-	hdr = open(os.path.join(ROOT, 'include', 'normalisr_hip.h')).read()
-	declared = set(re.findall(r'\b(nrm_[a-z0-9_]+)\s*\(', hdr))
-	lib = ctypes.CDLL(_lib.LIB_PATH)
-	for name in NEW_NAMES:
-		assert name in declared, name
-		assert name in _lib.exported_symbols(), name
-		assert hasattr(lib, name), name
-	assert declared == set(_lib.exported_symbols())
+	assert_plan_names('nrm_coex_plan_', PLAN_CALLS, ('nrm_covariates_pinv', 'nrm_cache_bytes'))
 	import normalisr
 	import normalisr_amd
 	assert 'cplan' in normalisr_amd.__all__ and 'cplan' in normalisr.__all__
@@ -40,16 +27,7 @@ def test_c_entry_plan_names_declared_and_exported():
 
 def test_cplan_imports_without_torch():
 	"""A child in which `import torch` fails: the module, its classes and the library's signatures are all there, and torch was never asked for by name."""
-	code = ("import sys; sys.modules['torch'] = None\n"
-			"sys.path.insert(0, {!r})\n"
-			"from normalisr_amd import cplan, _lib\n"
-			"assert callable(cplan.CoexPlan) and callable(cplan.DeviceMatrix)\n"
-			"lib = _lib.load()\n"
-			"assert lib.nrm_coex_plan_destroy(None) == 0\n"
-			"assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]\n"
-			"print('cplan without torch ok')\n").format(ROOT)
-	r = subprocess.run([sys.executable, '-c', code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-	assert r.returncode == 0 and 'cplan without torch ok' in r.stdout, r.stdout[-2000:]
+	binds_without_torch(('CoexPlan', 'DeviceMatrix'), (), 'nrm_coex_plan_destroy')
 	src = open(os.path.join(ROOT, 'normalisr_amd', 'cplan.py')).read()
 	assert not re.search(r'^\s*(import|from)\s+torch', src, re.M)
 
@@ -180,12 +158,4 @@ def test_c_entry_covariates_pinv_dtypes_and_limits(golden):
 def test_covariates_pinv_under_address_and_ub_sanitizers(tmp_path):
 	"""The new arithmetic of csrc/nrm_host_math.h and its entry in csrc/nrm_small_pinv.hip, built by g++ with -fsanitize=address,undefined beside a program with its own
 	main (tests/host/covariates_pinv_sanitize.cpp) and run directly: nothing loaded into python is run under a sanitizer."""
-	gxx = shutil.which('g++')
-	assert gxx is not None, 'g++ is needed to build the host arithmetic'
-	exe = str(tmp_path / 'covariates_pinv_sanitize')
-	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-pthread', '-w',
-						'-x', 'c++', os.path.join(ROOT, 'normalisr_amd', 'csrc', 'nrm_small_pinv.hip'), os.path.join(ROOT, 'tests', 'host', 'covariates_pinv_sanitize.cpp'), '-o', exe],
-					   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-	assert r.returncode == 0, r.stdout[-3000:]
-	r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-	assert r.returncode == 0 and 'covariates pinv ok' in r.stdout, r.stdout[-3000:]
+	build_and_run_host_program(tmp_path, ['normalisr_amd/csrc/nrm_small_pinv.hip', 'tests/host/covariates_pinv_sanitize.cpp'], 'covariates pinv ok')

@@ -2,49 +2,25 @@
 binds it without torch, the constructor and create refuse bad arguments -- create before any device call, in the reference's words --, the varying-row rule the
 plan's kernels decide by is held to de's own on its edge cases, and the host arithmetic of the checks runs under ASan + UBSan in a program of its own."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from cabi_harness import assert_plan_names, binds_without_torch, build_and_run_host_program
+from cabi_harness import vp as _vp
 from normalisr_amd import _lib
 from normalisr_amd.association import inv_rank
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_CALLS = ('create', 'design', 'upload', 'step', 'check', 'results', 'device_results', 'stream', 'info', 'time', 'destroy')
 TOO_FEW = 'Insufficient number of cells: must be greater than degrees of freedom removed + covariate + 1.'
 
 
-def _vp(a):
-	return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
 def test_de_plan_names_declared_and_exported():
-	hdr = open(os.path.join(ROOT, 'include', 'normalisr_hip.h')).read()
-	declared = set(re.findall(r'\b(nrm_[a-z0-9_]+)\s*\(', hdr))
-	lib = ctypes.CDLL(_lib.LIB_PATH)
-	for name in ('nrm_de_plan_' + c for c in PLAN_CALLS):
-		assert name in declared, name
-		assert name in _lib.exported_symbols(), name
-		assert hasattr(lib, name), name
-	assert declared == set(_lib.exported_symbols())
+	assert_plan_names('nrm_de_plan_', PLAN_CALLS)
 
 
 def test_de_plan_binds_without_torch():
-	code = ("import sys; sys.modules['torch'] = None\n"
-			"sys.path.insert(0, {!r})\n"
-			"from normalisr_amd import cplan, _lib\n"
-			"assert callable(cplan.DePlan) and callable(cplan.DeviceCSR) and callable(cplan.varying_rows)\n"
-			"lib = _lib.load()\n"
-			"assert lib.nrm_de_plan_destroy(None) == 0\n"
-			"assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]\n"
-			"print('de plan without torch ok')\n").format(ROOT)
-	r = subprocess.run([sys.executable, '-c', code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-	assert r.returncode == 0 and 'de plan without torch ok' in r.stdout, r.stdout[-2000:]
+	binds_without_torch(('DePlan', 'DeviceCSR', 'varying_rows'), (), 'nrm_de_plan_destroy')
 
 
 def _problem(n=12, nc=2):
@@ -207,12 +183,4 @@ def test_de_plan_argument_checks_under_address_and_ub_sanitizers(tmp_path):
 	"""csrc/nrm_de_plan_args.h -- every check create and design make before a device call, the library's own pseudo-inverse included -- built by g++ with
 	-fsanitize=address,undefined beside a program with its own main (tests/host/de_plan_args_sanitize.cpp) and run directly: nothing loaded into python runs
 	under a sanitizer."""
-	gxx = shutil.which('g++')
-	assert gxx is not None, 'g++ is needed to build the host arithmetic'
-	exe = str(tmp_path / 'de_plan_args_sanitize')
-	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-pthread', '-w',
-						'-x', 'c++', os.path.join(ROOT, 'normalisr_amd', 'csrc', 'nrm_small_pinv.hip'), os.path.join(ROOT, 'tests', 'host', 'de_plan_args_sanitize.cpp'), '-o', exe],
-					   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-	assert r.returncode == 0, r.stdout[-3000:]
-	r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-	assert r.returncode == 0 and 'de plan args ok' in r.stdout, r.stdout[-3000:]
+	build_and_run_host_program(tmp_path, ['normalisr_amd/csrc/nrm_small_pinv.hip', 'tests/host/de_plan_args_sanitize.cpp'], 'de plan args ok')

@@ -1,9 +1,6 @@
 """The front-half whole-problem entries (csrc/nrm_host_front.hip) where no GPU is needed: their host arithmetic (csrc/nrm_host_math.h) in a stand-alone program
 under g++ -fsanitize=address,undefined against numpy, every argument check before any device call, the imports of a process without torch, and the stability of
 the numpy restatement the GPU test compares the 63-covariate compute_var with."""
-import ctypes
-import os
-import shutil
 import subprocess
 import sys
 
@@ -12,10 +9,9 @@ import pytest
 
 import front_entries_child as child
 import front_numpy
+from cabi_harness import ROOT, build_and_run_host_program, close
+from cabi_harness import vp as VP
 from normalisr_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VP = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _ulps(a, b):
@@ -31,16 +27,6 @@ def test_front_entry_math_under_address_and_ub_sanitizers(golden, tmp_path):
 	from scipy.special import digamma
 	from normalisr_amd.norm import _pinv_gram_unit_rows
 	from normalisr_amd.qc import qc_thresholds
-	from test_gpu_parity import close
-	gxx = shutil.which('g++')
-	if gxx is None:
-		pytest.skip('g++ is needed to build the host arithmetic')
-	exe = str(tmp_path / 'front_entry_math_sanitize')
-	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-w',
-						os.path.join(ROOT, 'tests', 'host', 'front_entry_math_sanitize.cpp'), '-o', exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-	if r.returncode != 0 and 'sanitize' in r.stdout and ('cannot find' in r.stdout or 'unrecognized' in r.stdout):
-		pytest.skip('g++ cannot link the sanitizer runtimes here')
-	assert r.returncode == 0, r.stdout[-3000:]
 	g, h = golden('G18_front'), golden('G18_front_chain')
 	reads = g['reads'].astype(np.int64)
 	psi, psi_t0 = digamma(1.0 + np.arange(int(reads.max()) + 1)), float(digamma(float(reads.sum() + 2)))
@@ -62,8 +48,7 @@ def test_front_entry_math_under_address_and_ub_sanitizers(golden, tmp_path):
 	src, dst = str(tmp_path / 'in.bin'), str(tmp_path / 'out.txt')
 	with open(src, 'wb') as fh:
 		fh.write(blob)
-	r = subprocess.run([exe, src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-	assert r.returncode == 0 and 'front entry math ok' in r.stdout, r.stdout[-3000:]
+	build_and_run_host_program(tmp_path, ['tests/host/front_entry_math_sanitize.cpp'], 'front entry math ok', args=[src, dst], may_skip=True)
 	got = {}
 	for line in open(dst):
 		name, *vals = line.split()
@@ -188,7 +173,6 @@ def test_front_modules_import_without_torch():
 def test_wide_compute_var_restatement_is_stable():
 	"""The bound of the GPU test for 63 covariates of rank 62, close(1e-9, floor=1), means something only if the numpy restatement it compares with does not
 	itself move by that much: two orders of the covariate rows (the fit does not depend on the order) agree within the bound, for the seed the GPU test uses."""
-	from test_gpu_parity import close
 	y, dc = child.fitvar_wide()
 	assert y.shape == (child.FITVAR_TILE + 1, 1030) and y.dtype == np.float32 and dc.shape == (63, 1030) and np.linalg.matrix_rank(dc) == 62
 	a = front_numpy.compute_var(y, dc, stepmax=2)

@@ -2,40 +2,21 @@
 in which torch cannot be imported (tests/coex_plan_child.py: normalisr_amd._lib and .cplan only); this process holds what comes back to the reference's golden
 vectors, to the oracle and to norm.coex on the same arrays.  Bars: P-values within 1e-6 relative (the project's), covariances and variances within 1e-9 of their
 largest entry, zeros / ones / symmetry exact, replays bit for bit."""
-import json
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import cabi_harness
 import coex_plan_child as child
 import oracle
+from cabi_harness import p_close
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-P_TINY = 2.3e-308  # below: subnormal, compared absolutely
-
-
-def run_child(tmp_path, scenario, arrays, job, env=None, timeout=180):
-	src, dst = str(tmp_path / (scenario + '_in.npz')), str(tmp_path / (scenario + '_out.npz'))
-	np.savez(src, job=np.array(json.dumps(job)), **arrays)
-	e = dict(os.environ)
-	e.update(env or {})
-	r = subprocess.run([sys.executable, os.path.join(HERE, 'coex_plan_child.py'), scenario, src, dst], env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
-	assert r.returncode == 0 and 'child ok' in r.stdout, r.stdout[-3000:]
-	out = np.load(dst)
-	return out, json.loads(str(out['notes']))
-
-
-def p_close(p, ref, rtol=1e-6):
-	p, ref = np.asarray(p, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-	normal = ref >= P_TINY
-	err = float(np.max(np.abs(p[normal] - ref[normal]) / ref[normal])) if normal.any() else 0.
-	print('  P-values: worst relative error {:.2e}'.format(err))
-	return err < rtol and bool(np.all(np.abs(p[~normal] - ref[~normal]) <= 1e-307))
+run_child = functools.partial(cabi_harness.run_child, 'coex_plan_child.py', timeout=180)
+got = lambda out, name, tag='': cabi_harness.got(out, name, cabi_harness.COEX_KEYS, tag)
 
 
 def p_close32(p, ref, rtol=1e-6):
@@ -55,10 +36,6 @@ def scale_close(a, ref, rtol=1e-9):
 
 def exact_structure(p, d):
 	return bool((np.diag(p) == 0).all() and (np.diag(d) == 0).all() and (p == p.T).all() and (d == d.T).all())
-
-
-def got(out, name, tag=''):
-	return out['{}.p{}'.format(name, tag)], out['{}.dot{}'.format(name, tag)], out['{}.var{}'.format(name, tag)]
 
 
 def test_coex_plan_c_entry_golden_fp64_route(golden, tmp_path):

@@ -7,60 +7,20 @@ is the sparse-design route, so gamma, alpha, varg and vart are held as tests/tes
 1e-6 (floor 1e-12), alpha 1e-6 (floor 1e-9), varg 1e-9 (floor 1e-15), vart 1e-7 (floor 1e-15); fp32 gamma as tests/test_gpu_parity.py: 1e-6 (floor 1e-7).  The ones
 and zeros of rows that are not tested are exact.  Against norm.de under NRM_HOST_ENTRY=1 NRM_DE_SPARSE=force (the parent's route: the same lists into the same
 kernels) and between a replay and a fresh plan every array is equal, bit for bit."""
-import json
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import de_plan_child as child
 import oracle
-from conftest import relerr
+from cabi_harness import close, got, p_close, same
+from cabi_harness import run_child as _run_child
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-P_TINY = 2.3e-308  # below: subnormal, compared absolutely
-
-
-def run_child(tmp_path, scenario, arrays, job, env=None, timeout=240):
-	src, dst = str(tmp_path / (scenario + '_in.npz')), str(tmp_path / (scenario + '_out.npz'))
-	np.savez(src, job=np.array(json.dumps(job)), **arrays)
-	e = dict(os.environ)
-	e.update(env or {})
-	r = subprocess.run([sys.executable, os.path.join(HERE, 'de_plan_child.py'), scenario, src, dst], env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
-	assert r.returncode == 0 and 'child ok' in r.stdout, r.stdout[-3000:]
-	out = np.load(dst)
-	return out, json.loads(str(out['notes']))
-
-
-def close(a, b, rtol=1e-6, floor=0.):
-	err = relerr(a, b, floor)
-	print('  worst relative error {:.2e} (bar {:.0e}, floor {:.0e})'.format(err, rtol, floor))
-	return err < rtol
-
-
-def p_close(p, ref, rtol=1e-6):
-	p, ref = np.asarray(p, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-	normal = ref >= P_TINY
-	err = relerr(p[normal], ref[normal]) if normal.any() else 0.
-	print('  P-values: worst relative error {:.2e}'.format(err))
-	return err < rtol and bool(np.all(np.abs(p[~normal] - ref[~normal]) <= 1e-307))
-
-
-def got(out, name):
-	return tuple(out['{}.{}'.format(name, k)] if '{}.{}'.format(name, k) in out.files else None for k in child.KEYS)
-
-
-def same(a, b, what=''):
-	"""Two de results equal bit for bit: dtypes, shapes, every array."""
-	for k, x, y in zip(child.KEYS, a, b):
-		if x is None or y is None:
-			assert x is None and y is None, (what, k)
-			continue
-		assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), (what, k, float(np.abs(x.astype(np.float64) - y.astype(np.float64)).max()))
+run_child = functools.partial(_run_child, 'de_plan_child.py')  # (timeout=240)
 
 
 @pytest.fixture

@@ -3,17 +3,14 @@ One child process in which `import torch` fails (tests/front_entries_child.py) m
 the reference-held fixtures (G18_front, G18_front_chain, G19_lcpm_sparse, G20_qc) and the numpy restatements of tests/front_numpy.py.  Tolerances are the
 project's: integers exact, fp64 quantities close(1e-9, floor=1), scaling factors 1e-12 absolute, fp32 output the fp64 output rounded once, text files
 close(1e-6, floor=1).  No bit equality with the torch route is expected (its exp table is numpy's, its pseudo-inverses LAPACK's)."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import front_entries_child as child
 import front_numpy
-from test_gpu_parity import close
+from cabi_harness import close, start_child
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,11 +32,8 @@ def ran(tmp_path_factory):
 	env = dict(os.environ)
 	for k in ('NRM_HOST_ENTRY', 'NRM_DEBUG'):
 		env.pop(k, None)
-	r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'front_entries_child.py'), dst, str(work)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-					   timeout=600)
-	assert r.returncode == 0 and 'child ok' in r.stdout, r.stdout[-4000:]
-	arr = np.load(dst)
-	return arr, json.loads(str(arr['notes'])), str(work)
+	arr, notes = start_child('front_entries_child.py', [dst, str(work)], dst, env, timeout=600, tail=4000)
+	return arr, notes, str(work)
 
 
 def test_lcpm_dense_without_torch(golden, ran):

@@ -9,54 +9,24 @@ same lists, and a replay the launches of an eager step: against either every arr
 The screen (tests/single1_plan_child.py::screen): 65 groupings x 69 genes x 2051 cells with entries set with probability 1 / 65, and two rows de drops -- one all
 zeros, one ALL ONES, which left in would leave no cell with exactly one grouping.  tests/test_single1_plan_cpu.py holds every seed used here to the oracle's own
 assertions (each kept grouping varies on its selected cells, dof > 0)."""
-import json
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle
 import single1_plan_child as child
-from test_gpu_parity import close, p_close
-from test_gpu_single1_wide import held
+from cabi_harness import close, got, held, p_close, same, untested_rows_exact
+from cabi_harness import run_child as _run_child
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+run_child = functools.partial(_run_child, 'single1_plan_child.py')  # (timeout=240)
 KEPT = child.kept_rows()
 DROPPED = [child.ZERO_ROW, child.ONES_ROW]
 SEEDS, NCS = child.SEEDS, child.NCS
 FORMS = ['dense', 'scipy', 'devcsr', 'devcsr_data']  # (devcsr: no data array, every entry is 1; devcsr_data: with one)
-
-
-def run_child(tmp_path, scenario, arrays, job, env=None, timeout=240):
-	src, dst = str(tmp_path / (scenario + '_in.npz')), str(tmp_path / (scenario + '_out.npz'))
-	np.savez(src, job=np.array(json.dumps(job)), **arrays)
-	r = subprocess.run([sys.executable, os.path.join(HERE, 'single1_plan_child.py'), scenario, src, dst], env=dict(os.environ, **(env or {})), stdout=subprocess.PIPE,
-					   stderr=subprocess.STDOUT, text=True, timeout=timeout)
-	assert r.returncode == 0 and 'child ok' in r.stdout, r.stdout[-3000:]
-	out = np.load(dst)
-	return out, json.loads(str(out['notes']))
-
-
-def got(out, name):
-	return tuple(out['{}.{}'.format(name, k)] if '{}.{}'.format(name, k) in out.files else None for k in child.KEYS)
-
-
-def same(a, b, what=''):
-	"""Two de results equal bit for bit: dtypes, shapes, every array."""
-	for k, x, y in zip(child.KEYS, a, b):
-		if x is None or y is None:
-			assert x is None and y is None, (what, k)
-			continue
-		assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), (what, k, float(np.abs(x.astype(np.float64) - y.astype(np.float64)).max()) if x.size else 0.)
-
-
-def untested_rows_exact(res, rows):
-	p, gam, a, vg, vt = res
-	assert (p[rows] == 1).all() and (gam[rows] == 0).all() and (vg[rows] == 0).all() and (vt[rows] == 0).all() and (a is None or (a[rows] == 0).all())
 
 
 def inflate(res, ng0, kept):

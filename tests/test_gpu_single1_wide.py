@@ -19,6 +19,7 @@ import pytest
 import oracle
 import s1_reference as s1
 import s1_wide as sw
+from cabi_harness import held
 from test_gpu_parity import close, p_close
 from test_gpu_s1_stages import F32, F64, I32, I64, Buf, _env, _sync, note, plans, same, twice
 
@@ -147,16 +148,6 @@ def screen(nc, kind, seed=0):
 	if kind == 'onehot':
 		dc[:6] = rng.integers(6, size=N)[None] == np.arange(6)[:, None]
 	return dx, dy, dc
-
-
-def held(got, want, dtype, nc):
-	tol = 1e-6 if dtype == F32 else 1e-9
-	assert got[0].dtype == dtype
-	assert p_close(got[0], want[0], 1e-6), 'P'
-	assert close(got[1], want[1], tol, 1e-12), 'gamma'
-	assert close(got[2], want[2], max(tol, 1e-8), 1e-9), 'alpha'
-	assert close(got[3], want[3], tol), 'varx'
-	assert close(got[4], want[4], tol), 'vary'
 
 
 @pytest.mark.parametrize('nc,kind,dtype', [(9, 'plain', F32), (9, 'dup', F64), (12, 'onehot', F32), (12, 'plain', F64), (32, 'dup', F32), (32, 'onehot', F64)])

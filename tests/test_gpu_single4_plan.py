@@ -2,7 +2,7 @@
 child process in which torch cannot be imported (tests/single4_plan_child.py); this process holds what comes back to the reference's golden vectors, to the oracle's
 per-grouping loop and to the whole-problem entry nrm_association_tests_single4_host on the rows de keeps.
 
-Bars: `_same` of tests/test_gpu_single4_rank_deficient.py -- P-values 1e-6 relative, gamma 1e-9 (floor 1e-12), varg and vart 1e-9, alpha 1e-9 (floor 1e-9).  The
+Bars: same_bars of tests/cabi_harness.py (`_same` here) -- P-values 1e-6 relative, gamma 1e-9 (floor 1e-12), varg and vart 1e-9, alpha 1e-9 (floor 1e-9).  The
 plan and the entry run one step record (csrc/nrm_single4_step.h) on the same lists: P, gamma, varg and vart are equal bit for bit; alpha is summed on the device in
 another order than the entry sums it on the host and is held to the bars.  A replay runs the launches of an eager step: bit for bit.  The ones and zeros of rows
 that are not tested are exact.
@@ -10,36 +10,25 @@ that are not tested are exact.
 The screen (tests/single1_plan_child.py::screen): 65 groupings x 69 genes x 2051 cells with entries set with probability 1 / 65 -- nx no multiple of the row tile, a
 ragged last chunk of cells -- and two rows de drops, one all zeros and one all ones.  tests/test_single4_plan_cpu.py holds every screen used here to the conditions
 these tests rely on."""
-import json
+import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle
 import single4_plan_child as child
+from cabi_harness import got, same, untested_rows_exact
+from cabi_harness import run_child as _run_child
+from cabi_harness import same_bars as _same
 from normalisr_amd import cplan
-from test_gpu_single1_plan import got, same, untested_rows_exact
-from test_gpu_single4_rank_deficient import _same
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+run_child = functools.partial(_run_child, 'single4_plan_child.py')  # (timeout=240)
 KEPT = child.kept_rows()
 DROPPED = [child.ZERO_ROW, child.ONES_ROW]
 FORMS = ['dense', 'scipy', 'devcsr', 'devcsr_data']  # (devcsr: no data array, every entry is 1; devcsr_data: with one)
-
-
-def run_child(tmp_path, scenario, arrays, job, env=None, timeout=240):
-	src, dst = str(tmp_path / (scenario + '_in.npz')), str(tmp_path / (scenario + '_out.npz'))
-	np.savez(src, job=np.array(json.dumps(job)), **arrays)
-	r = subprocess.run([sys.executable, os.path.join(HERE, 'single4_plan_child.py'), scenario, src, dst], env=dict(os.environ, **(env or {})), stdout=subprocess.PIPE,
-					   stderr=subprocess.STDOUT, text=True, timeout=timeout)
-	assert r.returncode == 0 and 'child ok' in r.stdout, r.stdout[-3000:]
-	out = np.load(dst)
-	return out, json.loads(str(out['notes']))
 
 
 def inflate(res, ng0, kept):

@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 
 import oracle
+from cabi_harness import close, p_close
+from cabi_harness import same_bars as _same
 from conftest import relerr
-from test_gpu_parity import close, p_close
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,12 +26,6 @@ def _no_host_loop(monkeypatch):
 		raise AssertionError('the per-grouping algorithm on the host was taken')
 	monkeypatch.setattr(single4, '_per_grouping_host', refuse)
 	monkeypatch.setattr(single4, '_pairwise_host', refuse)
-
-
-def _same(got, p, gam, varg, vart, alpha=None, vtol=1e-9):
-	assert p_close(got[0], p) and close(got[1], gam, vtol, 1e-12) and close(got[3], varg, vtol) and close(got[4], vart, vtol)
-	if alpha is not None:
-		assert close(got[2], alpha, vtol, 1e-9)
 
 
 @pytest.mark.parametrize('route', ['auto', 'force'])

@@ -7,15 +7,11 @@
   * (c) every guard case has pairs of all three classes, a gene that must be hit and one that must not, and no undecided pair.
 
 The last test prints the worst ratio of emulation to unslackened bound per stage: s4_reference.SLACK is settled from it."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import s4_reference as s4
-from conftest import ROOT
+from cabi_harness import build_and_run_host_program
 
 WORST = {}
 F64, F32 = np.float64, np.float32
@@ -55,24 +51,11 @@ def _launches():
 
 def test_schedule_port_equals_gram_plan_under_address_and_ub_sanitizers(tmp_path):
 	"""Every field of GramSched and every workgroup's piece list (checksum), for the gram cases and 60 random launches each at 512, 608 and 208 slots."""
-	gxx = shutil.which('g++')
-	if gxx is None:
-		pytest.skip('no g++')
-	flags = ['-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-	probe = tmp_path / 'probe.cpp'
-	probe.write_text('int main() { return 0; }\n')
-	r = subprocess.run([gxx] + flags + ['-o', str(tmp_path / 'probe'), str(probe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-	if r.returncode != 0:
-		pytest.skip('g++ cannot build with -fsanitize=address,undefined here: ' + r.stdout[-200:])
-	exe = str(tmp_path / 'gram_port')
-	r = subprocess.run([gxx] + flags + ['-o', exe, os.path.join(ROOT, 'tests', 'host', 'gram_port_sanitize.cpp')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-	assert r.returncode == 0, r.stdout[-3000:]
 	launches = _launches()
 	inp = tmp_path / 'launches.txt'
 	inp.write_text(''.join(' '.join(str(v) for v in l) + '\n' for l in launches))
-	r = subprocess.run([exe, str(inp)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-	assert r.returncode == 0 and 'gram schedule printed: %d launches' % len(launches) in r.stdout, r.stdout[-2000:]
-	lines = r.stdout.strip().split('\n')[:-1]
+	out = build_and_run_host_program(tmp_path, ['tests/host/gram_port_sanitize.cpp'], 'gram schedule printed: %d launches' % len(launches), args=[str(inp)], may_skip=True)
+	lines = out.strip().split('\n')[:-1]
 	assert len(lines) == len(launches)
 	for l, line in zip(launches, lines):
 		s = s4.gram_schedule(*l[:9], whole=bool(l[9]))

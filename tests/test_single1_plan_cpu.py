@@ -2,51 +2,23 @@
 normalisr_amd.cplan.Single1Plan binds it without torch, the constructor and create refuse bad arguments -- create before any device call, in the reference's words --,
 and the host arithmetic of the checks runs under ASan + UBSan in a program of its own."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from cabi_harness import assert_plan_names, binds_without_torch, build_and_run_host_program
+from cabi_harness import vp as _vp
 from normalisr_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_CALLS = ('create', 'design', 'upload', 'step', 'check', 'results', 'device_results', 'stream', 'info', 'time', 'destroy')
 
 
-def _vp(a):
-	return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
 def test_single1_plan_names_declared_and_exported():
-	hdr = open(os.path.join(ROOT, 'include', 'normalisr_hip.h')).read()
-	declared = set(re.findall(r'\b(nrm_[a-z0-9_]+)\s*\(', hdr))
-	lib = ctypes.CDLL(_lib.LIB_PATH)
-	names = ['nrm_single1_plan_' + c for c in PLAN_CALLS]
-	assert len(names) == 11
-	for name in names:
-		assert name in declared, name
-		assert name in _lib.exported_symbols(), name
-		assert hasattr(lib, name), name
-	assert declared == set(_lib.exported_symbols())
+	assert len(assert_plan_names('nrm_single1_plan_', PLAN_CALLS)) == 11
 
 
 def test_single1_plan_binds_without_torch():
-	code = ("import sys; sys.modules['torch'] = None\n"
-			"sys.path.insert(0, {!r})\n"
-			"from normalisr_amd import cplan, _lib\n"
-			"assert callable(cplan.Single1Plan)\n"
-			"for m in ('step', 'check', 'results', 'qvalues', 'device_results', 'update', 'set_design', 'time', 'info', 'close', '__enter__', '__exit__'):\n"
-			"    assert callable(getattr(cplan.Single1Plan, m)), m\n"
-			"lib = _lib.load()\n"
-			"assert lib.nrm_single1_plan_destroy(None) == 0\n"
-			"assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]\n"
-			"print('single1 plan without torch ok')\n").format(ROOT)
-	r = subprocess.run([sys.executable, '-c', code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-	assert r.returncode == 0 and 'single1 plan without torch ok' in r.stdout, r.stdout[-2000:]
+	binds_without_torch(('Single1Plan', ), ('step', 'check', 'results', 'qvalues', 'device_results', 'update', 'set_design', 'time', 'info', 'close', '__enter__', '__exit__'), 'nrm_single1_plan_destroy')
 
 
 def _problem(n=12, nc=2):
@@ -152,17 +124,8 @@ def test_single1_plan_constructor_validation():
 
 
 def _sanitized_program(tmp_path, name, says):
-	"""tests/host/NAME.cpp -- a program with its own main over csrc/nrm_single1_plan_args.h -- built by g++ with -fsanitize=address,undefined and run directly: nothing
-	loaded into python runs under a sanitizer."""
-	gxx = shutil.which('g++')
-	assert gxx is not None, 'g++ is needed to build the host arithmetic'
-	exe = str(tmp_path / name)
-	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-pthread', '-w',
-						'-x', 'c++', os.path.join(ROOT, 'normalisr_amd', 'csrc', 'nrm_small_pinv.hip'), os.path.join(ROOT, 'tests', 'host', name + '.cpp'), '-o', exe],
-					   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-	assert r.returncode == 0, r.stdout[-3000:]
-	r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-	assert r.returncode == 0 and says in r.stdout, r.stdout[-3000:]
+	"""tests/host/NAME.cpp -- a program with its own main over csrc/nrm_single1_plan_args.h -- beside csrc/nrm_small_pinv.hip (cabi_harness.build_and_run_host_program)."""
+	build_and_run_host_program(tmp_path, ['normalisr_amd/csrc/nrm_small_pinv.hip', 'tests/host/{}.cpp'.format(name)], says)
 
 
 def test_single1_plan_argument_checks_under_address_and_ub_sanitizers(tmp_path):

@@ -3,51 +3,23 @@ normalisr_amd.cplan.Single4Plan binds it without torch, the constructor and crea
 the checks run under ASan + UBSan in a program of its own, and every screen tests/test_gpu_single4_plan.py builds is held, in numpy and the oracle, to the conditions
 those tests rely on."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from cabi_harness import assert_plan_names, binds_without_torch, build_and_run_host_program
+from cabi_harness import vp as _vp
 from normalisr_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_CALLS = ('create', 'design', 'upload', 'step', 'check', 'results', 'device_results', 'stream', 'info', 'time', 'destroy')
 
 
-def _vp(a):
-	return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
 def test_single4_plan_names_declared_and_exported():
-	hdr = open(os.path.join(ROOT, 'include', 'normalisr_hip.h')).read()
-	declared = set(re.findall(r'\b(nrm_[a-z0-9_]+)\s*\(', hdr))
-	lib = ctypes.CDLL(_lib.LIB_PATH)
-	names = ['nrm_single4_plan_' + c for c in PLAN_CALLS]
-	assert len(names) == 11
-	for name in names:
-		assert name in declared, name
-		assert name in _lib.exported_symbols(), name
-		assert hasattr(lib, name), name
-	assert declared == set(_lib.exported_symbols())
+	assert len(assert_plan_names('nrm_single4_plan_', PLAN_CALLS)) == 11
 
 
 def test_single4_plan_binds_without_torch():
-	code = ("import sys; sys.modules['torch'] = None\n"
-			"sys.path.insert(0, {!r})\n"
-			"from normalisr_amd import cplan, _lib\n"
-			"assert callable(cplan.Single4Plan)\n"
-			"for m in ('step', 'check', 'results', 'qvalues', 'device_results', 'update', 'set_design', 'time', 'info', 'close', '__enter__', '__exit__'):\n"
-			"    assert callable(getattr(cplan.Single4Plan, m)), m\n"
-			"lib = _lib.load()\n"
-			"assert lib.nrm_single4_plan_destroy(None) == 0\n"
-			"assert sys.modules['torch'] is None and not [m for m in sys.modules if m.startswith('torch.')]\n"
-			"print('single4 plan without torch ok')\n").format(ROOT)
-	r = subprocess.run([sys.executable, '-c', code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-	assert r.returncode == 0 and 'single4 plan without torch ok' in r.stdout, r.stdout[-2000:]
+	binds_without_torch(('Single4Plan', ), ('step', 'check', 'results', 'qvalues', 'device_results', 'update', 'set_design', 'time', 'info', 'close', '__enter__', '__exit__'), 'nrm_single4_plan_destroy')
 
 
 def _problem(n=12, nc=2):
@@ -173,15 +145,7 @@ def test_single4_plan_argument_checks_under_address_and_ub_sanitizers(tmp_path):
 	"""csrc/nrm_single4_plan_args.h -- every check create makes before a device call, the library's own pseudo-inverse included -- beside
 	tests/host/single4_plan_args_sanitize.cpp: a program with its own main, built by g++ with -fsanitize=address,undefined and run directly.  Nothing loaded into
 	python runs under a sanitizer."""
-	gxx = shutil.which('g++')
-	assert gxx is not None, 'g++ is needed to build the host arithmetic'
-	exe = str(tmp_path / 'single4_plan_args_sanitize')
-	r = subprocess.run([gxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', '-pthread', '-w',
-						'-x', 'c++', os.path.join(ROOT, 'normalisr_amd', 'csrc', 'nrm_small_pinv.hip'), os.path.join(ROOT, 'tests', 'host', 'single4_plan_args_sanitize.cpp'), '-o', exe],
-					   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-	assert r.returncode == 0, r.stdout[-3000:]
-	r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-	assert r.returncode == 0 and 'single4 plan args ok' in r.stdout, r.stdout[-3000:]
+	build_and_run_host_program(tmp_path, ['normalisr_amd/csrc/nrm_small_pinv.hip', 'tests/host/single4_plan_args_sanitize.cpp'], 'single4 plan args ok')
 
 
 def _residuals(rows, dc):

@@ -13,14 +13,13 @@ Per-kernel times come from a kernel trace of each child by itself (profiles/c_pl
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/time_c_plan.py --child c_plan --data DIR/c2
 
 Usage: time_c_plan.py [--rounds 3] [--steps 20] [--reps 5] [--warmup 5] [--out profiles/c_plan.json]"""
-import argparse
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
+
+import plan_timing as pt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -68,51 +67,24 @@ def child_c_plan(args):
 	return dict(ms_per_step=ms, guard_hits=hits, guard_worst=worst, info=info)
 
 
-def run_child(kind, args):
-	cmd = [sys.executable, os.path.abspath(__file__), '--child', kind, '--data', args.data, '--steps', str(args.steps), '--reps', str(args.reps), '--warmup', str(args.warmup)]
-	r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.child_timeout)
-	if r.returncode != 0:
-		raise RuntimeError('{} child failed ({}):\n{}'.format(kind, r.returncode, r.stderr[-3000:]))
-	return json.loads(r.stdout.strip().splitlines()[-1])
-
-
-def side(runs):
-	fig = [float(np.median(r['ms_per_step'])) for r in runs]
-	return dict(rounds_ms=[round(v, 4) for v in fig], median_ms=round(float(np.median(fig)), 4), min_ms=round(min(fig), 4), max_ms=round(max(fig), 4),
-				reps_ms=[[round(v, 4) for v in r['ms_per_step']] for r in runs], guard_hits=[r['guard_hits'] for r in runs], guard_worst=max(r['guard_worst'] for r in runs))
+def with_guard(runs):
+	return dict(pt.side(runs, 'ms_per_step'), guard_hits=[r['guard_hits'] for r in runs], guard_worst=max(r['guard_worst'] for r in runs))
 
 
 def main():
-	ap = argparse.ArgumentParser()
-	ap.add_argument('--rounds', type=int, default=3)
-	ap.add_argument('--steps', type=int, default=20)
-	ap.add_argument('--reps', type=int, default=5)
-	ap.add_argument('--warmup', type=int, default=5)
-	ap.add_argument('--out', default='profiles/c_plan.json')
-	ap.add_argument('--child', default=None)
-	ap.add_argument('--data', default=None)
-	ap.add_argument('--child-timeout', type=int, default=240)
-	args = ap.parse_args()
+	args = pt.arg_parser('profiles/c_plan.json', 240).parse_args()
 	if args.child:
 		print(json.dumps(dict(yardstick=child_yardstick, c_plan=child_c_plan)[args.child](args)))
 		return
-	with tempfile.TemporaryDirectory() as tmp:
-		args.data = os.path.join(tmp, 'c2')
-		ys, cs = [], []
-		for _ in range(args.rounds):
-			ys.append(run_child('yardstick', args))
-			cs.append(run_child('c_plan', args))
-	y, c = side(ys), side(cs)
+	ys, cs = pt.alternate(__file__, args, ('yardstick', 'c_plan'), 'c2')
+	y, c = with_guard(ys), with_guard(cs)
 	c['info'] = cs[-1]['info']
 	spread = y['max_ms'] - y['min_ms']
 	rec = dict(shape=dict(genes=NG, cells=N, dtype='float32', covariates=3, seed=SEED), rounds=args.rounds, steps=args.steps, reps=args.reps, warmup=args.warmup,
 			   yardstick=dict(what='normalisr_amd.distributed.CoexPlan.step (torch), device events around the steps', **y),
 			   c_plan=dict(what='cplan.CoexPlan.time: nrm_coex_plan_time, one hipGraphLaunch per step, no torch in the process', **c),
 			   margin_ms=round(spread, 4), within_margin=bool(c['median_ms'] <= y['median_ms'] + spread))
-	os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-	with open(args.out, 'w') as f:
-		f.write(json.dumps(rec, indent=1) + '\n')
-	print(json.dumps(rec))
+	pt.write(rec, args.out)
 
 
 if __name__ == '__main__':

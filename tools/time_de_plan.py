@@ -13,16 +13,14 @@ kernel trace of the c_plan child by itself (`--kernel-stats` names its CSV; prof
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/time_de_plan.py --child c_plan --data DIR/c4
 
 Usage: time_de_plan.py [--rounds 3] [--steps 20] [--reps 5] [--warmup 5] [--kernel-stats CSV] [--out profiles/de_plan.json]"""
-import argparse
-import csv
 import json
 import os
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
+
+import plan_timing as pt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -88,69 +86,21 @@ def child_c_plan(args):
 	return out
 
 
-def run_child(kind, args):
-	cmd = [sys.executable, os.path.abspath(__file__), '--child', kind, '--data', args.data, '--steps', str(args.steps), '--reps', str(args.reps), '--warmup', str(args.warmup)]
-	r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.child_timeout)
-	if r.returncode != 0:
-		raise RuntimeError('{} child failed ({}):\n{}'.format(kind, r.returncode, r.stderr[-3000:]))
-	return json.loads(r.stdout.strip().splitlines()[-1])
-
-
-def side(runs, key):
-	fig = [float(np.median(r[key])) for r in runs]
-	return dict(rounds_ms=[round(v, 4) for v in fig], median_ms=round(float(np.median(fig)), 4), min_ms=round(min(fig), 4), max_ms=round(max(fig), 4),
-				reps_ms=[[round(v, 4) for v in r[key]] for r in runs])
-
-
-def own_kernels_ms(path):
-	"""Mean time per launch of the plan's own kernels (one launch of each per step) from a `rocprofv3 --kernel-trace --stats` CSV of the c_plan child."""
-	per = {}
-	with open(path) as f:
-		for row in csv.DictReader(f):
-			for k in OWN_KERNELS:
-				if k + '<' in row['Name'] or k + '(' in row['Name']:
-					per[k] = per.get(k, 0.0) + float(row['AverageNs']) / 1e6
-	return per
-
-
 def main():
-	ap = argparse.ArgumentParser()
-	ap.add_argument('--rounds', type=int, default=3)
-	ap.add_argument('--steps', type=int, default=20)
-	ap.add_argument('--reps', type=int, default=5)
-	ap.add_argument('--warmup', type=int, default=5)
-	ap.add_argument('--out', default='profiles/de_plan.json')
-	ap.add_argument('--kernel-stats', default=None, help='kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of the c_plan child')
-	ap.add_argument('--child', default=None)
-	ap.add_argument('--data', default=None)
-	ap.add_argument('--child-timeout', type=int, default=420)
-	args = ap.parse_args()
+	args = pt.arg_parser('profiles/de_plan.json', 420, warmup=5, kernel_stats=True).parse_args()
 	if args.child:
 		print(json.dumps(dict(yardstick=child_yardstick, c_plan=child_c_plan)[args.child](args)))
 		return
-	with tempfile.TemporaryDirectory() as tmp:
-		args.data = os.path.join(tmp, 'c4')
-		ys, cs = [], []
-		for _ in range(args.rounds):
-			ys.append(run_child('yardstick', args))
-			cs.append(run_child('c_plan', args))
-	y, c, cq, cold = side(ys, 'ms_per_step'), side(cs, 'step'), side(cs, 'step_q'), side(cs, 'cold')
+	ys, cs = pt.alternate(__file__, args, ('yardstick', 'c_plan'), 'c4')
+	y, c, cq, cold = pt.side(ys, 'ms_per_step'), pt.side(cs, 'step'), pt.side(cs, 'step_q'), pt.side(cs, 'cold')
 	c['info'], cq['info'] = cs[-1]['step_info'], cs[-1]['step_q_info']
-	spread = y['max_ms'] - y['min_ms']
-	own = own_kernels_ms(args.kernel_stats) if args.kernel_stats else None
-	own_ms = None if own is None else round(sum(own.values()), 4)
 	rec = dict(shape=dict(groupings=NX, genes=NY, cells=N, dtype='float32', covariates=NC, seed=SEED), rounds=args.rounds, steps=args.steps, reps=args.reps, warmup=args.warmup,
 			   yardstick=dict(what='normalisr_amd.distributed.DePlan.step (torch), device events around the steps', **y),
 			   c_plan=dict(what='cplan.DePlan.time without alpha or q: nrm_de_plan_time, one hipGraphLaunch per step, no torch in the process', **c),
 			   c_plan_q=dict(what='the same with q=True: nrm_bh over all P-values inside the step', **cq),
 			   c_plan_cold=dict(what='set_design + step + check by the host clock, a new design every step', **cold),
-			   yardstick_spread_ms=round(spread, 4), own_kernels_ms=own, own_kernels_from=args.kernel_stats,
-			   margin_ms=None if own_ms is None else round(spread + own_ms, 4),
-			   within_margin=None if own_ms is None else bool(c['median_ms'] <= y['median_ms'] + spread + own_ms))
-	os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-	with open(args.out, 'w') as f:
-		f.write(json.dumps(rec, indent=1) + '\n')
-	print(json.dumps(rec))
+			   **pt.margin(y, c, OWN_KERNELS, args.kernel_stats))
+	pt.write(rec, args.out)
 
 
 if __name__ == '__main__':

@@ -7,7 +7,6 @@ Then the whole-command wall time of `normalisr lcpm` and `normalisr fitvar` on .
 line's default against NRM_HOST_ENTRY=0), alternating as well: the share of torch's import.  Writes one JSON record.
 
 Usage: time_front_entries.py [--rounds 3] [--reps 5] [--warmup 2] [--out profiles/front_entries.json]"""
-import argparse
 import json
 import os
 import subprocess
@@ -16,6 +15,8 @@ import tempfile
 import time
 
 import numpy as np
+
+import plan_timing as pt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -69,20 +70,6 @@ def child(args):
 	return rec
 
 
-def run_child(kind, args):
-	cmd = [sys.executable, os.path.abspath(__file__), '--child', kind, '--reps', str(args.reps), '--warmup', str(args.warmup)]
-	r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.child_timeout)
-	if r.returncode != 0:
-		raise RuntimeError('{} child failed ({}):\n{}'.format(kind, r.returncode, r.stderr[-3000:]))
-	return json.loads(r.stdout.strip().splitlines()[-1])
-
-
-def side(runs, op):
-	fig = [float(np.median(r[op])) for r in runs]
-	return dict(rounds_ms=[round(v, 3) for v in fig], median_ms=round(float(np.median(fig)), 3), min_ms=round(min(fig), 3), max_ms=round(max(fig), 3),
-				reps_ms=[r[op] for r in runs])
-
-
 def commands(rounds, tmp):
 	"""Wall time of `python -m normalisr_amd lcpm | fitvar` as child processes on .npy files of the G18 size, the default route and NRM_HOST_ENTRY=0 alternating."""
 	g = np.load(os.path.join(ROOT, 'tests', 'golden', 'G18_front.npz'))
@@ -110,33 +97,20 @@ def commands(rounds, tmp):
 
 
 def main():
-	ap = argparse.ArgumentParser()
-	ap.add_argument('--rounds', type=int, default=3)
-	ap.add_argument('--reps', type=int, default=5)
-	ap.add_argument('--warmup', type=int, default=2)
-	ap.add_argument('--out', default='profiles/front_entries.json')
-	ap.add_argument('--child', default=None)
-	ap.add_argument('--child-timeout', type=int, default=400)
-	args = ap.parse_args()
+	args = pt.arg_parser('profiles/front_entries.json', 400, warmup=2, steps=None).parse_args()
 	if args.child:
 		print(json.dumps(child(args)))
 		return
-	es, ts = [], []
-	for _ in range(args.rounds):
-		ts.append(run_child('torch', args))
-		es.append(run_child('entries', args))
+	ts, es = pt.alternate(__file__, args, ('torch', 'entries'))
 	rec = dict(shape=dict(genes=NG, cells=N, dtype='int32', covariates=8, seed=SEED, qc_params=QC_PARAMS), rounds=args.rounds, reps=args.reps, warmup=args.warmup,
 			   what='numpy in -> numpy out wall time per call (time.perf_counter), one process per route and round', check=dict(entries=es[-1]['check'], torch=ts[-1]['check']))
 	for op in ('lcpm', 'compute_var', 'qc_reads'):
-		e, t = side(es, op), side(ts, op)
+		e, t = pt.side(es, op, 3), pt.side(ts, op, 3)
 		spread = max(t['max_ms'] - t['min_ms'], e['max_ms'] - e['min_ms'])
 		rec[op] = dict(entries=e, torch=t, spread_ms=round(spread, 3), above_spread=bool(e['median_ms'] > t['median_ms'] + spread))
 	with tempfile.TemporaryDirectory() as tmp:
 		rec['commands_g18_npy'] = commands(args.rounds, tmp)
-	os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-	with open(args.out, 'w') as f:
-		f.write(json.dumps(rec, indent=1) + '\n')
-	print(json.dumps(rec))
+	pt.write(rec, args.out)
 
 
 if __name__ == '__main__':
