@@ -154,6 +154,7 @@ int64_t nrm_gram_workspace_bytes(void);
  *   nrm_gram_i8_band: as nrm_gram_f64_band with quantised operands (d_qb == d_qa, d_eb == d_ea for symmetric problems).
  *       plane_*_bytes: distance between an operand's digit planes, 0 = dense (m_pad / 32 * ceil(k_pad / 32) KB); an operand may be
  *       a block of 32-row groups of a larger quantised matrix: pass the pointer of its first group and the larger matrix's pitch.
+ *       d_ea 16-byte aligned (the kernel reads four row exponents at a time; any 32-row group of an aligned array is), ldd < 2^27.
  */
 int64_t nrm_quant_bytes(int64_t rows_pad, int64_t k_pad, int nslices);
 int nrm_quantize_rows(const double* d_x, int64_t rows_pad, int64_t k_pad, int64_t ldx, int nslices, void* d_q, int32_t* d_exp,

@@ -11,8 +11,8 @@
 // pairs with s + t < NS - 1 are dropped (each sits near 2^-(8 NS + 2) of full scale); the
 // NS (NS + 1) / 2 pairs kept are accumulated into ONE int32 accumulator set per weight w = s + t (NS sets): |d d'| <= 2^14,
 // at most NS pairs per set, so 2^14 NS K < 2^31 bounds a chunk to K <= 16 384 cells, after which the sets are combined in
-// fp64 (sum_w acc_w 256^w formed as two exact 64-bit integers joined by one fma: the correctly rounded exact value) and added
-// to the output.  Chunks and the partial pieces of the
+// fp64 (sum_w acc_w 256^w formed as two exact integers below 2^48, held in fp64, joined by one fma: the correctly rounded exact
+// value) and added to the output.  Chunks and the partial pieces of the
 // stream-K schedule are combined in fp64 in a fixed order: bitwise reproducible from run to run like the fp64 kernel.
 // Accuracy: the dropped digit products are the error, not the quantisation -- measured |delta r| <= 3e-14 (2e-15 typical at
 // 10 000 Gaussian cells; it grows with (max / rms)^2 of the rows and as 1 / sqrt(cells)), P-values to 4e-10 relative; on the
@@ -34,6 +34,14 @@
 // removing barrier and vmcnt waits altogether gains only 3 %: lockstep is not the cost); issuing the refill from waves 4-7 half
 // way through their MFMAs (4.05 ms, the branch breaks the MFMA block); a memory-clobbering asm between operand reads and MFMAs
 // (7.1 ms: every read drains first); s_setprio(1) around the MFMA block (11 ms).
+// The flush (end of a piece, and every QCHUNK k-steps inside one) is a burst per 32 x 32 sub-tile: the 16 row exponents in 4 loads of 16 bytes, one
+// wait, then 16 outputs of ~14 instructions (6 v_cvt_f64_i32, 5 fma, ldexp, address) stored back to back -- or, where the output is added to
+// (later chunks of a piece, accumulating launches), 8 old values requested at a time ahead of their use; the choice between the two bodies is
+// wave-uniform and taken once per sub-tile.  Addresses are a scalar base plus one 32-bit lane offset.  No scratch between the k loop and the end of
+// the flush (NS = 6: 8 B per lane in the whole kernel, one register of the prologue; NS = 5: none), none and no lane moves in either k loop.
+// Before, every output loaded its row exponent, waited (vmcnt(0): for the previous output's store as well), combined in 64-bit integers and
+// branched: 32 dependent round trips per wave and flush.  K2 alone at 5000 genes x 10 000 cells: 1.925 -> 1.902 ms, of 0.035 that no flush at
+// all would save (QI_EXP=8; DESIGN.md section 4, profiles/k2_flush_ab.txt).
 #include <type_traits>
 #include "nrm_gram_sched.h"
 #include "nrm_digits.h"
@@ -46,7 +54,7 @@
 #define QI_EDGE 0    // 1: edge tiles on four waves of one sub-tile each (round 6: built, parity-green, measured NOT to help -- see gram_piece_i8; kept for A/B builds)
 #endif
 #ifndef QI_EXP
-#define QI_EXP 0     // timing experiments (tools/build_exp.sh): 1 no DMA, 2 every DMA from k-steps 0-3 (L2 resident), 4 no barrier
+#define QI_EXP 0     // timing experiments (tools/build_exp.sh): 1 no DMA, 2 every DMA from k-steps 0-3 (L2 resident), 4 no barrier, 8 no flush
 #endif
 
 typedef int i4_t __attribute__((ext_vector_type(4)));
@@ -251,31 +259,83 @@ __device__ __forceinline__ void gram_piece_i8(const char* __restrict__ QA, const
 		cbase = C + (int64_t)row_w * ldc + col_w;
 		pitch = ldc;
 	}
-	// the lane's own part of the output address and of the row exponents' (column lane & 31, rows + 4 (lane >> 5)), once per piece
-	cbase += (int64_t)(4 * (lane >> 5)) * pitch + (lane & 31);
-	const int* ea_l = ea + row_w + 4 * (lane >> 5);
+	// Output and row-exponent addresses are a wave-uniform 64-bit base plus the lane's 32-bit byte offset (column lane & 31, rows + 4 (lane >> 5)), the
+	// form a global load or store takes with a scalar base: ONE vector register addresses all 32 outputs of a flush, where per-lane 64-bit pointers
+	// cost a register pair per output in a kernel that sits at the register cap (the pitch is below 2^27 doubles: gram_i8_impl)
+	const unsigned c_lane = ((unsigned)(4 * (lane >> 5)) * (unsigned)pitch + (unsigned)(lane & 31)) * 8u;
+	const unsigned e_lane = 16u * (unsigned)(lane >> 5);
+	const int* ea_w = ea + row_w;
 	const int eb_l = hw ? eb[edge_tj * GN + (lane & 31)] : eb_t[b_blk * 32 + (lane & 31)];
+	// The flush as a burst: nothing in it waits for memory between two outputs.  (As a loop of load exponent - wait - combine - branch - store it was 32
+	// dependent round trips per wave and flush, vmcnt counting the previous output's store as well, with all eight waves of the CU in it.)
 	auto flush = [&](bool first) {
+		if (QI_EXP & 8) {  // timing only: no flush at all (the accumulators stay live, or the MFMAs would go with it); outputs are garbage
+#pragma unroll
+			for (int w = 0; w < NS; w++)
+#pragma unroll
+				for (int i = 0; i < 2; i++) asm volatile("" ::"v"(acc[w][i]));
+			return;
+		}
+		const bool plain = first && !(accumulate && !slab);  // wave-uniform: two straight-line bodies, no branch per output
+		// (the lane offsets pass through an empty asm: seen as invariants of the k loop, the 32 output addresses of the flush inside it are formed per lane
+		// ahead of the loop, spilled, and reloaded one by one between the stores; the pitch likewise, or the 32 scalar row bases are, and the k loop spills
+		// scalar registers to lanes in the MFMA stream)
+		unsigned c_off = c_lane, e_off = e_lane;
+		int64_t row_pitch = pitch;
+		asm volatile("" : "+v"(c_off), "+v"(e_off), "+s"(row_pitch));
+		auto out = [&](int i, int q) {
+			return reinterpret_cast<double*>(reinterpret_cast<char*>(cbase + (int64_t)(i * 32 + (q & 3) + 8 * (q >> 2)) * row_pitch) + c_off);
+		};
 #pragma unroll
 		for (int i = 0; i < 2; i++) {
 			if (!want[i]) continue;
+			// the sub-tile's row exponents first: rows (q & 3) + 8 (q >> 2) + 32 i (+ 4 (lane >> 5)) are four consecutive ints at a 16-byte-aligned index,
+			// so 4 loads of 16 bytes and one wait where there were 16 loads with a wait each; the operand registers are dead here.  (Both sub-tiles'
+			// exponents ahead of the first would spare the second wait, which also waits for the first sub-tile's stores -- vmcnt counts in order --, but
+			// 16 registers more beside the 192 accumulators spill in the read-modify-write body and change the k loop's code: built, read, not kept.)
+			i4_t ex[4];
 #pragma unroll
-			for (int q = 0; q < 16; q++) {
-				const int rr = i * 32 + (q & 3) + 8 * (q >> 2);
-				// sum_w acc_w 256^w as two exact 64-bit integers (weights 0..2 and 3..NS-1: each below 2^49), so that the one
-				// fma that joins them is the only rounding: the chunk's value is the correctly rounded exact integer
-				long long lo = 0, hi = 0;
+			for (int g = 0; g < 4; g++) ex[g] = *reinterpret_cast<const i4_t*>(reinterpret_cast<const char*>(ea_w + i * 32 + 8 * g) + e_off);
+			__builtin_amdgcn_sched_barrier(0);
+			// sum_w acc_w 256^w as two exact integers held in fp64 (weights 0..2 and 3..NS-1: every product and partial sum is an integer below 2^48,
+			// so each fma is exact), joined by the one fma that rounds: the chunk's value is the correctly rounded exact integer.
+			// OWN: the accumulator goes through an empty asm, so that the read-modify-write body shares no subexpression with the plain one -- shared,
+			// the conversions of all 16 outputs are computed ahead of the branch between the bodies and their results spilled
+			auto value = [&](int q, auto own) {
+				double a[6];
 #pragma unroll
 				for (int w = 0; w < NS; w++) {
-					if (w < 3)
-						lo += (long long)acc[w][i][q] << (8 * w);
-					else
-						hi += (long long)acc[w][i][q] << (8 * (w - 3));
+					int t = acc[w][i][q];
+					if (decltype(own)::value) asm volatile("" : "+v"(t));
+					a[w] = (double)t;
 				}
-				double v = fma((double)hi, 16777216.0, (double)lo);
-				v = ldexp(v, ea_l[rr] + eb_l + 8 * (NS - 1));
-				double* o = cbase + (int64_t)rr * pitch;
-				*o = (first && !(accumulate && !slab)) ? v : *o + v;
+				const double lo = fma(a[2], 65536.0, fma(a[1], 256.0, a[0]));
+				double hi = fma(a[4], 256.0, a[3]);
+				if (NS == 6) hi = fma(a[NS - 1], 65536.0, hi);
+				return ldexp(fma(hi, 16777216.0, lo), ex[q >> 2][q & 3] + eb_l + 8 * (NS - 1));
+			};
+			// (sched_barrier: left alone the scheduler lifts all 96 conversions of a sub-tile to the top and spills their results -- and a scratch
+			// reload is a vmcnt wait between two stores again; two outputs at a time keep the fp64 pipe busy and fit the registers)
+			if (plain) {  // stores back to back
+#pragma unroll
+				for (int q = 0; q < 16; q++) {
+					*out(i, q) = value(q, std::false_type{});
+					if (q & 1) __builtin_amdgcn_sched_barrier(0);
+				}
+			} else {  // the old values requested before the first is used, half a sub-tile at a time: with all 16 in flight beside the 192 accumulators
+				      // and the exponents the first sub-tile spills, and a scratch reload is a wait between two stores again
+#pragma unroll
+				for (int h = 0; h < 16; h += 8) {
+					double old[8];
+#pragma unroll
+					for (int q = 0; q < 8; q++) old[q] = *out(i, h + q);
+					__builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+					for (int q = 0; q < 8; q++) {
+						*out(i, h + q) = old[q] + value(h + q, std::true_type{});
+						if (q & 1) __builtin_amdgcn_sched_barrier(0);
+					}
+				}
 			}
 		}
 	};
@@ -405,11 +465,13 @@ static int gram_i8_impl(const void* d_qa, const int32_t* d_ea, int64_t plane_a_b
 	NRM_REQUIRE(nslices == 5 || nslices == 6, "nrm_gram_i8: 5 or 6 slices");
 	NRM_REQUIRE(m_pad >= 0 && n_pad >= 0 && k_pad > 0 && m_pad % GM == 0 && n_pad % GN == 0, "nrm_gram_i8: sizes must be padded to %d", GM);
 	NRM_REQUIRE(ldd >= n_pad && ldd % 2 == 0, "nrm_gram_i8: pitch too small");
+	NRM_REQUIRE(ldd < (1 << 27), "nrm_gram_i8: pitch of 2^27 doubles or more (a lane's offset into its output rows is 32 bits)");
 	NRM_REQUIRE(!symmetric || m_pad == n_pad, "nrm_gram_i8: symmetric needs square output");
 	NRM_REQUIRE(row0 >= 0 && row0 <= row1 && row1 <= m_pad && row0 % (GSB * GM) == 0 && (row1 % (GSB * GM) == 0 || row1 == m_pad),
 				"nrm_gram_i8_band: rows [row0, row1) must be cut at multiples of %d", GSB * GM);
 	if (m_pad == 0 || n_pad == 0 || row0 == row1) return NRM_OK;
 	NRM_REQUIRE(d_qa && d_qb && d_ea && d_eb && d_dot && d_work, "nrm_gram_i8: null pointer");
+	NRM_REQUIRE((uintptr_t)d_ea % 16 == 0, "nrm_gram_i8: operand A's exponents must be 16-byte aligned (the flush reads them four at a time)");
 	if (g_num_cu_q == 0) {
 		int dev = 0;
 		NRM_HIP(hipGetDevice(&dev));
