@@ -459,6 +459,13 @@ int nrm_normvar_exp_probe(const double* d_x, int64_t count, double* d_out, void*
 int64_t nrm_normvar_device_covariates(void);
 int nrm_normvar_solve(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_lnw, const double* d_wt, const double* d_c, int64_t nc,
 					  int64_t ldc, double tol, int keepvar, double* d_mom, double* d_b, double* d_scale, int64_t* d_rank, int32_t* d_flags, void* stream);
+/* The variance-keeping scale is (dv / dv2)^wt_g with dv^2 = s2 / n - mean^2 and dv2^2 = (s2 - a . b) / n: differences of one-pass sums.  Where either difference is
+ * below 2^-20 of its minuend (a nearly flat weighted row, or one the covariates explain almost completely), keepvar != 0 and wt_g != 0, nrm_normvar_solve and the host
+ * route of nrm_normvar_host leave -1.0 in d_scale[g] (no computed scale is negative), and this entry replaces it by the scale from the reference's two-pass form,
+ * sum (y e - mean)^2 and sum (e (y - b . c))^2 over the row itself: a workgroup per gene that leaves at once when its gene is not marked.  Every other d_scale[g] keeps
+ * its bits.  Call it between the solve and nrm_normvar_apply, on the same stream; 1 <= nc <= nrm_wide_covariates(). */
+int nrm_normvar_rescale(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_lnw, const double* d_wt, const double* d_c, int64_t nc,
+						int64_t ldc, const double* d_b, double* d_scale, void* stream);
 /*
  * normvar with 64 .. nrm_wide_covariates() covariates (csrc/nrm_normvar_wide.hip), replacing the reference's per-gene pseudo-inverse and projection
  * (norm.py:154-163, called per gene from norm.py:232-259).  The host gives an orthonormal basis B (r, n) of the covariates' row space (normalisr_amd/norm.py:

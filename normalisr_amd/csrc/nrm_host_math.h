@@ -9,6 +9,7 @@
 #include "../../include/normalisr_hip.h"
 #include "nrm_jacobi.h"
 #include "nrm_jacobi_lanes.h"
+#include "nrm_nv_scale.h"
 
 void nrm_set_error(const char* fmt, ...);
 
@@ -228,12 +229,7 @@ static inline void nrm_normvar_coefficients(const double* mi, const double* hga,
 			hb[(size_t)(g * nc + q)] = t;
 			ab += a[q] * t;
 		}
-		if (keepvar) {
-			const double mean = hs1[(size_t)g] / (double)n;
-			const double dv = std::sqrt(std::fmax(hs2[(size_t)g] / (double)n - mean * mean, 0.0));  // norm.py:248-249
-			const double dv2 = std::sqrt(std::fmax(hs2[(size_t)g] - ab, 0.0) / (double)n);           // |y' - P y'|^2 = |y'|^2 - a . b
-			hscale[(size_t)g] = std::pow(dv / dv2, h_wt[g]);                                        // norm.py:259
-		}
+		if (keepvar) hscale[(size_t)g] = nrm_nv_scale(hs1[(size_t)g], hs2[(size_t)g], ab, (double)n, h_wt[g]);  // (NRM_NV_MARK where the sums have cancelled: nrm_normvar_rescale)
 	}
 }
 

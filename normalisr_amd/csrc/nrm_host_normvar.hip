@@ -120,6 +120,8 @@ extern "C" int nrm_normvar_host(const void* h_y, int y_dtype, int64_t rows, int6
 		NRM_TRY(nrm_normvar_solve(y.p, y_dtype, rows, n, n, lnw.as<double>(), wt.as<double>(), c.as<double>(), nc, n, tol, keepvar ? 1 : 0, mom.as<double>(), b.as<double>(),
 								  scale.as<double>(), rank.as<int64_t>(), flags.as<int32_t>(), st));
 	}
+	// genes whose one-pass variance sums have cancelled (csrc/nrm_nv_scale.h: marked by either route): their scale from the row itself
+	NRM_TRY(nrm_normvar_rescale(y.p, y_dtype, rows, n, n, lnw.as<double>(), wt.as<double>(), c.as<double>(), nc, n, b.as<double>(), scale.as<double>(), st));
 	// one pass writes the result, from b_g and the scale of either route
 	const size_t ob = (size_t)rows * n * nrm_esize(out_dtype);
 	NRM_TRY(out.alloc(ob));

@@ -6,6 +6,7 @@
 // P = the nc(nc+1)/2 products C_c * C_c'.  This file holds the two HBM-bound element-wise passes around them.
 #include "nrm_device.h"
 #include "nrm_jacobi.h"
+#include "nrm_nv_scale.h"
 
 #include "nrm_exp2_tab.h"
 
@@ -409,13 +410,7 @@ __global__ void __launch_bounds__(64) k_nv_solve(const double* __restrict__ mom,
 		ab += a[q] * t;
 	}
 	double sc = 1.0;
-	if (keepvar) {
-		const double s1 = mo[NP + NC], s2 = mo[NP + NC + 1];
-		const double mean = s1 / (double)n;
-		const double dv = sqrt(fmax(s2 / (double)n - mean * mean, 0.0));  // norm.py:248-249
-		const double dv2 = sqrt(fmax(s2 - ab, 0.0) / (double)n);          // |y' - P y'|^2 = |y'|^2 - a . b
-		sc = pow(dv / dv2, wt[g]);                                          // norm.py:259
-	}
+	if (keepvar) sc = nrm_nv_scale(mo[NP + NC], mo[NP + NC + 1], ab, (double)n, wt[g]);  // (NRM_NV_MARK where the one-pass sums have cancelled: nrm_normvar_rescale)
 	scale[g] = sc;
 }
 
@@ -453,3 +448,51 @@ extern "C" int nrm_normvar_solve(const void* d_y, int y_dtype, int64_t rows, int
 	return nrm_check_launch("nrm_normvar_solve");
 }
 
+
+// ---- the scale of a gene whose one-pass sums have cancelled (csrc/nrm_nv_scale.h) ---------------------------------------------------------------
+// A workgroup per gene; one whose scale is not NRM_NV_MARK leaves at once (every gene of the workload: the launch then costs its dispatch).  A marked gene
+// reads its row three times, as the reference does (norm.py:248-249,255-259): mean = sum y e / n;  dv^2 = sum (y e - mean)^2 / n;  dv2^2 = sum (e (y - b . c))^2 / n
+// with b as the solve left it;  scale = (dv / dv2)^wt.  Fixed summation order (a thread's cells in order, nrm_block_sum): the same bits every run.
+template <typename T>
+__global__ void __launch_bounds__(256) k_nv_rescale(const T* __restrict__ y, int64_t n, int64_t ldy, const double* __restrict__ lnw, const double* __restrict__ wt,
+													 const double* __restrict__ c, int nc, int64_t ldc, const double* __restrict__ b, double* __restrict__ scale) {
+	__shared__ double tab[64];
+	__shared__ double sm[4];
+	const int64_t g = blockIdx.x;
+	if (!(scale[g] < 0.0)) return;  // (uniform over the workgroup: before any barrier)
+	const int tid = threadIdx.x;
+	nv_exp_table(tab, tid);
+	__syncthreads();
+	const double ex = wt[g];
+	const T* row = y + g * ldy;
+	const double* bg = b + g * nc;
+	double a = 0.0;
+	for (int64_t k = tid; k < n; k += 256) a += (double)row[k] * nv_exp(ex * lnw[k], tab);
+	const double mean = nrm_block_sum<4>(a, sm) / (double)n;
+	double v1 = 0.0, v2 = 0.0;
+	for (int64_t k = tid; k < n; k += 256) {
+		const double e = nv_exp(ex * lnw[k], tab), yv = (double)row[k];
+		double fit = 0.0;
+		for (int q = 0; q < nc; q++) fit = fma(bg[q], c[(int64_t)q * ldc + k], fit);
+		const double d = yv * e - mean, r = e * (yv - fit);
+		v1 = fma(d, d, v1);
+		v2 = fma(r, r, v2);
+	}
+	v1 = nrm_block_sum<4>(v1, sm);
+	v2 = nrm_block_sum<4>(v2, sm);
+	if (tid == 0) scale[g] = pow(sqrt(v1 / (double)n) / sqrt(v2 / (double)n), ex);
+}
+
+// d_scale[g] == NRM_NV_MARK (what nrm_normvar_solve and the host's nrm_normvar_coefficients leave for a gene whose one-pass variance sums have cancelled) ->
+// (dv / dv2)^wt_g with dv, dv2 from the row itself; every other d_scale[g] is left as it is.  Between the solve and nrm_normvar_apply, on the same stream.
+extern "C" int nrm_normvar_rescale(const void* d_y, int y_dtype, int64_t rows, int64_t n, int64_t ldy, const double* d_lnw, const double* d_wt, const double* d_c,
+								   int64_t nc, int64_t ldc, const double* d_b, double* d_scale, void* stream) {
+	NRM_REQUIRE(y_dtype == NRM_F32 || y_dtype == NRM_F64, "nrm_normvar_rescale: bad dtype");
+	NRM_REQUIRE(rows > 0 && n > 0 && ldy >= n && nc > 0 && nc <= NRM_WIDE_NC && ldc >= n, "Unmatched gene or cell counts.");
+	NRM_REQUIRE(d_y && d_lnw && d_wt && d_c && d_b && d_scale, "nrm_normvar_rescale: null pointer");
+	if (y_dtype == NRM_F64)
+		hipLaunchKernelGGL(k_nv_rescale<double>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const double*)d_y, n, ldy, d_lnw, d_wt, d_c, (int)nc, ldc, d_b, d_scale);
+	else
+		hipLaunchKernelGGL(k_nv_rescale<float>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const float*)d_y, n, ldy, d_lnw, d_wt, d_c, (int)nc, ldc, d_b, d_scale);
+	return nrm_check_launch("k_nv_rescale");
+}

@@ -261,6 +261,15 @@ def _normvar_wide(eng, y, ycode, nt, ns, d_lnw, d_wt, basis, r, keepvar, out, oc
 	return cflags
 
 
+NV_TAU, NV_MARK = 2.0**-20, -1.0  # NRM_NV_TAU, NRM_NV_MARK of csrc/nrm_nv_scale.h: when the one-pass variance sums count as cancelled, and what then stands for the scale
+
+
+def _rescale(eng, y, ycode, nt, ns, d_lnw, d_wt, d_c, nc, d_b, d_scale):
+	"""Between the solve and the result pass, on every route: the scale of the genes marked NV_MARK from the row itself (nrm_normvar_rescale; nothing read back)."""
+	_lib.check(eng.lib.nrm_normvar_rescale(y.data_ptr(), ycode, nt, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr(), d_c.data_ptr(), nc, d_c.stride(0), d_b.data_ptr(),
+										   d_scale.data_ptr(), eng._stream()))
+
+
 def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, normmean=False, tol=1E-8, device_out=False):
 	"""Mean and variance normalisation, same contract as reference norm.py:166-289: returns [dtn, dcn] (+ [dextran]).
 	nth and bs are accepted for compatibility and ignored.
@@ -353,6 +362,7 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 				with _engine._Span(eng, 'normvar_solve'):
 					_lib.check(eng.lib.nrm_normvar_solve(y.data_ptr(), ycode, nt, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr(), d_c.data_ptr(), nc, d_c.stride(0), float(tol),
 														 1 if keepvar else 0, mom.data_ptr(), d_b.data_ptr(), d_scale.data_ptr(), d_rank.data_ptr(), flags.data_ptr(), eng._stream()))
+					_rescale(eng, y, ycode, nt, ns, d_lnw, d_wt, d_c, nc, d_b, d_scale)
 				out = torch.empty((nt, ns), dtype=tdt, device=eng.device)
 				with _engine._Span(eng, 'normvar_apply'):
 					_lib.check(eng.lib.nrm_normvar_apply(y.data_ptr(), ycode, nt, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr(), d_c.data_ptr(), nc, d_c.stride(0),
@@ -387,12 +397,18 @@ def normvar(dt, dc, w, wt, dextra=None, cat=1, nth=1, bs=500, keepvar=True, norm
 				scale = np.ones(nt)
 				if keepvar:
 					mean = s1[:nt].cpu().numpy() / ns
-					dv = np.sqrt(np.maximum(s2[:nt].cpu().numpy() / ns - mean * mean, 0.0))  # norm.py:248-249
-					dv2 = np.sqrt(np.maximum(s2[:nt].cpu().numpy() - np.einsum('gc,gc->g', ga, b), 0.0) / ns)  # |y' - P y'|^2 = |y'|^2 - a.b
+					h2 = s2[:nt].cpu().numpy()
+					d1, d2 = h2 / ns - mean * mean, h2 - np.einsum('gc,gc->g', ga, b)
+					dv = np.sqrt(np.maximum(d1, 0.0))  # norm.py:248-249
+					dv2 = np.sqrt(np.maximum(d2, 0.0) / ns)  # |y' - P y'|^2 = |y'|^2 - a.b
+					wt64 = np.asarray(wt, dtype=np.float64)
 					with np.errstate(divide='ignore', invalid='ignore'):
-						scale = (dv / dv2)**np.asarray(wt, dtype=np.float64)  # norm.py:259
+						scale = (dv / dv2)**wt64  # norm.py:259
+					# the rule of csrc/nrm_nv_scale.h: a difference that has cancelled marks its gene, nrm_normvar_rescale takes that scale from the row itself
+					scale[(wt64 != 0) & ((d1 < NV_TAU * (h2 / ns)) | (d2 < NV_TAU * h2))] = NV_MARK
 				out = torch.empty((nt, ns), dtype=tdt, device=eng.device)
 				d_b, d_scale = eng.upload(b), eng.upload(scale)
+				_rescale(eng, y, ycode, nt, ns, d_lnw, d_wt, d_c, nc, d_b, d_scale)
 				_lib.check(eng.lib.nrm_normvar_apply(y.data_ptr(), ycode, nt, ns, y.stride(0), d_lnw.data_ptr(), d_wt.data_ptr(), d_c.data_ptr(), nc,
 													 d_c.stride(0), d_b.data_ptr(), d_scale.data_ptr(), out.data_ptr(),
 													 _engine.dtype_code(out_dtype), ns, flags.data_ptr(), eng._stream()))
@@ -616,6 +632,7 @@ class NormvarPlan:
 		ocode = _engine.dtype_code(out)
 		_lib.check(eng.lib.nrm_normvar_solve(y.data_ptr(), ycode, nt, ns, y.stride(0), self._lnw.data_ptr(), self._wt.data_ptr(), self._c.data_ptr(), nc, self._c.stride(0), float(self.tol),
 											 1 if self.keepvar else 0, self._mom.data_ptr(), self._b.data_ptr(), self._scale.data_ptr(), self._rank.data_ptr(), self._flags.data_ptr(), eng._stream()))
+		_rescale(eng, y, ycode, nt, ns, self._lnw, self._wt, self._c, nc, self._b, self._scale)
 		_lib.check(eng.lib.nrm_normvar_apply(y.data_ptr(), ycode, nt, ns, y.stride(0), self._lnw.data_ptr(), self._wt.data_ptr(), self._c.data_ptr(), nc, self._c.stride(0),
 											 self._b.data_ptr(), self._scale.data_ptr(), out.data_ptr(), ocode, ns, self._flags.data_ptr(), eng._stream()))
 

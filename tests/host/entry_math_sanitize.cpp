@@ -1,6 +1,7 @@
 // The host arithmetic of the whole-problem entries (csrc/nrm_host_math.h: free of HIP headers) under g++ -fsanitize=address,undefined; tests/test_cabi_cpu.py
 // builds it beside csrc/nrm_small_pinv.hip (the eigenvalue routine of the full-rank certificate) and runs it.  Exercises, on exact-size heap buffers:
 //  * nrm_spd_inverse_host: M M^-1 = I for seeded SPD matrices, false for a zero pivot;
+//  * nrm_normvar_coefficients and the rule of csrc/nrm_nv_scale.h (the mark of a gene whose one-pass variance sums have cancelled);
 //  * nrm_constant_row, nrm_covariate_gram, the streaming de's covariate permutation and its way back for alpha;
 //  * with a file of cases as argv[1] (float64: count, then per case kind, nx, nc, rank, norm_mt, norm_ninv, tol, bx (nx, nc), ss_x (nx), mcc (nc, nc)):
 //    one line "verdict <0|1>" per case from nrm_pinv_rank_certified (kind 0) or nrm_full_rank_certified (kind 1) -- the test holds them to their numpy twins.
@@ -128,6 +129,34 @@ static void check_store() {
 	for (size_t i = 0; i < 3; i++) CHECK(d[i] == v[i] && f[i] == (float)v[i]);
 }
 
+// nrm_normvar_coefficients: b = M^+ a row by row, the one-pass scale, and the mark of csrc/nrm_nv_scale.h where either difference has cancelled
+static void check_normvar_coefficients() {
+	const int64_t rows = 5, nc = 2, n = 100, lda = 3;  // (a pitch above nc)
+	std::vector<double> mi((size_t)(rows * nc * nc)), ga((size_t)(rows * lda)), s1((size_t)rows), s2((size_t)rows), wt = {0.7, 0.7, 0.7, 0.0, 1.5}, hb, hs;
+	for (int64_t g = 0; g < rows; g++) {
+		mi[(size_t)(g * 4)] = 0.5, mi[(size_t)(g * 4 + 1)] = mi[(size_t)(g * 4 + 2)] = 0.125, mi[(size_t)(g * 4 + 3)] = 0.25;
+		ga[(size_t)(g * lda)] = 2.0, ga[(size_t)(g * lda + 1)] = -4.0, ga[(size_t)(g * lda + 2)] = 1e300;  // (the pitch padding is not read)
+	}
+	// b = (0.5, -0.75), a . b = 4.  rows: 0 ordinary; 1 a flat row (s2 / n - mean^2 = 0); 2 a row the covariates explain (s2 - a . b = 2^-30 s2); 3 the same with wt = 0; 4 ordinary
+	s1 = {10.0, 300.0, 10.0, 300.0, -50.0};
+	s2 = {400.0, 900.0, 4.0 / (1.0 - 0x1p-30), 900.0, 1000.0};
+	nrm_normvar_coefficients(mi.data(), ga.data(), lda, s1.data(), s2.data(), wt.data(), rows, nc, n, 1, hb, hs);
+	CHECK((int64_t)hb.size() == rows * nc && (int64_t)hs.size() == rows);
+	for (int64_t g = 0; g < rows; g++) CHECK(hb[(size_t)(g * 2)] == 0.5 && hb[(size_t)(g * 2 + 1)] == -0.75);
+	CHECK(hs[1] == NRM_NV_MARK && hs[2] == NRM_NV_MARK && hs[3] == 1.0);
+	for (int64_t g : {0, 4}) {  // the unmarked genes: the one-pass expressions as they have always stood
+		const double mean = s1[(size_t)g] / (double)n;
+		const double dv = std::sqrt(std::fmax(s2[(size_t)g] / (double)n - mean * mean, 0.0));
+		const double dv2 = std::sqrt(std::fmax(s2[(size_t)g] - 4.0, 0.0) / (double)n);
+		CHECK(hs[(size_t)g] == std::pow(dv / dv2, wt[(size_t)g]) && hs[(size_t)g] > 0);
+	}
+	// the threshold itself: a difference of exactly tau x its minuend is not below it
+	CHECK(nrm_nv_scale(0.0, 1.0, 1.0 - NRM_NV_TAU, 1.0, 1.0) != NRM_NV_MARK && nrm_nv_scale(0.0, 1.0, 1.0 - NRM_NV_TAU / 2, 1.0, 1.0) == NRM_NV_MARK);
+	CHECK(nrm_nv_scale(0.0, 1.0, 1.0, 1.0, 0.0) == 1.0);  // wt == 0: never marked, x^0 = 1 even for 0 / 0
+	nrm_normvar_coefficients(mi.data(), ga.data(), lda, s1.data(), s2.data(), wt.data(), rows, nc, n, 0, hb, hs);
+	for (double v : hs) CHECK(v == 1.0);  // keepvar == 0
+}
+
 static void certificates(const char* path) {
 	FILE* fh = fopen(path, "rb");
 	CHECK(fh != nullptr);
@@ -172,6 +201,7 @@ int main(int argc, char** argv) {
 			check_alpha_permutation<double>(nc, ci);
 		}
 	check_store();
+	check_normvar_coefficients();
 	bool ok = false;  // no covariates: the norms of M~ alone
 	CHECK(nrm_full_rank_certified(2.0, 0.5, nullptr, nullptr, 3, 0, 1e-8, &ok) == NRM_OK && ok);
 	CHECK(nrm_full_rank_certified(2.0, 1e9, nullptr, nullptr, 3, 0, 1e-8, &ok) == NRM_OK && !ok);
