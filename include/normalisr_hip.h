@@ -1186,6 +1186,58 @@ int nrm_single4_plan_info(nrm_single4_plan* plan, int64_t info[8]);
 int nrm_single4_plan_time(nrm_single4_plan* plan, int64_t steps, double* ms_per_step);
 int nrm_single4_plan_destroy(nrm_single4_plan* plan);
 
+/*
+ * Resident front-half plan (csrc/nrm_front_plan.hip): read counts in HBM in, normvar's (dtn, dcn) in HBM out -- the reference's chain lcpm (lcpm.py:21-208) ->
+ * normcov (norm.py:4-53) -> compute_var (norm.py:56-128) -> scaling_factor (lcpm.py:211-283) -> normvar (norm.py:166-289) with its default options: normalize=True,
+ * varscale=0, cat=1, keepvar=True, normmean=False, c=True, the scaling variable nt0mean with v0=0 and v1='max'.  Nothing is decided, allocated or read back on
+ * the host between the launches of a step: the totals, t0, the digamma and exp tables, lcpm's three covariate rows, normcov, the pseudo-inverse of compute_var's
+ * second regression, ln w and the rescale are kernels on device memory, so a step is one enqueue on ONE stream (no parallel branches) and one hipGraphLaunch from
+ * the second step on, and the graph stays valid when the counts are rewritten.  A coex / de plan of the same process adopts the output matrix.
+ *   nrm_front_plan_create: reads (genes, n_cells) of dtype NRM_I64 / NRM_I32 / NRM_I16 / NRM_U8.  reads_on_device == 0: a contiguous HOST array (ld == n_cells, or 0);
+ *       the plan owns a device copy that nrm_front_plan_upload rewrites.  reads_on_device != 0: a DEVICE pointer with row pitch ld, adopted: never copied, rewritten
+ *       in place by its owner between steps (in stream order with them); create synchronises the device.  h_cov (n_cov, n_cells) fp64, n_cov >= 0: the raw user
+ *       covariate rows a caller would stack in front of lcpm's three before normcov.  ntot (-1: the matrix total, lcpm.py:94-96), stepmax and eps (compute_var),
+ *       tol (normvar's rank rule, norm.py:152-160), out_dtype NRM_F64 (the reference's) or NRM_F32 for lcpm and dtn, count_cap: the tables hold psi(1 + x) for
+ *       x < count_cap, 2 <= count_cap <= nrm_lcpm_table_cap().  Every argument check is made before any device call (csrc/nrm_front_plan_args.h): NRM_E_ARG, in the
+ *       reference's words where it has any ("reads must not be empty.", "eps and stepmax must be positive.", a user row that is not finite, a constant user row:
+ *       "Detected constant covariate. ..." norm.py:34-37); n_cov + 3 + 1 > nrm_normvar_device_covariates(): NRM_E_UNSUPPORTED, the text names the bound.
+ *       Every buffer of a step is taken from the scratch pool here and given back by nrm_front_plan_destroy.
+ *   nrm_front_plan_upload: new counts (same shape and dtype) into the plan's own copy; NRM_E_ARG for an adopted matrix.
+ *   nrm_front_plan_step: nrm_lcpm_count; t0 = sum + 2, len = max + 1 and lcpm's refusals counted (one workgroup); tab[x] = psi(1 + x) - psi(t0) and exp(tab[x]) for
+ *       x < len, each entry on its own (csrc/nrm_digamma.h); nrm_lcpm_colsum and nrm_lcpm_write with table_len = count_cap (lcpm.py:107,158); lcpm's rows ln total,
+ *       genes - nnz, ln^2 total (lcpm.py:194-200) and normcov on [user rows; those three] with the ones row appended, a workgroup per row, two-pass mean and spread
+ *       in a fixed order; ([dc;1][dc;1]^T)^+ on unit-length rows by the lane Jacobi; the launches of nrm_compute_var_host; ln w and wt = (zeros / cells) / max
+ *       (lcpm.py:258,268-283); dcn = the continuous rows and the ones row times w (norm.py:261-273); nrm_normvar_solve / rescale / apply.  stream == NULL: the
+ *       plan's own.  Eager the first time, captured (thread-local) the second, one hipGraphLaunch afterwards; a failed capture leaves the plan eager with the reason
+ *       in nrm_last_error (NRM_OK).  NRM_DEBUG="graph=0": always eager.  No floating-point atomics: the same input gives the same bits, eager or replayed.
+ *   nrm_front_plan_check: synchronises the device, reads all counters once, clears them and answers in the order the reference would meet the conditions: a
+ *       negative entry (lcpm.py:86, NRM_E_ARG); no read at all (the assertion t0 > 2, lcpm.py:97: NRM_E_NUMERIC); a cell without a read (lcpm.py:196, NRM_E_ARG);
+ *       a count at or beyond count_cap (NRM_E_UNSUPPORTED, naming the cap and the count); a constant covariate row (norm.py:34-37, NRM_E_ARG); compute_var's two
+ *       assertions (norm.py:108,125-127: NRM_E_NUMERIC); scaling_factor's (lcpm.py:278-282: NRM_E_NUMERIC); normvar's zero rank (norm.py:160: NRM_E_DEVICE) and
+ *       non-finite results (norm.py:286: NRM_E_NUMERIC).  *near_constant (may be NULL): rows normcov would warn about (norm.py:44-47) since the last check.
+ *       After a refusal the plan is usable again once its counts are good.
+ *   nrm_front_plan_results: check, then into HOST arrays, any of them NULL: dtn (genes, n_cells) of out_dtype, dcn (n_cov + 4, n_cells) fp64, w (n_cells) and
+ *       wt (genes) fp64, lcpm (genes, n_cells) of out_dtype, the normalised covariates (n_cov + 4, n_cells) fp64.
+ *   nrm_front_plan_device_results: dtn, dcn and lcpm as DEVICE pointers (row pitch *ld = n_cells elements) and the plan's own stream; valid until destroy, written
+ *       by every step.
+ *   nrm_front_plan_info: info[0] captured, [1] steps, [2] iterations compute_var took in the last step checked, [3] the largest count of that step, [4] count_cap,
+ *       [5] covariates in all (n_cov + 4), [6] bytes resident, [7] near-constant rows at the last check.
+ *   nrm_front_plan_stream, nrm_front_plan_time, nrm_front_plan_destroy (accepts NULL): as nrm_coex_plan_*.
+ * Threads: create, check, results and destroy take the lock of the whole-problem entries; step, upload and time do not.  One thread at a time per plan.
+ */
+typedef struct nrm_front_plan nrm_front_plan;
+int nrm_front_plan_create(nrm_front_plan** plan, const void* reads, int dtype, int64_t genes, int64_t n_cells, int64_t ld, int reads_on_device, const double* h_cov,
+						  int64_t n_cov, int64_t ntot, int64_t stepmax, double eps, double tol, int out_dtype, int64_t count_cap);
+int nrm_front_plan_upload(nrm_front_plan* plan, const void* h_reads);
+int nrm_front_plan_step(nrm_front_plan* plan, void* stream);
+int nrm_front_plan_check(nrm_front_plan* plan, int64_t* near_constant);
+int nrm_front_plan_results(nrm_front_plan* plan, void* h_dtn, double* h_dcn, double* h_w, double* h_wt, void* h_lcpm, double* h_cov);
+int nrm_front_plan_device_results(nrm_front_plan* plan, void** d_dtn, void** d_dcn, void** d_lcpm, int64_t* ld, void** stream);
+int nrm_front_plan_stream(nrm_front_plan* plan, void** stream);
+int nrm_front_plan_info(nrm_front_plan* plan, int64_t info[8]);
+int nrm_front_plan_time(nrm_front_plan* plan, int64_t steps, double* ms_per_step);
+int nrm_front_plan_destroy(nrm_front_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif

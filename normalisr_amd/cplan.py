@@ -10,6 +10,8 @@ DePlan (nrm_de_plan_*) is the same for de(dg, dt, dc) with single=0 on the spars
 assertions and, on request, alpha and Benjamini-Hochberg q-values on the device; `results()` is `de`'s contract.  Single1Plan (nrm_single1_plan_*) is the same
 for single=1, a low-MOI screen: the row filter runs in front of the cell selection, the variances are per grouping.  Single4Plan (nrm_single4_plan_*) is the same
 for single=4, a high-MOI screen in closed form: what depends on the design alone is computed when the design is set, not in a step.
+FrontPlan (nrm_front_plan_*) is the front half in front of them: read counts in, normvar's (dtn, dcn) out -- lcpm, normcov, compute_var, scaling_factor and normvar
+with the reference's defaults as one graph --, whose output matrix a CoexPlan or DePlan of the same process adopts.
 """
 import ctypes
 
@@ -95,7 +97,7 @@ def _covariates(dc, pinv):
 
 
 class _Plan:
-	"""What the four plans share: the handle and its entries.  A class names its entries' prefix and the fields of its info()."""
+	"""What the plans share: the handle and its entries.  A class names its entries' prefix and the fields of its info()."""
 	_prefix = None
 	_info_fields = None
 
@@ -492,6 +494,134 @@ class Single4Plan(_DesignPlan):
 		back = _i64(0)
 		self._call('check', ctypes.byref(back))
 		return int(back.value)
+
+
+FRONT_INFO_FIELDS = ('captured', 'steps', 'cv_steps', 'max_count', 'count_cap', 'covariates', 'bytes', 'near_constant')
+_COUNT_CODES = {'int64': _lib.NRM_I64, 'int32': _lib.NRM_I32, 'int16': _lib.NRM_I16, 'uint8': _lib.NRM_U8}
+
+
+class FrontPlan(_Plan):
+	"""Read counts to normalised expression resident on the GPU (include/normalisr_hip.h: nrm_front_plan_*): lcpm -> normcov -> compute_var -> scaling_factor ->
+	normvar with the reference's default options as one HIP graph, nothing decided on the host in between:
+
+		with cplan.FrontPlan(reads, cov=batches, stepmax=1) as front:
+			front.step()
+			dtn, dcn = front.results()                      # == normvar(lcpm(reads)[0], normcov(vstack([batches, lcpm(reads)[3]])), w, scaling_factor(reads))
+			coex = cplan.CoexPlan(front.device_results()['dtn'], dcn)   # adopts the matrix where it lies
+			front.update(reads2); front.step()              # same shape and dtype, new counts: one graph launch
+
+	reads (n_gene, n_cell): a numpy integer array (int64 / int32 / int16 / uint8 as they are, other integer types as int64; the plan keeps its own device copy and
+	`update` re-uploads) or a device matrix of one of those four dtypes -- anything with data_ptr() or __cuda_array_interface__, such as a DeviceMatrix -- which is
+	adopted and rewritten in place by its owner.  cov (n_cov, n_cell): the raw covariate rows stacked in front of lcpm's three before normcov (None: none); with
+	lcpm's three and the constant row there may be nrm_normvar_device_covariates() in all (NotImplementedError beyond).  stepmax, eps: compute_var's; ntot: lcpm's;
+	tol: normvar's; out_dtype: float64 (the reference's) or float32 for lcpm and dtn.  count_cap: the tables hold counts below it; None for host input: the next
+	power of two above the matrix's maximum, 256 at the least; an adopted matrix must name one.  A step whose largest count reaches the cap is refused by check().
+	Not covered: sparse counts, the non-default options of lcpm / normcov / scaling_factor / normvar, qc_outlier and subset between fitvar and normvar (weights()
+	is there for a caller who wants them).
+	info(): captured, steps, cv_steps (iterations compute_var took in the last step checked), max_count (of that step), count_cap, covariates, bytes, near_constant."""
+	_prefix, _info_fields = 'nrm_front_plan_', FRONT_INFO_FIELDS
+
+	def __init__(self, reads, cov=None, stepmax=1, eps=1e-6, ntot=None, tol=1e-8, out_dtype=np.float64, count_cap=None, device=None):
+		super().__init__()
+		if hasattr(reads, 'tocsr'):
+			raise TypeError('FrontPlan: a sparse reads is not taken here (lcpm takes one).')
+		dev = _adopt(reads)
+		if dev is None:
+			reads = np.asarray(reads)
+			if reads.ndim != 2:
+				raise ValueError('reads must have 2 dimensions.')
+			if reads.dtype.kind not in 'iub':
+				raise TypeError('reads must be an integer matrix.')
+			if str(reads.dtype) not in _COUNT_CODES:
+				reads = reads.astype(np.int64)
+			reads = np.ascontiguousarray(reads)
+			ptr, shape, dtype, ld, self.adopted = reads.ctypes.data, reads.shape, reads.dtype, reads.shape[1], False
+		else:
+			ptr, shape, dtype, ld = dev
+			self.adopted = True
+			if str(dtype) not in _COUNT_CODES:
+				raise ValueError('FrontPlan: a device matrix must be int64, int32, int16 or uint8')
+			if count_cap is None:
+				raise ValueError('FrontPlan: count_cap must be given for a device matrix (its maximum is not looked at here)')
+		self.shape, self.dtype = (int(shape[0]), int(shape[1])), np.dtype(dtype)
+		self.out_dtype = np.dtype(out_dtype)
+		if self.out_dtype not in (np.float32, np.float64):
+			raise ValueError('out_dtype must be float32 or float64')
+		if eps <= 0 or stepmax <= 0:
+			raise ValueError('eps and stepmax must be positive.')
+		if int(stepmax) != stepmax:
+			raise ValueError('stepmax must be an integer.')
+		cov = np.zeros((0, self.shape[1])) if cov is None else np.asarray(cov)
+		if cov.ndim != 2:
+			raise ValueError('Covariates must have 2 dimensions.')
+		if cov.shape[1] != self.shape[1]:
+			raise ValueError('reads and cov must have the same cell count.')
+		if cov.dtype.kind not in 'iufb':
+			raise TypeError('cov must hold real numbers.')
+		cov = np.ascontiguousarray(cov, dtype=np.float64)
+		self.n_cov = int(cov.shape[0])
+		self.covariates = self.n_cov + 4  # lcpm's three rows and the constant row
+		if ntot is not None and (int(ntot) != ntot or ntot <= 0):
+			raise ValueError('ntot must be a positive integer.')
+		if count_cap is None:
+			top = int(reads.max()) if reads.size else 0
+			if top >= int(self._lib.nrm_lcpm_table_cap()):
+				raise NotImplementedError('FrontPlan tabulates psi(1 + count) for counts below {}; the largest count here is {}.'.format(int(self._lib.nrm_lcpm_table_cap()), top))
+			count_cap = max(256, 1 << max(top, 0).bit_length())
+		if int(count_cap) != count_cap:
+			raise ValueError('count_cap must be an integer.')
+		self.count_cap = int(count_cap)
+		self._open(device, reads, ptr, _COUNT_CODES[str(self.dtype)], self.shape[0], self.shape[1], ld, 1 if self.adopted else 0, cov.ctypes.data if self.n_cov else None, self.n_cov,
+				   -1 if ntot is None else int(ntot), int(stepmax), float(eps), float(tol), _code(self.out_dtype), self.count_cap)
+
+	def check(self):
+		"""Waits for the queued steps and tests what they counted, in the order the reference would meet it: ValueError for a negative entry, AssertionError for a
+		matrix without a read, ValueError for a cell without a read, NotImplementedError for a count at or beyond count_cap, ValueError for a constant covariate,
+		AssertionError for compute_var's, scaling_factor's and normvar's assertions, RuntimeError for zero-rank covariates.  Returns the rows normcov would warn about
+		as near constant since the last check, under the same RuntimeWarning."""
+		near = _i64(0)
+		self._call('check', ctypes.byref(near))
+		if near.value:
+			import warnings
+			warnings.warn('Detected near constant covariate. Results may be error-prone.', RuntimeWarning)
+		return int(near.value)
+
+	def _fetch(self, **want):
+		ng, n = self.shape
+		shapes = dict(dtn=((ng, n), self.out_dtype), dcn=((self.covariates, n), np.float64), w=((n, ), np.float64), wt=((ng, ), np.float64), lcpm=((ng, n), self.out_dtype),
+					  cov=((self.covariates, n), np.float64))
+		out = {k: np.empty(*shapes[k]) for k in shapes if want.get(k)}
+		self._call('results', *[out[k].ctypes.data if k in out else None for k in ('dtn', 'dcn', 'w', 'wt', 'lcpm', 'cov')])
+		return out
+
+	def results(self):
+		"""[dtn (n_gene, n_cell) of out_dtype, dcn (n_cov + 4, n_cell) float64] of the last step: normvar's return value."""
+		out = self._fetch(dtn=True, dcn=True)
+		return [out['dtn'], out['dcn']]
+
+	def weights(self):
+		"""compute_var's weights (n_cell,) of the last step."""
+		return self._fetch(w=True)['w']
+
+	def scaling(self):
+		"""scaling_factor's result (n_gene,) of the last step."""
+		return self._fetch(wt=True)['wt']
+
+	def lcpm(self):
+		"""lcpm (n_gene, n_cell) of out_dtype of the last step."""
+		return self._fetch(lcpm=True)['lcpm']
+
+	def normcov(self):
+		"""normcov([cov; lcpm's three rows]) with the constant row, (n_cov + 4, n_cell) float64, of the last step."""
+		return self._fetch(cov=True)['cov']
+
+	def device_results(self):
+		"""dict(dtn=, lcpm= DeviceMatrix objects of out_dtype -- what CoexPlan and DePlan adopt --, dcn= the device address of the scaled covariates (n_cov + 4, n_cell)
+		float64, ld= row pitch in elements, dtype=, stream= the plan's own stream)."""
+		dtn, dcn, lc, st, ld = _vp(), _vp(), _vp(), _vp(), _i64(0)
+		self._call('device_results', ctypes.byref(dtn), ctypes.byref(dcn), ctypes.byref(lc), ctypes.byref(ld), ctypes.byref(st))
+		return dict(dtn=DeviceMatrix(dtn.value, self.shape, self.out_dtype, ld.value), lcpm=DeviceMatrix(lc.value, self.shape, self.out_dtype, ld.value), dcn=dcn.value,
+					ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
 
 
 assert __name__ != "__main__"

@@ -1,0 +1,418 @@
+// Resident front-half plan behind the C ABI (include/normalisr_hip.h: nrm_front_plan_*): read counts resident in HBM in, (dtn, dcn) in HBM out -- the chain
+// lcpm -> normcov -> compute_var -> scaling_factor -> normvar of the reference (lcpm.py:21-283, norm.py:4-128,166-289) with its default options, as ONE enqueue on
+// ONE stream, and from the second step on one hipGraphLaunch (nrm_plan_core.h).  numpy and the library are all a caller needs: no torch.
+//
+// The large passes are the existing entries, called as they stand: nrm_lcpm_count / colsum / write, nrm_fitvar_* in the sequence of nrm_compute_var_host,
+// nrm_normvar_solve / rescale / apply in the sequence of norm.NormvarPlan._launch.  What the host did between them is here as small kernels that read their
+// operands from device memory, so that no launch argument of a step depends on the data and a captured graph stays valid when the counts are rewritten:
+//   k_front_scalars  ONE workgroup: t0 = sum + 2 (or ntot + 2), len = max + 1 (clamped to the cap), the counters of lcpm's refusals
+//   k_front_tables   tab[x] = psi(1 + x) - psi(t0), etab[x] = exp(tab[x]) for x < len; a thread per entry of the cap, every entry on its own (nrm_digamma.h)
+//   k_front_cov      a workgroup per covariate row: lcpm's three rows from the integer totals, then normcov on [user rows; those three], the ones row appended
+//   k_front_m2i      ONE workgroup: ([dc;1][dc;1]^T)^+ on unit-length rows by the lane Jacobi of nrm_jacobi_lanes.h (nrm_pinv_gram_unit_rows of the host entries)
+//   k_front_scale    ln w, and wt = (zeros / cells) / max_g (zeros / cells): scaling_factor's default variable rescaled with v0 = 0, v1 = 'max'
+//   k_front_dcn      normvar's scaled covariates: continuous rows and the ones row times w (norm.py:261-273 with cat = 1)
+// Sums over cells are per-thread partial sums in a fixed stride, added by the shuffle tree and the waves in their order: no floating-point atomics, the same bits
+// every run, eager or replayed.  Counters are integers.
+#include <memory>
+#include "nrm_device.h"
+#include "nrm_digamma.h"
+#include "nrm_front_plan_args.h"
+#include "nrm_host_entry.h"
+#include "nrm_jacobi_lanes.h"
+#include "nrm_plan_core.h"
+
+#define FP_M2_THREADS 1024
+#define FP_FLAGS 16  // [0] negative entry, [1] a cell without a read, [2] no read at all, [3] max >= cap, [4] constant covariate rows, [5] near-constant rows,
+					 // [6] scaling_factor, [7] 0, [8..11] compute_var's counters, [12..15] normvar's
+
+static_assert(NRM_FRONT_M2_ROWS * NRM_FRONT_M2_ROWS * 8 * 3 < 32768, "k_front_m2i keeps three square matrices in LDS");
+
+// fs[0] = t0, fs[1] = len (as a double: below 2^24); big[0] = the largest count of a step whose maximum reached the cap
+__global__ void __launch_bounds__(256) k_front_scalars(const int64_t* __restrict__ info, const int64_t* __restrict__ cell_total, int64_t n, int64_t ntot, int64_t cap,
+														double* __restrict__ fs, int32_t* __restrict__ flags, int64_t* __restrict__ big) {
+	__shared__ int sm[4];
+	int empty = 0;
+	for (int64_t k = threadIdx.x; k < n; k += 256) empty += cell_total[k] <= 0;
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) empty += __shfl_down(empty, o, 64);
+	if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = empty;
+	__syncthreads();
+	if (threadIdx.x != 0) return;
+	empty = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+	const int64_t sum = info[0], mx = info[1];
+	const double t0 = ntot < 0 ? (double)(sum + 2) : (double)ntot + 2.0;
+	const bool over = mx >= cap;
+	fs[0] = t0;
+	fs[1] = (double)(over ? cap : mx + 1);
+	// (one thread of one workgroup on one stream: nobody else writes these words while a step runs)
+	if (info[2]) flags[0] += 1;
+	if (empty) flags[1] += 1;
+	if (!(t0 > 2.0)) flags[2] += 1;
+	if (over) {
+		flags[3] += 1;
+		if (mx > big[0]) big[0] = mx;
+	}
+	big[1] = mx;
+}
+
+__global__ void __launch_bounds__(256) k_front_tables(const double* __restrict__ fs, int64_t cap, double* __restrict__ tab, double* __restrict__ etab) {
+	const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x, len = (int64_t)fs[1];
+	if (x >= len || x >= cap) return;
+	const double t = nrm_digamma(1.0 + (double)x) - nrm_digamma(fs[0]);  // (a t0 that is not positive -- negative entries -- gives NaN; the step is refused by its counter)
+	tab[x] = t;
+	etab[x] = exp(t);
+}
+
+// dc (nct, n): row r < n_cov the user's, the next three lcpm's, the last all ones.  cls[r] = the row's class (nrm_front_plan_args.h).
+__global__ void __launch_bounds__(256) k_front_cov(const double* __restrict__ user, int n_cov, const int64_t* __restrict__ cell_total, const int64_t* __restrict__ cell_nnz,
+													int64_t genes, int64_t n, int nct, double* __restrict__ dc, int32_t* __restrict__ cls, int32_t* __restrict__ flags) {
+	__shared__ double sm[4];
+	const int r = blockIdx.x, tid = threadIdx.x;
+	double* __restrict__ out = dc + (int64_t)r * n;
+	if (r == nct - 1) {
+		for (int64_t k = tid; k < n; k += 256) out[k] = 1.0;
+		if (tid == 0) cls[r] = NRM_COV_ONES;
+		return;
+	}
+	// the raw row, kept in `out`: every thread reads back only what it wrote itself
+	const int j = r - n_cov;
+	double first = 0.0;
+	{
+		if (j < 0) first = user[(int64_t)r * n];
+		else {
+			const double t = log((double)cell_total[0]);  // lcpm.py:194-200 (a cell without a read: -inf or NaN, and the step is refused by its counter)
+			first = j == 0 ? t : j == 1 ? (double)(genes - cell_nnz[0]) : t * t;
+		}
+	}
+	int cont = 0, differs = 0;
+	double s = 0.0;
+	for (int64_t k = tid; k < n; k += 256) {
+		double v;
+		if (j < 0) v = user[(int64_t)r * n + k];
+		else {
+			const double t = log((double)cell_total[k]);
+			v = j == 0 ? t : j == 1 ? (double)(genes - cell_nnz[k]) : t * t;
+		}
+		out[k] = v;
+		cont |= v != 0.0 && v != 1.0;
+		differs |= !(v == first);
+		s += v;
+	}
+	cont = __syncthreads_or(cont);
+	differs = __syncthreads_or(differs);
+	if (!differs && tid == 0) atomicAdd(&flags[4], 1);  // norm.py:34-37 (the values are still written: nothing downstream reads past a buffer for them)
+	if (!cont) {
+		if (tid == 0) cls[r] = NRM_COV_BINARY;
+		return;
+	}
+	const double mean = nrm_block_sum<4>(s, sm) / (double)n;  // norm.py:41
+	double q = 0.0;
+	for (int64_t k = tid; k < n; k += 256) {
+		const double d = out[k] - mean;
+		q += d * d;
+	}
+	const double sd = sqrt(nrm_block_sum<4>(q, sm) / (double)n);  // norm.py:43
+	if (tid == 0) {
+		cls[r] = NRM_COV_CONTINUOUS;
+		if (sd < 1e-50 || fabs(sd / mean) < 1e-6) atomicAdd(&flags[5], 1);  // norm.py:44-47: a warning
+	}
+	for (int64_t k = tid; k < n; k += 256) out[k] = (out[k] - mean) / sd;  // norm.py:42,48
+}
+
+struct FrontWorkgroup {
+	__device__ int lane() const { return threadIdx.x; }
+	__device__ int lanes() const { return blockDim.x; }
+	__device__ void sync() const { __syncthreads(); }
+};
+
+// m2i (r, r), r = nc + 1: the pseudo-inverse of x x^T for x = [dc; 1] on rows scaled to unit length, D pinv(D x x^T D) D (nrm_pinv_gram_unit_rows, nrm_host_math.h).
+// A wave owns a row's norm, then a pair's product: lanes stride the cells, the shuffle tree adds them -- a fixed order.
+__global__ void __launch_bounds__(FP_M2_THREADS) k_front_m2i(const double* __restrict__ dc, int nc, int64_t n, double tol, double* __restrict__ m2i) {
+	__shared__ double a[NRM_FRONT_M2_ROWS * NRM_FRONT_M2_ROWS], v[NRM_FRONT_M2_ROWS * NRM_FRONT_M2_ROWS], inv[NRM_FRONT_M2_ROWS * NRM_FRONT_M2_ROWS];
+	__shared__ double w[NRM_FRONT_M2_ROWS], red[2 * NRM_FRONT_M2_ROWS], d[NRM_FRONT_M2_ROWS];
+	__shared__ int64_t rank;
+	const int r = nc + 1, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = FP_M2_THREADS / 64;
+	for (int i = wid; i < r; i += nw) {
+		double s = 0.0;
+		for (int64_t k = lane; k < n; k += 64) {
+			const double x = i < nc ? dc[(int64_t)i * n + k] : 1.0;
+			s = fma(x, x, s);
+		}
+		s = nrm_wave_sum(s);
+		if (lane == 0) {
+			s = sqrt(s);
+			d[i] = 1.0 / (s > 0 ? s : 1.0);
+		}
+	}
+	__syncthreads();
+	const int npair = r * (r + 1) / 2;
+	for (int p = wid; p < npair; p += nw) {
+		int i = 0, q = p;
+		while (q >= r - i) q -= r - i, i++;  // pair p of the upper triangle, row by row: (i, j >= i)
+		const int j = i + q;
+		const double di = d[i], dj = d[j];
+		double s = 0.0;
+		for (int64_t k = lane; k < n; k += 64) {
+			const double xi = i < nc ? dc[(int64_t)i * n + k] : 1.0, xj = j < nc ? dc[(int64_t)j * n + k] : 1.0;
+			s = fma(xi * di, xj * dj, s);
+		}
+		s = nrm_wave_sum(s);
+		if (lane == 0) a[i * r + j] = a[j * r + i] = s;
+	}
+	__syncthreads();
+	nrm_pinv_lanes(FrontWorkgroup(), a, v, w, red, r, tol, inv, &rank);
+	__syncthreads();
+	for (int e = threadIdx.x; e < r * r; e += FP_M2_THREADS) m2i[e] = inv[e] * (d[e / r] * d[e % r]);
+}
+
+// lnw = ln w (normvar's operand); wt = (zeros / cells - 0) / (max_g - 0) (lcpm.py:258,268-283 with v0 = 0, v1 = 'max').  Every workgroup takes the maximum of
+// the integer zero counts for itself: exact, whatever the order.
+__global__ void __launch_bounds__(256) k_front_scale(const double* __restrict__ w, int64_t n, const int64_t* __restrict__ gene_zero, int64_t genes, double* __restrict__ lnw,
+													  double* __restrict__ wt, int32_t* __restrict__ flags) {
+	__shared__ int64_t sm[4];
+	int64_t mx = 0;
+	for (int64_t g = threadIdx.x; g < genes; g += 256) mx = gene_zero[g] > mx ? gene_zero[g] : mx;
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) {
+		const int64_t t = __shfl_xor(mx, o, 64);
+		mx = t > mx ? t : mx;
+	}
+	if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mx;
+	__syncthreads();
+	for (int i = 0; i < 4; i++) mx = sm[i] > mx ? sm[i] : mx;
+	const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	int bad = 0;
+	if (k < n) {
+		const double l = log(w[k]);
+		lnw[k] = l;
+		bad += !(fabs(l) <= 1.7976931348623157e308);
+	}
+	if (k < genes) {
+		const double t = ((double)gene_zero[k] / (double)n - 0.0) / ((double)mx / (double)n - 0.0);
+		wt[k] = t;
+		bad += !(fabs(t) <= 1.7976931348623157e308);
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0 && mx == 0) bad++;  // lcpm.py:278: v1 != v0
+	if (bad) atomicAdd(&flags[6], bad);
+}
+
+__global__ void __launch_bounds__(256) k_front_dcn(const double* __restrict__ dc, const int32_t* __restrict__ cls, const double* __restrict__ w, int64_t n,
+													double* __restrict__ dcn) {
+	const int r = blockIdx.y;
+	const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (k >= n) return;
+	const double v = dc[(int64_t)r * n + k];
+	dcn[(int64_t)r * n + k] = cls[r] != NRM_COV_BINARY ? v * w[k] : v;  // norm.py:261-273, cat = 1
+}
+
+struct nrm_front_plan : NrmPlanCore {
+	int64_t rows = 0, n = 0, ld = 0, n_cov = 0, nct = 0, ntot = -1, stepmax = 1, cap = 0;
+	int dtype = NRM_I32, out_dtype = NRM_F64;
+	double eps = 1e-6, tol = 1e-8;
+	bool adopted = false;
+	const void* x = nullptr;  // the counts a step reads: own_x, or the caller's
+	// lcpm | the covariates | compute_var (the buffers of nrm_compute_var_host) | normvar (those of NormvarPlan)
+	DevBuf own_x, ibuf, part, fs, big, flags, tab, etab, t1, lc;
+	DevBuf user, dc, dcn, cls, m2i;
+	DevBuf a, b, mean, sc, v, fpart, s, best, u, cw, mi, rank, ws, out;
+	DevBuf lnw, wt, mom, nb, scale, nrank, dtn;
+	int64_t cv_steps = 0, max_count = 0, warned = 0;
+	~nrm_front_plan() { shutdown(); }  // (its body runs before the DevBuf members go back to the pool: NrmPlanCore::shutdown)
+	int64_t* total() const { return ibuf.as<int64_t>(); }
+	int64_t* nnz() const { return total() + n; }
+	int64_t* zero() const { return total() + 2 * n; }
+	int64_t* info() const { return total() + 2 * n + rows; }
+	double* state() const { return out.as<double>(); }
+	double* w() const { return state() + 4 * (stepmax + 1); }
+};
+
+namespace {
+
+int plan_enqueue(nrm_front_plan* pl, hipStream_t st) {
+	const int64_t rows = pl->rows, n = pl->n, nc = pl->nct;
+	const int yd = pl->out_dtype;
+	int32_t* flags = pl->flags.as<int32_t>();
+	// lcpm: count, the scalars and the tables on the device, colsum, write
+	NRM_HIP(hipMemsetAsync(pl->ibuf.p, 0, (size_t)(2 * n + rows + 4) * 8, st));  // (the gene zero counts are integer atomics)
+	NRM_TRY(nrm_lcpm_count(pl->x, pl->dtype, rows, n, pl->ld, pl->total(), pl->nnz(), pl->zero(), pl->info(), pl->part.as<int64_t>(), st));
+	hipLaunchKernelGGL(k_front_scalars, dim3(1), dim3(256), 0, st, pl->info(), pl->total(), n, pl->ntot, pl->cap, pl->fs.as<double>(), flags, pl->big.as<int64_t>());
+	NRM_TRY(nrm_check_launch("k_front_scalars"));
+	hipLaunchKernelGGL(k_front_tables, dim3((unsigned)((pl->cap + 255) / 256)), dim3(256), 0, st, pl->fs.as<double>(), pl->cap, pl->tab.as<double>(), pl->etab.as<double>());
+	NRM_TRY(nrm_check_launch("k_front_tables"));
+	NRM_TRY(nrm_lcpm_colsum(pl->x, pl->dtype, rows, n, pl->ld, pl->etab.as<double>(), pl->cap, pl->part.as<double>(), pl->t1.as<double>(), st));
+	NRM_TRY(nrm_lcpm_write(pl->x, pl->dtype, rows, n, pl->ld, pl->tab.as<double>(), pl->cap, pl->t1.as<double>(), pl->lc.p, yd, n, st));
+	// lcpm's covariate rows, normcov, the pseudo-inverse of the second regression
+	double* c = pl->dc.as<double>();
+	hipLaunchKernelGGL(k_front_cov, dim3((unsigned)nc), dim3(256), 0, st, pl->user.as<double>(), (int)pl->n_cov, pl->total(), pl->nnz(), rows, n, (int)nc, c, pl->cls.as<int32_t>(),
+					   flags);
+	NRM_TRY(nrm_check_launch("k_front_cov"));
+	hipLaunchKernelGGL(k_front_m2i, dim3(1), dim3(FP_M2_THREADS), 0, st, c, (int)nc, n, 1e-8, pl->m2i.as<double>());
+	NRM_TRY(nrm_check_launch("k_front_m2i"));
+	// compute_var: the sequence of nrm_compute_var_host (nrm_host_front.hip) on lcpm in HBM
+	double *state = pl->state(), *s = pl->s.as<double>(), *best = pl->best.as<double>(), *u = pl->u.as<double>(), *cw = pl->cw.as<double>(), *ws = pl->ws.as<double>();
+	int32_t* fv_flags = flags + 8;
+	NRM_TRY(nrm_fitvar_plan_start(n, s, best, state, st));
+	for (int64_t i = 0; i < pl->stepmax; i++) {
+		const double* now = state + 4 * i;
+		NRM_TRY(nrm_fitvar_design(c, nc, n, n, s, now, pl->eps, u, cw, ws, st));
+		NRM_TRY(nrm_fitvar_pinv(n, nc, 1e-8, now, pl->eps, ws, pl->mi.as<double>(), pl->rank.as<int64_t>(), st));
+		NRM_TRY(nrm_fitvar_moments(pl->lc.p, yd, rows, n, n, cw, nc, n, pl->a.as<double>(), st));
+		NRM_TRY(nrm_fitvar_genes(pl->lc.p, yd, rows, n, n, u, c, nc, n, pl->a.as<double>(), pl->mi.as<double>(), pl->b.as<double>(), pl->mean.as<double>(), pl->sc.as<double>(), fv_flags,
+								 st));
+		NRM_TRY(nrm_fitvar_cells(pl->lc.p, yd, rows, n, n, u, c, nc, n, pl->b.as<double>(), pl->mean.as<double>(), pl->sc.as<double>(), pl->fpart.as<double>(), pl->v.as<double>(), st));
+		NRM_TRY(nrm_fitvar_update(pl->v.as<double>(), c, nc, n, n, pl->m2i.as<double>(), s, best, now, state + 4 * (i + 1), pl->eps, ws, st));
+	}
+	NRM_TRY(nrm_fitvar_weights(best, n, ws, pl->w(), fv_flags, st));
+	// scaling_factor's rescale, ln w, the scaled covariates
+	const unsigned blocks = (unsigned)((std::max(n, rows) + 255) / 256);
+	hipLaunchKernelGGL(k_front_scale, dim3(blocks), dim3(256), 0, st, pl->w(), n, pl->zero(), rows, pl->lnw.as<double>(), pl->wt.as<double>(), flags);
+	NRM_TRY(nrm_check_launch("k_front_scale"));
+	hipLaunchKernelGGL(k_front_dcn, dim3((unsigned)((n + 255) / 256), (unsigned)nc), dim3(256), 0, st, c, pl->cls.as<int32_t>(), pl->w(), n, pl->dcn.as<double>());
+	NRM_TRY(nrm_check_launch("k_front_dcn"));
+	// normvar: NormvarPlan._launch (normalisr_amd/norm.py)
+	int32_t* nv_flags = flags + 12;
+	NRM_TRY(nrm_normvar_solve(pl->lc.p, yd, rows, n, n, pl->lnw.as<double>(), pl->wt.as<double>(), c, nc, n, pl->tol, 1, pl->mom.as<double>(), pl->nb.as<double>(),
+							  pl->scale.as<double>(), pl->nrank.as<int64_t>(), nv_flags, st));
+	NRM_TRY(nrm_normvar_rescale(pl->lc.p, yd, rows, n, n, pl->lnw.as<double>(), pl->wt.as<double>(), c, nc, n, pl->nb.as<double>(), pl->scale.as<double>(), st));
+	return nrm_normvar_apply(pl->lc.p, yd, rows, n, n, pl->lnw.as<double>(), pl->wt.as<double>(), c, nc, n, pl->nb.as<double>(), pl->scale.as<double>(), pl->dtn.p, yd, n, nv_flags, st);
+}
+
+int plan_bind(nrm_front_plan* pl, const char* who) {
+	NRM_REQUIRE(pl != nullptr, "%s: null plan", who);
+	NRM_HIP(hipSetDevice(pl->device));
+	return NRM_OK;
+}
+
+int plan_upload(nrm_front_plan* pl, const char* who, const void* h_reads) {
+	return nrm_plan_upload(*pl, who, pl->adopted, h_reads, pl->own_x.p, pl->rows * pl->n * (int64_t)nrm_count_elem(pl->dtype));
+}
+
+// waits, reads every counter once, clears them; caller holds nrm_host_entry_mutex
+int plan_check(nrm_front_plan* pl, int64_t* near_constant) {
+	hipStream_t st = pl->last ? pl->last : pl->own;
+	if (near_constant) *near_constant = 0;
+	int32_t hf[FP_FLAGS];
+	int64_t hb[2] = {0, 0};
+	double hs[4] = {0, 0, 0, 0};
+	NRM_HIP(hipDeviceSynchronize());  // (steps may have gone to several streams since the last check)
+	NRM_TRY(nrm_read_flags(pl->flags.p, st, hf));
+	NRM_HIP(hipMemcpyAsync(hb, pl->big.p, sizeof(hb), hipMemcpyDeviceToHost, st));
+	NRM_HIP(hipMemcpyAsync(hs, pl->state() + 4 * pl->stepmax, sizeof(hs), hipMemcpyDeviceToHost, st));
+	NRM_TRY(nrm_fill_zero(pl->flags.p, FP_FLAGS * 4, (void*)st));
+	NRM_TRY(nrm_fill_zero(pl->big.p, 8, (void*)st));  // (big[1], the last step's maximum, stays: a second check reports it again)
+	NRM_HIP(hipStreamSynchronize(st));
+	if (pl->steps > 0) pl->cv_steps = (int64_t)hs[1], pl->max_count = hb[1];
+	pl->warned = hf[5];
+	if (near_constant) *near_constant = hf[5];
+	return nrm_front_plan_status(hf, pl->cap, hb[0]);
+}
+
+}  // namespace
+
+extern "C" int nrm_front_plan_create(nrm_front_plan** plan, const void* reads, int dtype, int64_t genes, int64_t n_cells, int64_t ld, int reads_on_device, const double* h_cov,
+									 int64_t n_cov, int64_t ntot, int64_t stepmax, double eps, double tol, int out_dtype, int64_t count_cap) {
+	NRM_REQUIRE(plan != nullptr, "nrm_front_plan_create: null plan pointer");
+	*plan = nullptr;
+	NrmFrontPlanArgs a;
+	a.reads = reads, a.dtype = dtype, a.rows = genes, a.n = n_cells, a.ld = ld ? ld : n_cells, a.on_device = reads_on_device, a.h_cov = h_cov, a.n_cov = n_cov;
+	a.ntot = ntot, a.stepmax = stepmax, a.eps = eps, a.tol = tol, a.out_dtype = out_dtype, a.count_cap = count_cap;
+	NRM_TRY(nrm_front_plan_create_args(a, nrm_normvar_device_covariates(), nrm_lcpm_table_cap()));  // every check: before any device call
+	NRM_REQUIRE(nrm_lcpm_row_tile() == 32 && nrm_fitvar_row_tile() == 32, "nrm_front_plan_create: the row tiles have changed (NRM_FRONT_MAX_ROWS)");
+
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_TRY(nrm_bind_device());
+	std::unique_ptr<nrm_front_plan> pl(new nrm_front_plan);
+	NRM_HIP(hipGetDevice(&pl->device));
+	const int64_t rows = genes, n = n_cells, nc = n_cov + NRM_FRONT_LCPM_ROWS + 1;
+	pl->rows = rows, pl->n = n, pl->ld = a.ld, pl->n_cov = n_cov, pl->nct = nc, pl->ntot = ntot < 0 ? -1 : ntot, pl->stepmax = stepmax, pl->cap = count_cap;
+	pl->dtype = dtype, pl->out_dtype = out_dtype, pl->eps = eps, pl->tol = tol, pl->adopted = reads_on_device != 0;
+	NRM_HIP(hipStreamCreateWithFlags(&pl->own, hipStreamNonBlocking));
+	if (pl->adopted)
+		pl->x = reads;
+	else {
+		NRM_TRY(pl->take(pl->own_x, (size_t)(rows * n) * nrm_count_elem(dtype)));
+		pl->x = pl->own_x.p;
+	}
+	const int64_t es = (int64_t)nrm_esize(out_dtype), lc_tiles = (rows + nrm_lcpm_row_tile() - 1) / nrm_lcpm_row_tile();
+	const int64_t fv_tiles = (rows + nrm_fitvar_row_tile() - 1) / nrm_fitvar_row_tile(), nstate = 4 * (stepmax + 1), npair = nc * (nc + 1) / 2;
+	nrm_front_plan* p = pl.get();
+	auto take = [p](DevBuf& b, size_t bytes) { return p->take(b, bytes); };
+	NRM_TRY(nrm_take_all(take, {{&p->ibuf, (2 * n + rows + 4) * 8}, {&p->part, std::max(nrm_lcpm_count_workspace(rows, n), lc_tiles * n) * 8}, {&p->fs, 32}, {&p->big, 16},
+								{&p->flags, FP_FLAGS * 4}, {&p->tab, count_cap * 8}, {&p->etab, count_cap * 8}, {&p->t1, n * 8}, {&p->lc, rows * n * es},
+								{&p->user, std::max<int64_t>(n_cov * n, 1) * 8}, {&p->dc, nc * n * 8}, {&p->dcn, nc * n * 8}, {&p->cls, nc * 4}, {&p->m2i, (nc + 1) * (nc + 1) * 8},
+								{&p->a, rows * nc * 8}, {&p->b, rows * nc * 8}, {&p->mean, rows * 8}, {&p->sc, rows * 8}, {&p->v, n * 8}, {&p->fpart, fv_tiles * n * 8}, {&p->s, n * 8},
+								{&p->best, n * 8}, {&p->u, n * 8}, {&p->cw, nc * n * 8}, {&p->mi, nc * nc * 8}, {&p->rank, 8}, {&p->ws, nrm_fitvar_plan_workspace(n, nc) * 8},
+								{&p->out, (nstate + n) * 8}, {&p->lnw, n * 8}, {&p->wt, rows * 8}, {&p->mom, rows * (npair + nc + 2) * 8}, {&p->nb, rows * nc * 8}, {&p->scale, rows * 8},
+								{&p->nrank, rows * 8}, {&p->dtn, rows * n * es}}));
+	NRM_TRY(nrm_fill_zero(p->flags.p, FP_FLAGS * 4, (void*)p->own));
+	NRM_TRY(nrm_fill_zero(p->big.p, 16, (void*)p->own));
+	NRM_TRY(nrm_fill_zero(p->tab.p, count_cap * 8, (void*)p->own));  // (entries past the largest count are never indexed; they are zero, not whatever the pool held)
+	NRM_TRY(nrm_fill_zero(p->etab.p, count_cap * 8, (void*)p->own));
+	NRM_TRY(nrm_fill_zero(p->out.p, (nstate + n) * 8, (void*)p->own));
+	if (n_cov > 0) NRM_HIP(hipMemcpyAsync(p->user.p, h_cov, (size_t)(n_cov * n) * 8, hipMemcpyHostToDevice, p->own));
+	NRM_HIP(hipStreamSynchronize(p->own));
+	if (pl->adopted)
+		NRM_HIP(hipDeviceSynchronize());  // (whatever the caller queued to fill its matrix is through before the first step reads it)
+	else
+		NRM_TRY(plan_upload(p, "nrm_front_plan_create", reads));
+	*plan = pl.release();
+	return NRM_OK;
+}
+
+extern "C" int nrm_front_plan_upload(nrm_front_plan* plan, const void* h_reads) {
+	NRM_TRY(plan_bind(plan, "nrm_front_plan_upload"));
+	return plan_upload(plan, "nrm_front_plan_upload", h_reads);
+}
+
+extern "C" int nrm_front_plan_step(nrm_front_plan* plan, void* stream) {
+	NRM_TRY(plan_bind(plan, "nrm_front_plan_step"));
+	return nrm_plan_step(*plan, "nrm_front_plan_step", stream, [plan](hipStream_t st) { return plan_enqueue(plan, st); });
+}
+
+extern "C" int nrm_front_plan_check(nrm_front_plan* plan, int64_t* near_constant) {
+	NRM_REQUIRE(plan != nullptr, "nrm_front_plan_check: null plan");
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_TRY(plan_bind(plan, "nrm_front_plan_check"));
+	return plan_check(plan, near_constant);
+}
+
+extern "C" int nrm_front_plan_results(nrm_front_plan* plan, void* h_dtn, double* h_dcn, double* h_w, double* h_wt, void* h_lcpm, double* h_cov) {
+	NRM_REQUIRE(plan != nullptr, "nrm_front_plan_results: null plan");
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_TRY(plan_bind(plan, "nrm_front_plan_results"));
+	NRM_REQUIRE(plan->steps > 0, "nrm_front_plan_results: no step has run");
+	NRM_TRY(plan_check(plan, nullptr));
+	const size_t mb = (size_t)(plan->rows * plan->n) * nrm_esize(plan->out_dtype), cb = (size_t)(plan->nct * plan->n) * 8;
+	NRM_TRY(copy_out(h_dtn, plan->dtn.p, mb));
+	NRM_TRY(copy_out(h_dcn, plan->dcn.p, cb));
+	NRM_TRY(copy_out(h_w, plan->w(), (size_t)plan->n * 8));
+	NRM_TRY(copy_out(h_wt, plan->wt.p, (size_t)plan->rows * 8));
+	NRM_TRY(copy_out(h_lcpm, plan->lc.p, mb));
+	return copy_out(h_cov, plan->dc.p, cb);
+}
+
+extern "C" int nrm_front_plan_device_results(nrm_front_plan* plan, void** d_dtn, void** d_dcn, void** d_lcpm, int64_t* ld, void** stream) {
+	NRM_REQUIRE(plan != nullptr, "nrm_front_plan_device_results: null plan");
+	if (d_dtn) *d_dtn = plan->dtn.p;
+	if (d_dcn) *d_dcn = plan->dcn.p;
+	if (d_lcpm) *d_lcpm = plan->lc.p;
+	if (ld) *ld = plan->n;
+	if (stream) *stream = (void*)plan->own;
+	return NRM_OK;
+}
+
+extern "C" int nrm_front_plan_stream(nrm_front_plan* plan, void** stream) { return nrm_plan_stream(plan, "nrm_front_plan_stream", stream); }
+
+extern "C" int nrm_front_plan_info(nrm_front_plan* plan, int64_t info[8]) {
+	NRM_REQUIRE(plan != nullptr && info != nullptr, "nrm_front_plan_info: null pointer");
+	info[0] = plan->exec ? 1 : 0, info[1] = plan->steps, info[2] = plan->cv_steps, info[3] = plan->max_count, info[4] = plan->cap, info[5] = plan->nct, info[6] = plan->bytes;
+	info[7] = plan->warned;
+	return NRM_OK;
+}
+
+extern "C" int nrm_front_plan_time(nrm_front_plan* plan, int64_t steps, double* ms_per_step) {
+	NRM_TRY(plan_bind(plan, "nrm_front_plan_time"));
+	return nrm_plan_time(*plan, "nrm_front_plan_time", steps, ms_per_step, [plan] { return nrm_front_plan_step(plan, nullptr); });
+}
+
+extern "C" int nrm_front_plan_destroy(nrm_front_plan* plan) { return nrm_plan_destroy(plan); }
