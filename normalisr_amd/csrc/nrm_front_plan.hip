@@ -2,9 +2,11 @@
 // lcpm -> normcov -> compute_var -> scaling_factor -> normvar of the reference (lcpm.py:21-283, norm.py:4-128,166-289) with its default options, as ONE enqueue on
 // ONE stream, and from the second step on one hipGraphLaunch (nrm_plan_core.h).  numpy and the library are all a caller needs: no torch.
 //
-// The large passes are the existing entries, called as they stand: nrm_lcpm_count / colsum / write, nrm_fitvar_* in the sequence of nrm_compute_var_host,
-// nrm_normvar_solve / rescale / apply in the sequence of norm.NormvarPlan._launch.  What the host did between them is here as small kernels that read their
-// operands from device memory, so that no launch argument of a step depends on the data and a captured graph stays valid when the counts are rewritten:
+// The large passes are the step records that the whole-problem entries fill per call and the plan keeps as members: NrmLcpmPasses (nrm_lcpm_step.h: count / colsum /
+// write), NrmFitvarStep (nrm_fitvar_step.h: compute_var's whole sequence) and NrmNormvarStep (nrm_normvar_step.h: solve, then rescale and apply).  Each holds its
+// sizes, its buffers and its launches once, for nrm_lcpm_host, nrm_compute_var_host, nrm_normvar_host and this plan alike.  What the host does between them in the
+// entries is here as small kernels that read their operands from device memory, so that no launch argument of a step depends on the data and a captured graph stays
+// valid when the counts are rewritten:
 //   k_front_scalars  ONE workgroup: t0 = sum + 2 (or ntot + 2), len = max + 1 (clamped to the cap), the counters of lcpm's refusals
 //   k_front_tables   tab[x] = psi(1 + x) - psi(t0), etab[x] = exp(tab[x]) for x < len; a thread per entry of the cap, every entry on its own (nrm_digamma.h)
 //   k_front_cov      a workgroup per covariate row: lcpm's three rows from the integer totals, then normcov on [user rows; those three], the ones row appended
@@ -16,9 +18,12 @@
 #include <memory>
 #include "nrm_device.h"
 #include "nrm_digamma.h"
+#include "nrm_fitvar_step.h"
 #include "nrm_front_plan_args.h"
 #include "nrm_host_entry.h"
 #include "nrm_jacobi_lanes.h"
+#include "nrm_lcpm_step.h"
+#include "nrm_normvar_step.h"
 #include "nrm_plan_core.h"
 
 #define FP_M2_THREADS 1024
@@ -206,75 +211,53 @@ __global__ void __launch_bounds__(256) k_front_dcn(const double* __restrict__ dc
 }
 
 struct nrm_front_plan : NrmPlanCore {
-	int64_t rows = 0, n = 0, ld = 0, n_cov = 0, nct = 0, ntot = -1, stepmax = 1, cap = 0;
-	int dtype = NRM_I32, out_dtype = NRM_F64;
-	double eps = 1e-6, tol = 1e-8;
+	int64_t rows = 0, n = 0, n_cov = 0, nct = 0, ntot = -1, cap = 0;
+	int out_dtype = NRM_F64;
 	bool adopted = false;
-	const void* x = nullptr;  // the counts a step reads: own_x, or the caller's
-	// lcpm | the covariates | compute_var (the buffers of nrm_compute_var_host) | normvar (those of NormvarPlan)
-	DevBuf own_x, ibuf, part, fs, big, flags, tab, etab, t1, lc;
+	// the three stages that the whole-problem entries run too, as their step records; around them what is the plan's own:
+	// the counts and lcpm's scalars, tables and result | the covariates | scaling_factor's operands and normvar's result
+	NrmLcpmPasses lc;
+	NrmFitvarStep fit;
+	NrmNormvarStep nv;
+	DevBuf own_x, fs, big, flags, tab, etab, t1, lcpm;
 	DevBuf user, dc, dcn, cls, m2i;
-	DevBuf a, b, mean, sc, v, fpart, s, best, u, cw, mi, rank, ws, out;
-	DevBuf lnw, wt, mom, nb, scale, nrank, dtn;
+	DevBuf lnw, wt, dtn;
 	int64_t cv_steps = 0, max_count = 0, warned = 0;
 	~nrm_front_plan() { shutdown(); }  // (its body runs before the DevBuf members go back to the pool: NrmPlanCore::shutdown)
-	int64_t* total() const { return ibuf.as<int64_t>(); }
-	int64_t* nnz() const { return total() + n; }
-	int64_t* zero() const { return total() + 2 * n; }
-	int64_t* info() const { return total() + 2 * n + rows; }
-	double* state() const { return out.as<double>(); }
-	double* w() const { return state() + 4 * (stepmax + 1); }
 };
 
 namespace {
 
 int plan_enqueue(nrm_front_plan* pl, hipStream_t st) {
 	const int64_t rows = pl->rows, n = pl->n, nc = pl->nct;
-	const int yd = pl->out_dtype;
 	int32_t* flags = pl->flags.as<int32_t>();
+	NrmLcpmPasses& lc = pl->lc;
 	// lcpm: count, the scalars and the tables on the device, colsum, write
-	NRM_HIP(hipMemsetAsync(pl->ibuf.p, 0, (size_t)(2 * n + rows + 4) * 8, st));  // (the gene zero counts are integer atomics)
-	NRM_TRY(nrm_lcpm_count(pl->x, pl->dtype, rows, n, pl->ld, pl->total(), pl->nnz(), pl->zero(), pl->info(), pl->part.as<int64_t>(), st));
-	hipLaunchKernelGGL(k_front_scalars, dim3(1), dim3(256), 0, st, pl->info(), pl->total(), n, pl->ntot, pl->cap, pl->fs.as<double>(), flags, pl->big.as<int64_t>());
+	NRM_TRY(lc.clear(st));  // (the gene zero counts are integer atomics)
+	NRM_TRY(lc.count(st));
+	hipLaunchKernelGGL(k_front_scalars, dim3(1), dim3(256), 0, st, lc.info(), lc.total(), n, pl->ntot, pl->cap, pl->fs.as<double>(), flags, pl->big.as<int64_t>());
 	NRM_TRY(nrm_check_launch("k_front_scalars"));
 	hipLaunchKernelGGL(k_front_tables, dim3((unsigned)((pl->cap + 255) / 256)), dim3(256), 0, st, pl->fs.as<double>(), pl->cap, pl->tab.as<double>(), pl->etab.as<double>());
 	NRM_TRY(nrm_check_launch("k_front_tables"));
-	NRM_TRY(nrm_lcpm_colsum(pl->x, pl->dtype, rows, n, pl->ld, pl->etab.as<double>(), pl->cap, pl->part.as<double>(), pl->t1.as<double>(), st));
-	NRM_TRY(nrm_lcpm_write(pl->x, pl->dtype, rows, n, pl->ld, pl->tab.as<double>(), pl->cap, pl->t1.as<double>(), pl->lc.p, yd, n, st));
+	NRM_TRY(lc.colsum(pl->etab.as<double>(), pl->cap, 0.0, pl->t1.as<double>(), st));  // (the unit is the CSR form's; the plan's counts are dense)
+	NRM_TRY(lc.write(pl->tab.as<double>(), pl->cap, pl->t1.as<double>(), pl->lcpm.p, pl->out_dtype, n, st));
 	// lcpm's covariate rows, normcov, the pseudo-inverse of the second regression
 	double* c = pl->dc.as<double>();
-	hipLaunchKernelGGL(k_front_cov, dim3((unsigned)nc), dim3(256), 0, st, pl->user.as<double>(), (int)pl->n_cov, pl->total(), pl->nnz(), rows, n, (int)nc, c, pl->cls.as<int32_t>(),
-					   flags);
+	hipLaunchKernelGGL(k_front_cov, dim3((unsigned)nc), dim3(256), 0, st, pl->user.as<double>(), (int)pl->n_cov, lc.total(), lc.nnz(), rows, n, (int)nc, c, pl->cls.as<int32_t>(), flags);
 	NRM_TRY(nrm_check_launch("k_front_cov"));
 	hipLaunchKernelGGL(k_front_m2i, dim3(1), dim3(FP_M2_THREADS), 0, st, c, (int)nc, n, 1e-8, pl->m2i.as<double>());
 	NRM_TRY(nrm_check_launch("k_front_m2i"));
-	// compute_var: the sequence of nrm_compute_var_host (nrm_host_front.hip) on lcpm in HBM
-	double *state = pl->state(), *s = pl->s.as<double>(), *best = pl->best.as<double>(), *u = pl->u.as<double>(), *cw = pl->cw.as<double>(), *ws = pl->ws.as<double>();
-	int32_t* fv_flags = flags + 8;
-	NRM_TRY(nrm_fitvar_plan_start(n, s, best, state, st));
-	for (int64_t i = 0; i < pl->stepmax; i++) {
-		const double* now = state + 4 * i;
-		NRM_TRY(nrm_fitvar_design(c, nc, n, n, s, now, pl->eps, u, cw, ws, st));
-		NRM_TRY(nrm_fitvar_pinv(n, nc, 1e-8, now, pl->eps, ws, pl->mi.as<double>(), pl->rank.as<int64_t>(), st));
-		NRM_TRY(nrm_fitvar_moments(pl->lc.p, yd, rows, n, n, cw, nc, n, pl->a.as<double>(), st));
-		NRM_TRY(nrm_fitvar_genes(pl->lc.p, yd, rows, n, n, u, c, nc, n, pl->a.as<double>(), pl->mi.as<double>(), pl->b.as<double>(), pl->mean.as<double>(), pl->sc.as<double>(), fv_flags,
-								 st));
-		NRM_TRY(nrm_fitvar_cells(pl->lc.p, yd, rows, n, n, u, c, nc, n, pl->b.as<double>(), pl->mean.as<double>(), pl->sc.as<double>(), pl->fpart.as<double>(), pl->v.as<double>(), st));
-		NRM_TRY(nrm_fitvar_update(pl->v.as<double>(), c, nc, n, n, pl->m2i.as<double>(), s, best, now, state + 4 * (i + 1), pl->eps, ws, st));
-	}
-	NRM_TRY(nrm_fitvar_weights(best, n, ws, pl->w(), fv_flags, st));
+	// compute_var on lcpm in HBM
+	NRM_TRY(pl->fit.enqueue(st));
 	// scaling_factor's rescale, ln w, the scaled covariates
 	const unsigned blocks = (unsigned)((std::max(n, rows) + 255) / 256);
-	hipLaunchKernelGGL(k_front_scale, dim3(blocks), dim3(256), 0, st, pl->w(), n, pl->zero(), rows, pl->lnw.as<double>(), pl->wt.as<double>(), flags);
+	hipLaunchKernelGGL(k_front_scale, dim3(blocks), dim3(256), 0, st, pl->fit.w(), n, lc.zero(), rows, pl->lnw.as<double>(), pl->wt.as<double>(), flags);
 	NRM_TRY(nrm_check_launch("k_front_scale"));
-	hipLaunchKernelGGL(k_front_dcn, dim3((unsigned)((n + 255) / 256), (unsigned)nc), dim3(256), 0, st, c, pl->cls.as<int32_t>(), pl->w(), n, pl->dcn.as<double>());
+	hipLaunchKernelGGL(k_front_dcn, dim3((unsigned)((n + 255) / 256), (unsigned)nc), dim3(256), 0, st, c, pl->cls.as<int32_t>(), pl->fit.w(), n, pl->dcn.as<double>());
 	NRM_TRY(nrm_check_launch("k_front_dcn"));
-	// normvar: NormvarPlan._launch (normalisr_amd/norm.py)
-	int32_t* nv_flags = flags + 12;
-	NRM_TRY(nrm_normvar_solve(pl->lc.p, yd, rows, n, n, pl->lnw.as<double>(), pl->wt.as<double>(), c, nc, n, pl->tol, 1, pl->mom.as<double>(), pl->nb.as<double>(),
-							  pl->scale.as<double>(), pl->nrank.as<int64_t>(), nv_flags, st));
-	NRM_TRY(nrm_normvar_rescale(pl->lc.p, yd, rows, n, n, pl->lnw.as<double>(), pl->wt.as<double>(), c, nc, n, pl->nb.as<double>(), pl->scale.as<double>(), st));
-	return nrm_normvar_apply(pl->lc.p, yd, rows, n, n, pl->lnw.as<double>(), pl->wt.as<double>(), c, nc, n, pl->nb.as<double>(), pl->scale.as<double>(), pl->dtn.p, yd, n, nv_flags, st);
+	// normvar: lcpm, ln w and the genes' exponents in, dtn out
+	NRM_TRY(pl->nv.solve(st));
+	return pl->nv.finish(st);
 }
 
 int plan_bind(nrm_front_plan* pl, const char* who) {
@@ -284,7 +267,7 @@ int plan_bind(nrm_front_plan* pl, const char* who) {
 }
 
 int plan_upload(nrm_front_plan* pl, const char* who, const void* h_reads) {
-	return nrm_plan_upload(*pl, who, pl->adopted, h_reads, pl->own_x.p, pl->rows * pl->n * (int64_t)nrm_count_elem(pl->dtype));
+	return nrm_plan_upload(*pl, who, pl->adopted, h_reads, pl->own_x.p, pl->rows * pl->n * (int64_t)nrm_count_elem(pl->lc.dtype));
 }
 
 // waits, reads every counter once, clears them; caller holds nrm_host_entry_mutex
@@ -297,7 +280,7 @@ int plan_check(nrm_front_plan* pl, int64_t* near_constant) {
 	NRM_HIP(hipDeviceSynchronize());  // (steps may have gone to several streams since the last check)
 	NRM_TRY(nrm_read_flags(pl->flags.p, st, hf));
 	NRM_HIP(hipMemcpyAsync(hb, pl->big.p, sizeof(hb), hipMemcpyDeviceToHost, st));
-	NRM_HIP(hipMemcpyAsync(hs, pl->state() + 4 * pl->stepmax, sizeof(hs), hipMemcpyDeviceToHost, st));
+	NRM_HIP(hipMemcpyAsync(hs, pl->fit.state() + 4 * pl->fit.stepmax, sizeof(hs), hipMemcpyDeviceToHost, st));
 	NRM_TRY(nrm_fill_zero(pl->flags.p, FP_FLAGS * 4, (void*)st));
 	NRM_TRY(nrm_fill_zero(pl->big.p, 8, (void*)st));  // (big[1], the last step's maximum, stays: a second check reports it again)
 	NRM_HIP(hipStreamSynchronize(st));
@@ -323,35 +306,37 @@ extern "C" int nrm_front_plan_create(nrm_front_plan** plan, const void* reads, i
 	NRM_TRY(nrm_bind_device());
 	std::unique_ptr<nrm_front_plan> pl(new nrm_front_plan);
 	NRM_HIP(hipGetDevice(&pl->device));
-	const int64_t rows = genes, n = n_cells, nc = n_cov + NRM_FRONT_LCPM_ROWS + 1;
-	pl->rows = rows, pl->n = n, pl->ld = a.ld, pl->n_cov = n_cov, pl->nct = nc, pl->ntot = ntot < 0 ? -1 : ntot, pl->stepmax = stepmax, pl->cap = count_cap;
-	pl->dtype = dtype, pl->out_dtype = out_dtype, pl->eps = eps, pl->tol = tol, pl->adopted = reads_on_device != 0;
-	NRM_HIP(hipStreamCreateWithFlags(&pl->own, hipStreamNonBlocking));
-	if (pl->adopted)
-		pl->x = reads;
-	else {
-		NRM_TRY(pl->take(pl->own_x, (size_t)(rows * n) * nrm_count_elem(dtype)));
-		pl->x = pl->own_x.p;
-	}
-	const int64_t es = (int64_t)nrm_esize(out_dtype), lc_tiles = (rows + nrm_lcpm_row_tile() - 1) / nrm_lcpm_row_tile();
-	const int64_t fv_tiles = (rows + nrm_fitvar_row_tile() - 1) / nrm_fitvar_row_tile(), nstate = 4 * (stepmax + 1), npair = nc * (nc + 1) / 2;
+	const int64_t rows = genes, n = n_cells, nc = n_cov + NRM_FRONT_LCPM_ROWS + 1, es = (int64_t)nrm_esize(out_dtype);
 	nrm_front_plan* p = pl.get();
+	p->rows = rows, p->n = n, p->n_cov = n_cov, p->nct = nc, p->ntot = ntot < 0 ? -1 : ntot, p->cap = count_cap, p->out_dtype = out_dtype, p->adopted = reads_on_device != 0;
+	NRM_HIP(hipStreamCreateWithFlags(&p->own, hipStreamNonBlocking));
 	auto take = [p](DevBuf& b, size_t bytes) { return p->take(b, bytes); };
-	NRM_TRY(nrm_take_all(take, {{&p->ibuf, (2 * n + rows + 4) * 8}, {&p->part, std::max(nrm_lcpm_count_workspace(rows, n), lc_tiles * n) * 8}, {&p->fs, 32}, {&p->big, 16},
-								{&p->flags, FP_FLAGS * 4}, {&p->tab, count_cap * 8}, {&p->etab, count_cap * 8}, {&p->t1, n * 8}, {&p->lc, rows * n * es},
-								{&p->user, std::max<int64_t>(n_cov * n, 1) * 8}, {&p->dc, nc * n * 8}, {&p->dcn, nc * n * 8}, {&p->cls, nc * 4}, {&p->m2i, (nc + 1) * (nc + 1) * 8},
-								{&p->a, rows * nc * 8}, {&p->b, rows * nc * 8}, {&p->mean, rows * 8}, {&p->sc, rows * 8}, {&p->v, n * 8}, {&p->fpart, fv_tiles * n * 8}, {&p->s, n * 8},
-								{&p->best, n * 8}, {&p->u, n * 8}, {&p->cw, nc * n * 8}, {&p->mi, nc * nc * 8}, {&p->rank, 8}, {&p->ws, nrm_fitvar_plan_workspace(n, nc) * 8},
-								{&p->out, (nstate + n) * 8}, {&p->lnw, n * 8}, {&p->wt, rows * 8}, {&p->mom, rows * (npair + nc + 2) * 8}, {&p->nb, rows * nc * 8}, {&p->scale, rows * 8},
-								{&p->nrank, rows * 8}, {&p->dtn, rows * n * es}}));
+	if (!p->adopted) NRM_TRY(take(p->own_x, (size_t)(rows * n) * nrm_count_elem(dtype)));
+	// lcpm | the covariates | compute_var | normvar: each record sizes its own buffers, the plan what lies between them
+	NrmLcpmPasses& lc = p->lc;
+	lc.rows = rows, lc.n = n, lc.dtype = dtype, lc.d_x = p->adopted ? reads : p->own_x.p, lc.ld = a.ld;
+	NRM_TRY(lc.alloc(take));
+	NRM_TRY(nrm_take_all(take, {{&p->fs, 32}, {&p->big, 16}, {&p->flags, FP_FLAGS * 4}, {&p->tab, count_cap * 8}, {&p->etab, count_cap * 8}, {&p->t1, n * 8}, {&p->lcpm, rows * n * es},
+								{&p->user, std::max<int64_t>(n_cov * n, 1) * 8}, {&p->dc, nc * n * 8}, {&p->dcn, nc * n * 8}, {&p->cls, nc * 4}, {&p->m2i, (nc + 1) * (nc + 1) * 8}}));
+	NrmFitvarStep& fit = p->fit;
+	fit.rows = rows, fit.n = n, fit.ldy = n, fit.nc = nc, fit.stepmax = stepmax, fit.eps = eps, fit.y_dtype = out_dtype;
+	fit.d_y = p->lcpm.p, fit.d_c = p->dc.as<double>(), fit.d_m2i = p->m2i.as<double>(), fit.flags = p->flags.as<int32_t>() + 8;
+	NRM_TRY(fit.alloc(take));
+	NRM_TRY(nrm_take_all(take, {{&p->lnw, n * 8}, {&p->wt, rows * 8}}));
+	NrmNormvarStep& nv = p->nv;
+	nv.rows = rows, nv.n = n, nv.ldy = n, nv.nc = nc, nv.ldo = n, nv.tol = tol, nv.keepvar = 1, nv.y_dtype = nv.out_dtype = out_dtype;
+	nv.d_y = p->lcpm.p, nv.d_lnw = p->lnw.as<double>(), nv.d_wt = p->wt.as<double>(), nv.d_c = p->dc.as<double>(), nv.flags = p->flags.as<int32_t>() + 12;
+	NRM_TRY(nv.alloc(take));
+	NRM_TRY(take(p->dtn, (size_t)(rows * n * es)));
+	nv.d_out = p->dtn.p;
 	NRM_TRY(nrm_fill_zero(p->flags.p, FP_FLAGS * 4, (void*)p->own));
 	NRM_TRY(nrm_fill_zero(p->big.p, 16, (void*)p->own));
 	NRM_TRY(nrm_fill_zero(p->tab.p, count_cap * 8, (void*)p->own));  // (entries past the largest count are never indexed; they are zero, not whatever the pool held)
 	NRM_TRY(nrm_fill_zero(p->etab.p, count_cap * 8, (void*)p->own));
-	NRM_TRY(nrm_fill_zero(p->out.p, (nstate + n) * 8, (void*)p->own));
+	NRM_TRY(nrm_fill_zero(fit.out.p, fit.out_doubles() * 8, (void*)p->own));
 	if (n_cov > 0) NRM_HIP(hipMemcpyAsync(p->user.p, h_cov, (size_t)(n_cov * n) * 8, hipMemcpyHostToDevice, p->own));
 	NRM_HIP(hipStreamSynchronize(p->own));
-	if (pl->adopted)
+	if (p->adopted)
 		NRM_HIP(hipDeviceSynchronize());  // (whatever the caller queued to fill its matrix is through before the first step reads it)
 	else
 		NRM_TRY(plan_upload(p, "nrm_front_plan_create", reads));
@@ -385,9 +370,9 @@ extern "C" int nrm_front_plan_results(nrm_front_plan* plan, void* h_dtn, double*
 	const size_t mb = (size_t)(plan->rows * plan->n) * nrm_esize(plan->out_dtype), cb = (size_t)(plan->nct * plan->n) * 8;
 	NRM_TRY(copy_out(h_dtn, plan->dtn.p, mb));
 	NRM_TRY(copy_out(h_dcn, plan->dcn.p, cb));
-	NRM_TRY(copy_out(h_w, plan->w(), (size_t)plan->n * 8));
+	NRM_TRY(copy_out(h_w, plan->fit.w(), (size_t)plan->n * 8));
 	NRM_TRY(copy_out(h_wt, plan->wt.p, (size_t)plan->rows * 8));
-	NRM_TRY(copy_out(h_lcpm, plan->lc.p, mb));
+	NRM_TRY(copy_out(h_lcpm, plan->lcpm.p, mb));
 	return copy_out(h_cov, plan->dc.p, cb);
 }
 
@@ -395,7 +380,7 @@ extern "C" int nrm_front_plan_device_results(nrm_front_plan* plan, void** d_dtn,
 	NRM_REQUIRE(plan != nullptr, "nrm_front_plan_device_results: null plan");
 	if (d_dtn) *d_dtn = plan->dtn.p;
 	if (d_dcn) *d_dcn = plan->dcn.p;
-	if (d_lcpm) *d_lcpm = plan->lc.p;
+	if (d_lcpm) *d_lcpm = plan->lcpm.p;
 	if (ld) *ld = plan->n;
 	if (stream) *stream = (void*)plan->own;
 	return NRM_OK;

@@ -68,6 +68,34 @@ static inline int nrm_front_plan_create_args(const NrmFrontPlanArgs& a, int64_t 
 	return NRM_OK;
 }
 
+// compute_var's counters ([0] nrm_fitvar_genes, [1] nrm_fitvar_weights) as what the reference raises (norm.py:108,125-127).  nrm_compute_var_host and the plan's
+// check both say it through here.
+static inline int nrm_compute_var_status(const int32_t f[2]) {
+	if (f[0]) {
+		nrm_set_error("compute_var: %d genes with a constant residual, whose spread divides (norm.py:108,125)", f[0]);
+		return NRM_E_NUMERIC;
+	}
+	if (f[1]) {
+		nrm_set_error("compute_var: %d weights are not finite and positive (norm.py:125-127)", f[1]);
+		return NRM_E_NUMERIC;
+	}
+	return NRM_OK;
+}
+
+// normvar's counters ([0] genes of rank 0: nrm_normvar_solve, [1] nrm_normvar_apply) as what the reference raises (norm.py:160,286).  The plan's check says both
+// through here; nrm_normvar_host hands the count of [0] to its caller with NRM_OK (*zero_rank) and says [1] through here.
+static inline int nrm_normvar_status(const int32_t f[2]) {
+	if (f[0]) {
+		nrm_set_error("Zero-rank covariates found.");
+		return NRM_E_DEVICE;
+	}
+	if (f[1]) {
+		nrm_set_error("normvar: non-finite results (norm.py:286)");
+		return NRM_E_NUMERIC;
+	}
+	return NRM_OK;
+}
+
 // The plan's counters as what the reference raises, in the order it would meet them: lcpm (lcpm.py:86, :97, :196), the table cap, normcov (norm.py:34-37),
 // compute_var (norm.py:108,125-127), scaling_factor (lcpm.py:278-282), normvar (norm.py:160,286).  f: the sixteen counters; cap and count for the cap's words.
 static inline int nrm_front_plan_status(const int32_t f[16], int64_t cap, int64_t count) {
@@ -82,25 +110,10 @@ static inline int nrm_front_plan_status(const int32_t f[16], int64_t cap, int64_
 		return NRM_E_UNSUPPORTED;
 	}
 	NRM_REQUIRE(!f[4], "Detected constant covariate. Please only provide full-rank covariate without constant covariate.");
-	if (f[8]) {
-		nrm_set_error("compute_var: %d genes with a constant residual, whose spread divides (norm.py:108,125)", f[8]);
-		return NRM_E_NUMERIC;
-	}
-	if (f[9]) {
-		nrm_set_error("compute_var: %d weights are not finite and positive (norm.py:125-127)", f[9]);
-		return NRM_E_NUMERIC;
-	}
+	if (const int rc = nrm_compute_var_status(f + 8)) return rc;
 	if (f[6]) {
 		nrm_set_error("scaling_factor: no gene has a zero entry, or a value is not finite (lcpm.py:278-282)");
 		return NRM_E_NUMERIC;
 	}
-	if (f[12]) {
-		nrm_set_error("Zero-rank covariates found.");
-		return NRM_E_DEVICE;
-	}
-	if (f[13]) {
-		nrm_set_error("normvar: non-finite results (norm.py:286)");
-		return NRM_E_NUMERIC;
-	}
-	return NRM_OK;
+	return nrm_normvar_status(f + 12);
 }

@@ -63,7 +63,7 @@ struct DevBuf {
 		return reinterpret_cast<T*>(p);
 	}
 };
-// the `take` of a step record (nrm_single1_step.h, nrm_de_sparse_step.h) for a caller that keeps no count of its pool bytes; a table of buffers through a `take`
+// the `take` of a step record (nrm_single1_step.h, nrm_de_sparse_step.h, nrm_lcpm_step.h, nrm_fitvar_step.h, nrm_normvar_step.h) for a caller that keeps no count of its pool bytes; a table of buffers through a `take`
 static inline int nrm_take_plain(DevBuf& b, size_t bytes) { return b.alloc(bytes); }
 template <typename Take>
 int nrm_take_all(Take take, std::initializer_list<std::pair<DevBuf*, int64_t>> table) {

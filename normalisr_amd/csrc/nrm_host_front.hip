@@ -1,12 +1,18 @@
 // The front half of the pipeline as whole-problem entries, numpy buffers in, numpy buffers out, no torch: nrm_lcpm_host / nrm_lcpm_csr_host (lcpm.py:21-208 and
 // the zero counts of lcpm.py:258), nrm_compute_var_host (norm.py:56-128) and nrm_qc_reads_host / nrm_qc_reads_csr_host (qc.py:4-85).  The kernels are those of
-// csrc/nrm_lcpm.hip, nrm_lcpm_sparse.hip, nrm_fitvar.hip, nrm_fitvar_plan.hip and nrm_qc.hip, unchanged, sequenced here as normalisr_amd/lcpm.py, norm.py
-// (ComputeVarPlan._launch) and qc.py sequence them, on the library's own scratch pool.  The arithmetic between two launches is in nrm_host_math.h.
+// csrc/nrm_lcpm.hip, nrm_lcpm_sparse.hip, nrm_fitvar.hip, nrm_fitvar_plan.hip and nrm_qc.hip, unchanged, on the library's own scratch pool.  lcpm's passes and
+// compute_var's sequence are the step records NrmLcpmPasses (nrm_lcpm_step.h) and NrmFitvarStep (nrm_fitvar_step.h), which the resident plan of nrm_front_plan.hip
+// runs too: an entry uploads, fills a record per call, and does on the host what lies around it -- the read-back and the tables between lcpm's passes, the
+// pseudo-inverse before compute_var, the counters' words after it (nrm_front_plan_args.h).  qc_reads is sequenced here as normalisr_amd/qc.py sequences it.  The
+// arithmetic between two launches is in nrm_host_math.h.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "nrm_fitvar_step.h"
+#include "nrm_front_plan_args.h"
 #include "nrm_host_entry.h"
+#include "nrm_lcpm_step.h"
 
 static const char* const MALFORMED_CSR =
 	"Malformed CSR matrix: indptr must rise from 0 to the number of stored entries, and the columns of every row must lie in [0, n_cell) and "
@@ -35,6 +41,11 @@ struct FrontCounts {
 		NRM_TRY(upload_bytes(h_indices, z * 4, indices, st));
 		return upload_bytes(h_data, z * nrm_count_elem(dt), x, st);
 	}
+	// what lcpm's passes read of it (nrm_lcpm_step.h); a dense matrix uploaded here is contiguous
+	void view(NrmLcpmPasses& p) const {
+		p.rows = rows, p.n = n, p.dtype = dtype, p.csr = csr, p.d_x = x.p, p.ld = n;
+		p.d_indptr = indptr.as<int64_t>(), p.d_indices = indices.as<int32_t>(), p.stored = nnz;
+	}
 };
 
 static int front_check_dense(const char* what, const void* h_x, int dtype, int64_t rows, int64_t n) {
@@ -60,27 +71,22 @@ static int lcpm_check(const char* what, bool have_out, void* h_gene_zero, int64_
 	return NRM_OK;
 }
 
-// the three passes on a matrix already in HBM: count, one read-back, the tables on the host, colsum, write, copy out
+// the three passes on a matrix already in HBM (nrm_lcpm_step.h): count, one read-back, the tables on the host, colsum, write, copy out
 static int lcpm_run(const FrontCounts& m, int normalize, int64_t ntot, void* h_out, int out_dtype, double* h_cov, int64_t* h_gene_zero, int64_t* h_info, hipStream_t st) {
 	const int64_t rows = m.rows, n = m.n;
-	DevBuf ibuf, part;
-	NRM_TRY(ibuf.alloc_zero((size_t)(2 * n + rows + 4) * 8, st));
-	int64_t *d_total = ibuf.as<int64_t>(), *d_nnz = d_total + n, *d_zero = d_total + 2 * n, *d_info = d_total + 2 * n + rows;
-	const int64_t cwords = m.csr ? nrm_lcpm_csr_workspace(rows, n) : nrm_lcpm_count_workspace(rows, n);
-	const int64_t tiles = (rows + nrm_lcpm_row_tile() - 1) / nrm_lcpm_row_tile();
-	NRM_TRY(part.alloc((size_t)std::max(cwords, tiles * n) * 8));  // (the count pass's slabs, then the column sums' partials)
-	if (m.csr)
-		NRM_TRY(nrm_lcpm_csr_count(m.indptr.as<int64_t>(), m.indices.as<int32_t>(), m.x.p, m.dtype, rows, n, m.nnz, d_total, d_nnz, d_zero, d_info, part.as<int64_t>(), st));
-	else
-		NRM_TRY(nrm_lcpm_count(m.x.p, m.dtype, rows, n, n, d_total, d_nnz, d_zero, d_info, part.as<int64_t>(), st));
+	NrmLcpmPasses lc;
+	m.view(lc);
+	NRM_TRY(lc.alloc(nrm_take_plain));
+	NRM_TRY(lc.clear(st));
+	NRM_TRY(lc.count(st));
 	std::vector<int64_t> h;
-	NRM_TRY(download(h, ibuf.p, (size_t)(2 * n + rows + 4)));  // (one small read-back: 2 n_cell + n_gene + 4 integers)
-	const int64_t* info = &h[(size_t)(2 * n + rows)];
+	NRM_TRY(download(h, lc.ibuf.p, (size_t)lc.block_words()));  // (one small read-back: 2 n_cell + n_gene + 4 integers)
+	const int64_t* info = &h[(size_t)(lc.info() - lc.total())];
 	NRM_REQUIRE(!info[3], "%s", MALFORMED_CSR);
 	NRM_REQUIRE(!info[2] || (!h_out && !h_cov), "Negative value in d detected.");  // (the zero counts alone, lcpm.py:258, do not depend on it)
 	h_info[0] = info[0];
 	h_info[1] = info[1];
-	if (h_gene_zero) memcpy(h_gene_zero, &h[(size_t)(2 * n)], (size_t)rows * 8);
+	if (h_gene_zero) memcpy(h_gene_zero, &h[(size_t)(lc.zero() - lc.total())], (size_t)rows * 8);
 	if (h_cov) NRM_REQUIRE(nrm_lcpm_cov_rows(h.data(), h.data() + n, rows, n, h_cov) < 0, "Found cell with no read at all. Please remove.");
 	if (!h_out) return NRM_OK;
 	const double t0 = ntot < 0 ? (double)(info[0] + 2) : (double)ntot + 2.0;
@@ -104,18 +110,11 @@ static int lcpm_run(const FrontCounts& m, int normalize, int64_t ntot, void* h_o
 		NRM_TRY(d_exp.alloc((size_t)len * 8));
 		NRM_HIP(hipMemcpy(d_exp.p, etab.data(), (size_t)len * 8, hipMemcpyHostToDevice));
 		NRM_TRY(d_t1.alloc((size_t)n * 8));
-		if (m.csr)
-			NRM_TRY(nrm_lcpm_csr_colsum(m.indptr.as<int64_t>(), m.indices.as<int32_t>(), m.x.p, m.dtype, rows, n, m.nnz, d_exp.as<double>(), len, unit, d_total, part.as<int64_t>(),
-										d_t1.as<double>(), st));
-		else
-			NRM_TRY(nrm_lcpm_colsum(m.x.p, m.dtype, rows, n, n, d_exp.as<double>(), len, part.as<double>(), d_t1.as<double>(), st));
+		NRM_TRY(lc.colsum(d_exp.as<double>(), len, unit, d_t1.as<double>(), st));
 	}
 	const size_t ob = (size_t)rows * n * nrm_esize(out_dtype);
 	NRM_TRY(out.alloc(ob));
-	if (m.csr)
-		NRM_TRY(nrm_lcpm_csr_write(m.indptr.as<int64_t>(), m.indices.as<int32_t>(), m.x.p, m.dtype, rows, n, m.nnz, d_tab.as<double>(), len, d_t1.as<double>(), out.p, out_dtype, n, st));
-	else
-		NRM_TRY(nrm_lcpm_write(m.x.p, m.dtype, rows, n, n, d_tab.as<double>(), len, d_t1.as<double>(), out.p, out_dtype, n, st));
+	NRM_TRY(lc.write(d_tab.as<double>(), len, d_t1.as<double>(), out.p, out_dtype, n, st));
 	return copy_out(h_out, out.p, ob);
 }
 
@@ -166,45 +165,25 @@ extern "C" int nrm_compute_var_host(const void* h_y, int y_dtype, int64_t rows, 
 	nrm_pinv_gram_unit_rows(c1.data(), nc + 1, n, 1e-8, m2i.data(), &rank2);
 	NRM_TRY(nrm_bind_device());
 	hipStream_t st = nullptr;
-	DevBuf y, c, dm2i, a, b, mean, sc, v, part, s, best, u, cw, mi, rank, ws, out, flags;
+	DevBuf y, c, dm2i, flags;
 	NRM_TRY(upload_matrix(h_y, y_dtype, rows, n, y, st));
 	NRM_TRY(upload_matrix(h_c, NRM_F64, nc, n, c, st));
 	NRM_TRY(dm2i.alloc(m2i.size() * 8));
 	NRM_HIP(hipMemcpy(dm2i.p, m2i.data(), m2i.size() * 8, hipMemcpyHostToDevice));
-	const int64_t tiles = (rows + nrm_fitvar_row_tile() - 1) / nrm_fitvar_row_tile(), nstate = 4 * (stepmax + 1);
-	NRM_TRY(nrm_take_all(nrm_take_plain, {{&a, rows * nc * 8}, {&b, rows * nc * 8}, {&mean, rows * 8}, {&sc, rows * 8}, {&v, n * 8}, {&part, tiles * n * 8}, {&s, n * 8},
-										  {&best, n * 8}, {&u, n * 8}, {&cw, nc * n * 8}, {&mi, nc * nc * 8}, {&rank, 8}, {&ws, nrm_fitvar_plan_workspace(n, nc) * 8},
-										  {&out, (nstate + n) * 8}}));
+	NrmFitvarStep fit;
+	fit.rows = rows, fit.n = n, fit.ldy = n, fit.nc = nc, fit.stepmax = stepmax, fit.eps = eps, fit.y_dtype = y_dtype;
+	fit.d_y = y.p, fit.d_c = c.as<double>(), fit.d_m2i = dm2i.as<double>();
+	NRM_TRY(fit.alloc(nrm_take_plain));
 	NRM_TRY(flags.alloc_zero(16, st));
-	// the state records (one per iteration and the first) and, right after the last, the weights: both are read in one copy
-	double *d_state = out.as<double>(), *d_w = d_state + nstate;
-	NRM_TRY(nrm_fitvar_plan_start(n, s.as<double>(), best.as<double>(), d_state, st));
-	for (int64_t i = 0; i < stepmax; i++) {
-		const double* now = d_state + 4 * i;
-		NRM_TRY(nrm_fitvar_design(c.as<double>(), nc, n, n, s.as<double>(), now, eps, u.as<double>(), cw.as<double>(), ws.as<double>(), st));
-		NRM_TRY(nrm_fitvar_pinv(n, nc, 1e-8, now, eps, ws.as<double>(), mi.as<double>(), rank.as<int64_t>(), st));
-		NRM_TRY(nrm_fitvar_moments(y.p, y_dtype, rows, n, n, cw.as<double>(), nc, n, a.as<double>(), st));
-		NRM_TRY(nrm_fitvar_genes(y.p, y_dtype, rows, n, n, u.as<double>(), c.as<double>(), nc, n, a.as<double>(), mi.as<double>(), b.as<double>(), mean.as<double>(), sc.as<double>(),
-								 flags.as<int32_t>(), st));
-		NRM_TRY(nrm_fitvar_cells(y.p, y_dtype, rows, n, n, u.as<double>(), c.as<double>(), nc, n, b.as<double>(), mean.as<double>(), sc.as<double>(), part.as<double>(), v.as<double>(),
-								 st));
-		NRM_TRY(nrm_fitvar_update(v.as<double>(), c.as<double>(), nc, n, n, dm2i.as<double>(), s.as<double>(), best.as<double>(), now, d_state + 4 * (i + 1), eps, ws.as<double>(), st));
-	}
-	NRM_TRY(nrm_fitvar_weights(best.as<double>(), n, ws.as<double>(), d_w, flags.as<int32_t>(), st));
+	fit.flags = flags.as<int32_t>();
+	NRM_TRY(fit.enqueue(st));
 	int32_t hf[4];
 	NRM_TRY(nrm_read_flags(flags.p, st, hf));
 	std::vector<double> ho;
-	NRM_TRY(download(ho, d_state + 4 * stepmax, (size_t)(4 + n)));
+	NRM_TRY(download(ho, fit.state() + 4 * stepmax, (size_t)(4 + n)));  // (the last state record and the weights behind it, in one copy)
 	h_state[0] = ho[0];  // best change (the reference's bestv)
 	h_state[1] = ho[1];  // steps taken
-	if (hf[0]) {
-		nrm_set_error("compute_var: %d genes with a constant residual, whose spread divides (norm.py:108,125)", hf[0]);
-		return NRM_E_NUMERIC;
-	}
-	if (hf[1]) {
-		nrm_set_error("compute_var: %d weights are not finite and positive (norm.py:125-127)", hf[1]);
-		return NRM_E_NUMERIC;
-	}
+	NRM_TRY(nrm_compute_var_status(hf));
 	memcpy(h_w, ho.data() + 4, (size_t)n * 8);
 	return NRM_OK;
 }

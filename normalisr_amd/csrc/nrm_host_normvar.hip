@@ -1,10 +1,13 @@
 // nrm_normvar_host (the expression side of norm.py:166-289) and nrm_binnet_host (binnet.py:134-173), numpy buffers in, numpy buffers out, no torch: the kernels
-// normalisr_amd/norm.py and binnet.py drive through the device-pointer entries, sequenced here in C++ with the library's own scratch pool.
+// normalisr_amd/norm.py and binnet.py drive through the device-pointer entries, with the library's own scratch pool.  normvar's buffers and its launches are the
+// step record NrmNormvarStep (nrm_normvar_step.h), which the resident plan of nrm_front_plan.hip runs too; the counters' words are in nrm_front_plan_args.h.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "nrm_front_plan_args.h"
 #include "nrm_host_entry.h"
+#include "nrm_normvar_step.h"
 
 // ---- binnet (binnet.py:134-173) ------------------------------------------------------------------------------------------------------------
 extern "C" int nrm_binnet_host(const void* h_p, int p_dtype, int64_t ng, double qcut, unsigned char* h_net, int64_t* total) {
@@ -33,8 +36,9 @@ extern "C" int nrm_binnet_host(const void* h_p, int p_dtype, int64_t ng, double 
 
 // ---- normvar (norm.py:166-289): the expression side, whole problem ------------------------------------------------------------------------------
 // h_y (rows, n) fp32 / fp64 -> h_out (rows, n): gene g multiplied by e_gk = w_k^wt_g, the covariates C e_g removed, the variance put back (keepvar).  The
-// three kernels of csrc/nrm_normvar.hip as normalisr_amd.norm.normvar launches them: per-gene moments in one pass, a lane per gene solving its small OLS with the
-// reference's rank rule, one pass writing the result.  1 .. nrm_normvar_device_covariates() covariates; up to 32 through the Gram-launch form below
+// kernels of csrc/nrm_normvar.hip through NrmNormvarStep: solve (per-gene moments in one pass, a lane per gene solving its small OLS with the reference's rank
+// rule), then finish (the marked genes' rescale, one pass writing the result).  1 .. nrm_normvar_device_covariates() covariates; up to 32 through the Gram-launch
+// form below, which fills the record's b and scale from the host and calls finish
 // (NRM_E_UNSUPPORTED beyond: the package's form with numpy's stacked SVD);
 // *zero_rank = genes whose covariates have rank 0 (norm.py:158-159 raises for them: the caller does); non-finite results: NRM_E_NUMERIC (norm.py:286).
 // The covariates' own scaling (norm.py:261-273) is a few numpy lines on (nc, n) and stays with the caller.
@@ -49,11 +53,14 @@ extern "C" int nrm_normvar_host(const void* h_y, int y_dtype, int64_t rows, int6
 		return NRM_E_UNSUPPORTED;
 	}
 	hipStream_t st = nullptr;
-	DevBuf y, lnw, wt, c, mom, b, scale, rank, flags, out;
+	DevBuf y, lnw, wt, c, flags, out;
 	NRM_TRY(upload_matrix(h_y, y_dtype, rows, n, y, st));
 	NRM_TRY(upload_matrix(h_lnw, NRM_F64, 1, n, lnw, st));
 	NRM_TRY(upload_matrix(h_wt, NRM_F64, 1, rows, wt, st));
 	NRM_TRY(upload_matrix(h_c, NRM_F64, nc, n, c, st));
+	NrmNormvarStep nv;
+	nv.rows = rows, nv.n = n, nv.ldy = n, nv.nc = nc, nv.ldo = n, nv.tol = tol, nv.keepvar = keepvar, nv.y_dtype = y_dtype, nv.out_dtype = out_dtype;
+	nv.d_y = y.p, nv.d_lnw = lnw.as<double>(), nv.d_wt = wt.as<double>(), nv.d_c = c.as<double>();
 	const bool wide = nc > nrm_normvar_device_covariates();
 	if (wide) {
 		// 9 .. 32 covariates (round 6; the entry answered NRM_E_UNSUPPORTED): the Gram-launch form of normalisr_amd/norm.py without torch -- U = e^2 and V = e^2 y
@@ -106,36 +113,29 @@ extern "C" int nrm_normvar_host(const void* h_y, int y_dtype, int64_t rows, int6
 		*zero_rank = zr;
 		if (zr) return NRM_OK;
 		nrm_normvar_coefficients(mi.data(), hga.data(), cp, hs1.data(), hs2.data(), h_wt, rows, nc, n, keepvar, hb, hscale);
-		NRM_TRY(b.alloc((size_t)rows * nc * 8));
-		NRM_TRY(scale.alloc((size_t)rows * 8));
-		NRM_HIP(hipMemcpy(b.p, hb.data(), hb.size() * 8, hipMemcpyHostToDevice));
-		NRM_HIP(hipMemcpy(scale.p, hscale.data(), hscale.size() * 8, hipMemcpyHostToDevice));
+		NRM_TRY(nv.alloc_coefficients(nrm_take_plain));
+		NRM_HIP(hipMemcpy(nv.b.p, hb.data(), hb.size() * 8, hipMemcpyHostToDevice));
+		NRM_HIP(hipMemcpy(nv.scale.p, hscale.data(), hscale.size() * 8, hipMemcpyHostToDevice));
 		NRM_TRY(flags.alloc_zero(16, st));
+		nv.flags = flags.as<int32_t>();
 	} else {
-		NRM_TRY(mom.alloc((size_t)rows * (size_t)(nc * (nc + 1) / 2 + nc + 2) * 8));
-		NRM_TRY(b.alloc((size_t)rows * nc * 8));
-		NRM_TRY(scale.alloc((size_t)rows * 8));
-		NRM_TRY(rank.alloc((size_t)rows * 8));
+		NRM_TRY(nv.alloc(nrm_take_plain));
 		NRM_TRY(flags.alloc_zero(16, st));
-		NRM_TRY(nrm_normvar_solve(y.p, y_dtype, rows, n, n, lnw.as<double>(), wt.as<double>(), c.as<double>(), nc, n, tol, keepvar ? 1 : 0, mom.as<double>(), b.as<double>(),
-								  scale.as<double>(), rank.as<int64_t>(), flags.as<int32_t>(), st));
+		nv.flags = flags.as<int32_t>();
+		NRM_TRY(nv.solve(st));
 	}
-	// genes whose one-pass variance sums have cancelled (csrc/nrm_nv_scale.h: marked by either route): their scale from the row itself
-	NRM_TRY(nrm_normvar_rescale(y.p, y_dtype, rows, n, n, lnw.as<double>(), wt.as<double>(), c.as<double>(), nc, n, b.as<double>(), scale.as<double>(), st));
-	// one pass writes the result, from b_g and the scale of either route
+	// the rescale of the genes either route has marked, then the one pass that writes the result from b_g and the scale: NrmNormvarStep::finish
 	const size_t ob = (size_t)rows * n * nrm_esize(out_dtype);
 	NRM_TRY(out.alloc(ob));
-	NRM_TRY(nrm_normvar_apply(y.p, y_dtype, rows, n, n, lnw.as<double>(), wt.as<double>(), c.as<double>(), nc, n, b.as<double>(), scale.as<double>(), out.p, out_dtype, n,
-							  flags.as<int32_t>(), st));
+	nv.d_out = out.p;
+	NRM_TRY(nv.finish(st));
 	int32_t hf[4];
 	NRM_TRY(nrm_read_flags(flags.p, st, hf));
 	if (!wide) {
 		*zero_rank = hf[0];
 		if (hf[0]) return NRM_OK;
 	}
-	if (hf[1]) {
-		nrm_set_error("normvar: non-finite results (norm.py:286)");
-		return NRM_E_NUMERIC;
-	}
+	const int32_t results[2] = {0, hf[1]};  // (rank 0 is the caller's to raise, from *zero_rank)
+	NRM_TRY(nrm_normvar_status(results));
 	return copy_out(h_out, out.p, ob);
 }

@@ -625,6 +625,7 @@ class NormvarPlan:
 				self._flags = eng.zeros((4, ), torch.int32)
 
 	def _launch(self):
+		# (the C library's twin on its own buffers: NrmNormvarStep, csrc/nrm_normvar_step.h)
 		eng, y, out = self.eng, self.dt, self.out
 		nt, ns = y.shape
 		nc = self.dc.shape[0]
@@ -720,6 +721,7 @@ class ComputeVarPlan:
 			self._flags = eng.zeros((4, ), torch.int32)
 
 	def _launch(self):
+		# (the C library's twin on its own buffers: NrmFitvarStep::enqueue, csrc/nrm_fitvar_step.h)
 		eng, y, lib = self.eng, self.dt, self.eng.lib
 		nt, ns = y.shape
 		nc = self.dc.shape[0]

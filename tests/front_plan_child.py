@@ -182,5 +182,18 @@ def scenario_two(job, arr, out, lib, _lib, cplan):
 	return notes
 
 
+def scenario_stepmax_pair(job, arr, out, lib, _lib, cplan):
+	"""Two plans of different stepmax alive at once on the same counts, stepped alternately: eager, captured, replayed."""
+	notes = {}
+	with cplan.FrontPlan(arr['x'], arr['cov'], stepmax=1) as p1, cplan.FrontPlan(arr['x'], arr['cov'], stepmax=3) as p3:
+		for _ in range(3):
+			p1.step()
+			p3.step()
+		_store(out, 's1', p1)
+		_store(out, 's3', p3)
+		notes['s1'], notes['s3'] = p1.info(), p3.info()
+	return notes
+
+
 if __name__ == '__main__':
 	h.child_main(sys.argv, globals())

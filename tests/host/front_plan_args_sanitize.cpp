@@ -1,7 +1,8 @@
 // The argument checks of the resident front-half plan (csrc/nrm_front_plan_args.h: free of HIP headers) under g++ -fsanitize=address,undefined;
 // tests/test_front_plan_cpu.py builds and runs it.  Every operand is a heap buffer of the exact size, so a check that read a cell too many would be caught: null
 // pointers, dtypes, shapes and pitches, the covariate bound, a user row that is not finite, a constant user row, eps, stepmax, tol, ntot, count_cap; normcov's row
-// classification; and the reading of the plan's sixteen counters in the reference's order.
+// classification; and the reading of the plan's sixteen counters in the reference's order: every combination of the ten it reads, and of the two that compute_var
+// and normvar each have (nrm_compute_var_status, nrm_normvar_status: what the whole-problem entries say too).  The messages are written out here in full.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -180,6 +181,58 @@ int main() {
 			CHECK(nrm_front_plan_status(f, 256, 300) == order[i].rc && strstr(g_err, order[i].words));
 			for (int j = i + 1; j < 10; j++) f[order[j].slot] = 1;
 			CHECK(nrm_front_plan_status(f, 256, 300) == order[i].rc && strstr(g_err, order[i].words));
+		}
+	}
+	{  // all 2^10 on/off combinations of the ten counters nrm_front_plan_status reads: the code and the whole message are those of the first one set, in the order
+	   // lcpm, cap, normcov, compute_var, scaling_factor, normvar; a counter that is set holds slot + 2, so that a message with a count shows whose it printed
+		struct Full {
+			int slot, rc;
+			const char* text;
+		};
+		const Full order[10] = {{0, NRM_E_ARG, "Negative value in d detected."},
+								{2, NRM_E_NUMERIC, "lcpm: the matrix holds no read (t0 = sum + 2 > 2, lcpm.py:95)"},
+								{1, NRM_E_ARG, "Found cell with no read at all. Please remove."},
+								{3, NRM_E_UNSUPPORTED, "nrm_front_plan: the plan tabulates psi(1 + count) for counts below count_cap = 256; the largest count here is 300."},
+								{4, NRM_E_ARG, CONSTANT},
+								{8, NRM_E_NUMERIC, "compute_var: 10 genes with a constant residual, whose spread divides (norm.py:108,125)"},
+								{9, NRM_E_NUMERIC, "compute_var: 11 weights are not finite and positive (norm.py:125-127)"},
+								{6, NRM_E_NUMERIC, "scaling_factor: no gene has a zero entry, or a value is not finite (lcpm.py:278-282)"},
+								{12, NRM_E_DEVICE, "Zero-rank covariates found."},
+								{13, NRM_E_NUMERIC, "normvar: non-finite results (norm.py:286)"}};
+		for (int mask = 0; mask < 1024; mask++) {
+			int32_t f[16];
+			memset(f, 0, sizeof(f));
+			f[5] = mask & 1 ? 3 : 0, f[7] = 5, f[10] = f[11] = f[14] = f[15] = 7;  // a warning and the words nobody reads: never a refusal
+			int first = -1;
+			for (int i = 9; i >= 0; i--)
+				if (mask >> i & 1) f[order[i].slot] = order[i].slot + 2, first = i;
+			strcpy(g_err, "untouched");
+			const int rc = nrm_front_plan_status(f, 256, 300);
+			if (first < 0)
+				CHECK(rc == NRM_OK && !strcmp(g_err, "untouched"));
+			else
+				CHECK(rc == order[first].rc && !strcmp(g_err, order[first].text));
+		}
+	}
+	{  // the stages' own readings, which the whole-problem entries share with the plan: every on/off combination of compute_var's two counters and of normvar's two
+		for (int mask = 0; mask < 4; mask++) {
+			const int32_t f[2] = {mask & 1 ? 4 : 0, mask & 2 ? 9 : 0};
+			strcpy(g_err, "untouched");
+			const int cv = nrm_compute_var_status(f);
+			if (mask & 1)
+				CHECK(cv == NRM_E_NUMERIC && !strcmp(g_err, "compute_var: 4 genes with a constant residual, whose spread divides (norm.py:108,125)"));
+			else if (mask & 2)
+				CHECK(cv == NRM_E_NUMERIC && !strcmp(g_err, "compute_var: 9 weights are not finite and positive (norm.py:125-127)"));
+			else
+				CHECK(cv == NRM_OK && !strcmp(g_err, "untouched"));
+			strcpy(g_err, "untouched");
+			const int nv = nrm_normvar_status(f);
+			if (mask & 1)
+				CHECK(nv == NRM_E_DEVICE && !strcmp(g_err, "Zero-rank covariates found."));
+			else if (mask & 2)
+				CHECK(nv == NRM_E_NUMERIC && !strcmp(g_err, "normvar: non-finite results (norm.py:286)"));
+			else
+				CHECK(nv == NRM_OK && !strcmp(g_err, "untouched"));
 		}
 	}
 	printf("front plan args ok\n");

@@ -230,6 +230,23 @@ def test_front_plan_errors_through_check(tmp_path):
 		same_bits(stages(out, name + '.after'), fresh, name)
 
 
+def test_front_plan_two_stepmax_side_by_side(tmp_path):
+	"""Two plans with stepmax 1 and 3 alive at once on the same 70 x 131 counts (three row tiles, the last ragged): each keeps a compute_var state block of its own
+	length (csrc/nrm_fitvar_step.h: 4 (stepmax + 1) + n doubles).  What does not depend on stepmax -- lcpm, the covariates, the scaling factors -- is the same to the
+	bit, each plan's iteration count lies within its own stepmax, and both finish with finite results."""
+	x, cov = child.counts(80, 70, 131), child.onehot(81, 2, 131)
+	out, info = run_child(tmp_path, 'stepmax_pair', dict(x=x, cov=cov), {})
+	print(info)
+	s1, s3 = stages(out, 's1'), stages(out, 's3')
+	for k in ('lcpm', 'cov', 'wt'):
+		assert s1[k].dtype == s3[k].dtype and np.array_equal(s1[k], s3[k]), k
+	assert 1 <= info['s1']['cv_steps'] <= 1 and 1 <= info['s3']['cv_steps'] <= 3
+	for s, i in ((s1, info['s1']), (s3, info['s3'])):
+		assert i['captured'] == 1 and i['steps'] == 3 and i['covariates'] == 6
+		assert s['w'].shape == (131, ) and np.isfinite(s['w']).all() and s['w'].min() > 0 and np.isfinite(s['dtn']).all() and np.isfinite(s['dcn']).all()
+	assert info['s3']['bytes'] - info['s1']['bytes'] == 4 * 2 * 8  # the two state records more, and nothing else
+
+
 def test_front_plan_two_plans_and_teardown(tmp_path):
 	a, b, cov = child.counts(70, 37, 203), child.counts(71, 40, 300), child.onehot(72, 2, 203)
 	out, n = run_child(tmp_path, 'two', dict(a=a, b=b, cov=cov), {})
