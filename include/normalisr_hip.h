@@ -1202,7 +1202,17 @@ int nrm_single4_plan_destroy(nrm_single4_plan* plan);
  *       reference's words where it has any ("reads must not be empty.", "eps and stepmax must be positive.", a user row that is not finite, a constant user row:
  *       "Detected constant covariate. ..." norm.py:34-37); n_cov + 3 + 1 > nrm_normvar_device_covariates(): NRM_E_UNSUPPORTED, the text names the bound.
  *       Every buffer of a step is taken from the scratch pool here and given back by nrm_front_plan_destroy.
- *   nrm_front_plan_upload: new counts (same shape and dtype) into the plan's own copy; NRM_E_ARG for an adopted matrix.
+ *   nrm_front_plan_create_csr: the same plan on SPARSE counts, canonical CSR over the genes as nrm_lcpm_csr_count takes it -- indptr (genes + 1) int64, indices
+ *       int32 strictly increasing inside a row, data of one of the four count dtypes, stored zeros legal -- in arrays that hold nnz_cap >= max(nnz, 1) elements; no
+ *       (genes, n_cells) matrix of counts is ever formed.  on_device == 0: HOST arrays of nnz stored entries; the plan owns three device buffers of capacity nnz_cap
+ *       that nrm_front_plan_upload_csr rewrites.  on_device != 0: DEVICE arrays, adopted and rewritten in place by their owner, the pattern included; nnz is then
+ *       only checked against nnz_cap, and every step reads the number of stored entries from indptr[genes].  The other arguments are nrm_front_plan_create's.  Checked
+ *       before any device call as well: 0 <= nnz <= nnz_cap, nnz_cap >= 1, the arrays' alignment, and for host arrays 0 = indptr[0] <= ... <= indptr[genes] = nnz
+ *       (NRM_E_ARG in the words of nrm_lcpm_csr_host's malformed matrix).  What needs every entry -- columns inside [0, n_cells) and strictly increasing -- is the
+ *       count kernel's, at every step, and is reported by check.  No step reads outside the genes + 1 offsets and the nnz_cap entries, whatever the arrays hold.
+ *   nrm_front_plan_upload: new counts (same shape and dtype) into the plan's own copy; NRM_E_ARG for an adopted matrix or a plan on CSR counts.
+ *   nrm_front_plan_upload_csr: new CSR counts (same shape and dtype, any pattern, nnz <= nnz_cap, the offsets checked as in create_csr) into the plan's own arrays;
+ *       NRM_E_ARG, before any copy, for an adopted matrix, for nnz > nnz_cap, and for a plan on a dense matrix.  The graph of the step stays as it is.
  *   nrm_front_plan_step: nrm_lcpm_count; t0 = sum + 2, len = max + 1 and lcpm's refusals counted (one workgroup); tab[x] = psi(1 + x) - psi(t0) and exp(tab[x]) for
  *       x < len, each entry on its own (csrc/nrm_digamma.h); nrm_lcpm_colsum and nrm_lcpm_write with table_len = count_cap (lcpm.py:107,158); lcpm's rows ln total,
  *       genes - nnz, ln^2 total (lcpm.py:194-200) and normcov on [user rows; those three] with the ones row appended, a workgroup per row, two-pass mean and spread
@@ -1210,7 +1220,11 @@ int nrm_single4_plan_destroy(nrm_single4_plan* plan);
  *       (lcpm.py:258,268-283); dcn = the continuous rows and the ones row times w (norm.py:261-273); nrm_normvar_solve / rescale / apply.  stream == NULL: the
  *       plan's own.  Eager the first time, captured (thread-local) the second, one hipGraphLaunch afterwards; a failed capture leaves the plan eager with the reason
  *       in nrm_last_error (NRM_OK).  NRM_DEBUG="graph=0": always eager.  No floating-point atomics: the same input gives the same bits, eager or replayed.
+ *       On CSR counts the three lcpm passes are nrm_lcpm_csr_count / colsum / write in the form that reads its data-dependent scalars on the device: the stored
+ *       entries from indptr[genes], clamped to nnz_cap, and the fixed-point unit max (E[x] - E[0]) / x from a word a kernel fills from the table just written
+ *       (an integer maximum on the bit patterns); from the covariate rows on, the step is the dense one.
  *   nrm_front_plan_check: synchronises the device, reads all counters once, clears them and answers in the order the reference would meet the conditions: a
+ *       malformed CSR matrix (a word of its own beside the sixteen counters: NRM_E_ARG in the words of nrm_lcpm_csr_host, in front of everything else); a
  *       negative entry (lcpm.py:86, NRM_E_ARG); no read at all (the assertion t0 > 2, lcpm.py:97: NRM_E_NUMERIC); a cell without a read (lcpm.py:196, NRM_E_ARG);
  *       a count at or beyond count_cap (NRM_E_UNSUPPORTED, naming the cap and the count); a constant covariate row (norm.py:34-37, NRM_E_ARG); compute_var's two
  *       assertions (norm.py:108,125-127: NRM_E_NUMERIC); scaling_factor's (lcpm.py:278-282: NRM_E_NUMERIC); normvar's zero rank (norm.py:160: NRM_E_DEVICE) and
@@ -1228,7 +1242,11 @@ int nrm_single4_plan_destroy(nrm_single4_plan* plan);
 typedef struct nrm_front_plan nrm_front_plan;
 int nrm_front_plan_create(nrm_front_plan** plan, const void* reads, int dtype, int64_t genes, int64_t n_cells, int64_t ld, int reads_on_device, const double* h_cov,
 						  int64_t n_cov, int64_t ntot, int64_t stepmax, double eps, double tol, int out_dtype, int64_t count_cap);
+int nrm_front_plan_create_csr(nrm_front_plan** plan, const int64_t* indptr, const int32_t* indices, const void* data, int dtype, int64_t genes, int64_t n_cells, int64_t nnz,
+							  int64_t nnz_cap, int on_device, const double* h_cov, int64_t n_cov, int64_t ntot, int64_t stepmax, double eps, double tol, int out_dtype,
+							  int64_t count_cap);
 int nrm_front_plan_upload(nrm_front_plan* plan, const void* h_reads);
+int nrm_front_plan_upload_csr(nrm_front_plan* plan, const int64_t* h_indptr, const int32_t* h_indices, const void* h_data, int64_t nnz);
 int nrm_front_plan_step(nrm_front_plan* plan, void* stream);
 int nrm_front_plan_check(nrm_front_plan* plan, int64_t* near_constant);
 int nrm_front_plan_results(nrm_front_plan* plan, void* h_dtn, double* h_dcn, double* h_w, double* h_wt, void* h_lcpm, double* h_cov);

@@ -232,7 +232,9 @@ _SIGNATURES = {
 	'nrm_single4_plan_time': ([_vp, _i64, ctypes.POINTER(_dbl)], _i32),
 	'nrm_single4_plan_destroy': ([_vp], _i32),
 	'nrm_front_plan_create': ([ctypes.POINTER(_vp), _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _dbl, _dbl, _i32, _i64], _i32),
+	'nrm_front_plan_create_csr': ([ctypes.POINTER(_vp), _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _dbl, _dbl, _i32, _i64], _i32),
 	'nrm_front_plan_upload': ([_vp, _vp], _i32),
+	'nrm_front_plan_upload_csr': ([_vp, _vp, _vp, _vp, _i64], _i32),
 	'nrm_front_plan_step': ([_vp, _vp], _i32),
 	'nrm_front_plan_check': ([_vp, ctypes.POINTER(_i64)], _i32),
 	'nrm_front_plan_results': ([_vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),

@@ -11,7 +11,8 @@ assertions and, on request, alpha and Benjamini-Hochberg q-values on the device;
 for single=1, a low-MOI screen: the row filter runs in front of the cell selection, the variances are per grouping.  Single4Plan (nrm_single4_plan_*) is the same
 for single=4, a high-MOI screen in closed form: what depends on the design alone is computed when the design is set, not in a step.
 FrontPlan (nrm_front_plan_*) is the front half in front of them: read counts in, normvar's (dtn, dcn) out -- lcpm, normcov, compute_var, scaling_factor and normvar
-with the reference's defaults as one graph --, whose output matrix a CoexPlan or DePlan of the same process adopts.
+with the reference's defaults as one graph --, whose output matrix a CoexPlan or DePlan of the same process adopts.  FrontPlanCSR (nrm_front_plan_create_csr)
+is the same plan on sparse counts: canonical CSR in HBM, never densified.
 """
 import ctypes
 
@@ -100,6 +101,7 @@ class _Plan:
 	"""What the plans share: the handle and its entries.  A class names its entries' prefix and the fields of its info()."""
 	_prefix = None
 	_info_fields = None
+	_create = 'create'  # the entry that makes the handle
 
 	def __init__(self):
 		self._h = self._keep = None
@@ -115,7 +117,7 @@ class _Plan:
 		if device is not None:
 			_lib.check(self._lib.nrm_set_device(int(device)))
 		h = _vp()
-		_lib.check(getattr(self._lib, self._prefix + 'create')(ctypes.byref(h), *args))
+		_lib.check(getattr(self._lib, self._prefix + self._create)(ctypes.byref(h), *args))
 		self._h = h
 		self._keep = keep if self.adopted else None  # (an adopted matrix lives as long as the plan reads it)
 
@@ -227,15 +229,16 @@ DE_INFO_FIELDS = ('route', 'captured', 'steps', 'reruns', 'rank', 'dof', 'bytes'
 
 
 class DeviceCSR:
-	"""A canonical CSR design (n_grouping, n_cell) in device-visible memory by its three addresses: indptr (n_grouping + 1) int64, indices (nnz) int32 -- the cell of
-	every stored entry, strictly increasing inside a row --, data (nnz) of `dtype` (float32 / float64) or None for all ones.  What a caller without an array library
-	hands to DePlan; the library checks the structure (ValueError for a malformed matrix)."""
+	"""A canonical CSR matrix in device-visible memory by its three addresses: indptr (rows + 1) int64, indices (nnz) int32 -- the cell of every stored entry,
+	strictly increasing inside a row --, data (nnz) of `dtype`.  A design (n_grouping, n_cell) for DePlan: float32 / float64, or None for all ones.  Read counts
+	(n_gene, n_cell) for FrontPlanCSR: int64 / int32 / int16 / uint8; nnz then only has to lie within the plan's nnz_cap, every step reads indptr[rows].  What a
+	caller without an array library hands over; the library checks the structure (ValueError for a malformed matrix)."""
 
 	def __init__(self, indptr, indices, data, shape, nnz, dtype=np.float64):
 		self.indptr, self.indices, self.data = int(indptr), int(indices) if indices else None, int(data) if data else None
 		self.shape, self.nnz, self.dtype = (int(shape[0]), int(shape[1])), int(nnz), np.dtype(dtype)
-		if self.dtype not in (np.float32, np.float64):
-			raise ValueError('DeviceCSR: data must be float32 or float64')
+		if self.dtype not in (np.float32, np.float64) and str(self.dtype) not in ('int64', 'int32', 'int16', 'uint8'):
+			raise ValueError('DeviceCSR: data must be float32 or float64 (a design), or int64, int32, int16 or uint8 (read counts)')
 		if self.nnz < 0 or (self.nnz > 0 and self.indices is None):
 			raise ValueError('DeviceCSR: indices are missing')
 
@@ -271,6 +274,8 @@ def _design(dg):
 	"""The arguments nrm_de_plan_create / nrm_de_plan_design take for a design, its shape, and what must stay alive while the library reads it."""
 	from . import de_sparse
 	if isinstance(dg, DeviceCSR):
+		if dg.dtype not in (np.float32, np.float64):
+			raise ValueError('DeviceCSR: the data of a design must be float32 or float64')
 		return (1, dg.data, _code(dg.dtype), 0, dg.indptr, dg.indices, dg.nnz, 1), dg.shape, dg
 	csr = de_sparse.as_design_csr(dg)
 	if csr is not None:
@@ -500,50 +505,12 @@ FRONT_INFO_FIELDS = ('captured', 'steps', 'cv_steps', 'max_count', 'count_cap', 
 _COUNT_CODES = {'int64': _lib.NRM_I64, 'int32': _lib.NRM_I32, 'int16': _lib.NRM_I16, 'uint8': _lib.NRM_U8}
 
 
-class FrontPlan(_Plan):
-	"""Read counts to normalised expression resident on the GPU (include/normalisr_hip.h: nrm_front_plan_*): lcpm -> normcov -> compute_var -> scaling_factor ->
-	normvar with the reference's default options as one HIP graph, nothing decided on the host in between:
-
-		with cplan.FrontPlan(reads, cov=batches, stepmax=1) as front:
-			front.step()
-			dtn, dcn = front.results()                      # == normvar(lcpm(reads)[0], normcov(vstack([batches, lcpm(reads)[3]])), w, scaling_factor(reads))
-			coex = cplan.CoexPlan(front.device_results()['dtn'], dcn)   # adopts the matrix where it lies
-			front.update(reads2); front.step()              # same shape and dtype, new counts: one graph launch
-
-	reads (n_gene, n_cell): a numpy integer array (int64 / int32 / int16 / uint8 as they are, other integer types as int64; the plan keeps its own device copy and
-	`update` re-uploads) or a device matrix of one of those four dtypes -- anything with data_ptr() or __cuda_array_interface__, such as a DeviceMatrix -- which is
-	adopted and rewritten in place by its owner.  cov (n_cov, n_cell): the raw covariate rows stacked in front of lcpm's three before normcov (None: none); with
-	lcpm's three and the constant row there may be nrm_normvar_device_covariates() in all (NotImplementedError beyond).  stepmax, eps: compute_var's; ntot: lcpm's;
-	tol: normvar's; out_dtype: float64 (the reference's) or float32 for lcpm and dtn.  count_cap: the tables hold counts below it; None for host input: the next
-	power of two above the matrix's maximum, 256 at the least; an adopted matrix must name one.  A step whose largest count reaches the cap is refused by check().
-	Not covered: sparse counts, the non-default options of lcpm / normcov / scaling_factor / normvar, qc_outlier and subset between fitvar and normvar (weights()
-	is there for a caller who wants them).
-	info(): captured, steps, cv_steps (iterations compute_var took in the last step checked), max_count (of that step), count_cap, covariates, bytes, near_constant."""
+class _FrontPlan(_Plan):
+	"""What FrontPlan and FrontPlanCSR share: the checks of the options, check() and everything that reads a step's results."""
 	_prefix, _info_fields = 'nrm_front_plan_', FRONT_INFO_FIELDS
 
-	def __init__(self, reads, cov=None, stepmax=1, eps=1e-6, ntot=None, tol=1e-8, out_dtype=np.float64, count_cap=None, device=None):
-		super().__init__()
-		if hasattr(reads, 'tocsr'):
-			raise TypeError('FrontPlan: a sparse reads is not taken here (lcpm takes one).')
-		dev = _adopt(reads)
-		if dev is None:
-			reads = np.asarray(reads)
-			if reads.ndim != 2:
-				raise ValueError('reads must have 2 dimensions.')
-			if reads.dtype.kind not in 'iub':
-				raise TypeError('reads must be an integer matrix.')
-			if str(reads.dtype) not in _COUNT_CODES:
-				reads = reads.astype(np.int64)
-			reads = np.ascontiguousarray(reads)
-			ptr, shape, dtype, ld, self.adopted = reads.ctypes.data, reads.shape, reads.dtype, reads.shape[1], False
-		else:
-			ptr, shape, dtype, ld = dev
-			self.adopted = True
-			if str(dtype) not in _COUNT_CODES:
-				raise ValueError('FrontPlan: a device matrix must be int64, int32, int16 or uint8')
-			if count_cap is None:
-				raise ValueError('FrontPlan: count_cap must be given for a device matrix (its maximum is not looked at here)')
-		self.shape, self.dtype = (int(shape[0]), int(shape[1])), np.dtype(dtype)
+	def _options(self, cov, stepmax, eps, ntot, out_dtype):
+		"""The options both constructors take, checked; self.shape is set.  -> cov as a contiguous float64 matrix (n_cov, n_cell)."""
 		self.out_dtype = np.dtype(out_dtype)
 		if self.out_dtype not in (np.float32, np.float64):
 			raise ValueError('out_dtype must be float32 or float64')
@@ -563,16 +530,22 @@ class FrontPlan(_Plan):
 		self.covariates = self.n_cov + 4  # lcpm's three rows and the constant row
 		if ntot is not None and (int(ntot) != ntot or ntot <= 0):
 			raise ValueError('ntot must be a positive integer.')
+		return cov
+
+	def _set_count_cap(self, count_cap, values):
+		"""count_cap as given, or (None, host input) the next power of two above the largest of `values`, 256 at the least."""
 		if count_cap is None:
-			top = int(reads.max()) if reads.size else 0
+			top = int(values.max()) if values.size else 0
 			if top >= int(self._lib.nrm_lcpm_table_cap()):
-				raise NotImplementedError('FrontPlan tabulates psi(1 + count) for counts below {}; the largest count here is {}.'.format(int(self._lib.nrm_lcpm_table_cap()), top))
+				raise NotImplementedError('{} tabulates psi(1 + count) for counts below {}; the largest count here is {}.'.format(type(self).__name__, int(self._lib.nrm_lcpm_table_cap()), top))
 			count_cap = max(256, 1 << max(top, 0).bit_length())
 		if int(count_cap) != count_cap:
 			raise ValueError('count_cap must be an integer.')
 		self.count_cap = int(count_cap)
-		self._open(device, reads, ptr, _COUNT_CODES[str(self.dtype)], self.shape[0], self.shape[1], ld, 1 if self.adopted else 0, cov.ctypes.data if self.n_cov else None, self.n_cov,
-				   -1 if ntot is None else int(ntot), int(stepmax), float(eps), float(tol), _code(self.out_dtype), self.count_cap)
+
+	def _tail(self, cov, ntot, stepmax, eps, tol):
+		"""The arguments both create entries end in."""
+		return (cov.ctypes.data if self.n_cov else None, self.n_cov, -1 if ntot is None else int(ntot), int(stepmax), float(eps), float(tol), _code(self.out_dtype), self.count_cap)
 
 	def check(self):
 		"""Waits for the queued steps and tests what they counted, in the order the reference would meet it: ValueError for a negative entry, AssertionError for a
@@ -622,6 +595,130 @@ class FrontPlan(_Plan):
 		self._call('device_results', ctypes.byref(dtn), ctypes.byref(dcn), ctypes.byref(lc), ctypes.byref(ld), ctypes.byref(st))
 		return dict(dtn=DeviceMatrix(dtn.value, self.shape, self.out_dtype, ld.value), lcpm=DeviceMatrix(lc.value, self.shape, self.out_dtype, ld.value), dcn=dcn.value,
 					ld=int(ld.value), dtype=self.out_dtype, stream=st.value)
+
+
+class FrontPlan(_FrontPlan):
+	"""Read counts to normalised expression resident on the GPU (include/normalisr_hip.h: nrm_front_plan_*): lcpm -> normcov -> compute_var -> scaling_factor ->
+	normvar with the reference's default options as one HIP graph, nothing decided on the host in between:
+
+		with cplan.FrontPlan(reads, cov=batches, stepmax=1) as front:
+			front.step()
+			dtn, dcn = front.results()                      # == normvar(lcpm(reads)[0], normcov(vstack([batches, lcpm(reads)[3]])), w, scaling_factor(reads))
+			coex = cplan.CoexPlan(front.device_results()['dtn'], dcn)   # adopts the matrix where it lies
+			front.update(reads2); front.step()              # same shape and dtype, new counts: one graph launch
+
+	reads (n_gene, n_cell): a numpy integer array (int64 / int32 / int16 / uint8 as they are, other integer types as int64; the plan keeps its own device copy and
+	`update` re-uploads) or a device matrix of one of those four dtypes -- anything with data_ptr() or __cuda_array_interface__, such as a DeviceMatrix -- which is
+	adopted and rewritten in place by its owner.  cov (n_cov, n_cell): the raw covariate rows stacked in front of lcpm's three before normcov (None: none); with
+	lcpm's three and the constant row there may be nrm_normvar_device_covariates() in all (NotImplementedError beyond).  stepmax, eps: compute_var's; ntot: lcpm's;
+	tol: normvar's; out_dtype: float64 (the reference's) or float32 for lcpm and dtn.  count_cap: the tables hold counts below it; None for host input: the next
+	power of two above the matrix's maximum, 256 at the least; an adopted matrix must name one.  A step whose largest count reaches the cap is refused by check().
+	Not covered: the non-default options of lcpm / normcov / scaling_factor / normvar, qc_outlier and subset between fitvar and normvar (weights() is there for a
+	caller who wants them).  Sparse counts are FrontPlanCSR's.
+	info(): captured, steps, cv_steps (iterations compute_var took in the last step checked), max_count (of that step), count_cap, covariates, bytes, near_constant."""
+
+	def __init__(self, reads, cov=None, stepmax=1, eps=1e-6, ntot=None, tol=1e-8, out_dtype=np.float64, count_cap=None, device=None):
+		super().__init__()
+		if hasattr(reads, 'tocsr') or isinstance(reads, DeviceCSR):
+			raise TypeError('FrontPlan: a sparse reads is not taken here (FrontPlanCSR takes one).')
+		dev = _adopt(reads)
+		if dev is None:
+			reads = np.asarray(reads)
+			if reads.ndim != 2:
+				raise ValueError('reads must have 2 dimensions.')
+			if reads.dtype.kind not in 'iub':
+				raise TypeError('reads must be an integer matrix.')
+			if str(reads.dtype) not in _COUNT_CODES:
+				reads = reads.astype(np.int64)
+			reads = np.ascontiguousarray(reads)
+			ptr, shape, dtype, ld, self.adopted = reads.ctypes.data, reads.shape, reads.dtype, reads.shape[1], False
+		else:
+			ptr, shape, dtype, ld = dev
+			self.adopted = True
+			if str(dtype) not in _COUNT_CODES:
+				raise ValueError('FrontPlan: a device matrix must be int64, int32, int16 or uint8')
+			if count_cap is None:
+				raise ValueError('FrontPlan: count_cap must be given for a device matrix (its maximum is not looked at here)')
+		self.shape, self.dtype = (int(shape[0]), int(shape[1])), np.dtype(dtype)
+		cov = self._options(cov, stepmax, eps, ntot, out_dtype)
+		self._set_count_cap(count_cap, reads)
+		self._open(device, reads, ptr, _COUNT_CODES[str(self.dtype)], self.shape[0], self.shape[1], ld, 1 if self.adopted else 0, *self._tail(cov, ntot, stepmax, eps, tol))
+
+
+class FrontPlanCSR(_FrontPlan):
+	"""FrontPlan on sparse read counts (nrm_front_plan_create_csr): canonical CSR over the genes resident in HBM, the same step as one HIP graph, and no
+	(n_gene, n_cell) matrix of counts anywhere -- the plan is CSR whatever the density.
+
+		with cplan.FrontPlanCSR(scipy.sparse.csr_matrix(reads), cov=batches, nnz_cap=2 * reads.nnz) as front:
+			front.step()
+			dtn, dcn = front.results()
+			front.update(reads2); front.step()              # same shape and dtype, any pattern with at most nnz_cap stored entries: one graph launch
+
+	reads (n_gene, n_cell): any scipy.sparse matrix of an integer dtype, canonicalised on the host (lcpm.canonical_csr: duplicates summed, columns sorted, zeros
+	dropped; int64 / int32 / int16 / uint8 data as they are, other integer types as int64), of which the plan keeps its own three device arrays of nnz_cap entries
+	(None: the matrix's own count) that `update` rewrites; or a cplan.DeviceCSR of one of those four dtypes, which is adopted: its owner rewrites the three arrays in
+	place, the pattern included, every step reads the number of stored entries from indptr[n_gene], and count_cap and nnz_cap (the elements indices and data hold)
+	must be named.  The other arguments, the methods and info() are FrontPlan's.  check() raises ValueError for a malformed matrix -- indptr not rising from 0 to at
+	most nnz_cap, a column outside [0, n_cell) or not above the one before it -- in front of FrontPlan's exceptions; no step reads outside the arrays for one."""
+	_create = 'create_csr'
+
+	def __init__(self, reads, cov=None, stepmax=1, eps=1e-6, ntot=None, tol=1e-8, out_dtype=np.float64, count_cap=None, nnz_cap=None, device=None):
+		super().__init__()
+		self.adopted = isinstance(reads, DeviceCSR)
+		if self.adopted:
+			if str(reads.dtype) not in _COUNT_CODES:
+				raise ValueError('FrontPlanCSR: a DeviceCSR of read counts must be int64, int32, int16 or uint8')
+			if count_cap is None or nnz_cap is None:
+				raise ValueError('FrontPlanCSR: count_cap and nnz_cap must be given for a DeviceCSR (its arrays are not looked at here)')
+			if reads.indices is None or reads.data is None:
+				raise ValueError('FrontPlanCSR: a DeviceCSR of read counts has indices and data')
+			self.shape, self.dtype = reads.shape, reads.dtype
+			ptrs, nnz, values = (reads.indptr, reads.indices, reads.data), reads.nnz, None
+		else:
+			arrays = self._host_csr(reads, None)
+			self.shape, self.dtype = (int(reads.shape[0]), int(reads.shape[1])), arrays[2].dtype
+			ptrs, nnz, values = tuple(a.ctypes.data for a in arrays), int(arrays[2].size), arrays[2]
+		cov = self._options(cov, stepmax, eps, ntot, out_dtype)
+		self._set_count_cap(count_cap, values)
+		if nnz_cap is None:
+			nnz_cap = max(nnz, 1)  # (a matrix without a stored entry still gets arrays: check() then says that it holds no read)
+		if int(nnz_cap) != nnz_cap:
+			raise ValueError('nnz_cap must be an integer.')
+		self.nnz_cap = int(nnz_cap)
+		if self.nnz_cap < max(nnz, 1):
+			raise ValueError('FrontPlanCSR: nnz_cap = {} is below the {} stored entries of reads (and 1 at the least)'.format(self.nnz_cap, nnz))
+		self._open(device, reads, ptrs[0], ptrs[1], ptrs[2], _COUNT_CODES[str(self.dtype)], self.shape[0], self.shape[1], nnz, self.nnz_cap, 1 if self.adopted else 0,
+				   *self._tail(cov, ntot, stepmax, eps, tol))
+
+	@staticmethod
+	def _host_csr(reads, dtype):
+		"""(indptr int64, indices int32, data) of a scipy.sparse count matrix, canonical and contiguous; data in the plan's dtype (None: the one FrontPlan would keep
+		the input in)."""
+		if not hasattr(reads, 'tocsr'):
+			raise TypeError('FrontPlanCSR: reads must be a scipy.sparse matrix or a cplan.DeviceCSR (FrontPlan takes a dense matrix).')
+		if len(reads.shape) != 2:
+			raise ValueError('reads must have 2 dimensions.')
+		if reads.dtype.kind not in 'iub':
+			raise TypeError('reads must be an integer matrix.')
+		want = reads.dtype if str(reads.dtype) in _COUNT_CODES else np.dtype(np.int64)
+		if dtype is not None and want != dtype:
+			raise ValueError('FrontPlanCSR.update: reads of dtype {}, the plan holds {}'.format(want, dtype))
+		from .lcpm import canonical_csr  # (imports without torch)
+		indptr, indices, data = canonical_csr(reads)
+		return np.ascontiguousarray(indptr), np.ascontiguousarray(indices), np.ascontiguousarray(data.astype(want))
+
+	def update(self, reads):
+		"""New counts of the same shape and dtype, of any pattern with at most nnz_cap stored entries, into the plan's own arrays (ValueError beyond nnz_cap, before
+		any device call, and for an adopted matrix: its owner rewrites it in place)."""
+		if self.adopted:
+			raise ValueError('FrontPlanCSR.update: the plan adopted a device matrix; its owner rewrites it in place')
+		indptr, indices, data = self._host_csr(reads, self.dtype)
+		if tuple(int(v) for v in reads.shape) != self.shape:
+			raise ValueError('Unmatching dx/dy/dc dimensions.')
+		if data.size > self.nnz_cap:
+			raise ValueError('FrontPlanCSR.update: {} stored entries, beyond the plan\'s nnz_cap = {}'.format(int(data.size), self.nnz_cap))
+		self._call('upload_csr', indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, int(data.size))
+		return self
 
 
 assert __name__ != "__main__"

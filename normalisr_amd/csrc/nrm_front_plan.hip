@@ -9,12 +9,15 @@
 // valid when the counts are rewritten:
 //   k_front_scalars  ONE workgroup: t0 = sum + 2 (or ntot + 2), len = max + 1 (clamped to the cap), the counters of lcpm's refusals
 //   k_front_tables   tab[x] = psi(1 + x) - psi(t0), etab[x] = exp(tab[x]) for x < len; a thread per entry of the cap, every entry on its own (nrm_digamma.h)
+//   k_front_unit     CSR counts only: the largest (etab[x] - etab[0]) / x of the table just written, the bound of the CSR column sum's fixed point
 //   k_front_cov      a workgroup per covariate row: lcpm's three rows from the integer totals, then normcov on [user rows; those three], the ones row appended
 //   k_front_m2i      ONE workgroup: ([dc;1][dc;1]^T)^+ on unit-length rows by the lane Jacobi of nrm_jacobi_lanes.h (nrm_pinv_gram_unit_rows of the host entries)
 //   k_front_scale    ln w, and wt = (zeros / cells) / max_g (zeros / cells): scaling_factor's default variable rescaled with v0 = 0, v1 = 'max'
 //   k_front_dcn      normvar's scaled covariates: continuous rows and the ones row times w (norm.py:261-273 with cat = 1)
 // Sums over cells are per-thread partial sums in a fixed stride, added by the shuffle tree and the waves in their order: no floating-point atomics, the same bits
 // every run, eager or replayed.  Counters are integers.
+// On CSR counts (nrm_front_plan_create_csr) the step is the same with the CSR form of lcpm's three passes: their two data-dependent scalars -- the number of stored
+// entries and the unit -- are read on the device (nrm_lcpm_step.h: d_unit), so the graph survives a rewrite of the matrix, its pattern included.
 #include <memory>
 #include "nrm_device.h"
 #include "nrm_digamma.h"
@@ -32,7 +35,8 @@
 
 static_assert(NRM_FRONT_M2_ROWS * NRM_FRONT_M2_ROWS * 8 * 3 < 32768, "k_front_m2i keeps three square matrices in LDS");
 
-// fs[0] = t0, fs[1] = len (as a double: below 2^24); big[0] = the largest count of a step whose maximum reached the cap
+// fs[0] = t0, fs[1] = len (as a double: below 2^24), fs[2] = 0: the unit, cleared for k_front_unit; big[0] = the largest count of a step whose maximum reached
+// the cap, big[1] = steps whose CSR matrix was malformed (the count pass's info[3]), big[2] = this step's largest count
 __global__ void __launch_bounds__(256) k_front_scalars(const int64_t* __restrict__ info, const int64_t* __restrict__ cell_total, int64_t n, int64_t ntot, int64_t cap,
 														double* __restrict__ fs, int32_t* __restrict__ flags, int64_t* __restrict__ big) {
 	__shared__ int sm[4];
@@ -49,7 +53,9 @@ __global__ void __launch_bounds__(256) k_front_scalars(const int64_t* __restrict
 	const bool over = mx >= cap;
 	fs[0] = t0;
 	fs[1] = (double)(over ? cap : mx + 1);
+	fs[2] = 0.0;
 	// (one thread of one workgroup on one stream: nobody else writes these words while a step runs)
+	if (info[3]) big[1] += 1;
 	if (info[2]) flags[0] += 1;
 	if (empty) flags[1] += 1;
 	if (!(t0 > 2.0)) flags[2] += 1;
@@ -57,7 +63,7 @@ __global__ void __launch_bounds__(256) k_front_scalars(const int64_t* __restrict
 		flags[3] += 1;
 		if (mx > big[0]) big[0] = mx;
 	}
-	big[1] = mx;
+	big[2] = mx;
 }
 
 __global__ void __launch_bounds__(256) k_front_tables(const double* __restrict__ fs, int64_t cap, double* __restrict__ tab, double* __restrict__ etab) {
@@ -66,6 +72,24 @@ __global__ void __launch_bounds__(256) k_front_tables(const double* __restrict__
 	const double t = nrm_digamma(1.0 + (double)x) - nrm_digamma(fs[0]);  // (a t0 that is not positive -- negative entries -- gives NaN; the step is refused by its counter)
 	tab[x] = t;
 	etab[x] = exp(t);
+}
+
+// unit = max over 1 <= x < len of (etab[x] - etab[0]) / x (nrm_lcpm_tables, nrm_host_math.h), from the device's own table: total_k * unit bounds the terms
+// etab[x] - etab[0] that nrm_lcpm_csr_colsum adds for cell k.  Non-negative doubles order as their bit patterns: an integer maximum, whatever the order of the
+// workgroups.  A quotient that is not a positive number (a NaN table: negative entries, refused by their counter) is left out.  k_front_scalars cleared the word.
+__global__ void __launch_bounds__(256) k_front_unit(const double* fs, int64_t cap, const double* __restrict__ etab, unsigned long long* unit_bits) {
+	const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x, len = (int64_t)fs[1];
+	double u = 0.0;
+	if (x >= 1 && x < len && x < cap) {
+		const double q = (etab[x] - etab[0]) / (double)x;
+		u = q > 0.0 ? q : 0.0;
+	}
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) {
+		const double t = __shfl_xor(u, o, 64);
+		u = t > u ? t : u;
+	}
+	if ((threadIdx.x & 63) == 0 && u > 0.0) atomicMax(unit_bits, (unsigned long long)__double_as_longlong(u));
 }
 
 // dc (nct, n): row r < n_cov the user's, the next three lcpm's, the last all ones.  cls[r] = the row's class (nrm_front_plan_args.h).
@@ -213,13 +237,14 @@ __global__ void __launch_bounds__(256) k_front_dcn(const double* __restrict__ dc
 struct nrm_front_plan : NrmPlanCore {
 	int64_t rows = 0, n = 0, n_cov = 0, nct = 0, ntot = -1, cap = 0;
 	int out_dtype = NRM_F64;
-	bool adopted = false;
+	bool adopted = false, csr = false;
+	int64_t nnz_cap = 0;  // CSR: elements the indices and values hold (the plan's own, or the adopted arrays')
 	// the three stages that the whole-problem entries run too, as their step records; around them what is the plan's own:
 	// the counts and lcpm's scalars, tables and result | the covariates | scaling_factor's operands and normvar's result
 	NrmLcpmPasses lc;
 	NrmFitvarStep fit;
 	NrmNormvarStep nv;
-	DevBuf own_x, fs, big, flags, tab, etab, t1, lcpm;
+	DevBuf own_x, own_indptr, own_indices, fs, big, flags, tab, etab, t1, lcpm;  // own_x: the dense matrix, or the CSR values
 	DevBuf user, dc, dcn, cls, m2i;
 	DevBuf lnw, wt, dtn;
 	int64_t cv_steps = 0, max_count = 0, warned = 0;
@@ -239,7 +264,11 @@ int plan_enqueue(nrm_front_plan* pl, hipStream_t st) {
 	NRM_TRY(nrm_check_launch("k_front_scalars"));
 	hipLaunchKernelGGL(k_front_tables, dim3((unsigned)((pl->cap + 255) / 256)), dim3(256), 0, st, pl->fs.as<double>(), pl->cap, pl->tab.as<double>(), pl->etab.as<double>());
 	NRM_TRY(nrm_check_launch("k_front_tables"));
-	NRM_TRY(lc.colsum(pl->etab.as<double>(), pl->cap, 0.0, pl->t1.as<double>(), st));  // (the unit is the CSR form's; the plan's counts are dense)
+	if (pl->csr) {
+		hipLaunchKernelGGL(k_front_unit, dim3((unsigned)((pl->cap + 255) / 256)), dim3(256), 0, st, pl->fs.as<double>(), pl->cap, pl->etab.as<double>(), pl->fs.as<unsigned long long>() + 2);
+		NRM_TRY(nrm_check_launch("k_front_unit"));
+	}
+	NRM_TRY(lc.colsum(pl->etab.as<double>(), pl->cap, 0.0, pl->t1.as<double>(), st));  // (the unit by value is not read: the CSR form takes lc.d_unit = fs + 2)
 	NRM_TRY(lc.write(pl->tab.as<double>(), pl->cap, pl->t1.as<double>(), pl->lcpm.p, pl->out_dtype, n, st));
 	// lcpm's covariate rows, normcov, the pseudo-inverse of the second regression
 	double* c = pl->dc.as<double>();
@@ -267,7 +296,17 @@ int plan_bind(nrm_front_plan* pl, const char* who) {
 }
 
 int plan_upload(nrm_front_plan* pl, const char* who, const void* h_reads) {
+	NRM_REQUIRE(!pl->csr, "%s: the plan holds CSR counts (nrm_front_plan_upload_csr)", who);
 	return nrm_plan_upload(*pl, who, pl->adopted, h_reads, pl->own_x.p, pl->rows * pl->n * (int64_t)nrm_count_elem(pl->lc.dtype));
+}
+
+// the three arrays into the plan's own; entries past nnz keep what they held, and no step reads them (the count is indptr[rows])
+int plan_upload_csr(nrm_front_plan* pl, const char* who, const int64_t* h_indptr, const int32_t* h_indices, const void* h_data, int64_t nnz) {
+	NRM_TRY(nrm_front_plan_upload_csr_args(pl->csr, pl->adopted, pl->rows, pl->nnz_cap, h_indptr, h_indices, h_data, nnz));  // every check: before any copy
+	NRM_TRY(nrm_plan_upload(*pl, who, false, h_indptr, pl->own_indptr.p, (pl->rows + 1) * 8));
+	if (nnz == 0) return NRM_OK;
+	NRM_TRY(nrm_plan_upload(*pl, who, false, h_indices, pl->own_indices.p, nnz * 4));
+	return nrm_plan_upload(*pl, who, false, h_data, pl->own_x.p, nnz * (int64_t)nrm_count_elem(pl->lc.dtype));
 }
 
 // waits, reads every counter once, clears them; caller holds nrm_host_entry_mutex
@@ -275,78 +314,116 @@ int plan_check(nrm_front_plan* pl, int64_t* near_constant) {
 	hipStream_t st = pl->last ? pl->last : pl->own;
 	if (near_constant) *near_constant = 0;
 	int32_t hf[FP_FLAGS];
-	int64_t hb[2] = {0, 0};
+	int64_t hb[3] = {0, 0, 0};
 	double hs[4] = {0, 0, 0, 0};
 	NRM_HIP(hipDeviceSynchronize());  // (steps may have gone to several streams since the last check)
 	NRM_TRY(nrm_read_flags(pl->flags.p, st, hf));
 	NRM_HIP(hipMemcpyAsync(hb, pl->big.p, sizeof(hb), hipMemcpyDeviceToHost, st));
 	NRM_HIP(hipMemcpyAsync(hs, pl->fit.state() + 4 * pl->fit.stepmax, sizeof(hs), hipMemcpyDeviceToHost, st));
 	NRM_TRY(nrm_fill_zero(pl->flags.p, FP_FLAGS * 4, (void*)st));
-	NRM_TRY(nrm_fill_zero(pl->big.p, 8, (void*)st));  // (big[1], the last step's maximum, stays: a second check reports it again)
+	NRM_TRY(nrm_fill_zero(pl->big.p, 16, (void*)st));  // (big[2], the last step's maximum, stays: a second check reports it again)
 	NRM_HIP(hipStreamSynchronize(st));
-	if (pl->steps > 0) pl->cv_steps = (int64_t)hs[1], pl->max_count = hb[1];
+	if (pl->steps > 0) pl->cv_steps = (int64_t)hs[1], pl->max_count = hb[2];
 	pl->warned = hf[5];
 	if (near_constant) *near_constant = hf[5];
-	return nrm_front_plan_status(hf, pl->cap, hb[0]);
+	return nrm_front_plan_status_csr(hb[1], hf, pl->cap, hb[0]);
 }
 
 }  // namespace
+
+// the plan of checked arguments: the buffers, the three step records, the covariates and -- for counts of its own -- the first upload
+static int plan_build(nrm_front_plan** plan, const NrmFrontPlanArgs& a, const char* who) {
+	NRM_REQUIRE(nrm_lcpm_row_tile() == 32 && nrm_fitvar_row_tile() == 32, "%s: the row tiles have changed (NRM_FRONT_MAX_ROWS)", who);
+	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
+	NRM_TRY(nrm_bind_device());
+	std::unique_ptr<nrm_front_plan> pl(new nrm_front_plan);
+	NRM_HIP(hipGetDevice(&pl->device));
+	const int64_t rows = a.rows, n = a.n, n_cov = a.n_cov, nc = n_cov + NRM_FRONT_LCPM_ROWS + 1, es = (int64_t)nrm_esize(a.out_dtype), count_cap = a.count_cap;
+	nrm_front_plan* p = pl.get();
+	p->rows = rows, p->n = n, p->n_cov = n_cov, p->nct = nc, p->ntot = a.ntot < 0 ? -1 : a.ntot, p->cap = count_cap, p->out_dtype = a.out_dtype, p->adopted = a.on_device != 0;
+	p->csr = a.csr != 0, p->nnz_cap = a.nnz_cap;
+	NRM_HIP(hipStreamCreateWithFlags(&p->own, hipStreamNonBlocking));
+	auto take = [p](DevBuf& b, size_t bytes) { return p->take(b, bytes); };
+	// the counts: a dense matrix, or three arrays of the capacity -- never a (rows, n) matrix for CSR counts
+	if (!p->adopted && !p->csr) NRM_TRY(take(p->own_x, (size_t)(rows * n) * nrm_count_elem(a.dtype)));
+	if (!p->adopted && p->csr)
+		NRM_TRY(nrm_take_all(take, {{&p->own_indptr, (rows + 1) * 8}, {&p->own_indices, a.nnz_cap * 4}, {&p->own_x, a.nnz_cap * (int64_t)nrm_count_elem(a.dtype)}}));
+	NRM_TRY(take(p->fs, 32));  // (in front of lc.alloc: the CSR passes read their unit from fs + 2)
+	// lcpm | the covariates | compute_var | normvar: each record sizes its own buffers, the plan what lies between them
+	NrmLcpmPasses& lc = p->lc;
+	lc.rows = rows, lc.n = n, lc.dtype = a.dtype, lc.d_x = p->adopted ? a.reads : p->own_x.p, lc.ld = a.ld;
+	if (p->csr) {
+		lc.csr = true, lc.stored = a.nnz_cap, lc.d_unit = p->fs.as<double>() + 2;
+		lc.d_indptr = p->adopted ? a.indptr : p->own_indptr.as<int64_t>(), lc.d_indices = p->adopted ? a.indices : p->own_indices.as<int32_t>();
+	}
+	NRM_TRY(lc.alloc(take));
+	NRM_TRY(nrm_take_all(take, {{&p->big, 24}, {&p->flags, FP_FLAGS * 4}, {&p->tab, count_cap * 8}, {&p->etab, count_cap * 8}, {&p->t1, n * 8}, {&p->lcpm, rows * n * es},
+								{&p->user, std::max<int64_t>(n_cov * n, 1) * 8}, {&p->dc, nc * n * 8}, {&p->dcn, nc * n * 8}, {&p->cls, nc * 4}, {&p->m2i, (nc + 1) * (nc + 1) * 8}}));
+	NrmFitvarStep& fit = p->fit;
+	fit.rows = rows, fit.n = n, fit.ldy = n, fit.nc = nc, fit.stepmax = a.stepmax, fit.eps = a.eps, fit.y_dtype = a.out_dtype;
+	fit.d_y = p->lcpm.p, fit.d_c = p->dc.as<double>(), fit.d_m2i = p->m2i.as<double>(), fit.flags = p->flags.as<int32_t>() + 8;
+	NRM_TRY(fit.alloc(take));
+	NRM_TRY(nrm_take_all(take, {{&p->lnw, n * 8}, {&p->wt, rows * 8}}));
+	NrmNormvarStep& nv = p->nv;
+	nv.rows = rows, nv.n = n, nv.ldy = n, nv.nc = nc, nv.ldo = n, nv.tol = a.tol, nv.keepvar = 1, nv.y_dtype = nv.out_dtype = a.out_dtype;
+	nv.d_y = p->lcpm.p, nv.d_lnw = p->lnw.as<double>(), nv.d_wt = p->wt.as<double>(), nv.d_c = p->dc.as<double>(), nv.flags = p->flags.as<int32_t>() + 12;
+	NRM_TRY(nv.alloc(take));
+	NRM_TRY(take(p->dtn, (size_t)(rows * n * es)));
+	nv.d_out = p->dtn.p;
+	NRM_TRY(nrm_fill_zero(p->flags.p, FP_FLAGS * 4, (void*)p->own));
+	NRM_TRY(nrm_fill_zero(p->big.p, 24, (void*)p->own));
+	NRM_TRY(nrm_fill_zero(p->fs.p, 32, (void*)p->own));
+	NRM_TRY(nrm_fill_zero(p->tab.p, count_cap * 8, (void*)p->own));  // (entries past the largest count are never indexed; they are zero, not whatever the pool held)
+	NRM_TRY(nrm_fill_zero(p->etab.p, count_cap * 8, (void*)p->own));
+	NRM_TRY(nrm_fill_zero(fit.out.p, fit.out_doubles() * 8, (void*)p->own));
+	if (n_cov > 0) NRM_HIP(hipMemcpyAsync(p->user.p, a.h_cov, (size_t)(n_cov * n) * 8, hipMemcpyHostToDevice, p->own));
+	NRM_HIP(hipStreamSynchronize(p->own));
+	if (p->adopted)
+		NRM_HIP(hipDeviceSynchronize());  // (whatever the caller queued to fill its matrix is through before the first step reads it)
+	else if (p->csr)
+		NRM_TRY(plan_upload_csr(p, who, a.indptr, a.indices, a.reads, a.nnz));
+	else
+		NRM_TRY(plan_upload(p, who, a.reads));
+	*plan = pl.release();
+	return NRM_OK;
+}
+
+static void plan_options(NrmFrontPlanArgs& a, const double* h_cov, int64_t n_cov, int64_t ntot, int64_t stepmax, double eps, double tol, int out_dtype, int64_t count_cap) {
+	a.h_cov = h_cov, a.n_cov = n_cov, a.ntot = ntot, a.stepmax = stepmax, a.eps = eps, a.tol = tol, a.out_dtype = out_dtype, a.count_cap = count_cap;
+}
 
 extern "C" int nrm_front_plan_create(nrm_front_plan** plan, const void* reads, int dtype, int64_t genes, int64_t n_cells, int64_t ld, int reads_on_device, const double* h_cov,
 									 int64_t n_cov, int64_t ntot, int64_t stepmax, double eps, double tol, int out_dtype, int64_t count_cap) {
 	NRM_REQUIRE(plan != nullptr, "nrm_front_plan_create: null plan pointer");
 	*plan = nullptr;
 	NrmFrontPlanArgs a;
-	a.reads = reads, a.dtype = dtype, a.rows = genes, a.n = n_cells, a.ld = ld ? ld : n_cells, a.on_device = reads_on_device, a.h_cov = h_cov, a.n_cov = n_cov;
-	a.ntot = ntot, a.stepmax = stepmax, a.eps = eps, a.tol = tol, a.out_dtype = out_dtype, a.count_cap = count_cap;
+	a.reads = reads, a.dtype = dtype, a.rows = genes, a.n = n_cells, a.ld = ld ? ld : n_cells, a.on_device = reads_on_device;
+	plan_options(a, h_cov, n_cov, ntot, stepmax, eps, tol, out_dtype, count_cap);
 	NRM_TRY(nrm_front_plan_create_args(a, nrm_normvar_device_covariates(), nrm_lcpm_table_cap()));  // every check: before any device call
-	NRM_REQUIRE(nrm_lcpm_row_tile() == 32 && nrm_fitvar_row_tile() == 32, "nrm_front_plan_create: the row tiles have changed (NRM_FRONT_MAX_ROWS)");
+	return plan_build(plan, a, "nrm_front_plan_create");
+}
 
-	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
-	NRM_TRY(nrm_bind_device());
-	std::unique_ptr<nrm_front_plan> pl(new nrm_front_plan);
-	NRM_HIP(hipGetDevice(&pl->device));
-	const int64_t rows = genes, n = n_cells, nc = n_cov + NRM_FRONT_LCPM_ROWS + 1, es = (int64_t)nrm_esize(out_dtype);
-	nrm_front_plan* p = pl.get();
-	p->rows = rows, p->n = n, p->n_cov = n_cov, p->nct = nc, p->ntot = ntot < 0 ? -1 : ntot, p->cap = count_cap, p->out_dtype = out_dtype, p->adopted = reads_on_device != 0;
-	NRM_HIP(hipStreamCreateWithFlags(&p->own, hipStreamNonBlocking));
-	auto take = [p](DevBuf& b, size_t bytes) { return p->take(b, bytes); };
-	if (!p->adopted) NRM_TRY(take(p->own_x, (size_t)(rows * n) * nrm_count_elem(dtype)));
-	// lcpm | the covariates | compute_var | normvar: each record sizes its own buffers, the plan what lies between them
-	NrmLcpmPasses& lc = p->lc;
-	lc.rows = rows, lc.n = n, lc.dtype = dtype, lc.d_x = p->adopted ? reads : p->own_x.p, lc.ld = a.ld;
-	NRM_TRY(lc.alloc(take));
-	NRM_TRY(nrm_take_all(take, {{&p->fs, 32}, {&p->big, 16}, {&p->flags, FP_FLAGS * 4}, {&p->tab, count_cap * 8}, {&p->etab, count_cap * 8}, {&p->t1, n * 8}, {&p->lcpm, rows * n * es},
-								{&p->user, std::max<int64_t>(n_cov * n, 1) * 8}, {&p->dc, nc * n * 8}, {&p->dcn, nc * n * 8}, {&p->cls, nc * 4}, {&p->m2i, (nc + 1) * (nc + 1) * 8}}));
-	NrmFitvarStep& fit = p->fit;
-	fit.rows = rows, fit.n = n, fit.ldy = n, fit.nc = nc, fit.stepmax = stepmax, fit.eps = eps, fit.y_dtype = out_dtype;
-	fit.d_y = p->lcpm.p, fit.d_c = p->dc.as<double>(), fit.d_m2i = p->m2i.as<double>(), fit.flags = p->flags.as<int32_t>() + 8;
-	NRM_TRY(fit.alloc(take));
-	NRM_TRY(nrm_take_all(take, {{&p->lnw, n * 8}, {&p->wt, rows * 8}}));
-	NrmNormvarStep& nv = p->nv;
-	nv.rows = rows, nv.n = n, nv.ldy = n, nv.nc = nc, nv.ldo = n, nv.tol = tol, nv.keepvar = 1, nv.y_dtype = nv.out_dtype = out_dtype;
-	nv.d_y = p->lcpm.p, nv.d_lnw = p->lnw.as<double>(), nv.d_wt = p->wt.as<double>(), nv.d_c = p->dc.as<double>(), nv.flags = p->flags.as<int32_t>() + 12;
-	NRM_TRY(nv.alloc(take));
-	NRM_TRY(take(p->dtn, (size_t)(rows * n * es)));
-	nv.d_out = p->dtn.p;
-	NRM_TRY(nrm_fill_zero(p->flags.p, FP_FLAGS * 4, (void*)p->own));
-	NRM_TRY(nrm_fill_zero(p->big.p, 16, (void*)p->own));
-	NRM_TRY(nrm_fill_zero(p->tab.p, count_cap * 8, (void*)p->own));  // (entries past the largest count are never indexed; they are zero, not whatever the pool held)
-	NRM_TRY(nrm_fill_zero(p->etab.p, count_cap * 8, (void*)p->own));
-	NRM_TRY(nrm_fill_zero(fit.out.p, fit.out_doubles() * 8, (void*)p->own));
-	if (n_cov > 0) NRM_HIP(hipMemcpyAsync(p->user.p, h_cov, (size_t)(n_cov * n) * 8, hipMemcpyHostToDevice, p->own));
-	NRM_HIP(hipStreamSynchronize(p->own));
-	if (p->adopted)
-		NRM_HIP(hipDeviceSynchronize());  // (whatever the caller queued to fill its matrix is through before the first step reads it)
-	else
-		NRM_TRY(plan_upload(p, "nrm_front_plan_create", reads));
-	*plan = pl.release();
-	return NRM_OK;
+extern "C" int nrm_front_plan_create_csr(nrm_front_plan** plan, const int64_t* indptr, const int32_t* indices, const void* data, int dtype, int64_t genes, int64_t n_cells,
+										 int64_t nnz, int64_t nnz_cap, int on_device, const double* h_cov, int64_t n_cov, int64_t ntot, int64_t stepmax, double eps, double tol,
+										 int out_dtype, int64_t count_cap) {
+	NRM_REQUIRE(plan != nullptr, "nrm_front_plan_create_csr: null plan pointer");
+	*plan = nullptr;
+	NrmFrontPlanArgs a;
+	a.csr = 1, a.indptr = indptr, a.indices = indices, a.reads = data, a.nnz = nnz, a.nnz_cap = nnz_cap;
+	a.dtype = dtype, a.rows = genes, a.n = n_cells, a.ld = n_cells, a.on_device = on_device;
+	plan_options(a, h_cov, n_cov, ntot, stepmax, eps, tol, out_dtype, count_cap);
+	NRM_TRY(nrm_front_plan_create_csr_args(a, nrm_normvar_device_covariates(), nrm_lcpm_table_cap()));  // every check: before any device call
+	return plan_build(plan, a, "nrm_front_plan_create_csr");
 }
 
 extern "C" int nrm_front_plan_upload(nrm_front_plan* plan, const void* h_reads) {
 	NRM_TRY(plan_bind(plan, "nrm_front_plan_upload"));
 	return plan_upload(plan, "nrm_front_plan_upload", h_reads);
+}
+
+extern "C" int nrm_front_plan_upload_csr(nrm_front_plan* plan, const int64_t* h_indptr, const int32_t* h_indices, const void* h_data, int64_t nnz) {
+	NRM_TRY(plan_bind(plan, "nrm_front_plan_upload_csr"));
+	return plan_upload_csr(plan, "nrm_front_plan_upload_csr", h_indptr, h_indices, h_data, nnz);
 }
 
 extern "C" int nrm_front_plan_step(nrm_front_plan* plan, void* stream) {

@@ -1,7 +1,7 @@
-// What nrm_front_plan_create (nrm_front_plan.hip) decides before any device call: every argument check, the user covariate rows' finiteness and normcov's
-// constant-row test on them (norm.py:34-37), and the host restatement of normcov's row classification (norm.py:39) that the device kernel k_front_cov applies to
-// every row of every step.  Free of HIP headers, like nrm_de_plan_args.h, so that g++ can build it with -fsanitize=address,undefined for the CPU test-suite
-// (tests/host/front_plan_args_sanitize.cpp).
+// What nrm_front_plan_create and nrm_front_plan_create_csr (nrm_front_plan.hip) decide before any device call: every argument check, for canonical CSR host arrays
+// the O(rows) part of the structure, the user covariate rows' finiteness and normcov's constant-row test on them (norm.py:34-37), and the host restatement of
+// normcov's row classification (norm.py:39) that the device kernel k_front_cov applies to every row of every step.  Free of HIP headers, like nrm_de_plan_args.h,
+// so that g++ can build it with -fsanitize=address,undefined for the CPU test-suite (tests/host/front_plan_args_sanitize.cpp, front_plan_csr_args_sanitize.cpp).
 #pragma once
 #include "nrm_host_logic.h"
 
@@ -25,9 +25,28 @@ struct NrmFrontPlanArgs {
 	double eps = 1e-6, tol = 1e-8;
 	int out_dtype = NRM_F64;
 	int64_t count_cap = 0;
+	// nrm_front_plan_create_csr: `reads` is the stored values; indptr (rows + 1) int64, indices int32; nnz stored entries in arrays of nnz_cap elements
+	int csr = 0;
+	const int64_t* indptr = nullptr;
+	const int32_t* indices = nullptr;
+	int64_t nnz = 0, nnz_cap = 0;
 };
 
+// what the eager CSR path says of a malformed matrix (nrm_host_front.hip; normalisr_amd/lcpm.py: MALFORMED_CSR)
+#define NRM_MALFORMED_CSR                                                                                                                      \
+	"Malformed CSR matrix: indptr must rise from 0 to the number of stored entries, and the columns of every row must lie in [0, n_cell) and " \
+	"increase strictly (sum duplicates and sort the indices first)."
+
 static inline bool nrm_front_count_dtype(int dtype) { return dtype == NRM_I64 || dtype == NRM_I32 || dtype == NRM_I16 || dtype == NRM_U8; }
+static inline int nrm_front_count_bytes(int dtype) { return dtype == NRM_I64 ? 8 : dtype == NRM_I32 ? 4 : dtype == NRM_I16 ? 2 : 1; }
+
+// the O(rows) part of a host CSR matrix's structure: 0 = p[0] <= p[1] <= ... <= p[rows] = nnz (the columns of every entry are the count kernel's to check)
+static inline int nrm_front_csr_offsets(const int64_t* indptr, int64_t rows, int64_t nnz) {
+	bool ok = indptr[0] == 0 && indptr[rows] == nnz;
+	for (int64_t r = 0; r < rows && ok; r++) ok = indptr[r] <= indptr[r + 1];
+	NRM_REQUIRE(ok, "%s", NRM_MALFORMED_CSR);
+	return NRM_OK;
+}
 
 // normcov's view of one covariate row of n cells: NRM_COV_CONSTANT, NRM_COV_BINARY or NRM_COV_CONTINUOUS
 static inline int nrm_normcov_row_class(const double* row, int64_t n) {
@@ -39,15 +58,20 @@ static inline int nrm_normcov_row_class(const double* row, int64_t n) {
 	return same ? NRM_COV_CONSTANT : cont ? NRM_COV_CONTINUOUS : NRM_COV_BINARY;
 }
 
-// Every check of create.  max_covariates: nrm_normvar_device_covariates(); table_cap: nrm_lcpm_table_cap().
-static inline int nrm_front_plan_create_args(const NrmFrontPlanArgs& a, int64_t max_covariates, int64_t table_cap) {
-	const char* who = "nrm_front_plan_create";
-	NRM_REQUIRE(a.reads != nullptr && a.n_cov >= 0 && (a.n_cov == 0 || a.h_cov != nullptr), "%s: null pointer", who);
+// Every check of create (a.csr == 0) and of create_csr, under the entry's name.  max_covariates: nrm_normvar_device_covariates(); table_cap: nrm_lcpm_table_cap().
+static inline int nrm_front_plan_args_check(const char* who, const NrmFrontPlanArgs& a, int64_t max_covariates, int64_t table_cap) {
+	NRM_REQUIRE(a.reads != nullptr && (!a.csr || (a.indptr != nullptr && a.indices != nullptr)) && a.n_cov >= 0 && (a.n_cov == 0 || a.h_cov != nullptr), "%s: null pointer", who);
 	NRM_REQUIRE(a.rows > 0 && a.n > 0, "reads must not be empty.");
 	NRM_REQUIRE(nrm_front_count_dtype(a.dtype), "%s: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8", who);
 	NRM_REQUIRE(a.out_dtype == NRM_F32 || a.out_dtype == NRM_F64, "%s: out_dtype must be NRM_F32 or NRM_F64", who);
 	NRM_REQUIRE(a.rows <= NRM_FRONT_MAX_ROWS && a.n <= 0x7fffffffLL, "%s: at most %lld genes and 2^31 - 1 cells", who, (long long)NRM_FRONT_MAX_ROWS);
-	NRM_REQUIRE(a.on_device ? a.ld >= a.n : a.ld == a.n, "%s: row pitch smaller than the row (a host matrix is contiguous)", who);
+	if (a.csr) {
+		NRM_REQUIRE(a.nnz_cap >= 1 && a.nnz >= 0 && a.nnz <= a.nnz_cap, "%s: 0 <= nnz <= nnz_cap and nnz_cap >= 1 must hold", who);
+		NRM_REQUIRE((uintptr_t)a.indptr % 8 == 0 && (uintptr_t)a.indices % 4 == 0 && (uintptr_t)a.reads % (uintptr_t)nrm_front_count_bytes(a.dtype) == 0, "%s: misaligned CSR arrays", who);
+		if (!a.on_device)
+			if (const int rc = nrm_front_csr_offsets(a.indptr, a.rows, a.nnz)) return rc;
+	} else
+		NRM_REQUIRE(a.on_device ? a.ld >= a.n : a.ld == a.n, "%s: row pitch smaller than the row (a host matrix is contiguous)", who);
 	const int64_t total = a.n_cov + NRM_FRONT_LCPM_ROWS + 1;
 	if (total > max_covariates || total + 1 > NRM_FRONT_M2_ROWS) {
 		const int64_t bound = max_covariates < NRM_FRONT_M2_ROWS - 1 ? max_covariates : NRM_FRONT_M2_ROWS - 1;
@@ -66,6 +90,23 @@ static inline int nrm_front_plan_create_args(const NrmFrontPlanArgs& a, int64_t 
 		NRM_REQUIRE(nrm_normcov_row_class(row, a.n) != NRM_COV_CONSTANT, "Detected constant covariate. Please only provide full-rank covariate without constant covariate.");
 	}
 	return NRM_OK;
+}
+static inline int nrm_front_plan_create_args(const NrmFrontPlanArgs& a, int64_t max_covariates, int64_t table_cap) {
+	NRM_REQUIRE(!a.csr, "nrm_front_plan_create: a dense matrix (nrm_front_plan_create_csr takes CSR counts)");
+	return nrm_front_plan_args_check("nrm_front_plan_create", a, max_covariates, table_cap);
+}
+static inline int nrm_front_plan_create_csr_args(const NrmFrontPlanArgs& a, int64_t max_covariates, int64_t table_cap) {
+	NRM_REQUIRE(a.csr, "nrm_front_plan_create_csr: CSR counts (nrm_front_plan_create takes a dense matrix)");
+	return nrm_front_plan_args_check("nrm_front_plan_create_csr", a, max_covariates, table_cap);
+}
+// Every check of upload_csr, before any copy: the plan holds CSR counts of its own, the new ones fit, and their offsets are a CSR matrix's
+static inline int nrm_front_plan_upload_csr_args(bool csr, bool adopted, int64_t rows, int64_t nnz_cap, const int64_t* indptr, const int32_t* indices, const void* data, int64_t nnz) {
+	const char* who = "nrm_front_plan_upload_csr";
+	NRM_REQUIRE(csr, "%s: the plan holds a dense matrix (nrm_front_plan_upload)", who);
+	NRM_REQUIRE(!adopted, "%s: the plan adopted the caller's device matrix (rewrite it in place)", who);
+	NRM_REQUIRE(indptr != nullptr && (nnz <= 0 || (indices != nullptr && data != nullptr)), "%s: null pointer", who);
+	NRM_REQUIRE(nnz >= 0 && nnz <= nnz_cap, "%s: %lld stored entries, beyond the plan's nnz_cap = %lld", who, (long long)nnz, (long long)nnz_cap);
+	return nrm_front_csr_offsets(indptr, rows, nnz);
 }
 
 // compute_var's counters ([0] nrm_fitvar_genes, [1] nrm_fitvar_weights) as what the reference raises (norm.py:108,125-127).  nrm_compute_var_host and the plan's
@@ -116,4 +157,10 @@ static inline int nrm_front_plan_status(const int32_t f[16], int64_t cap, int64_
 		return NRM_E_NUMERIC;
 	}
 	return nrm_normvar_status(f + 12);
+}
+// The same with the count pass's structure check in front (a CSR plan; a dense plan's word stays 0): malformed is a word of its own beside the sixteen, met
+// before anything the malformed matrix's numbers may have set
+static inline int nrm_front_plan_status_csr(int64_t malformed, const int32_t f[16], int64_t cap, int64_t count) {
+	NRM_REQUIRE(!malformed, "%s", NRM_MALFORMED_CSR);
+	return nrm_front_plan_status(f, cap, count);
 }

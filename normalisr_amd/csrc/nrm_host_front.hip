@@ -14,9 +14,7 @@
 #include "nrm_host_entry.h"
 #include "nrm_lcpm_step.h"
 
-static const char* const MALFORMED_CSR =
-	"Malformed CSR matrix: indptr must rise from 0 to the number of stored entries, and the columns of every row must lie in [0, n_cell) and "
-	"increase strictly (sum duplicates and sort the indices first).";
+static const char* const MALFORMED_CSR = NRM_MALFORMED_CSR;  // (nrm_front_plan_args.h: the resident plan says the same)
 
 // a host array of any element size in HBM (upload_matrix knows fp32 / fp64 only); nothing is copied for an empty array
 static int upload_bytes(const void* h, int64_t bytes, DevBuf& d, hipStream_t st) {

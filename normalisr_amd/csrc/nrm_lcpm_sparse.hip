@@ -13,6 +13,10 @@
 //                 barrier per step), then every lane reads four cells, looks up T only where the count is not zero, and stores 16 bytes: each output
 //                 element is stored once.
 // Nothing here trusts the structure: indptr is clamped to [0, nnz], a column outside the chunk is skipped, a count outside the table reads its end.
+// The two launch arguments that depend on the data -- the number of stored entries and `unit` -- come in two forms.  The entries of the C ABI pass them by value.
+// A resident plan (nrm_front_plan.hip), whose captured graph must survive a rewrite of the matrix, pattern included, passes dev = 1 and d_unit: nnz is then the
+// CAPACITY of indices and data, the stored entries are indptr[rows] clamped to [0, nnz] (lcs_entries), unit is *d_unit, and no launch argument depends on the
+// data.  Whatever the buffers hold, no thread reads outside the rows + 1 offsets and the nnz entries.
 #include <cmath>
 
 #include "nrm_device.h"
@@ -37,6 +41,9 @@ __device__ __forceinline__ int lcs_shift(int64_t total, double unit) {
 	return e < -60 ? -60 : e > 900 ? 900 : e;
 }
 
+// the stored entries: the argument, or (dev) indptr[rows] clamped to the capacity -- an indptr[rows] outside [0, capacity] then differs from it, which lcs_rows reports
+__device__ __forceinline__ int64_t lcs_entries(const int64_t* __restrict__ indptr, int64_t rows, int64_t nnz, int dev) { return dev ? nrm_clamp(indptr[rows], 0, nnz) : nnz; }
+
 // The rows' bounds of a tile into LDS, clamped; returns 1 for an indptr that is not 0 = p[0] <= p[1] <= ... <= p[rows] = nnz (threads below LCS_TR)
 __device__ __forceinline__ int lcs_rows(const int64_t* __restrict__ indptr, int64_t rows, int64_t nnz, int64_t row0, int nr, int64_t* s_cur, int64_t* s_end) {
 	int bad = 0;
@@ -59,11 +66,12 @@ __device__ __forceinline__ int lcs_rows(const int64_t* __restrict__ indptr, int6
 // slab[tile][k] = 256 * (the tile's total of cell k) + its count of non-zeros (at most LCS_TR); rec[tile] = {total, maximum, minimum, malformed}
 template <typename T>
 __global__ void __launch_bounds__(512) k_lcs_count(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t rows, int64_t n,
-												   int64_t nnz, int64_t* __restrict__ slab, int64_t* __restrict__ rec, int64_t* __restrict__ gene_zero) {
+												   int64_t nnz_arg, int dev, int64_t* __restrict__ slab, int64_t* __restrict__ rec, int64_t* __restrict__ gene_zero) {
 	__shared__ lcs_u64 s_acc[LCS_CW];
 	__shared__ int64_t s_cur[LCS_TR], s_end[LCS_TR];
 	__shared__ int64_t s_stat[8][4];
 	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+	const int64_t nnz = lcs_entries(indptr, rows, nnz_arg, dev);
 	const int64_t row0 = (int64_t)blockIdx.x * LCS_TR;
 	const int nr = (int)(rows - row0 < LCS_TR ? rows - row0 : LCS_TR);
 	int bad = lcs_rows(indptr, rows, nnz, row0, nr, s_cur, s_end);
@@ -185,12 +193,14 @@ __global__ void __launch_bounds__(256) k_lcs_count_finish(const int64_t* __restr
 // ---- pass 2: per-cell sums of E[x] - E[0] in fixed point ---------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void __launch_bounds__(512) k_lcs_colsum(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t rows, int64_t n,
-													int64_t nnz, const double* __restrict__ tab, int64_t tlen, double unit, const int64_t* __restrict__ cell_total,
-													int64_t* __restrict__ slab) {
+													int64_t nnz_arg, int dev, const double* __restrict__ tab, int64_t tlen, double unit_arg, const double* __restrict__ d_unit,
+													const int64_t* __restrict__ cell_total, int64_t* __restrict__ slab) {
 	__shared__ lcs_u64 s_acc[LCS_CW];
 	__shared__ short s_shift[LCS_CW];
 	__shared__ int64_t s_cur[LCS_TR], s_end[LCS_TR];
 	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+	const int64_t nnz = lcs_entries(indptr, rows, nnz_arg, dev);
+	const double unit = d_unit ? *d_unit : unit_arg;
 	const int64_t row0 = (int64_t)blockIdx.x * LCS_TR;
 	const int nr = (int)(rows - row0 < LCS_TR ? rows - row0 : LCS_TR);
 	(void)lcs_rows(indptr, rows, nnz, row0, nr, s_cur, s_end);
@@ -219,9 +229,10 @@ __global__ void __launch_bounds__(512) k_lcs_colsum(const int64_t* __restrict__ 
 }
 
 // t1[k] = ln(rows * E[0] + 2^-shift_k * (the tiles' integers of cell k, added in a fixed order)) - ln 1e6
-__global__ void __launch_bounds__(256) k_lcs_finish(const int64_t* __restrict__ slab, int64_t tiles, int64_t n, int64_t rows, const double* __restrict__ tab, double unit,
-													const int64_t* __restrict__ cell_total, double* __restrict__ t1) {
+__global__ void __launch_bounds__(256) k_lcs_finish(const int64_t* __restrict__ slab, int64_t tiles, int64_t n, int64_t rows, const double* __restrict__ tab, double unit_arg,
+													const double* __restrict__ d_unit, const int64_t* __restrict__ cell_total, double* __restrict__ t1) {
 	__shared__ lcs_u64 sm[4][64];
+	const double unit = d_unit ? *d_unit : unit_arg;
 	const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 	const int64_t k = (int64_t)blockIdx.x * 64 + lane;
 	lcs_u64 s = 0;
@@ -240,12 +251,13 @@ __global__ void __launch_bounds__(256) k_lcs_finish(const int64_t* __restrict__ 
 // A lane owns cells c0 + 1024 j + 4 lane .. + 3, j = 0 .. 3, of a chunk.  ALIGNED (the launcher: out, ldo and t1 on 16-byte boundaries): 16-byte stores.
 template <typename T, typename OutT, bool ALIGNED>
 __global__ void __launch_bounds__(256) k_lcs_write(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, const T* __restrict__ val, int64_t rows, int64_t n,
-												   int64_t nnz, const double* __restrict__ tab, int64_t tlen, const double* __restrict__ t1, OutT* __restrict__ out,
+												   int64_t nnz_arg, int dev, const double* __restrict__ tab, int64_t tlen, const double* __restrict__ t1, OutT* __restrict__ out,
 												   int64_t ldo) {
 	__shared__ __attribute__((aligned(16))) int s_img[2][LCS_CW];
 	typedef int iv_t __attribute__((ext_vector_type(4)));
 	typedef double dv_t __attribute__((ext_vector_type(2)));
 	const int tid = threadIdx.x;
+	const int64_t nnz = lcs_entries(indptr, rows, nnz_arg, dev);
 	for (int i = tid; i < 2 * LCS_CW; i += 256) (&s_img[0][0])[i] = 0;
 	__syncthreads();
 	const double t0 = tab[0];
@@ -316,20 +328,21 @@ __global__ void __launch_bounds__(256) k_lcs_write(const int64_t* __restrict__ i
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------------------------------
+// nrm_lcpm_csr_passes_* (nrm_lcpm_step.h) launch both forms; the entries of the C ABI below are their by-value form (dev = 0, d_unit = NULL).
 static int lcs_check(const char* what, const void* d_indptr, const void* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz) {
 	NRM_REQUIRE(nrm_count_elem(dtype) != 0, "%s: counts are NRM_I64, NRM_I32, NRM_I16 or NRM_U8", what);
 	return nrm_csr_args_check(what, d_indptr, d_indices, d_data, nrm_count_elem(dtype), rows, n, nnz);
 }
 
-extern "C" int nrm_lcpm_csr_count(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
-								  int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_gene_zero, int64_t* d_info, int64_t* d_partial, void* stream) {
+int nrm_lcpm_csr_passes_count(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz, int dev,
+							  int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_gene_zero, int64_t* d_info, int64_t* d_partial, void* stream) {
 	NRM_TRY(lcs_check("nrm_lcpm_csr_count", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
 	NRM_REQUIRE(d_cell_total && d_cell_nnz && d_gene_zero && d_info && d_partial, "nrm_lcpm_csr_count: null pointer");
 	const int64_t tiles = (rows + LCS_TR - 1) / LCS_TR;
 	NRM_REQUIRE(tiles <= 0x7fffffffLL, "nrm_lcpm_csr_count: too many rows");
 	hipStream_t st = (hipStream_t)stream;
 #define LCS_GO(TY) \
-	hipLaunchKernelGGL((k_lcs_count<TY>), dim3((unsigned)tiles), dim3(512), 0, st, d_indptr, d_indices, (const TY*)d_data, rows, n, nnz, d_partial, d_partial + tiles * n, d_gene_zero)
+	hipLaunchKernelGGL((k_lcs_count<TY>), dim3((unsigned)tiles), dim3(512), 0, st, d_indptr, d_indices, (const TY*)d_data, rows, n, nnz, dev, d_partial, d_partial + tiles * n, d_gene_zero)
 	NRM_BY_COUNT_DTYPE(LCS_GO)
 #undef LCS_GO
 	NRM_TRY(nrm_check_launch("k_lcs_count"));
@@ -337,29 +350,30 @@ extern "C" int nrm_lcpm_csr_count(const int64_t* d_indptr, const int32_t* d_indi
 	return nrm_check_launch("k_lcs_count_finish");
 }
 
-extern "C" int nrm_lcpm_csr_colsum(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
-								   const double* d_exp_table, int64_t table_len, double unit, const int64_t* d_cell_total, int64_t* d_partial, double* d_t1,
-								   void* stream) {
+int nrm_lcpm_csr_passes_colsum(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz, int dev,
+							   const double* d_exp_table, int64_t table_len, double unit, const double* d_unit, const int64_t* d_cell_total, int64_t* d_partial, double* d_t1,
+							   void* stream) {
 	NRM_TRY(lcs_check("nrm_lcpm_csr_colsum", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
 	NRM_REQUIRE(d_exp_table && table_len > 0 && table_len <= LCS_TAB_CAP && d_cell_total && d_partial && d_t1, "nrm_lcpm_csr_colsum: bad arguments");
-	NRM_REQUIRE(unit >= 0.0 && std::isfinite(unit), "nrm_lcpm_csr_colsum: unit must be the largest (E[x] - E[0]) / x of the table");
+	NRM_REQUIRE(d_unit || (unit >= 0.0 && std::isfinite(unit)), "nrm_lcpm_csr_colsum: unit must be the largest (E[x] - E[0]) / x of the table");
 	const int64_t tiles = (rows + LCS_TR - 1) / LCS_TR;
 	hipStream_t st = (hipStream_t)stream;
-#define LCS_GO(TY) \
-	hipLaunchKernelGGL((k_lcs_colsum<TY>), dim3((unsigned)tiles), dim3(512), 0, st, d_indptr, d_indices, (const TY*)d_data, rows, n, nnz, d_exp_table, table_len, unit, d_cell_total, d_partial)
+#define LCS_GO(TY)                                                                                                                                                          \
+	hipLaunchKernelGGL((k_lcs_colsum<TY>), dim3((unsigned)tiles), dim3(512), 0, st, d_indptr, d_indices, (const TY*)d_data, rows, n, nnz, dev, d_exp_table, table_len, unit, d_unit, \
+					   d_cell_total, d_partial)
 	NRM_BY_COUNT_DTYPE(LCS_GO)
 #undef LCS_GO
 	NRM_TRY(nrm_check_launch("k_lcs_colsum"));
-	hipLaunchKernelGGL(k_lcs_finish, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_partial, tiles, n, rows, d_exp_table, unit, d_cell_total, d_t1);
+	hipLaunchKernelGGL(k_lcs_finish, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, d_partial, tiles, n, rows, d_exp_table, unit, d_unit, d_cell_total, d_t1);
 	return nrm_check_launch("k_lcs_finish");
 }
 
 template <typename T>
-static void lcs_launch_write(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int64_t rows, int64_t n, int64_t nnz, const double* d_table,
+static void lcs_launch_write(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int64_t rows, int64_t n, int64_t nnz, int dev, const double* d_table,
 							 int64_t table_len, const double* d_t1, void* d_out, int out_dtype, int64_t ldo, bool al, hipStream_t st) {
 	const dim3 grid((unsigned)(rows < 16384 ? rows : 16384));
 #define LCS_GO4(TO, AL) \
-	hipLaunchKernelGGL((k_lcs_write<T, TO, AL>), grid, dim3(256), 0, st, d_indptr, d_indices, (const T*)d_data, rows, n, nnz, d_table, table_len, d_t1, (TO*)d_out, ldo)
+	hipLaunchKernelGGL((k_lcs_write<T, TO, AL>), grid, dim3(256), 0, st, d_indptr, d_indices, (const T*)d_data, rows, n, nnz, dev, d_table, table_len, d_t1, (TO*)d_out, ldo)
 #define LCS_GO(TO)              \
 	do {                        \
 		if (al) LCS_GO4(TO, true); \
@@ -371,14 +385,30 @@ static void lcs_launch_write(const int64_t* d_indptr, const int32_t* d_indices, 
 #undef LCS_GO4
 }
 
-extern "C" int nrm_lcpm_csr_write(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
-								  const double* d_table, int64_t table_len, const double* d_t1, void* d_out, int out_dtype, int64_t ldo, void* stream) {
+int nrm_lcpm_csr_passes_write(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz, int dev,
+							  const double* d_table, int64_t table_len, const double* d_t1, void* d_out, int out_dtype, int64_t ldo, void* stream) {
 	NRM_TRY(lcs_check("nrm_lcpm_csr_write", d_indptr, d_indices, d_data, dtype, rows, n, nnz));
 	NRM_REQUIRE(out_dtype == NRM_F32 || out_dtype == NRM_F64, "nrm_lcpm_csr_write: bad dtype");
 	NRM_REQUIRE(d_table && table_len > 0 && table_len <= LCS_TAB_CAP && d_out && ldo >= n, "nrm_lcpm_csr_write: bad arguments");
 	const bool al = (uintptr_t)d_out % 16 == 0 && (ldo * (out_dtype == NRM_F64 ? 8 : 4)) % 16 == 0 && (d_t1 == nullptr || (uintptr_t)d_t1 % 16 == 0);
-#define LCS_GO(TY) lcs_launch_write<TY>(d_indptr, d_indices, d_data, rows, n, nnz, d_table, table_len, d_t1, d_out, out_dtype, ldo, al, (hipStream_t)stream)
+#define LCS_GO(TY) lcs_launch_write<TY>(d_indptr, d_indices, d_data, rows, n, nnz, dev, d_table, table_len, d_t1, d_out, out_dtype, ldo, al, (hipStream_t)stream)
 	NRM_BY_COUNT_DTYPE(LCS_GO)
 #undef LCS_GO
 	return nrm_check_launch("k_lcs_write");
+}
+
+extern "C" int nrm_lcpm_csr_count(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
+								  int64_t* d_cell_total, int64_t* d_cell_nnz, int64_t* d_gene_zero, int64_t* d_info, int64_t* d_partial, void* stream) {
+	return nrm_lcpm_csr_passes_count(d_indptr, d_indices, d_data, dtype, rows, n, nnz, 0, d_cell_total, d_cell_nnz, d_gene_zero, d_info, d_partial, stream);
+}
+
+extern "C" int nrm_lcpm_csr_colsum(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
+								   const double* d_exp_table, int64_t table_len, double unit, const int64_t* d_cell_total, int64_t* d_partial, double* d_t1,
+								   void* stream) {
+	return nrm_lcpm_csr_passes_colsum(d_indptr, d_indices, d_data, dtype, rows, n, nnz, 0, d_exp_table, table_len, unit, nullptr, d_cell_total, d_partial, d_t1, stream);
+}
+
+extern "C" int nrm_lcpm_csr_write(const int64_t* d_indptr, const int32_t* d_indices, const void* d_data, int dtype, int64_t rows, int64_t n, int64_t nnz,
+								  const double* d_table, int64_t table_len, const double* d_t1, void* d_out, int out_dtype, int64_t ldo, void* stream) {
+	return nrm_lcpm_csr_passes_write(d_indptr, d_indices, d_data, dtype, rows, n, nnz, 0, d_table, table_len, d_t1, d_out, out_dtype, ldo, stream);
 }

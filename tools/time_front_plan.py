@@ -11,7 +11,15 @@ runs numpy and small copies between its launches, at 5000 genes x 10 000 cells i
 A child's figure is the median of its reps (ms per step); the record holds, per side, the rounds' figures, their median and min-max spread.  There is no verdict
 and no bar: the two numbers are compared within one run only.
 
-Usage: time_front_plan.py [--rounds 3] [--steps 20] [--reps 5] [--warmup 5] [--out profiles/front_plan.json]"""
+--csr: the plan on sparse counts (cplan.FrontPlanCSR, nrm_front_plan_create_csr) against the dense plan instead, neither child able to import torch, on the same
+counts (61 % zeros) and on a thinned matrix of the same shape with about 90 % zeros:
+
+  dense_plan  cplan.FrontPlan(out_dtype=float32) on each matrix, timed as c_plan is;
+  csr_plan    cplan.FrontPlanCSR(out_dtype=float32) on scipy.sparse.csr_matrix of each.
+
+The record (profiles/front_plan_csr.json) holds both sides per matrix, their spreads and info()['bytes'] of every plan.  No bar here either.
+
+Usage: time_front_plan.py [--csr] [--rounds 3] [--steps 20] [--reps 5] [--warmup 5] [--out profiles/front_plan.json | profiles/front_plan_csr.json]"""
 import json
 import os
 import sys
@@ -34,6 +42,55 @@ def problem():
 	x[0, x.sum(axis=0) == 0] = 1
 	batch = rng.integers(0, 4, N)
 	return x, (batch[None, :] == np.arange(4)[:, None]).astype(np.float64)
+
+
+def thinned(x, zeros=0.9):
+	"""x with stored entries dropped at random until about `zeros` of the matrix is zero; every cell keeps a read."""
+	rng = np.random.default_rng(SEED + 1)
+	keep = (1.0 - zeros) / (x != 0).mean()
+	y = np.where(rng.random(x.shape) < keep, x, 0).astype(x.dtype)
+	y[0, y.sum(axis=0) == 0] = 1
+	return y
+
+
+MATRICES = ('counts', 'thinned')
+
+
+def child_front(args, sparse):
+	"""FrontPlan (sparse=False) or FrontPlanCSR on both matrices: ms per step of every rep, info() and the share of stored entries, per matrix."""
+	sys.modules['torch'] = None  # `import torch` raises ImportError here
+	import scipy.sparse
+	from normalisr_amd import cplan
+	x, onehot = problem()
+	out = {}
+	for name, m in zip(MATRICES, (x, thinned(x))):
+		make = (lambda: cplan.FrontPlanCSR(scipy.sparse.csr_matrix(m), onehot, out_dtype=np.float32)) if sparse else (lambda: cplan.FrontPlan(m, onehot, out_dtype=np.float32))
+		with make() as plan:
+			for _ in range(args.warmup):
+				plan.step()
+			plan.check()
+			out[name] = [plan.time(args.steps) for _ in range(args.reps)]
+			plan.check()
+			out[name + '_info'] = plan.info()
+			out[name + '_stored'] = float((m != 0).mean())
+	assert sys.modules['torch'] is None
+	return out
+
+
+def main_csr(args):
+	ds, cs = pt.alternate(__file__, args, ('dense_plan', 'csr_plan'))
+	rec = dict(tool='time_front_plan --csr', shape=dict(genes=NG, cells=N, counts='int32', user_covariates=4, covariates=8, seed=SEED, out_dtype='float32'), rounds=args.rounds,
+			   steps=args.steps, reps=args.reps, warmup=args.warmup,
+			   what=dict(dense_plan='cplan.FrontPlan(out_dtype=float32).time: nrm_front_plan_time, one hipGraphLaunch per step, no torch in the process',
+						 csr_plan='cplan.FrontPlanCSR(out_dtype=float32).time on scipy.sparse.csr_matrix of the same counts: the same step with the CSR form of lcpm\'s three passes'),
+			   matrices={}, note='no bar: the two sides are compared within this run only')
+	for name in MATRICES:
+		d, c = pt.side(ds, name), pt.side(cs, name)
+		d['info'], c['info'] = ds[-1][name + '_info'], cs[-1][name + '_info']
+		rec['matrices'][name] = dict(stored_share=round(ds[-1][name + '_stored'], 4), dense_plan=d, csr_plan=c,
+									 spreads_ms=dict(dense_plan=round(d['max_ms'] - d['min_ms'], 4), csr_plan=round(c['max_ms'] - c['min_ms'], 4)),
+									 bytes=dict(dense_plan=d['info']['bytes'], csr_plan=c['info']['bytes']))
+	pt.write(rec, args.out)
 
 
 def child_yardstick(args):
@@ -79,10 +136,17 @@ def child_c_plan(args):
 
 
 def main():
-	args = pt.arg_parser('profiles/front_plan.json', 300).parse_args()
+	ap = pt.arg_parser('profiles/front_plan.json', 300)
+	ap.add_argument('--csr', action='store_true', help='FrontPlanCSR against FrontPlan on two matrices -> profiles/front_plan_csr.json')
+	args = ap.parse_args()
 	if args.child:
-		print(json.dumps(dict(yardstick=child_yardstick, c_plan=child_c_plan)[args.child](args)))
+		kinds = dict(yardstick=child_yardstick, c_plan=child_c_plan, dense_plan=lambda a: child_front(a, False), csr_plan=lambda a: child_front(a, True))
+		print(json.dumps(kinds[args.child](args)))
 		return
+	if args.csr:
+		if args.out == 'profiles/front_plan.json':
+			args.out = 'profiles/front_plan_csr.json'
+		return main_csr(args)
 	ys, cs = pt.alternate(__file__, args, ('yardstick', 'c_plan'))
 	y, c, c64 = pt.side(ys, 'ms_per_step'), pt.side(cs, 'ms_per_step'), pt.side(cs, 'ms_per_step_f64')
 	c['info'], c64['info'] = cs[-1]['info'], cs[-1]['info_f64']
