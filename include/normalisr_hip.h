@@ -891,6 +891,43 @@ int nrm_fitvar_weights(const double* d_best, int64_t n, double* d_ws, double* d_
 int nrm_fitvar_pinv_host(const double* m, int64_t n, double tol, double* inv, int64_t* rank);
 
 /*
+ * The inverse of one symmetric positive definite matrix on the device (csrc/nrm_chol_inverse.hip), replacing the pseudo-inverse of the weighted covariates' Gram
+ * matrix that compute_var takes per iteration (reference norm.py:100 through association.py:4-134) where an orthonormal basis of the covariates' row space makes
+ * that matrix positive definite (below).  Blocked right-looking Cholesky M = L L^T in block columns of 64, W = L^-1 block row by block row, N = W^T W; tile
+ * products on the fp64 matrix cores.  The launch sequence (4 ceil(r / 64) - 1 launches on the one stream) depends on r only, every element is one workgroup's sum
+ * in a fixed order (no floating-point atomics: the same bits every run and every graph replay), no workgroup waits for another.  1 <= r <= nrm_wide_covariates().
+ *   nrm_chol_inverse_workspace: doubles of d_ws for r; 0 outside 1 .. nrm_wide_covariates()
+ *   nrm_chol_inverse:      d_m (r, ldm) symmetric, row-major, read in full, not modified -> d_inv (r, ldi), the full symmetric inverse (inv[i][j] and inv[j][i] the
+ *       same bits).  The first failure of a call decides: a value of d_m or a pivot that is not finite, d_status[1] += 1; a pivot that is not positive,
+ *       d_status[0] += 1; in either case d_inv is written as zeros (every launch runs to its end: no loop depends on the data).
+ *   nrm_chol_inverse_host: the same blocked algorithm, block boundaries and status rules on host buffers, one thread (not the matrix cores' bits)
+ * NRM_E_ARG for r, a pitch or a pointer, before any device call.
+ */
+int64_t nrm_chol_inverse_workspace(int64_t r);
+int nrm_chol_inverse(const double* d_m, int64_t ldm, int64_t r, double* d_inv, int64_t ldi, double* d_ws, int32_t* d_status /* int32[2] */, void* stream);
+int nrm_chol_inverse_host(const double* m, int64_t ldm, int64_t r, double* inv, int64_t ldi, int32_t* status /* int32[2] */);
+
+/*
+ * compute_var's iteration with 64 .. nrm_wide_covariates() covariates and nothing on the host (norm.ComputeVarPlan; csrc/nrm_fitvar_plan.hip), replacing
+ * reference norm.py:99-100 and norm.py:109-110.  The caller gives orthonormal bases B (r, n) of the covariates' row space and B1 (r1, n) of span([C;1])
+ * (normalisr_amd/norm.py: _fitvar_bases).  B diag(u) spans what C diag(u) spans, so the first regression is nrm_fitvar_moments / genes / cells with d_c = B,
+ * nc = r and d_mi = the inverse of M = (B u)(B u)^T from nrm_gram_f64_whole and nrm_chol_inverse; the second is the projection B1^T (B1 l).  State records, the
+ * stop rule and d_flags as for the entries above; d_ws: nrm_fitvar_wide_workspace doubles, the same block for every call of one plan.
+ *   nrm_fitvar_wide_workspace: 0 for sizes the two entries do not take (n <= r, r > nrm_wide_covariates(), r1 > nrm_wide_covariates() + 1)
+ *   nrm_fitvar_wide_design:  d_u = 1 / d_s, d_bu (rows_pad, ldbu) = B u with rows r .. rows_pad and cells n .. ldbu zero (rows_pad a multiple of 128, ldbu of 16:
+ *       the operand of nrm_gram_f64_whole), d_cw (r, n) = (B u) u: each one rounded operation, in the order of nrm_fitvar_design.  kappa = (max u / min u)^2 from
+ *       per-chunk extrema; d_flags[2] += 1 when !(hi >= safety tol kappa && (full || lo < tol / (safety kappa))): no certificate that the reference's rank rule
+ *       (association.py:77-80) keeps exactly the r directions of B for these weights (hi, lo: eigenvalues r and r + 1 of C C^T over the largest; full: r == nc).
+ *   nrm_fitvar_wide_update:  after nrm_fitvar_cells: l = log sqrt v, coef = B1 l (per-chunk partial sums added in order), new = exp(B1^T coef) s, then as
+ *       nrm_fitvar_update (norm.py:109-120).  The coefficients stay at d_ws + 2 ceil(n / 256) + ceil(n / 1024) r1 (tests).
+ */
+int64_t nrm_fitvar_wide_workspace(int64_t n, int64_t r, int64_t r1);
+int nrm_fitvar_wide_design(const double* d_b, int64_t r, int64_t ldb, int64_t n, const double* d_s, const double* d_state, double eps, double hi, double lo, double tol,
+						   double safety, int full, double* d_u, double* d_bu, int64_t rows_pad, int64_t ldbu, double* d_cw, double* d_ws, int32_t* d_flags, void* stream);
+int nrm_fitvar_wide_update(const double* d_v, const double* d_b1, int64_t r1, int64_t ldb1, int64_t n, double* d_s, double* d_best, const double* d_state,
+						   double* d_state_next, double eps, double* d_ws, void* stream);
+
+/*
  * The front half of the pipeline as WHOLE-PROBLEM entries (csrc/nrm_host_front.hip): HOST buffers in, HOST buffers out, no torch -- the kernels above, sequenced
  * as normalisr_amd/lcpm.py, norm.py and qc.py sequence them, uploads and scratch inside the library.  One call at a time per process, on the device of
  * nrm_set_device.  Every argument is checked before any device call; the messages are the reference's.  The host arithmetic is csrc/nrm_host_math.h.

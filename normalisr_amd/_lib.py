@@ -169,6 +169,12 @@ _SIGNATURES = {
 	'nrm_fitvar_update': ([_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp], _i32),
 	'nrm_fitvar_weights': ([_vp, _i64, _vp, _vp, _vp, _vp], _i32),
 	'nrm_fitvar_pinv_host': ([_vp, _i64, _dbl, _vp, _vp], _i32),
+	'nrm_chol_inverse_workspace': ([_i64], _i64),
+	'nrm_chol_inverse': ([_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp], _i32),
+	'nrm_chol_inverse_host': ([_vp, _i64, _i64, _vp, _i64, _vp], _i32),
+	'nrm_fitvar_wide_workspace': ([_i64, _i64, _i64], _i64),
+	'nrm_fitvar_wide_design': ([_vp, _i64, _i64, _i64, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
+	'nrm_fitvar_wide_update': ([_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _dbl, _vp, _vp], _i32),
 	'nrm_lcpm_host': ([_vp, _i32, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp], _i32),
 	'nrm_lcpm_csr_host': ([_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp], _i32),
 	'nrm_compute_var_host': ([_vp, _i32, _i64, _i64, _vp, _i64, _i64, _dbl, _vp, _vp], _i32),

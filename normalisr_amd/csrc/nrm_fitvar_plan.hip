@@ -310,6 +310,158 @@ extern "C" int nrm_fitvar_weights(const double* d_best, int64_t n, double* d_ws,
 	return nrm_check_launch("k_fvp_w");
 }
 
+// ---- 64 .. nrm_wide_covariates() covariates: the iteration on an orthonormal basis B (r, n) of the covariates' row space (normalisr_amd/norm.py: _fitvar_bases) ----
+// B diag(u) spans what C diag(u) spans, so the first regression's fitted values are those on B u, and M = (B u)(B u)^T is positive definite with condition
+// <= (u_max / u_min)^2: nrm_gram_f64_whole and nrm_chol_inverse (csrc/nrm_chol_inverse.hip) take the place of k_fvp_design's triangles and k_fvp_pinv.  That M has the
+// rank the reference's rule gives C diag(u^2) C^T is certified as in norm._wide_basis, here, because u is known here only: flags[2] counts the iterations without it.
+// The second regression is the projection B1^T (B1 l) on an orthonormal basis B1 (r1, n) of span([C;1]).
+//   k_fvw_design   u = 1 / s, Bu = B u into the Gram kernel's padded operand (rows to 128, cells to 16, padding zero), cw = Bu u; a chunk's extrema of u
+//   k_fvw_cert     kappa from the chunks' extrema in order; flags[2] += !(hi >= safety tol kappa && (full || lo < tol / (safety kappa)))
+//   k_fvw_logsum   l = log sqrt v, per chunk of FVP_LCH cells the partial sums of B1 l
+//   k_fvw_coef     coef = the chunks added in order
+//   k_fvw_new      new = exp(coef^T B1_k) s_k, the workgroup's minimum;  then k_fvp_apply and k_fvp_state as above
+#define FVW_ROWS 16  // rows of Bu per workgroup of the design pass
+
+__global__ void __launch_bounds__(256) k_fvw_design(const double* __restrict__ b, int r, int64_t ldb, int64_t n, int rows_pad, int64_t kp, const double* __restrict__ s,
+													 const double* __restrict__ state, double eps, double* __restrict__ u, double* __restrict__ bu, double* __restrict__ cw,
+													 double* __restrict__ umin, double* __restrict__ umax) {
+	__shared__ double sm[4];
+	if (fvp_stopped(state, eps)) return;
+	const int64_t k = (int64_t)blockIdx.x * FVP_CH + threadIdx.x;
+	const double uk = k < n ? 1.0 / s[k] : 0.0;
+	const int r0 = blockIdx.y * FVW_ROWS;
+	if (k < kp)
+		for (int q = r0; q < r0 + FVW_ROWS && q < rows_pad; q++) {
+			double v = 0.0;
+			if (q < r && k < n) {
+				v = b[(int64_t)q * ldb + k] * uk;
+				cw[(int64_t)q * n + k] = v * uk;
+			}
+			bu[(int64_t)q * kp + k] = v;
+		}
+	if (blockIdx.y == 0 && (int64_t)blockIdx.x * FVP_CH < n) {  // (a chunk of padding cells only has no extrema)
+		if (k < n) u[k] = uk;
+		const double lo = fvp_block_ext<false>(k < n ? uk : __longlong_as_double(0x7ff0000000000000LL), sm);
+		const double hi = fvp_block_ext<true>(k < n ? uk : 0.0, sm);
+		if (threadIdx.x == 0) umin[blockIdx.x] = lo, umax[blockIdx.x] = hi;
+	}
+}
+
+__global__ void __launch_bounds__(256) k_fvw_cert(int64_t blocks, const double* __restrict__ umin, const double* __restrict__ umax, const double* __restrict__ state, double eps,
+												   double hi, double lo, double tol, double safety, int full, int32_t* __restrict__ flags) {
+	__shared__ double sm[4];
+	if (fvp_stopped(state, eps)) return;
+	const double a = fvp_all_ext<false>(umin, blocks, sm), z = fvp_all_ext<true>(umax, blocks, sm);
+	const double kappa = (z / a) * (z / a);
+	if (threadIdx.x == 0 && !(hi >= safety * tol * kappa && (full || lo < tol / (safety * kappa)))) flags[2] += 1;
+}
+
+__global__ void __launch_bounds__(256) k_fvw_logsum(const double* __restrict__ v, const double* __restrict__ b1, int r1, int64_t ldb1, int64_t n, const double* __restrict__ state,
+													 double eps, double* __restrict__ gpart) {
+	__shared__ double sl[FVP_LCH];
+	if (fvp_stopped(state, eps)) return;
+	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+	const int64_t k0 = (int64_t)blockIdx.x * FVP_LCH;
+	for (int j = tid; j < FVP_LCH; j += 256) sl[j] = k0 + j < n ? log(sqrt(v[k0 + j])) : 0.0;
+	__syncthreads();
+	for (int q = wid; q < r1; q += 4) {
+		double t = 0.0;
+		for (int j = lane; j < FVP_LCH; j += 64)
+			if (k0 + j < n) t = fma(b1[(int64_t)q * ldb1 + k0 + j], sl[j], t);
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
+		if (lane == 0) gpart[(int64_t)blockIdx.x * r1 + q] = t;
+	}
+}
+
+__global__ void __launch_bounds__(256) k_fvw_coef(const double* __restrict__ gpart, int64_t lchunks, int r1, const double* __restrict__ state, double eps, double* __restrict__ coef) {
+	if (fvp_stopped(state, eps)) return;
+	const int q = blockIdx.x * 256 + threadIdx.x;
+	if (q < r1) {
+		double t = 0.0;
+		for (int64_t c = 0; c < lchunks; c++) t += gpart[c * r1 + q];
+		coef[q] = t;
+	}
+}
+
+__global__ void __launch_bounds__(256) k_fvw_new(const double* __restrict__ coef, const double* __restrict__ b1, int r1, int64_t ldb1, int64_t n, const double* __restrict__ s,
+												  const double* __restrict__ state, double eps, double* __restrict__ snew, double* __restrict__ minpart) {
+	__shared__ double cf[NRM_WIDE_NC + 1], sm[4];
+	if (fvp_stopped(state, eps)) return;
+	for (int q = threadIdx.x; q < r1; q += 256) cf[q] = coef[q];
+	__syncthreads();
+	const int64_t k = (int64_t)blockIdx.x * FVP_CH + threadIdx.x;
+	double nv = __longlong_as_double(0x7ff0000000000000LL);  // (+inf: cells beyond n do not count in the minimum)
+	if (k < n) {
+		double f = 0.0;
+		for (int q = 0; q < r1; q++) f = fma(cf[q], b1[(int64_t)q * ldb1 + k], f);
+		nv = exp(f) * s[k];
+		snew[k] = nv;
+	}
+	nv = fvp_block_ext<false>(nv, sm);
+	if (threadIdx.x == 0) minpart[blockIdx.x] = nv;
+}
+
+// the scratch of the two wide entries, in doubles: the chunks' extrema of u | the chunks' B1 l | coef | a minimum and a maximum per workgroup | the new scale
+struct FvwScratch {
+	int64_t blocks, lchunks;
+	double *umin, *umax, *gpart, *coef, *minpart, *maxpart, *snew;
+	int64_t doubles;
+	FvwScratch(int64_t n, int64_t r1, double* ws) {
+		blocks = (n + FVP_CH - 1) / FVP_CH;
+		lchunks = (n + FVP_LCH - 1) / FVP_LCH;
+		umin = ws;
+		umax = umin + blocks;
+		gpart = umax + blocks;
+		coef = gpart + lchunks * r1;
+		minpart = coef + r1;
+		maxpart = minpart + blocks;
+		snew = maxpart + blocks;
+		doubles = (snew + n) - ws;
+	}
+};
+
+static bool fvw_sizes(int64_t n, int64_t r, int64_t r1) { return n > 0 && n <= (int64_t)FVP_CH * 0x7fffffff && r >= 1 && r <= NRM_WIDE_NC && r1 >= 1 && r1 <= NRM_WIDE_NC + 1 && n > r; }
+
+extern "C" int64_t nrm_fitvar_wide_workspace(int64_t n, int64_t r, int64_t r1) {
+	if (!fvw_sizes(n, r, r1)) return 0;
+	return FvwScratch(n, r1, nullptr).doubles;
+}
+
+extern "C" int nrm_fitvar_wide_design(const double* d_b, int64_t r, int64_t ldb, int64_t n, const double* d_s, const double* d_state, double eps, double hi, double lo, double tol,
+									  double safety, int full, double* d_u, double* d_bu, int64_t rows_pad, int64_t ldbu, double* d_cw, double* d_ws, int32_t* d_flags,
+									  void* stream) {
+	NRM_REQUIRE(fvw_sizes(n, r, 1), "nrm_fitvar_wide_design: 1 to %d basis rows on more cells than rows", NRM_WIDE_NC);
+	NRM_REQUIRE(d_b && d_s && d_state && d_u && d_bu && d_cw && d_ws && d_flags && ldb >= n, "nrm_fitvar_wide_design: bad argument");
+	NRM_REQUIRE(rows_pad >= r && rows_pad % 128 == 0 && ldbu >= n && ldbu % 16 == 0, "nrm_fitvar_wide_design: Bu must be padded to 128 rows and 16 cells");
+	NRM_REQUIRE(tol > 0 && safety >= 1 && hi > 0 && lo >= 0, "nrm_fitvar_wide_design: bad certificate");
+	const FvwScratch w(n, 1, d_ws);
+	hipStream_t st = (hipStream_t)stream;
+	const dim3 grid((unsigned)((ldbu + FVP_CH - 1) / FVP_CH), (unsigned)((rows_pad + FVW_ROWS - 1) / FVW_ROWS));
+	hipLaunchKernelGGL(k_fvw_design, grid, dim3(256), 0, st, d_b, (int)r, ldb, n, (int)rows_pad, ldbu, d_s, d_state, eps, d_u, d_bu, d_cw, w.umin, w.umax);
+	NRM_TRY(nrm_check_launch("k_fvw_design"));
+	hipLaunchKernelGGL(k_fvw_cert, dim3(1), dim3(256), 0, st, w.blocks, w.umin, w.umax, d_state, eps, hi, lo, tol, safety, full, d_flags);
+	return nrm_check_launch("k_fvw_cert");
+}
+
+extern "C" int nrm_fitvar_wide_update(const double* d_v, const double* d_b1, int64_t r1, int64_t ldb1, int64_t n, double* d_s, double* d_best, const double* d_state,
+									  double* d_state_next, double eps, double* d_ws, void* stream) {
+	NRM_REQUIRE(fvw_sizes(n, 1, r1) && n >= r1, "nrm_fitvar_wide_update: 1 to %d basis rows on at least as many cells", NRM_WIDE_NC + 1);
+	NRM_REQUIRE(d_v && d_b1 && d_s && d_best && d_state && d_state_next && d_state != d_state_next && d_ws && ldb1 >= n, "nrm_fitvar_wide_update: bad argument");
+	const FvwScratch w(n, r1, d_ws);
+	hipStream_t st = (hipStream_t)stream;
+	hipLaunchKernelGGL(k_fvw_logsum, dim3((unsigned)w.lchunks), dim3(256), 0, st, d_v, d_b1, (int)r1, ldb1, n, d_state, eps, w.gpart);
+	NRM_TRY(nrm_check_launch("k_fvw_logsum"));
+	hipLaunchKernelGGL(k_fvw_coef, dim3((unsigned)((r1 + 255) / 256)), dim3(256), 0, st, w.gpart, w.lchunks, (int)r1, d_state, eps, w.coef);
+	NRM_TRY(nrm_check_launch("k_fvw_coef"));
+	hipLaunchKernelGGL(k_fvw_new, dim3((unsigned)w.blocks), dim3(256), 0, st, w.coef, d_b1, (int)r1, ldb1, n, d_s, d_state, eps, w.snew, w.minpart);
+	NRM_TRY(nrm_check_launch("k_fvw_new"));
+	hipLaunchKernelGGL(k_fvp_apply, dim3((unsigned)w.blocks), dim3(256), 0, st, n, w.blocks, d_s, d_state, eps, w.snew, w.minpart, w.maxpart);
+	NRM_TRY(nrm_check_launch("k_fvp_apply"));
+	hipLaunchKernelGGL(k_fvp_state, dim3((unsigned)w.blocks), dim3(256), 0, st, n, w.blocks, w.snew, w.maxpart, d_state, eps, d_s, d_best, d_state_next);
+	return nrm_check_launch("k_fvp_state");
+}
+
 extern "C" int nrm_fitvar_pinv_host(const double* m, int64_t n, double tol, double* inv, int64_t* rank) {
 	NRM_REQUIRE(m && inv && rank && n >= 1 && n <= FVP_NC + 1 && tol > 0, "nrm_fitvar_pinv_host: bad argument");
 	const int nn = (int)n;

@@ -184,6 +184,36 @@ def _wide_basis(dc, w, wt, tol=1E-8, safety=WIDE_SAFETY):
 	return b, r, certified, (hi, lo, kappa)
 
 
+def _fitvar_bases(dc, tol=1E-8):
+	"""(B, r, hi, lo, B1) for ComputeVarPlan with many covariates.  B (r, n_cell) as in _wide_basis, from the eigen-decomposition of dc dc^T with r by the rule of
+	inv_rank on that matrix -- the rank inv_rank(cu cu^T) gives at u = 1 -- and hi = lambda_r / lambda_1, lo = lambda_{r+1} / lambda_1 (0 for r = n_cov): what the
+	rank certificate of _wide_basis needs beside kappa = (u_max / u_min)^2, which only the device knows (nrm_fitvar_wide_design evaluates it per iteration).
+	B1 (r1, n_cell): an orthonormal basis of the directions of [dc; 1] that _pinv_gram_unit_rows keeps (the Gram matrix of the rows scaled to unit length, the rule
+	of inv_rank on it), so that B1^T B1 is the projector of the second regression, c1^T _pinv_gram_unit_rows(c1) c1."""
+	c64 = np.asarray(dc, dtype=np.float64)
+	nc, ns = c64.shape
+	lam, u = np.linalg.eigh(np.matmul(c64, c64.T))
+	lam, u = lam[::-1], u[:, ::-1]
+	assert np.isfinite(lam).all() and lam[0] > 0  # (the reference: 0 / 0 in inv_rank for covariates that are all zero, infs or NaNs refused)
+	r = int((lam >= tol * lam[0]).sum())
+	hi = float(lam[r - 1] / lam[0])
+	lo = float(max(lam[r], 0.0) / lam[0]) if r < nc else 0.0
+	b = (u[:, :r] / np.sqrt(lam[:r])).T @ c64
+	c1 = np.concatenate([c64, np.ones((1, ns))], axis=0)
+	d = np.sqrt(np.einsum('ij,ij->i', c1, c1))
+	xs = c1 * (1 / np.where(d > 0, d, 1.0))[:, None]
+	lam1, u1 = np.linalg.eigh(np.matmul(xs, xs.T))
+	lam1, u1 = lam1[::-1], u1[:, ::-1]
+	r1 = int((lam1 >= tol * lam1[0]).sum())
+	b1 = (u1[:, :r1] / np.sqrt(lam1[:r1])).T @ xs
+	return b, r, hi, lo, b1
+
+
+def _fitvar_certified(hi, lo, full, kappa, tol=1E-8, safety=WIDE_SAFETY):
+	"""The rank certificate of _wide_basis for weights of spread kappa = (u_max / u_min)^2 (nrm_fitvar_wide_design holds the same expression)."""
+	return bool(hi >= safety * tol * kappa and (full or lo < tol / (safety * kappa)))
+
+
 def _normvar_wide_reference(dt, dc, w, wt, keepvar, tol=1E-8):
 	"""The reference's per-gene algorithm (norm.py:150-163,244-259) in host numpy with inv_rank: one (nc, nc) pseudo-inverse per gene.  What normvar does for
 	covariates without the certificate of _wide_basis -- slow, and the reference's answer."""
@@ -673,6 +703,11 @@ class ComputeVarPlan:
 	small state record in HBM.  A step enqueues all stepmax iterations and the weights; no kernel waits for the host and the host decides nothing, so a step is ONE
 	HIP graph from the second on and that graph stays valid when dt is rewritten in place.  Iterations enqueued past the stop condition leave the state as it is.
 	The covariates' upload, the pseudo-inverse of [dc;1][dc;1]^T (host inv_rank: it does not depend on dt) and every buffer are made once, here.
+	64 to nrm_wide_covariates() covariates (with more cells than covariates): orthonormal bases of the covariates' row space and of span(dc, 1) are made once on
+	the host (_fitvar_bases) and stand in for the covariates; an iteration's matrix (B u)(B u)^T is then positive definite, formed on the fp64 matrix cores
+	(nrm_gram_f64_whole) and inverted by a blocked Cholesky inverse spread over the chip (csrc/nrm_chol_inverse.hip) -- no eigen-decomposition on the device, one
+	stream, one graph.  That the basis keeps the directions the reference's rank rule keeps is certified as in _wide_basis: at creation for equal weights
+	(NotImplementedError otherwise), per iteration on the device for the weights as they are (check() raises NotImplementedError: compute_var() is then the call).
 	check() reads the counters of the steps since the last check and raises what compute_var raises (norm.py:125-127); results() returns the weights as compute_var
 	does and sets steps_taken (iterations that ran) and best_change (the smallest maximum relative change of the scale, the reference's bestv)."""
 
@@ -688,10 +723,21 @@ class ComputeVarPlan:
 			raise ValueError('dt and dc must have the same cell count.')
 		nt, ns = shape
 		nc = dc.shape[0]
-		if nc == 0 or nc > 63:
-			raise NotImplementedError('compute_var on the device takes 1 to 63 covariates.')
+		if nc == 0:
+			raise NotImplementedError('compute_var on the device takes at least one covariate.')
+		self.wide = nc > 63
+		if self.wide:
+			_check_wide('compute_var', nc, ns)
 		if nt == 0 or ns == 0:
 			raise ValueError('dt must not be empty.')
+		if self.wide:
+			# the bases of _fitvar_bases in the place of the covariates; refused when the rank certificate fails already for equal weights (nearly collinear
+			# covariates: an eigenvalue of dc dc^T inside the band around the rank rule's tolerance) -- host numpy, before any device call
+			b, r, hi, lo, b1 = self._bases = _fitvar_bases(dc)
+			self.rank, self._cert = r, (hi, lo, 1E-8, WIDE_SAFETY, 1 if r == nc else 0)
+			if not _fitvar_certified(hi, lo, r == nc, 1.0):
+				raise NotImplementedError('ComputeVarPlan beyond 63 covariates needs covariates whose rank is certain: eigenvalue {} of dc dc^T is {:.3g} of the largest, the '
+										  'next {:.3g}, around the rank rule\'s 1e-8.  compute_var() is the call for these covariates.'.format(r, hi, lo))
 		if not _engine.is_dev(dt):
 			raise ValueError('ComputeVarPlan takes a logCPM matrix resident in HBM (a torch CUDA tensor); compute_var() is the call for host arrays.')
 		self.eng = eng = eng or _engine.get_engine(dt.device.index)
@@ -700,10 +746,13 @@ class ComputeVarPlan:
 			raise ValueError('ComputeVarPlan takes an fp32 or fp64 matrix with unit column stride.')
 		self.dt, self.stepmax, self.eps = dt, int(stepmax), float(eps)
 		self.dc = c64 = np.array(dc, dtype=np.float64, order='C')
-		c1 = np.concatenate([c64, np.ones((1, ns))], axis=0)  # the second regression has an intercept (norm.py:92,109-110)
-		m2i = _pinv_gram_unit_rows(c1)
 		self.steps_taken = self.best_change = None
 		self._graph = StepGraph(torch)
+		if self.wide:
+			self._init_wide(nt, ns)
+			return
+		c1 = np.concatenate([c64, np.ones((1, ns))], axis=0)  # the second regression has an intercept (norm.py:92,109-110)
+		m2i = _pinv_gram_unit_rows(c1)
 		with eng.lock, torch.cuda.device(eng.device):
 			f64 = dict(dtype=torch.float64, device=eng.device)
 			self._c, self._m2i = eng.upload(c64), eng.upload(np.ascontiguousarray(m2i, dtype=np.float64))
@@ -720,8 +769,56 @@ class ComputeVarPlan:
 			self.w = self._out[4 * (self.stepmax + 1):]
 			self._flags = eng.zeros((4, ), torch.int32)
 
+	def _init_wide(self, nt, ns):
+		"""64 .. nrm_wide_covariates() covariates: the bases uploaded once, and every buffer of a step."""
+		eng, torch, lib = self.eng, self.eng.torch, self.eng.lib
+		b, r, hi, lo, b1 = self._bases
+		del self._bases
+		r1 = b1.shape[0]
+		rp, kp = _engine.round_up(r, ROW_TILE), _engine.round_up(ns, K_TILE)
+		with eng.lock, torch.cuda.device(eng.device):
+			f64 = dict(dtype=torch.float64, device=eng.device)
+			self._c, self._b1 = eng.upload(np.ascontiguousarray(b)), eng.upload(np.ascontiguousarray(b1))
+			self._a, self._b = torch.empty((nt, r), **f64), torch.empty((nt, r), **f64)
+			self._mean, self._sc, self._v = torch.empty((nt, ), **f64), torch.empty((nt, ), **f64), torch.empty((ns, ), **f64)
+			self._part = torch.empty((-(-nt // int(lib.nrm_fitvar_row_tile())), ns), **f64)
+			self._s, self._best, self._u = torch.empty((ns, ), **f64), torch.empty((ns, ), **f64), torch.empty((ns, ), **f64)
+			self._cw, self._mi = torch.empty((r, ns), **f64), torch.empty((r, r), **f64)
+			self._bu, self._m = torch.empty((rp, kp), **f64), torch.empty((rp, rp), **f64)
+			self._ws = torch.empty((int(lib.nrm_fitvar_wide_workspace(ns, r, r1)), ), **f64)
+			self._ciws = torch.empty((int(lib.nrm_chol_inverse_workspace(r)), ), **f64)
+			self._out = torch.empty((4 * (self.stepmax + 1) + ns, ), **f64)
+			self._state = self._out[:4 * (self.stepmax + 1)].view(self.stepmax + 1, 4)
+			self.w = self._out[4 * (self.stepmax + 1):]
+			self._flags = eng.zeros((8, ), torch.int32)  # [0], [1] as below; [2] iterations without the rank certificate; [3], [4] nrm_chol_inverse's status
+
+	def _launch_wide(self):
+		eng, y, lib = self.eng, self.dt, self.eng.lib
+		nt, ns = y.shape
+		r, r1 = self._c.shape[0], self._b1.shape[0]
+		rp, kp = self._bu.shape
+		ycode = _engine.dtype_code(y)
+		st, p = eng._stream(), lambda t: t.data_ptr()
+		hi, lo, tol, safety, full = self._cert
+		_lib.check(lib.nrm_fitvar_plan_start(ns, p(self._s), p(self._best), p(self._state[0]), st))
+		for i in range(self.stepmax):
+			now, nxt = p(self._state[i]), p(self._state[i + 1])
+			_lib.check(lib.nrm_fitvar_wide_design(p(self._c), r, self._c.stride(0), ns, p(self._s), now, self.eps, hi, lo, tol, safety, full, p(self._u), p(self._bu), rp, kp,
+												  p(self._cw), p(self._ws), p(self._flags), st))
+			_lib.check(lib.nrm_gram_f64_whole(p(self._bu), p(self._bu), rp, rp, kp, kp, kp, p(self._m), rp, r, r, st))
+			_lib.check(lib.nrm_chol_inverse(p(self._m), rp, r, p(self._mi), r, p(self._ciws), p(self._flags) + 12, st))
+			_lib.check(lib.nrm_fitvar_moments(p(y), ycode, nt, ns, y.stride(0), p(self._cw), r, self._cw.stride(0), p(self._a), st))
+			_lib.check(lib.nrm_fitvar_genes(p(y), ycode, nt, ns, y.stride(0), p(self._u), p(self._c), r, self._c.stride(0), p(self._a), p(self._mi), p(self._b), p(self._mean),
+											p(self._sc), p(self._flags), st))
+			_lib.check(lib.nrm_fitvar_cells(p(y), ycode, nt, ns, y.stride(0), p(self._u), p(self._c), r, self._c.stride(0), p(self._b), p(self._mean), p(self._sc), p(self._part),
+											p(self._v), st))
+			_lib.check(lib.nrm_fitvar_wide_update(p(self._v), p(self._b1), r1, self._b1.stride(0), ns, p(self._s), p(self._best), now, nxt, self.eps, p(self._ws), st))
+		_lib.check(lib.nrm_fitvar_weights(p(self._best), ns, p(self._ws), p(self.w), p(self._flags), st))
+
 	def _launch(self):
 		# (the C library's twin on its own buffers: NrmFitvarStep::enqueue, csrc/nrm_fitvar_step.h)
+		if self.wide:
+			return self._launch_wide()
 		eng, y, lib = self.eng, self.dt, self.eng.lib
 		nt, ns = y.shape
 		nc = self.dc.shape[0]
@@ -754,6 +851,10 @@ class ComputeVarPlan:
 			f = self._flags.cpu().numpy()
 			self._flags.zero_()
 		assert not f[0]  # a gene whose residual is constant: its spread divides (norm.py:108), the result is not finite (norm.py:125)
+		if self.wide and f[2]:
+			raise NotImplementedError('ComputeVarPlan: {} iteration(s) ran with cell weights too far apart for the rank certificate of the covariates\' basis; compute_var() is '
+									  'the call for these weights.'.format(int(f[2])))
+		assert not (self.wide and (f[3] or f[4]))  # nrm_chol_inverse: a pivot that is not positive, a value that is not finite
 		assert not f[1]  # weights finite and positive (norm.py:126-127), `best is not None` (norm.py:122)
 		return True
 
