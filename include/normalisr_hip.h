@@ -193,6 +193,9 @@ int nrm_pvalue_plan_fill_many(const double* dof, int64_t count, double* out, int
 
 /* Elementwise p-values from R^2 (device arrays); kernel-level entry for the table tests. */
 int nrm_pvalues_from_r2(const double* d_r2, int64_t count, double dof, double* d_p, void* stream);
+/* The same for ln p (csrc/nrm_pvalue.h: nrm_logpvalue): finite for every 0 < fl(1 - R^2) < 1, whatever dof and R^2 -- at 100 000 cells an
+ * R^2 of 0.0022 has ln p = -110, and every R^2 >= 1/4 a p that is 0 in double precision --, 0 where p = 1, -inf where fl(1 - R^2) <= 0. */
+int nrm_logpvalues_from_r2(const double* d_r2, int64_t count, double dof, double* d_lnp, void* stream);
 
 /*
  * K3 -- per-pair sweep: R^2 = dot^2/(ssx_i ssy_j) -> p-value, effect size, optional Pearson r and t.
@@ -231,6 +234,24 @@ int nrm_assoc_sweep_band(const double* d_dot, int64_t ldd, const double* d_ssx, 
 int nrm_assoc_sweep_mirror(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t mx, int64_t my,
 						   int64_t n_cells, double dof, void* d_p, void* d_stat, int out_dtype, int64_t ldo, int64_t r0, int64_t c0,
 						   int32_t* d_flags, int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol, void* stream);
+
+/* The three sweeps with the form of their first result as an argument: p_kind 0 = p (the entries above, which forward here), 1 = ln p,
+ * rounded once to out_dtype.  ln p = 0 where p = 1, -inf exactly where p is a 0 that is no underflow (fl(1 - R^2) <= 0, and the diagonal of a
+ * symmetric problem), finite for every other pair; NaN propagates and d_flags[0], [1] count as for p.  Everything else a sweep writes is the
+ * same bytes for either p_kind (of a whole call: unless the guard below certifies it in one form and not in the other -- nrm_association_tests_host_pk).  The guard of the integer engine (fix_nslices != 0) in this form: a pair is uncertified when the bound on
+ * |d ln p| exceeds guard_tol * max(1, |ln p|), and only pairs with fl(1 - R^2) <= 0 are exempt (csrc/nrm_fix.h). */
+int nrm_assoc_sweep_pk(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy,
+					   int64_t nx, int64_t ny, int64_t n_cells, double dof, int symmetric, int stat_kind,
+					   void* d_p, void* d_stat, void* d_r, void* d_t, int out_dtype, int64_t ldo,
+					   int32_t* d_flags, int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol, int p_kind, void* stream);
+int nrm_assoc_sweep_band_pk(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy,
+							int64_t nx, int64_t ny, int64_t n_cells, double dof, int symmetric, int stat_kind,
+							void* d_p, void* d_stat, void* d_r, void* d_t, int out_dtype, int64_t ldo,
+							int32_t* d_flags, int64_t row0, int64_t row1, int fix_nslices, const double* d_fixx, const double* d_fixy,
+							double guard_tol, int p_kind, void* stream);
+int nrm_assoc_sweep_mirror_pk(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t mx, int64_t my,
+							  int64_t n_cells, double dof, void* d_p, void* d_stat, int out_dtype, int64_t ldo, int64_t r0, int64_t c0,
+							  int32_t* d_flags, int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol, int p_kind, void* stream);
 
 /*
  * alpha[i,j,c] = by[j,c] - gamma[i,j] * bx[i,c]  (association.py:238-243), fp64 coefficients in, out_dtype out.
@@ -280,6 +301,10 @@ int nrm_de_small_sweep(const double* d_g, const double* d_ssraw, const double* d
 					   int64_t nx, int64_t ny, int64_t n_cells, double dof, int stat_kind, void* d_p, void* d_stat, void* d_r,
 					   void* d_t, int out_dtype, int64_t ldo, double* d_ssy, double* d_by, int32_t* d_flags,
 					   int const_last /* as above: covariate nc-1 in column 31, the design rows from column nc-1 on */, void* stream);
+/* The same with p_kind (0 = p, 1 = ln p in d_p: nrm_assoc_sweep_pk above). */
+int nrm_de_small_sweep_pk(const double* d_g, const double* d_ssraw, const double* d_dci, int64_t nc, int rank, const double* d_ssx,
+						  int64_t nx, int64_t ny, int64_t n_cells, double dof, int stat_kind, void* d_p, void* d_stat, void* d_r,
+						  void* d_t, int out_dtype, int64_t ldo, double* d_ssy, double* d_by, int32_t* d_flags, int const_last, int p_kind, void* stream);
 
 /*
  * single=4 sweep (competition-aware DE, association.py:421-576 in closed form).
@@ -515,6 +540,16 @@ int nrm_association_tests_host(const void* h_dx, int x_dtype, int64_t nx,
 							   const double* h_dci, int rank, int dimreduce, int return_dot,
 							   void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary,
 							   void* h_r, void* h_t, int out_dtype);
+/* The same with p_kind: 1 writes ln p into h_p (nrm_assoc_sweep_pk above) on every route the entry takes -- dense, streaming de, sparse design,
+ * the fp64 rerun after a guard hit; 0 is nrm_association_tests_host.  When the integer pass is not certified for ln P, ln P comes from the fp64 pass and
+ * the other results from the call with p_kind 0, its own rerun included (up to four passes).  A call certified for ln P but not for P keeps the integer
+ * engine's other results, where p_kind 0 returns the fp64 kernel's (1e-13 apart): the one case in which they are not the same bytes. */
+int nrm_association_tests_host_pk(const void* h_dx, int x_dtype, int64_t nx,
+								  const void* h_dy, int y_dtype, int64_t ny,
+								  const void* h_dc, int c_dtype, int64_t nc, int64_t n_cells,
+								  const double* h_dci, int rank, int dimreduce, int return_dot,
+								  void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary,
+								  void* h_r, void* h_t, int out_dtype, int p_kind);
 
 /* (Round 5) nrm_association_tests_host streams the raw expression rows (nrm_gram_skinny, as the Python engine does) when dy is given and nx + nc <= 32 --
  * case-control DE, BASELINE configs[2]; NRM_DEBUG="de_path=general" keeps K1 + K2 -- and takes the sparse-design path below by itself when dy is given and the design matrix qualifies -- at most

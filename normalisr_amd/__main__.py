@@ -64,6 +64,8 @@ def build_parser():
 	p.add_argument('--clfc_out', dest='clfc_out', action='store', help='Output covariate log fold changes, (predictors, genes*covariates) row-major, TSV.')
 	p.add_argument('--vard_out', dest='vard_out', action='store', help='Output variance of each predictor unexplained by covariates, TSV.')
 	p.add_argument('--vart_out', dest='vart_out', action='store', help='Output variance of expression unexplained by covariates (predictors x genes), TSV.')
+	p.add_argument('--logp', dest='logp', action='store_true', default=None,
+				   help='Write the natural logarithm of the P-values into pv_out: finite where a P-value underflows to 0 (method "ignore", one GPU).')
 	p.add_argument('--gpus', dest='gpus', action='store', type=int, default=1, help='GPUs of this node to shard the problem over (one process per GPU, RCCL); every rank reads only its gene rows of exp_in. Default: 1.')
 
 	p = sub.add_parser('coex', help='Co-expression analysis.')
@@ -76,6 +78,8 @@ def build_parser():
 	p.add_argument('--var_out', dest='var_out', action='store', help='Output variance of each gene unexplained by covariates, TSV.')
 	p.add_argument('--dot_out', dest='dot_out', action='store',
 				   help='Output covariance of gene pairs after covariate removal (inner product / cell count), TSV. Pearson R = dot/sqrt(var_i var_j).')
+	p.add_argument('--logp', dest='logp', action='store_true', default=None,
+				   help='Write the natural logarithm of the P-values into pv_out: finite where a P-value underflows to 0; -INF on the diagonal (one GPU).')
 	p.add_argument('--gpus', dest='gpus', action='store', type=int, default=1, help='GPUs of this node to shard the problem over (one process per GPU, RCCL); every rank reads only its gene rows of exp_in. Default: 1.')
 	p = sub.add_parser('lcpm', help='Compute Bayesian expectation of logCPM and cellular summary covariates from read counts.')
 	p.add_argument('reads_in', help='Input read-count matrix (genes x cells) without row or column names: TSV if dense (default), Matrix Market (.mtx, .mtx.gz) with -s.')
@@ -185,6 +189,8 @@ def main(argv=None):
 		return 1
 	if args.get('gpus', 1) < 1:
 		raise ValueError('--gpus must be positive')
+	if args.get('gpus', 1) > 1 and args.get('logp'):
+		raise NotImplementedError('--logp is available on one GPU only (the sharded paths return P-values).')
 	if args.get('gpus', 1) > 1:  # one process per GPU, started before anything in this process touches a GPU
 		from . import launch
 		return launch.run_sharded(args['cmd'], args)

@@ -53,9 +53,14 @@ _SIGNATURES = {
 	'nrm_pvalue_plan_init_many': ([_vp, _i64, _vp, _i64], _i32),
 	'nrm_pvalue_plan_fill_many': ([_vp, _i64, _vp, _i64], _i32),
 	'nrm_pvalues_from_r2': ([_vp, _i64, _dbl, _vp, _vp], _i32),
+	'nrm_logpvalues_from_r2': ([_vp, _i64, _dbl, _vp, _vp], _i32),
 	'nrm_assoc_sweep': ([_vp, _i64, _vp, _vp, _i64, _i64, _i64, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _dbl, _vp], _i32),
 	'nrm_assoc_sweep_band': ([_vp, _i64, _vp, _vp, _i64, _i64, _i64, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _vp], _i32),
 	'nrm_assoc_sweep_mirror': ([_vp, _i64, _vp, _vp, _i64, _i64, _i64, _dbl, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _dbl, _vp], _i32),
+	# the same three with p_kind (0 = P, 1 = ln P) before the stream
+	'nrm_assoc_sweep_pk': ([_vp, _i64, _vp, _vp, _i64, _i64, _i64, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _dbl, _i32, _vp], _i32),
+	'nrm_assoc_sweep_band_pk': ([_vp, _i64, _vp, _vp, _i64, _i64, _i64, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _i32, _vp], _i32),
+	'nrm_assoc_sweep_mirror_pk': ([_vp, _i64, _vp, _vp, _i64, _i64, _i64, _dbl, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _dbl, _i32, _vp], _i32),
 	'nrm_host_mirror_rows': ([_vp, _i64, _i32, _i64, _i64, _i32], _i32),
 	'nrm_copy_rect_to_host': ([_vp, _i64, _vp, _i64, _i64, _i64, _vp], _i32),
 	'nrm_single4_sweep': ([_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _dbl, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp], _i32),
@@ -74,6 +79,7 @@ _SIGNATURES = {
 	'nrm_gram_skinny': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _dbl, _vp, _vp], _i32),
 	'nrm_gram_skinny_workspace_bytes': ([], _i64),
 	'nrm_de_small_sweep': ([_vp, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i64, _dbl, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp], _i32),
+	'nrm_de_small_sweep_pk': ([_vp, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i64, _dbl, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _vp], _i32),
 	'nrm_single1_sweep': ([_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp], _i32),
 	'nrm_de_sparse_chunk': ([], _i64),
 	'nrm_de_sparse_max_covariates': ([], _i64),
@@ -130,6 +136,8 @@ _SIGNATURES = {
 	'nrm_small_eigvals': ([_vp, _i64, _vp], _i32),
 	'nrm_association_tests_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32,
 									_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32], _i32),
+	'nrm_association_tests_host_pk': ([_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32,
+									   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32], _i32),
 	'nrm_lcpm_row_tile': ([], _i64),
 	'nrm_lcpm_table_cap': ([], _i64),
 	'nrm_lcpm_count_workspace': ([_i64, _i64], _i64),

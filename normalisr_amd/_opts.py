@@ -57,3 +57,10 @@ def debug(key, default=None):
 	if v is None:
 		v = os.environ.get('NRM_' + key.upper())
 	return default if v is None else v
+
+
+def refuse_logp(logp, what):
+	"""logp=True (ln P instead of P: DESIGN.md section 4f) exists for one-shot single=0 calls -- association_tests, coex, de.  Everything else that takes the
+	keyword refuses it here, before any device call."""
+	if logp:
+		raise NotImplementedError('logp=True is available for single=0 calls of association_tests, coex and de only; {} returns P-values.'.format(what))

@@ -235,7 +235,7 @@ def _result(shape, dtype):
 	return np.empty(shape, dtype=dtype) if a is None else a
 
 
-def _single0_host_entry(dx, dy, dc64, dci, dcr, dimreduce, return_dot, want_alpha, out_dtype, want_rt):
+def _single0_host_entry(dx, dy, dc64, dci, dcr, dimreduce, return_dot, want_alpha, out_dtype, want_rt, logp=False):
 	"""single=0 through nrm_association_tests_host (include/normalisr_hip.h): the C entry a maintainer of the reference would bind --
 	host buffers in, host buffers out, uploads, kernels, the integer engine's guard and its fp64 rerun inside the library.  Used
 	when torch cannot be imported: the package then needs numpy and the library only."""
@@ -256,9 +256,9 @@ def _single0_host_entry(dx, dy, dc64, dci, dcr, dimreduce, return_dot, want_alph
 	t = _result((nx, ny), odt) if want_rt else None
 	dc64 = np.ascontiguousarray(dc64)
 	dci = np.ascontiguousarray(dci, dtype=np.float64)
-	_lib.check(lib.nrm_association_tests_host(vp(dx), code(dx), nx, vp(dy), 0 if samexy else code(dy), 0 if samexy else ny, vp(dc64), _lib.NRM_F64, nc, n,
-											  vp(dci), int(dcr), int(dimreduce), 1 if (samexy or return_dot) else 0, vp(p), vp(stat), vp(alpha), vp(varx), vp(vary),
-											  vp(r), vp(t), _engine.dtype_code(odt)))
+	_lib.check(lib.nrm_association_tests_host_pk(vp(dx), code(dx), nx, vp(dy), 0 if samexy else code(dy), 0 if samexy else ny, vp(dc64), _lib.NRM_F64, nc, n,
+												 vp(dci), int(dcr), int(dimreduce), 1 if (samexy or return_dot) else 0, vp(p), vp(stat), vp(alpha), vp(varx), vp(vary),
+												 vp(r), vp(t), _engine.dtype_code(odt), 1 if logp else 0))
 	return dict(p=p, stat=stat, alpha=alpha, varx=varx, vary=vary, r=r, t=t, dof=n - 1 - dcr - dimreduce)
 
 
@@ -363,7 +363,7 @@ def _single14_without_torch(single, dx, dy, dc, lowmem, return_dot, ka):
 
 
 def association_tests(dx, dy, dc, bsx=0, bsy=0, nth=1, lowmem=True, return_dot=True, single=0, bs4=500,
-					  return_stats=False, device_out=False, **ka):
+					  return_stats=False, device_out=False, logp=False, **ka):
 	"""All-pairs association tests between rows of dx and dy (or dx with itself when dy is None).
 
 	Same contract as association.py:761-1093: returns (P-values, dot|gamma, alpha|None, varx|None, vary).
@@ -374,12 +374,18 @@ def association_tests(dx, dy, dc, bsx=0, bsy=0, nth=1, lowmem=True, return_dot=T
 	device=<index> runs the call on that GPU instead of the current one (also engine.use_device, NORMALISR_DEVICE).
 	dx may be sparse for single = 0, 1, 4 -- a scipy.sparse matrix, a de_sparse.DesignCSR, a torch.sparse_csr CUDA tensor -- with the results of the densified
 	matrix; dy and dc are dense.
+	logp=True (single=0 only; NotImplementedError otherwise): the first result holds ln P, the natural logarithm of the P-values, in the same shape, dtype and
+	place (also with device_out=True), rounded once to that dtype; everything else is the same bytes -- with one exception: a call that the integer
+	engine's guard certifies for ln P but not for P keeps the integer engine's other results, where the call without logp takes them from the fp64 kernel (1e-13 apart).  ln P = 0 where P = 1, -inf exactly where P is a 0 that is
+	no underflow (R^2 >= 1 as computed; the diagonal when dy is None), and finite for every other pair whatever the number of cells.
 	"""
+	if logp and single != 0:
+		raise NotImplementedError('logp=True is available for single=0 only (single=1, 4 and 5 return P-values).')
 	device = ka.pop('device', None)
 	if device is not None:
 		with _engine.use_device(device):
 			return association_tests(dx, dy, dc, bsx=bsx, bsy=bsy, nth=nth, lowmem=lowmem, return_dot=return_dot, single=single, bs4=bs4,
-									 return_stats=return_stats, device_out=device_out, **ka)
+									 return_stats=return_stats, device_out=device_out, logp=logp, **ka)
 	bs = ka.pop('bs', None)  # the reference's docstring promises `bs` (coex.py:38) but crashes on it (SURVEY Q8)
 	if bs is not None and not bsx and not bsy:
 		bsx = bsy = bs
@@ -462,12 +468,17 @@ def association_tests(dx, dy, dc, bsx=0, bsy=0, nth=1, lowmem=True, return_dot=T
 		if device_out:
 			raise RuntimeError('device_out=True returns torch tensors: torch is needed for it.')
 		res = _single0_host_entry(_engine.as_input(dx), None if samexy else _engine.as_input(dy), dc64, dci, dcr, dimreduce, return_dot,
-								  not lowmem, out_dtype, return_stats)
+								  not lowmem, out_dtype, return_stats, logp=logp)
 	else:
 		prep = lambda a: a if is_dev(a) else _engine.as_input(a)
 		res = _engine.get_engine().association_single0(prep(dx), None if samexy else prep(dy), dc64, dci, dcr,
 								  dimreduce, return_dot=return_dot, want_alpha=not lowmem, out_dtype=out_dtype,
-								  want_rt=return_stats, device_out=device_out and not return_stats)
+								  want_rt=return_stats, device_out=device_out and not return_stats, logp=logp)
+	if logp:
+		# the reference's assertion on its P-values (association.py:1078-1079: finite, within [0, 1]) for their logarithms: no NaN and <= 0 (-inf is a value)
+		# (a NaN anywhere makes the maximum NaN and the comparison False; numpy arrays and, with device_out, torch tensors alike)
+		if not bool(res['p'].max() <= 0):
+			raise AssertionError('ln P: NaN or positive results (association.py:1078-1079 for logp=True)')
 	stat = res['stat']
 	if device_out and samexy and not return_dot:
 		raise NotImplementedError('device_out with dy=None and return_dot=False')

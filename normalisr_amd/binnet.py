@@ -71,7 +71,8 @@ def bh(pv, weight=None, on_device=None):
 	entries the reference's fp32 count stalls; the device's stays exact).  on_device=True sends a numpy array (1-D or 2-D) the same way: upload, nrm_bh, download --
 	or, in a process on the library's whole-problem entries (no torch; NRM_HOST_ENTRY=1), nrm_bh_host.  Any other dtype runs the host code and raises what it raises.
 	weight is not None ALWAYS runs the host code (a device tensor is downloaded and the result uploaded again): the reference adds the weights up sequentially, in
-	the order of the entries, and no parallel sum reproduces that order's rounding."""
+	the order of the entries, and no parallel sum reproduces that order's rounding.
+	pv holds P-values, not their logarithms: the result of a logp=True call is refused by the assertion 0 <= p <= 1 (q-values on ln P are a follow-up)."""
 	is_dev = hasattr(pv, 'is_cuda') and pv.is_cuda
 	native = str(getattr(pv, 'dtype', '')).replace('torch.', '') in ('float32', 'float64')
 	if weight is not None or (is_dev and not native):
@@ -129,7 +130,8 @@ def _bh_device(pv, is_dev):
 def binnet(net, qcut):
 	"""Binarise a symmetric co-expression P-value matrix: per-row BH q-values over the off-diagonal entries,
 	thresholded at qcut (binnet.py:134-173).  Returns a boolean (n_gene, n_gene) matrix, diagonal False.
-	A torch CUDA tensor is accepted (and then returned) so that coex -> binnet can stay in HBM."""
+	A torch CUDA tensor is accepted (and then returned) so that coex -> binnet can stay in HBM.
+	net holds P-values, not their logarithms: coex(..., logp=True)[0] is refused by the assertion 0 <= p <= 1 (a follow-up)."""
 	from . import _lib
 	on_device = hasattr(net, 'is_cuda') and net.is_cuda  # torch tensor already in HBM (e.g. coex(..., device_out=True)[0])
 	if not on_device:

@@ -18,7 +18,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _opts
 
 _vp, _i64, _dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double
 INFO_FIELDS = ('engine', 'captured', 'steps', 'reruns', 'rank', 'dof', 'bytes')
@@ -184,7 +184,8 @@ class CoexPlan(_Plan):
 	info(): engine (0: fp64 kernel, 5 / 6: digit planes of the integer engine), captured, steps, reruns, rank, dof, bytes."""
 	_prefix, _info_fields = 'nrm_coex_plan_', INFO_FIELDS
 
-	def __init__(self, dt, dc, dimreduce=0, out_dtype=None, device=None, pinv='numpy'):
+	def __init__(self, dt, dc, dimreduce=0, out_dtype=None, device=None, pinv='numpy', logp=False):
+		_opts.refuse_logp(logp, 'cplan.CoexPlan')
 		super().__init__()
 		if pinv not in ('numpy', 'library'):
 			raise ValueError("pinv must be 'numpy' or 'library'")
@@ -389,7 +390,8 @@ class DePlan(_DesignPlan):
 	info(): route (0: the sparse-design kernels, 1: K1 and the fp64 Gram kernel after a hand-back), captured, steps, reruns, rank, dof, bytes, rows_kept."""
 	_prefix, _info_fields = 'nrm_de_plan_', DE_INFO_FIELDS
 
-	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None, pinv='numpy'):
+	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None, pinv='numpy', logp=False):
+		_opts.refuse_logp(logp, 'cplan.DePlan')
 		super().__init__()
 		if pinv not in ('numpy', 'library'):
 			raise ValueError("pinv must be 'numpy' or 'library'")
@@ -430,7 +432,8 @@ class Single1Plan(_DesignPlan):
 	info(): route (0), captured, steps, cells_kept (cells that carry exactly one grouping), covariates, reserved (0), bytes, rows_kept."""
 	_prefix, _info_fields = 'nrm_single1_plan_', S1_INFO_FIELDS
 
-	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None):
+	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None, logp=False):
+		_opts.refuse_logp(logp, 'cplan.Single1Plan')
 		super().__init__()
 		if np.ndim(dimreduce) != 0:
 			raise NotImplementedError('Single1Plan: one dimreduce for all genes (association_tests(..., single=1) takes one per gene)')
@@ -468,7 +471,8 @@ class Single4Plan(_DesignPlan):
 	info(): route (0: the sparse-design kernels, 1: K1 and the fp64 Gram kernel after a hand-back), captured, steps, reruns, rank, dof, bytes, rows_kept."""
 	_prefix, _info_fields = 'nrm_single4_plan_', DE_INFO_FIELDS
 
-	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None, pinv='numpy', tol=1e-8):
+	def __init__(self, dg, dt, dc, dimreduce=0, lowmem=True, q=False, out_dtype=None, device=None, pinv='numpy', tol=1e-8, logp=False):
+		_opts.refuse_logp(logp, 'cplan.Single4Plan')
 		super().__init__()
 		if pinv not in ('numpy', 'library'):
 			raise ValueError("pinv must be 'numpy' or 'library'")

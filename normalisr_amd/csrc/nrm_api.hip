@@ -338,12 +338,13 @@ static bool de_path_general() {  // NRM_DEBUG="de_path=general" (or NRM_DE_PATH=
 static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny,
 										  const void* h_dc, int c_dtype, int64_t nc, int64_t n, const double* h_dci, int rank,
 										  int dimreduce, int return_dot, void* h_p, void* h_stat, void* h_alpha, void* h_varx,
-										  void* h_vary, void* h_r, void* h_t, int out_dtype, int nslices, int64_t* guard_hits, bool allow_sparse);
+										  void* h_vary, void* h_r, void* h_t, int out_dtype, int nslices, int64_t* guard_hits, bool allow_sparse, int p_kind);
 
-extern "C" int nrm_association_tests_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny,
-										  const void* h_dc, int c_dtype, int64_t nc, int64_t n, const double* h_dci, int rank,
-										  int dimreduce, int return_dot, void* h_p, void* h_stat, void* h_alpha, void* h_varx,
-										  void* h_vary, void* h_r, void* h_t, int out_dtype) {
+extern "C" int nrm_association_tests_host_pk(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny,
+											 const void* h_dc, int c_dtype, int64_t nc, int64_t n, const double* h_dci, int rank,
+											 int dimreduce, int return_dot, void* h_p, void* h_stat, void* h_alpha, void* h_varx,
+											 void* h_vary, void* h_r, void* h_t, int out_dtype, int p_kind) {
+	NRM_REQUIRE(p_kind == 0 || p_kind == 1, "p_kind must be 0 (P-values) or 1 (their natural logarithms)");
 	std::lock_guard<std::mutex> serial(g_host_entry);
 	NRM_TRY(nrm_bind_device());
 	// K2 engine as in the Python host (NRM_GRAM): exact fixed-point contraction on the int8 matrix cores (6 slices = 46 bits; i8x5: 5
@@ -355,19 +356,43 @@ extern "C" int nrm_association_tests_host(const void* h_dx, int x_dtype, int64_t
 	g_guard_worst = 0.0;
 	int64_t hits = 0;
 	int rc = association_tests_host_impl(h_dx, x_dtype, nx, h_dy, y_dtype, ny, h_dc, c_dtype, nc, n, h_dci, rank, dimreduce, return_dot, h_p, h_stat,
-										 h_alpha, h_varx, h_vary, h_r, h_t, out_dtype, nslices, &hits, true);
+										 h_alpha, h_varx, h_vary, h_r, h_t, out_dtype, nslices, &hits, true, p_kind);
 	if (rc == NRM_OK && hits > 0) {  // pairs the guard could not certify (or rows the sparse-design kernels handed back): the whole call again on the fp64 matrix cores
 		g_guard_hits = hits;
+		if (p_kind) {
+			// ln P: the guard's rule differs from the one for P (csrc/nrm_fix.h), and p_kind changes the first result only.  So everything else is what the call
+			// returns without it -- its own verdict and rerun included --, and ln P alone comes from the fp64 pass, whose other results go to scratch.
+			int64_t lin = 0;
+			rc = association_tests_host_impl(h_dx, x_dtype, nx, h_dy, y_dtype, ny, h_dc, c_dtype, nc, n, h_dci, rank, dimreduce, return_dot, h_p, h_stat, h_alpha, h_varx, h_vary,
+											 h_r, h_t, out_dtype, nslices, &lin, true, 0);
+			if (rc == NRM_OK && lin > 0)
+				rc = association_tests_host_impl(h_dx, x_dtype, nx, h_dy, y_dtype, ny, h_dc, c_dtype, nc, n, h_dci, rank, dimreduce, return_dot, h_p, h_stat, h_alpha, h_varx,
+												 h_vary, h_r, h_t, out_dtype, 0, nullptr, false, 0);
+			if (rc != NRM_OK) return rc;
+			const size_t rows_y = (size_t)(h_dy ? ny : nx), ob = (size_t)nx * rows_y * nrm_esize(out_dtype);
+			std::vector<char> s_stat(ob), s_alpha(h_alpha ? ob * (size_t)nc : 0), s_varx(h_varx ? (size_t)nx * 8 : 0), s_vary(rows_y * 8), s_r(h_r ? ob : 0), s_t(h_t ? ob : 0);
+			return association_tests_host_impl(h_dx, x_dtype, nx, h_dy, y_dtype, ny, h_dc, c_dtype, nc, n, h_dci, rank, dimreduce, return_dot, h_p, s_stat.data(),
+											   h_alpha ? s_alpha.data() : nullptr, h_varx ? s_varx.data() : nullptr, s_vary.data(), h_r ? s_r.data() : nullptr,
+											   h_t ? s_t.data() : nullptr, out_dtype, 0, nullptr, false, 1);
+		}
 		rc = association_tests_host_impl(h_dx, x_dtype, nx, h_dy, y_dtype, ny, h_dc, c_dtype, nc, n, h_dci, rank, dimreduce, return_dot, h_p, h_stat,
-										 h_alpha, h_varx, h_vary, h_r, h_t, out_dtype, 0, nullptr, false);
+										 h_alpha, h_varx, h_vary, h_r, h_t, out_dtype, 0, nullptr, false, p_kind);
 	}
 	return rc;
+}
+
+extern "C" int nrm_association_tests_host(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny,
+										  const void* h_dc, int c_dtype, int64_t nc, int64_t n, const double* h_dci, int rank,
+										  int dimreduce, int return_dot, void* h_p, void* h_stat, void* h_alpha, void* h_varx,
+										  void* h_vary, void* h_r, void* h_t, int out_dtype) {
+	return nrm_association_tests_host_pk(h_dx, x_dtype, nx, h_dy, y_dtype, ny, h_dc, c_dtype, nc, n, h_dci, rank, dimreduce, return_dot, h_p, h_stat, h_alpha, h_varx, h_vary,
+										 h_r, h_t, out_dtype, 0);
 }
 
 static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny,
 										  const void* h_dc, int c_dtype, int64_t nc, int64_t n, const double* h_dci, int rank,
 										  int dimreduce, int return_dot, void* h_p, void* h_stat, void* h_alpha, void* h_varx,
-										  void* h_vary, void* h_r, void* h_t, int out_dtype, int nslices, int64_t* guard_hits, bool allow_sparse) {
+										  void* h_vary, void* h_r, void* h_t, int out_dtype, int nslices, int64_t* guard_hits, bool allow_sparse, int p_kind) {
 	const bool samexy = (h_dy == nullptr);
 	if (samexy) {
 		ny = nx;
@@ -402,7 +427,7 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	// (engine.association_de_streaming); NRM_DEBUG de_path=general keeps K1 + K2
 	if (allow_sparse && !samexy && nx + nc <= 32 && !de_path_general()) {
 		return nrm_host_de_streaming(dx.p, x_dtype, nx, h_dy, y_dtype, ny, c64.data(), nc, n, h_dci, rank, dof, return_dot ? 0 : 1, h_p, h_stat, want_alpha ? h_alpha : nullptr,
-									 h_varx, h_vary, h_r, h_t, out_dtype);
+									 h_varx, h_vary, h_r, h_t, out_dtype, p_kind);
 	}
 	bool dy_up = false;
 	if (allow_sparse && !samexy && nrm_de_sparse_wanted(nx, ny, n, nc)) {
@@ -411,7 +436,7 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 		int taken = 0;
 		int64_t back = 0;
 		NRM_TRY(nrm_host_de_sparse(dx.p, x_dtype, nx, dy.p, y_dtype, ny, dc.as<double>(), c64.data(), nc, n, dci.as<double>(), rank, dof, (return_dot ? 0 : 1), h_p, h_stat,
-								   want_alpha ? h_alpha : nullptr, h_varx, h_vary, h_r, h_t, out_dtype, &taken, &back));
+								   want_alpha ? h_alpha : nullptr, h_varx, h_vary, h_r, h_t, out_dtype, &taken, &back, p_kind));
 		if (taken) {
 			if (back > 0 && guard_hits) *guard_hits = back;
 			return NRM_OK;
@@ -465,6 +490,7 @@ static int association_tests_host_impl(const void* h_dx, int x_dtype, int64_t nx
 	ops.qy = samexy ? qx.p : qy.p, ops.ey = samexy ? ops.ex : ey.as<int32_t>(), ops.fy = samexy ? ops.fx : fy.as<double>(), ops.ry = samexy ? ops.rx : ry.as<double>(), ops.ssy = sy;
 	ops.nx = nx, ops.ny = ny, ops.n = n, ops.mp = mp, ops.np_ = np_, ops.kp = kp;
 	ops.nslices = nslices, ops.samexy = samexy ? 1 : 0, ops.stat_kind = stat_kind, ops.out_dtype = out_dtype, ops.dof = dof, ops.guard_tol = guard_tol;
+	ops.p_kind = p_kind;
 	ops.dot = dot.as<double>(), ops.gwork = gwork.p, ops.flags = flags.as<int32_t>();
 	ops.p = out.p.p, ops.stat = out.stat.p, ops.r = out.r.p, ops.t = out.t.p;
 	CopyStream cs;

@@ -56,9 +56,10 @@ struct NrmDeSparseStep {
 							(want_alpha && ncu) ? by.as<double>() : nullptr, flags.as<int32_t>(), st);
 	}
 	// P-values and the statistic (nx, ny) of out_dtype, r and t on request; alpha (nx, ny, nc) when the step keeps b_y
-	int enqueue_sweep(hipStream_t st, void* p, void* stat, void* r, void* t, void* alpha, int stat_kind) {
-		NRM_TRY(nrm_assoc_sweep(dot.as<double>(), nyp, ssx.as<double>(), ssy.as<double>(), nx, ny, n, dof, 0, stat_kind, p, stat, r, t, out_dtype, ny, flags.as<int32_t>(), 0, nullptr,
-								nullptr, 0.0, st));
+	// (p_kind 1: ln p in p, nrm_assoc_sweep_pk; the resident plan keeps 0)
+	int enqueue_sweep(hipStream_t st, void* p, void* stat, void* r, void* t, void* alpha, int stat_kind, int p_kind = 0) {
+		NRM_TRY(nrm_assoc_sweep_pk(dot.as<double>(), nyp, ssx.as<double>(), ssy.as<double>(), nx, ny, n, dof, 0, stat_kind, p, stat, r, t, out_dtype, ny, flags.as<int32_t>(), 0,
+								   nullptr, nullptr, 0.0, p_kind, st));
 		return want_alpha ? nrm_alpha(stat, out_dtype, ny, stat_kind, ssx.as<double>(), n, bx.as<double>(), by.as<double>(), nx, ny, nc, alpha, out_dtype, st) : NRM_OK;
 	}
 };

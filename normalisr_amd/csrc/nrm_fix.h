@@ -14,6 +14,7 @@
 //      c_i = sqrt(max_s V_is / sum_k q_ik^2),  g_i = sqrt(n) 2^(sh_i - 1) / |x~_i|;
 //   3. counts the pairs whose P-value that bound could move by more than the budget (relative; |d ln p| <= dof |r| |delta r| /
 //      (1 - R^2)) unless the P-value is 0 on the whole interval.  The host reruns a call with such pairs on the fp64 Gram kernel.
+//      (A sweep that returns ln p, p_kind 1: more than budget * max(1, |ln p|), and only x <= 0 is exempt -- nrm_fix_guard_ln.)
 //
 // Per-row record, NRM_FIX_STRIDE doubles: [0..4] u_s = 2^sh 256^s S_s (0 beyond NS - 2), [5] c, [6] g, [7] 2^(sh + B) / rms (the
 // effective max/rms of the quantisation, diagnostics only).
@@ -137,6 +138,21 @@ __device__ __forceinline__ void nrm_fix_guard(const FixArgs& f, double cx, doubl
 		}
 	} else
 		a.worst = fmaxf(a.worst, err);
+}
+
+// The exact test of one pair of a sweep that returns ln p (lnp: its value for this pair).  The bound above IS a bound on |d ln p|;
+// the contract -- a relative 1e-6 on a quantity in [0, 1] -- becomes one on a quantity that is not: a pair is uncertified when the
+// bound exceeds budget * max(1, |ln p|).  No P-value is 0 here, so none is exempt for that; only x <= 0 (ln p = -inf, R^2 >= 1 as
+// computed: the same -inf anywhere on the interval's upper side) is, and nrm_fix_close has nothing to do.  The screen of a thread
+// (nrm_fix_screen) stays as it is: it tests against max(1, |ln p|) >= 1, so a thread it certifies is certified here as well.
+__device__ __forceinline__ void nrm_fix_guard_ln(const FixArgs& f, double cx, double gx, const FixCol& y, double r2, double sqrt_dof, double lnp, FixAcc& a) {
+	double dr, ar, num, den;
+	nrm_fix_bound(f, cx, gx, y, r2, sqrt_dof, dr, ar, num, den);
+	if (lnp == -INFINITY) return;
+	const double scale = fmax(1.0, fabs(lnp));
+	const float err = __fdividef((float)num, (float)(den * scale));
+	if (num > f.budget * den * scale || !(num == num)) a.bad++;
+	a.worst = fmaxf(a.worst, err);
 }
 
 template <typename Plan, typename PFn>

@@ -56,7 +56,7 @@ int sparse_products(const NrmDesignLists& L, const void* d_y, int y_dtype, int64
 
 int nrm_host_de_sparse(const void* d_x, int x_dtype, int64_t nx, const void* d_y, int y_dtype, int64_t ny, const double* d_c, const double* h_c64, int64_t nc, int64_t n,
 					   const double* d_dci, int rank, double dof, int stat_kind, void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary, void* h_r, void* h_t,
-					   int out_dtype, int* taken, int64_t* handed_back) {
+					   int out_dtype, int* taken, int64_t* handed_back, int p_kind) {
 	hipStream_t st = nullptr;
 	*taken = 0;
 	*handed_back = 0;
@@ -87,7 +87,7 @@ int nrm_host_de_sparse(const void* d_x, int x_dtype, int64_t nx, const void* d_y
 	DevBuf oalpha;
 	NRM_TRY(out.alloc(ob, h_r != nullptr, h_t != nullptr));
 	if (s.want_alpha) NRM_TRY(oalpha.alloc(ob * nc));
-	NRM_TRY(s.enqueue_sweep(st, out.p.p, out.stat.p, out.r.p, out.t.p, oalpha.p, stat_kind));
+	NRM_TRY(s.enqueue_sweep(st, out.p.p, out.stat.p, out.r.p, out.t.p, oalpha.p, stat_kind, p_kind));
 	int32_t hf[4];
 	NRM_TRY(nrm_read_flags(s.flags.p, st, hf));
 	NRM_TRY(nrm_assoc_assertions(hf, " tiles"));
@@ -111,7 +111,7 @@ int nrm_host_de_sparse(const void* d_x, int x_dtype, int64_t nx, const void* d_y
 // to 16 cells when n is not a multiple of 16 (the kernel streams 16-cell slabs without bounds checks).
 int nrm_host_de_streaming(const void* d_x, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const double* h_c64, int64_t nc, int64_t n,
 						  const double* h_dci, int rank, double dof, int stat_kind, void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary, void* h_r, void* h_t,
-						  int out_dtype) {
+						  int out_dtype, int p_kind) {
 	hipStream_t st = nullptr;
 	NRM_REQUIRE(nx + nc <= 32 && nx > 0 && ny > 0, "nrm_host_de_streaming: needs nx + nc <= 32");
 	double cval = 0.0;
@@ -183,8 +183,8 @@ int nrm_host_de_streaming(const void* d_x, int x_dtype, int64_t nx, const void* 
 	NRM_TRY(ssy.alloc((size_t)nyp * 8));
 	if (want_alpha) NRM_TRY(by.alloc_zero((size_t)ny * nc * 8, st));
 	NRM_TRY(flags.alloc_zero(16, st));
-	NRM_TRY(nrm_de_small_sweep(g.as<double>(), ssraw.as<double>(), nc ? dciz.as<double>() : nullptr, nc, rank, ssx.as<double>(), nx, ny, n, dof, stat_kind, out.p.p, out.stat.p,
-							   out.r.p, out.t.p, out_dtype, ny, ssy.as<double>(), want_alpha ? by.as<double>() : nullptr, flags.as<int32_t>(), const_last, st));
+	NRM_TRY(nrm_de_small_sweep_pk(g.as<double>(), ssraw.as<double>(), nc ? dciz.as<double>() : nullptr, nc, rank, ssx.as<double>(), nx, ny, n, dof, stat_kind, out.p.p, out.stat.p,
+							   out.r.p, out.t.p, out_dtype, ny, ssy.as<double>(), want_alpha ? by.as<double>() : nullptr, flags.as<int32_t>(), const_last, p_kind, st));
 	if (want_alpha) {
 		NRM_TRY(oalpha.alloc(ob * nc));
 		NRM_TRY(nrm_alpha(out.stat.p, out_dtype, ny, stat_kind, ssx.as<double>(), n, coefx.as<double>(), by.as<double>(), nx, ny, nc, oalpha.p, out_dtype, st));

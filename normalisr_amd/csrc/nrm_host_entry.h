@@ -194,6 +194,7 @@ struct NrmAssocOperands {
 	const double *ssx = nullptr, *ssy = nullptr;
 	int64_t nx = 0, ny = 0, n = 0, mp = 0, np_ = 0, kp = 0;
 	int nslices = 0, samexy = 0, stat_kind = 0, out_dtype = NRM_F64;
+	int p_kind = 0;  // the form of p: 0 = P-values, 1 = their logarithms (nrm_assoc_sweep_pk)
 	double dof = 0.0, guard_tol = 0.0;
 	double* dot = nullptr;
 	void* gwork = nullptr;
@@ -207,8 +208,8 @@ static inline int nrm_assoc_band(const NrmAssocOperands& o, int64_t a, int64_t b
 		NRM_TRY(nrm_gram_i8_band(o.qx, o.ex, 0, o.qy, o.ey, 0, o.mp, o.np_, o.kp, o.nslices, o.dot, o.np_, o.samexy, o.nx, o.ny, a, b == o.nx ? o.mp : b, o.gwork, st));
 	else
 		NRM_TRY(nrm_gram_f64_band(o.rx, o.ry, o.mp, o.np_, o.kp, o.kp, o.kp, o.dot, o.np_, o.samexy, o.nx, o.ny, a, b == o.nx ? o.mp : b, o.gwork, st));
-	return nrm_assoc_sweep_band(o.dot, o.np_, o.ssx, o.ssy, o.nx, o.ny, o.n, o.dof, o.samexy, o.stat_kind, o.p, o.stat, o.r, o.t, o.out_dtype, o.ny, o.flags, a, b, o.nslices,
-								o.nslices ? o.fx : nullptr, o.nslices ? o.fy : nullptr, o.guard_tol, st);
+	return nrm_assoc_sweep_band_pk(o.dot, o.np_, o.ssx, o.ssy, o.nx, o.ny, o.n, o.dof, o.samexy, o.stat_kind, o.p, o.stat, o.r, o.t, o.out_dtype, o.ny, o.flags, a, b, o.nslices,
+								   o.nslices ? o.fx : nullptr, o.nslices ? o.fy : nullptr, o.guard_tol, o.p_kind, st);
 }
 // the K2 engine of a dense single=0 problem of n cells: 6 digit planes from 2048 cells (the integer engine's error in r grows as 1 / sqrt(n)) when the rows are
 // 16-byte aligned (K1's fused quantiser), NRM_GRAM = i8 | i8x5 | f64 overriding, 0 = the fp64 kernel
@@ -267,8 +268,8 @@ int sparse_products(const NrmDesignLists& L, const void* d_y, int y_dtype, int64
 // (dense, or empty) and nothing was written; *handed_back = rows too close to the span of the covariates (the caller runs the dense fp64 path)
 int nrm_host_de_sparse(const void* d_x, int x_dtype, int64_t nx, const void* d_y, int y_dtype, int64_t ny, const double* d_c, const double* h_c64, int64_t nc, int64_t n,
 					   const double* d_dci, int rank, double dof, int stat_kind, void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary, void* h_r, void* h_t,
-					   int out_dtype, int* taken, int64_t* handed_back);
+					   int out_dtype, int* taken, int64_t* handed_back, int p_kind = 0);
 // de with nx + nc <= 32: the streaming kernel (nrm_host_de.hip); d_x in HBM, h_dy uploaded inside
 int nrm_host_de_streaming(const void* d_x, int x_dtype, int64_t nx, const void* h_dy, int y_dtype, int64_t ny, const double* h_c64, int64_t nc, int64_t n,
 						  const double* h_dci, int rank, double dof, int stat_kind, void* h_p, void* h_stat, void* h_alpha, void* h_varx, void* h_vary, void* h_r, void* h_t,
-						  int out_dtype);
+						  int out_dtype, int p_kind = 0);

@@ -20,6 +20,11 @@
 //    library's range-by-range rational functions, of which a wavefront executes every branch any of its lanes takes.
 // nrm_pvalue_fast is the straight-line form of the fast path for the sweep kernels (no branch: the unrolled pairs of a thread
 // interleave); pairs it cannot take (ok = false) go through nrm_pvalue afterwards, which returns the same bits wherever both apply.
+//
+// nrm_logpvalue / nrm_logpvalue_fast return ln p from the same plan and the same two routes, with the last step of each taken in
+// logarithms: -alpha u + ln(bracket) on the fast path, lnf + ln(cf / a) or log1p(-2 exp(lnf) cf) on the general one.  Nothing
+// underflows: ln p is finite for every 0 < x < 1 (x = 2^-53 at 500 000 cells: ln p = -9e6), and the shortcut for R^2 >= 1/4
+// (nrm_zero_above_quarter) has no counterpart.  ln p = 0 where p = 1 (x >= 1), -inf where x <= 0; NaN propagates.
 #pragma once
 #include "nrm_common.h"
 #include "nrm_erfcx_tab.h"
@@ -140,4 +145,64 @@ __device__ __forceinline__ double nrm_pvalue_fast(double r2, const PvalPlan& pl,
 	ok = small || zero;
 	const double p = nrm_pvalue_series<NRM_PCOEF_SMALL>(nrm_neglog1m_small(small ? w : 0.0), pl);
 	return x >= 1.0 ? 1.0 : (zero ? 0.0 : p);
+}
+
+// ---- ln p ---------------------------------------------------------------------------------------------------------------------
+// The fast path's formula in logarithms.  The bracket erfcx(sqrt z) + sqrt(z) poly(u) lies in (0, 1] and falls as 1 / sqrt(pi z):
+// its logarithm never leaves the normal range, and its relative error (3e-14, a function of u alone) is an absolute error of ln p.
+template <int NT>
+__device__ __forceinline__ double nrm_logpvalue_series(double u, const PvalPlan& pl) {
+	const double z = pl.alpha * u;
+	const double sz = sqrt(z);
+	double poly = pl.coef[NT - 1];
+#pragma unroll
+	for (int j = NT - 2; j >= 0; j--) poly = fma(poly, u, pl.coef[j]);
+	return log(fma(sz, poly, nrm_erfcx_pos(sz))) - z;
+}
+
+// ln of nrm_pvalue(r2, pl), finite for every 0 < x = fl(1 - r2) < 1
+__device__ __forceinline__ double nrm_logpvalue(double r2, const PvalPlan& pl) {
+	double x = 1.0 - r2;
+	if (!(x > 0.0)) return (x != x) ? x : -INFINITY;  // where the linear path returns a 0 that is no underflow; NaN propagates
+	if (x >= 1.0) return 0.0;
+	double w = 1.0 - x;
+	if (w < 0.25 && pl.umax >= 0.3) return nrm_logpvalue_series<NRM_PCOEF_SMALL>(nrm_neglog1m_small(w), pl);
+	double u = -log1p(-w);
+	if (u <= pl.umax) return nrm_logpvalue_series<NRM_PCOEF>(u, pl);
+	double a = pl.a;
+	double lnf = -a * u + 0.5 * log(w) + pl.ln_front;  // ln[ x^a (1-x)^(1/2) / B(a,1/2) ]
+	if (x < (a + 1.0) / (a + 2.5)) return lnf + log(nrm_betacf(a, 0.5, x) / a);
+	return log1p(-2.0 * exp(lnf) * nrm_betacf(0.5, a, w));
+}
+
+// Straight-line form: the value of nrm_logpvalue(r2, pl) whenever ok comes back true (R^2 in [0, 1/4) and a plan with a fast path, or
+// x <= 0); otherwise the result is meaningless and the caller evaluates nrm_logpvalue.
+__device__ __forceinline__ double nrm_logpvalue_fast(double r2, const PvalPlan& pl, bool& ok) {
+	const double x = 1.0 - r2, w = 1.0 - x;
+	const bool small = w >= 0.0 && w < 0.25 && pl.umax >= 0.3;  // u <= -ln(3/4) = 0.2877
+	const bool none = x <= 0.0;                                 // R^2 >= 1 as computed
+	ok = small || none;
+	const double lp = nrm_logpvalue_series<NRM_PCOEF_SMALL>(nrm_neglog1m_small(small ? w : 0.0), pl);
+	return x >= 1.0 ? 0.0 : (none ? -INFINITY : lp);
+}
+
+// the P-value in the form a sweep was compiled for: p_kind 0 = p, 1 = ln p
+template <int PK>
+__device__ __forceinline__ double nrm_pvalue_kind(double r2, const PvalPlan& pl) {
+	if constexpr (PK != 0)
+		return nrm_logpvalue(r2, pl);
+	else
+		return nrm_pvalue(r2, pl);
+}
+template <int PK>
+__device__ __forceinline__ double nrm_pvalue_kind_fast(double r2, const PvalPlan& pl, bool& ok) {
+	if constexpr (PK != 0)
+		return nrm_logpvalue_fast(r2, pl, ok);
+	else
+		return nrm_pvalue_fast(r2, pl, ok);
+}
+// what a pair without a test holds (coex's diagonal: triu + transpose leaves exact zeros there)
+template <int PK>
+__device__ __forceinline__ double nrm_pvalue_none() {
+	return PK != 0 ? -INFINITY : 0.0;
 }

@@ -3,6 +3,7 @@
 // assertion, beta.cdf), :1037-1057 (coef->dot conversion, symmetrise, zero diagonal).
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include "nrm_device.h"
 #include "nrm_pvalue.h"
 #include "nrm_fix.h"
@@ -43,6 +44,13 @@ __global__ void __launch_bounds__(256) k_pvalues_from_r2(const double* __restric
 	for (; i < count; i += stride) p[i] = nrm_pvalue(r2[i], pl);
 }
 
+__global__ void __launch_bounds__(256) k_logpvalues_from_r2(const double* __restrict__ r2, int64_t count, PvalPlan pl,
+															 double* __restrict__ lnp) {
+	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	int64_t stride = (int64_t)gridDim.x * blockDim.x;
+	for (; i < count; i += stride) lnp[i] = nrm_logpvalue(r2[i], pl);
+}
+
 #define SW_T 64
 #define SW_T_ 64
 
@@ -71,9 +79,11 @@ __device__ __forceinline__ FixCol fix_column(const FixArgs& f, int64_t col, int6
 	if (f.fx && col < ncols) y = nrm_fix_col(f.fy + col * NRM_FIX_STRIDE);
 	return y;
 }
+// (PK != 0, ln p: no pair is exempt because its P-value is 0, so there is nothing to close)
+template <int PK = 0>
 __device__ __forceinline__ void fix_finish(const FixArgs& f, int32_t* __restrict__ flags, FixAcc& a, const PvalPlan& pl) {
 	if (!f.fx || !flags) return;
-	nrm_fix_close(a, pl, PV_FN);
+	if constexpr (PK == 0) nrm_fix_close(a, pl, PV_FN);
 	int bad = a.bad;
 	float worst = a.worst;
 #pragma unroll
@@ -91,7 +101,9 @@ __device__ __forceinline__ void fix_finish(const FixArgs& f, int32_t* __restrict
 
 // One workgroup = one 64x64 tile of the (nx, ny) output.  The source tile of dot is staged through LDS
 // so that the mirrored half of a symmetric (coex) problem is read coalesced and transposed on chip.
-template <typename OutT>
+// PK (all four sweeps): the form of the first result, 0 = p, 1 = ln p (nrm_pvalue.h); a compile-time parameter, so that the p
+// kernels are the code they were before ln p existed.
+template <typename OutT, int PK>
 __global__ void __launch_bounds__(256, 3) k_assoc_sweep(const double* __restrict__ dot, int64_t ldd,
 													  const double* __restrict__ ssx, const double* __restrict__ ssy,
 													  int64_t nx, int64_t ny, double ncells, double dof, int symmetric,
@@ -161,14 +173,14 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep(const double* __restrict
 		double r2 = (d * d) / (vx * vy);  // = gamma^2 vx / vy  (association.py:235)
 		double p, stat, rr, tt;
 		if (symmetric && gi == gj) {
-			p = 0.0;  // triu(.,1) + transpose leaves exact zeros on the diagonal (Q1)
+			p = nrm_pvalue_none<PK>();  // triu(.,1) + transpose leaves exact zeros on the diagonal (Q1)
 			stat = 0.0;
 			rr = 0.0;
 			tt = 0.0;
 		} else {
 			if (!isfinite(r2) || !isfinite(vx) || !isfinite(vy)) bad_nf = 1;
 			if (r2 > 1.0 + 1e-8) bad_rng = 1;  // association.py:248
-			p = nrm_pvalue(r2, pl);
+			p = nrm_pvalue_kind<PK>(r2, pl);
 			stat = stat_kind ? d / vx : d / ncells;
 			rr = d / sqrt(vx * vy);
 			double rc = fmin(r2, 1.0);
@@ -187,14 +199,17 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep(const double* __restrict
 			const int64_t gi = (int64_t)bi * SW_T + r;
 			if (gi >= nx || gj >= ny || (symmetric && gi == gj)) continue;
 			const double d = pair_dot(r), r2 = (d * d) / (sx[r] * sy[tx]);
-			nrm_fix_guard(fix, sfx[r][5], sfx[r][6], fy, r2, sqrt_dof, nrm_pvalue(r2, pl) != 0.0, facc);
+			if constexpr (PK != 0)
+				nrm_fix_guard_ln(fix, sfx[r][5], sfx[r][6], fy, r2, sqrt_dof, nrm_logpvalue(r2, pl), facc);
+			else
+				nrm_fix_guard(fix, sfx[r][5], sfx[r][6], fy, r2, sqrt_dof, nrm_pvalue(r2, pl) != 0.0, facc);
 		}
 	}
 	if (flags) {
 		if (bad_nf) atomicAdd(&flags[0], 1);
 		if (bad_rng) atomicAdd(&flags[1], 1);
 	}
-	fix_finish(fix, flags, facc, pl);
+	fix_finish<PK>(fix, flags, facc, pl);
 }
 
 // Symmetric (coex) sweep over the upper triangle of 64x64 tiles only: every p-value is computed once and
@@ -203,7 +218,7 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep(const double* __restrict
 // tables are staged, computes, stores its results and leaves a copy in LDS; ONE barrier that waits for LDS only (the stores stay
 // in flight: __syncthreads() would drain them, and at 3 workgroups per CU those drains were a third of this kernel's time)
 // publishes the tile, and the mirrored block is stored from its transpose.
-template <typename OutT, int SR>  // SR: rows of a workgroup's piece of a tile (64, 32 or 16; 32 = two workgroups per tile: a finer tail)
+template <typename OutT, int SR, int PK>  // SR: rows of a workgroup's piece of a tile (64, 32 or 16; 32 = two workgroups per tile: a finer tail)
 __global__ void __launch_bounds__(256, 3) k_assoc_sweep_sym(const double* __restrict__ dot, int64_t ldd, const double* __restrict__ ss,
 														  int64_t ng, int nb, double ncells, PvalPlan pl, OutT* __restrict__ p_out,
 														  OutT* __restrict__ stat_out, int64_t ldo, int32_t* __restrict__ flags, int bi0, FixArgs fix) {
@@ -261,7 +276,7 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep_sym(const double* __rest
 		const double vx = sx[r], vy = sy[tx];
 		const double r2 = (d * d) / (vx * vy);
 		bool ok;
-		double p = nrm_pvalue_fast(r2, pl, ok);  // no branch around it: the NI evaluations of a thread interleave
+		double p = nrm_pvalue_kind_fast<PK>(r2, pl, ok);  // no branch around it: the NI evaluations of a thread interleave
 		double st = d / ncells;
 		if (pair) {
 			if (!isfinite(r2) || !isfinite(vx) || !isfinite(vy)) bad_nf = 1;
@@ -269,7 +284,7 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep_sym(const double* __rest
 			if (!ok) slow |= 1u << i;
 			if (fix.fx && fix.budget > 0.0) nrm_fix_note(facc, sfx[r][5], sfx[r][6], r2);
 		} else {
-			p = 0.0;
+			p = nrm_pvalue_none<PK>();
 			st = 0.0;
 		}
 		tp[r][tx] = (OutT)p;
@@ -287,7 +302,7 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep_sym(const double* __rest
 			const int64_t gi = (int64_t)bi * SW_T + h0 + r;
 			double d = dot[gi * ldd + gj];
 			if (fix.fx) d += nrm_fix_corr(sfx[r], fy, fix.top, fix.inv_n);
-			const OutT p = (OutT)nrm_pvalue((d * d) / (sx[r] * sy[tx]), pl);
+			const OutT p = (OutT)nrm_pvalue_kind<PK>((d * d) / (sx[r] * sy[tx]), pl);
 			tp[r][tx] = p;
 			p_out[gi * ldo + gj] = p;  // (after the store above, from the same thread: this one stays)
 		}
@@ -299,7 +314,10 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep_sym(const double* __rest
 			const int64_t gi = (int64_t)bi * SW_T + h0 + r;
 			if (gi >= ng || gj >= ng || gi == gj || (bi == bj && h0 + r > tx)) continue;
 			const double d = dv[i] + nrm_fix_corr(sfx[r], fy, fix.top, fix.inv_n);
-			nrm_fix_guard(fix, sfx[r][5], sfx[r][6], fy, (d * d) / (sx[r] * sy[tx]), sqrt_dof, tp[r][tx] != (OutT)0, facc);
+			if constexpr (PK != 0)  // (ln p as stored: the output type's rounding of the scale is far inside the bound's own slack)
+				nrm_fix_guard_ln(fix, sfx[r][5], sfx[r][6], fy, (d * d) / (sx[r] * sy[tx]), sqrt_dof, (double)tp[r][tx], facc);
+			else
+				nrm_fix_guard(fix, sfx[r][5], sfx[r][6], fy, (d * d) / (sx[r] * sy[tx]), sqrt_dof, tp[r][tx] != (OutT)0, facc);
 		}
 	}
 	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // tp / ts are complete; the stores above stay in flight
@@ -321,14 +339,14 @@ __global__ void __launch_bounds__(256, 3) k_assoc_sweep_sym(const double* __rest
 		if (bad_nf) atomicAdd(&flags[0], 1);
 		if (bad_rng) atomicAdd(&flags[1], 1);
 	}
-	fix_finish(fix, flags, facc, pl);
+	fix_finish<PK>(fix, flags, facc, pl);
 }
 
 // Off-diagonal rectangle of a symmetric (coex) problem: rows [r0, r0 + mx) against columns [c0, c0 + my) with c0 + my <= r0.
 // Every p-value is computed once and written twice -- at (r0 + i, c0 + j) and, through an LDS transpose, at (c0 + j, r0 + i) --
 // so that a pipelined coex (rows arriving chunk by chunk) can finish and ship both halves of a chunk's pairs at once.
 // (fp64 outputs need 195 registers: two waves per SIMD is what the kernel gets, and what it asks for)
-template <typename OutT>
+template <typename OutT, int PK>
 __global__ void __launch_bounds__(256, sizeof(OutT) == 8 ? 2 : 3) k_assoc_sweep_mirror(const double* __restrict__ dot, int64_t ldd, const double* __restrict__ ssx,
 															 const double* __restrict__ ssy, int64_t mx, int64_t my, double ncells, PvalPlan pl,
 															 OutT* __restrict__ p_out, OutT* __restrict__ stat_out, int64_t ldo, int64_t r0,
@@ -372,7 +390,7 @@ __global__ void __launch_bounds__(256, sizeof(OutT) == 8 ? 2 : 3) k_assoc_sweep_
 		const double vx = sx[r], vy = sy[tx];
 		const double r2 = (d * d) / (vx * vy);
 		bool ok;
-		double p = nrm_pvalue_fast(r2, pl, ok);
+		double p = nrm_pvalue_kind_fast<PK>(r2, pl, ok);
 		double st = d / ncells;
 		if (pair) {
 			if (!isfinite(r2) || !isfinite(vx) || !isfinite(vy)) bad_nf = 1;
@@ -382,7 +400,7 @@ __global__ void __launch_bounds__(256, sizeof(OutT) == 8 ? 2 : 3) k_assoc_sweep_
 			p_out[(r0 + gi) * ldo + c0 + gj] = (OutT)p;
 			stat_out[(r0 + gi) * ldo + c0 + gj] = (OutT)st;
 		} else {
-			p = 0.0;
+			p = nrm_pvalue_none<PK>();
 			st = 0.0;
 		}
 		tp[r][tx] = (OutT)p;
@@ -396,7 +414,7 @@ __global__ void __launch_bounds__(256, sizeof(OutT) == 8 ? 2 : 3) k_assoc_sweep_
 			const int64_t gi = (int64_t)bi * SW_T + r;
 			double d = dot[gi * ldd + gj];
 			if (fix.fx) d += nrm_fix_corr(sfx[r], fy, fix.top, fix.inv_n);
-			const OutT p = (OutT)nrm_pvalue((d * d) / (sx[r] * sy[tx]), pl);
+			const OutT p = (OutT)nrm_pvalue_kind<PK>((d * d) / (sx[r] * sy[tx]), pl);
 			tp[r][tx] = p;
 			p_out[(r0 + gi) * ldo + c0 + gj] = p;
 		}
@@ -408,7 +426,10 @@ __global__ void __launch_bounds__(256, sizeof(OutT) == 8 ? 2 : 3) k_assoc_sweep_
 			const int64_t gi = (int64_t)bi * SW_T + r;
 			if (gi >= mx || gj >= my) continue;
 			const double d = dv[i] + nrm_fix_corr(sfx[r], fy, fix.top, fix.inv_n);
-			nrm_fix_guard(fix, sfx[r][5], sfx[r][6], fy, (d * d) / (sx[r] * sy[tx]), sqrt_dof, tp[r][tx] != (OutT)0, facc);
+			if constexpr (PK != 0)  // (ln p as stored: the output type's rounding of the scale is far inside the bound's own slack)
+				nrm_fix_guard_ln(fix, sfx[r][5], sfx[r][6], fy, (d * d) / (sx[r] * sy[tx]), sqrt_dof, (double)tp[r][tx], facc);
+			else
+				nrm_fix_guard(fix, sfx[r][5], sfx[r][6], fy, (d * d) / (sx[r] * sy[tx]), sqrt_dof, tp[r][tx] != (OutT)0, facc);
 		}
 	}
 	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // tp / ts are complete; the stores above stay in flight
@@ -426,13 +447,13 @@ __global__ void __launch_bounds__(256, sizeof(OutT) == 8 ? 2 : 3) k_assoc_sweep_
 		if (bad_nf) atomicAdd(&flags[0], 1);
 		if (bad_rng) atomicAdd(&flags[1], 1);
 	}
-	fix_finish(fix, flags, facc, pl);
+	fix_finish<PK>(fix, flags, facc, pl);
 }
 
 // Sweep for the streaming de path (nrm_gram_skinny): one thread per gene.  G[y] = [y C^T (nc) | y X~^T (nx) | 0...],
 // ssraw[y] = |y|^2.  |y~|^2 = |y|^2 - a dci a^T with a = y C^T (association.py:226-230 expanded), y~.x~ = y.x~.
 #define DS_NZ 32
-template <typename OutT>
+template <typename OutT, int PK>
 __global__ void __launch_bounds__(256) k_de_small_sweep(const double* __restrict__ G, const double* __restrict__ ssraw,
 														 const double* __restrict__ dci, int nc, int rank_pos,
 														 const double* __restrict__ ssx, int nx, int64_t ny, double ncells, double dof,
@@ -491,7 +512,7 @@ __global__ void __launch_bounds__(256) k_de_small_sweep(const double* __restrict
 			if (!isfinite(r2) || !isfinite(vy)) bad_nf = 1;
 			if (r2 > 1.0 + 1e-8) bad_rng = 1;
 			const int64_t o = (int64_t)x * ldo + y;
-			const double pval = nrm_pvalue(r2, pl);
+			const double pval = nrm_pvalue_kind<PK>(r2, pl);
 			p_out[o] = (OutT)pval;
 			stat_out[o] = (OutT)(stat_kind ? d / vx : d / ncells);
 			if (r_out) r_out[o] = (OutT)(d / sqrt(vx * vy));
@@ -540,11 +561,26 @@ extern "C" int nrm_pvalues_from_r2(const double* d_r2, int64_t count, double dof
 	return nrm_check_launch("k_pvalues_from_r2");
 }
 
-extern "C" int nrm_assoc_sweep_band(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t nx,
+extern "C" int nrm_logpvalues_from_r2(const double* d_r2, int64_t count, double dof, double* d_lnp, void* stream) {
+	nrm_pvalue_plan plan;
+	int rc = nrm_pvalue_plan_init(&plan, dof);
+	if (rc) return rc;
+	if (count <= 0) return NRM_OK;
+	NRM_REQUIRE(d_r2 && d_lnp, "nrm_logpvalues_from_r2: null pointer");
+	int grid = (int)((count + 255) / 256);
+	if (grid > 4096) grid = 4096;
+	hipLaunchKernelGGL(k_logpvalues_from_r2, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_r2, count, to_dev(plan), d_lnp);
+	return nrm_check_launch("k_logpvalues_from_r2");
+}
+
+#define NRM_REQUIRE_PKIND(k) NRM_REQUIRE((k) == 0 || (k) == 1, "p_kind must be 0 (P-values) or 1 (their natural logarithms)")
+
+extern "C" int nrm_assoc_sweep_band_pk(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t nx,
 									int64_t ny, int64_t n_cells, double dof, int symmetric, int stat_kind, void* d_p,
 									void* d_stat, void* d_r, void* d_t, int out_dtype, int64_t ldo, int32_t* d_flags,
 									int64_t row0, int64_t row1, int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol,
-									void* stream) {
+									int p_kind, void* stream) {
+	NRM_REQUIRE_PKIND(p_kind);
 	NRM_REQUIRE(nx >= 0 && ny >= 0 && n_cells > 0, "nrm_assoc_sweep: bad sizes");
 	NRM_REQUIRE(fix_nslices == 0 || ((fix_nslices == 5 || fix_nslices == 6) && d_fixx && d_fixy && d_flags), "nrm_assoc_sweep: row records need 5 or 6 slices, both tables and flags");
 	const FixArgs fix = nrm_fix_args(fix_nslices ? d_fixx : nullptr, d_fixy, fix_nslices, n_cells, dof, guard_tol);
@@ -564,22 +600,58 @@ extern "C" int nrm_assoc_sweep_band(const double* d_dot, int64_t ldd, const doub
 		const int64_t nb = (nx + SW_T - 1) / SW_T;
 		const unsigned tiles = (unsigned)((b1 - b0) * nb - (b1 * (b1 - 1) - b0 * (b0 - 1)) / 2);
 		// pieces of 32 rows: 0.185 ms on BASELINE configs[1] against 0.196 with whole tiles (tools/k3_time.py), 16 rows gain nothing more
-		if (out_dtype == NRM_F64)
-			hipLaunchKernelGGL((k_assoc_sweep_sym<double, 32>), dim3(tiles * 2), dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, nx, (int)nb,
-							   (double)n_cells, to_dev(plan), (double*)d_p, (double*)d_stat, ldo, d_flags, (int)b0, fix);
-		else
-			hipLaunchKernelGGL((k_assoc_sweep_sym<float, 32>), dim3(tiles * 2), dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, nx, (int)nb,
-							   (double)n_cells, to_dev(plan), (float*)d_p, (float*)d_stat, ldo, d_flags, (int)b0, fix);
+		auto launch = [&](auto kernel, auto* out) {
+			using O = std::remove_pointer_t<decltype(out)>;
+			hipLaunchKernelGGL(kernel, dim3(tiles * 2), dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, nx, (int)nb, (double)n_cells, to_dev(plan), (O*)d_p,
+							   (O*)d_stat, ldo, d_flags, (int)b0, fix);
+		};
+		if (out_dtype == NRM_F64) {
+			if (p_kind)
+				launch(k_assoc_sweep_sym<double, 32, 1>, (double*)nullptr);
+			else
+				launch(k_assoc_sweep_sym<double, 32, 0>, (double*)nullptr);
+		} else {
+			if (p_kind)
+				launch(k_assoc_sweep_sym<float, 32, 1>, (float*)nullptr);
+			else
+				launch(k_assoc_sweep_sym<float, 32, 0>, (float*)nullptr);
+		}
 		return nrm_check_launch("k_assoc_sweep_sym");
 	}
 	dim3 grid((unsigned)((ny + SW_T - 1) / SW_T), (unsigned)(b1 - b0));
-	if (out_dtype == NRM_F64)
-		hipLaunchKernelGGL(k_assoc_sweep<double>, grid, dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, d_ssy, nx, ny,
-						   (double)n_cells, dof, symmetric, stat_kind, to_dev(plan), d_p, d_stat, d_r, d_t, ldo, d_flags, (int)b0, fix);
-	else
-		hipLaunchKernelGGL(k_assoc_sweep<float>, grid, dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, d_ssy, nx, ny,
-						   (double)n_cells, dof, symmetric, stat_kind, to_dev(plan), d_p, d_stat, d_r, d_t, ldo, d_flags, (int)b0, fix);
+	auto launch = [&](auto kernel) {
+		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, d_ssy, nx, ny, (double)n_cells, dof, symmetric, stat_kind, to_dev(plan), d_p,
+						   d_stat, d_r, d_t, ldo, d_flags, (int)b0, fix);
+	};
+	if (out_dtype == NRM_F64) {
+		if (p_kind)
+			launch(k_assoc_sweep<double, 1>);
+		else
+			launch(k_assoc_sweep<double, 0>);
+	} else {
+		if (p_kind)
+			launch(k_assoc_sweep<float, 1>);
+		else
+			launch(k_assoc_sweep<float, 0>);
+	}
 	return nrm_check_launch("k_assoc_sweep");
+}
+
+extern "C" int nrm_assoc_sweep_band(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t nx,
+									int64_t ny, int64_t n_cells, double dof, int symmetric, int stat_kind, void* d_p,
+									void* d_stat, void* d_r, void* d_t, int out_dtype, int64_t ldo, int32_t* d_flags,
+									int64_t row0, int64_t row1, int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol,
+									void* stream) {
+	return nrm_assoc_sweep_band_pk(d_dot, ldd, d_ssx, d_ssy, nx, ny, n_cells, dof, symmetric, stat_kind, d_p, d_stat, d_r, d_t, out_dtype, ldo, d_flags, row0, row1,
+								   fix_nslices, d_fixx, d_fixy, guard_tol, 0, stream);
+}
+
+extern "C" int nrm_assoc_sweep_pk(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t nx,
+								  int64_t ny, int64_t n_cells, double dof, int symmetric, int stat_kind, void* d_p,
+								  void* d_stat, void* d_r, void* d_t, int out_dtype, int64_t ldo, int32_t* d_flags,
+								  int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol, int p_kind, void* stream) {
+	return nrm_assoc_sweep_band_pk(d_dot, ldd, d_ssx, d_ssy, nx, ny, n_cells, dof, symmetric, stat_kind, d_p, d_stat, d_r, d_t, out_dtype, ldo, d_flags, 0, nx, fix_nslices,
+								   d_fixx, d_fixy, guard_tol, p_kind, stream);
 }
 
 extern "C" int nrm_assoc_sweep(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t nx,
@@ -590,9 +662,10 @@ extern "C" int nrm_assoc_sweep(const double* d_dot, int64_t ldd, const double* d
 								ldo, d_flags, 0, nx, fix_nslices, d_fixx, d_fixy, guard_tol, stream);
 }
 
-extern "C" int nrm_assoc_sweep_mirror(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t mx, int64_t my,
-									  int64_t n_cells, double dof, void* d_p, void* d_stat, int out_dtype, int64_t ldo, int64_t r0, int64_t c0,
-									  int32_t* d_flags, int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol, void* stream) {
+extern "C" int nrm_assoc_sweep_mirror_pk(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t mx, int64_t my,
+										 int64_t n_cells, double dof, void* d_p, void* d_stat, int out_dtype, int64_t ldo, int64_t r0, int64_t c0,
+										 int32_t* d_flags, int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol, int p_kind, void* stream) {
+	NRM_REQUIRE_PKIND(p_kind);
 	NRM_REQUIRE(fix_nslices == 0 || ((fix_nslices == 5 || fix_nslices == 6) && d_fixx && d_fixy && d_flags), "nrm_assoc_sweep: row records need 5 or 6 slices, both tables and flags");
 	const FixArgs fix = nrm_fix_args(fix_nslices ? d_fixx : nullptr, d_fixy, fix_nslices, n_cells, dof, guard_tol);
 	NRM_REQUIRE(mx >= 0 && my >= 0 && n_cells > 0 && r0 >= 0 && c0 >= 0 && c0 + my <= r0, "nrm_assoc_sweep_mirror: the rectangle must lie below the diagonal");
@@ -603,13 +676,30 @@ extern "C" int nrm_assoc_sweep_mirror(const double* d_dot, int64_t ldd, const do
 	if (mx == 0 || my == 0) return NRM_OK;
 	NRM_REQUIRE(d_dot && d_ssx && d_ssy && d_p && d_stat && ldd >= my && ldo >= r0 + mx, "nrm_assoc_sweep_mirror: null pointer or small pitch");
 	dim3 grid((unsigned)((my + SW_T - 1) / SW_T), (unsigned)((mx + SW_T - 1) / SW_T));
-	if (out_dtype == NRM_F64)
-		hipLaunchKernelGGL(k_assoc_sweep_mirror<double>, grid, dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, d_ssy, mx, my, (double)n_cells,
-						   to_dev(plan), (double*)d_p, (double*)d_stat, ldo, r0, c0, d_flags, fix);
-	else
-		hipLaunchKernelGGL(k_assoc_sweep_mirror<float>, grid, dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, d_ssy, mx, my, (double)n_cells,
-						   to_dev(plan), (float*)d_p, (float*)d_stat, ldo, r0, c0, d_flags, fix);
+	auto launch = [&](auto kernel, auto* out) {
+		using O = std::remove_pointer_t<decltype(out)>;
+		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, d_dot, ldd, d_ssx, d_ssy, mx, my, (double)n_cells, to_dev(plan), (O*)d_p, (O*)d_stat, ldo, r0,
+						   c0, d_flags, fix);
+	};
+	if (out_dtype == NRM_F64) {
+		if (p_kind)
+			launch(k_assoc_sweep_mirror<double, 1>, (double*)nullptr);
+		else
+			launch(k_assoc_sweep_mirror<double, 0>, (double*)nullptr);
+	} else {
+		if (p_kind)
+			launch(k_assoc_sweep_mirror<float, 1>, (float*)nullptr);
+		else
+			launch(k_assoc_sweep_mirror<float, 0>, (float*)nullptr);
+	}
 	return nrm_check_launch("k_assoc_sweep_mirror");
+}
+
+extern "C" int nrm_assoc_sweep_mirror(const double* d_dot, int64_t ldd, const double* d_ssx, const double* d_ssy, int64_t mx, int64_t my,
+									  int64_t n_cells, double dof, void* d_p, void* d_stat, int out_dtype, int64_t ldo, int64_t r0, int64_t c0,
+									  int32_t* d_flags, int fix_nslices, const double* d_fixx, const double* d_fixy, double guard_tol, void* stream) {
+	return nrm_assoc_sweep_mirror_pk(d_dot, ldd, d_ssx, d_ssy, mx, my, n_cells, dof, d_p, d_stat, out_dtype, ldo, r0, c0, d_flags, fix_nslices, d_fixx, d_fixy, guard_tol, 0,
+									 stream);
 }
 
 extern "C" int nrm_alpha(const void* d_stat, int stat_dtype, int64_t ldg, int stat_kind, const double* d_ssx, int64_t n_cells,
@@ -632,9 +722,10 @@ extern "C" int nrm_alpha(const void* d_stat, int stat_dtype, int64_t ldg, int st
 	return nrm_check_launch("k_alpha");
 }
 
-extern "C" int nrm_de_small_sweep(const double* d_g, const double* d_ssraw, const double* d_dci, int64_t nc, int rank, const double* d_ssx,
-								  int64_t nx, int64_t ny, int64_t n_cells, double dof, int stat_kind, void* d_p, void* d_stat, void* d_r,
-								  void* d_t, int out_dtype, int64_t ldo, double* d_ssy, double* d_by, int32_t* d_flags, int const_last, void* stream) {
+extern "C" int nrm_de_small_sweep_pk(const double* d_g, const double* d_ssraw, const double* d_dci, int64_t nc, int rank, const double* d_ssx,
+									 int64_t nx, int64_t ny, int64_t n_cells, double dof, int stat_kind, void* d_p, void* d_stat, void* d_r,
+									 void* d_t, int out_dtype, int64_t ldo, double* d_ssy, double* d_by, int32_t* d_flags, int const_last, int p_kind, void* stream) {
+	NRM_REQUIRE_PKIND(p_kind);
 	NRM_REQUIRE(nx > 0 && ny > 0 && nc >= 0 && nx + nc <= DS_NZ, "nrm_de_small_sweep: needs nx + nc <= %d", DS_NZ);
 	NRM_REQUIRE(!const_last || nc >= 1, "nrm_de_small_sweep: const_last needs a covariate");
 	NRM_REQUIRE(out_dtype == NRM_F32 || out_dtype == NRM_F64, "nrm_de_small_sweep: bad out_dtype");
@@ -645,13 +736,28 @@ extern "C" int nrm_de_small_sweep(const double* d_g, const double* d_ssraw, cons
 	if (rc) return rc;
 	const int rank_pos = (rank > 0 && nc > 0) ? 1 : 0;
 	dim3 grid((unsigned)((ny + 255) / 256));
-	if (out_dtype == NRM_F64)
-		hipLaunchKernelGGL(k_de_small_sweep<double>, grid, dim3(256), 0, (hipStream_t)stream, d_g, d_ssraw, d_dci, (int)nc, rank_pos, d_ssx,
-						   (int)nx, ny, (double)n_cells, dof, stat_kind, to_dev(plan), (double*)d_p, (double*)d_stat, (double*)d_r,
-						   (double*)d_t, ldo, d_ssy, d_by, d_flags, const_last);
-	else
-		hipLaunchKernelGGL(k_de_small_sweep<float>, grid, dim3(256), 0, (hipStream_t)stream, d_g, d_ssraw, d_dci, (int)nc, rank_pos, d_ssx,
-						   (int)nx, ny, (double)n_cells, dof, stat_kind, to_dev(plan), (float*)d_p, (float*)d_stat, (float*)d_r,
-						   (float*)d_t, ldo, d_ssy, d_by, d_flags, const_last);
+	auto launch = [&](auto kernel, auto* out) {
+		using O = std::remove_pointer_t<decltype(out)>;
+		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, d_g, d_ssraw, d_dci, (int)nc, rank_pos, d_ssx, (int)nx, ny, (double)n_cells, dof, stat_kind,
+						   to_dev(plan), (O*)d_p, (O*)d_stat, (O*)d_r, (O*)d_t, ldo, d_ssy, d_by, d_flags, const_last);
+	};
+	if (out_dtype == NRM_F64) {
+		if (p_kind)
+			launch(k_de_small_sweep<double, 1>, (double*)nullptr);
+		else
+			launch(k_de_small_sweep<double, 0>, (double*)nullptr);
+	} else {
+		if (p_kind)
+			launch(k_de_small_sweep<float, 1>, (float*)nullptr);
+		else
+			launch(k_de_small_sweep<float, 0>, (float*)nullptr);
+	}
 	return nrm_check_launch("k_de_small_sweep");
+}
+
+extern "C" int nrm_de_small_sweep(const double* d_g, const double* d_ssraw, const double* d_dci, int64_t nc, int rank, const double* d_ssx,
+								  int64_t nx, int64_t ny, int64_t n_cells, double dof, int stat_kind, void* d_p, void* d_stat, void* d_r,
+								  void* d_t, int out_dtype, int64_t ldo, double* d_ssy, double* d_by, int32_t* d_flags, int const_last, void* stream) {
+	return nrm_de_small_sweep_pk(d_g, d_ssraw, d_dci, nc, rank, d_ssx, nx, ny, n_cells, dof, stat_kind, d_p, d_stat, d_r, d_t, out_dtype, ldo, d_ssy, d_by, d_flags, const_last,
+								 0, stream);
 }

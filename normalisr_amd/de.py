@@ -110,20 +110,34 @@ def _de_sparse_design(dg, dt, dc, bs, ka):
 		gid, h = _varying_rows_device(design)
 		sub = design if gid.all() else _device_rows(design, gid, h)
 	res = association_tests(sub, dt, dc, bsx=bs, bsy=bs, return_dot=False, **ka)
-	return _inflate(gid, res, dg.shape[0], dt, dc.shape[0])
+	return _inflate(gid, res, dg.shape[0], dt, dc.shape[0], logp=bool(ka.get('logp', False)))
 
 
-def _inflate(gid, res, ng0, dt, nc):
-	"""The results of the tested rows put back among all groupings (de.py:107-122) and the reference's assertions on them (de.py:124-131)."""
+def _logp_within(a):
+	"""The assertion on P-values for their logarithms (logp=True): no NaN and nothing above 0; -inf is a value (P = 0 that is no underflow)."""
+	if a.size == 0:
+		return True
+	if a.size >= (1 << 18) and a.dtype in (np.float32, np.float64) and a.flags.c_contiguous:
+		from . import _lib
+		out = np.empty(3)
+		_lib.check(_lib.load().nrm_host_minmax(a.ctypes.data, _engine.dtype_code(a), a.size, 0, out.ctypes.data))
+		return bool(out[2] == 0 and out[1] <= 0)
+	return bool(a.max() <= 0)  # (a NaN anywhere makes the maximum NaN and the comparison False)
+
+
+def _inflate(gid, res, ng0, dt, nc, logp=False):
+	"""The results of the tested rows put back among all groupings (de.py:107-122) and the reference's assertions on them (de.py:124-131).
+	logp: the first array holds ln P -- rows that were not tested get ln 1 = 0, and the assertion on it is "no NaN and <= 0"."""
+	p_ok = _logp_within if logp else (lambda a: _finite_within(a, 0, 1))
 	p, gam, alpha, varg, vart = res
 	nt = dt.shape[0]
 	odt = dt.dtype if dt.dtype in (np.float32, np.float64) else np.dtype(np.float64)
 	if bool(gid.all()) and p.dtype == odt:  # nothing to re-inflate (de.py:107-122 is the identity then)
 		P, G, A, VG = p, gam, alpha, varg
 		VT = vart if np.ndim(vart) == 2 else np.broadcast_to(vart, (ng0, nt)).copy()  # single=0: (n_gene,) for every row (SURVEY Q5)
-		assert _finite_within(P, 0, 1) and _finite_within(G) and _finite_within(VG, 0) and _finite_within(VT, 0)
+		assert p_ok(P) and _finite_within(G) and _finite_within(VG, 0) and _finite_within(VT, 0)
 		return (P, G, A, VG, VT)
-	P = np.ones((ng0, nt), dtype=odt)
+	P = np.zeros((ng0, nt), dtype=odt) if logp else np.ones((ng0, nt), dtype=odt)
 	P[gid] = p
 	G = np.zeros((ng0, nt), dtype=odt)
 	G[gid] = gam
@@ -135,7 +149,7 @@ def _inflate(gid, res, ng0, dt, nc):
 	VG[gid] = varg
 	VT = np.zeros((ng0, nt), dtype=odt)
 	VT[gid] = vart  # (n_gene,) for single=0 broadcasts to every tested row
-	assert _finite_within(P, 0, 1) and _finite_within(G) and _finite_within(VG, 0) and _finite_within(VT, 0)
+	assert p_ok(P) and _finite_within(G) and _finite_within(VG, 0) and _finite_within(VT, 0)
 	return (P, G, A, VG, VT)
 
 
@@ -167,10 +181,14 @@ def de(dg, dt, dc, bs=0, **ka):
 	varg (n_group,), vart (n_group,n_gene)).  Keyword arguments single, lowmem, nth, dimreduce, tol, ...
 	are passed to association_tests.  Single-valued grouping rows are not tested and come back with
 	p=1, gamma=0, alpha=0, varg=0, vart=0 (de.py:107-122).
+	logp=True (single=0 only): the first result holds ln P, finite wherever P is a number other than an exact 0; rows that are not
+	tested come back with ln P = 0.
 	dg may be sparse -- a scipy.sparse matrix, a de_sparse.DesignCSR or a torch.sparse_csr CUDA tensor: the results are those of the densified
 	matrix, and the dense matrix is never formed on the host (DESIGN.md section 4c says which routes scatter it on the device).
 	"""
 	from . import de_sparse
+	if ka.get('logp', False) and ka.get('single', 0) != 0:  # (before the row filter, which for a design in HBM runs on the device)
+		raise NotImplementedError('logp=True is available for single=0 only (single=1, 4 and 5 return P-values).')
 	if de_sparse.is_sparse_design(dg):
 		return _de_sparse_design(dg, dt, dc, bs, ka)
 	dg0 = np.asarray(dg)
@@ -181,7 +199,7 @@ def de(dg, dt, dc, bs=0, **ka):
 	gid = _varying_rows(dg0)
 	allrows = bool(gid.all())
 	res = association_tests(dg0 if allrows else dg0[gid], dt, dc, bsx=bs, bsy=bs, return_dot=False, **ka)
-	return _inflate(gid, res, dg0.shape[0], dt, dc.shape[0])
+	return _inflate(gid, res, dg0.shape[0], dt, dc.shape[0], logp=bool(ka.get('logp', False)))
 
 
 assert __name__ != "__main__"

@@ -334,7 +334,8 @@ class CoexPlan:
 	step() runs one full pass and leaves the outputs of this rank's block pairs in self.outputs:
 	list of dict(bi, bj, row_lo, nx, ny, symmetric, p, stat)."""
 
-	def __init__(self, dt_local, dc, rank=0, world=1, group=None, backend=None, dimreduce=0, out_dtype=None):
+	def __init__(self, dt_local, dc, rank=0, world=1, group=None, backend=None, dimreduce=0, out_dtype=None, logp=False):
+		_opts.refuse_logp(logp, 'distributed.CoexPlan')
 		self.rank, self.world, self.group = rank, world, group
 		self.be = backend if backend is not None else HipBackend(dt_local.device.index)
 		self.x = dt_local
@@ -787,7 +788,8 @@ class DePlan:
 	from dx's values -- so a write to dx (torch counts it in ._version) drops the graph, those lists and a refusal of the sparse kernels, and
 	the next step decides again (eagerly) and the one after it captures again."""
 
-	def __init__(self, dx, dy_local, dc, rank=0, world=1, dimreduce=0, return_dot=False, device=None):
+	def __init__(self, dx, dy_local, dc, rank=0, world=1, dimreduce=0, return_dot=False, device=None, logp=False):
+		_opts.refuse_logp(logp, 'distributed.DePlan')
 		from .association import _prepare_covariates
 		from .engine import get_engine
 		self.rank, self.world = rank, world
@@ -909,7 +911,7 @@ def _certified_coex_step(x, dc, rank, world, group, dimreduce):
 	return plan
 
 
-def coex(dt_local, dc, group=None, dimreduce=0, out_dir=None):
+def coex(dt_local, dc, group=None, dimreduce=0, out_dir=None, logp=False):
 	"""Sharded norm.coex for one-process-per-GPU programs: every rank passes ITS block of gene rows (same row count on
 	every rank; numpy or a torch tensor on its GPU) and the replicated covariates.  Rank 0 gets (p, dot, var) as numpy
 	arrays with the reference's contract (symmetric, zero diagonals; coex.py:4-48); other ranks get None.  Every rank
@@ -919,6 +921,7 @@ def coex(dt_local, dc, group=None, dimreduce=0, out_dir=None):
 	    dist.init_process_group('nccl'); torch.cuda.set_device(local_rank)
 	    res = normalisr_amd.distributed.coex(dt[rank * R:(rank + 1) * R], dc)
 	"""
+	_opts.refuse_logp(logp, 'distributed.coex')
 	import torch
 	rank, world, group = _world(group)
 	dev = torch.device('cuda', torch.cuda.current_device())
@@ -926,11 +929,12 @@ def coex(dt_local, dc, group=None, dimreduce=0, out_dir=None):
 	return plan.assemble(out_dir=out_dir)
 
 
-def coex_binnet(dt_local, dc, qcut, group=None, dimreduce=0, out_dir=None):
+def coex_binnet(dt_local, dc, qcut, group=None, dimreduce=0, out_dir=None, logp=False):
 	"""coex -> binnet as one sharded device pipeline (examples/GSE123139/code/cmd_coex.sh:40-42 chains the two through a
 	P-value file): every rank completes its rows of the P-value matrix in HBM and binarises them there (per-row BH,
 	binnet.py:134-173), so the n_gene^2 P-values never cross PCIe -- only one byte per pair does.  Rank 0 gets the boolean
 	(n_gene, n_gene) network (net.npy in out_dir if given), other ranks None."""
+	_opts.refuse_logp(logp, 'distributed.coex_binnet')
 	import torch
 	rank, world, group = _world(group)
 	dev = torch.device('cuda', torch.cuda.current_device())
@@ -986,12 +990,13 @@ def _de_other_methods(dg, dt_local, dc, group, dimreduce, out_dir, single, ka):
 	return None if out is None else (out['p'], out['gamma'], None, out['varg'], out['vart'])
 
 
-def de(dg, dt_local, dc, group=None, dimreduce=0, out_dir=None, single=0, **ka):
+def de(dg, dt_local, dc, group=None, dimreduce=0, out_dir=None, single=0, logp=False, **ka):
 	"""Sharded norm.de for one-process-per-GPU programs: every rank passes the full grouping matrix dg, ITS
 	block of gene rows of dt (numpy or a torch tensor on its GPU; the blocks may differ in size) and the replicated
 	covariates.  No collective on the data path; every rank writes its gene columns into result arrays shared by the ranks
 	and rank 0 returns (p, gamma, None, varg, vart) with the reference's contract (de.py:4-132, constant groupings
 	re-inflated), other ranks get None.  single = 0 (resident DePlan), 1 or 4 (see _de_other_methods)."""
+	_opts.refuse_logp(logp, 'distributed.de')
 	if single not in (0, 1, 4):
 		raise ValueError('Unknown value single={}'.format(single))
 	from . import de_sparse

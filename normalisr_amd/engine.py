@@ -615,7 +615,7 @@ class Engine:
 		return (isinstance(dy, np.ndarray) and dy.nbytes >= 2 * self.CHUNK_BYTES and _opts.debug('pipeline', '1') != '0')
 
 	@serialised
-	def association_de_chunked(self, dx, dy, dc, dci, rank, dof, stat_kind, out_dtype, cov=None):
+	def association_de_chunked(self, dx, dy, dc, dci, rank, dof, stat_kind, out_dtype, cov=None, p_kind=0):
 		"""General de path with the expression rows streamed from the host: every chunk of genes is an independent
 		problem against the same residualised design rows (association.py:890-909: the reference's tiles are independent
 		in the same way), so the H2D leg -- the longest leg of a one-shot call -- hides the kernels."""
@@ -645,9 +645,9 @@ class Engine:
 				yc.record_stream(main)
 				ry = self.residualize(yc, d_c, d_dci, rank, nslices=self.gram_slices(n), keep_fp64=False)
 				dot = self.gram(rx, ry, False, nslices=self.gram_slices(n))
-				_lib.check(self.lib.nrm_assoc_sweep(dot.data_ptr(), dot.stride(0), rx.ss.data_ptr(), ry.ss.data_ptr(), nx, b - a, int(n),
-													float(dof), 0, int(stat_kind), p.data_ptr() + a * esz, stat.data_ptr() + a * esz, 0, 0,
-													dtype_code(out_dtype), ny, flags.data_ptr(), *self.fix_args(rx, ry), self._stream()))
+				_lib.check(self.lib.nrm_assoc_sweep_pk(dot.data_ptr(), dot.stride(0), rx.ss.data_ptr(), ry.ss.data_ptr(), nx, b - a, int(n),
+													   float(dof), 0, int(stat_kind), p.data_ptr() + a * esz, stat.data_ptr() + a * esz, 0, 0,
+													   dtype_code(out_dtype), ny, flags.data_ptr(), *self.fix_args(rx, ry), int(p_kind), self._stream()))
 				_lib.check(self.lib.nrm_copy_rows(ssy.data_ptr() + a * 8, 8 * (b - a), ry.ss.data_ptr(), 8 * (b - a), 8 * (b - a), 1, self._stream()))
 			self.check_flags(flags)
 			return dict(p=self.download(p), stat=self.download(stat), alpha=None, varx=self.variances(rx.ss, nx, n, out_dtype),
@@ -691,7 +691,7 @@ class Engine:
 		host['pinned'] = []
 
 	@serialised
-	def association_banded(self, rx, ry, samexy, nx, ny, n, dof, stat_kind, out_dtype, host):
+	def association_banded(self, rx, ry, samexy, nx, ny, n, dof, stat_kind, out_dtype, host, p_kind=0):
 		"""K2 + K3 band by band on the compute stream while finished bands of p and stat travel to the page-locked result
 		arrays on a copy stream.  Same kernels as the one-launch path; K2's split of the cells between workgroups depends
 		on the tiles of a launch, so dot may differ from it in the last bits (each path is bitwise reproducible)."""
@@ -711,9 +711,9 @@ class Engine:
 				done = []
 				for a, b in zip(cuts[:-1], cuts[1:]):
 					self.gram(rx, ry, samexy, dot=dot, rows=(a, rx.rows_pad if b == nx else b), nslices=self.gram_slices(n))
-					_lib.check(self.lib.nrm_assoc_sweep_band(dot.data_ptr(), dot.stride(0), rx.ss.data_ptr(), ry.ss.data_ptr(), nx, ny, int(n),
-															 float(dof), 1 if samexy else 0, int(stat_kind), p.data_ptr(), stat.data_ptr(), 0, 0,
-															 dtype_code(out_dtype), max(ny, 1), flags.data_ptr(), a, b, *self.fix_args(rx, ry), self._stream()))
+					_lib.check(self.lib.nrm_assoc_sweep_band_pk(dot.data_ptr(), dot.stride(0), rx.ss.data_ptr(), ry.ss.data_ptr(), nx, ny, int(n),
+																float(dof), 1 if samexy else 0, int(stat_kind), p.data_ptr(), stat.data_ptr(), 0, 0,
+																dtype_code(out_dtype), max(ny, 1), flags.data_ptr(), a, b, *self.fix_args(rx, ry), int(p_kind), self._stream()))
 					ev = torch.cuda.Event()
 					ev.record(main)
 					done.append(ev)
@@ -739,7 +739,7 @@ class Engine:
 				and dx.nbytes >= (32 << 20) and (dx.shape[1] * dx.itemsize) % 16 == 0 and (dc.shape[0] == 0 or (dc.shape[1] * 8) % 16 == 0))
 
 	@serialised
-	def association_coex_pipelined(self, dx, dc, dci, rank, dimreduce, out_dtype, cov=None):
+	def association_coex_pipelined(self, dx, dc, dci, rank, dimreduce, out_dtype, cov=None, p_kind=0):
 		"""norm.coex, numpy in -> numpy out, with the three PCIe / compute legs overlapped.  The gene rows travel to the GPU in
 		chunks of BAND rows on a copy stream; as soon as chunk c = rows [a, b) has landed, K1 residualises and quantises it, K2
 		contracts it with itself (symmetric) and with all earlier rows [0, a) (a rectangle), K3 turns both into P-values --
@@ -840,14 +840,15 @@ class Engine:
 					self.residualize_into(whole, a, xc, d_c, d_dci, rank)
 					blk = self.row_block(whole, a, a + rpc, rows=b - a)
 					dot = self.gram(blk, blk, True, nslices=ns)
-					_lib.check(self.lib.nrm_assoc_sweep(dot.data_ptr(), dot.stride(0), blk.ss.data_ptr(), blk.ss.data_ptr(), b - a, b - a, int(n), float(dof), 1, 0,
-														p.data_ptr() + (a * ng + a) * esz, stat.data_ptr() + (a * ng + a) * esz, 0, 0, code, ng, flags.data_ptr(),
-														*self.fix_args(blk, blk), self._stream()))
+					_lib.check(self.lib.nrm_assoc_sweep_pk(dot.data_ptr(), dot.stride(0), blk.ss.data_ptr(), blk.ss.data_ptr(), b - a, b - a, int(n), float(dof), 1, 0,
+														   p.data_ptr() + (a * ng + a) * esz, stat.data_ptr() + (a * ng + a) * esz, 0, 0, code, ng, flags.data_ptr(),
+														   *self.fix_args(blk, blk), int(p_kind), self._stream()))
 					if a > 0:
 						prev = self.row_block(whole, 0, a, rows=a)
 						dot2 = self.gram(blk, prev, False, nslices=ns)
-						_lib.check(self.lib.nrm_assoc_sweep_mirror(dot2.data_ptr(), dot2.stride(0), blk.ss.data_ptr(), ss.data_ptr(), b - a, a, int(n), float(dof),
-																   p.data_ptr(), stat.data_ptr(), code, ng, a, 0, flags.data_ptr(), *self.fix_args(blk, prev), self._stream()))
+						_lib.check(self.lib.nrm_assoc_sweep_mirror_pk(dot2.data_ptr(), dot2.stride(0), blk.ss.data_ptr(), ss.data_ptr(), b - a, a, int(n), float(dof),
+																	  p.data_ptr(), stat.data_ptr(), code, ng, a, 0, flags.data_ptr(), *self.fix_args(blk, prev), int(p_kind),
+																	  self._stream()))
 					done = torch.cuda.Event()
 					done.record(main)
 					pending.append((ci, a, b, done))
@@ -876,12 +877,13 @@ class Engine:
 			return res
 
 	@serialised
-	def coex_blocks_resident(self, block_fn, n_genes, n, dc, dci, rank, dimreduce, out_dtype, block_rows=3840, timings=None):
+	def coex_blocks_resident(self, block_fn, n_genes, n, dc, dci, rank, dimreduce, out_dtype, block_rows=3840, timings=None, logp=False):
 		"""coex of a matrix that is too large to sit in HBM next to its own digit planes (BASELINE configs[4]: 30 000 genes x 500 000
 		cells fp64 = 120 GB in, 90 GB of planes) on ONE GPU: the gene rows arrive block by block -- block_fn(lo, hi) returns rows
 		[lo, hi) as a device tensor, which is dropped as soon as K1 has residualised and quantised it into the resident planes -- then
 		K2 and K3 run band by band over the whole symmetric problem (the reference walks the same pair space tile by tile,
-		association.py:890-909).  Results stay in HBM: dict(p, stat = covariance, ss, flags).  block_rows: a multiple of 128."""
+		association.py:890-909).  Results stay in HBM: dict(p, stat = covariance, ss, flags).  block_rows: a multiple of 128.  logp: p holds ln P."""
+		p_kind = 1 if logp else 0
 		torch = self.torch
 		ns = self.gram_slices(n)
 		assert ns, 'coex_blocks_resident runs on the integer engine (2048 <= cells < 2^22)'
@@ -919,9 +921,9 @@ class Engine:
 			for a, b in zip(cuts[:-1], cuts[1:]):
 				self.gram(whole, whole, True, dot=dot, rows=(a, mp if b == n_genes else b), nslices=ns)
 				with _Span(self, 'sweep'):
-					_lib.check(self.lib.nrm_assoc_sweep_band(dot.data_ptr(), dot.stride(0), ss.data_ptr(), ss.data_ptr(), n_genes, n_genes, int(n), float(dof), 1, 0,
-															 p.data_ptr(), stat.data_ptr(), 0, 0, dtype_code(out_dtype), n_genes, flags.data_ptr(), a, b,
-															 *self.fix_args(whole, whole), self._stream()))
+					_lib.check(self.lib.nrm_assoc_sweep_band_pk(dot.data_ptr(), dot.stride(0), ss.data_ptr(), ss.data_ptr(), n_genes, n_genes, int(n), float(dof), 1, 0,
+																p.data_ptr(), stat.data_ptr(), 0, 0, dtype_code(out_dtype), n_genes, flags.data_ptr(), a, b,
+																*self.fix_args(whole, whole), int(p_kind), self._stream()))
 			mark('swept')
 			if timings is not None:
 				torch.cuda.synchronize(self.device)
@@ -930,7 +932,7 @@ class Engine:
 			return dict(p=p, stat=stat, ss=ss, flags=flags, dof=dof, dot=dot)
 
 	@serialised
-	def sweep(self, dot, ssx, ssy, nx, ny, n_cells, dof, symmetric, stat_kind, out_dtype, want_rt=False, flags=None, fix=None):
+	def sweep(self, dot, ssx, ssy, nx, ny, n_cells, dof, symmetric, stat_kind, out_dtype, want_rt=False, flags=None, fix=None, p_kind=0):
 		"""K3: p, stat (covariance or gamma) and optionally Pearson r and t for every pair.  fix = fix_args(rx, ry) when dot came
 		from the integer engine."""
 		torch = self.torch
@@ -942,11 +944,11 @@ class Engine:
 			t = torch.empty((nx, ny), dtype=tdt, device=self.device) if want_rt else None
 			if flags is None:
 				flags = self.new_flags()
-			_lib.check(self.lib.nrm_assoc_sweep(dot.data_ptr(), dot.stride(0), ssx.data_ptr(), ssy.data_ptr(), nx, ny,
-												int(n_cells), float(dof), 1 if symmetric else 0, int(stat_kind),
-												p.data_ptr(), stat.data_ptr(), 0 if r is None else r.data_ptr(),
-												0 if t is None else t.data_ptr(), dtype_code(out_dtype), max(ny, 1),
-												flags.data_ptr(), *(fix if fix is not None else (0, 0, 0, 0.0)), self._stream()))
+			_lib.check(self.lib.nrm_assoc_sweep_pk(dot.data_ptr(), dot.stride(0), ssx.data_ptr(), ssy.data_ptr(), nx, ny,
+												   int(n_cells), float(dof), 1 if symmetric else 0, int(stat_kind),
+												   p.data_ptr(), stat.data_ptr(), 0 if r is None else r.data_ptr(),
+												   0 if t is None else t.data_ptr(), dtype_code(out_dtype), max(ny, 1),
+												   flags.data_ptr(), *(fix if fix is not None else (0, 0, 0, 0.0)), int(p_kind), self._stream()))
 		return p, stat, r, t, flags
 
 	@serialised
@@ -1027,7 +1029,7 @@ class Engine:
 
 	@serialised
 	def association_de_streaming(self, dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt=False, cov=None,
-								 resident=False, state=None):
+								 resident=False, state=None, p_kind=0):
 		"""de with nx + nc <= 32: stream the raw expression rows once (HBM-bound), see csrc/nrm_gram_skinny.hip.
 		state: a dict owned by the caller that keeps the buffers worth keeping between calls on the same covariates (the permuted
 		covariates, the Z buffer).  A DePlan passes its own, so that the pointers its captured HIP graph holds live exactly as long
@@ -1106,10 +1108,11 @@ class Engine:
 			by = self.zeros((ny, nc), torch.float64) if (want_alpha and nc) else None
 			flags = self.new_flags()
 			stat_kind = 0 if return_dot else 1
-			_lib.check(self.lib.nrm_de_small_sweep(g.data_ptr(), ssraw.data_ptr(), 0 if d_dciz is None else d_dciz.data_ptr(), nc, int(rank),
-												   rx.ss.data_ptr(), nx, ny, n, float(dof), stat_kind, p.data_ptr(), stat.data_ptr(),
-												   0 if r is None else r.data_ptr(), 0 if t is None else t.data_ptr(), dtype_code(out_dtype),
-												   ny, ssy.data_ptr(), 0 if by is None else by.data_ptr(), flags.data_ptr(), 1 if ci >= 0 else 0, self._stream()))
+			_lib.check(self.lib.nrm_de_small_sweep_pk(g.data_ptr(), ssraw.data_ptr(), 0 if d_dciz is None else d_dciz.data_ptr(), nc, int(rank),
+													  rx.ss.data_ptr(), nx, ny, n, float(dof), stat_kind, p.data_ptr(), stat.data_ptr(),
+													  0 if r is None else r.data_ptr(), 0 if t is None else t.data_ptr(), dtype_code(out_dtype),
+													  ny, ssy.data_ptr(), 0 if by is None else by.data_ptr(), flags.data_ptr(), 1 if ci >= 0 else 0, int(p_kind),
+													  self._stream()))
 			alpha = None
 			if want_alpha:
 				if nc > 0:
@@ -1132,8 +1135,9 @@ class Engine:
 
 	@serialised
 	def association_single0(self, dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt=False, cov=None,
-							device_out=False, resident=False, state=None):
+							device_out=False, resident=False, state=None, logp=False):
 		"""Whole-problem single=0 path on one device.  dy None -> coex (symmetric).
+		logp: res['p'] holds ln P instead of P -- every route below passes it to its sweep as p_kind.
 		cov: optional (d_c, d_dci) already on the device (repeated calls with the same covariates).
 		A call whose P-values the integer engine's guard cannot certify (GuardHit) is redone on the fp64 Gram kernel; resident calls
 		leave that to whoever reads the flags (DePlan.results)."""
@@ -1141,6 +1145,10 @@ class Engine:
 		import time
 		t0 = time.perf_counter()
 		self._tls.path = None
+		if logp:
+			res = self._association_single0_logp(dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, state)
+			self._log_single0(dx, dy, t0, 'ln P')
+			return res
 		try:
 			res = self._association_single0(dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, state)
 		except GuardHit as g:
@@ -1148,17 +1156,48 @@ class Engine:
 			with self.forced_f64():
 				res = self._association_single0(dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, state)
 			self.last_guard = dict(hits=g.hits, worst=g.worst, fallback=True)
-		if not resident and logging.getLogger().isEnabledFor(logging.INFO):
-			# which engine ran, how fast, what the guard said (the reference logs its batch decisions: association.py:745-757, run.py:274-276)
-			el = time.perf_counter() - t0
-			nx, n = dx.shape
-			tests = nx * (nx - 1) // 2 if dy is None else nx * dy.shape[0]
-			g = self.last_guard
-			logging.info('normalisr_amd: %s, %d tests over %d cells on %s in %.1f ms (%.3g tests/s incl. transfers); %s', 'coex' if dy is None else 'de', tests, n,
-						 getattr(self._tls, 'path', None) or 'the device', 1e3 * el, tests / max(el, 1e-9),
-						 'fp64 matrix cores, no guard needed' if (g['hits'] == 0 and g['worst'] == 0 and not g['fallback']) else
-						 ('guard: %d pairs not certified by the integer engine (largest estimate %.2g): redone on the fp64 matrix cores' % (g['hits'], g['worst']) if g['fallback']
-						  else 'guard: every P-value certified by the integer engine (largest relative error bound %.2g, budget %.2g)' % (g['worst'], self.guard_tol)))
+		if not resident:
+			self._log_single0(dx, dy, t0, 'P-value')
+		return res
+
+	def _log_single0(self, dx, dy, t0, what):
+		"""Which engine ran, how fast, what the guard said (the reference logs its batch decisions: association.py:745-757, run.py:274-276)."""
+		import logging
+		import time
+		if not logging.getLogger().isEnabledFor(logging.INFO):
+			return
+		el = time.perf_counter() - t0
+		nx, n = dx.shape
+		tests = nx * (nx - 1) // 2 if dy is None else nx * dy.shape[0]
+		g = self.last_guard
+		logging.info('normalisr_amd: %s, %d tests over %d cells on %s in %.1f ms (%.3g tests/s incl. transfers); %s', 'coex' if dy is None else 'de', tests, n,
+					 getattr(self._tls, 'path', None) or 'the device', 1e3 * el, tests / max(el, 1e-9),
+					 'fp64 matrix cores, no guard needed' if (g['hits'] == 0 and g['worst'] == 0 and not g['fallback']) else
+					 ('guard: %d pairs not certified by the integer engine (largest estimate %.2g): redone on the fp64 matrix cores' % (g['hits'], g['worst']) if g['fallback']
+					  else 'guard: every %s certified by the integer engine (largest relative error bound %.2g, budget %.2g)' % (what, g['worst'], self.guard_tol)))
+
+	def _association_single0_logp(self, dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, state):
+		"""association_single0 with ln P in res['p']: every route passes p_kind = 1 to its sweep.  Pairs the integer engine's guard cannot certify in this form
+		(more than guard_tol * max(1, |ln P|): csrc/nrm_fix.h) send ln P to the fp64 Gram kernel, as P-values go there -- and everything else the call returns
+		is then taken from the call without logp (its own verdict and rerun included): the rule differs between the two forms, and logp=True is to change the
+		first result only.  Up to four passes on that path (ln P on the integer engine, ln P on the fp64 kernel, the call without logp and its own rerun); with
+		strongly correlated rows, which are exempt as P = 0 but not as ln P, it can be the usual path (its cost is not measured).
+		Not reconciled: a call certified for ln P whose P-values are not -- its other results come from the integer engine, the call without logp takes
+		them from the fp64 kernel (1e-13 apart)."""
+		import logging
+		if resident:
+			raise NotImplementedError('logp=True is not available to resident (plan) callers: single=0 one-shot calls only.')
+		args = (dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, False, state)
+		try:
+			return self._association_single0(*args, p_kind=1)
+		except GuardHit as g:
+			logging.info('normalisr_amd: integer Gram engine: %s (ln P); taking ln P from the fp64 matrix cores.', g)
+			hit = g
+		with self.forced_f64():
+			lnp = self._association_single0(*args, p_kind=1)['p']
+		res = self.association_single0(dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, False, state)
+		res['p'] = lnp
+		self.last_guard = dict(hits=hit.hits, worst=hit.worst, fallback=True)
 		return res
 
 	def forced_f64(self):
@@ -1174,7 +1213,7 @@ class Engine:
 				self._force_f64 = prev
 		return ctx()
 
-	def _association_single0(self, dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, state=None):
+	def _association_single0(self, dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, state=None, p_kind=0):
 		samexy = dy is None
 		from . import de_sparse
 		# a DesignCSR (a sparse design in HBM): the sparse-design kernel reads its entry lists and no matrix; every other route reads design.dense(), one scatter on the device
@@ -1184,7 +1223,7 @@ class Engine:
 				dx = dx.dense()
 			self._tls.path = 'the streaming de kernel (fp64 matrix cores, raw rows read once)'
 			return self.association_de_streaming(dx, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov,
-												 resident=resident and not (want_alpha or want_rt), state=state)
+												 resident=resident and not (want_alpha or want_rt), state=state, p_kind=p_kind)
 		if de_sparse.candidate(self, dx, dy, dc, samexy):
 			# a design matrix with few entries (gRNA incidence): the expression rows are read once, raw (csrc/nrm_de_sparse.hip)
 			with self.torch.cuda.device(self.device):
@@ -1199,7 +1238,7 @@ class Engine:
 						state['sparse'] = lists
 			if lists[2].ok and not (state is not None and state.get('sparse_refused') is dx):
 				self._tls.path = 'the sparse-design kernel (expression rows read once, %d design entries)' % lists[2].nnz
-				return self._association_de_sparse(dx, lists[2], dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident)
+				return self._association_de_sparse(dx, lists[2], dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, p_kind)
 		if csr:
 			dx = dx.dense()
 		nx, n = dx.shape
@@ -1210,10 +1249,10 @@ class Engine:
 		eng_name = (lambda k: 'the integer Gram engine (%d-bit fixed point on the int8 matrix cores)' % (8 * k - 2) if k else 'the fp64 Gram kernel')(self.gram_slices(n))
 		if samexy and not (device_out or resident or want_rt or want_alpha) and self.coex_pipelined_ok(dx, dc, n):
 			self._tls.path = eng_name + ', rows uploaded / results returned chunk by chunk beside the kernels'
-			return self.association_coex_pipelined(dx, dc, dci, rank, dimreduce, out_dtype, cov)
+			return self.association_coex_pipelined(dx, dc, dci, rank, dimreduce, out_dtype, cov, p_kind=p_kind)
 		if not (samexy or device_out or resident or want_rt or want_alpha) and self.chunked_ok(dy):
 			self._tls.path = eng_name + ', expression rows uploaded in chunks beside the kernels'
-			return self.association_de_chunked(dx, dy, dc, dci, rank, dof, stat_kind, out_dtype, cov)
+			return self.association_de_chunked(dx, dy, dc, dci, rank, dof, stat_kind, out_dtype, cov, p_kind=p_kind)
 		self._tls.path = eng_name
 		d_c, d_dci = self.covariates(dc, dci) if cov is None else cov
 		ns = self.gram_slices(n)  # integer engine: K1 writes the digit planes itself and the fp64 residuals are never stored
@@ -1230,11 +1269,11 @@ class Engine:
 			# to stall that copy by ~20 ms -- twice the whole C2 call
 			host = self.start_host_results(nx, ny, out_dtype)
 		if host is not None:
-			p, stat = self.association_banded(rx, ry, samexy, nx, ny, n, dof, stat_kind, out_dtype, host)
+			p, stat = self.association_banded(rx, ry, samexy, nx, ny, n, dof, stat_kind, out_dtype, host, p_kind=p_kind)
 			return dict(p=p, stat=stat, alpha=None, varx=None if samexy else self.variances(rx.ss, nx, n, out_dtype),
 						vary=self.variances(ry.ss, ny, n, out_dtype), dof=dof)
 		dot = self.gram(rx, ry, samexy, nslices=ns)
-		p, stat, r, t, flags = self.sweep(dot, rx.ss, ry.ss, nx, ny, n, dof, samexy, stat_kind, out_dtype, want_rt, fix=self.fix_args(rx, ry))
+		p, stat, r, t, flags = self.sweep(dot, rx.ss, ry.ss, nx, ny, n, dof, samexy, stat_kind, out_dtype, want_rt, fix=self.fix_args(rx, ry), p_kind=p_kind)
 		alpha = None
 		if want_alpha:
 			if nc > 0 and not samexy:
@@ -1254,7 +1293,7 @@ class Engine:
 		return res
 
 
-	def _association_de_sparse(self, d_x, lists, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident):
+	def _association_de_sparse(self, d_x, lists, dy, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, cov, device_out, resident, p_kind=0):
 		"""single=0 de through de_sparse.run: same results dictionary as the dense path of _association_single0."""
 		from . import de_sparse
 		nx, n = d_x.shape
@@ -1265,7 +1304,7 @@ class Engine:
 			d_c, d_dci = self.covariates(dc, dci) if cov is None else cov
 			flags = self.new_flags()
 			dot, rx, ssy, coefy = de_sparse.run(self, d_x, lists, dy, d_c, d_dci, rank, nx, ny, n, nc, want_alpha, flags)
-			p, stat, r, t, flags = self.sweep(dot, rx.ss, ssy, nx, ny, n, dof, False, stat_kind, out_dtype, want_rt, flags=flags)
+			p, stat, r, t, flags = self.sweep(dot, rx.ss, ssy, nx, ny, n, dof, False, stat_kind, out_dtype, want_rt, flags=flags, p_kind=p_kind)
 			alpha = None
 			if want_alpha:
 				alpha = self.download(self.alpha(stat, stat_kind, rx.ss, n, rx.coef, coefy, nc)) if nc > 0 else np.zeros((nx, ny, nc), dtype=out_dtype)
@@ -1288,7 +1327,7 @@ class Engine:
 				rows_h = redo.cpu().numpy()
 				sub = dy[rows_h] if isinstance(dy, np.ndarray) else dy.index_select(0, redo)
 				with self.forced_f64():
-					part = self._association_single0(d_x, sub, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, (d_c, d_dci), True, False)
+					part = self._association_single0(d_x, sub, dc, dci, rank, dimreduce, return_dot, want_alpha, out_dtype, want_rt, (d_c, d_dci), True, False, p_kind=p_kind)
 				as_dev = lambda v: v if hasattr(v, 'is_cuda') else self.torch.from_numpy(np.ascontiguousarray(v)).to(self.device)  # (the streaming de kernel answers in numpy)
 				p[:, redo] = as_dev(part['p'])
 				stat[:, redo] = as_dev(part['stat'])

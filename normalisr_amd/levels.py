@@ -19,6 +19,7 @@ import logging
 import numpy as np
 
 from .association import _check_dimreduce, _prepare_covariates
+from . import _opts
 from . import engine as _engine
 
 RHO_MIN = 1e-6    # a new row keeping at least this part of its squared length outside the span is a new direction
@@ -115,7 +116,8 @@ class CoexLevels:
 	Attributes: level (appends so far), dc (all rows so far), rank, dof, rebuilt (one bool per append), info (the last append's rho and counters).
 	A dt tensor written in place after construction (torch counts such writes) makes the next append or results rebuild from its current content."""
 
-	def __init__(self, dt, dc, dimreduce=0, device=None):
+	def __init__(self, dt, dc, dimreduce=0, device=None, logp=False):
+		_opts.refuse_logp(logp, 'CoexLevels')
 		dev = _engine.is_dev(dt)
 		if not dev:
 			dt = np.asarray(dt)
@@ -299,7 +301,7 @@ def _iter_levels(dt, dc, namet, sets, qcut, lvmax, n, nmin, dimreduce, condcov, 
 		yield rec
 
 
-def coex_levels(dt, dc, namet, sets, qcut, lvmax=5, n=100, nmin=5, dimreduce=0, condcov=True, keep=('net', ), strict=True, device_out=False):
+def coex_levels(dt, dc, namet, sets, qcut, lvmax=5, n=100, nmin=5, dimreduce=0, condcov=True, keep=('net', ), strict=True, device_out=False, logp=False):
 	"""The loop of the reference's co-expression example (cmd_coex.sh:37-46) on a resident problem: for level 0 .. lvmax, co-expression given the covariates so far
 	(CoexLevels.results), the binary network (binnet.binnet at qcut), the principal genes and their top gene set (enrich.top_pathway with n, nmin; sets: a GeneSets,
 	bound once, or a BoundSets), the top principal component of that set's genes as one more covariate (gocovt.pccovt with condcov), appended.  Between levels only
@@ -308,6 +310,7 @@ def coex_levels(dt, dc, namet, sets, qcut, lvmax=5, n=100, nmin=5, dimreduce=0, 
 	of p, dot, var, net keep names (numpy, or with device_out=True torch CUDA tensors; var is numpy).
 	strict=True raises what a step raises (RuntimeError 'Empty binary network.' / 'Not enough principal genes...', ValueError 'No GO enrichment found for given
 	criteria.'); strict=False ends the loop there and returns the completed levels and a last record with what that level had produced and stopped=<message>."""
+	_opts.refuse_logp(logp, 'coex_levels')
 	out = []
 	for rec in _iter_levels(dt, dc, namet, sets, qcut, lvmax, n, nmin, dimreduce, condcov, keep, device_out):
 		err = rec.pop('error', None)

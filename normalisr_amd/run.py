@@ -244,13 +244,13 @@ def _call_bh(m, ka):
 # (index into the result tuple, transform, format); written when the argument was given)
 COMMANDS = {
 	'de': dict(inputs=('design_in', 'exp_in', 'cov_in'),
-			   options=dict(nth=('nth', int), bs=('bs', int), dimr=('dimreduce', int), method=('single', _de_method),
+			   options=dict(nth=('nth', int), bs=('bs', int), dimr=('dimreduce', int), method=('single', _de_method), logp=('logp', bool),
 							# the reference leaves lowmem=True and then fails writing None: asking for the file asks for alpha
 							clfc_out=('lowmem', lambda name: False)),
 			   call=_call_de,
 			   outputs=dict(pv_out=(0, None, fmt_float), lfc_out=(1, None, fmt_float), clfc_out=(2, _flat_alpha, fmt_float),
 							vard_out=(3, None, fmt_float), vart_out=(4, None, fmt_float))),
-	'coex': dict(inputs=('exp_in', 'cov_in'), options=dict(nth=('nth', int), bs=('bs', int), dimr=('dimreduce', int)), call=_call_coex,
+	'coex': dict(inputs=('exp_in', 'cov_in'), options=dict(nth=('nth', int), bs=('bs', int), dimr=('dimreduce', int), logp=('logp', bool)), call=_call_coex,
 				 outputs=dict(pv_out=(0, None, fmt_float), dot_out=(1, None, fmt_float), var_out=(2, None, fmt_float))),
 	'normvar': dict(inputs=('lcpm_in', 'cov_in', 'weights_in', 'scale_in'), options=dict(nth=('nth', int), bs=('bs', int)), call=_call_normvar,
 					outputs=dict(exp_out=(0, None, fmt_float), cov_out=(1, None, fmt_float))),

@@ -206,7 +206,8 @@ class Single1Plan:
 	raises on the way (:917-918, dof <= 0, non-finite results, R^2 > 1) is counted on the device and looked at once, in results().
 	dx / dy: torch CUDA tensors resident in HBM (numpy arrays are uploaded once); dc: host array."""
 
-	def __init__(self, dx, dy, dc, dimreduce=0, lowmem=True, return_dot=True, lists=None, eng=None):
+	def __init__(self, dx, dy, dc, dimreduce=0, lowmem=True, return_dot=True, lists=None, eng=None, logp=False):
+		_opts.refuse_logp(logp, 'single1.Single1Plan')
 		from . import de_sparse
 		if lists is None and de_sparse.is_sparse_design(dx):
 			raise TypeError('Single1Plan takes a dense design: DesignCSR.dense() gives one (association_tests(..., single=1) takes the sparse design itself).')

@@ -357,7 +357,8 @@ class Single4Plan:
 	calling the public function every step.  dx / dy may be rewritten in place between steps (torch counts that in ._version): the next step is the
 	public call on the new values, the one after it decides anew and the graph is captured again -- the old one is never replayed."""
 
-	def __init__(self, dx, dy, dc, dimreduce=0, lowmem=True, return_dot=True, eng=None):
+	def __init__(self, dx, dy, dc, dimreduce=0, lowmem=True, return_dot=True, eng=None, logp=False):
+		_opts.refuse_logp(logp, 'single4.Single4Plan')
 		from . import de_sparse
 		if de_sparse.is_sparse_design(dx):
 			raise TypeError('Single4Plan takes a dense design: DesignCSR.dense() gives one (association_tests(..., single=4) takes the sparse design itself).')
