@@ -430,6 +430,14 @@ int nrm_binnet(const void* d_p, int p_dtype, int64_t ng, int64_t ldp, double qcu
  * *d_total counts this block's selected entries (the caller sums the blocks before the "Empty binary network" test). */
 int nrm_binnet_rows(const void* d_p, int p_dtype, int64_t rows, int64_t ng, int64_t ldp, int64_t row0, double qcut,
 					unsigned char* d_out, int64_t ldo, unsigned long long* d_total, int32_t* d_flags, void* stream);
+/* The two entries with the form of the matrix as an argument: p_kind = 0, P-values, is what the entries above pass; p_kind = 1: d_p holds ln P (what the
+ * p_kind = 1 sweeps write, nrm_assoc_sweep_pk).  Valid entries are <= 0 and no NaN; -inf is the exact zero of the linear form (coex's diagonal) and both zeros are
+ * ln 1; d_flags[0] counts the rows with other entries.  Row i's edges are { j != i : lnp_ij <= tau* }, tau* = max{ v : v + (ln m - ln c_v) <= ln qcut }, m = ng - 1,
+ * c_v = #{off-diagonal entries <= v}, evaluated in fp64 for both dtypes.  d_out, d_total as above. */
+int nrm_binnet_pk(const void* d_p, int p_dtype, int64_t ng, int64_t ldp, double qcut, unsigned char* d_out, int64_t ldo,
+				  unsigned long long* d_total, int32_t* d_flags, int p_kind, void* stream);
+int nrm_binnet_rows_pk(const void* d_p, int p_dtype, int64_t rows, int64_t ng, int64_t ldp, int64_t row0, double qcut,
+					   unsigned char* d_out, int64_t ldo, unsigned long long* d_total, int32_t* d_flags, int p_kind, void* stream);
 
 /*
  * bh -- Benjamini-Hochberg q-values over ALL entries of a P-value matrix that lies in HBM (reference binnet.py:77-131 with weight=None; csrc/nrm_bh.hip): what
@@ -450,6 +458,12 @@ int nrm_binnet_rows(const void* d_p, int p_dtype, int64_t rows, int64_t ng, int6
  *       position (uint32), [2] q per sorted position after the suffix minimum (p_dtype), [3] 0.  For the stage tests.
  *   nrm_bh_host:   the whole problem from host buffers (as nrm_binnet_host: no torch, the library's scratch pool, the device of nrm_set_device): h_p (n) -> h_q (n);
  *       *identical = 1 when every entry holds the same value; NRM_E_NUMERIC "P-values must be finite and within [0, 1]" for entries that are not.
+ *   nrm_bh_pk, nrm_bh_host_pk: the same with the form of the entries as an argument; p_kind = 0 is what nrm_bh and nrm_bh_host pass.  p_kind = 1: the entries are
+ *       ln P.  Valid: <= 0 and no NaN (-inf is the exact zero of the linear form; +0.0 and -0.0 are both ln 1); d_flags[0] counts the others.  With u over the
+ *       distinct values and c(u) the exact number of entries <= u:  ln q(u) = min(0, u + (ln N - ln c(u))), then the minimum over u' >= u, in fp64 for both dtypes;
+ *       an fp32 result is that value rounded once at the store.  -inf gives -inf, c = N leaves u itself, equal entries get equal bytes, the output is
+ *       non-decreasing in the input.  Keys are the complemented bit patterns of |ln P|; workspace, layout ([2] then holds ln q) and launch sequence are those of the
+ *       linear form: the sequence depends on (n, dtype, p_kind) only.
  * Threads: the device-pointer entries keep no state (any thread, the caller orders work by its streams and owns d_work for the duration); the host entry takes the
  * lock all whole-problem entries share -- one such call at a time per process.
  */
@@ -459,6 +473,9 @@ int nrm_bh(const void* d_p, int p_dtype, int64_t rows, int64_t cols, int64_t ldp
 		   int32_t* d_flags /* [2] */, void* stream);
 int nrm_bh_layout(int64_t n, int p_dtype, int64_t offsets[4]);
 int nrm_bh_host(const void* h_p, int p_dtype, int64_t n, void* h_q, int32_t* identical);
+int nrm_bh_pk(const void* d_p, int p_dtype, int64_t rows, int64_t cols, int64_t ldp, void* d_q, int64_t ldq, void* d_work, int64_t work_bytes,
+			  int32_t* d_flags /* [2] */, int p_kind, void* stream);
+int nrm_bh_host_pk(const void* h_p, int p_dtype, int64_t n, void* h_q, int32_t* identical, int p_kind);
 
 /*
  * normvar (reference norm.py:131-289): per-gene weighted covariate removal, e_gk = w_k^wt_g.
@@ -581,6 +598,8 @@ int nrm_association_tests_single4_pinv_host(const void* h_dx, int x_dtype, int64
 											int64_t nc, int64_t n_cells, const double* h_dci, int rank, int dimreduce, int return_dot, double tol, void* h_p,
 											void* h_stat, void* h_alpha, void* h_varx, void* h_vary, int out_dtype);
 int nrm_binnet_host(const void* h_p, int p_dtype, int64_t ng, double qcut, unsigned char* h_net, int64_t* total);
+/* p_kind = 1: h_p holds ln P (nrm_binnet_pk); 0 is what nrm_binnet_host passes */
+int nrm_binnet_host_pk(const void* h_p, int p_dtype, int64_t ng, double qcut, unsigned char* h_net, int64_t* total, int p_kind);
 /* (Round 6) What the package needs to follow the reference's per-grouping algorithm of single=4 without torch where the closed form of
  * nrm_association_tests_single4_host does not apply (rank-deficient A A^T, mpc / method / qr, dy=None): the Gram matrices association.py:926-968 forms with
  * numpy.matmul, on the fp64 Gram kernel -- h_out (ra, rb) fp64 = A B^T over n cells (h_b == NULL: B = A), optionally the rows' sums of squares -- and the

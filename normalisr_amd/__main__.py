@@ -116,10 +116,14 @@ def build_parser():
 	p.add_argument('pv_in', help='Input P-value matrix of gene pairwise co-expression (genes x genes), TSV.')
 	p.add_argument('net_out', help='Output binary co-expression network (genes x genes, 0/1), TSV.')
 	p.add_argument('qcut', type=float, help='Q-value cutoff for binary network.')
+	p.add_argument('--logp', dest='logp', action='store_true', default=None,
+				   help='pv_in holds the natural logarithms of the P-values (pv_out of coex --logp; -INF on the diagonal): the network is cut on ln q.')
 
 	p = sub.add_parser('bh', help='Benjamini-Hochberg q-values over all entries of a P-value matrix (pv_out of de); a sub-command of this build\'s own.')
 	p.add_argument('pv_in', help='Input P-value matrix or vector, TSV.')
 	p.add_argument('q_out', help='Output q-values in the same shape, TSV.')
+	p.add_argument('--logp', dest='logp', action='store_true', default=None,
+				   help='pv_in holds the natural logarithms of the P-values (pv_out of de --logp); q_out receives ln q, finite where q underflows to 0.')
 
 	p = sub.add_parser('principal', help='List the principal genes of a binary co-expression network: the genes with the most co-expressed genes (the selection of '
 					   'the reference\'s gocovt, without its GO enrichment).')

@@ -113,11 +113,15 @@ _SIGNATURES = {
 	'nrm_single1_cells': ([_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp], _i32),
 	'nrm_binnet': ([_vp, _i32, _i64, _i64, _dbl, _vp, _i64, _vp, _vp, _vp], _i32),
 	'nrm_binnet_rows': ([_vp, _i32, _i64, _i64, _i64, _i64, _dbl, _vp, _i64, _vp, _vp, _vp], _i32),
+	'nrm_binnet_pk': ([_vp, _i32, _i64, _i64, _dbl, _vp, _i64, _vp, _vp, _i32, _vp], _i32),
+	'nrm_binnet_rows_pk': ([_vp, _i32, _i64, _i64, _i64, _i64, _dbl, _vp, _i64, _vp, _vp, _i32, _vp], _i32),
 	'nrm_bh_workspace_bytes': ([_i64, _i32], _i64),
 	'nrm_bh_tile': ([], _i64),
 	'nrm_bh': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
 	'nrm_bh_layout': ([_i64, _i32, ctypes.POINTER(_i64)], _i32),
 	'nrm_bh_host': ([_vp, _i32, _i64, _vp, ctypes.POINTER(_i32)], _i32),
+	'nrm_bh_pk': ([_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _vp], _i32),
+	'nrm_bh_host_pk': ([_vp, _i32, _i64, _vp, ctypes.POINTER(_i32), _i32], _i32),
 	'nrm_normvar_weights': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp], _i32),
 	'nrm_normvar_apply': ([_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp], _i32),
 	'nrm_normvar_device_covariates': ([], _i64),
@@ -130,6 +134,7 @@ _SIGNATURES = {
 	'nrm_association_tests_single4_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _i32], _i32),
 	'nrm_association_tests_single4_pinv_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _i32], _i32),
 	'nrm_binnet_host': ([_vp, _i32, _i64, _dbl, _vp, _vp], _i32),
+	'nrm_binnet_host_pk': ([_vp, _i32, _i64, _dbl, _vp, _vp, _i32], _i32),
 	'nrm_gram_host': ([_vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _vp], _i32),
 	'nrm_pvalues_host': ([_vp, _i64, _dbl, _vp], _i32),
 	'nrm_normvar_host': ([_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _dbl, _i32, _vp, _i32, _vp], _i32),

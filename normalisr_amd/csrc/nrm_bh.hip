@@ -21,6 +21,12 @@
 //                   that position's q into d_q
 // The launch sequence depends on (N, dtype) only, never on the data, and nothing is read back: nrm_bh can be queued behind a plan's step and captured into a HIP graph.
 // Every digit indexes a 256-bin table and every search stays inside [0, N), so entries that are not P-values cannot send an access out of range.
+//
+// The ln form (nrm_bh_pk with p_kind = 1): the entries are ln P -- <= 0 and no NaN, -inf being the exact zero of the linear form -- and the
+// output is ln q(u) = min(0, u + (ln N - ln c(u))), then the minimum over u' >= u, evaluated in fp64 for both dtypes and rounded once at the store.  k_bh_keys, k_bh_q
+// and k_bh_lookup take p_kind as a compile-time parameter: keys are the complemented bit patterns of |ln P| (ascending key = ascending ln P, -inf first, both zeros the
+// largest key); the sort, the scans, the tie ends, the suffix minimum and the sampled levels are the same launches on the same workspace, so the launch sequence
+// depends on (N, dtype, p_kind) only.  The p_kind = 0 instantiations are the code they were.
 #include "nrm_device.h"
 #include "nrm_host_entry.h"
 
@@ -52,6 +58,21 @@ __device__ __forceinline__ uint64_t bh_key(double p) {
 }
 __device__ __forceinline__ float bh_value(uint32_t k) { return __uint_as_float(k); }
 __device__ __forceinline__ double bh_value(uint64_t k) { return __longlong_as_double((long long)k); }
+
+// The ln form (p_kind = 1): the complemented bit pattern of |ln P|.  Ascending key is ascending ln P, -inf (the exact zero of the linear form) comes first, both
+// zeros (ln 1) share the largest key; whatever the input bits, the key is an unsigned integer like any other and the sort treats it as one.
+__device__ __forceinline__ uint32_t bh_key_ln(float p) { return ~(__float_as_uint(p) & 0x7fffffffu); }
+__device__ __forceinline__ uint64_t bh_key_ln(double p) { return ~((uint64_t)__double_as_longlong(p) & 0x7fffffffffffffffull); }
+// ln P of a key of the ln form, in fp64: -|ln P|, and +0.0 for ln 1
+__device__ __forceinline__ double bh_value_ln(uint32_t k) { return k == 0xffffffffu ? 0.0 : -(double)__uint_as_float(~k); }
+__device__ __forceinline__ double bh_value_ln(uint64_t k) { return k == 0xffffffffffffffffull ? 0.0 : -__longlong_as_double((long long)~k); }
+template <int PK, typename T>
+__device__ __forceinline__ typename BhKey<T>::type bh_key_of(T p) {
+	if constexpr (PK)
+		return bh_key_ln(p);
+	else
+		return bh_key(p);
+}
 
 template <typename V>
 __device__ __forceinline__ V bh_min(V a, V b) {
@@ -90,7 +111,7 @@ __device__ __forceinline__ void bh_load_items(const V* __restrict__ a, int64_t t
 }
 
 // ---- a. keys ----------------------------------------------------------------------------------------------------------------------------------------------------
-template <typename T, bool VEC>
+template <typename T, bool VEC, int PK = 0>
 __global__ void __launch_bounds__(BH_THREADS) k_bh_keys(const T* __restrict__ p, int64_t n, int64_t cols, int64_t ld, typename BhKey<T>::type* __restrict__ keys,
 														 int32_t* __restrict__ flags) {
 	__shared__ double sm[BH_NW];
@@ -101,8 +122,12 @@ __global__ void __launch_bounds__(BH_THREADS) k_bh_keys(const T* __restrict__ p,
 #pragma unroll
 	for (int j = 0; j < 4; j++)
 		if (i0 + j < n) {
-			if (!(v[j] >= (T)0 && v[j] <= (T)1)) bad += 1.0;  // NaN, infinite, < 0, > 1 (binnet.py:104); it still gets a key
-			keys[i0 + j] = bh_key(v[j]);
+			if constexpr (PK) {
+				if (!(v[j] <= (T)0)) bad += 1.0;  // NaN or > 0: no ln P (-inf is one: ln 0); it still gets a key
+			} else {
+				if (!(v[j] >= (T)0 && v[j] <= (T)1)) bad += 1.0;  // NaN, infinite, < 0, > 1 (binnet.py:104); it still gets a key
+			}
+			keys[i0 + j] = bh_key_of<PK, T>(v[j]);
 		}
 	bad = nrm_block_sum<BH_NW, true>(bad, sm);
 	if (threadIdx.x == 0 && bad > 0.0) atomicAdd(&flags[0], (int)bad);
@@ -338,7 +363,8 @@ __global__ void __launch_bounds__(BH_THREADS) k_bh_suffix_top(const V* __restric
 	}
 }
 // c and q before the suffix minimum for every sorted position, the tile's smallest q, and d_flags[1]
-template <typename T>
+// (PK = 1: ln q = min(0, u + (ln N - ln c)) in fp64 for both dtypes, rounded once at the store; c = N leaves u itself; -inf stays -inf)
+template <typename T, int PK = 0>
 __global__ void __launch_bounds__(BH_THREADS) k_bh_q(const typename BhKey<T>::type* __restrict__ s, int64_t n, const uint32_t* __restrict__ end_after,
 													  uint32_t* __restrict__ cnt, T* __restrict__ q, T* __restrict__ tile_q, int32_t* __restrict__ flags) {
 	typedef typename BhKey<T>::type K;
@@ -350,16 +376,24 @@ __global__ void __launch_bounds__(BH_THREADS) k_bh_q(const typename BhKey<T>::ty
 	bh_end_marks<K>(s, t0, n, k, e);
 	bh_tile_suffix_min<uint32_t>(e, end_after[blockIdx.x], BH_NO_END, sme);  // e[j]: the last position holding the key of position t0 + j
 	const double dn = (double)n;
+	double ln_n = 0.0;
+	if constexpr (PK) ln_n = log(dn);
 	T qmin = (T)2;
 #pragma unroll
 	for (int j = 0; j < BH_ITEMS; j++) {
 		if (t0 + j < n) {
 			const uint32_t c = e[j] + 1u;
-			double w = (double)c / dn;
-			if (sizeof(T) == 4) w = (double)(float)w;
-			T qv = (T)((double)bh_value(k[j]) / w);
-			if (!isfinite((double)qv)) qv = (T)1;
-			qv = qv > (T)1 ? (T)1 : (qv < (T)0 ? (T)0 : qv);
+			T qv;
+			if constexpr (PK) {
+				const double lq = bh_value_ln(k[j]) + (ln_n - log((double)c));
+				qv = lq < 0.0 ? (T)lq : (T)0;  // (a NaN -- only from entries that are counted as invalid -- becomes 0 as well)
+			} else {
+				double w = (double)c / dn;
+				if (sizeof(T) == 4) w = (double)(float)w;
+				qv = (T)((double)bh_value(k[j]) / w);
+				if (!isfinite((double)qv)) qv = (T)1;
+				qv = qv > (T)1 ? (T)1 : (qv < (T)0 ? (T)0 : qv);
+			}
 			cnt[t0 + j] = c;
 			q[t0 + j] = qv;
 			qmin = bh_min(qmin, qv);
@@ -403,7 +437,7 @@ __global__ void __launch_bounds__(BH_THREADS) k_bh_sample(const K* __restrict__ 
 	if (i < n_dst) dst[i] = src[(i + 1) * F - 1];  // (n_dst = n_src / F: inside src)
 }
 // (p and out may be the same matrix: a thread reads its four entries before it writes them)
-template <typename T, bool VEC>
+template <typename T, bool VEC, int PK = 0>
 __global__ void __launch_bounds__(BH_THREADS) k_bh_lookup(const T* p, int64_t n, int64_t cols, int64_t ldp, const BhLevels<typename BhKey<T>::type> lv,
 														   const T* __restrict__ q, T* out, int64_t ldq) {
 	typedef typename BhKey<T>::type K;
@@ -413,7 +447,7 @@ __global__ void __launch_bounds__(BH_THREADS) k_bh_lookup(const T* p, int64_t n,
 	bh_load4<T, VEC>(p, i0, n, cols, ldp, v);
 #pragma unroll
 	for (int j = 0; j < 4; j++) {
-		const K key = bh_key(v[j]);
+		const K key = bh_key_of<PK, T>(v[j]);
 		int64_t g = 0;  // the group of the level at hand: keys [g F, g F + F) of it, cut at its end (the top level is one group)
 		for (int k = lv.count - 1; k >= 0; k--) {
 			int64_t lo = g * F, hi = lo + F < lv.n[k] ? lo + F : lv.n[k];  // g <= n[k + 1] = n[k] / F: lo <= n[k], every probe inside [0, n[k])
@@ -497,7 +531,7 @@ extern "C" int nrm_bh_layout(int64_t n, int p_dtype, int64_t offsets[4]) {
 	return NRM_OK;
 }
 
-template <typename T>
+template <typename T, int PK>
 static int bh_run(const T* p, int64_t n, int64_t cols, int64_t ldp, T* out, int64_t ldq, char* work, const BhLayout& L, int32_t* flags, hipStream_t st) {
 	typedef typename BhKey<T>::type K;
 	K *a = (K*)(work + L.keys), *b = (K*)(work + L.other);
@@ -506,9 +540,9 @@ static int bh_run(const T* p, int64_t n, int64_t cols, int64_t ldp, T* out, int6
 	const dim3 wg(BH_THREADS), tiles((unsigned)L.nb), quads((unsigned)((n + 4 * BH_THREADS - 1) / (4 * BH_THREADS)));
 	const bool vec_in = (ldp == cols || n == cols) && (uintptr_t)p % 16 == 0;  // the flattened input is one contiguous, 16-byte aligned run
 	if (vec_in)
-		hipLaunchKernelGGL((k_bh_keys<T, true>), quads, wg, 0, st, p, n, cols, ldp, a, flags);
+		hipLaunchKernelGGL((k_bh_keys<T, true, PK>), quads, wg, 0, st, p, n, cols, ldp, a, flags);
 	else
-		hipLaunchKernelGGL((k_bh_keys<T, false>), quads, wg, 0, st, p, n, cols, ldp, a, flags);
+		hipLaunchKernelGGL((k_bh_keys<T, false, PK>), quads, wg, 0, st, p, n, cols, ldp, a, flags);
 	for (int pass = 0; pass < (int)sizeof(K); pass++) {
 		const int shift = 8 * pass;
 		hipLaunchKernelGGL((k_bh_hist<K>), tiles, wg, 0, st, (const K*)a, n, shift, table, L.nb);
@@ -526,7 +560,7 @@ static int bh_run(const T* p, int64_t n, int64_t cols, int64_t ldp, T* out, int6
 	// (an even number of passes: a is the workspace's first buffer again, b is free for c)
 	hipLaunchKernelGGL((k_bh_ends<K>), tiles, wg, 0, st, (const K*)a, n, tile_end);
 	hipLaunchKernelGGL((k_bh_suffix_top<uint32_t>), dim3(1), wg, 0, st, (const uint32_t*)tile_end, L.nb, BH_NO_END, end_after);
-	hipLaunchKernelGGL((k_bh_q<T>), tiles, wg, 0, st, (const K*)a, n, (const uint32_t*)end_after, (uint32_t*)b, q, tile_q, flags);
+	hipLaunchKernelGGL((k_bh_q<T, PK>), tiles, wg, 0, st, (const K*)a, n, (const uint32_t*)end_after, (uint32_t*)b, q, tile_q, flags);
 	hipLaunchKernelGGL((k_bh_suffix_top<T>), dim3(1), wg, 0, st, (const T*)tile_q, L.nb, (T)2, q_after);
 	hipLaunchKernelGGL((k_bh_q_apply<T>), tiles, wg, 0, st, q, n, (const T*)q_after);
 	BhLevels<K> lv;
@@ -538,14 +572,15 @@ static int bh_run(const T* p, int64_t n, int64_t cols, int64_t ldp, T* out, int6
 			hipLaunchKernelGGL((k_bh_sample<K>), dim3((unsigned)((lv.n[k] + BH_THREADS - 1) / BH_THREADS)), wg, 0, st, lv.a[k - 1], (K*)(work + L.level_at[k]), lv.n[k]);
 	}
 	if (vec_in)
-		hipLaunchKernelGGL((k_bh_lookup<T, true>), quads, wg, 0, st, p, n, cols, ldp, lv, (const T*)q, out, ldq);
+		hipLaunchKernelGGL((k_bh_lookup<T, true, PK>), quads, wg, 0, st, p, n, cols, ldp, lv, (const T*)q, out, ldq);
 	else
-		hipLaunchKernelGGL((k_bh_lookup<T, false>), quads, wg, 0, st, p, n, cols, ldp, lv, (const T*)q, out, ldq);
+		hipLaunchKernelGGL((k_bh_lookup<T, false, PK>), quads, wg, 0, st, p, n, cols, ldp, lv, (const T*)q, out, ldq);
 	return nrm_check_launch("nrm_bh");
 }
 
-extern "C" int nrm_bh(const void* d_p, int p_dtype, int64_t rows, int64_t cols, int64_t ldp, void* d_q, int64_t ldq, void* d_work, int64_t work_bytes, int32_t* d_flags,
-					  void* stream) {
+extern "C" int nrm_bh_pk(const void* d_p, int p_dtype, int64_t rows, int64_t cols, int64_t ldp, void* d_q, int64_t ldq, void* d_work, int64_t work_bytes, int32_t* d_flags,
+						 int p_kind, void* stream) {
+	NRM_REQUIRE(p_kind == 0 || p_kind == 1, "nrm_bh: p_kind is 0 (P) or 1 (ln P)");
 	NRM_REQUIRE(rows >= 0 && cols >= 0 && rows <= 0x7fffffffLL && cols <= 0x7fffffffLL, "nrm_bh: bad shape");
 	const int64_t n = rows * cols;
 	NRM_TRY(bh_size_check(n, p_dtype));
@@ -559,14 +594,24 @@ extern "C" int nrm_bh(const void* d_p, int p_dtype, int64_t rows, int64_t cols, 
 	NRM_REQUIRE(work_bytes >= L.total, "nrm_bh: the workspace holds %lld bytes, nrm_bh_workspace_bytes asks for %lld", (long long)work_bytes, (long long)L.total);
 	hipStream_t st = (hipStream_t)stream;
 	NRM_HIP(hipMemsetAsync(d_flags, 0, 2 * sizeof(int32_t), st));
-	if (p_dtype == NRM_F64) return bh_run<double>((const double*)d_p, n, cols, ldp, (double*)d_q, ldq, (char*)d_work, L, d_flags, st);
-	return bh_run<float>((const float*)d_p, n, cols, ldp, (float*)d_q, ldq, (char*)d_work, L, d_flags, st);
+	if (p_kind) {
+		if (p_dtype == NRM_F64) return bh_run<double, 1>((const double*)d_p, n, cols, ldp, (double*)d_q, ldq, (char*)d_work, L, d_flags, st);
+		return bh_run<float, 1>((const float*)d_p, n, cols, ldp, (float*)d_q, ldq, (char*)d_work, L, d_flags, st);
+	}
+	if (p_dtype == NRM_F64) return bh_run<double, 0>((const double*)d_p, n, cols, ldp, (double*)d_q, ldq, (char*)d_work, L, d_flags, st);
+	return bh_run<float, 0>((const float*)d_p, n, cols, ldp, (float*)d_q, ldq, (char*)d_work, L, d_flags, st);
 }
 
-extern "C" int nrm_bh_host(const void* h_p, int p_dtype, int64_t n, void* h_q, int32_t* identical) {
+extern "C" int nrm_bh(const void* d_p, int p_dtype, int64_t rows, int64_t cols, int64_t ldp, void* d_q, int64_t ldq, void* d_work, int64_t work_bytes, int32_t* d_flags,
+					  void* stream) {
+	return nrm_bh_pk(d_p, p_dtype, rows, cols, ldp, d_q, ldq, d_work, work_bytes, d_flags, 0, stream);
+}
+
+extern "C" int nrm_bh_host_pk(const void* h_p, int p_dtype, int64_t n, void* h_q, int32_t* identical, int p_kind) {
 	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
 	NRM_TRY(nrm_bind_device());
 	NRM_REQUIRE(h_p && h_q && identical, "nrm_bh_host: null pointer");
+	NRM_REQUIRE(p_kind == 0 || p_kind == 1, "nrm_bh_host: p_kind is 0 (P) or 1 (ln P)");
 	NRM_TRY(bh_size_check(n, p_dtype));
 	hipStream_t st = nullptr;
 	DevBuf dp, work, flags;
@@ -575,13 +620,18 @@ extern "C" int nrm_bh_host(const void* h_p, int p_dtype, int64_t n, void* h_q, i
 	bh_layout(n, p_dtype, L);
 	NRM_TRY(work.alloc((size_t)L.total));
 	NRM_TRY(flags.alloc(16));
-	NRM_TRY(nrm_bh(dp.p, p_dtype, 1, n, n, dp.p, n, work.p, L.total, flags.as<int32_t>(), st));
+	NRM_TRY(nrm_bh_pk(dp.p, p_dtype, 1, n, n, dp.p, n, work.p, L.total, flags.as<int32_t>(), p_kind, st));
 	int32_t hf[2];
 	NRM_TRY(nrm_read_flags(flags.p, st, hf));
 	if (hf[0]) {
-		nrm_set_error("P-values must be finite and within [0, 1] (binnet.py:104): %d entries are not", hf[0]);
+		if (p_kind)
+			nrm_set_error("ln P-values must be <= 0 and no NaN: %d entries are not", hf[0]);
+		else
+			nrm_set_error("P-values must be finite and within [0, 1] (binnet.py:104): %d entries are not", hf[0]);
 		return NRM_E_NUMERIC;
 	}
 	*identical = hf[1] ? 0 : 1;
 	return copy_out(h_q, dp.p, (size_t)n * nrm_esize(p_dtype));
 }
+
+extern "C" int nrm_bh_host(const void* h_p, int p_dtype, int64_t n, void* h_q, int32_t* identical) { return nrm_bh_host_pk(h_p, p_dtype, n, h_q, identical, 0); }

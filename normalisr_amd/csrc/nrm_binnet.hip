@@ -9,6 +9,11 @@
 // tau* is found with counting passes: k <- #{p <= qcut (1+d) k / m} started from above converges to the
 // largest k for which ANY element of rank > k fails the test even with a relative slack d >> rounding error,
 // so only the few distinct values just below that bound need the reference's exact floating-point test.
+//
+// The ln form (nrm_binnet_rows_pk with p_kind = 1): the matrix holds ln P (<= 0 and no NaN; -inf is the exact zero of the
+// linear form), the edges of row i are { lnp <= tau* }, tau* = max{ v : v + (ln m - ln c_v) <= ln qcut } in fp64 for both dtypes.  The same search on
+// ln P: k <- #{lnp <= ln qcut + (ln k - ln m) + slack}.  The row policies and the kernel take p_kind as a compile-time parameter; the p_kind = 0
+// instantiations are the code they were.
 #include "nrm_device.h"
 #include <cstdlib>
 
@@ -45,11 +50,32 @@ __device__ __forceinline__ float bn_floor_to<float>(double x) {
 	return f;
 }
 
+// the same for a bound of the ln form, which may be -inf (selects the -inf entries only), NaN (selects nothing) or lie below -3e38: no clamps
+template <typename T>
+__device__ __forceinline__ T bn_floor_ln(double x) {
+	if constexpr (sizeof(T) == 8)
+		return (T)x;
+	else {
+		float f = (float)x;
+		if ((double)f > x) f = nextafterf(f, -INFINITY);  // (beyond -FLT_MAX the conversion gives -FLT_MAX and this step -inf)
+		return f;
+	}
+}
+
+// The bin of the starting histogram for an entry lnp <= ltop of the ln form (PK = 1): exp(lnp - ltop) in (0, 1] scaled to nb bins, as the linear form bins p / top.
+// The exponential is fp32 hardware arithmetic: its relative error (1e-6 where the bin is not 0) is far below a bin's relative width (>= 1 / nb), so an entry lands
+// at most one bin off, which the two bins of slack of the search's start absorb.  -inf and everything far below ltop land in bin 0.
+__device__ __forceinline__ int bn_ln_bin(double lnp, double ltop, int nb) {
+	const int b = (int)(__expf((float)(lnp - ltop)) * (float)nb);
+	return b < nb ? b : nb - 1;
+}
+
 // Row access policies for the counting passes: GlobalRow re-reads the row (L2-resident) on every pass; RegRow<ITEMS> loads it
 // once into registers (ITEMS values per lane, 256 lanes) so that the ~15 passes of a row are register-only.
-template <typename T, int BS = 256>
+// PK = 1: the row holds ln P (valid: <= 0 and no NaN; -inf is the exact zero of the linear form); the counting passes compare ln P with a bound in ln space.
+template <typename T, int BS = 256, int PK = 0>
 struct GlobalRow {
-	static constexpr int THREADS = BS, MASK_BYTES = 16;
+	static constexpr int THREADS = BS, MASK_BYTES = 16, KIND = PK;
 	const T* p;
 	int64_t ng, self;
 	int phase = 0;
@@ -57,7 +83,11 @@ struct GlobalRow {
 	__device__ __forceinline__ GlobalRow(const T* row, int64_t ng_, int64_t self_) : p(row), ng(ng_), self(self_), bad(0) {
 		for (int64_t j = threadIdx.x; j < ng; j += BS) {
 			const double v = (double)p[j];
-			if (!(v >= 0.0 && v <= 1.0)) bad += 1.0;
+			if constexpr (PK) {
+				if (!(v <= 0.0)) bad += 1.0;
+			} else {
+				if (!(v >= 0.0 && v <= 1.0)) bad += 1.0;
+			}
 		}
 	}
 	template <typename F>
@@ -73,20 +103,26 @@ struct GlobalRow {
 		return (int64_t)nrm_block_sum<BS / 64, true>(c, sm);
 	}
 	__device__ __forceinline__ double max_le(double x, double* sm) const {
-		double m = -1.0;
+		double m = PK ? -INFINITY : -1.0;  // (ln form: called only where an entry <= x exists)
 		each([&](double pj) {
 			if (pj <= x) m = fmax(m, pj);
 		});
 		return bn_block_max<BS / 64>(m, sm);
 	}
 	__device__ __forceinline__ void histogram(double top, unsigned* hist, int nb) const {
-		const double scale = (double)nb / top;
-		each([&](double pj) {
-			if (pj <= top) {
-				int b = (int)(pj * scale);
-				atomicAdd(&hist[b < nb ? b : nb - 1], 1u);
-			}
-		});
+		if constexpr (PK) {
+			each([&](double pj) {
+				if (pj <= top) atomicAdd(&hist[bn_ln_bin(pj, top, nb)], 1u);
+			});
+		} else {
+			const double scale = (double)nb / top;
+			each([&](double pj) {
+				if (pj <= top) {
+					int b = (int)(pj * scale);
+					atomicAdd(&hist[b < nb ? b : nb - 1], 1u);
+				}
+			});
+		}
 	}
 	__device__ __forceinline__ double emit(unsigned char* o, double tau, unsigned char*) const {
 		double cnt = 0;
@@ -98,9 +134,9 @@ struct GlobalRow {
 		return cnt;
 	}
 };
-template <typename T, int ITEMS, int BS = 256>
+template <typename T, int ITEMS, int BS = 256, int PK = 0>
 struct RegRow {
-	static constexpr int THREADS = BS, NW = BS / 64;
+	static constexpr int THREADS = BS, NW = BS / 64, KIND = PK;
 	static constexpr int MASK_BYTES = ITEMS * BS <= 32768 ? ITEMS * BS : 16;  // the row's mask staged in LDS for 16-byte stores (wide rows: direct)
 	T v[ITEMS];  // entries outside the row or on the diagonal hold 2 (> any p-value: never counted, never a maximum <= x)
 	int64_t ng;
@@ -144,8 +180,12 @@ struct RegRow {
 #pragma unroll
 		for (int q = 0; q < ITEMS; q++) {
 			const int64_t j = elem(q);
-			if (!(v[q] >= (T)0 && v[q] <= (T)1)) bad += 1.0;
-			if (j >= ng || j == self) v[q] = (T)2;
+			if constexpr (PK) {
+				if (!(v[q] <= (T)0)) bad += 1.0;
+			} else {
+				if (!(v[q] >= (T)0 && v[q] <= (T)1)) bad += 1.0;
+			}
+			if (j >= ng || j == self) v[q] = (T)2;  // (> any ln P as well)
 		}
 	}
 	template <typename F>
@@ -156,7 +196,7 @@ struct RegRow {
 	}
 	// counting in the matrix dtype with wave ballots: one compare per item and no fp64 arithmetic in the ~15 passes of a row
 	__device__ __forceinline__ int64_t count_le(double x, double* sm) {
-		const T xf = bn_floor_to<T>(fmin(x, 1.5));
+		const T xf = PK ? bn_floor_ln<T>(fmin(x, 1.5)) : bn_floor_to<T>(fmin(x, 1.5));
 		int c = 0;
 #pragma unroll
 		for (int q = 0; q < ITEMS; q++) c += __popcll(__ballot(v[q] <= xf));
@@ -172,8 +212,8 @@ struct RegRow {
 		return (int64_t)t;
 	}
 	__device__ __forceinline__ double max_le(double x, double* sm) {
-		const T xf = bn_floor_to<T>(fmin(x, 1.5));
-		T m = (T)-1;
+		const T xf = PK ? bn_floor_ln<T>(fmin(x, 1.5)) : bn_floor_to<T>(fmin(x, 1.5));
+		T m = PK ? (T)-INFINITY : (T)-1;  // (ln form: called only where an entry <= x exists; -inf itself may be the answer)
 #pragma unroll
 		for (int q = 0; q < ITEMS; q++) m = (v[q] <= xf && v[q] > m) ? v[q] : m;
 #pragma unroll
@@ -192,7 +232,7 @@ struct RegRow {
 	}
 	__device__ __forceinline__ double emit(unsigned char* o, double tau, unsigned char* stage) const {
 		double cnt = 0;
-		const T tf = bn_floor_to<T>(fmin(tau, 1.5));
+		const T tf = PK ? bn_floor_ln<T>(tau) : bn_floor_to<T>(fmin(tau, 1.5));  // (ln form: tau <= 0, or NaN when nothing is selected -- no entry is <= NaN)
 		const bool staged = MASK_BYTES == ITEMS * BS && ((uintptr_t)o % 16 == 0);  // the mask leaves in 16-byte pieces from LDS
 		const bool vec = ((uintptr_t)o % VEC == 0);
 #pragma unroll
@@ -234,14 +274,20 @@ struct RegRow {
 	}
 	// the entries <= top into a histogram of nb bins over [0, top) in LDS (hist zeroed by the caller)
 	__device__ __forceinline__ void histogram(double top, unsigned* hist, int nb) const {
-		const T tf = bn_floor_to<T>(fmin(top, 1.5));
-		const double scale = (double)nb / top;
+		const T tf = PK ? bn_floor_ln<T>(top) : bn_floor_to<T>(fmin(top, 1.5));
+		if constexpr (PK) {
 #pragma unroll
-		for (int q = 0; q < ITEMS; q++)
-			if (v[q] <= tf) {
-				int b = (int)((double)v[q] * scale);
-				atomicAdd(&hist[b < nb ? b : nb - 1], 1u);
-			}
+			for (int q = 0; q < ITEMS; q++)
+				if (v[q] <= tf) atomicAdd(&hist[bn_ln_bin((double)v[q], top, nb)], 1u);
+		} else {
+			const double scale = (double)nb / top;
+#pragma unroll
+			for (int q = 0; q < ITEMS; q++)
+				if (v[q] <= tf) {
+					int b = (int)((double)v[q] * scale);
+					atomicAdd(&hist[b < nb ? b : nb - 1], 1u);
+				}
+		}
 	}
 };
 
@@ -255,13 +301,20 @@ __global__ void __launch_bounds__(Row::THREADS) k_binnet_rows(const T* __restric
 	const double m = (double)(ng - 1);
 	const T qc = (T)qcut;  // the reference compares in the matrix dtype (numpy weak-scalar promotion)
 	const double slack = sizeof(T) == 4 ? 1e-5 : 1e-12;
+	// The ln form (Row::KIND = 1): row i's edges are { lnp <= tau* }, tau* = max{ v : v + (ln m - ln c_v) <= ln qcut }, the test in fp64 for both dtypes.  The
+	// counting passes run on ln P: k <- #{lnp <= ln qcut + (ln k - ln m) + lslack}.  Every quantity of the exact test near the bound is below 800 in magnitude, so its
+	// rounding stays under 1e-12 and an additive slack of 1e-9 covers it for fp32 rows too (their entries convert to fp64 exactly).
+	constexpr int PK = Row::KIND;
+	constexpr double lslack = 1e-9;
+	double lqc = 0.0, lm = 0.0;
+	if constexpr (PK) lqc = log(qcut), lm = log(m);
 	if (dbg && threadIdx.x == 0) dbg[i * 6] = wall_clock64();
 	Row r(prow, ng, row0 + i);  // row i of this block is gene row0 + i: its diagonal entry sits in that column
 	// validity (binnet.py:151-152): finite and inside [0,1]
 	if (nrm_block_sum<NW, true>(r.bad, sm) > 0 && threadIdx.x == 0) atomicAdd(&flags[0], 1);
 	if (dbg && threadIdx.x == 0) dbg[i * 6 + 1] = wall_clock64();
 	double x = 2.0;       // every entry is a candidate
-	double tau = -1.0;    // tau*: nothing selected yet
+	double tau = PK ? (double)NAN : -1.0;  // tau*: nothing selected yet (ln form: -inf is a value, NaN is below nothing)
 	bool none = false;
 	{
 		// Where to start.  The loop below finds the largest k with k = g(k), g(k) = #{p <= top k / m}, top = qcut (1 + slack), by
@@ -272,7 +325,7 @@ __global__ void __launch_bounds__(Row::THREADS) k_binnet_rows(const T* __restric
 		__shared__ unsigned s_hist[BN_BINS];
 		__shared__ unsigned s_scan[NW];
 		constexpr int PB = (BN_BINS + Row::THREADS - 1) / Row::THREADS;  // bins per thread
-		const double top = qcut * (1.0 + slack);
+		const double top = PK ? lqc + lslack : qcut * (1.0 + slack);  // (ln form: the bins are those of exp(lnp - top), the same fractions of top)
 		for (int b = threadIdx.x; b < BN_BINS; b += Row::THREADS) s_hist[b] = 0u;
 		__syncthreads();
 		r.histogram(top, s_hist, BN_BINS);
@@ -311,6 +364,8 @@ __global__ void __launch_bounds__(Row::THREADS) k_binnet_rows(const T* __restric
 		best = bn_block_max<NW>(best, sm);
 		if (best < 0.0)
 			none = true;  // not a single entry below top
+		else if constexpr (PK)
+			x = fmin(2.0, top + log((best + 1.0) / (double)BN_BINS) + 1e-9);
 		else
 			x = fmin(2.0, top * (best + 1.0) / (double)BN_BINS * (1.0 + 1e-9));
 	}
@@ -318,7 +373,7 @@ __global__ void __launch_bounds__(Row::THREADS) k_binnet_rows(const T* __restric
 		// skip everything that fails the test even with slack: largest fixed point of k <- #{p <= min(x, qcut (1+slack) k/m)}
 		int64_t k = r.count_le(x, sm);
 		while (k > 0) {
-			const double bound = fmin(x, qcut * (1.0 + slack) * (double)k / m);
+			const double bound = PK ? fmin(x, lqc + lslack + (log((double)k) - lm)) : fmin(x, qcut * (1.0 + slack) * (double)k / m);
 			const int64_t c = r.count_le(bound, sm);
 			if (c == k) {
 				x = bound;
@@ -328,6 +383,15 @@ __global__ void __launch_bounds__(Row::THREADS) k_binnet_rows(const T* __restric
 		}
 		if (k == 0) break;
 		const double v = r.max_le(x, sm);
+		if constexpr (PK) {
+			const int64_t c = r.count_le(v, sm);
+			if (v + (lm - log((double)c)) <= lqc) {  // (v = -inf passes for every c)
+				tau = v;
+				break;
+			}
+			x = nextafter(v, -INFINITY);  // v fails (so it is finite): continue strictly below it
+			continue;
+		}
 		if (v < 0.0) break;
 		const int64_t c = r.count_le(v, sm);
 		// the reference's arithmetic, in the matrix dtype: w = c/m, q = v/w, clipped to [0,1]  (binnet.py:121-125)
@@ -359,7 +423,7 @@ extern "C" int nrm_binnet_debug_buffer(void* d_stamps) {
 	return NRM_OK;
 }
 
-template <typename T>
+template <typename T, int PK>
 static void bn_launch(const T* p, int64_t rows, int64_t ng, int64_t ldp, double qcut, unsigned char* out, int64_t ldo, unsigned long long* total,
 					  int32_t* flags, int64_t row0, hipStream_t st) {
 	dim3 grid((unsigned)rows);
@@ -369,26 +433,27 @@ static void bn_launch(const T* p, int64_t rows, int64_t ng, int64_t ldp, double 
 	// (workgroup sizes measured on MI355X, tools/time_binnet.py: 256 threads up to 20 480 entries, 512 above -- smaller workgroups have
 	// cheaper barriers per counting pass and more rows in flight per CU)
 	if (ng <= 8 * 256)
-		BN_GO(RegRow<T, 8>);
+		BN_GO(RegRow<T, 8, 256, PK>);
 	else if (ng <= 32 * 256)
-		BN_GO(RegRow<T, 32>);
+		BN_GO(RegRow<T, 32, 256, PK>);
 	else if (ng <= 80 * 256 && sizeof(T) == 4)
-		BN_GO(RegRow<T, 80>);
+		BN_GO(RegRow<T, 80, 256, PK>);
 	else if (ng <= 40 * 512)
-		BN_GO(RegRow<T, 40, 512>);
+		BN_GO(RegRow<T, 40, 512, PK>);
 	else if (ng <= 60 * 512)
-		BN_GO(RegRow<T, 60, 512>);
+		BN_GO(RegRow<T, 60, 512, PK>);
 	else if (ng <= 60 * 1024)
-		BN_GO(RegRow<T, 60, 1024>);
+		BN_GO(RegRow<T, 60, 1024, PK>);
 	else if (ng <= 96 * 1024 && sizeof(T) == 4)
-		BN_GO(RegRow<T, 96, 1024>);
+		BN_GO(RegRow<T, 96, 1024, PK>);
 	else
-		BN_GO(GlobalRow<T>);
+		BN_GO(GlobalRow<T, 256, PK>);
 #undef BN_GO
 }
 
-extern "C" int nrm_binnet_rows(const void* d_p, int p_dtype, int64_t rows, int64_t ng, int64_t ldp, int64_t row0, double qcut,
-							   unsigned char* d_out, int64_t ldo, unsigned long long* d_total, int32_t* d_flags, void* stream) {
+extern "C" int nrm_binnet_rows_pk(const void* d_p, int p_dtype, int64_t rows, int64_t ng, int64_t ldp, int64_t row0, double qcut,
+								  unsigned char* d_out, int64_t ldo, unsigned long long* d_total, int32_t* d_flags, int p_kind, void* stream) {
+	NRM_REQUIRE(p_kind == 0 || p_kind == 1, "nrm_binnet: p_kind is 0 (P) or 1 (ln P)");
 	NRM_REQUIRE(p_dtype == NRM_F32 || p_dtype == NRM_F64, "nrm_binnet: bad dtype");
 	NRM_REQUIRE(ng > 1 && ldp >= ng && ldo >= ng, "Wrong shape of net or namet.");
 	NRM_REQUIRE(rows >= 0 && row0 >= 0 && row0 + rows <= ng, "nrm_binnet_rows: rows [row0, row0 + rows) outside the matrix");
@@ -397,11 +462,26 @@ extern "C" int nrm_binnet_rows(const void* d_p, int p_dtype, int64_t rows, int64
 	hipStream_t st = (hipStream_t)stream;
 	NRM_HIP(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), st));
 	if (rows == 0) return NRM_OK;
-	if (p_dtype == NRM_F64)
-		bn_launch<double>((const double*)d_p, rows, ng, ldp, qcut, d_out, ldo, d_total, d_flags, row0, st);
+	if (p_kind) {
+		if (p_dtype == NRM_F64)
+			bn_launch<double, 1>((const double*)d_p, rows, ng, ldp, qcut, d_out, ldo, d_total, d_flags, row0, st);
+		else
+			bn_launch<float, 1>((const float*)d_p, rows, ng, ldp, qcut, d_out, ldo, d_total, d_flags, row0, st);
+	} else if (p_dtype == NRM_F64)
+		bn_launch<double, 0>((const double*)d_p, rows, ng, ldp, qcut, d_out, ldo, d_total, d_flags, row0, st);
 	else
-		bn_launch<float>((const float*)d_p, rows, ng, ldp, qcut, d_out, ldo, d_total, d_flags, row0, st);
+		bn_launch<float, 0>((const float*)d_p, rows, ng, ldp, qcut, d_out, ldo, d_total, d_flags, row0, st);
 	return nrm_check_launch("k_binnet_rows");
+}
+
+extern "C" int nrm_binnet_rows(const void* d_p, int p_dtype, int64_t rows, int64_t ng, int64_t ldp, int64_t row0, double qcut,
+							   unsigned char* d_out, int64_t ldo, unsigned long long* d_total, int32_t* d_flags, void* stream) {
+	return nrm_binnet_rows_pk(d_p, p_dtype, rows, ng, ldp, row0, qcut, d_out, ldo, d_total, d_flags, 0, stream);
+}
+
+extern "C" int nrm_binnet_pk(const void* d_p, int p_dtype, int64_t ng, int64_t ldp, double qcut, unsigned char* d_out, int64_t ldo,
+							 unsigned long long* d_total, int32_t* d_flags, int p_kind, void* stream) {
+	return nrm_binnet_rows_pk(d_p, p_dtype, ng, ng, ldp, 0, qcut, d_out, ldo, d_total, d_flags, p_kind, stream);
 }
 
 extern "C" int nrm_binnet(const void* d_p, int p_dtype, int64_t ng, int64_t ldp, double qcut, unsigned char* d_out, int64_t ldo,

@@ -10,7 +10,7 @@
 #include "nrm_normvar_step.h"
 
 // ---- binnet (binnet.py:134-173) ------------------------------------------------------------------------------------------------------------
-extern "C" int nrm_binnet_host(const void* h_p, int p_dtype, int64_t ng, double qcut, unsigned char* h_net, int64_t* total) {
+extern "C" int nrm_binnet_host_pk(const void* h_p, int p_dtype, int64_t ng, double qcut, unsigned char* h_net, int64_t* total, int p_kind) {
 	std::lock_guard<std::mutex> serial(nrm_host_entry_mutex());
 	NRM_TRY(nrm_bind_device());
 	NRM_REQUIRE(h_p && h_net && total && ng > 0 && (p_dtype == NRM_F32 || p_dtype == NRM_F64), "nrm_binnet_host: bad arguments");
@@ -21,17 +21,24 @@ extern "C" int nrm_binnet_host(const void* h_p, int p_dtype, int64_t ng, double 
 	NRM_TRY(dn.alloc((size_t)ng * ng));
 	NRM_TRY(tot.alloc_zero(8, st));
 	NRM_TRY(flags.alloc_zero(16, st));
-	NRM_TRY(nrm_binnet(dp.p, p_dtype, ng, ng, qcut, dn.as<unsigned char>(), ng, tot.as<unsigned long long>(), flags.as<int32_t>(), st));
+	NRM_TRY(nrm_binnet_pk(dp.p, p_dtype, ng, ng, qcut, dn.as<unsigned char>(), ng, tot.as<unsigned long long>(), flags.as<int32_t>(), p_kind, st));
 	int32_t hf[4];
 	NRM_TRY(nrm_read_flags(flags.p, st, hf));
 	if (hf[0]) {
-		nrm_set_error("P-values must be finite and within [0, 1] (binnet.py:151-152): %d rows are not", hf[0]);
+		if (p_kind)
+			nrm_set_error("ln P-values must be <= 0 and no NaN: %d rows hold entries that are not", hf[0]);
+		else
+			nrm_set_error("P-values must be finite and within [0, 1] (binnet.py:151-152): %d rows are not", hf[0]);
 		return NRM_E_NUMERIC;
 	}
 	unsigned long long t = 0;
 	NRM_HIP(hipMemcpy(&t, tot.p, 8, hipMemcpyDeviceToHost));
 	*total = (int64_t)t;
 	return copy_out(h_net, dn.p, (size_t)ng * ng);
+}
+
+extern "C" int nrm_binnet_host(const void* h_p, int p_dtype, int64_t ng, double qcut, unsigned char* h_net, int64_t* total) {
+	return nrm_binnet_host_pk(h_p, p_dtype, ng, qcut, h_net, total, 0);
 }
 
 // ---- normvar (norm.py:166-289): the expression side, whole problem ------------------------------------------------------------------------------

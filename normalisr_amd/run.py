@@ -231,13 +231,13 @@ def _call_lcpm(m, ka):
 
 def _call_binnet(m, ka):
 	from .binnet import binnet
-	return (binnet(m['pv_in'], ka['qcut']).astype('u1', copy=False), )
+	return (binnet(m['pv_in'], ka['qcut'], logp=bool(ka.get('logp'))).astype('u1', copy=False), )
 
 
 def _call_bh(m, ka):
-	"""Benjamini-Hochberg q-values over ALL entries of the matrix (what de's pv_out holds), in its shape; on the device (nrm_bh_host)."""
+	"""Benjamini-Hochberg q-values over ALL entries of the matrix (what de's pv_out holds), in its shape; on the device (nrm_bh_host_pk).  --logp: ln P in, ln q out."""
 	from .binnet import bh
-	return (bh(m['pv_in'], on_device=True), )
+	return (bh(m['pv_in'], on_device=True, logp=bool(ka.get('logp'))), )
 
 
 # name -> inputs (matrix arguments), options (argument key -> (keyword, converter)), call, outputs (argument key ->
@@ -254,8 +254,8 @@ COMMANDS = {
 				 outputs=dict(pv_out=(0, None, fmt_float), dot_out=(1, None, fmt_float), var_out=(2, None, fmt_float))),
 	'normvar': dict(inputs=('lcpm_in', 'cov_in', 'weights_in', 'scale_in'), options=dict(nth=('nth', int), bs=('bs', int)), call=_call_normvar,
 					outputs=dict(exp_out=(0, None, fmt_float), cov_out=(1, None, fmt_float))),
-	'binnet': dict(inputs=('pv_in', ), options=dict(qcut=('qcut', float)), call=_call_binnet, outputs=dict(net_out=(0, None, fmt_int))),
-	'bh': dict(inputs=('pv_in', ), options={}, call=_call_bh, outputs=dict(q_out=(0, None, fmt_float))),
+	'binnet': dict(inputs=('pv_in', ), options=dict(qcut=('qcut', float), logp=('logp', bool)), call=_call_binnet, outputs=dict(net_out=(0, None, fmt_int))),
+	'bh': dict(inputs=('pv_in', ), options=dict(logp=('logp', bool)), call=_call_bh, outputs=dict(q_out=(0, None, fmt_float))),
 	# the reference passes var=None to its writer when --var_out is given (lowmem stays True, run.py:175,188-189) and fails: asking for the file asks for lowmem=False
 	'lcpm': dict(inputs=('reads_in', 'cov_in'), options=dict(nth=('nth', _nth), rseed=('seed', int), var_out=('lowmem', lambda name: False)), call=_call_lcpm,
 				 outputs=dict(lcpm_out=(0, None, fmt_float), cov_out=(2, None, fmt_float), scale_out=(1, None, fmt_float), var_out=(3, None, fmt_float))),
